@@ -7,12 +7,24 @@ CrossEntropyLoss(randint targets) -> backward} -> AdamW.step, on ONE synthetic b
 (benchmark.py:462-467), B = 128 per GPU, drop_path 0.1 (scripts/benchmark.sh:9), random-init weights.
 
     python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full                      # + every figure beyond the headline (below)
+    python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR          # + the last timed step's outputs as DIR/*.npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
 One process per GPU; N > 1 shards images over ranks (weak scaling, 128 images per GPU) with gradients
 all-reduced by RCCL (lemevit_amd.dist.FlatGradSync: chunks of the flat fp32 gradient buffer, overlapped with backward;
 --ddp selects torch DDP instead).  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps (`value`, `ms_per_step`) and prints the line.  Everything else runs only with
+--full: the host issue probe (`host_issue_ms_per_step`), the kernel-timing roofline (`roofline`), the forward pass timed after the
+train region (`forward_*`), the committed HBM-traffic figures (`hbm_step_*`) and the CPU baseline (`cpu_baseline`); the --no-* switches
+below still turn single parts of --full off.
+
+--dump-outputs DIR writes, right after the timed region, what its last step handed the caller: `logits` (+ `loss` and, for the
+updated model, a fixed seeded sample of the parameters, their gradients and the floating-point buffers in train mode), float32,
+at most ~40 MB.  The inputs (weights, images, targets, DropPath draws) depend only on the arguments, so two builds can be compared
+output for output.
 
 `roofline` is measured live for the dominant kernel of the timed region: the library's launch-timing probe brackets every GEMM (forward-form tile / register-stationary /
 whole-width kernels, the transpose-read dX kernel, the split-K weight-gradient kernel and its slab reduce), every attention launch and every persistent stage / stem launch with
@@ -70,7 +82,49 @@ def parse():
     ap.add_argument("--graph", type=int, default=-1, help="(-1 = auto: eager for train, graph replay for infer)  1 = capture the step into a hipGraph (lemevit_amd.graph.GraphedStep) and replay it; default 0 = "
                     "eager launches, which are faster here: the weight-gradient GEMMs overlap the dX chain on a side stream, and the "
                     "runtime serialises the branches of a captured graph (38.0 vs 39.6 ms per step)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="also measure everything beyond the headline figure: host issue time, the kernel-timing roofline, the forward-pass "
+                    "probe (train mode), the committed HBM-traffic figures and the CPU baseline (the --no-* switches above turn single parts off)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write what the last timed step computed (logits, loss, sampled parameters / gradients / buffers) "
+                    "to DIR/<name>.npy as float32")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+DUMP_SAMPLE = 1 << 22          # elements per sampled array of --dump-outputs (16 MB as float32)
+
+
+def _dump_sample(tensors, n_max: int = DUMP_SAMPLE):
+    """The tensors flattened into one fp32 vector (in the given order); above n_max elements, a fixed sample of it: n_max sorted indices drawn
+    with a CPU generator seeded 0, so the positions depend only on the total size."""
+    flat = torch.cat([t.detach().reshape(-1).float() for t in tensors])
+    if flat.numel() <= n_max:
+        return flat
+    g = torch.Generator().manual_seed(0)
+    idx = torch.randint(flat.numel(), (n_max,), generator=g).sort().values
+    return flat[idx.to(flat.device)]
+
+
+def dump_outputs(out_dir: str, last: dict, model, train: bool):
+    """--dump-outputs: what the timed path handed its caller in its last step -- the logits, and in train mode the loss and the model the step
+    updated (parameters, their gradients and the BatchNorm buffers, each sampled by _dump_sample) -- as float32 DIR/<name>.npy."""
+    import numpy as np
+    arrays = {"logits": last["logits"]}
+    if train:
+        arrays["loss"] = last["loss"].reshape(1)
+        params = [p for _, p in model.named_parameters()]
+        arrays["params_sample"] = _dump_sample(params)
+        grads = [p.grad for p in params if p.grad is not None]
+        if grads:
+            arrays["grads_sample"] = _dump_sample(grads)
+        bufs = [b for _, b in model.named_buffers() if b.dtype.is_floating_point]
+        if bufs:
+            arrays["buffers_sample"] = _dump_sample(bufs, 1 << 20)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().float().cpu().numpy())
+    print(f"bench.py: wrote {', '.join(sorted(arrays))} to {out_dir}", file=sys.stderr)
 
 
 def cpu_baseline(model_name: str, img: int, mode: str):
@@ -294,19 +348,22 @@ def main():
             opt = torch.optim.AdamW([dict(params=decay, weight_decay=0.05), dict(params=no_decay, weight_decay=0.0)], lr=1e-4, eps=1e-8, fused=True,
                                     capturable=bool(args.graph))
         net = wrap_ddp(model, local) if use_ddp else model
+        last = {}           # the last step's logits / loss (detached: no autograd graph outlives its step) for --dump-outputs
 
         def step():
             opt.zero_grad(set_to_none=True)
             with torch.autocast("cuda", torch.bfloat16):
                 out = net(x)
                 target = torch.empty((args.batch,), device=dev, dtype=torch.long).random_(1000)
-                loss_fn(out, target).backward()
+                loss = loss_fn(out, target)
+                loss.backward()
+            last["logits"], last["loss"] = out.detach(), loss.detach()
             if gsync is not None:
                 gsync.finish()
             opt.step()
     else:
         from lemevit_amd.graph import split_forward
-        infer_outs = []
+        infer_outs, last = [], {}
         if args.infer_parts <= 0:
             args.infer_parts, parts_table = pick_infer_parts(model, x, bool(args.graph) and world == 1)
 
@@ -353,10 +410,14 @@ def main():
     sync()
     dt = time.perf_counter() - t0
     check_handoffs("timed region")
+    if args.dump_outputs and rank == 0:
+        if not train:
+            last["logits"] = torch.cat(infer_outs)          # (split_forward: one output per sub-batch)
+        dump_outputs(args.dump_outputs, last, model, train)
     # host time to ENQUEUE one step, measured on an EMPTY launch queue (issuing K steps back to back only measures the queue's
     # back-pressure: the host blocks once the device is a queue depth behind) -- median of 5 single steps, each preceded by a sync
     issue = []
-    for _ in range(0 if args.no_issue_probe else 5):
+    for _ in range(5 if args.full and not args.no_issue_probe else 0):
         sync()
         ti = time.perf_counter()
         step()
@@ -364,7 +425,7 @@ def main():
     sync()
     t_issued = sorted(issue)[len(issue) // 2] * args.steps if issue else None
     kernel_timing_note, probe, probe_alone = None, None, None
-    if not args.no_kernel_timing:
+    if args.full and not args.no_kernel_timing:
         # Same schedule as the timed region: 3 eager steps right AFTER it with the library's launch-timing probe on (lmv_debug_launch_timing: HIP events around
         # every forward-form Linear entry point and every persistent stage / stem launch, recorded on the stream the launch is issued on -- the native block
         # schedule's launches included).  Events cannot be timed inside a captured graph, and in eager mode they cost ~1 ms per step, which must not leak
@@ -411,7 +472,7 @@ def main():
     # model on the same batch right after the train region (eval mode, no_grad, bf16 autocast, hipGraph replay as in --mode infer) and
     # reports it as extra keys of the same JSON line.  The timed train region above is not touched by it.
     fwd_dt, fwd_iters, fwd_note, fwd_probe = None, 0, None, None
-    if train and not args.no_forward_probe:
+    if args.full and train and not args.no_forward_probe:
         model.eval()
 
         from lemevit_amd.graph import split_forward
@@ -558,18 +619,19 @@ def main():
             "config": {"workload": f"{args.model} {args.img}x{args.img} bf16-autocast {'train step (fwd+bwd+AdamW)' if train else 'forward'}, "
                                    f"batch {args.batch}/GPU, drop_path 0.1, random-init weights", "global_batch": args.batch * world,
                        "parallelism": f"dp{world}", "launch": graph_note},
-            "host_issue_ms_per_step": None if t_issued is None else round(1e3 * t_issued / args.steps, 3),
             "model_tflops": None if gflop is None else round(value * gflop * mult / 1e3, 2),
             "model_frac_of_bf16_peak": None if gflop is None else round(value * gflop * mult / 1e3 / (PEAK_BF16_TFLOPS * world), 4),
-            "roofline": roof,
             # the sticky error word of the persistent stage kernels, READ here (pinned host memory; every region above ended in a synchronise + check that raises on a non-zero
             # word, so a line is only printed with 0 -- but it is the counter, not a literal)
             "stage_errors": _ops.stage_error_count(reset=False, sync=False), "ranks_seen": ranks_seen, "device_uuids": device_uuids,
             "grad_wire": None if not (train and world > 1) else ("torch DDP bf16 hook" if (args.ddp or args.force_ddp) else ("bf16" if args.grad_wire == "bf16" else "fp32")),
         }
+        if args.full:
+            line["host_issue_ms_per_step"] = None if t_issued is None else round(1e3 * t_issued / args.steps, 3)
+            line["roofline"] = roof
         # HBM traffic of the WHOLE step over its wall time: bytes per step from the newest committed PMC pass over this command (tools/pmc_step_traffic.sh: FETCH_SIZE x 2 +
         # WRITE_SIZE summed over every kernel of a step), quoted only while it was measured on these kernel sources
-        if world == 1 and args.model == "lemevit_base" and args.img == 224 and args.batch == 128:
+        if args.full and world == 1 and args.model == "lemevit_base" and args.img == 224 and args.batch == 128:
             import glob
             cands_s = sorted(glob.glob(os.path.join(ROOT, "profiles", "r[0-9][0-9]_train_hbm_traffic.json" if train else "r[0-9][0-9]_infer_hbm_traffic.json")))
             d_ = _matching(cands_s[-1]) if cands_s else None
@@ -589,7 +651,7 @@ def main():
                                     f"{fwd_iters} iterations, fused inference schedule")
         if parts_table is not None:
             line["forward_schedule_probe_ms"] = {f"{k}_sub_batches": v for k, v in parts_table.items()}      # --infer-parts 0: chosen before the timed region
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(args.model, args.img, args.mode)
         os.write(json_fd, (json.dumps(line) + "\n").encode())
     if dist.is_initialized():

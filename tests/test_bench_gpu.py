@@ -21,7 +21,8 @@ def _json_line(out: str) -> dict:
 
 
 def test_bench_single_gpu_line_has_forward_keys():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2", "--no-cpu-baseline"], cwd=ROOT,
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2", "--full", "--no-cpu-baseline"],
+                       cwd=ROOT,
                        capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     line = _json_line(r.stdout)
@@ -33,6 +34,29 @@ def test_bench_single_gpu_line_has_forward_keys():
     assert line["forward_ms"] < line["ms_per_step"]
     assert "hipGraph replay" in line["forward_note"]          # (whole batch or --infer-parts graph branches: whichever the schedule probe measured faster -- forward_schedule_probe_ms)
     assert line["stage_errors"] == 0 and "forward_schedule_probe_ms" in line
+
+
+def test_bench_plain_line_and_dump_outputs(tmp_path):
+    """A plain run carries the headline keys only (everything else is --full), --steps sets the timed steps, and --dump-outputs writes the last timed step's
+    logits / loss / sampled parameters, gradients and buffers as finite float32 arrays, 64 MB at most."""
+    import numpy as np
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--dump-outputs", str(out)], cwd=ROOT,
+                       capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = _json_line(r.stdout)
+    assert line["steps"] == 2 and line["ms_per_step"] > 0 and line["value"] > 0 and line["unit"] == "images/sec" and line["higher_is_better"] is True
+    assert line["dtype"] == "bf16" and line["metric"] == "images/sec LeMeViT-Base 224^2 bf16 fwd+bwd"
+    assert abs(line["value"] - 128 * 1e3 / line["ms_per_step"]) < 1e-2 * line["value"]
+    for k in ("roofline", "host_issue_ms_per_step", "forward_ms", "cpu_baseline", "hbm_step_mb"):
+        assert k not in line, k
+    names = sorted(p.name for p in out.iterdir())
+    assert names == ["buffers_sample.npy", "grads_sample.npy", "logits.npy", "loss.npy", "params_sample.npy"], names
+    assert sum(p.stat().st_size for p in out.iterdir()) <= 64 << 20
+    arrays = {n: np.load(out / n) for n in names}
+    assert arrays["logits.npy"].shape == (128, 1000) and arrays["loss.npy"].shape == (1,)
+    for n, a in arrays.items():
+        assert a.dtype == np.float32 and np.isfinite(a).all(), n
 
 
 @pytest.mark.skipif(torch.cuda.device_count() < 2, reason="needs two MI355X: bench.py --gpus 2 over RCCL, one device per rank (BASELINE config 4)")

@@ -3,9 +3,9 @@
 # (weight gradients in line), the per-kernel table of a forward pass, HBM traffic per step, the PMC traffic of the kernel bench.py's roofline names (the weight-gradient GEMM) and of the
 # forward Linear launches, per-kernel PMC tables, stage times / timelines, the CPU-baseline protocol and the stock-eager column.
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT; O=gpurun_out/r06; mkdir -p $O
-python bench.py > $O/bench_train.json 2> $O/bench_train.err
-python bench.py --mode infer --no-cpu-baseline > $O/bench_infer.json 2>> $O/bench_train.err
-python bench.py --mode infer --no-cpu-baseline --infer-parts 1 > $O/bench_infer_one_stream.json 2>> $O/bench_train.err
+python bench.py --full > $O/bench_train.json 2> $O/bench_train.err
+python bench.py --full --mode infer --no-cpu-baseline > $O/bench_infer.json 2>> $O/bench_train.err
+python bench.py --full --mode infer --no-cpu-baseline --infer-parts 1 > $O/bench_infer_one_stream.json 2>> $O/bench_train.err
 rocprofv3 --kernel-trace --stats -d $O/kt -o trace -- python bench.py --no-cpu-baseline --no-kernel-timing --no-issue-probe --no-forward-probe > $O/bench_under_rocprof.log 2>&1
 DB=$(find $O/kt -name "*.db" | head -1)
 python tools/rocpd_stats.py $DB > $O/train_kernel_stats_full.csv
@@ -25,8 +25,8 @@ bash tools/pmc_kernels.sh $O/pmc_per_kernel_infer.csv --mode infer --infer-parts
 python tools/sstage_timeline.py 5 > $O/sstage_timeline.txt 2>&1
 (python tools/dstage_timeline.py 1 128 4 192; python tools/dstage_timeline.py 1 128 4 96) > $O/dstage_timeline.txt 2>&1
 (python tools/stage_times.py lemevit_base 128; python tools/stage_times.py lemevit_tiny 256) > $O/stage_times.txt 2>&1
-python bench.py --model lemevit_tiny --batch 256 --mode infer --no-cpu-baseline > $O/bench_tiny224_b256_infer.json 2>/dev/null
-python bench.py --img 384 --batch 64 --mode infer --no-cpu-baseline > $O/bench_base384_b64_infer.json 2>/dev/null
+python bench.py --full --model lemevit_tiny --batch 256 --mode infer --no-cpu-baseline > $O/bench_tiny224_b256_infer.json 2>/dev/null
+python bench.py --full --img 384 --batch 64 --mode infer --no-cpu-baseline > $O/bench_base384_b64_infer.json 2>/dev/null
 python tools/stock_eager.py > $O/stock_eager.txt 2>&1
 bash tools/infer_sequence.sh $O/infer_sequence_graph.csv 1 > /dev/null 2>&1
 bash tools/infer_sequence.sh $O/infer_sequence_eager.csv 0 > /dev/null 2>&1
