@@ -44,11 +44,9 @@ enum {
 
 int lmv_abi_version(void);
 const char* lmv_last_error(void);
-/* Tuning switches (A/B runs, parity tests of alternative code paths): these two change / read a switch at run time.  Five of them are also read from the environment, ONCE, when
- * the library is loaded -- never on a launch path: LMV_GEMM_W8, LMV_GEMM_RS, LMV_GEMM_WN, LMV_DW_TARGET_BLOCKS, LMV_STAGE_TICKET_SKEW.  Keys: "gemm_bk", "gemm_bk32_tiles", "dw_bk",
- * "dw_target_blocks", "gemm_no_dma", "gemm_w8", "gemm_cumap", "gemm_nst", "gemm_nst_dw", "gemm_rs", "dwconv_v", "mlp_tm", "attn_pv16",
- * "attn_fuse_dq", "attn_fused_bwd", "attn_pair", "ln_bwd_blocks", "ln_bwd_minrows", "stage_ticket_skew" (test switch) (lemevit_amd/csrc/common.h: LmvConfig).
- * Process-wide, not synchronised: set them between launches. */
+/* Run-time switches of alternative code paths (the GPU parity tests run both sides): these two change / read one.  Keys: "gemm_rs", "gemm_wn",
+ * "mlp_rw96", "mlp_tm", "stage_ticket_skew" (test switch) (lemevit_amd/csrc/common.h: LmvConfig); an unknown key is LMV_ERR_SHAPE.  None is read from the
+ * environment.  Process-wide, not synchronised: set them between launches. */
 int lmv_config_set(const char* key, int value);
 int lmv_config_get(const char* key, int* value);
 

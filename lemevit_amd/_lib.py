@@ -206,7 +206,7 @@ lib = _load()
 
 
 def config_set(key: str, value: int) -> None:
-    """lmv_config_set: change a tuning switch of the library at run time (tests, tools/ sweeps)."""
+    """lmv_config_set: change a run-time switch of the library (csrc/common.h: LmvConfig; the GPU tests run both sides)."""
     if lib.lmv_config_set(key.encode(), int(value)):
         raise RuntimeError(f"lmv_config_set: {lib.lmv_last_error().decode(errors='replace')}")
 

@@ -100,25 +100,14 @@ def aux_streams(dev, n: int) -> list:
     return lst[:n]
 
 
-# The split-K reductions of a block's weight gradients are deferred (ops.DwBatch) and summed by ONE launch at the end of the block's
-# backward pass instead of one ~7 us launch behind every GEMM (LMV_DW_BATCH=0: the per-GEMM path, for A/B runs).
-_DW_BATCH = False      # (a module attribute for A/B runs, no environment switch) measured: 0.5 ms SLOWER per step (the slabs of a whole block leave the MALL before they are read back)
-_batches: Dict[tuple, "ops.DwBatch"] = {}
-
-
+# (Measured and dropped: deferring the split-K reductions of a block's weight gradients into one launch at the end of its backward
+#  pass -- 0.5 ms slower per step, the slabs of a whole block leave the MALL before they are read back.)
 def _dw(probs, N: int, K: int) -> None:
     dev = probs[0].a.device
     raw = _fork(dev)
-    batch = None
-    if _DW_BATCH:
-        batch = _batches.get((dev.index, raw))
-        if batch is None:
-            batch = _batches[(dev.index, raw)] = ops.DwBatch()
-    ops.linear_dw(probs, N, K, stream=raw, batch=batch)          # launched on the side stream by handle: no current-stream switch
+    ops.linear_dw(probs, N, K, stream=raw)          # launched on the side stream by handle: no current-stream switch
     if raw is not None:
         _inflight.append((dev.index, probs))
-    elif batch is not None:
-        batch.keep.append(probs)
 
 
 def _dwconv_w(dy: Tensor, x: Tensor, dweight: Tensor, dbias: Tensor, H: int, W: int) -> None:
@@ -132,7 +121,7 @@ def _dwconv_w(dy: Tensor, x: Tensor, dweight: Tensor, dbias: Tensor, H: int, W: 
 # last weight-gradient GEMM and the dwconv weight gradient were requested moments before: the main stream idled ~10-20 us per block
 # there) but at the end of the NEXT block's backward pass, when they have long finished; whatever they read stays referenced until
 # then.  The last blocks of a backward pass are joined by an autograd final callback, i.e. before .backward() returns to the caller.
-_DEFER = int(os.environ.get("LMV_JOIN_DEFER", "1"))       # blocks a join may trail behind (0: join at the end of every block)
+_DEFER = 1                                                 # blocks a join may trail behind
 _pending: "Dict[int, collections.deque]" = {}              # device index -> deque of (event recorded on that device's side stream, references)
 _event_pool: "Dict[int, List[torch.cuda.Event]]" = {}      # device index -> reusable events
 _cb_token = None                                           # identity of the backward pass whose final callback is queued (see defer_join)
@@ -173,58 +162,28 @@ def defer_join(dev_index: int, refs) -> None:
     ev.record(side)
     _pending.setdefault(dev_index, collections.deque()).append((ev, refs))
     keep = _DEFER
-    if keep > 0:
-        # one final callback per backward pass: the marker is the pass's graph task (a new pass -- also one that follows a pass which
-        # raised before its callbacks ran -- has a different one), not a process-wide flag
+    # one final callback per backward pass: the marker is the pass's graph task (a new pass -- also one that follows a pass which
+    # raised before its callbacks ran -- has a different one), not a process-wide flag
+    try:
+        token = torch._C._current_graph_task_id()
+    except Exception:
+        token = -1
+    if token == -1:                   # not inside a backward pass (a schedule driven by hand): join now
+        keep = 0
+    elif _cb_token != token:
         try:
-            token = torch._C._current_graph_task_id()
-        except Exception:
-            token = -1
-        if token == -1:                   # not inside a backward pass (a schedule driven by hand): join now
+            torch.autograd.Variable._execution_engine.queue_callback(_final_join)
+            _cb_token = token
+        except RuntimeError:
             keep = 0
-        elif _cb_token != token:
-            try:
-                torch.autograd.Variable._execution_engine.queue_callback(_final_join)
-                _cb_token = token
-            except RuntimeError:
-                keep = 0
     _wait_pending(keep, dev_index)
 
 
 def _join() -> None:
-    for (di, raw), batch in _batches.items():
-        if batch.segs:
-            batch.flush(stream=raw)                 # one reduce launch for every weight gradient of the block, behind its GEMMs
     if _inflight:
         refs = list(_inflight)
         _inflight.clear()
         defer_join(refs[-1][0], refs)
-
-
-# The meta-token self-attention of an S block (16 tokens: B * h tiny workgroups, ~13 us of mostly launch ramp and tail per
-# direction) is independent of the image-token attention next to it: it is launched on a SECOND side stream by raw handle and
-# joined before the projection that consumes both, so it runs inside the image-token kernel's shadow.
-_META_SIDE = False      # (a module attribute for A/B runs, no environment switch) measured: 0.3 ms SLOWER per step (4 stream-wait API calls per block for ~20 us of hidden kernels); kept as an A/B switch
-_meta_streams: Dict[int, tuple] = {}
-
-
-def _meta_fork(dev) -> Optional[int]:
-    if not _META_SIDE or torch.cuda.is_current_stream_capturing():
-        return None
-    ent = _meta_streams.get(dev.index)
-    if ent is None:
-        side = torch.cuda.Stream(device=dev)
-        ent = _meta_streams[dev.index] = (side, side.cuda_stream, torch.cuda.Event(), torch.cuda.Event())
-    side, raw, fork, _ = ent
-    fork.record()
-    side.wait_event(fork)
-    return raw
-
-
-def _meta_join(dev) -> None:
-    side, _, _, join = _meta_streams[dev.index]
-    join.record(side)
-    torch.cuda.current_stream(dev).wait_event(join)
 
 
 def _empty(rows_like: Tensor, cols: int) -> Tensor:
@@ -238,11 +197,6 @@ def _rps(t: Tensor) -> int:
 # ------------------------------------------------------------------------------------------------
 # MLP half of a block:  t <- t + ds * fc2(GELU(fc1(LN2(t))))   for every stream t in `ts`
 # ------------------------------------------------------------------------------------------------
-def _lib_config(key: str) -> int:
-    from . import _lib
-    return _lib.config_get(key)
-
-
 def _mlp_fwd(P: Dict[str, Tensor], ts: Sequence[Tensor], ds: Sequence[Optional[Tensor]], save: bool, fc1_fold=None, pre_ln=None):
     C = ts[0].shape[-1]
     Hd = P["mlp.0.weight"].shape[0]
@@ -289,16 +243,9 @@ def _attn_S_fwd(P, ts, ds, save, want_ln2=False):
     xn, st = ops.layernorm_fwd_multi(ts, P["norm1.weight"], P["norm1.bias"], BLOCK_LN_EPS, want_stats=save)
     qkv = [_empty(t, 3 * C) for t in ts]
     ops.linear_fwd([Prob(a, P["attn.qkv.weight"], o, bias=P["attn.qkv.bias"]) for a, o in zip(xn, qkv)], 3 * C, C)
-    if len(qkv) == 2 and not _META_SIDE:
+    if len(qkv) == 2:
         ao, lse = ops.attn_fwd_pair(qkv, C, ops.SDPA_SCALE, want_lse=save)      # image tokens + meta tokens: one launch
-    elif len(qkv) == 2:
-        raw = _meta_fork(qkv[1].device)
-        ao_c, lse_c = ops.attn_fwd((qkv[1], 0), (qkv[1], C), (qkv[1], 2 * C), C, ops.SDPA_SCALE, want_lse=save, stream=raw)
-        ao_x, lse_x = ops.attn_fwd((qkv[0], 0), (qkv[0], C), (qkv[0], 2 * C), C, ops.SDPA_SCALE, want_lse=save)
-        if raw is not None:
-            _meta_join(qkv[1].device)
-        ao, lse = (ao_x, ao_c), (lse_x, lse_c)
-    else:
+    else:                                                                        # "Sx": image tokens only
         ao, lse = zip(*[ops.attn_fwd((q, 0), (q, C), (q, 2 * C), C, ops.SDPA_SCALE, want_lse=save) for q in qkv])
     out = [torch.empty_like(t) for t in ts]
     probs = [Prob(a, P["attn.proj.weight"], o, bias=P["attn.proj.bias"], res=t, row_scale=s, rps=_rps(t)) for a, o, t, s in zip(ao, out, ts, ds)]
@@ -322,15 +269,11 @@ def _attn_S_bwd(P, G, saved, douts, ds, g=None):
     dao = [torch.empty_like(t) for t in ts]
     ops.linear_dx([Prob(gi, P["attn.proj.weight"], o) for gi, o in zip(g, dao)], C, C)
     dqkv = [torch.empty_like(q) for q in qkv]
-    if len(qkv) == 2 and not _META_SIDE:
+    if len(qkv) == 2:
         ops.attn_bwd_pair(qkv, ao, lse, dao, dqkv, C, ops.SDPA_SCALE)
-    else:
-        raw = _meta_fork(qkv[1].device) if len(qkv) == 2 else None
-        for i in reversed(range(len(qkv))):              # meta tokens first (side stream), image tokens on the main stream
-            q, a, l, da, dq = qkv[i], ao[i], lse[i], dao[i], dqkv[i]
-            ops.attn_bwd((q, 0), (q, C), (q, 2 * C), a, l, da, (dq, 0), (dq, C), (dq, 2 * C), C, ops.SDPA_SCALE, stream=raw if i == 1 else None)
-        if raw is not None:
-            _meta_join(qkv[1].device)
+    else:                                                # "Sx": image tokens only
+        q, dq = qkv[0], dqkv[0]
+        ops.attn_bwd((q, 0), (q, C), (q, 2 * C), ao[0], lse[0], dao[0], (dq, 0), (dq, C), (dq, 2 * C), C, ops.SDPA_SCALE)
     _dw([Prob(dq, xi, G["attn.qkv.weight"], bias_grad=G["attn.qkv.bias"]) for dq, xi in zip(dqkv, xn)], 3 * C, C)
     dxn = [torch.empty_like(t) for t in ts]
     ops.linear_dx([Prob(dq, P["attn.qkv.weight"], o) for dq, o in zip(dqkv, dxn)], 3 * C, C)
@@ -477,7 +420,7 @@ def block_forward(kind: str, x: Tensor, c: Tensor, H: int, W: int, P: Dict[str, 
         # (the one-kernel / LayerNorm-folded MLP half of the fused inference schedule has no use for norm2's output: csrc/block.hip::res_ln_ok)
         Hd = P["mlp.0.weight"].shape[0]
         rows = xp.numel() // xp.shape[-1] + c.numel() // c.shape[-1]
-        split = xp.shape[-1] == 384 and Hd == 1536 and 16384 <= rows <= 65536 and bool(_lib_config("mlp_split384"))      # csrc/block.hip::mlp_fwd: LayerNorm + rsgemm fc1 + wngemm fc2
+        split = xp.shape[-1] == 384 and Hd == 1536 and 16384 <= rows <= 65536      # csrc/block.hip::mlp_fwd: LayerNorm + rsgemm fc1 + wngemm fc2
         folded = fc1_fold is not None and not save and not split
         r = _attn_S_fwd(P, [xp, c], [masks[0], masks[2]], save, want_ln2=not folded)
         (x2, c1), sa, ln2 = r if not folded else (r[0], r[1], None)

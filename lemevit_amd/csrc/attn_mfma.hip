@@ -1482,10 +1482,9 @@ size_t lmv_attn_mfma_bwd_acc_bytes(const AttnArgs& a) {
 int lmv_attn_mfma_fwd(const AttnArgs& a, hipStream_t st) {
   const int per = qt_per_block_for(a), nqt = (a.Lq + 15) / 16;
   dim3 grid((nqt + per - 1) / per, a.H, a.B), block(256);
-  const int pv16 = lmv_config().attn_pv16;      // A/B testing
-  if (a.Lk == 196 && pv16) hipLaunchKernelGGL((mfma_fwd_kernel<14, 196, true>), grid, block, 0, st, a, per);      // stage-3 self-attention at 224^2
-  else if (a.Lk == 16 && pv16) hipLaunchKernelGGL((mfma_fwd_kernel<2, 16, true>), grid, block, 0, st, a, per);    // 16 meta-token keys (DCA x direction, meta self-attention)
-  else if (a.Lk == 49 && pv16) hipLaunchKernelGGL((mfma_fwd_kernel<4, 49, true>), grid, block, 0, st, a, per);    // stage 4
+  if (a.Lk == 196) hipLaunchKernelGGL((mfma_fwd_kernel<14, 196, true>), grid, block, 0, st, a, per);      // stage-3 self-attention at 224^2
+  else if (a.Lk == 16) hipLaunchKernelGGL((mfma_fwd_kernel<2, 16, true>), grid, block, 0, st, a, per);    // 16 meta-token keys (DCA x direction, meta self-attention)
+  else if (a.Lk == 49) hipLaunchKernelGGL((mfma_fwd_kernel<4, 49, true>), grid, block, 0, st, a, per);    // stage 4
   else
   switch (nkt_for(a.Lk)) {
     case 2: hipLaunchKernelGGL((mfma_fwd_kernel<2>), grid, block, 0, st, a, per); break;
@@ -1500,15 +1499,12 @@ int lmv_attn_mfma_fwd(const AttnArgs& a, hipStream_t st) {
 // acc: lmv_attn_mfma_bwd_acc_bytes() of fp32 scratch (only touched when the query range is split)
 int lmv_attn_mfma_bwd(const AttnArgs& a, float* delta, float* acc, hipStream_t st) {
   const int per = qt_per_block_for(a), nqt = (a.Lq + 15) / 16, nkt = nkt_for(a.Lk);
-  const bool fuse_dq = lmv_config().attn_fuse_dq != 0, fused_bwd = lmv_config().attn_fused_bwd != 0;      // A/B testing
-  if (fused_bwd && nkt >= 4 && a.Lq > 16 && a.Lq <= nkt * 16) {
-    // one workgroup per (b, h): dQ, dK and dV from ONE pass over the scores
+  if (nkt >= 4 && a.Lq > 16 && a.Lq <= nkt * 16) {
+    // one workgroup per (b, h): dQ, dK and dV from ONE pass over the scores; 196 / 49 keys: round 5's body (dQ by query tile, one
+    // barrier per block, mfma_bwd_fused_body2), other lengths: round 2's
     dim3 grid(1, a.H, a.B), block(256);
-    const bool v2 = lmv_config().attn_fused_bwd == 2;          // round 5: dQ by query tile, one barrier per block (mfma_bwd_fused_body2)
-    if (a.Lk == 196 && v2) hipLaunchKernelGGL((mfma_bwd_fused_kernel<14, 196, 2>), grid, block, 0, st, a);
-    else if (a.Lk == 49 && v2) hipLaunchKernelGGL((mfma_bwd_fused_kernel<4, 49, 2>), grid, block, 0, st, a);
-    else if (a.Lk == 196) hipLaunchKernelGGL((mfma_bwd_fused_kernel<14, 196>), grid, block, 0, st, a);
-    else if (a.Lk == 49) hipLaunchKernelGGL((mfma_bwd_fused_kernel<4, 49>), grid, block, 0, st, a);
+    if (a.Lk == 196) hipLaunchKernelGGL((mfma_bwd_fused_kernel<14, 196, 2>), grid, block, 0, st, a);
+    else if (a.Lk == 49) hipLaunchKernelGGL((mfma_bwd_fused_kernel<4, 49, 2>), grid, block, 0, st, a);
     else if (nkt == 4) hipLaunchKernelGGL((mfma_bwd_fused_kernel<4>), grid, block, 0, st, a);
     else if (nkt == 8) hipLaunchKernelGGL((mfma_bwd_fused_kernel<8>), grid, block, 0, st, a);
     else hipLaunchKernelGGL((mfma_bwd_fused_kernel<14>), grid, block, 0, st, a);
@@ -1520,12 +1516,9 @@ int lmv_attn_mfma_bwd(const AttnArgs& a, float* delta, float* acc, hipStream_t s
     int nk, pr, lds;
     if (int rc = long_geometry(a, &nk, &pr, &lds)) return rc;
     hipLaunchKernelGGL(mfma_bwd_dq_long_kernel, dim3((nqt + pr - 1) / pr, a.H, a.B), dim3(256), lds, st, a, delta, pr, nk);
-  } else if (nkt == 2 && fuse_dq) {
-    // <= 32 keys: dQ comes out of the dK / dV kernel below
-  } else {
+  } else if (nkt != 2) {          // (<= 32 keys: dQ comes out of the dK / dV kernel below)
     dim3 grid((nqt + per - 1) / per, a.H, a.B), block(256);
     switch (nkt) {
-      case 2: hipLaunchKernelGGL((mfma_bwd_dq_kernel<2>), grid, block, 0, st, a, delta, per); break;
       case 4: hipLaunchKernelGGL((mfma_bwd_dq_kernel<4>), grid, block, 0, st, a, delta, per); break;
       case 8: hipLaunchKernelGGL((mfma_bwd_dq_kernel<8>), grid, block, 0, st, a, delta, per); break;
       default: hipLaunchKernelGGL((mfma_bwd_dq_kernel<14>), grid, block, 0, st, a, delta, per); break;
@@ -1538,20 +1531,20 @@ int lmv_attn_mfma_bwd(const AttnArgs& a, float* delta, float* acc, hipStream_t s
   float* acc_k = acc; float* acc_v = acc + acc_elems;
   if (nsplit > 1) {
 #define DKV(N, K) hipLaunchKernelGGL((mfma_bwd_dkv_kernel<N, K, true>), grid, block, 0, st, a, delta, acc_k, acc_v, qpb)
-    if (nkt == 2 && fuse_dq && a.Lk == 16) hipLaunchKernelGGL((mfma_bwd_dkv_kernel<2, 1, true, true, 16>), grid, block, 0, st, a, delta, acc_k, acc_v, qpb);
-    else if (nkt == 2 && fuse_dq) hipLaunchKernelGGL((mfma_bwd_dkv_kernel<2, 1, true, true>), grid, block, 0, st, a, delta, acc_k, acc_v, qpb);
+    if (nkt == 2 && a.Lk == 16) hipLaunchKernelGGL((mfma_bwd_dkv_kernel<2, 1, true, true, 16>), grid, block, 0, st, a, delta, acc_k, acc_v, qpb);
+    else if (nkt == 2) hipLaunchKernelGGL((mfma_bwd_dkv_kernel<2, 1, true, true>), grid, block, 0, st, a, delta, acc_k, acc_v, qpb);
     else
-    switch (nkt) { case 2: DKV(2, 1); break; case 4: DKV(4, 2); break; case 8: DKV(8, 4); break; default: DKV(14, 4); break; }
+    switch (nkt) { case 4: DKV(4, 2); break; case 8: DKV(8, 4); break; default: DKV(14, 4); break; }
 #undef DKV
     const unsigned n = 2u * (unsigned)a.B * a.H * a.Lk * (D / 4);
     hipLaunchKernelGGL(scatter_sum_kernel, dim3((n + 255) / 256), dim3(256), 0, st, (const float*)acc_k, (const float*)acc_v, (bf16_t*)a.dk, (bf16_t*)a.dv,
                        a.k_bs, a.k_rs, a.v_bs, a.v_rs, a.B, a.H, a.Lk, nkt * 16, nsplit);
   } else {
 #define DKV(N, K) hipLaunchKernelGGL((mfma_bwd_dkv_kernel<N, K, false>), grid, block, 0, st, a, delta, acc_k, acc_v, qpb)
-    if (nkt == 2 && fuse_dq && a.Lk == 16) hipLaunchKernelGGL((mfma_bwd_dkv_kernel<2, 1, false, true, 16>), grid, block, 0, st, a, delta, acc_k, acc_v, qpb);
-    else if (nkt == 2 && fuse_dq) hipLaunchKernelGGL((mfma_bwd_dkv_kernel<2, 1, false, true>), grid, block, 0, st, a, delta, acc_k, acc_v, qpb);
+    if (nkt == 2 && a.Lk == 16) hipLaunchKernelGGL((mfma_bwd_dkv_kernel<2, 1, false, true, 16>), grid, block, 0, st, a, delta, acc_k, acc_v, qpb);
+    else if (nkt == 2) hipLaunchKernelGGL((mfma_bwd_dkv_kernel<2, 1, false, true>), grid, block, 0, st, a, delta, acc_k, acc_v, qpb);
     else
-    switch (nkt) { case 2: DKV(2, 1); break; case 4: DKV(4, 2); break; case 8: DKV(8, 4); break; default: DKV(14, 4); break; }
+    switch (nkt) { case 4: DKV(4, 2); break; case 8: DKV(8, 4); break; default: DKV(14, 4); break; }
 #undef DKV
   }
   LMV_CHECK_LAUNCH("attn_mfma_bwd");
@@ -1561,8 +1554,7 @@ int lmv_attn_mfma_bwd(const AttnArgs& a, float* delta, float* acc, hipStream_t s
 // Pair launches (two independent problems with the same B and H): merged when problem 1 is the stage-3 / stage-4 image-token
 // self-attention (196 / 49 keys, Lq == Lk) and problem 2 the 16 x 16 meta-token one; 1 = merged, 0 = not applicable
 int lmv_attn_mfma_fwd_pair(const AttnArgs& a1, const AttnArgs& a2, hipStream_t st) {
-  const int on = lmv_config().attn_pair;      // A/B testing
-  if (!on || a1.B != a2.B || a1.H != a2.H || a2.Lk != 16 || a2.Lq != 16 || a1.Lq != a1.Lk || (a1.Lk != 196 && a1.Lk != 49)) return 0;
+  if (a1.B != a2.B || a1.H != a2.H || a2.Lk != 16 || a2.Lq != 16 || a1.Lq != a1.Lk || (a1.Lk != 196 && a1.Lk != 49)) return 0;
   const int per1 = qt_per_block_for(a1), nqt1 = (a1.Lq + 15) / 16, nblk1 = (nqt1 + per1 - 1) / per1;
   dim3 grid((nblk1 + 1) * a1.H * a1.B), block(256);
   if (a1.Lk == 196) hipLaunchKernelGGL((mfma_fwd_pair_kernel<14, 196, 2, 16>), grid, block, 0, st, a1, a2, per1, 1, nblk1);
@@ -1571,13 +1563,9 @@ int lmv_attn_mfma_fwd_pair(const AttnArgs& a1, const AttnArgs& a2, hipStream_t s
 }
 
 int lmv_attn_mfma_bwd_pair(const AttnArgs& a1, const AttnArgs& a2, hipStream_t st) {
-  const int on = lmv_config().attn_pair;
-  if (!on || a1.B != a2.B || a1.H != a2.H || a2.Lk != 16 || a2.Lq != 16 || a1.Lq != a1.Lk || (a1.Lk != 196 && a1.Lk != 49)) return 0;
+  if (a1.B != a2.B || a1.H != a2.H || a2.Lk != 16 || a2.Lq != 16 || a1.Lq != a1.Lk || (a1.Lk != 196 && a1.Lk != 49)) return 0;
   dim3 grid(2 * a1.H * a1.B), block(256);
-  const bool v2 = lmv_config().attn_fused_bwd == 2;
-  if (a1.Lk == 196 && v2) hipLaunchKernelGGL((mfma_bwd_pair_kernel<14, 196, 2>), grid, block, 0, st, a1, a2);
-  else if (v2) hipLaunchKernelGGL((mfma_bwd_pair_kernel<4, 49, 2>), grid, block, 0, st, a1, a2);
-  else if (a1.Lk == 196) hipLaunchKernelGGL((mfma_bwd_pair_kernel<14, 196>), grid, block, 0, st, a1, a2);
-  else hipLaunchKernelGGL((mfma_bwd_pair_kernel<4, 49>), grid, block, 0, st, a1, a2);
+  if (a1.Lk == 196) hipLaunchKernelGGL((mfma_bwd_pair_kernel<14, 196, 2>), grid, block, 0, st, a1, a2);
+  else hipLaunchKernelGGL((mfma_bwd_pair_kernel<4, 49, 2>), grid, block, 0, st, a1, a2);
   return 1;
 }

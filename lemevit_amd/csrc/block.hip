@@ -124,11 +124,11 @@ inline bool fold_qkv(const Dims& D) { return D.C >= 192; }
 
 // split384 (below): the C = 384 MLP half of the fused inference schedule as three launches instead of the one-kernel form (measured faster
 // at 27136 rows -- 9.51 -> 9.38 ms -- and at 37888 rows -- Base 384^2 forward 16.5 -> 16.1 ms)
-inline bool mlp_split384(const Dims& D) { const int64_t r = D.rows[0] + D.rows[1]; return lmv_config().mlp_split384 && D.C == 384 && D.Hd == 1536 && r >= 16384 && r <= 65536; }
+inline bool mlp_split384(const Dims& D) { const int64_t r = D.rows[0] + D.rows[1]; return D.C == 384 && D.Hd == 1536 && r >= 16384 && r <= 65536; }
 // "S" blocks: the attention projection (residual epilogue) and the norm2 that follows it in ONE launch (lmv_linear_res_ln_fwd), wherever
 // the MLP half reads norm2's output from memory (training; the split inference form) -- lemevit_amd/ops.py::res_ln_fused is the same rule
 inline bool res_ln_ok(const lmv_block_desc* d, const Dims& D, int save) {
-  if (D.kind != LMV_BLOCK_S || D.dtype != LMV_BF16 || !lmv_config().res_ln_fused || D.rows[0] + D.rows[1] < 16384 || D.rows[0] + D.rows[1] > 32768) return false;
+  if (D.kind != LMV_BLOCK_S || D.dtype != LMV_BF16 || D.rows[0] + D.rows[1] < 16384 || D.rows[0] + D.rows[1] > 32768) return false;
   if (!lmv_linear_res_ln_fwd_supported(D.C, D.C, D.dtype)) return false;
   return !(fused_on(d, D, save) && !mlp_split384(D));
 }
@@ -327,7 +327,7 @@ int ln_bwd(Side& sd, const lmv_ln_segment* seg, int nseg, const float* gamma, fl
 // enough rows to fill the chip): dy never reaches memory.  p[i].a = dY, p[i].w = the transposed weight; seg as for ln_bwd.
 inline bool dx_ln_fused_ok(const Dims& D, const void* wt, int N) {
   const int64_t rows = D.rows[0] + D.rows[1];      // one round of 128-row panels on the chip (csrc/wngemm.hip::lmv_wn_eligible)
-  return wt && D.dtype == LMV_BF16 && lmv_config().dx_ln_fused && lmv_linear_dx_ln_bwd_supported(D.C, N, D.dtype) && rows >= 16384 && rows <= 32768;
+  return wt && D.dtype == LMV_BF16 && lmv_linear_dx_ln_bwd_supported(D.C, N, D.dtype) && rows >= 16384 && rows <= 32768;
 }
 int dx_ln_bwd(Side& sd, const lmv_linear_problem* p, const lmv_ln_segment* seg, int nseg, int N, const float* gamma, float* dgamma, float* dbeta, const Dims& D,
               void* ws, size_t ws_bytes) {
@@ -476,7 +476,7 @@ int block_fwd_body(const lmv_block_desc* d, const Dims& D, const Fwd& f, const v
   const bool fq = fused_on(d, D, save) && fold_qkv(D);      // norm1 folded into the projections: no LayerNorm launch, no normalised copy
   // C = 96 blocks: norm1 runs INSIDE the projection launches (csrc/rswgemm.hip: exact LayerNorm on the register-resident rows, the
   // normalised rows and their statistics written from there) -- lemevit_amd/ops.py::ln_exact_fused is the same rule
-  const bool ex = !fq && D.dtype == LMV_BF16 && lmv_config().ln_exact_fused && D.kind != LMV_BLOCK_S &&
+  const bool ex = !fq && D.dtype == LMV_BF16 && D.kind != LMV_BLOCK_S &&
                   lmv_ln_linear_exact_fwd_supported(cb ? 2 * D.C : 3 * D.C, D.C, D.dtype) && lmv_ln_linear_exact_fwd_supported(D.C, D.C, D.dtype);
   const void* src[2] = {f.xp, c};                           // token rows the projections read (fq / ex: raw; else LN1 output)
   if (!fq && !ex) {

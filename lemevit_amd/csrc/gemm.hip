@@ -93,10 +93,8 @@ __global__ __launch_bounds__(CF::NTHR, MINW) void gemm_kernel(const GemmArgs g) 
     // Inside an XCD the dispatcher deals workgroups round-robin over its 32 CUs (tools/native/hwid_probe.hip): the XCD-local
     // workgroups i, i + 32, i + 64, i + 96 share a CU.  Hand those four CONSECUTIVE tiles (same m-tile, neighbouring n-tiles) so
     // that their A rows can meet in the CU's vector L1 instead of each going to L2.
-    if (g.cumap) {
-      const int chunk = idx & ~127;
-      if (chunk + 128 <= len) idx = chunk + ((idx & 31) << 2) + ((idx >> 5) & 3);
-    }
+    const int chunk = idx & ~127;
+    if (chunk + 128 <= len) idx = chunk + ((idx & 31) << 2) + ((idx >> 5) & 3);
     bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
   }
   const bool second = g.nprob > 1 && !g.concat && bid >= g.p[1].tile_begin;      // workgroup-uniform
@@ -367,9 +365,8 @@ static int reduce_lanes(int64_t n4, int nslabs) {      // slab lanes: enough blo
 }
 
 enum Mode { MODE_FWD = 0, MODE_DX = 1, MODE_DW = 2 };
-enum Tile { TILE_128 = 0, TILE_128W8 = 3 };
 
-struct Plan { GemmArgs g; int total, splits, bk, tile, dma, nsplit[2]; size_t ws_bytes; };
+struct Plan { GemmArgs g; int total, splits, bk, dma, nsplit[2]; size_t ws_bytes; };
 
 int make_plan(const lmv_linear_problem* p, int nproblems, int N, int K, int act, int dtype, Mode mode, Plan* pl) {
   if (nproblems < 1 || nproblems > 2) LMV_FAIL(LMV_ERR_SHAPE, "linear: nproblems must be 1 or 2 (got %d)", nproblems);
@@ -406,7 +403,6 @@ int make_plan(const lmv_linear_problem* p, int nproblems, int N, int K, int act,
     if (P.Kred % 32) all32 = false;
   }
   const bool bf = dtype == LMV_BF16;
-  const LmvConfig& cf = lmv_config();      // A/B switches: read from the environment ONCE at library load (lmv_config_set changes them at run time)
   // bf16: 64-deep k-tiles unless the reduction is a short non-multiple of 64 (C = 96 layers); fp32: 32-deep
   int bk = (bf && (mode == MODE_DW || all64 || min_kred >= 512)) ? 64 : 32;
   // Occupancy beats k-tile depth whenever the launch has enough tiles to put 4 workgroups on every CU: half of a
@@ -414,25 +410,20 @@ int make_plan(const lmv_linear_problem* p, int nproblems, int N, int K, int act,
   // hide.  The 32-deep variant needs 32 KB of LDS and <= 128 registers (4 per CU) against 64 KB / 160 (2 per CU).
   int64_t tiles128 = 0;
   for (int i = 0; i < nproblems; ++i) tiles128 += (int64_t)((g.p[i].M + 127) / 128) * ((out_cols + 127) / 128);
-  if (bf && all32 && mode != MODE_DW && tiles128 >= cf.gemm_bk32_tiles) bk = 32;
-  // dW: 32-deep as well (3 workgroups per CU; tools/dw_sweep.py: best or within 5 % of best on every layer shape)
-  if (bf && all32 && mode == MODE_DW && cf.dw_bk == 32) bk = 32;
-  if (bf && cf.gemm_bk == 32 && all32) bk = 32;
-  if (bf && cf.gemm_bk == 64 && all64) bk = 64;
-  const bool no_dma = cf.gemm_no_dma != 0;
-  const bool dma = bf && !no_dma && (bk == 64 ? all64 : all32);
+  if (bf && all32 && mode != MODE_DW && tiles128 >= 512) bk = 32;
+  // dW: 32-deep as well (3 workgroups per CU; tools/history/dw_sweep.py: best or within 5 % of best on every layer shape)
+  if (bf && all32 && mode == MODE_DW) bk = 32;
+  const bool dma = bf && (bk == 64 ? all64 : all32);
   // Tile: 128 x 128 everywhere.  (256 x 128 / 256 x 256 tiles and the 128 x 384 "BigK" tile were measured slower on every layer shape of
   // the model in rounds 1 - 2 -- tile quantisation on 636 / 2544-tile launches, one workgroup per CU -- and left the library in round 3;
   // they live on the branch r02-gemm-experiments.)
-  int tile = TILE_128;
   // 64-deep k-tiles at FOUR waves per SIMD: the 128x128 tile on 8 waves of 32x64 (2 workgroups of 64 KB per CU).  Every operand
   // row is then a whole 128-byte line per k-tile -- the 32-deep loop asks L2 for half lines, and L2 (82 % busy on the stage-3 fc2
   // shape, tools/pmc_mem.sh) serves a half line in the same slot as a whole one -- at the price of 1.5x the LDS fragment reads.
   // Measured (tools/bench_kernels.py): forward 3-12 % faster on every K % 64 == 0 shape; dX faster only on the launches that
   // cannot fill 4 workgroups per CU (stage 4), slower elsewhere; dW much slower.
-  const bool w8 = bf && !no_dma && all64 && cf.gemm_w8 && cf.gemm_bk == 0 &&
-                  (mode == MODE_FWD || (mode == MODE_DX && (tiles128 < 512 || cf.gemm_w8 == 2)));
-  if (w8) { bk = 64; tile = TILE_128W8; }
+  const bool w8 = bf && all64 && (mode == MODE_FWD || (mode == MODE_DX && tiles128 < 512));
+  if (w8) bk = 64;      // (the only 64-deep LDS-DMA plans of the forward and dX: launch_mode)
   const int bm = 128, bn = 128;
   g.tiles_n = (out_cols + bn - 1) / bn;
   // dW of two problems that accumulate into the same dW / db (x and c rows through shared weights): one reduction
@@ -455,9 +446,7 @@ int make_plan(const lmv_linear_problem* p, int nproblems, int N, int K, int act,
   if (mode == MODE_DW) {
     // Split the token reduction so that ONE generation of workgroups fills the chip: slots = CUs x resident workgroups
     // (3 at 32-deep k-tiles, 2 at 64-deep); each split ends in a plain store of its partial tile.
-    const int target = cf.dw_target_blocks;
-    int per_xcd = target > 0 ? target / 8 : 32 * (bk == 32 && dma ? 3 : 2);
-    if (tile != TILE_128) per_xcd /= 2;      // 8-wave workgroups
+    const int per_xcd = 32 * (bk == 32 && dma ? 3 : 2);
     // The workgroups of one split run on one XCD (they share the token rows through its L2), so the split count is a
     // multiple of 8 -- every XCD gets the same number -- or, when one split's tiles already overfill an XCD, 4 / 2 / 1
     // with the tiles of a split divided over the XCDs that share it.
@@ -483,11 +472,10 @@ int make_plan(const lmv_linear_problem* p, int nproblems, int N, int K, int act,
     g.slab_stride = (int64_t)N * K + N;
     pl->ws_bytes = (size_t)slabs * g.slab_stride * sizeof(float);
   }
-  g.cumap = cf.gemm_cumap;
 #ifdef LMV_GEMM_TIMING
   { const char* e = getenv("LMV_GEMM_DBG_PTR"); g.dbg = e ? (unsigned long long*)strtoull(e, nullptr, 0) : nullptr; }
 #endif
-  pl->total = total; pl->splits = splits; pl->bk = bk; pl->tile = tile; pl->dma = dma;
+  pl->total = total; pl->splits = splits; pl->bk = bk; pl->dma = dma;
   return LMV_OK;
 }
 
@@ -517,22 +505,24 @@ int launch_mode(const Plan& pl, dim3 grid, bool bf, hipStream_t st) {
     if constexpr (ATR != BTR) { LMV_FAIL(LMV_ERR_SHAPE, "conv3x3s2: no data-gradient form"); }
     else {
       if (!bf || !pl.dma) LMV_FAIL(LMV_ERR_SHAPE, "conv3x3s2: bf16 with whole k-tiles only (rows and 9 Cin padded to a multiple of 64)");
-      if (pl.bk == 32) return launch_one<bf16_t, ATR, BTR, SPLITK, 32, true, C128, 3, 2, false, true>(g, grid, st);
-      if (pl.tile == TILE_128W8) return launch_one<bf16_t, ATR, BTR, SPLITK, 64, true, C128w8, 4, 2, false, true>(g, grid, st);
-      return launch_one<bf16_t, ATR, BTR, SPLITK, 64, true, C128, 1, 2, false, true>(g, grid, st);
+      // (KP and the row count are multiples of 64: the forward always plans the 8-wave kernel, the weight gradient 32-deep k-tiles)
+      if constexpr (SPLITK) return launch_one<bf16_t, ATR, BTR, SPLITK, 32, true, C128, 3, 2, false, true>(g, grid, st);
+      else return launch_one<bf16_t, ATR, BTR, SPLITK, 64, true, C128w8, 4, 2, false, true>(g, grid, st);
     }
   }
   if (!bf) return launch_one<float, ATR, BTR, SPLITK, 32, false, C128>(g, grid, st);
-  if (!pl.dma) return pl.bk == 64 ? launch_one<bf16_t, ATR, BTR, SPLITK, 64, false, C128>(g, grid, st)
-                                  : launch_one<bf16_t, ATR, BTR, SPLITK, 32, false, C128>(g, grid, st);
-  // 32-deep k-tiles: 32 KB of LDS and (capped by MINW) <= 128 / 168 registers: 4 (fwd, dX) or 3 (dW) workgroups per CU
-  if (pl.bk == 32) {
-    const LmvConfig& cf = lmv_config();
-    if ((SPLITK ? cf.gemm_nst_dw : cf.gemm_nst) == 3) return launch_one<bf16_t, ATR, BTR, SPLITK, 32, true, C128, 3, 3>(g, grid, st);      // 3-deep ring, 48 KB: 3 workgroups per CU (dW: 140 registers cap it at 3 anyway)
-    return launch_one<bf16_t, ATR, BTR, SPLITK, 32, true, C128, SPLITK ? 3 : 4>(g, grid, st);
+  // (make_plan: a dW plan is 32-deep exactly when every reduction is a multiple of 32, and then always LDS-DMA; a 64-deep LDS-DMA
+  //  forward or dX plan always takes the 8-wave tile)
+  if constexpr (SPLITK) {
+    if (!pl.dma) return launch_one<bf16_t, ATR, BTR, SPLITK, 64, false, C128>(g, grid, st);
+    return launch_one<bf16_t, ATR, BTR, SPLITK, 32, true, C128, 3, 3>(g, grid, st);      // 3-deep ring, 48 KB: 3 workgroups per CU (140 registers cap it at 3 anyway)
+  } else {
+    if (!pl.dma) return pl.bk == 64 ? launch_one<bf16_t, ATR, BTR, SPLITK, 64, false, C128>(g, grid, st)
+                                    : launch_one<bf16_t, ATR, BTR, SPLITK, 32, false, C128>(g, grid, st);
+    // 32-deep k-tiles: 32 KB of LDS and (capped by MINW) <= 128 registers: 4 workgroups per CU
+    if (pl.bk == 32) return launch_one<bf16_t, ATR, BTR, SPLITK, 32, true, C128, 4>(g, grid, st);
+    return launch_one<bf16_t, ATR, BTR, SPLITK, 64, true, C128w8, 4>(g, grid, st);
   }
-  if (pl.tile == TILE_128W8) return launch_one<bf16_t, ATR, BTR, SPLITK, 64, true, C128w8, 4>(g, grid, st);
-  return launch_one<bf16_t, ATR, BTR, SPLITK, 64, true, C128>(g, grid, st);
 }
 
 int launch(const lmv_linear_problem* p, int nproblems, int N, int K, int act, int dtype, void* stream, Mode mode, void* ws, size_t ws_bytes,
@@ -615,8 +605,7 @@ int launch_ln(const lmv_linear_problem* p, int nproblems, int N, int K, float ep
   else if (!pl.dma) rc = pl.bk == 64 ? launch_one<bf16_t, false, false, false, 64, false, C128, 1, 2, true>(g, grid, st)
                                      : launch_one<bf16_t, false, false, false, 32, false, C128, 1, 2, true>(g, grid, st);
   else if (pl.bk == 32) rc = launch_one<bf16_t, false, false, false, 32, true, C128, 3, 2, true>(g, grid, st);
-  else if (pl.tile == TILE_128W8) rc = launch_one<bf16_t, false, false, false, 64, true, C128w8, 4, 2, true>(g, grid, st);
-  else rc = launch_one<bf16_t, false, false, false, 64, true, C128, 1, 2, true>(g, grid, st);
+  else rc = launch_one<bf16_t, false, false, false, 64, true, C128w8, 4, 2, true>(g, grid, st);      // (a 64-deep LDS-DMA forward plan is always the 8-wave one)
   if (rc) return rc;
   LMV_CHECK_LAUNCH("ln_linear");
   return LMV_OK;

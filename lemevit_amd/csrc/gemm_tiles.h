@@ -44,7 +44,6 @@ struct GemmArgs {
   Problem p[2];
   int nprob, N, lda, ldb, ldc, act, tiles_n, kt_per_split;
   ConvGeo cv;
-  int cumap;                     // fwd / dX: CU-aware tile order (see gemm_kernel)
   int ntiles, nsplits, concat;   // dW: tiles of dW, k-splits, and whether problem 1's rows extend problem 0's reduction
   float ln_eps;           // LayerNorm-folded forward (lmv_ln_linear_fwd): eps of the folded LayerNorm
 #ifdef LMV_GEMM_TIMING

@@ -115,32 +115,14 @@ extern "C" int lmv_debug_launch_timing_read(float* ms, double* flops, double* by
 
 extern "C" int lmv_abi_version(void) { return LMV_ABI_VERSION; }
 
-// ---- A/B switches: lmv_config_set(key, value) at run time (tests, tools); five of them also from the environment, read once, here (round 6: the other ~25 LMV_* variables are gone) ------------------------------------------------------------------------------------
-#include <stdlib.h>
-#include <string.h>
+// ---- test switches (common.h: LmvConfig) ---------------------------------------------------------------------------------------
 namespace {
-int env_int(const char* name, int dflt) { const char* e = name ? getenv(name) : nullptr; return e && *e ? atoi(e) : dflt; }
-struct ConfigKey { const char* key; const char* env; int LmvConfig::*field; int dflt; };
+struct ConfigKey { const char* key; int LmvConfig::*field; };
 const ConfigKey kConfigKeys[] = {
-    {"gemm_bk", nullptr, &LmvConfig::gemm_bk, 0}, {"gemm_bk32_tiles", nullptr, &LmvConfig::gemm_bk32_tiles, 512},
-    {"dw_bk", nullptr, &LmvConfig::dw_bk, 32}, {"dw_target_blocks", "LMV_DW_TARGET_BLOCKS", &LmvConfig::dw_target_blocks, 0},
-    {"gemm_no_dma", nullptr, &LmvConfig::gemm_no_dma, 0}, {"gemm_w8", "LMV_GEMM_W8", &LmvConfig::gemm_w8, 1},
-    {"gemm_cumap", nullptr, &LmvConfig::gemm_cumap, 1}, {"gemm_nst", nullptr, &LmvConfig::gemm_nst, 2},
-    {"gemm_nst_dw", nullptr, &LmvConfig::gemm_nst_dw, 3}, {"gemm_rs", "LMV_GEMM_RS", &LmvConfig::gemm_rs, 1}, {"gemm_wn", "LMV_GEMM_WN", &LmvConfig::gemm_wn, 1},
-    {"dwconv_v", nullptr, &LmvConfig::dwconv_v, 0},
-    {"stage_ticket_skew", "LMV_STAGE_TICKET_SKEW", &LmvConfig::stage_ticket_skew, 0}, {"mlp_tm", nullptr, &LmvConfig::mlp_tm, 0}, {"mlp_rw96", nullptr, &LmvConfig::mlp_rw96, 1}, {"mlp_split384", nullptr, &LmvConfig::mlp_split384, 1}, {"dx_ln_fused", nullptr, &LmvConfig::dx_ln_fused, 1}, {"res_ln_fused", nullptr, &LmvConfig::res_ln_fused, 1}, {"ln_exact_fused", nullptr, &LmvConfig::ln_exact_fused, 1}, {"attn_pv16", nullptr, &LmvConfig::attn_pv16, 1},
-    {"attn_fuse_dq", nullptr, &LmvConfig::attn_fuse_dq, 1}, {"attn_fused_bwd", nullptr, &LmvConfig::attn_fused_bwd, 2},
-    {"attn_pair", nullptr, &LmvConfig::attn_pair, 1}, {"ln_bwd_blocks", nullptr, &LmvConfig::ln_bwd_blocks, 1024},
-    {"ln_bwd_minrows", nullptr, &LmvConfig::ln_bwd_minrows, 2},
+    {"gemm_rs", &LmvConfig::gemm_rs}, {"gemm_wn", &LmvConfig::gemm_wn}, {"mlp_rw96", &LmvConfig::mlp_rw96}, {"mlp_tm", &LmvConfig::mlp_tm},
+    {"stage_ticket_skew", &LmvConfig::stage_ticket_skew},
 };
-LmvConfig config_from_env() {
-  LmvConfig c{};
-  for (const ConfigKey& k : kConfigKeys) c.*(k.field) = env_int(k.env, k.dflt);
-  if (c.ln_bwd_blocks <= 0 || c.ln_bwd_blocks > 2048) c.ln_bwd_blocks = 512;
-  if (c.ln_bwd_minrows <= 0) c.ln_bwd_minrows = 2;
-  return c;
-}
-LmvConfig g_config = config_from_env();      // static initialisation = library load
+LmvConfig g_config;
 }  // namespace
 LmvConfig& lmv_config() { return g_config; }
 extern "C" int lmv_config_set(const char* key, int value) {

@@ -223,7 +223,7 @@ inline bool pick_geometry(int nch, int max_it, int* lpr_log2, int* nit) {
 
 inline int bwd_blocks(int64_t rows, int l2) {
   const int rpb = TPB >> l2;
-  const int cap = lmv_config().ln_bwd_blocks, minrows = lmv_config().ln_bwd_minrows;
+  constexpr int cap = 1024, minrows = 2;
   int64_t blocks = (rows + minrows * rpb - 1) / (minrows * rpb);           // >= 2 rows per row group
   return (int)(blocks > cap ? cap : (blocks < 1 ? 1 : blocks));
 }

@@ -746,10 +746,10 @@ def native_block_backward(kind: str, state, x: Tensor, c: Tensor, dx: Optional[T
     _fill_ptrs(d, kind, names, G, "g_")
     nbytes = _sized(lib.lmv_block_bwd_scratch_bytes, d, kind, x, c, H, W)
     side = side_stream_handle(x.device)
-    defer = side is not None and blocks_mod._DEFER > 0
-    # deferred join (blocks.defer_join): the side stream may still read this block's scratch while the next blocks run -> rotate buffers
+    defer = side is not None
+    # deferred join (blocks.defer_join, one block behind): the side stream may still read this block's scratch while the next block runs -> two buffers
     global _bwd_slot
-    _bwd_slot = (_bwd_slot + 1) % (blocks_mod._DEFER + 1) if defer else 0
+    _bwd_slot = 1 - _bwd_slot if defer else 0
     scratch = _persistent(("bwd", _bwd_slot), nbytes, x.device)
     dx0, dc0 = torch.empty_like(x), torch.empty_like(c)
     d.flags = 1 if defer else 0          # LMV_BLOCK_NO_JOIN
