@@ -671,7 +671,7 @@ int conv_geo(ConvGeo* cv, const void* x, int B, int H, int W, int Cin, int Cout,
   if (!x || !lmv_aligned16(x)) LMV_FAIL(LMV_ERR_SHAPE, "conv3x3s2: null / misaligned map");
   *cv = ConvGeo{};
   cv->on = 1; cv->H = H; cv->W = W; cv->Cin = Cin; cv->Ho = Ho; cv->Wo = Wo; cv->HoWo = Ho * Wo; cv->x = x;
-  auto magic = [](unsigned d) { return ((1ull << 40) + d - 1) / d; };
+  auto magic = [](unsigned d) { return ((1ull << LMV_CV_SHIFT) + d - 1) / d; };      // (cv_div: exact for every shape admitted above)
   cv->m_cin = magic((unsigned)Cin); cv->m_wo = magic((unsigned)Wo); cv->m_howo = magic((unsigned)(Ho * Wo));
   return LMV_OK;
 }

@@ -34,7 +34,9 @@ struct ReduceSegDev { const float* ws; float* out_w; float* out_b; int64_t strid
 // Implicit-GEMM form of Conv2d(Cin, Cout, 3, stride 2, padding 1) on an NHWC map (round 6; lmv_conv3x3s2_fwd / _dw): the "patch matrix" operand [B Ho Wo, KP] (column
 // (ky * 3 + kx) * Cin + ci, zeros behind 9 Cin) is never materialised -- the LDS-DMA loads of a k-tile take their 16-byte pieces straight from the map (per-lane source address:
 // the panel image in LDS is the one the plain GEMM builds), padding taps and the pad columns from a page of zeros.  Divisions by Cin / Wo / Ho Wo are multiplications by
-// ceil(2^40 / d) (exact for n d < 2^40: n < 2^22 rows, d < 2^13).
+// m = ceil(2^41 / d) and a shift by 41 (LMV_CV_SHIFT).  With e = m d - 2^41 < d, floor(n m / 2^41) = floor(n / d) while n e < 2^41: conv_geo admits n < 2^22 rows and
+// d = Ho Wo < 2^19, so n e < 2^41 (n m < 2^63).  A shift by 40 is not enough there: B = 15, 954 x 1152 map (Ho Wo = 274 752) put the last pixel in image 15.
+#define LMV_CV_SHIFT 41
 struct ConvGeo {
   int on, H, W, Cin, Ho, Wo, HoWo, pad_;
   unsigned long long m_cin, m_wo, m_howo;
@@ -138,7 +140,7 @@ __device__ __forceinline__ void panel_dma(unsigned char* panel, const bf16_t* __
 // outside the map and for k >= 9 Cin.  A 16-byte piece (8 channels) never straddles a tap because Cin % 8 == 0.  Not TR: the forward operand (rows = pixels, reduction over k);
 // TR: the weight-gradient operand (reduction over pixels, columns = k).
 __device__ __attribute__((aligned(128))) unsigned lmv_zero_page[32];
-__device__ __forceinline__ unsigned cv_div(unsigned n, unsigned long long m) { return (unsigned)(((unsigned long long)n * m) >> 40); }
+__device__ __forceinline__ unsigned cv_div(unsigned n, unsigned long long m) { return (unsigned)(((unsigned long long)n * m) >> LMV_CV_SHIFT); }
 __device__ __forceinline__ const bf16_t* cv_src(const ConvGeo& cv, int pixel, int k) {
   const unsigned b = cv_div((unsigned)pixel, cv.m_howo), rem = (unsigned)pixel - b * (unsigned)cv.HoWo, oy = cv_div(rem, cv.m_wo), ox = rem - oy * (unsigned)cv.Wo;
   const unsigned tap = cv_div((unsigned)k, cv.m_cin), ci = (unsigned)k - tap * (unsigned)cv.Cin, ky = (tap * 11u) >> 5, kx = tap - 3u * ky;

@@ -479,11 +479,13 @@ def im2col3x3s2_nhwc(x: Tensor, KP: int) -> Tensor:
 
 
 def conv3x3s2_implicit_ok(x: Tensor, Cout: int, KP: int) -> bool:
-    """Whether lmv_conv3x3s2_fwd / _dw take this NHWC map (bf16, whole k-tiles): else the patch-matrix form (im2col3x3s2_nhwc + linear_*)."""
+    """Whether lmv_conv3x3s2_fwd / _dw take this NHWC map (bf16, whole k-tiles): else the patch-matrix form (im2col3x3s2_nhwc + linear_*).
+    Mirrors every bound of conv_geo (csrc/gemm.hip): a shape it admits here and the library refuses would raise instead of falling back."""
     B, H, W, C_ = x.shape
-    rows = B * ((H + 1) // 2) * ((W + 1) // 2)
-    return (x.is_cuda and x.dtype == torch.bfloat16 and C_ % 8 == 0 and Cout % 8 == 0 and KP % 64 == 0 and KP >= 9 * C_ and rows % 64 == 0 and rows < (1 << 22) and KP < (1 << 13)
-            and x.numel() < (1 << 31))
+    Ho, Wo = (H + 1) // 2, (W + 1) // 2
+    rows = B * Ho * Wo
+    return (x.is_cuda and x.dtype == torch.bfloat16 and x.is_contiguous() and x.data_ptr() % 16 == 0 and min(B, H, W, C_, Cout) > 0 and C_ % 8 == 0 and Cout % 8 == 0
+            and KP % 64 == 0 and KP >= 9 * C_ and rows % 64 == 0 and rows < (1 << 22) and KP < (1 << 13) and Ho * Wo < (1 << 19) and x.numel() < (1 << 31))
 
 
 def conv3x3s2_fwd(x: Tensor, wm: Tensor, bias: Optional[Tensor], act: int = ACT_NONE) -> Tensor:

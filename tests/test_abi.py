@@ -129,3 +129,37 @@ def test_schedule_helpers_without_gpu():
     assert not M.image_ranges(torch.device("cuda", 0), 128, parts=1).on
     fn = _lib.lib.lmv_block_fwd_range
     assert fn.restype is ctypes.c_int and len(fn.argtypes) == 11
+
+
+def test_conv_implicit_bounds_without_gpu():
+    """The implicit conv's index arithmetic (csrc/gemm_tiles.h, cv_div; bounds of conv_geo in csrc/gemm.hip) by exact integer emulation: the quotient
+    floor(n ceil(2^s / d) / 2^s) must equal n / d for every admitted n < 2^22, d = Ho Wo < 2^19, which holds when 22 + 19 <= s; a shift by 40 mis-divides
+    the last pixel of B = 15 on a 954 x 1152 map.  And ops.conv3x3s2_implicit_ok must refuse what conv_geo refuses (Ho Wo >= 2^19), so that the model falls
+    back to the patch-matrix form instead of raising."""
+    import types
+    import numpy as np
+    from lemevit_amd import ops
+    src = open(os.path.join(ROOT, "lemevit_amd", "csrc", "gemm_tiles.h")).read()
+    shift = int(re.search(r"#define LMV_CV_SHIFT (\d+)", src).group(1))
+    assert ">> LMV_CV_SHIFT" in src
+    assert "(1ull << LMV_CV_SHIFT)" in open(os.path.join(ROOT, "lemevit_amd", "csrc", "gemm.hip")).read()
+    assert 22 + 19 <= shift and 22 + shift + 1 <= 64
+
+    def quot(n, d, s):
+        return (n * (((1 << s) + d - 1) // d)) >> s
+    d = 477 * 576
+    n = np.arange(15 * d, dtype=np.uint64)
+    assert int((quot(n, d, 40) != n // d).sum()) == 1
+    assert bool((quot(n, d, shift) == n // d).all())
+    for d in (1, 3, 8, 1 << 12, (1 << 19) - 1, (1 << 18) + 1, 274752, 524287):      # the largest n of the admitted range, and the worst remainder
+        for n in ((1 << 22) - 1, ((1 << 22) - 1) // d * d - 1, ((1 << 22) - 1) // d * d):
+            if n >= 0:
+                assert quot(n, d, shift) == n // d, (n, d)
+
+    def nhwc(B, H, W, C):
+        return types.SimpleNamespace(shape=(B, H, W, C), is_cuda=True, dtype=torch.bfloat16, is_contiguous=lambda: True, data_ptr=lambda: 1 << 20,
+                                     numel=lambda: B * H * W * C)
+    assert ops.conv3x3s2_implicit_ok(nhwc(15, 954, 1152, 8), 16, 128)
+    assert not ops.conv3x3s2_implicit_ok(nhwc(1, 1536, 1536, 8), 16, 128)            # Ho Wo = 589 824 >= 2^19
+    assert not ops.conv3x3s2_implicit_ok(nhwc(16, 1024, 1024, 8), 16, 128)           # rows = 2^22
+    assert not ops.conv3x3s2_implicit_ok(nhwc(1, 64, 64, 12), 16, 128)               # Cin % 8

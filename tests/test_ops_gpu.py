@@ -59,7 +59,8 @@ def gelu_grad64(x):
 # ------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("rows,N,K", [(300, 96, 64), (4096, 288, 96), (1000, 1152, 384), (129, 384, 1536), (16, 64, 256), (2051, 1000, 512),
-                                      (140001, 384, 128), (70003, 200, 64)])      # the last two: > 1024 tiles (several generations of workgroups)
+                                      (140001, 384, 128), (70003, 200, 64),      # these two: > 1024 tiles (several generations of workgroups)
+                                      (65536, 192, 64), (67200, 192, 64)])       # stage-1 tokens of the dense backbone at 1024^2 / 1344 x 800
 def test_linear_fwd(dtype, rows, N, K):
     o = ops()
     a, a64 = rnd((rows, K), "a", dtype)
@@ -95,7 +96,7 @@ def test_linear_dual(dtype):
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
-@pytest.mark.parametrize("rows,N,K", [(300, 96, 64), (4100, 288, 96), (777, 1536, 384), (130, 384, 1536), (513, 1000, 512)])
+@pytest.mark.parametrize("rows,N,K", [(300, 96, 64), (4100, 288, 96), (777, 1536, 384), (130, 384, 1536), (513, 1000, 512), (65536, 192, 64), (67200, 192, 64)])
 def test_linear_dx(dtype, rows, N, K):
     o = ops()
     dy, dy64 = rnd((rows, N), "dy", dtype)
@@ -109,7 +110,8 @@ def test_linear_dx(dtype, rows, N, K):
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
-@pytest.mark.parametrize("rows,N,K", [(300, 96, 64), (40000, 288, 96), (5000, 1152, 384), (2049, 384, 1536), (128, 1000, 512)])
+@pytest.mark.parametrize("rows,N,K", [(300, 96, 64), (40000, 288, 96), (5000, 1152, 384), (2049, 384, 1536), (128, 1000, 512),
+                                      (262147, 256, 64)])         # split-K slab count at the stage-1 token count of a B = 4 batch at 1024^2, ragged
 def test_linear_dw(dtype, rows, N, K):
     o = ops()
     dy, dy64 = rnd((rows, N), "dy", dtype)
@@ -188,7 +190,7 @@ def test_linear_fwd_dx_bigk(dtype, rows, rows_c, N, K):
 
 # ------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("dtype", DTYPES)
-@pytest.mark.parametrize("rows,C", [(1000, 64), (3137, 96), (800, 192), (212, 320), (333, 384), (65, 512), (48, 1280), (16, 2048), (5, 128)])
+@pytest.mark.parametrize("rows,C", [(1000, 64), (3137, 96), (800, 192), (212, 320), (333, 384), (65, 512), (48, 1280), (16, 2048), (5, 128), (262147, 64)])
 def test_layernorm(dtype, rows, C):
     o = ops()
     x, x64 = rnd((rows, C), "x", dtype, 2.0)
@@ -228,7 +230,9 @@ def test_layernorm(dtype, rows, C):
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
-@pytest.mark.parametrize("B,H,W,C", [(2, 56, 56, 96), (3, 7, 7, 512), (1, 35, 35, 64), (2, 14, 14, 384), (1, 5, 3, 32)])
+@pytest.mark.parametrize("B,H,W,C", [(2, 56, 56, 96), (3, 7, 7, 512), (1, 35, 35, 64), (2, 14, 14, 384), (1, 5, 3, 32),
+                                     # position-embedding maps of the dense backbone: 1024^2, 1344 x 800, 1000 x 600 (stages 1 and 2)
+                                     (1, 256, 256, 64), (1, 336, 200, 64), (1, 250, 150, 64), (1, 125, 75, 128)])
 def test_dwconv(dtype, B, H, W, C):
     o = ops()
     x, x64 = rnd((B, H * W, C), "x", dtype)
@@ -265,6 +269,10 @@ ATTN_CASES = [  # name, B, Lq, Lk, C, self (packed qkv) ?
     ("stream_4096", 1, 4096, 4096, 64, True),
     # BASELINE config 5 (Base at 384^2): DCA with N = 9216 (stage 1, C = 96) and N = 2304 (stage 2, C = 192) image tokens against 16 meta tokens
     ("fewq_9216", 1, 16, 9216, 96, False), ("fewk_9216", 1, 9216, 16, 96, False), ("fewq_2304", 2, 16, 2304, 192, False), ("fewk_2304", 2, 2304, 16, 192, False),
+    # the dense Tiny backbone at detection sizes: stage-3 self-attention at 1344 x 800 (4200 tokens, C = 192), stage 4 at 1024^2 (1024 tokens, C = 320),
+    # stage-1 DCA at 1024^2 / 1344 x 800 (65 536 / 67 200 image tokens against 16 meta tokens)
+    ("sa4200_192", 1, 4200, 4200, 192, True), ("sa1024_320", 1, 1024, 1024, 320, True),
+    ("fewq_65536", 1, 16, 65536, 64, False), ("fewk_65536", 1, 65536, 16, 64, False), ("fewq_67200", 1, 16, 67200, 64, False), ("fewk_67200", 1, 67200, 16, 64, False),
 ]
 
 
@@ -302,6 +310,69 @@ def test_attention(dtype, case):
         o.attn_bwd(q, k, v, out, lse, do, (dqp, 0), (dkv, 0), (dkv, C), C, scale)
         assert_close(dqp[..., :C], q64.grad, dtype, name + " dq", tol32=2e-5, tol16=3e-3)
         assert_close(dkv, torch.cat([k64.grad, v64.grad], -1), dtype, name + " dkv", tol32=2e-5, tol16=3e-3)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("B,Lq,Lk", [(2, 64, 700), (1, 128, 4200)], ids=["lk700", "lk4200"])
+def test_attention_stream_extremes(dtype, B, Lq, Lk):
+    """The streaming kernel's online softmax (csrc/attn_mfma.hip, mfma_fwd_stream_kernel: 256-key chunks, the running maximum and the O / row-sum rescale, the
+    mask of the ragged last chunk) at logits far from O(1): the scaled logits span about +-43, and each row's maximum sits in the LAST, ragged chunk (rows of
+    the first half: the running state of every earlier chunk is rescaled by ~e^-80 when that chunk arrives) or in the FIRST chunk (second half: every later
+    chunk adds terms of ~e^-80).  Per head, two key coordinates code the chunk (+-1/8: last chunk / first chunk), the query's matching coordinate (1600)
+    lifts that chunk's logits to +40 and pushes every other key to -40; the other 30 coordinates of q are 0.8 k_t, so inside the lifted chunk the row peaks
+    at key t -- for the first-half rows t walks the ragged last key tile as well.  (The code sits in a small key coordinate times a large query one on
+    purpose: a component c shared by all keys the row attends to leaves dQ unchanged in exact arithmetic, but enters the bf16 kernels' dQ as c times the
+    rounding of sum_j dS_ij -- dS is rounded to bf16 and D = dO . O is formed from the bf16 output -- which is a property of any bf16 attention backward,
+    not of the streaming.  With c = 2 that term alone exceeds the budget of test_attention in those two coordinates.)
+    The same coding makes dK in the two code coordinates ~ 1600 scale sum_i dS_ij, three orders of magnitude above the rest of dK and above dV, so dV, dK in the
+    code coordinates and dK in the other coordinates are each held to test_attention's tolerances relative to their OWN max-abs.
+    Only the bf16 case runs the streaming MFMA kernels (mfma_fwd_stream_kernel, mfma_bwd_dkv_long_kernel); fp32 attention always takes the scalar kernels of
+    csrc/attn.hip, and the fp32 case checks those at the same logits."""
+    o = ops()
+    C, h, scale, D = 64, 2, 0.2, 32
+    last0 = (Lk - 1) // 256 * 256                                             # first key of the ragged last chunk
+    assert Lk % 16 and Lk - last0 < 256, "the last chunk must be ragged"
+    kv = det_tensor((B, Lk, 2 * C), "sx.kv", 7, 1.5)
+    qp = det_tensor((B, Lq, 3 * C), "sx.q", 7, 0.1)
+    j, i = torch.arange(Lk), torch.arange(Lq)
+    first_half = (i < Lq // 2)[:, None]
+    for hh in range(h):
+        c0 = hh * D
+        kv[:, :, c0 + 30] = torch.where(j >= last0, 0.125, -0.125)
+        kv[:, :, c0 + 31] = torch.where(j < 256, 0.125, -0.125)
+        kv = kv.to(dtype).float()
+        for b in range(B):
+            tgt = torch.where(first_half[:, 0], last0 + (i * 7 + 3 * hh + b) % (Lk - last0), (i * 5 + 11 * hh + b) % 256)
+            qp[b, :, c0:c0 + 30] = 0.8 * kv[b, tgt, c0:c0 + 30]
+            qp[b, :, c0 + 30:c0 + 32] = torch.where(first_half, torch.tensor([1600.0, 0.0]), torch.tensor([0.0, 1600.0]))
+    qp, kv = qp.to(dtype), kv.to(dtype)
+    q64, k64, v64 = qp.to(torch.float64)[..., :C], kv.to(torch.float64)[..., :C], kv.to(torch.float64)[..., C:]
+    logits = torch.stack([q64[..., hh * D:(hh + 1) * D] @ k64[..., hh * D:(hh + 1) * D].transpose(-1, -2) for hh in range(h)], 1) * scale     # [B, h, Lq, Lk]
+    # the operating point this test is about, on the rounded operands the kernel reads
+    assert float(logits.amax()) > 40 and float(logits.amin()) < -40, (float(logits.amax()), float(logits.amin()))
+    am = logits.argmax(-1)
+    assert bool((am[..., :Lq // 2] >= last0).all()) and bool((am[..., Lq // 2:] < 256).all()), "row maxima must sit in the last / first chunk"
+    assert bool((am[..., :Lq // 2] >= Lk // 16 * 16).any()), "some row maxima must sit in the ragged last key tile"
+    qg, kvg = qp.to(dev()), kv.to(dev())
+    q64 = q64.clone().requires_grad_(True); k64 = k64.clone().requires_grad_(True); v64 = v64.clone().requires_grad_(True)
+    ref = _attn_ref(q64, k64, v64, h, scale)
+    q, k, v = (qg, 0), (kvg, 0), (kvg, C)
+    out, lse = o.attn_fwd(q, k, v, C, scale, want_lse=True)
+    assert_close(out, ref.detach(), dtype, "stream extremes fwd")
+    assert_close(lse, torch.logsumexp(logits, -1), torch.float32, "stream extremes lse", 2e-5)
+    do, do64 = rnd((B, Lq, C), "sx.do", dtype)
+    (ref * do64).sum().backward()
+    dqp = torch.zeros_like(qg); dkv = torch.full_like(kvg, float("nan"))
+    o.attn_bwd(q, k, v, out, lse, do, (dqp, 0), (dkv, 0), (dkv, C), C, scale)
+    code = [hh * D + c for hh in range(h) for c in (30, 31)]
+    rest = [c for c in range(C) if c not in code]
+    checks = [("dq", dqp[..., :C], q64.grad), ("dv", dkv[..., C:], v64.grad), ("dk code coordinates", dkv[..., code], k64.grad[..., code]),
+              ("dk other coordinates", dkv[..., rest], k64.grad[..., rest])]
+    for what, got, want in checks:
+        e = float((got.detach().cpu().double() - want).abs().max()) / float(want.abs().max())
+        print(f"stream extremes Lk = {Lk} {dtype}: {what}: max-abs {float(want.abs().max()):.3g}, worst err {e:.2e} of it")
+    for what, got, want in checks:
+        assert_close(got, want, dtype, "stream extremes " + what, tol32=2e-5, tol16=3e-3)
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
@@ -460,8 +531,12 @@ def test_linear_fwd_skinny(N, K):
 
 
 # ------------------------------------------------------------------------------------------------
+CONV_LARGE = [(1, 32, 64, 512, 512), (1, 64, 128, 256, 256)]       # the dense Tiny stem's conv2 and the stage-2 transition at 1024^2
+
+
 @pytest.mark.parametrize("dtype", DTYPES)
-@pytest.mark.parametrize("B,Ci,Co,H,W", [(2, 48, 96, 112, 112), (2, 96, 192, 56, 56), (2, 192, 384, 28, 28), (3, 384, 512, 14, 14), (1, 64, 128, 9, 7), (2, 8, 16, 5, 6)])
+@pytest.mark.parametrize("B,Ci,Co,H,W", [(2, 48, 96, 112, 112), (2, 96, 192, 56, 56), (2, 192, 384, 28, 28), (3, 384, 512, 14, 14), (1, 64, 128, 9, 7), (2, 8, 16, 5, 6)]
+                         + CONV_LARGE)
 def test_conv3x3s2_native(dtype, B, Ci, Co, H, W):
     """Row f1: the second stem convolution and the three stage transitions of LeMeViT-Base (models/lemevit.py:701-703, :714-717) as
     im2col + the block GEMM -- forward, data gradient (col2im gather) and weight / bias gradient vs float64 F.conv2d on the same
@@ -487,7 +562,7 @@ def test_conv3x3s2_native(dtype, B, Ci, Co, H, W):
 
 
 @pytest.mark.parametrize("B,Ci,Co,H,W", [(2, 48, 96, 112, 112), (8, 96, 192, 56, 56), (16, 192, 384, 28, 28), (64, 384, 512, 14, 14), (64, 64, 128, 9, 7), (64, 8, 16, 5, 6),
-                                         (128, 24, 40, 3, 3)])
+                                         (128, 24, 40, 3, 3)] + CONV_LARGE)
 def test_conv3x3s2_implicit(B, Ci, Co, H, W):
     """Round 6: the same convolutions as an implicit GEMM (lmv_conv3x3s2_fwd / _dw: the LDS-DMA loads gather the patch elements from the NHWC map; no patch matrix).  Forward and
     weight / bias gradient against float64 F.conv2d on the rounded operands, and BIT-identical to the patch-matrix form (the same panel images reach the same kernel); odd maps
@@ -520,6 +595,89 @@ def test_conv3x3s2_implicit(B, Ci, Co, H, W):
     assert_close(dx, x64.grad, dtype, "implicit conv dx", tol16=4e-3)
     for a, b, what in zip(res[True], res[False], ("y", "dx", "dw", "db")):
         assert torch.equal(a, b), f"implicit vs patch-matrix form: {what} differs by {float((a.float() - b.float()).abs().max()):.3e}"
+
+
+def _cv_div40(n, d):
+    """Python mirror of the implicit conv's division before the fix: floor(n * ceil(2^40 / d) / 2^40) (exact only while n (m d - 2^40) < 2^40)."""
+    m = ((1 << 40) + d - 1) // d
+    return (n * m) >> 40
+
+
+def _conv_rows_ref(x, wm, bias, rows, Ho, Wo):
+    """float64 output rows [len(rows), Cout] of Conv2d(3 x 3, stride 2, padding 1) on the NHWC map x (CPU) with the [Cout, KP] matrix wm (column (ky 3 + kx) Cin + ci)."""
+    Bx, H, W, Ci = x.shape
+    b, rem = rows // (Ho * Wo), rows % (Ho * Wo)
+    oy, ox = rem // Wo, rem % Wo
+    t = torch.arange(3)
+    iy = (2 * oy - 1)[:, None, None] + t[None, :, None]; ix = (2 * ox - 1)[:, None, None] + t[None, None, :]       # [n, 3, 3]
+    ok = ((iy >= 0) & (iy < H) & (ix >= 0) & (ix < W)).to(torch.float64)
+    p = x[b[:, None, None], iy.clamp(0, H - 1), ix.clamp(0, W - 1)].to(torch.float64) * ok[..., None]               # [n, 3, 3, Ci]
+    return p.reshape(len(rows), 9 * Ci) @ wm[:, :9 * Ci].to(torch.float64).t() + bias.to(torch.float64), p.reshape(len(rows), 9 * Ci)
+
+
+def test_conv3x3s2_implicit_exact_division():
+    """The implicit conv gathers pixel p of image b = p / (Ho Wo) through a magic-number division (gemm_tiles.h, cv_div).  With m = ceil(2^40 / d) and a shift by
+    40 it was exact only while p (m d - 2^40) < 2^40, and conv_geo admits Ho Wo < 2^19 and B Ho Wo < 2^22: at B = 15 on a 954 x 1152 map (Ho Wo = 274 752) the
+    last pixel was put into image 15, every tap of it read the zero page, and its output row came out as the bias alone.  The shape is kept only while the old
+    arithmetic (mirrored here) mis-divides at least one pixel of it, so the test keeps its meaning.  Forward on every mis-divided row, the last output image row
+    of every image and a strided sample; dW / db with dY zero outside those rows -- with a dense dY one wrong row out of 4 M would vanish in dW's rounding."""
+    o = ops()
+    B, H, W, Ci, Co = 15, 954, 1152, 8, 16
+    Ho, Wo = (H + 1) // 2, (W + 1) // 2
+    rows, KP = B * Ho * Wo, (9 * Ci + 63) // 64 * 64
+    n = np.arange(rows, dtype=np.int64)
+    b40 = _cv_div40(n, Ho * Wo)
+    oy40 = _cv_div40(np.where(b40 * Ho * Wo <= n, n - b40 * Ho * Wo, 0), Wo)
+    bad = np.nonzero((b40 != n // (Ho * Wo)) | (oy40 != (n % (Ho * Wo)) // Wo))[0]
+    assert len(bad) >= 1, "the old division must fail somewhere on this shape"
+    x = det_tensor((B, H, W, Ci), "cvd.x", 7).to(torch.bfloat16)
+    xh = x.to(dev())
+    assert o.conv3x3s2_implicit_ok(xh, Co, KP)
+    wm = torch.zeros(Co, KP, dtype=torch.bfloat16); wm[:, :9 * Ci] = det_tensor((Co, 9 * Ci), "cvd.w", 7, 1 / math.sqrt(9 * Ci)).to(torch.bfloat16)
+    bias = det_tensor((Co,), "cvd.b", 7, 0.3)
+    y = o.conv3x3s2_fwd(xh, wm.to(dev()), bias.to(dev()))
+    last_row = torch.cat([torch.arange(bb * Ho * Wo + (Ho - 1) * Wo, (bb + 1) * Ho * Wo) for bb in range(B)])
+    sel = torch.cat([torch.from_numpy(bad), last_row, torch.arange(0, rows, 4099), torch.tensor([0, rows - 1])]).unique()
+    ref, patches = _conv_rows_ref(x, wm, bias, sel, Ho, Wo)
+    got = y[sel.to(dev())]
+    assert_close(got, ref, torch.bfloat16, "conv fwd, selected rows")
+    assert_close(y[torch.from_numpy(bad).to(dev())], ref[torch.searchsorted(sel, torch.from_numpy(bad))], torch.bfloat16, "conv fwd, rows the old division mis-divides")
+    gsel = det_tensor((len(sel), Co), "cvd.g", 7).to(torch.bfloat16)
+    g = torch.zeros(rows, Co, device=dev(), dtype=torch.bfloat16); g[sel.to(dev())] = gsel.to(dev())
+    dwm = torch.zeros(Co, KP, device=dev()); db = torch.zeros(Co, device=dev())
+    o.conv3x3s2_dw(g, xh, dwm, db)
+    assert_close(dwm[:, :9 * Ci], gsel.double().t() @ patches, torch.float32, "conv dw", tol32=2e-5 * 4)
+    assert not bool(dwm[:, 9 * Ci:].any()), "columns behind 9 Cin"
+    assert_close(db, gsel.double().sum(0), torch.float32, "conv db", tol32=2e-5)
+
+
+def test_conv3x3s2_outside_implicit_bounds_takes_patch_form():
+    """A map with Ho Wo >= 2^19 (B = 1, 1536 x 1536) is refused by the implicit conv's conv_geo (csrc/gemm.hip): conv3x3s2_implicit_ok must say so, so that
+    _Conv3x3s2Fn takes the patch-matrix form (im2col + GEMM) forward and backward instead of raising LMV_ERR_SHAPE.  Against float64 F.conv2d: forward and dX on
+    sampled rows, dW and db in full."""
+    from lemevit_amd.model import _Conv3x3s2Fn
+    B, Ci, Co, H, W = 1, 8, 16, 1536, 1536
+    KP = (9 * Ci + 63) // 64 * 64
+    assert (B * ((H + 1) // 2) * ((W + 1) // 2)) % 64 == 0 and ((H + 1) // 2) * ((W + 1) // 2) >= (1 << 19)
+    x, x64 = rnd((B, Ci, H, W), "cbig.x", torch.bfloat16)
+    w32 = det_tensor((Co, Ci, 3, 3), "cbig.w", 7, 1.0 / math.sqrt(9 * Ci)); b32 = det_tensor((Co,), "cbig.b", 7, 0.3)
+    xg = x.contiguous(memory_format=torch.channels_last).requires_grad_(True)
+    wg = w32.to(dev()).requires_grad_(True); bg = b32.to(dev()).requires_grad_(True)
+    y = _Conv3x3s2Fn.apply(xg, wg, bg, torch.bfloat16)
+    assert not ops().conv3x3s2_implicit_ok(xg.detach().permute(0, 2, 3, 1), Co, KP)
+    assert y.grad_fn.meta[-1] is False, "the patch-matrix form was expected"
+    gy, gy64 = rnd(tuple(y.shape), "cbig.gy", torch.bfloat16)
+    (y.float() * gy.float()).sum().backward()
+    x64 = x64.requires_grad_(True); w64 = w32.to(torch.bfloat16).double().requires_grad_(True); b64 = b32.double().requires_grad_(True)
+    ref = torch.nn.functional.conv2d(x64, w64, b64, stride=2, padding=1)
+    (ref * gy64).sum().backward()
+    rs = torch.cat([torch.arange(0, ref.shape[2], 7), torch.tensor([ref.shape[2] - 1])])
+    assert_close(y[:, :, rs], ref.detach()[:, :, rs], torch.bfloat16, "patch-form conv fwd, sampled rows")
+    assert_close(y[:, :, :, -1], ref.detach()[:, :, :, -1], torch.bfloat16, "patch-form conv fwd, last column")
+    xs = torch.cat([torch.arange(0, H, 5), torch.tensor([H - 1])])
+    assert_close(xg.grad[:, :, xs], x64.grad[:, :, xs], torch.bfloat16, "patch-form conv dx, sampled rows", tol16=4e-3)
+    assert_close(wg.grad, w64.grad, torch.float32, "patch-form conv dw", tol32=2e-5 * 4)
+    assert_close(bg.grad, b64.grad, torch.float32, "patch-form conv db", tol32=2e-5)
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
