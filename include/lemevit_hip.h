@@ -230,6 +230,12 @@ int lmv_batchnorm_train_fwd(const void* x, const float* gamma, const float* beta
 int lmv_batchnorm_train_bwd(const void* dy, const void* x, const float* gamma, const float* beta, const float* stats, int act, void* dx,
                             float* dgamma, float* dbeta, int64_t rows, int C, void* workspace, size_t workspace_bytes, int dtype,
                             void* stream);
+/* The apply step of lmv_batchnorm_train_fwd alone, from statistics it returned: y = (x - stats[0:C]) * stats[C:2C] * gamma + beta
+ * (-> GELU), with the forward's launch geometry, so y is bit-equal to the y of the lmv_batchnorm_train_fwd call that produced `stats`.
+ * Running statistics are not touched and no workspace is needed.  A checkpointed stem / transition recomputes its BatchNorm with it in
+ * the backward pass (the running statistics were updated once, in the forward pass). */
+int lmv_batchnorm_apply_fwd(const void* x, const float* gamma, const float* beta, const float* stats, int act, void* y, int64_t rows, int C,
+                            int dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Conditional position embedding: y = x + dwconv3x3(x) + bias, NHWC (models/lemevit.py:510,546).

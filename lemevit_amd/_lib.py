@@ -123,6 +123,7 @@ SIGNATURES = {
     "lmv_batchnorm_workspace_bytes": (_Z, [_I]),
     "lmv_batchnorm_train_fwd": (_I, [_P, _P, _P, _P, _P, _F, _F, _I, _P, _P, _L, _I, _P, _Z, _I, _P]),
     "lmv_batchnorm_train_bwd": (_I, [_P, _P, _P, _P, _P, _I, _P, _P, _P, _L, _I, _P, _Z, _I, _P]),
+    "lmv_batchnorm_apply_fwd": (_I, [_P, _P, _P, _P, _I, _P, _L, _I, _I, _P]),
     "lmv_dwconv3x3_residual_fwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "lmv_dwconv3x3_residual_bwd_data": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "lmv_dwconv3x3_bwd_weight_workspace_bytes": (_Z, [_I, _I, _I, _I, _I]),

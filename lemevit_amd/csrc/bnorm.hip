@@ -296,6 +296,15 @@ int bwd_t(const T* dy, const T* x, const float* gamma, const float* beta, const 
   return LMV_OK;
 }
 
+template <typename T>
+int apply_t(const T* x, const float* gamma, const float* beta, const float* stats, int act, T* y, int64_t rows, int C, hipStream_t st) {
+  const Geo g = make_geo<T>(rows, C);                            // the training forward's geometry: y is bit-equal to its bn_apply output
+  if (act) hipLaunchKernelGGL((bn_apply_kernel<T, true>), dim3(g.blocks), dim3(TPB), 0, st, x, stats, gamma, beta, y, g);
+  else hipLaunchKernelGGL((bn_apply_kernel<T, false>), dim3(g.blocks), dim3(TPB), 0, st, x, stats, gamma, beta, y, g);
+  LMV_CHECK_LAUNCH("batchnorm_apply_fwd");
+  return LMV_OK;
+}
+
 }  // namespace
 
 extern "C" size_t lmv_batchnorm_workspace_bytes(int C) { return C > 0 ? ((size_t)MAX_BLOCKS * 2 * C + 2 * (size_t)C) * sizeof(float) : 0; }
@@ -322,4 +331,14 @@ extern "C" int lmv_batchnorm_train_bwd(const void* dy, const void* x, const floa
   hipStream_t st = (hipStream_t)stream;
   if (dtype == LMV_BF16) return bwd_t<bf16_t>((const bf16_t*)dy, (const bf16_t*)x, gamma, beta, stats, act, (bf16_t*)dx, dgamma, dbeta, rows, C, (float*)workspace, st);
   return bwd_t<float>((const float*)dy, (const float*)x, gamma, beta, stats, act, (float*)dx, dgamma, dbeta, rows, C, (float*)workspace, st);
+}
+
+extern "C" int lmv_batchnorm_apply_fwd(const void* x, const float* gamma, const float* beta, const float* stats, int act, void* y, int64_t rows, int C,
+                                       int dtype, void* stream) {
+  if (int rc = check("batchnorm_apply_fwd", x, y, rows, C, dtype)) return rc;
+  if (!gamma || !beta || !stats) LMV_FAIL(LMV_ERR_SHAPE, "batchnorm_apply_fwd: null gamma / beta / stats");
+  if (act != LMV_ACT_NONE && act != LMV_ACT_GELU) LMV_FAIL(LMV_ERR_SHAPE, "batchnorm_apply_fwd: act must be NONE or GELU");
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == LMV_BF16) return apply_t<bf16_t>((const bf16_t*)x, gamma, beta, stats, act, (bf16_t*)y, rows, C, st);
+  return apply_t<float>((const float*)x, gamma, beta, stats, act, (float*)y, rows, C, st);
 }

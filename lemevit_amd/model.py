@@ -20,6 +20,7 @@ statistics, fp32 master weights and gradients (the bf16 matrix copies are cached
 """
 from __future__ import annotations
 
+import operator
 import os
 import threading
 import weakref
@@ -272,23 +273,53 @@ class _BNActFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, running_mean, running_var, momentum, eps, gelu):
+        y, x2d, stats, g32, b32 = _bn_train_fwd(x, weight, bias, running_mean, running_var, momentum, eps, gelu)
+        ctx.save_for_backward(x2d, stats, g32, b32)
+        ctx.meta = (gelu, tuple(x.shape), weight.dtype, bias.dtype)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        return _bn_bwd(ctx, dy) + (None, None, None, None, None)
+
+
+def _bn_train_fwd(x, weight, bias, running_mean, running_var, momentum, eps, gelu):
+    """-> (y NCHW-shaped channels-last view, x2d, batch statistics [2, C], fp32 gamma, fp32 beta); running statistics updated in place."""
+    B, C, H, W = x.shape
+    x2d = x.detach().permute(0, 2, 3, 1).contiguous().view(B * H * W, C)        # no copy for channels-last input
+    g32, b32 = compute_copy(weight, torch.float32), compute_copy(bias, torch.float32)
+    y, stats = ops.batchnorm_train_fwd(x2d, g32, b32, running_mean, running_var, momentum, eps, gelu)
+    return y.view(B, H, W, C).permute(0, 3, 1, 2), x2d, stats, g32, b32
+
+
+def _bn_bwd(ctx, dy):
+    x2d, stats, g32, b32 = ctx.saved_tensors
+    gelu, (B, C, H, W), wdt, bdt = ctx.meta
+    g = dy.permute(0, 2, 3, 1).contiguous().view(B * H * W, C)
+    if g.dtype != x2d.dtype:
+        g = g.to(x2d.dtype)
+    dx, dgamma, dbeta = ops.batchnorm_train_bwd(g, x2d, g32, b32, stats, gelu)
+    return dx.view(B, H, W, C).permute(0, 3, 1, 2), dgamma.to(wdt), dbeta.to(bdt)
+
+
+class _BNApplyFn(torch.autograd.Function):
+    """A training-mode BatchNorm (+ GELU) recomputed from the batch statistics its forward pass returned (lmv_batchnorm_apply_fwd: bit-equal
+    to that pass's output, running statistics untouched) -- the backward recompute of a checkpointed stem / transition.  Its backward is
+    _BNActFn's: the gradient still runs through the batch statistics."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, stats, gelu):
         B, C, H, W = x.shape
-        x2d = x.detach().permute(0, 2, 3, 1).contiguous().view(B * H * W, C)        # no copy for channels-last input
+        x2d = x.detach().permute(0, 2, 3, 1).contiguous().view(B * H * W, C)
         g32, b32 = compute_copy(weight, torch.float32), compute_copy(bias, torch.float32)
-        y, stats = ops.batchnorm_train_fwd(x2d, g32, b32, running_mean, running_var, momentum, eps, gelu)
+        y = ops.batchnorm_apply_fwd(x2d, g32, b32, stats, gelu)
         ctx.save_for_backward(x2d, stats, g32, b32)
         ctx.meta = (gelu, (B, C, H, W), weight.dtype, bias.dtype)
         return y.view(B, H, W, C).permute(0, 3, 1, 2)
 
     @staticmethod
     def backward(ctx, dy):
-        x2d, stats, g32, b32 = ctx.saved_tensors
-        gelu, (B, C, H, W), wdt, bdt = ctx.meta
-        g = dy.permute(0, 2, 3, 1).contiguous().view(B * H * W, C)
-        if g.dtype != x2d.dtype:
-            g = g.to(x2d.dtype)
-        dx, dgamma, dbeta = ops.batchnorm_train_bwd(g, x2d, g32, b32, stats, gelu)
-        return dx.view(B, H, W, C).permute(0, 3, 1, 2), dgamma.to(wdt), dbeta.to(bdt), None, None, None, None, None
+        return _bn_bwd(ctx, dy) + (None, None)
 
 
 
@@ -299,9 +330,16 @@ def _bn_native(m: nn.Module, x: Tensor) -> bool:
             and x.shape[0] * x.shape[2] * x.shape[3] > 1 and m.weight.dtype == torch.float32)
 
 
-def _bn_train(m: nn.BatchNorm2d, x: Tensor, gelu: bool = False) -> Tensor:
+def _bn_train(m: nn.BatchNorm2d, x: Tensor, gelu: bool = False, ck: Optional[dict] = None, key: int = 0) -> Tensor:
+    """ck (a checkpointed downsample, _CkptDownsampleFn): the forward pass (grad off) keeps the batch statistics under `key`; the backward
+    recompute applies them (_BNApplyFn) -- the running statistics and num_batches_tracked move once per step, in the forward pass."""
+    if ck is not None and ck["recompute"]:
+        return _BNApplyFn.apply(x, m.weight, m.bias, ck["stats"][key], gelu)
     if m.num_batches_tracked is not None:
         m.num_batches_tracked.add_(1)
+    if ck is not None:
+        y, _, ck["stats"][key], _, _ = _bn_train_fwd(x, m.weight, m.bias, m.running_mean, m.running_var, float(m.momentum), float(m.eps), gelu)
+        return y
     return _BNActFn.apply(x, m.weight, m.bias, m.running_mean, m.running_var, float(m.momentum), float(m.eps), gelu)
 
 
@@ -699,13 +737,22 @@ def _join_ranges(device) -> None:
         rs[1] = False
 
 
-def native_block_forward(kind: str, x: Tensor, c: Tensor, H: int, W: int, names, P: Dict[str, Tensor], masks, save: bool, folds=None, wts=None):
+def native_block_forward(kind: str, x: Tensor, c: Tensor, H: int, W: int, names, P: Dict[str, Tensor], masks, save: bool, folds=None, wts=None,
+                         ckpt: bool = False):
     """lmv_block_fwd: returns (x_out, c_out, state) with state = (descriptor, arena) for native_block_backward (save=True).
-    Inside image_ranges() (training): one lmv_block_fwd_range call per range of images, each on its own stream."""
+    Inside image_ranges() (training): one lmv_block_fwd_range call per range of images, each on its own stream.
+    ckpt (save=True, a checkpointed block): the same calls write a reused per-device arena, state = (descriptor, None), and the
+    descriptor keeps the range cuts (d._cuts) -- native_block_backward recomputes the arena with them."""
     from ._lib import lib, check
     d = _block_desc(kind, x, c, H, W, names, P, masks, None if save else folds, wts if save else None)
     nbytes = _sized(lib.lmv_block_arena_bytes, d, kind, x, c, H, W)
-    arena = torch.empty(nbytes, device=x.device, dtype=torch.uint8) if save else _persistent("fwd", nbytes, x.device)
+    if ckpt:
+        # (the blocks of a stage share one size, so the arena only grows at a stage's first block -- behind image_ranges' join of the
+        # previous stage's range streams, which is where the replaced buffer goes back to the allocator)
+        arena = _persistent("ckpt", nbytes, x.device)
+    else:
+        arena = torch.empty(nbytes, device=x.device, dtype=torch.uint8) if save else _persistent("fwd", nbytes, x.device)
+    d._cuts = None
     xo = torch.empty_like(x) if kind != "C" else None
     co = torch.empty_like(c)
     rs = _range_state.get(x.device.index) if save else None
@@ -732,7 +779,35 @@ def native_block_forward(kind: str, x: Tensor, c: Tensor, H: int, W: int, names,
             check(lib.lmv_block_fwd_range(d, x.data_ptr(), c.data_ptr(), None if xo is None else xo.data_ptr(), co.data_ptr(), arena.data_ptr(), arena.numel(), 1,
                                           cuts[i], cuts[i + 1] - cuts[i], st.cuda_stream), "lmv_block_fwd_range")
         rs[1] = True
-    return (x if xo is None else xo), co, ((d, arena) if save else None)
+        d._cuts = cuts
+    return (x if xo is None else xo), co, ((d, None if ckpt else arena) if save else None)
+
+
+def _recompute_arena(kind: str, d, x: Tensor, c: Tensor, H: int, W: int) -> Tensor:
+    """The arena of a checkpointed block, rewritten by the forward calls of its forward pass: same descriptor (operand copies, transposed
+    weights, DropPath masks), save = 1, and the same image-range cuts -- the kernel selection follows the row count of a call, so a
+    whole-batch call would not reproduce a ranged forward bit for bit.  The ranges run in order on the current stream (the first auxiliary
+    stream is the weight-gradient side stream now).
+
+    A fresh buffer per block, released through the deferred side-stream join (native_block_backward hands it to blocks.defer_join): the
+    side stream still reads block k's arena while block k - 1 runs, and the join of block k is made at the end of block k - 1
+    (_wait_pending keeps one position), so block k - 2 allocates after that wait and gets block k's memory back.  At most two
+    recompute arenas are live at a time."""
+    from ._lib import lib, check
+    nbytes = _sized(lib.lmv_block_arena_bytes, d, kind, x, c, H, W)
+    arena = torch.empty(nbytes, device=x.device, dtype=torch.uint8)
+    xo = torch.empty_like(x) if kind != "C" else None
+    co = torch.empty_like(c)
+    d.flags = 0
+    st = ops._stream()
+    xp, cp, xop, cop = x.data_ptr(), c.data_ptr(), None if xo is None else xo.data_ptr(), co.data_ptr()
+    if d._cuts is None:
+        check(lib.lmv_block_fwd(d, xp, cp, xop, cop, arena.data_ptr(), arena.numel(), 1, st), "lmv_block_fwd")
+    else:
+        cuts = d._cuts
+        for i in range(len(cuts) - 1):
+            check(lib.lmv_block_fwd_range(d, xp, cp, xop, cop, arena.data_ptr(), arena.numel(), 1, cuts[i], cuts[i + 1] - cuts[i], st), "lmv_block_fwd_range")
+    return arena
 
 
 def native_block_backward(kind: str, state, x: Tensor, c: Tensor, dx: Optional[Tensor], dc: Tensor, H: int, W: int, names, G: Dict[str, Tensor]):
@@ -740,6 +815,8 @@ def native_block_backward(kind: str, state, x: Tensor, c: Tensor, dx: Optional[T
     from . import blocks as blocks_mod
     from .blocks import side_stream_handle
     d, arena = state
+    if arena is None:                    # a checkpointed block (native_block_forward(ckpt=True))
+        arena = _recompute_arena(kind, d, x, c, H, W)
     for n in names:
         if G[n].dtype != torch.float32:
             raise TypeError("lemevit_amd: gradient accumulators must be float32")
@@ -764,8 +841,11 @@ def native_block_backward(kind: str, state, x: Tensor, c: Tensor, dx: Optional[T
 # one autograd node per block
 # ------------------------------------------------------------------------------------------------
 class _BlockFn(torch.autograd.Function):
+    """ckpt (a stage in use_checkpoint_stages): only the inputs x, c are kept; backward recomputes the block's saved set with the same calls,
+    descriptor, operand copies and DropPath masks first (native_block_backward / blocks.block_forward(save=True))."""
+
     @staticmethod
-    def forward(ctx, x, c, kind, H, W, masks, names, *params):
+    def forward(ctx, x, c, kind, H, W, masks, names, ckpt, *params):
         cd = x.dtype
         P = {n: compute_copy(p, cd if _is_matrix(n) else torch.float32) for n, p in zip(names, params)}
         ctx.native = _native_ok(kind, x, c)
@@ -778,13 +858,15 @@ class _BlockFn(torch.autograd.Function):
                     sh, wt = getattr(w, "_lmv_shadow", None), getattr(w, "_lmv_shadow_t", None)
                     if wt is not None and sh is not None and (P[n] is sh or P[n].data_ptr() == sh.data_ptr()):
                         wts[n] = wt
-            xo, co, state = native_block_forward(kind, x, c, H, W, names, P, masks, save=True, wts=wts)
+            xo, co, state = native_block_forward(kind, x, c, H, W, names, P, masks, save=True, wts=wts, ckpt=ckpt)
             saved = (x, c, state)
         else:
             if x.is_cuda:
                 _join_ranges(x.device)
             xo, co, saved = block_forward(kind, x, c, H, W, P, masks, save=True)
-        ctx.kind, ctx.H, ctx.W, ctx.masks, ctx.names = kind, H, W, masks, names
+            if ckpt:
+                saved = (x, c)              # the same calls as the unchecked block (save=True); their saved set is dropped here
+        ctx.kind, ctx.H, ctx.W, ctx.masks, ctx.names, ctx.ckpt = kind, H, W, masks, names, ckpt
         ctx.saved, ctx.P = saved, P
         ctx.pmeta = [(p.shape, p.dtype) for p in params]
         ctx.params = params
@@ -829,7 +911,9 @@ class _BlockFn(torch.autograd.Function):
             if kind == "C" and dx is not None:
                 dx0 = dx0 + dx                      # the untouched x's pass-through gradient (as blocks.block_backward)
         else:
-            dx0, dc0 = block_backward(kind, ctx.saved, None if dx is None else dx.contiguous(), None if dc is None else dc.contiguous(), ctx.H, ctx.W, P, G, ctx.masks)
+            saved = block_forward(kind, ctx.saved[0], ctx.saved[1], ctx.H, ctx.W, P, ctx.masks, save=True)[2] if ctx.ckpt else ctx.saved
+            dx0, dc0 = block_backward(kind, saved, None if dx is None else dx.contiguous(), None if dc is None else dc.contiguous(), ctx.H, ctx.W, P, G, ctx.masks)
+            del saved
         cb = getattr(ctx.params[0], "_lmv_grad_cb", None) if inplace else None
         ctx.saved = ctx.params = None
         if cb is not None or not inplace:
@@ -840,19 +924,20 @@ class _BlockFn(torch.autograd.Function):
         if cb is not None:
             cb()                     # lemevit_amd.dist.FlatGradSync: this block closes a chunk of the flat gradient buffer -> start its all-reduce
         if inplace:
-            return (dx0, dc0, None, None, None, None, None, *([None] * len(names)))
+            return (dx0, dc0, None, None, None, None, None, None, *([None] * len(names)))
         pg = [G[n] if dt == torch.float32 else G[n].to(dt) for n, (_, dt) in zip(names, ctx.pmeta)]
-        return (dx0, dc0, None, None, None, None, None, *pg)
+        return (dx0, dc0, None, None, None, None, None, None, *pg)
 
 
 def run_block(kind: str, x: Tensor, c: Tensor, H: int, W: int, params: "OrderedDict[str, Tensor]",
-              masks: Sequence[Optional[Tensor]]) -> Tuple[Tensor, Tensor]:
-    """LeMeBlock on token-major tensors; picks the autograd node or the no-grad fast path."""
+              masks: Sequence[Optional[Tensor]], ckpt: bool = False) -> Tuple[Tensor, Tensor]:
+    """LeMeBlock on token-major tensors; picks the autograd node or the no-grad fast path.  ckpt: recompute the block in backward
+    (_BlockFn); a forward without an autograd graph is unaffected."""
     names = PARAM_NAMES[kind]
     plist = [params[n] for n in names]
     need_grad = torch.is_grad_enabled() and (x.requires_grad or c.requires_grad or any(p.requires_grad for p in plist))
     if need_grad:
-        out = _BlockFn.apply(x, c, kind, H, W, tuple(masks), names, *plist)
+        out = _BlockFn.apply(x, c, kind, H, W, tuple(masks), names, bool(ckpt), *plist)
         return (x, out) if kind == "C" else ((out, c) if kind == "Sx" else out)
     cd = x.dtype
     P = {n: compute_copy(p, cd if _is_matrix(n) else torch.float32) for n, p in zip(names, plist)}
@@ -1229,6 +1314,7 @@ class LeMeBlock(nn.Module):
         self.norm2 = nn.LayerNorm(dim, eps=1e-6)
         self.mlp = nn.Sequential(nn.Linear(dim, int(mlp_ratio * dim)), nn.Identity(), nn.GELU(), nn.Linear(int(mlp_ratio * dim), dim))
         self.drop_prob = float(drop_path)
+        self.grad_checkpointing = False     # recompute in backward (LeMeViT.use_checkpoint_stages / set_grad_checkpointing)
         self._pcache = None
 
     def _params(self) -> "OrderedDict[str, Tensor]":
@@ -1259,7 +1345,7 @@ class LeMeBlock(nn.Module):
             masks = self._masks(x.shape[0], x.device)
             if any(m is not None for m in masks):
                 _cache_filled()          # masks drawn HERE are kernels on the current stream: image_ranges() must re-fork its range streams behind them
-        return run_block(self.kind, x, c, H, W, self._params(), masks)
+        return run_block(self.kind, x, c, H, W, self._params(), masks, ckpt=self.grad_checkpointing)
 
     def forward(self, x: Tensor, c: Tensor) -> Tuple[Tensor, Tensor]:
         """Reference signature: x NCHW in / out (models/lemevit.py:652)."""
@@ -1269,6 +1355,76 @@ class LeMeBlock(nn.Module):
         xt = x.permute(0, 2, 3, 1).reshape(B, H * W, C).contiguous()
         xt, c = self.forward_tokens(xt, c.contiguous(), H, W)
         return xt.reshape(B, H, W, C).permute(0, 3, 1, 2), c
+
+
+def _downsample_mods(mods: List[nn.Module], x: Tensor, cd: torch.dtype, fold: bool, ck: Optional[dict] = None) -> Tensor:
+    """The layers of LeMeViT._run_downsample on the native kernels.  ck: see _bn_train (the backward recompute takes the training-mode
+    BatchNorms its forward pass took, by module index)."""
+    i = 0
+    while i < len(mods):
+        m = mods[i]
+        bn = mods[i + 1] if i + 1 < len(mods) and isinstance(mods[i + 1], nn.BatchNorm2d) and mods[i + 1].track_running_stats else None
+        if fold and isinstance(m, nn.Conv2d) and bn is not None:
+            w, b, b32 = _folded_conv_bn(m, bn, cd)
+            if _is_stem_conv1(m, x):
+                gelu = i + 2 < len(mods) and isinstance(mods[i + 2], nn.GELU) and getattr(mods[i + 2], "approximate", "none") == "none"
+                x = _StemConv1Fn.apply(x, w, b32, cd, gelu)
+                i += 3 if gelu else 2
+            elif _is_conv3x3s2(m, x) and cd in (torch.float32, torch.bfloat16):
+                x = _Conv3x3s2Fn.apply(x, w, b32, cd)
+                i += 2
+            else:
+                # (no vendor-library convolution behind the native ones: the stock PyTorch-ROCm column lives in tools/stock_eager.py)
+                raise NotImplementedError(f"lemevit_amd: no native kernel for {m} on a {tuple(x.shape)} {x.dtype} map (the library carries the 3 x 3 / stride-2 / padding-1 "
+                                          "convolutions of the LeMeViT stem and stage transitions, channels a multiple of 8, fp32 / bf16)")
+        elif _is_stem_conv1(m, x) and cd in (torch.float32, torch.bfloat16):
+            x = _StemConv1Fn.apply(x, m.weight, m.bias, cd)
+            i += 1
+        elif _is_conv3x3s2(m, x) and cd in (torch.float32, torch.bfloat16):
+            x = _Conv3x3s2Fn.apply(x, m.weight, m.bias, cd)
+            i += 1
+        elif (i in ck["stats"]) if (ck is not None and ck["recompute"]) else _bn_native(m, x):
+            gelu = i + 1 < len(mods) and isinstance(mods[i + 1], nn.GELU) and getattr(mods[i + 1], "approximate", "none") == "none"
+            x = _bn_train(m, x, gelu, ck, i)
+            i += 2 if gelu else 1
+        else:
+            if isinstance(m, nn.Conv2d):
+                raise NotImplementedError(f"lemevit_amd: no native kernel for {m} on a {tuple(x.shape)} {x.dtype} map (see above)")
+            x = m(x)          # (element-wise glue of a caller-built Sequential: activation, Identity, an eval-mode normalisation under autograd)
+            i += 1
+    return x
+
+
+
+class _CkptDownsampleFn(torch.autograd.Function):
+    """A checkpointed stem / stage transition (use_checkpoint_stages non-empty, as the reference's checkpoint_wrapper around every
+    downsample layer, models/lemevit.py:706-707, 718-719): the forward pass runs the layers without an autograd graph and keeps only the
+    input map and each training-mode BatchNorm's batch statistics [2, C]; the backward pass re-runs the convolutions on the same kernels,
+    the BatchNorms from those statistics (_BNApplyFn) -- an eval-mode BatchNorm with the call its forward made -- under the forward's
+    autocast state, and differentiates that.  Values, the running statistics included, are those of the unchecked path."""
+
+    @staticmethod
+    def forward(ctx, mods, x, cd, autocast, *params):
+        ck = {"recompute": False, "stats": {}}
+        y = _downsample_mods(mods, x, cd, False, ck)
+        ctx.save_for_backward(x)
+        ctx.mods, ctx.cd, ctx.autocast, ctx.ck, ctx.params = mods, cd, autocast, ck, params
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        (x,) = ctx.saved_tensors
+        need_x, need_p = ctx.needs_input_grad[1], ctx.needs_input_grad[4:]
+        ck = dict(ctx.ck, recompute=True)
+        with torch.enable_grad(), torch.autocast("cuda", dtype=ctx.cd if ctx.autocast else torch.bfloat16, enabled=ctx.autocast):
+            xr = x.detach().requires_grad_(need_x)
+            y = _downsample_mods(ctx.mods, xr, ctx.cd, False, ck)
+        inputs = ([xr] if need_x else []) + [p for p, n in zip(ctx.params, need_p) if n]
+        grads = list(torch.autograd.grad(y, inputs, dy, allow_unused=True))
+        dx = grads.pop(0) if need_x else None
+        dps = [grads.pop(0) if n else None for n in need_p]
+        ctx.mods = ctx.ck = ctx.params = None
+        return (None, dx, None, None, *dps)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1331,6 +1487,31 @@ class LeMeViT(nn.Module):
         self.head = nn.Linear(embed_dim[-1], num_classes) if num_classes > 0 else nn.Identity()
         self.apply(self._init_weights)
         self.default_cfg = _cfg()
+        self._set_checkpoint_stages(use_checkpoint_stages)
+
+    def _set_checkpoint_stages(self, stages) -> None:
+        """Activation checkpointing (models/lemevit.py:706-707, 718-719, 767-768): every block of the listed stages and -- for a non-empty
+        list -- the stem and every stage transition keep only their inputs and recompute the rest in backward.  Only a forward that builds
+        an autograd graph is affected; values are bit-identical to the unchecked model."""
+        idx = []
+        for i in stages:
+            try:
+                j = None if isinstance(i, bool) else operator.index(i)          # any integer-like index (numpy integers, 0-d integer tensors); not bools or floats
+            except TypeError:
+                j = None
+            if j is None or not 0 <= j < self.num_stages:
+                raise ValueError(f"use_checkpoint_stages: {i!r} is not a stage index in range({self.num_stages})")
+            idx.append(j)
+        self.use_checkpoint_stages = sorted(set(idx))
+        self.grad_checkpointing = bool(idx)          # the stem and the transitions
+        for i, stage in enumerate(self.stages):
+            for blk in stage:
+                blk.grad_checkpointing = i in idx
+
+    @torch.jit.ignore
+    def set_grad_checkpointing(self, enable: bool = True) -> None:
+        """timm's convention (benchmark.py / train.py --grad-checkpointing): all stages, the stem and the transitions; False: none."""
+        self._set_checkpoint_stages(range(self.num_stages) if enable else [])
 
     def _init_weights(self, m):                      # models/lemevit.py:789-796
         if isinstance(m, nn.Linear):
@@ -1366,46 +1547,21 @@ class LeMeViT(nn.Module):
     def _run_downsample(self, seq: nn.Module, x: Tensor) -> Tensor:
         """Conv-BN(-GELU-Conv-BN) of the stem / a stage transition (models/lemevit.py:713-728).  In inference (eval mode,
         no grad) every BatchNorm is folded into the weights of the convolution before it: y = conv(x; w*s, (b-mu)*s+beta),
-        s = gamma / sqrt(var + eps) -- the same affine map, one kernel and one pass over the feature map less per layer."""
+        s = gamma / sqrt(var + eps) -- the same affine map, one kernel and one pass over the feature map less per layer.
+        With activation checkpointing on (use_checkpoint_stages non-empty / set_grad_checkpointing) and an autograd graph being built, the
+        layers run as ONE _CkptDownsampleFn node that keeps only its input map and the batch statistics of its training-mode BatchNorms."""
         if not isinstance(seq, nn.Sequential):
             return seq(x)
         cd = x.dtype if not torch.is_autocast_enabled() else torch.get_autocast_dtype("cuda")
         fold = not (self.training or torch.is_grad_enabled())
-        mods, i = list(seq), 0
+        mods = list(seq)
         if fold and _stem_applies(mods, x, cd):
             return _stem_fused(mods, x, cd)
-        while i < len(mods):
-            m = mods[i]
-            bn = mods[i + 1] if i + 1 < len(mods) and isinstance(mods[i + 1], nn.BatchNorm2d) and mods[i + 1].track_running_stats else None
-            if fold and isinstance(m, nn.Conv2d) and bn is not None:
-                w, b, b32 = _folded_conv_bn(m, bn, cd)
-                if _is_stem_conv1(m, x):
-                    gelu = i + 2 < len(mods) and isinstance(mods[i + 2], nn.GELU) and getattr(mods[i + 2], "approximate", "none") == "none"
-                    x = _StemConv1Fn.apply(x, w, b32, cd, gelu)
-                    i += 3 if gelu else 2
-                elif _is_conv3x3s2(m, x) and cd in (torch.float32, torch.bfloat16):
-                    x = _Conv3x3s2Fn.apply(x, w, b32, cd)
-                    i += 2
-                else:
-                    # (no vendor-library convolution behind the native ones: the stock PyTorch-ROCm column lives in tools/stock_eager.py)
-                    raise NotImplementedError(f"lemevit_amd: no native kernel for {m} on a {tuple(x.shape)} {x.dtype} map (the library carries the 3 x 3 / stride-2 / padding-1 "
-                                              "convolutions of the LeMeViT stem and stage transitions, channels a multiple of 8, fp32 / bf16)")
-            elif _is_stem_conv1(m, x) and cd in (torch.float32, torch.bfloat16):
-                x = _StemConv1Fn.apply(x, m.weight, m.bias, cd)
-                i += 1
-            elif _is_conv3x3s2(m, x) and cd in (torch.float32, torch.bfloat16):
-                x = _Conv3x3s2Fn.apply(x, m.weight, m.bias, cd)
-                i += 1
-            elif _bn_native(m, x):
-                gelu = i + 1 < len(mods) and isinstance(mods[i + 1], nn.GELU) and getattr(mods[i + 1], "approximate", "none") == "none"
-                x = _bn_train(m, x, gelu)
-                i += 2 if gelu else 1
-            else:
-                if isinstance(m, nn.Conv2d):
-                    raise NotImplementedError(f"lemevit_amd: no native kernel for {m} on a {tuple(x.shape)} {x.dtype} map (see above)")
-                x = m(x)          # (element-wise glue of a caller-built Sequential: activation, Identity, an eval-mode normalisation under autograd)
-                i += 1
-        return x
+        if getattr(self, "grad_checkpointing", False) and torch.is_grad_enabled():
+            params = [p for m in mods for p in m.parameters(recurse=False)]
+            if x.requires_grad or any(p.requires_grad for p in params):
+                return _CkptDownsampleFn.apply(mods, x, cd, torch.is_autocast_enabled(), *params)
+        return _downsample_mods(mods, x, cd, fold)
 
     def _draw_drop_path(self, B: int, device) -> Dict[int, List[Optional[Tensor]]]:
         """All DropPath masks of one forward pass from ONE uniform draw (instead of ~120 tiny bernoulli_/div_ launches):

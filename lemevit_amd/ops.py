@@ -185,6 +185,15 @@ def batchnorm_train_fwd(x2d: Tensor, gamma: Tensor, beta: Tensor, running_mean: 
     return y, stats
 
 
+def batchnorm_apply_fwd(x2d: Tensor, gamma: Tensor, beta: Tensor, stats: Tensor, gelu: bool = False) -> Tensor:
+    """y of batchnorm_train_fwd recomputed from the stats [2, C] it returned (bit-equal); running statistics untouched."""
+    rows, C_ = x2d.shape
+    y = torch.empty_like(x2d)
+    check(lib.lmv_batchnorm_apply_fwd(_ptr(x2d), _f32(gamma), _f32(beta), _f32(stats), ACT_GELU if gelu else ACT_NONE, _ptr(y), rows, C_,
+                                      dtype_code(x2d), _stream()), "lmv_batchnorm_apply_fwd")
+    return y
+
+
 def batchnorm_train_bwd(dy2d: Tensor, x2d: Tensor, gamma: Tensor, beta: Tensor, stats: Tensor, gelu: bool = False):
     """Returns (dx, dgamma, dbeta) of batchnorm_train_fwd."""
     rows, C_ = x2d.shape

@@ -70,8 +70,9 @@ def load_checkpoint(model: torch.nn.Module, path: str, strict: bool = True):
 
 def _variant(pretrained, kwargs, **hp):
     kwargs.pop("pretrained_cfg", None); kwargs.pop("pretrained_cfg_overlay", None)
+    kwargs.setdefault("use_checkpoint_stages", [])
     model = LeMeViT(head_dim=32, queries_len=16, qkv_bias=True, qk_scale=None, attn_drop=0.0, qk_dims=None, cpe_ks=3, pre_norm=True,
-                    mlp_dwconv=False, representation_size=None, layer_scale_init_value=-1, use_checkpoint_stages=[], **hp, **kwargs)
+                    mlp_dwconv=False, representation_size=None, layer_scale_init_value=-1, **hp, **kwargs)
     model.default_cfg = _cfg()
     if pretrained:                      # the reference treats `pretrained` as a checkpoint PATH (models/lemevit.py:868-870)
         load_checkpoint(model, pretrained)
