@@ -16,7 +16,7 @@ and stride-2 down-sample conv+BatchNorm, the 16-token meta MLPs, and the BN/LN/m
 
 Compute dtype: fp32 input without autocast -> exact-fp32 kernels; bf16 input (``model.to(bfloat16)``)
 or ``torch.autocast('cuda', torch.bfloat16)`` -> bf16 MFMA kernels with fp32 accumulation, fp32
-statistics, fp32 master weights and gradients (the bf16 matrix copies are cached per parameter version).
+statistics, fp32 master weights and gradients (the bf16 matrix copies are derived operands, see ``derived``).
 """
 from __future__ import annotations
 
@@ -46,16 +46,12 @@ def _cfg(url: str = "", **kwargs) -> dict:
 
 
 # ------------------------------------------------------------------------------------------------
-# compute-dtype copies of parameters
+# derived operands: what the kernels read instead of the parameters themselves (bf16 casts, LayerNorm and conv + BatchNorm folds,
+# GEMM weight matrices, the packed stem and stages, the classifier tail, the first meta-token MLP's output), cached under ONE rule
 # ------------------------------------------------------------------------------------------------
-_copy_cache: Dict[int, tuple] = {}
-
-
-def _is_matrix(name: str) -> bool:
-    return name.endswith(".weight") and (name.startswith("attn.") or name.startswith("mlp."))
-
-
-_train_pass = 0          # bumped by every training-mode forward pass: casts made for an earlier pass are not reused
+_train_pass = 0          # bumped by every training-mode forward pass (see derived)
+_casts_launched = 0      # operand builds and DropPath draws on the current stream (cache_fills)
+_derived: Dict[tuple, tuple] = {}          # (id(owner), tag) -> (weakref to owner, stamp, weakrefs to sources, value)
 
 
 def new_training_pass() -> None:
@@ -65,32 +61,34 @@ def new_training_pass() -> None:
     _blocks.drain_deferred()        # a backward pass that raised leaves deferred side-stream joins (and its final callback) behind
 
 
-def compute_copy(p: Tensor, want: torch.dtype) -> Tensor:
-    """Detached tensor with p's values in dtype `want`.
-
-    Inference: casts are cached per parameter version (load_state_dict / copy_ bump it).  Training: the cache is only
-    valid within ONE forward pass -- fused optimizers (torch.optim.AdamW(fused=True), torch._fused_adamw_) update the
-    parameters in place WITHOUT bumping ``_version``, so a version-keyed cache would keep feeding stale bf16 weights to
-    the kernels.  An optimizer that maintains the bf16 copy itself (lemevit_amd.optim.FlatAdamW) attaches it as
-    ``p._lmv_shadow`` and no cast is launched at all."""
-    if p.dtype == want:
-        return p.detach()
-    shadow = getattr(p, "_lmv_shadow", None)
-    if shadow is not None and shadow.dtype == want and shadow.device == p.device:
-        return shadow
-    key = id(p)
-    ent = _copy_cache.get(key)
-    stamp = (p._version, _train_pass, torch.is_grad_enabled() and p.requires_grad)      # a later training pass invalidates inference casts too
-    if ent is not None and ent[0]() is p and ent[1] == stamp and ent[2].dtype == want and ent[2].device == p.device:
-        return ent[2]
-    global _casts_launched
-    _casts_launched += 1             # a kernel on the current stream: image_ranges() re-forks its range streams behind it
-    t = ops.cast(p.detach().contiguous(), want)
-    _copy_cache[key] = (weakref.ref(p), stamp, t)
-    return t
+def _no_source():
+    return None          # stands in for the weakref of an absent source (a bias that is None)
 
 
-_casts_launched = 0
+def derived(owner, tag, sources: Sequence[Optional[Tensor]], build):
+    """build()'s value for (owner, tag): built once (without autograd) and served until a source may have changed, i.e. until
+    * a source tensor was replaced (identity), written in place (``_version``) or re-homed (``data_ptr``: ``p.data = t`` and
+      ``model.to()`` swap a Parameter's storage without bumping its version);
+    * a training pass has started since the build (new_training_pass).  Fused optimizers (torch.optim.AdamW(fused=True),
+      lmv_adamw_flat), the native BatchNorm kernel's running statistics and every other write through a raw pointer change
+      parameters in place WITHOUT bumping ``_version``, so a value built before a training pass must not survive it.  Code that
+      writes parameters that way outside a training pass calls new_training_pass() itself (optim.ModelEma.update);
+    * the grad mode differs, where a source requires grad.
+    `tag` carries everything else the value depends on (dtype, KP, stage kind): another tag is another entry.  An entry holds weak
+    references only -- `build` must return tensors of its own, not the owner or a source -- so it goes with its owner and is never
+    served for a recycled id().  Every build is a fill (cache_fills)."""
+    key = (id(owner), tag)
+    stamp = (_train_pass, torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in sources),
+             tuple(None if t is None else (t._version, t.data_ptr()) for t in sources))
+    ent = _derived.get(key)
+    if ent is not None and ent[0]() is owner and ent[1] == stamp and all(r() is t for r, t in zip(ent[2], sources)):
+        return ent[3]
+    with torch.no_grad():
+        value = build()
+    _cache_filled()
+    refs = tuple(_no_source if t is None else weakref.ref(t) for t in sources)
+    _derived[key] = (weakref.ref(owner, lambda _r, k=key, pop=_derived.pop: pop(k, None)), stamp, refs, value)      # (bound: interpreter exit may clear the global first)
+    return value
 
 
 def _cache_filled() -> None:
@@ -104,28 +102,29 @@ def cache_fills() -> int:
     return _casts_launched
 
 
-_fold_cache: dict = {}
-_conv1_cache: dict = {}
+def _is_matrix(name: str) -> bool:
+    return name.endswith(".weight") and (name.startswith("attn.") or name.startswith("mlp."))
 
-# Inference: LayerNorm folded into the Linear that consumes it (ops.ln_fold -> lmv_ln_linear_fwd / lmv_mlp_fused_fwd).  The folded
-# operands are cached per version of the four parameters involved (and per training pass, see compute_copy).
+
+def compute_copy(p: Tensor, want: torch.dtype) -> Tensor:
+    """Detached tensor with p's values in dtype `want` (a derived operand).  An optimizer that maintains the bf16 copy itself
+    (lemevit_amd.optim.FlatAdamW) attaches it as ``p._lmv_shadow`` and no cast is launched at all."""
+    if p.dtype == want:
+        return p.detach()
+    shadow = getattr(p, "_lmv_shadow", None)
+    if shadow is not None and shadow.dtype == want and shadow.device == p.device:
+        return shadow
+    return derived(p, ("cast", want), (p,), lambda: ops.cast(p.detach().contiguous(), want))
+
+
+# Inference: LayerNorm folded into the Linear that consumes it (ops.ln_fold -> lmv_ln_linear_fwd / lmv_mlp_fused_fwd).
 _FUSED = os.environ.get("LMV_FUSED", "1") != "0"          # 0: LayerNorm + Linear launches as in the training schedule (A/B runs)
-_ln_fold_cache: dict = {}
 _FOLD_PAIRS = {"S": (("attn.qkv", "norm1"),), "D": (("attn.qkv1", "norm1"), ("attn.qkv2", "norm1")), "C": (("attn.q", "norm1"), ("attn.kv", "norm1"))}
 
 
 def _ln_fold_cached(w: Tensor, b: Optional[Tensor], g: Tensor, be: Tensor, dtype: torch.dtype) -> "ops.Folded":
-    key = (id(w), dtype)
-    stamp = tuple(t._version for t in (w, g, be)) + (None if b is None else b._version, _train_pass, id(g), id(be))
-    ent = _ln_fold_cache.get(key)
-    if ent is not None and ent[0]() is w and ent[1] == stamp:
-        return ent[2]
-    with torch.no_grad():
-        f32 = lambda t: None if t is None else t.detach().float().contiguous()
-        F = ops.ln_fold(f32(w), f32(b), f32(g), f32(be), dtype)
-    _cache_filled()
-    _ln_fold_cache[key] = (weakref.ref(w, lambda _r, k=key: _ln_fold_cache.pop(k, None)), stamp, F)      # dropped with the parameter (a deleted model does not leak its folds)
-    return F
+    f32 = lambda t: None if t is None else t.detach().float().contiguous()
+    return derived(w, ("ln_fold", dtype), (w, b, g, be), lambda: ops.ln_fold(f32(w), f32(b), f32(g), f32(be), dtype))
 
 
 def block_folds(kind: str, params: "Dict[str, Tensor]", dtype: torch.dtype):
@@ -138,18 +137,12 @@ def block_folds(kind: str, params: "Dict[str, Tensor]", dtype: torch.dtype):
 
 
 def _conv1_matrix(weight: Tensor, dtype: torch.dtype) -> Tensor:
-    """[Cout, 3, 3, 3] stem weight -> the [Cout, 32] GEMM operand of ops.im2col3x3s2_c3 (columns 27..31 zero), cached per version."""
-    key = (id(weight), dtype)
-    ent = _conv1_cache.get(key)
-    stamp = (weight._version, _train_pass, torch.is_grad_enabled() and weight.requires_grad)      # see compute_copy
-    if ent is not None and ent[0]() is weight and ent[1] == stamp:
-        return ent[2]
-    with torch.no_grad():
+    """[Cout, 3, 3, 3] stem weight -> the [Cout, 32] GEMM operand of ops.im2col3x3s2_c3 (columns 27..31 zero), a derived operand."""
+    def build():
         m = torch.zeros(weight.shape[0], 32, device=weight.device, dtype=dtype)
         m[:, :27] = weight.detach().reshape(weight.shape[0], 27)
-    _cache_filled()
-    _conv1_cache[key] = (weakref.ref(weight, lambda _r, k=key: _conv1_cache.pop(k, None)), stamp, m)
-    return m
+        return m
+    return derived(weight, ("conv1", dtype), (weight,), build)
 
 
 class _StemConv1Fn(torch.autograd.Function):
@@ -186,26 +179,15 @@ class _StemConv1Fn(torch.autograd.Function):
         return None, dw, (None if bdt is None else db.to(bdt)), None, None
 
 
-_conv_cache: dict = {}
-
-
 def _conv_matrix(weight: Tensor, dtype: torch.dtype, KP: int) -> Tensor:
     """[Cout, Cin, 3, 3] weight -> the [Cout, KP] GEMM operand of ops.im2col3x3s2_nhwc: column (ky * 3 + kx) * Cin + ci, zero padding
-    behind 9 Cin.  Cached like _conv1_matrix (per parameter version AND training pass)."""
-    key = (id(weight), dtype, KP)
-    ent = _conv_cache.get(key)
-    stamp = (weight._version, _train_pass, torch.is_grad_enabled() and weight.requires_grad, weight.data_ptr())
-    if ent is not None and ent[0]() is weight and ent[1] == stamp:
-        return ent[2]
-    with torch.no_grad():
+    behind 9 Cin.  A derived operand: that of an eval-mode conv + BatchNorm fold goes with the folded weight."""
+    def build():
         Co, Ci = weight.shape[0], weight.shape[1]
         m = torch.zeros(Co, KP, device=weight.device, dtype=dtype)
         m[:, :9 * Ci] = weight.detach().permute(0, 2, 3, 1).reshape(Co, 9 * Ci)
-    # dropped with `weight`: the eval-mode conv + BatchNorm fold builds a NEW folded weight after every training pass, whose matrix would
-    # otherwise stay cached under the dead tensor's id (~5 MB per train -> eval cycle for Base)
-    _cache_filled()
-    _conv_cache[key] = (weakref.ref(weight, lambda _r, k=key: _conv_cache.pop(k, None)), stamp, m)
-    return m
+        return m
+    return derived(weight, ("conv", dtype, KP), (weight,), build)
 
 
 class _Conv3x3s2Fn(torch.autograd.Function):
@@ -459,34 +441,25 @@ class _TailFn(torch.autograd.Function):
         return dx.to(xdt), dc.to(cdt), dg.to(gdt), dbeta.to(bdt), None, dW, db, None
 
 
-_tail_cache: dict = {}
-
-
 def _tail_infer(norm_c: nn.LayerNorm, bn: nn.BatchNorm2d, head: nn.Linear, xt: Tensor, c: Tensor, cd: torch.dtype) -> Tensor:
     """No-grad classifier tail (models/lemevit.py:815-835): logits = head(mean(BN_eval(x)) + mean(LayerNorm(c))).  The BatchNorm affine
-    (scale, shift), the fp32 LayerNorm affine and the padded classifier operands are cached until one of their source tensors changes."""
-    src = [bn.weight, bn.bias, bn.running_mean, bn.running_var, norm_c.weight, norm_c.bias, head.weight, head.bias]
-    ver = (_train_pass, cd) + tuple(-1 if t is None else t._version for t in src) + tuple(0 if t is None else t.data_ptr() for t in src)
-    key = (id(bn), id(head))
-    ent = _tail_cache.get(key)
-    if ent is None or ent[0] != ver:
-        with torch.no_grad():
-            a = torch.rsqrt(bn.running_var.float() + bn.eps)
-            if bn.weight is not None:
-                a = a * bn.weight.float()
-            b = -bn.running_mean.float() * a
-            if bn.bias is not None:
-                b = b + bn.bias.float()
-            N, K = head.weight.shape
-            Np = (N + 7) // 8 * 8
-            Wp = torch.zeros((Np, K), device=xt.device, dtype=cd); Wp[:N] = head.weight.detach().to(cd)
-            bp = torch.zeros((Np,), device=xt.device, dtype=torch.float32)
-            if head.bias is not None:
-                bp[:N] = head.bias.detach().float()
-            ent = (ver, a.contiguous(), b.contiguous(), norm_c.weight.detach().float().contiguous(), norm_c.bias.detach().float().contiguous(), Wp, bp, N)
-        _cache_filled()
-        _tail_cache[key] = ent
-    _, a, b, g32, b32, Wp, bp, N = ent
+    (scale, shift), the fp32 LayerNorm affine and the padded classifier operands are derived operands."""
+    def build():
+        a = torch.rsqrt(bn.running_var.float() + bn.eps)
+        if bn.weight is not None:
+            a = a * bn.weight.float()
+        b = -bn.running_mean.float() * a
+        if bn.bias is not None:
+            b = b + bn.bias.float()
+        N, K = head.weight.shape
+        Np = (N + 7) // 8 * 8
+        Wp = torch.zeros((Np, K), device=xt.device, dtype=cd); Wp[:N] = head.weight.detach().to(cd)
+        bp = torch.zeros((Np,), device=xt.device, dtype=torch.float32)
+        if head.bias is not None:
+            bp[:N] = head.bias.detach().float()
+        return a.contiguous(), b.contiguous(), norm_c.weight.detach().float().contiguous(), norm_c.bias.detach().float().contiguous(), Wp, bp, N
+    src = (bn.weight, bn.bias, bn.running_mean, bn.running_var, norm_c.weight, norm_c.bias, head.weight, head.bias)
+    a, b, g32, b32, Wp, bp, N = derived(head, ("tail", cd), src, build)
     cc = c.detach().to(cd).contiguous()
     (cn,), _ = ops.layernorm_fwd_multi([cc], g32, b32, float(norm_c.eps), want_stats=False)
     pooled = ops.token_mean2_affine_fwd(xt.detach().to(cd).contiguous(), cn, a, b)
@@ -515,41 +488,42 @@ def _is_meta_mlp(seq: nn.Module, c: Tensor, cd: torch.dtype) -> bool:
             and l1.weight.dtype == torch.float32 and c.dtype in (torch.float32, torch.bfloat16))
 
 
+def _meta_mlp(mlp: nn.Module, c: Tensor, cd: torch.dtype) -> Tensor:
+    if _is_meta_mlp(mlp, c, cd):
+        l1, n1, _, l2, n2 = mlp
+        return _MetaMLPFn.apply(c, l1.weight, l1.bias, n1.weight, n1.bias, l2.weight, l2.bias, n2.weight, n2.bias, n1.eps, n2.eps, cd)
+    return mlp(c)
+
+
 def _is_stem_conv1(m: nn.Module, x: Tensor) -> bool:
     return (isinstance(m, nn.Conv2d) and m.in_channels == 3 and m.kernel_size == (3, 3) and m.stride == (2, 2) and m.padding == (1, 1)
             and m.dilation == (1, 1) and m.groups == 1 and m.out_channels % 8 == 0 and m.padding_mode == "zeros" and not x.requires_grad
             and x.dtype in (torch.float32, torch.bfloat16))
 
 
+def _conv_bn_sources(conv: nn.Conv2d, bn: nn.BatchNorm2d):
+    return conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var
+
+
+def _fold_conv_bn(conv: nn.Conv2d, bn: nn.BatchNorm2d, dtype: torch.dtype):
+    """(weight, bias, fp32 bias) of conv followed by eval-mode BatchNorm (no autograd)."""
+    s = (bn.running_var.float() + bn.eps).rsqrt()
+    if bn.weight is not None:
+        s = s * bn.weight.float()
+    w = conv.weight.float() * s[:, None, None, None]
+    b0 = conv.bias.float() if conv.bias is not None else torch.zeros_like(s)
+    b = (b0 - bn.running_mean.float()) * s
+    if bn.bias is not None:
+        b = b + bn.bias.float()
+    return w.to(dtype).contiguous(memory_format=torch.channels_last), b.to(dtype), b.contiguous()
+
+
 def _folded_conv_bn(conv: nn.Conv2d, bn: nn.BatchNorm2d, dtype: torch.dtype):
-    """(weight, bias, fp32 bias) of conv followed by eval-mode BatchNorm, cached until any of the six source tensors changes."""
-    src = [conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var]
-    # _train_pass: fused optimizers and the native BatchNorm kernel update these tensors in place WITHOUT bumping
-    # ``_version`` (see compute_copy), so a fold made before a training pass must not survive it
-    ver = (_train_pass,) + tuple(-1 if t is None else t._version for t in src) + tuple(0 if t is None else t.data_ptr() for t in src)
-    key = (id(conv), id(bn), dtype)
-    ent = _fold_cache.get(key)
-    if ent is not None and ent[0] == ver:
-        return ent[1], ent[2], ent[3]
-    with torch.no_grad():
-        s = (bn.running_var.float() + bn.eps).rsqrt()
-        if bn.weight is not None:
-            s = s * bn.weight.float()
-        w = conv.weight.float() * s[:, None, None, None]
-        b0 = conv.bias.float() if conv.bias is not None else torch.zeros_like(s)
-        b = (b0 - bn.running_mean.float()) * s
-        if bn.bias is not None:
-            b = b + bn.bias.float()
-        w = w.to(dtype).contiguous(memory_format=torch.channels_last)
-        b32 = b.contiguous()
-        b = b.to(dtype)
-    _cache_filled()
-    _fold_cache[key] = (ver, w, b, b32)
-    return w, b, b32
+    """_fold_conv_bn as a derived operand."""
+    return derived(conv, ("conv_bn", dtype), _conv_bn_sources(conv, bn), lambda: _fold_conv_bn(conv, bn, dtype))
 
 
 _STEM = os.environ.get("LMV_STEM", "1") != "0"          # 0: the stem as im2col + GEMM launches (A/B runs)
-_stem_cache: dict = {}
 
 
 def _stem_applies(mods, x: Tensor, cd: torch.dtype) -> bool:
@@ -568,21 +542,16 @@ def _stem_applies(mods, x: Tensor, cd: torch.dtype) -> bool:
 
 def _stem_fused(mods, x: Tensor, cd: torch.dtype) -> Tensor:
     c1, b1, _, c2, b2 = mods
-    w1, _, b1f = _folded_conv_bn(c1, b1, cd)
-    w2, _, b2f = _folded_conv_bn(c2, b2, cd)
-    key = (id(c1), id(c2))
-    ent = _stem_cache.get(key)
-    if ent is not None and ent[3]() is not c1:          # a recycled id: the module the entry was built for is gone
-        ent = None
-    if ent is None or ent[0] is not w1 or ent[1] is not w2:          # (the folds are new tensors whenever a source tensor changed)
+
+    def build():
+        (w1, _, b1f), (w2, _, b2f) = _fold_conv_bn(c1, b1, cd), _fold_conv_bn(c2, b2, cd)
         Cm = w1.shape[0]
         w1m = torch.zeros(Cm, 32, device=w1.device, dtype=cd)
         w1m[:, :27] = w1.reshape(Cm, 27)
         w2m = w2.permute(0, 2, 3, 1).reshape(w2.shape[0], 9 * Cm).contiguous()
-        ent = (w1, w2, ops.stem_pack(w1m, w2m), weakref.ref(c1, lambda _r, k=key: _stem_cache.pop(k, None)))          # evicted with the module, as _conv_cache / _sstage_cache
-        _cache_filled()
-        _stem_cache[key] = ent
-    y = ops.stem_fwd(x, ent[2], b1f, b2f, w1.shape[0], w2.shape[0])
+        return ops.stem_pack(w1m, w2m), b1f, b2f, Cm, w2.shape[0]
+    wpk, b1f, b2f, Cm, Co = derived(c1, ("stem", cd), _conv_bn_sources(c1, b1) + _conv_bn_sources(c2, b2), build)
+    y = ops.stem_fwd(x, wpk, b1f, b2f, Cm, Co)
     return y.permute(0, 3, 1, 2)                     # NCHW-shaped, channels-last-strided: _to_tokens takes it without a copy
 
 
@@ -973,7 +942,6 @@ launches = _LaunchContext()
 _DSTAGE = os.environ.get("LMV_DSTAGE", "1") != "0"        # 0: stages of D blocks on the per-block schedule (A/B runs)
 _INFER_SIDE = os.environ.get("LMV_INFER_SIDE", "1") != "0"        # inference: the meta-token MLP of a stage on a forked stream next to its transition convolution (0: in line)
 _INFER_TAIL_PARTS = int(os.environ.get("LMV_INFER_TAIL_PARTS", "2"))      # inference: sub-batches of the per-launch stages behind the last persistent stage kernel (1: whole batch)
-_sstage_cache: dict = {}
 
 
 def _sstage_applies(stage, xt: Tensor, c: Tensor, H: int, W: int) -> Optional[str]:
@@ -1015,29 +983,23 @@ def _whole_stage_fwd(whole: str, xt: Tensor, c: Tensor, packed, H: int, W: int):
 
 
 def _sstage_packed(stage, kind: str = "S") -> "ops.SStagePacked":
-    """The stage's parameters in the kernel's layout, cached per parameter version (and per training pass, see compute_copy)."""
-    key = (id(stage), kind)          # one stage resolves to different kernels at different resolutions ("S" at 14 x 14, "S2" at 24 x 24): one pack per (stage, kind)
-    plist = [p for blk in stage for p in blk._params().values()]
-    stamp = tuple(p._version for p in plist) + tuple(id(p) for p in plist) + (_train_pass,)
-    ent = _sstage_cache.get(key)
-    if ent is not None and ent[0]() is stage and ent[1] == stamp:
-        return ent[2]
-    blocks = []
-    for blk in stage:
-        P = blk._params()
-        d = {}
-        for n in {"S": ops.SSTAGE_NAMES, "S2": ops.SSTAGE_NAMES, "D": ops.DSTAGE_NAMES, "D2": ops.D2STAGE_NAMES, "C": ops.CSTAGE_NAMES}[kind]:
-            if n == "pos_embed.weight":
-                d[n] = P[n].detach().float().reshape(P[n].shape[0], 9).contiguous()
-            elif _is_matrix(n):
-                d[n] = compute_copy(P[n], torch.bfloat16)
-            else:
-                d[n] = compute_copy(P[n], torch.float32)
-        blocks.append(d)
-    packed = {"S": ops.sstage_pack, "S2": ops.s2stage_pack, "D": ops.dstage_pack, "D2": ops.d2stage_pack, "C": ops.cstage_pack}[kind](blocks, stage[0].attn.num_heads)
-    _cache_filled()
-    _sstage_cache[key] = (weakref.ref(stage, lambda _r, k=key: _sstage_cache.pop(k, None)), stamp, packed)
-    return packed
+    """The stage's parameters in the kernel's layout, a derived operand.  One stage resolves to different kernels at different resolutions
+    ("S" at 14 x 14, "S2" at 24 x 24): one pack per (stage, kind)."""
+    def build():
+        blocks = []
+        for blk in stage:
+            P = blk._params()
+            d = {}
+            for n in {"S": ops.SSTAGE_NAMES, "S2": ops.SSTAGE_NAMES, "D": ops.DSTAGE_NAMES, "D2": ops.D2STAGE_NAMES, "C": ops.CSTAGE_NAMES}[kind]:
+                if n == "pos_embed.weight":
+                    d[n] = P[n].detach().float().reshape(P[n].shape[0], 9).contiguous()
+                elif _is_matrix(n):
+                    d[n] = compute_copy(P[n], torch.bfloat16)
+                else:
+                    d[n] = compute_copy(P[n], torch.float32)
+            blocks.append(d)
+        return {"S": ops.sstage_pack, "S2": ops.s2stage_pack, "D": ops.dstage_pack, "D2": ops.d2stage_pack, "C": ops.cstage_pack}[kind](blocks, stage[0].attn.num_heads)
+    return derived(stage, ("stage", kind), [p for blk in stage for p in blk._params().values()], build)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1054,7 +1016,7 @@ class _AttnModuleFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, kind, x, c, *params):
-        new_training_pass()                      # parameters may have been updated in place since the last call (see compute_copy)
+        new_training_pass()                      # parameters may have been updated in place since the last call (see derived)
         cd = x.dtype
         x = x.contiguous()
         c = None if c is None else c.contiguous()
@@ -1323,9 +1285,13 @@ class LeMeBlock(nn.Module):
             self._pcache = OrderedDict((n, table[n]) for n in PARAM_NAMES[self.attn_type])
         return self._pcache
 
-    def _apply(self, fn, *a, **k):     # .to()/.cuda() may replace Parameters
+    def _apply(self, fn, *a, **k):     # .to()/.cuda()/.to_empty() may replace Parameters
         self._pcache = None
         return super()._apply(fn, *a, **k)
+
+    def _load_from_state_dict(self, *a, **k):     # load_state_dict(..., assign=True) replaces them (called before the submodules load)
+        self._pcache = None
+        return super()._load_from_state_dict(*a, **k)
 
     @property
     def kind(self) -> str:
@@ -1350,7 +1316,7 @@ class LeMeBlock(nn.Module):
     def forward(self, x: Tensor, c: Tensor) -> Tuple[Tensor, Tensor]:
         """Reference signature: x NCHW in / out (models/lemevit.py:652)."""
         if torch.is_grad_enabled():
-            new_training_pass()        # parameters may have been updated in place since the last call (see compute_copy)
+            new_training_pass()        # parameters may have been updated in place since the last call (see derived)
         B, C, H, W = x.shape
         xt = x.permute(0, 2, 3, 1).reshape(B, H * W, C).contiguous()
         xt, c = self.forward_tokens(xt, c.contiguous(), H, W)
@@ -1573,11 +1539,11 @@ class LeMeViT(nn.Module):
                 and "_masks" not in blk.__dict__]
         if not plan:
             return {}
-        nmask = sum(n for _, n in plan)
-        keep = getattr(self, "_dp_keep", None)      # cached on the device: no per-step host-to-device copy
-        if keep is None or keep.shape[0] != nmask or keep.device != torch.device(device):
-            keep = torch.tensor([1.0 - blk.drop_prob for blk, n in plan for _ in range(n)], dtype=torch.float32, device=device)
-            self._dp_keep = keep
+        probs = [1.0 - blk.drop_prob for blk, n in plan for _ in range(n)]
+        ent = self.__dict__.get("_dp_keep")      # (probabilities, their device copy): no per-step host-to-device copy
+        if ent is None or ent[0] != probs or ent[1].device != torch.device(device):
+            ent = self._dp_keep = (probs, torch.tensor(probs, dtype=torch.float32, device=device))
+        keep = ent[1]
         u = torch.rand((keep.shape[0], B), device=device, dtype=torch.float32)
         scale = (u < keep[:, None]).to(torch.float32) / keep[:, None]
         out, r = {}, 0
@@ -1612,24 +1578,11 @@ class LeMeViT(nn.Module):
     def _meta_tokens_for(self, i: int, c: Tensor, hoist: bool, B: int, cd: torch.dtype) -> Tensor:
         """The meta tokens entering stage i: meta_token_downsample[i] (models/lemevit.py:731-743, :812, :819)."""
         mlp = self.meta_token_downsample[i]
-        pre = None
         if hoist and not torch.is_grad_enabled() and not self.training:
-            # inference: the first meta-token MLP sees the learned meta tokens only (models/lemevit.py:731-743, :812, :833) -- a constant of the weights, cached per parameter version
-            plist = [self.meta_tokens] + list(mlp.parameters())
-            stamp = (_train_pass, cd) + tuple(p._version for p in plist) + tuple(p.data_ptr() for p in plist)
-            ent = getattr(self, "_meta0_cache", None)
-            if ent is not None and ent[0] == stamp:
-                pre = ent[1]
-        if pre is not None:
-            c = pre
-        elif _is_meta_mlp(mlp, c, cd):
-            l1, n1, _, l2, n2 = mlp
-            c = _MetaMLPFn.apply(c, l1.weight, l1.bias, n1.weight, n1.bias, l2.weight, l2.bias, n2.weight, n2.bias, n1.eps, n2.eps, cd)
+            # inference: the first meta-token MLP sees the learned meta tokens only (models/lemevit.py:731-743, :812, :833) -- a constant of the weights
+            c = derived(self, ("meta0", cd), [self.meta_tokens, *mlp.parameters()], lambda: _meta_mlp(mlp, c, cd).detach())
         else:
-            c = mlp(c)
-        if pre is None and hoist and not torch.is_grad_enabled() and not self.training:
-            self._meta0_cache = (stamp, c.detach())
-            _cache_filled()
+            c = _meta_mlp(mlp, c, cd)
         if hoist:
             c = c.expand(B, -1, -1)
         return c.to(cd).contiguous()
@@ -1786,13 +1739,7 @@ class LeMeViTBackbone(LeMeViT):
             if i == 0 or not isinstance(self.downsample_layers[i], nn.Identity):
                 x = self._run_downsample(self.downsample_layers[i], x if xt is None else self._to_nchw(xt, H, W))
                 xt, H, W = self._to_tokens(x, cd)
-            mlp = self.meta_token_downsample[i]
-            if _is_meta_mlp(mlp, c, cd):
-                l1, n1, _, l2, n2 = mlp
-                c = _MetaMLPFn.apply(c, l1.weight, l1.bias, n1.weight, n1.bias, l2.weight, l2.bias, n2.weight, n2.bias, n1.eps, n2.eps, cd)
-            else:
-                c = mlp(c)
-            c = c.to(cd).contiguous()
+            c = _meta_mlp(self.meta_token_downsample[i], c, cd).to(cd).contiguous()
             for blk in self.stages[i]:
                 xt, c = blk.forward_tokens(xt, c, H, W, masks=all_masks.get(id(blk)) if all_masks else None)
             if i > 0:

@@ -2,7 +2,7 @@
 
 ``torch.optim.AdamW(fused=True)`` walks the ~450 block parameters of LeMeViT-Base in 16 multi-tensor launches, and every
 training pass then re-casts the 146 weight matrices to bf16 for the kernels (fused optimizers update in place without
-bumping ``Tensor._version``, so those casts cannot be cached: see model.compute_copy).  Here the block parameters live in
+bumping ``Tensor._version``, so those casts cannot be cached: see model.derived).  Here the block parameters live in
 ONE flat fp32 buffer, their gradients in ONE flat fp32 buffer that the block backward writes straight into
 (``_BlockFn`` accumulates into ``p.grad`` and hands autograd ``None``), and one launch of ``lmv_adamw_flat`` updates
 everything and refreshes the bf16 operand copies in the same pass.  The handful of non-block parameters (stem, stage
@@ -13,6 +13,7 @@ gradients written in place -- wrap the model in DDP with a regular optimizer ins
 """
 from __future__ import annotations
 
+import weakref
 from typing import Callable, Dict, Iterable, List, Optional, Tuple
 
 import torch
@@ -244,22 +245,23 @@ class ModelEma:
             if k not in src:
                 raise KeyError(k)
             (self._pairs_f if v.dtype.is_floating_point else self._pairs_i).append((v, k))
-        self._src_cache: Optional[Tuple[int, List[Tensor], List[Tensor]]] = None
+        self._src_cache: Optional[Tuple[weakref.ref, List[Tensor], List[Tensor]]] = None
 
     def _sources(self, model: nn.Module) -> Tuple[List[Tensor], List[Tensor]]:
-        """The source tensors of the non-flat entries, looked up ONCE per source module (parameters and buffers are updated in place, so the tensors stay the same objects):
-        the reference's flow builds the EMA from the bare model and then calls update() with the DistributedDataParallel wrapper (main.py:316, engine.py) -- the wrapper's
-        state_dict keys carry a 'module.' prefix, so the wrapper is peeled first (timm's ModelEmaV2 zips the two state_dicts positionally for the same reason)."""
+        """The Parameter and buffer objects behind the non-flat entries, looked up ONCE per source module: they are updated in place, and update() reads
+        their current storage (``p.data = t`` re-homes a Parameter -- FlatAdamW built after the first update does -- without replacing it).  The reference's flow builds
+        the EMA from the bare model and then calls update() with the DistributedDataParallel wrapper (main.py:316, engine.py) -- the wrapper's state_dict keys carry a
+        'module.' prefix, so the wrapper is peeled first (timm's ModelEmaV2 zips the two state_dicts positionally for the same reason)."""
         bare = model
         while hasattr(bare, "module") and isinstance(getattr(bare, "module"), nn.Module) and not isinstance(bare, type(self.module)):
             bare = bare.module
         ent = self._src_cache
-        if ent is None or ent[0] != id(bare):
-            src = bare.state_dict()
+        if ent is None or ent[0]() is not bare:
+            src = bare.state_dict(keep_vars=True)
             missing = [k for _, k in self._pairs_f + self._pairs_i if k not in src]
             if missing:
                 raise KeyError(f"ModelEma.update: the model has no state_dict entry {missing[0]!r} (and {len(missing) - 1} more)")
-            ent = self._src_cache = (id(bare), [src[k] for _, k in self._pairs_f], [src[k] for _, k in self._pairs_i])
+            ent = self._src_cache = (weakref.ref(bare), [src[k] for _, k in self._pairs_f], [src[k] for _, k in self._pairs_i])
         return ent[1], ent[2]
 
     @torch.no_grad()

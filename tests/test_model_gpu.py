@@ -357,9 +357,10 @@ def test_attention_modules_are_differentiable(kind, dtype, tol):
     assert (o1.detach().float() - o2.float()).abs().max().item() <= 2e-2 * o2.float().abs().max().item()
 
 
-def test_one_model_two_resolutions(monkeypatch):
+def test_one_model_two_resolutions_packs_per_stage(monkeypatch):
     """stage 3 of one model instance resolves to the "S" kernel (sstage layout) at 14 x 14 tokens and to the "S2" kind of the D-stage kernel (dstage layout)
-    at 24 x 24; the packed-parameter cache is keyed by (stage, kind) and the ops refuse a foreign pack.  224 -> 384 -> 224 on one instance, each against the per-block schedule."""
+    at 24 x 24; that stage instance holds one derived pack per kind (model.derived, tag ("stage", kind)) and the ops refuse a foreign pack.  224 -> 384 -> 224 on one instance,
+    each against the per-block schedule."""
     import lemevit_amd.model as M
     m = _model("lemevit_tiny", 10, 5).eval()
     imgs = {r: det_tensor((2, 3, r, r), f"tworez.{r}", 2).to(DEV) for r in (224, 384)}
@@ -375,7 +376,7 @@ def test_one_model_two_resolutions(monkeypatch):
             torch.cuda.synchronize()
             d = (out - ref[r]).abs().max().item() / ref[r].abs().max().item()
             assert d <= 3e-2, (r, d)
-    kinds = sorted(k[1] for k in M._sstage_cache if isinstance(k, tuple))
+    kinds = sorted(tag[1] for owner, tag in M._derived if owner == id(m.stages[3]) and tag[0] == "stage")
     assert "S" in kinds and "S2" in kinds, kinds
 
 
