@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define LMV_ABI_VERSION 12
+#define LMV_ABI_VERSION 13
 
 enum { LMV_F32 = 0, LMV_BF16 = 1 };
 enum {
@@ -310,6 +310,17 @@ int lmv_cast(const void* src, int src_dtype, void* dst, int dst_dtype, int64_t n
  * lmv_linear_fwd(patches, W[Cout, 32]) is then the convolution (NHWC output), lmv_linear_dw its weight gradient. */
 int lmv_im2col3x3s2_c3(const void* x, int x_dtype, void* patches, int dtype, int B, int H, int W, int64_t sb, int64_t sc, int64_t sh,
                        int64_t sw, void* stream);
+/* The same convolution for ANY channel count, and its data gradient (csrc/conv1.hip; the Cin == 3 launches of the model stay on lmv_im2col3x3s2_c3):
+ *   lmv_im2col3x3s2_nchw: patches[(b, ho, wo)][ci * 9 + ky * 3 + kx] = x[b][ci][2 ho - 1 + ky][2 wo - 1 + kx] (zero outside the image), columns 9 Cin .. KP - 1 zero,
+ *     KP >= 9 Cin a multiple of 32 -> [B * ceil(H/2) * ceil(W/2), KP] in `dtype`; x ([B, Cin, H, W], fp32 or bf16) is read through its element strides.
+ *   lmv_conv3x3s2_nchw_dx: dx[b, ci, h, w] = sum over co and the taps (ky, kx) with h + 1 - ky = 2 ho, w + 1 - kx = 2 wo, ho < Ho, wo < Wo of
+ *     dy[(b, ho, wo), co] * wm[co, ci * 9 + ky * 3 + kx] -- ONE launch, no patch-gradient matrix.  dy [B Ho Wo, Co] and wm [Co, KP] in `dtype` (16-byte aligned, Co % 8 == 0,
+ *     Co <= 128 for bf16 / 64 for fp32), fp32 accumulation (MFMA), dx in `dx_dtype` written through the element strides (sb, sc, sh, sw) of a [B, Cin, H, W] image: every
+ *     element exactly once (no pre-zeroed buffer, no atomics), every sum in one fixed order -- two launches agree bit for bit. */
+int lmv_im2col3x3s2_nchw(const void* x, int x_dtype, void* patches, int dtype, int B, int Cin, int H, int W, int KP, int64_t sb, int64_t sc, int64_t sh, int64_t sw,
+                         void* stream);
+int lmv_conv3x3s2_nchw_dx(const void* dy, const void* wm, void* dx, int dx_dtype, int B, int Cin, int H, int W, int Co, int KP, int64_t sb, int64_t sc, int64_t sh,
+                          int64_t sw, int dtype, void* stream);
 int lmv_row_scale(const void* x, const float* scale, void* y, int64_t rows, int C, int rows_per_sample, int dtype, void* stream);
 /* The same for up to two row segments in ONE launch (the x and c gradients of a block, each with its own DropPath vector). */
 typedef struct lmv_row_scale_segment {

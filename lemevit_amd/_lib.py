@@ -17,7 +17,7 @@ LIB_PATH = os.environ.get("LMV_LIB_PATH") or os.path.join(_HERE, "csrc", "liblem
 
 LMV_F32, LMV_BF16 = 0, 1
 ACT_NONE, ACT_GELU, ACT_GELU_GRAD = 0, 1, 2
-ABI_VERSION = 12
+ABI_VERSION = 13
 
 
 class LinearProblem(C.Structure):
@@ -139,6 +139,8 @@ SIGNATURES = {
     "lmv_dca_core_fwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _Z, _I, _P]),
     "lmv_cast": (_I, [_P, _I, _P, _I, _L, _P]),
     "lmv_im2col3x3s2_c3": (_I, [_P, _I, _P, _I, _I, _I, _I, _L, _L, _L, _L, _P]),
+    "lmv_im2col3x3s2_nchw": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _L, _L, _L, _L, _P]),
+    "lmv_conv3x3s2_nchw_dx": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _L, _L, _L, _L, _I, _P]),
     "lmv_row_scale_multi": (_I, [_P, _I, _I, _I, _P]),
     "lmv_transpose_batch": (_I, [C.POINTER(TransposeSeg), _I, _I, _P]),
     "lmv_row_scale": (_I, [_P, _P, _P, _L, _I, _I, _I, _P]),

@@ -137,46 +137,58 @@ def block_folds(kind: str, params: "Dict[str, Tensor]", dtype: torch.dtype):
 
 
 def _conv1_matrix(weight: Tensor, dtype: torch.dtype) -> Tensor:
-    """[Cout, 3, 3, 3] stem weight -> the [Cout, 32] GEMM operand of ops.im2col3x3s2_c3 (columns 27..31 zero), a derived operand."""
+    """[Cout, Cin, 3, 3] stem weight -> the [Cout, KP] GEMM operand of ops.im2col3x3s2_c3 / _nchw (column ci * 9 + ky * 3 + kx: the weight's own order; KP = 9 Cin rounded up to
+    a multiple of 32, the columns behind 9 Cin zero; Cin == 3: [Cout, 32]), a derived operand."""
     def build():
-        m = torch.zeros(weight.shape[0], 32, device=weight.device, dtype=dtype)
-        m[:, :27] = weight.detach().reshape(weight.shape[0], 27)
+        K = 9 * weight.shape[1]
+        m = torch.zeros(weight.shape[0], (K + 31) // 32 * 32, device=weight.device, dtype=dtype)
+        m[:, :K] = weight.detach().reshape(weight.shape[0], K)
         return m
     return derived(weight, ("conv1", dtype), (weight,), build)
 
 
 class _StemConv1Fn(torch.autograd.Function):
-    """First convolution of the stem (models/lemevit.py:713: 3 -> C/2 channels, 3x3, stride 2, padding 1) as im2col + the
-    block GEMM kernels: y[NHWC] = patches @ W^T + b, dW = dY^T @ patches.  The image batch needs no gradient.  (MIOpen's
-    implicit-GEMM kernel for this 27-deep reduction takes 455 us at B = 128; this is ~5x faster, weight gradient included.)"""
+    """First convolution of the stem (models/lemevit.py:713: in_chans -> C/2 channels, 3x3, stride 2, padding 1) as im2col + the
+    block GEMM kernels: y[NHWC] = patches @ W^T + b, dW = dY^T @ patches; three channels take the 32-wide patch kernel, any other count
+    (1 .. 32, not a multiple of 8) ops.im2col3x3s2_nchw.  An image that requires grad gets dX from ONE ops.conv3x3s2_nchw_dx launch (no patch-gradient
+    matrix); one that does not costs nothing extra.  (MIOpen's implicit-GEMM kernel for the 27-deep reduction takes 455 us at B = 128; this is ~5x
+    faster, weight gradient included.)"""
 
     @staticmethod
     def forward(ctx, x, weight, bias, cd, gelu=False):
         """gelu=True (inference only, BatchNorm folded into the weights): the GELU behind the first stem BatchNorm rides the GEMM epilogue."""
-        B, _, H, W = x.shape
+        B, Ci, H, W = x.shape
         Ho, Wo, Co = (H + 1) // 2, (W + 1) // 2, weight.shape[0]
-        patches = ops.im2col3x3s2_c3(x, cd)
+        Wm = _conv1_matrix(weight, cd)
+        patches = ops.im2col3x3s2_c3(x, cd) if Ci == 3 else ops.im2col3x3s2_nchw(x, cd, Wm.shape[1])
         y = torch.empty(B * Ho * Wo, Co, device=x.device, dtype=cd)
         b32 = None if bias is None else compute_copy(bias, torch.float32)
-        ops.linear_fwd([Prob(patches, _conv1_matrix(weight, cd), y, bias=b32)], Co, 32, ops.ACT_GELU if gelu else ops.ACT_NONE)
+        ops.linear_fwd([Prob(patches, Wm, y, bias=b32)], Co, Wm.shape[1], ops.ACT_GELU if gelu else ops.ACT_NONE)
         assert not (gelu and torch.is_grad_enabled() and weight.requires_grad), "the fused GELU epilogue has no backward"
-        ctx.save_for_backward(patches)
+        if ctx.needs_input_grad[0]:
+            ctx.save_for_backward(patches, Wm, x)
+        else:
+            ctx.save_for_backward(patches)
         ctx.meta = (weight.shape, weight.dtype, None if bias is None else bias.dtype)
         return y.view(B, Ho, Wo, Co).permute(0, 3, 1, 2)            # NCHW-shaped, channels-last-strided: no copy
 
     @staticmethod
     def backward(ctx, dy):
-        (patches,) = ctx.saved_tensors
+        patches = ctx.saved_tensors[0]
         wshape, wdt, bdt = ctx.meta
-        Co = wshape[0]
+        Co, KP = wshape[0], patches.shape[1]
         g = dy.permute(0, 2, 3, 1).contiguous().view(-1, Co)
         if g.dtype != patches.dtype:
             g = g.to(patches.dtype)
-        dwm = torch.zeros(Co, 32, device=g.device, dtype=torch.float32)
+        dwm = torch.zeros(Co, KP, device=g.device, dtype=torch.float32)
         db = torch.zeros(Co, device=g.device, dtype=torch.float32)
-        ops.linear_dw([Prob(g, patches, dwm, bias_grad=db)], Co, 32)
-        dw = dwm[:, :27].reshape(wshape).to(wdt)
-        return None, dw, (None if bdt is None else db.to(bdt)), None, None
+        ops.linear_dw([Prob(g, patches, dwm, bias_grad=db)], Co, KP)
+        dw = dwm[:, :9 * wshape[1]].reshape(wshape).to(wdt)
+        dx = None
+        if ctx.needs_input_grad[0]:
+            _, Wm, x = ctx.saved_tensors
+            dx = ops.conv3x3s2_nchw_dx(g, Wm, like=x)
+        return dx, dw, (None if bdt is None else db.to(bdt)), None, None
 
 
 def _conv_matrix(weight: Tensor, dtype: torch.dtype, KP: int) -> Tensor:
@@ -496,8 +508,9 @@ def _meta_mlp(mlp: nn.Module, c: Tensor, cd: torch.dtype) -> Tensor:
 
 
 def _is_stem_conv1(m: nn.Module, x: Tensor) -> bool:
-    return (isinstance(m, nn.Conv2d) and m.in_channels == 3 and m.kernel_size == (3, 3) and m.stride == (2, 2) and m.padding == (1, 1)
-            and m.dilation == (1, 1) and m.groups == 1 and m.out_channels % 8 == 0 and m.padding_mode == "zeros" and not x.requires_grad
+    """The stem's first convolution on an image: 1 .. 32 input channels, not a multiple of 8 (those are channels-last feature maps to _Conv3x3s2Fn)."""
+    return (isinstance(m, nn.Conv2d) and 1 <= m.in_channels <= 32 and m.in_channels % 8 != 0 and m.kernel_size == (3, 3) and m.stride == (2, 2) and m.padding == (1, 1)
+            and m.dilation == (1, 1) and m.groups == 1 and m.out_channels % 8 == 0 and m.padding_mode == "zeros"
             and x.dtype in (torch.float32, torch.bfloat16))
 
 
@@ -1323,6 +1336,11 @@ class LeMeBlock(nn.Module):
         return xt.reshape(B, H, W, C).permute(0, 3, 1, 2), c
 
 
+def _no_conv_kernel(m: nn.Module, x: Tensor) -> str:
+    return (f"lemevit_amd: no native kernel for {m} on a {tuple(x.shape)} {x.dtype} map (the library carries the 3 x 3 / stride-2 / padding-1 convolutions of the LeMeViT stem and "
+            "stage transitions: 1 .. 32 input channels for the image, otherwise channels a multiple of 8, fp32 / bf16)")
+
+
 def _downsample_mods(mods: List[nn.Module], x: Tensor, cd: torch.dtype, fold: bool, ck: Optional[dict] = None) -> Tensor:
     """The layers of LeMeViT._run_downsample on the native kernels.  ck: see _bn_train (the backward recompute takes the training-mode
     BatchNorms its forward pass took, by module index)."""
@@ -1341,8 +1359,7 @@ def _downsample_mods(mods: List[nn.Module], x: Tensor, cd: torch.dtype, fold: bo
                 i += 2
             else:
                 # (no vendor-library convolution behind the native ones: the stock PyTorch-ROCm column lives in tools/stock_eager.py)
-                raise NotImplementedError(f"lemevit_amd: no native kernel for {m} on a {tuple(x.shape)} {x.dtype} map (the library carries the 3 x 3 / stride-2 / padding-1 "
-                                          "convolutions of the LeMeViT stem and stage transitions, channels a multiple of 8, fp32 / bf16)")
+                raise NotImplementedError(_no_conv_kernel(m, x))
         elif _is_stem_conv1(m, x) and cd in (torch.float32, torch.bfloat16):
             x = _StemConv1Fn.apply(x, m.weight, m.bias, cd)
             i += 1
@@ -1355,7 +1372,7 @@ def _downsample_mods(mods: List[nn.Module], x: Tensor, cd: torch.dtype, fold: bo
             i += 2 if gelu else 1
         else:
             if isinstance(m, nn.Conv2d):
-                raise NotImplementedError(f"lemevit_amd: no native kernel for {m} on a {tuple(x.shape)} {x.dtype} map (see above)")
+                raise NotImplementedError(_no_conv_kernel(m, x))
             x = m(x)          # (element-wise glue of a caller-built Sequential: activation, Identity, an eval-mode normalisation under autograd)
             i += 1
     return x

@@ -479,6 +479,32 @@ def im2col3x3s2_c3(x: Tensor, dtype: torch.dtype) -> Tensor:
     return out
 
 
+def im2col3x3s2_nchw(x: Tensor, dtype: torch.dtype, KP: Optional[int] = None) -> Tensor:
+    """[B, Cin, H, W] images (any strides, fp32 or bf16) -> [B * ceil(H/2) * ceil(W/2), KP] patch matrix in the weight's own column order
+    ci * 9 + ky * 3 + kx, columns 9 Cin .. KP - 1 zero (KP: a multiple of 32, default the smallest that holds 9 Cin)."""
+    B, C_, H, W = x.shape
+    KP = (9 * C_ + 31) // 32 * 32 if KP is None else KP
+    if not x.is_cuda:
+        raise RuntimeError("lemevit_amd: tensors must be on the GPU (no CPU fallback exists)")
+    out = torch.empty(B * ((H + 1) // 2) * ((W + 1) // 2), KP, device=x.device, dtype=dtype)
+    sb, sc, sh, sw = x.stride()
+    check(lib.lmv_im2col3x3s2_nchw(x.data_ptr(), dtype_code(x), _ptr(out), dtype_code(out), B, C_, H, W, KP, sb, sc, sh, sw, _stream()), "lmv_im2col3x3s2_nchw")
+    return out
+
+
+def conv3x3s2_nchw_dx(dy: Tensor, wm: Tensor, like: Tensor) -> Tensor:
+    """Data gradient of Conv2d(Cin, Co, 3, stride 2, padding 1) in one launch: dy [B * Ho * Wo, Co] and wm [Co, KP] (column ci * 9 + ky * 3 + kx) in the
+    compute type -> the gradient of the image `like` [B, Cin, H, W], with its shape, dtype and memory format (every element written once)."""
+    B, C_, H, W = like.shape
+    Co, KP = wm.shape
+    if dy.dtype != wm.dtype or dy.shape != (B * ((H + 1) // 2) * ((W + 1) // 2), Co):
+        raise ValueError(f"conv3x3s2_nchw_dx: dy {tuple(dy.shape)} {dy.dtype} does not match wm {tuple(wm.shape)} {wm.dtype} and the image {tuple(like.shape)}")
+    dx = torch.empty_like(like, memory_format=torch.preserve_format)          # (dense strides in the image's dimension order, also for a strided view)
+    sb, sc, sh, sw = dx.stride()
+    check(lib.lmv_conv3x3s2_nchw_dx(_ptr(dy), _ptr(wm), dx.data_ptr(), dtype_code(dx), B, C_, H, W, Co, KP, sb, sc, sh, sw, dtype_code(dy), _stream()), "lmv_conv3x3s2_nchw_dx")
+    return dx
+
+
 def im2col3x3s2_nhwc(x: Tensor, KP: int) -> Tensor:
     """x [B, H, W, C] (NHWC, contiguous) -> [B * ceil(H/2) * ceil(W/2), KP] patch matrix of a 3x3 / stride-2 / pad-1 convolution."""
     B, H, W, C_ = x.shape

@@ -65,7 +65,27 @@ def load_checkpoint(model: torch.nn.Module, path: str, strict: bool = True):
             if k.startswith(prefix):
                 k = k[len(prefix):]
         clean[k] = v
+    _adapt_input_conv(model, clean)
     return model.load_state_dict(clean, strict=strict)
+
+
+_INPUT_CONV = "downsample_layers.0.0.weight"
+
+
+def _adapt_input_conv(model: torch.nn.Module, sd: dict) -> None:
+    """An RGB checkpoint into an in_chans = N model (timm's adapt_input_conv, applied to the stem's first convolution and only when the channel counts
+    differ): N == 1 sums the three input channels; otherwise they are repeated ceil(N / 3) times, cut to N and scaled by 3 / N."""
+    w = sd.get(_INPUT_CONV)
+    own = model.state_dict().get(_INPUT_CONV)
+    if w is None or own is None or w.dim() != 4 or w.shape[1] != 3 or own.shape[1] == 3 or w.shape[0] != own.shape[0] or w.shape[2:] != own.shape[2:]:
+        return
+    n = own.shape[1]
+    wf = w.float()
+    if n == 1:
+        wf = wf.sum(dim=1, keepdim=True)
+    else:
+        wf = wf.repeat(1, (n + 2) // 3, 1, 1)[:, :n] * (3.0 / n)
+    sd[_INPUT_CONV] = wf.to(w.dtype)
 
 
 def _variant(pretrained, kwargs, **hp):
