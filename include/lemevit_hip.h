@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define LMV_ABI_VERSION 13
+#define LMV_ABI_VERSION 14
 
 enum { LMV_F32 = 0, LMV_BF16 = 1 };
 enum {
@@ -58,12 +58,15 @@ int lmv_config_get(const char* key, int* value);
  *
  *   fwd : out[r, n] = res[r, n] + row_scale[r / rows_per_sample] * act(sum_k a[r,k] w[n,k] + bias[n])
  *         (act == LMV_ACT_GELU_GRAD: out[r, n] = row_scale * (sum_k a[r,k] w[n,k] + bias[n]) * gelu'(aux[r, n]), no residual: a dX through
- *          a TRANSPOSED weight copy)
+ *          a TRANSPOSED weight copy;
+ *          act == LMV_ACT_GELU_BWD: out[r, n] = aux[r, n] * gelu'(sum_k a[r,k] w[n,k] + bias[n]) -- the GELU backward of a forward that kept no pre-activation
+ *          (lmv_linear_fwd(.., LMV_ACT_GELU) with out_pre = NULL): z is recomputed from the saved rows, aux is the incoming gradient.  A kernel of its own
+ *          (csrc/convbn.hip): N <= 128, K a multiple of 32, no residual / row_scale / out_pre)
  *   dx  : out[r, k] = (sum_n a[r,n] w[n,k]) (* gelu'(aux[r,k]) if act == LMV_ACT_GELU_GRAD)
  *   dw  : dw[n, k] += sum_r dy[r,n] x[r,k] ;  db[n] += sum_r dy[r,n]      (fp32; split-K partial slabs in
  *         `workspace` + a reduce kernel: deterministic, no atomics)
  * ------------------------------------------------------------------------------------------ */
-enum { LMV_ACT_NONE = 0, LMV_ACT_GELU = 1, LMV_ACT_GELU_GRAD = 2 };
+enum { LMV_ACT_NONE = 0, LMV_ACT_GELU = 1, LMV_ACT_GELU_GRAD = 2, LMV_ACT_GELU_BWD = 3 };
 
 typedef struct {
   const void* a;           /* fwd: x [rows, K]; dx: dy [rows, N]; dw: dy [rows, N]            */
@@ -71,7 +74,7 @@ typedef struct {
   const float* bias;       /* fwd: [N] or NULL                                                  */
   const void* res;         /* fwd: residual [rows, N] or NULL (dx: [rows, K] added to out)      */
   const float* row_scale;  /* per-sample DropPath scale [rows / rows_per_sample] or NULL        */
-  const void* aux;         /* dx with GELU_GRAD: pre-activation u [rows, K]                     */
+  const void* aux;         /* dx with GELU_GRAD: pre-activation u [rows, K]; fwd with GELU_BWD: incoming gradient [rows, N] */
   void* out;               /* fwd: [rows, N]; dx: [rows, K]; dw: fp32 dW [N, K] (accumulated)   */
   void* out_pre;           /* fwd: optional copy of the pre-activation (training) or NULL       */
   float* bias_grad;        /* dw: fp32 db [N] (accumulated) or NULL                             */
@@ -351,6 +354,19 @@ int lmv_conv3x3s2_fwd(const void* x, const void* wm, const float* bias, void* y,
 size_t lmv_conv3x3s2_dw_workspace_bytes(int B, int H, int W, int Cin, int Cout, int KP, int dtype);
 int lmv_conv3x3s2_dw(const void* dy, const void* x, float* dwm, float* dbias, int B, int H, int W, int Cin, int Cout, int KP, void* workspace, size_t workspace_bytes, int dtype,
                      void* stream);
+/* A frozen (eval-mode) BatchNorm2d behind one of these convolutions, under autograd (csrc/convbn.hip): the BatchNorm is folded into the GEMM operand, with gradients.
+ * With r = 1 / sqrt(var + eps) and s = gamma r (all vectors fp32 [Co], w the fp32 master weight [Co, Cin, 3, 3], b its bias or NULL):
+ *   lmv_conv_bn_fold (one launch): wm[co, col] = w[co, ci, tap] s[co] in `dtype` with the columns 9 Cin .. KP - 1 zero -- col = ci * 9 + tap for LMV_FOLD_CI_TAP
+ *     (the operand of lmv_im2col3x3s2_c3 / _nchw), col = tap * Cin + ci for LMV_FOLD_TAP_CI (lmv_im2col3x3s2_nhwc / lmv_conv3x3s2_fwd) --,
+ *     bf = (b - mean) s + beta and sc = s.  Co % 8 == 0, KP >= 9 Cin a multiple of 8.
+ *   lmv_conv_bn_fold_bwd (one launch) from the folded gradients dwm [Co, KP] / dbf [Co] (fp32) that lmv_linear_dw / lmv_conv3x3s2_dw produced:
+ *     dW = dwm s in the weight's own [Co, Cin, 3, 3] layout, db = dbf s, dgamma = r (sum_k dwm[co, k] w[co, k] + dbf (b - mean)), dbeta = dbf -- WRITTEN, not
+ *     accumulated; each of the four may be NULL.  The per-channel sums run in one fixed order: two launches agree bit for bit. */
+enum { LMV_FOLD_CI_TAP = 0, LMV_FOLD_TAP_CI = 1 };
+int lmv_conv_bn_fold(const float* w, const float* b, const float* gamma, const float* beta, const float* mean, const float* var, float eps, int Co, int Cin, int KP,
+                     int layout, void* wm, float* bf, float* sc, int dtype, void* stream);
+int lmv_conv_bn_fold_bwd(const float* dwm, const float* dbf, const float* w, const float* b, const float* gamma, const float* mean, const float* var, float eps, int Co,
+                         int Cin, int KP, int layout, float* dW, float* db, float* dgamma, float* dbeta, void* stream);
 /* Classifier tail (models/lemevit.py:815-835, `x.flatten(2).mean(-1) + c.mean(1)`): out[b, :] = mean_l x[b, l, :] + mean_m c[b, m, :]
  * for token-major x [B, L, C] and c [B, M, C] (c may be NULL), out [B, C] in `dtype`; and its backward, the broadcast
  * dx[b, l, :] = g[b, :] / L, dc[b, m, :] = g[b, :] / M (dc may be NULL). */

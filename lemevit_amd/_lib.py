@@ -16,8 +16,9 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LMV_LIB_PATH") or os.path.join(_HERE, "csrc", "liblemevit_hip.so")          # LMV_LIB_PATH: another build of the same library (A/B runs of kernel variants inside one gpurun call)
 
 LMV_F32, LMV_BF16 = 0, 1
-ACT_NONE, ACT_GELU, ACT_GELU_GRAD = 0, 1, 2
-ABI_VERSION = 13
+ACT_NONE, ACT_GELU, ACT_GELU_GRAD, ACT_GELU_BWD = 0, 1, 2, 3
+FOLD_CI_TAP, FOLD_TAP_CI = 0, 1
+ABI_VERSION = 14
 
 
 class LinearProblem(C.Structure):
@@ -148,6 +149,8 @@ SIGNATURES = {
     "lmv_conv3x3s2_fwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "lmv_conv3x3s2_dw_workspace_bytes": (_Z, [_I, _I, _I, _I, _I, _I, _I]),
     "lmv_conv3x3s2_dw": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _Z, _I, _P]),
+    "lmv_conv_bn_fold": (_I, [_P, _P, _P, _P, _P, _P, _F, _I, _I, _I, _I, _P, _P, _P, _I, _P]),
+    "lmv_conv_bn_fold_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _F, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "lmv_col2im3x3s2_nhwc": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "lmv_token_mean2_fwd": (_I, [_P, _I, _P, _I, _I, _I, _P, _I, _P]),
     "lmv_token_mean2_affine_fwd": (_I, [_P, _I, _P, _I, _I, _I, _P, _P, _P, _I, _P]),

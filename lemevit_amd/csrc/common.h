@@ -110,6 +110,8 @@ bool lmv_wn_eligible(const lmv_linear_problem* p, int nproblems, int N, int K, i
 bool lmv_mlp_rw96_eligible(const lmv_mlp_problem* p, int nproblems, int C, int hidden);
 int lmv_mlp_rw96_fwd(const lmv_mlp_problem* p, int nproblems, const lmv_mlp_weights* w, float eps, hipStream_t st);
 int lmv_wn_linear(const lmv_linear_problem* p, int nproblems, int N, int K, int act, hipStream_t st);
+// csrc/convbn.hip: lmv_linear_fwd(.., LMV_ACT_GELU_BWD) -- out = aux * GELU'(a w^T + bias), a kernel of its own (validates its arguments itself)
+int lmv_gelu_bwd_linear(const lmv_linear_problem* p, int nproblems, int N, int K, int dtype, hipStream_t st);
 
 static inline bool lmv_aligned16(const void* p) { return (((uintptr_t)p) & 15u) == 0; }
 

@@ -625,7 +625,8 @@ extern "C" int lmv_attn_out_proj_residual(const lmv_linear_problem* p, int nprob
 }
 
 extern "C" int lmv_linear_fwd(const lmv_linear_problem* p, int nproblems, int N, int K, int act, int dtype, void* stream) {
-  if (act != LMV_ACT_NONE && act != LMV_ACT_GELU && act != LMV_ACT_GELU_GRAD) LMV_FAIL(LMV_ERR_SHAPE, "linear_fwd: act must be NONE, GELU or GELU_GRAD");
+  if (act == LMV_ACT_GELU_BWD) return lmv_gelu_bwd_linear(p, nproblems, N, K, dtype, (hipStream_t)stream);      // (csrc/convbn.hip: not an epilogue mode of the kernels below)
+  if (act != LMV_ACT_NONE && act != LMV_ACT_GELU && act != LMV_ACT_GELU_GRAD) LMV_FAIL(LMV_ERR_SHAPE, "linear_fwd: act must be NONE, GELU, GELU_GRAD or GELU_BWD");
   for (int i = 0; i < nproblems && i < 2; ++i)
     if (act == LMV_ACT_GELU_GRAD && (!p[i].aux || p[i].res)) LMV_FAIL(LMV_ERR_SHAPE, "linear_fwd: GELU_GRAD needs aux and takes no residual");
   double rows = 0., bytes = 2.0 * N * K + 4.0 * N;          // algorithmic HBM bytes: A in, C out (+ pre-activation copy out, + residual in, + the GELU' operand in), W and bias once (bf16 = 2 B)

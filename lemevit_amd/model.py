@@ -260,6 +260,102 @@ def _is_conv3x3s2(m: nn.Module, x: Tensor) -> bool:
 _CONV_IMPLICIT = os.environ.get("LMV_CONV_IMPLICIT", "1") != "0"      # 0: the patch-matrix form of the 3 x 3 / stride-2 convolutions (im2col + GEMM; A/B runs)
 
 
+_FROZEN_BN = os.environ.get("LMV_FROZEN_BN", "1") != "0"      # 0: an eval-mode BatchNorm under autograd runs as library glue behind its convolution (A/B runs, parity tests)
+
+
+def _bn_frozen(m: Optional[nn.Module]) -> bool:
+    """A BatchNorm2d that is a fixed per-channel affine map of fp32 vectors: eval mode, running statistics, affine."""
+    return (_FROZEN_BN and isinstance(m, nn.BatchNorm2d) and not m.training and m.track_running_stats and m.running_mean is not None and m.running_var is not None
+            and m.affine and all(t.dtype == torch.float32 for t in (m.weight, m.bias, m.running_mean, m.running_var)))
+
+
+def _conv_bn_pairs(m: nn.Module, bn: Optional[nn.Module], x: Tensor, cd: torch.dtype) -> bool:
+    """Conv2d + frozen BatchNorm2d that run as ONE autograd node (_ConvBNFn) on the native convolution paths."""
+    return (_bn_frozen(bn) and cd in (torch.float32, torch.bfloat16) and x.is_cuda and (_is_stem_conv1(m, x) or _is_conv3x3s2(m, x)) and m.weight.dtype == torch.float32
+            and (m.bias is None or m.bias.dtype == torch.float32) and m.weight.is_contiguous() and bn.num_features == m.out_channels)
+
+
+class _ConvBNFn(torch.autograd.Function):
+    """Conv2d(Cin, Cout, 3, stride 2, padding 1) -> frozen BatchNorm2d (-> exact GELU, behind the first stem convolution) as one node on the convolution paths of
+    _StemConv1Fn (image: im2col + GEMM, one-launch dX) and _Conv3x3s2Fn (channels-last map: implicit or patch-matrix GEMM).  The BatchNorm is folded into the GEMM
+    operand with gradients (ops.conv_bn_fold / conv_bn_fold_bwd: one launch each per pass), so no pass over the feature map is spent on it and no map is saved for
+    it:  y = act(conv(x; W s, (b - mu) s + beta)), s = gamma / sqrt(var + eps);  dW = dW' s, db = db' s, dgamma = r (sum_k dW'_k W_k + db' (b - mu)), dbeta = db'
+    from the folded gradients dW', db' of the weight-gradient GEMM.  The GELU rides the forward GEMM's epilogue; its backward recomputes the pre-activation from the
+    saved patch rows (ops.linear_fwd(ACT_GELU_BWD)).  The weight-gradient GEMM runs only where W, b, gamma or beta requires grad, dX only where x does."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, gamma, beta, conv, bn, cd, gelu):
+        B, Ci, H, W = x.shape
+        Co = weight.shape[0]
+        Ho, Wo = (H + 1) // 2, (W + 1) // 2
+        stem1 = _is_stem_conv1(conv, x)
+        if stem1:
+            KP, layout = (9 * Ci + 31) // 32 * 32, ops.FOLD_CI_TAP
+        else:
+            KP, layout = ((9 * Ci + 63) // 64 * 64 if cd == torch.bfloat16 else 9 * Ci), ops.FOLD_TAP_CI      # bf16: whole 64-deep k-steps (the GEMM's LDS-DMA path)
+        eps = float(bn.eps)
+        Wm, bf, _ = derived(conv, ("conv_bn_train", cd, KP, layout), _conv_bn_sources(conv, bn),
+                            lambda: ops.conv_bn_fold(weight.detach(), None if bias is None else bias.detach(), gamma.detach(), beta.detach(), bn.running_mean, bn.running_var,
+                                                     eps, cd, KP, layout))
+        act = ops.ACT_GELU if gelu else ops.ACT_NONE
+        implicit = False
+        if stem1:
+            saved = ops.im2col3x3s2_c3(x, cd) if Ci == 3 else ops.im2col3x3s2_nchw(x, cd, KP)
+        else:
+            assert not gelu
+            xh = x.detach().permute(0, 2, 3, 1).to(cd).contiguous()            # NHWC; no copy for channels-last input of the right dtype
+            implicit = _CONV_IMPLICIT and ops.conv3x3s2_implicit_ok(xh, Co, KP)
+            saved = xh if implicit else ops.im2col3x3s2_nhwc(xh, KP)
+        if implicit:
+            y = ops.conv3x3s2_fwd(saved, Wm, bf)
+        else:
+            y = torch.empty(B * Ho * Wo, Co, device=x.device, dtype=cd)
+            ops.linear_fwd([Prob(saved, Wm, y, bias=bf)], Co, KP, act)
+        need_x, need_p = ctx.needs_input_grad[0], any(ctx.needs_input_grad[1:5])
+        regelu = gelu and (need_x or need_p)          # the GELU backward wants the patch rows AND the folded operand
+        ctx.save_for_backward(*([saved] if need_p or regelu else []), *([Wm, bf] if need_x or regelu else []), *([x] if need_x and stem1 else []))
+        ctx.meta = (tuple(x.shape), x.dtype, stem1, implicit, layout, gelu, eps, need_p, KP, cd)
+        ctx.mods = (conv, bn)
+        return y.view(B, Ho, Wo, Co).permute(0, 3, 1, 2)                    # NCHW-shaped, channels-last-strided: no copy
+
+    @staticmethod
+    def backward(ctx, dy):
+        (B, Ci, H, W), xdt, stem1, implicit, layout, gelu, eps, need_p, KP, cd = ctx.meta
+        conv, bn = ctx.mods
+        need_x = ctx.needs_input_grad[0]
+        sv = list(ctx.saved_tensors)
+        saved = sv.pop(0) if need_p or gelu else None          # the patch matrix, or the NHWC map of the implicit form
+        Wm, bf = (sv.pop(0), sv.pop(0)) if need_x or gelu else (None, None)
+        Co = conv.weight.shape[0]
+        g = dy.permute(0, 2, 3, 1).contiguous().view(-1, Co)
+        if g.dtype != cd:
+            g = g.to(cd)
+        if gelu:          # dz = da * GELU'(z), z recomputed from the patch rows in the same launch
+            dz = torch.empty_like(g)
+            ops.linear_fwd([Prob(saved, Wm, dz, bias=bf, aux=g)], Co, KP, ops.ACT_GELU_BWD)
+            g = dz
+        grads = [None, None, None, None]
+        if need_p:
+            dwm = torch.zeros(Co, KP, device=g.device, dtype=torch.float32)
+            dbf = torch.zeros(Co, device=g.device, dtype=torch.float32)
+            if implicit:
+                ops.conv3x3s2_dw(g, saved, dwm, dbf)
+            else:
+                ops.linear_dw([Prob(g, saved, dwm, bias_grad=dbf)], Co, KP)
+            want = [bool(n) for n in ctx.needs_input_grad[1:5]]
+            want[1] = want[1] and conv.bias is not None
+            grads = list(ops.conv_bn_fold_bwd(dwm, dbf, conv.weight.detach(), None if conv.bias is None else conv.bias.detach(), bn.weight.detach(), bn.running_mean,
+                                              bn.running_var, eps, layout, want))
+        dx = None
+        if need_x and stem1:
+            dx = ops.conv3x3s2_nchw_dx(g, Wm, like=sv.pop(0))
+        elif need_x:
+            dp = torch.empty(g.shape[0], KP, device=g.device, dtype=g.dtype)
+            ops.linear_dx([Prob(g, Wm, dp)], Co, KP)
+            dx = ops.col2im3x3s2_nhwc(dp, B, H, W, Ci).permute(0, 3, 1, 2).to(xdt)
+        return (dx, *grads, None, None, None, None)
+
+
 class _BNActFn(torch.autograd.Function):
     """Training-mode BatchNorm2d (+ the GELU behind the first stem BatchNorm) on a channels-last feature map
     (models/lemevit.py:698-704, 714-717, 773): lmv_batchnorm_train_fwd / _bwd instead of MIOpen's batch-norm kernels plus
@@ -394,15 +490,25 @@ class _TailFn(torch.autograd.Function):
     logits = head(mean_tokens(x) + mean_tokens(LayerNorm(c))) for token-major x [B, L, C] (already through the final BatchNorm)
     and the meta tokens c [B, M, C] -- lmv_layernorm_fwd -> lmv_token_mean2_fwd -> lmv_linear_fwd, and a hand-written backward
     (lmv_linear_dx / _dw, lmv_token_mean2_bwd, lmv_layernorm_bwd) instead of ~25 library kernels.  head = None returns the
-    pooled features (forward_features)."""
+    pooled features (forward_features).
+    Eval form (bn_w .. bn_eps given: the final BatchNorm frozen, x NOT yet through it): the affine map commutes with the token mean, so the forward is
+    lmv_token_mean2_affine_fwd on x itself and the backward, with xbar = lmv_token_mean2_fwd(x, NULL) recomputed, dx[b, l, :] = dpooled[b, :] gamma r / L,
+    dgamma = sum_b dpooled (xbar_b - mu) r, dbeta = sum_b dpooled -- no BatchNorm pass over [B, C, H, W] in either direction."""
 
     @staticmethod
-    def forward(ctx, x, c, g, b, eps, hw, hb, cd):
+    def forward(ctx, x, c, g, b, eps, hw, hb, cd, bn_w=None, bn_b=None, bn_mean=None, bn_var=None, bn_eps=0.0):
         xc = x.detach().to(cd).contiguous()
         cc = c.detach().to(cd).contiguous()
         f32 = lambda p: compute_copy(p, torch.float32)
         (cn,), (st,) = ops.layernorm_fwd_multi([cc], f32(g), f32(b), eps, want_stats=True)
-        pooled = ops.token_mean2_fwd(xc, cn)
+        ctx.bn = None
+        if bn_w is not None:
+            r = torch.rsqrt(bn_var + bn_eps)
+            a = (bn_w.detach() * r).contiguous()
+            pooled = ops.token_mean2_affine_fwd(xc, cn, a, (bn_b.detach() - bn_mean * a).contiguous())
+            ctx.bn = (xc if (ctx.needs_input_grad[8] or ctx.needs_input_grad[9]) else None, a, r, bn_mean)
+        else:
+            pooled = ops.token_mean2_fwd(xc, cn)
         ctx.dims = (xc.shape[1], cc.shape[1])
         ctx.meta = (x.dtype, c.dtype, g.dtype, b.dtype, None if hw is None else hw.dtype, None if hb is None else hb.dtype, None if hw is None else hw.shape)
         if hw is None:
@@ -446,11 +552,23 @@ class _TailFn(torch.autograd.Function):
             db = None if hbdt is None else dbf[:N].to(hbdt)
         else:
             dpooled = dout.contiguous().to(cc.dtype)
-        dx, dcn = ops.token_mean2_bwd(dpooled, L, M)
+        dbn_w = dbn_b = None
+        if ctx.bn is not None:
+            xc, a, r, mu = ctx.bn
+            dp32 = dpooled.float()
+            dx, _ = ops.token_mean2_bwd((dp32 * a).to(dpooled.dtype), L, 0)
+            _, dcn = ops.token_mean2_bwd(dpooled, 1, M)          # (its one-row dx is dropped)
+            if ctx.needs_input_grad[8]:
+                dbn_w = (dp32 * (ops.token_mean2_fwd(xc, None).float() - mu) * r).sum(0)
+            if ctx.needs_input_grad[9]:
+                dbn_b = dp32.sum(0)
+            ctx.bn = None
+        else:
+            dx, dcn = ops.token_mean2_bwd(dpooled, L, M)
         dg = torch.zeros_like(g32); dbeta = torch.zeros_like(g32)
         (dc,) = ops.layernorm_bwd_multi([dcn], [cc], [st], g32, dg, dbeta, [None])
         ctx.saved = None
-        return dx.to(xdt), dc.to(cdt), dg.to(gdt), dbeta.to(bdt), None, dW, db, None
+        return dx.to(xdt), dc.to(cdt), dg.to(gdt), dbeta.to(bdt), None, dW, db, None, dbn_w, dbn_b, None, None, None
 
 
 def _tail_infer(norm_c: nn.LayerNorm, bn: nn.BatchNorm2d, head: nn.Linear, xt: Tensor, c: Tensor, cd: torch.dtype) -> Tensor:
@@ -1360,6 +1478,11 @@ def _downsample_mods(mods: List[nn.Module], x: Tensor, cd: torch.dtype, fold: bo
             else:
                 # (no vendor-library convolution behind the native ones: the stock PyTorch-ROCm column lives in tools/stock_eager.py)
                 raise NotImplementedError(_no_conv_kernel(m, x))
+        elif _conv_bn_pairs(m, bn, x, cd) and not (ck is not None and ck["recompute"] and (i + 1) in ck["stats"]):
+            # a frozen BatchNorm under autograd (the dense backbones' train(), an eval-mode classifier with an image that requires grad): folded into the convolution
+            gelu = _is_stem_conv1(m, x) and i + 2 < len(mods) and isinstance(mods[i + 2], nn.GELU) and getattr(mods[i + 2], "approximate", "none") == "none"
+            x = _ConvBNFn.apply(x, m.weight, m.bias, bn.weight, bn.bias, m, bn, cd, gelu)
+            i += 3 if gelu else 2
         elif _is_stem_conv1(m, x) and cd in (torch.float32, torch.bfloat16):
             x = _StemConv1Fn.apply(x, m.weight, m.bias, cd)
             i += 1
@@ -1680,10 +1803,14 @@ class LeMeViT(nn.Module):
         bn = self.norm
         if head is not False and isinstance(self.pre_logits, nn.Identity) and (self.training or torch.is_grad_enabled()) and _tail_native(self.norm_c, head, xt, c, cd):
             # training: final BatchNorm (native kernels) -> LayerNorm(c) + both mean-pools + add (+ classifier) as ONE autograd node
+            hw, hb = (None, None) if head is None else (head.weight, head.bias)
+            if _bn_frozen(bn) and bn.num_features == xt.shape[-1]:          # frozen BatchNorm under autograd: folded into the pool, forward and backward
+                self._tail_done = head is not None
+                return _TailFn.apply(xt, c, self.norm_c.weight, self.norm_c.bias, float(self.norm_c.eps), hw, hb, cd, bn.weight, bn.bias, bn.running_mean, bn.running_var,
+                                     float(bn.eps))
             xn = self._to_nchw(xt, H, W)
             xn = _bn_train(bn, xn) if _bn_native(bn, xn) else bn(xn)
             xb = xn.permute(0, 2, 3, 1).reshape(B, H * W, -1)           # token-major view of the channels-last map: no copy
-            hw, hb = (None, None) if head is None else (head.weight, head.bias)
             self._tail_done = head is not None
             return _TailFn.apply(xb, c, self.norm_c.weight, self.norm_c.bias, float(self.norm_c.eps), hw, hb, cd)
         if (head is not False and head is not None and not bn.training and bn.track_running_stats and isinstance(self.pre_logits, nn.Identity)

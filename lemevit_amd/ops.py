@@ -13,7 +13,7 @@ from typing import List, Optional, Sequence, Tuple
 import torch
 
 from . import _lib
-from ._lib import ACT_GELU, ACT_GELU_GRAD, ACT_NONE, AttnDesc, LinearProblem, LnSegment, check, lib
+from ._lib import ACT_GELU, ACT_GELU_BWD, ACT_GELU_GRAD, ACT_NONE, FOLD_CI_TAP, FOLD_TAP_CI, AttnDesc, LinearProblem, LnSegment, check, lib
 
 Tensor = torch.Tensor
 HEAD_DIM = 32
@@ -97,7 +97,8 @@ def _pack(probs: Sequence[Prob]):
 
 
 def linear_fwd(probs: Sequence[Prob], N: int, K: int, act: int = ACT_NONE) -> None:
-    """out = res + row_scale * act(a @ w^T + bias) for up to two problems sharing (N, K)."""
+    """out = res + row_scale * act(a @ w^T + bias) for up to two problems sharing (N, K).  act = ACT_GELU_BWD: out = aux * GELU'(a @ w^T + bias), the backward
+    of an ACT_GELU launch that kept no pre-activation (aux: the incoming gradient [rows, N]; N <= 128, K % 32 == 0)."""
     check(lib.lmv_linear_fwd(_pack(probs), len(probs), N, K, act, dtype_code(probs[0].a), _stream()), "lmv_linear_fwd")
 
 
@@ -540,6 +541,36 @@ def conv3x3s2_dw(dy: Tensor, x: Tensor, dwm: Tensor, dbias: Optional[Tensor]) ->
     st = _stream()
     ws = _workspace(lib.lmv_conv3x3s2_dw_workspace_bytes(B, H, W, C_, Co, KP, dtype_code(x)), x.device, st)
     check(lib.lmv_conv3x3s2_dw(_ptr(dy), _ptr(x), _f32(dwm), None if dbias is None else _f32(dbias), B, H, W, C_, Co, KP, ws.data_ptr(), ws.numel(), dtype_code(x), st), "lmv_conv3x3s2_dw")
+
+
+def conv_bn_fold(weight: Tensor, bias: Optional[Tensor], gamma: Tensor, beta: Tensor, mean: Tensor, var: Tensor, eps: float, dtype: torch.dtype, KP: int,
+                 layout: int) -> Tuple[Tensor, Tensor, Tensor]:
+    """Conv2d(Cin, Co, 3) weight [Co, Cin, 3, 3] (fp32) followed by an eval-mode BatchNorm2d (fp32 gamma, beta, running mean / variance) -> (wm, bf, s) in ONE launch:
+    wm [Co, KP] = W s in `dtype` (column ci * 9 + tap for FOLD_CI_TAP, tap * Cin + ci for FOLD_TAP_CI; the columns behind 9 Cin zero), bf = (b - mean) s + beta and
+    s = gamma / sqrt(var + eps) in fp32."""
+    Co, Cin = weight.shape[0], weight.shape[1]
+    if weight.dtype != torch.float32 or tuple(weight.shape[2:]) != (3, 3):
+        raise TypeError("conv_bn_fold: takes the fp32 master weight [Co, Cin, 3, 3]")
+    wm = torch.empty((Co, KP), device=weight.device, dtype=dtype)
+    bf = torch.empty(Co, device=weight.device, dtype=torch.float32)
+    s = torch.empty(Co, device=weight.device, dtype=torch.float32)
+    check(lib.lmv_conv_bn_fold(_f32(weight), _f32(bias), _f32(gamma), _f32(beta), _f32(mean), _f32(var), eps, Co, Cin, KP, layout, _ptr(wm), _ptr(bf), _ptr(s),
+                               dtype_code(wm), _stream()), "lmv_conv_bn_fold")
+    return wm, bf, s
+
+
+def conv_bn_fold_bwd(dwm: Tensor, dbf: Tensor, weight: Tensor, bias: Optional[Tensor], gamma: Tensor, mean: Tensor, var: Tensor, eps: float, layout: int,
+                     want: Sequence[bool] = (True, True, True, True)):
+    """Gradients of conv_bn_fold's sources from the folded gradients dwm [Co, KP] / dbf [Co] (fp32) in ONE launch: (dW [Co, Cin, 3, 3], db, dgamma, dbeta), fp32, written
+    (not accumulated); None where `want` is False."""
+    Co, Cin = weight.shape[0], weight.shape[1]
+    if dwm.shape[0] != Co or dbf.numel() != Co:
+        raise ValueError(f"conv_bn_fold_bwd: dwm {tuple(dwm.shape)} / dbf {tuple(dbf.shape)} do not match the weight {tuple(weight.shape)}")
+    new = lambda w, shape: torch.empty(shape, device=weight.device, dtype=torch.float32) if w else None
+    dW, db, dg, dbe = new(want[0], weight.shape), new(want[1], (Co,)), new(want[2], (Co,)), new(want[3], (Co,))
+    check(lib.lmv_conv_bn_fold_bwd(_f32(dwm), _f32(dbf), _f32(weight), _f32(bias), _f32(gamma), _f32(mean), _f32(var), eps, Co, Cin, dwm.shape[1], layout,
+                                   _ptr(dW), _ptr(db), _ptr(dg), _ptr(dbe), _stream()), "lmv_conv_bn_fold_bwd")
+    return dW, db, dg, dbe
 
 
 def col2im3x3s2_nhwc(dpatches: Tensor, B: int, H: int, W: int, C_: int) -> Tensor:
