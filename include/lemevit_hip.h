@@ -288,6 +288,13 @@ int lmv_attn_bwd(const lmv_attn_desc* d, void* workspace, size_t workspace_bytes
  * The workspace must be large enough for either problem (max of lmv_attn_workspace_bytes). */
 int lmv_attn_fwd_pair(const lmv_attn_desc* d, void* workspace, size_t workspace_bytes, int dtype, void* stream);
 int lmv_attn_bwd_pair(const lmv_attn_desc* d, void* workspace, size_t workspace_bytes, int dtype, void* stream);
+/* The probabilities the forward never materialises (csrc/attnmap.hip), recomputed from the forward's log-sum-exp:
+ *   P[b,h,i,j] = exp(scale * q[b,i,h,:].k[b,j,h,:] - lse[b,h,i]).
+ * d: the descriptor of the lmv_attn_fwd call whose probabilities are wanted (q, k, their strides, B, H, Lq, Lk, scale, lse are read;
+ * v, o and the gradient fields are ignored).  head_mean = 0: p is [B, H, Lq, Lk] fp32; 1: p is [B, Lq, Lk] = (1/H) sum_h, summed in
+ * the fixed order h = 0 .. H-1.  Every element of p is written exactly once; no workspace, no atomics, no pre-zeroed buffer.
+ * p must be 16-byte aligned; one (b, h) plane Lq * Lk must stay below 2^31 elements. */
+int lmv_attn_probs(const lmv_attn_desc* d, float* p, int head_mean, int dtype, void* stream);
 
 /* Named cores of the reference seam; thin wrappers that fill an lmv_attn_desc.
  *   sa : StandardAttention      qkv [B,L,3C] -> o [B,L,C]                        (:199-205)

@@ -433,6 +433,19 @@ def block_forward(kind: str, x: Tensor, c: Tensor, H: int, W: int, P: Dict[str, 
     return x3, c2, ((x, sa, sm) if save else None)
 
 
+def attention_state(kind: str, x: Tensor, c: Tensor, H: int, W: int, P: Dict[str, Tensor]):
+    """The saved set of the block's attention half alone -- the packed projections and the log-sum-exp of every attention call, exactly what
+    block_forward(save=True) keeps as its second element -- on the inference math (no DropPath).  LeMeViT.attention_maps recomputes the probabilities
+    from it (ops.attn_probs); the block's outputs come from the ordinary forward, so asking for a block's maps changes nothing downstream."""
+    xp = ops.dwconv_residual_fwd(x, P["pos_embed.weight"], P["pos_embed.bias"], H, W)
+    if kind == "C":
+        return _attn_C_fwd(P, xp, c, None, True)[1]
+    if kind == "Sx":
+        return _attn_S_fwd(P, [xp], [None], True)[1]
+    fwd = {"S": _attn_S_fwd, "D": _attn_D_fwd, "D2": _attn_D2_fwd}[kind]
+    return fwd(P, [xp, c], [None, None], True)[1]
+
+
 def block_backward(kind: str, saved, dx: Tensor, dc: Tensor, H: int, W: int, P: Dict[str, Tensor], G: Dict[str, Tensor],
                    masks: Sequence[Optional[Tensor]]) -> Tuple[Tensor, Tensor]:
     """Gradients wrt the block inputs; parameter gradients are accumulated (fp32) into G."""

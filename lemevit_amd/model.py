@@ -20,6 +20,7 @@ statistics, fp32 master weights and gradients (the bf16 matrix copies are derive
 """
 from __future__ import annotations
 
+import math
 import operator
 import os
 import threading
@@ -32,7 +33,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import ops
-from .blocks import BLOCK_LN_EPS, PARAM_NAMES, block_backward, block_forward
+from .blocks import BLOCK_LN_EPS, PARAM_NAMES, attention_state, block_backward, block_forward
 from .ops import Prob
 
 Tensor = torch.Tensor
@@ -1081,6 +1082,8 @@ def _sstage_applies(stage, xt: Tensor, c: Tensor, H: int, W: int) -> Optional[st
     (nothing is saved for a backward pass, no DropPath), bf16.  None: the per-block schedule."""
     if not (_SSTAGE and _FUSED and _NATIVE) or ops.stage_kernels_disabled or torch.is_grad_enabled() or xt.dtype != torch.bfloat16 or len(stage) == 0 or not xt.is_cuda:
         return None
+    if _map_pass.rec is not None:          # LeMeViT.attention_maps: the probabilities never exist inside the persistent stage kernels
+        return None
     kind = getattr(stage[0], "kind", None)
     if kind not in ("S", "D", "D2", "C"):
         return None
@@ -1264,6 +1267,7 @@ class StandardAttention(nn.Module):
         self.num_heads = num_heads
         self.qkv = nn.Linear(dim, 3 * dim)
         self.proj = nn.Linear(dim, dim)
+        self.attn_viz = nn.Identity()          # models/lemevit.py:181,249,355,451: the hook point of LeMeViT.attention_maps
 
     def forward(self, x):
         P = _attn_params(self.qkv, self.proj)
@@ -1295,6 +1299,7 @@ class DualCrossAttention(nn.Module):
         self.qkv2 = nn.Linear(dim, 3 * dim)
         self.proj_x = nn.Linear(dim, dim)
         self.proj_c = nn.Linear(dim, dim)
+        self.attn_viz = nn.Identity()          # models/lemevit.py:181,249,355,451: the hook point of LeMeViT.attention_maps
 
     def forward(self, x, c):
         P = _attn_params(self.qkv1, self.qkv2, self.proj_x, self.proj_c)
@@ -1329,6 +1334,7 @@ class DualCrossAttention_v2(nn.Module):
         self.kv2 = nn.Linear(dim, 2 * dim)
         self.proj_x = nn.Linear(dim, dim)
         self.proj_c = nn.Linear(dim, dim)
+        self.attn_viz = nn.Identity()          # models/lemevit.py:181,249,355,451: the hook point of LeMeViT.attention_maps
 
     def forward(self, x, c):
         P = _attn_params(self.qv1, self.kv2, self.proj_x, self.proj_c)
@@ -1361,6 +1367,7 @@ class CrossAttention(nn.Module):
         self.q = nn.Linear(dim, dim)
         self.kv = nn.Linear(dim, 2 * dim)
         self.proj = nn.Linear(dim, dim)
+        self.attn_viz = nn.Identity()          # models/lemevit.py:181,249,355,451: the hook point of LeMeViT.attention_maps
 
     def forward(self, x, c):
         P = _attn_params(self.q, self.kv, self.proj)
@@ -1380,6 +1387,118 @@ class CrossAttention(nn.Module):
         out = torch.empty_like(c)
         ops.linear_fwd(_lin_probs([(ao, self.proj, out)], x.dtype), C, C)
         return out
+
+
+# ------------------------------------------------------------------------------------------------
+# attention maps (LeMeViT.attention_maps): the probabilities the flash-style attention kernels never materialise, recomputed by ops.attn_probs from
+# the packed projections and the log-sum-exps a saving block forward keeps (blocks.attention_state)
+# ------------------------------------------------------------------------------------------------
+class _MapPass(threading.local):
+    rec = None          # the recorder of the attention_maps call in progress on this host thread
+
+
+_map_pass = _MapPass()
+MAP_FIELDS = ("image_from_meta", "meta_from_image", "image_self", "meta_self")          # in the order a block computes them (models/lemevit.py:297,300; :632,634)
+
+
+class AttentionMaps:
+    """One block's maps: `kind` ("C" / "D" / "D2" / "S" / "Sx"), `grid` = (H, W) of its image tokens, and whichever of MAP_FIELDS the block has,
+    fp32 (an extra head axis after the batch with heads="all"):
+      image_from_meta [B, H, W, M]   every image token's distribution over the meta tokens          (D, D2)
+      meta_from_image [B, M, H, W]   every meta token's distribution over the image                  (C, D, D2)
+      image_self      [B, R, H, W]   the image-token self-attention rows asked for (image_queries)   (S, Sx)
+      meta_self       [B, M, M]      the meta-token self-attention                                   (S)"""
+
+    def __init__(self, kind: str, grid: Tuple[int, int]):
+        self.kind, self.grid = kind, grid
+
+    def items(self):
+        return [(f, getattr(self, f)) for f in MAP_FIELDS if hasattr(self, f)]
+
+    def __repr__(self):
+        return f"AttentionMaps(kind={self.kind!r}, grid={self.grid}, " + ", ".join(f"{f}={tuple(t.shape)}" for f, t in self.items()) + ")"
+
+
+def map_query_rows(image_queries, H: int, W: int) -> Optional[List[int]]:
+    """Query rows of an H x W token grid for attention_maps(image_queries=...): None -> [], "all" -> None (every row), a list of (fy, fx) fractions
+    in [0, 1) -> row floor(fy H) * W + floor(fx W), so one list serves the grid of every stage."""
+    if image_queries is None:
+        return []
+    if isinstance(image_queries, str):
+        if image_queries != "all":
+            raise ValueError(f"attention_maps: image_queries must be None, 'all' or a list of (fy, fx) fractions, got {image_queries!r}")
+        return None
+    rows = []
+    for fy, fx in image_queries:
+        if not (0.0 <= fy < 1.0 and 0.0 <= fx < 1.0):
+            raise ValueError(f"attention_maps: image_queries fractions must lie in [0, 1), got {(fy, fx)!r}")
+        rows.append(int(math.floor(fy * H)) * W + int(math.floor(fx * W)))
+    return rows
+
+
+def map_shapes(kind: str, B: int, nh: Optional[int], M: int, H: int, W: int, rows: Optional[List[int]]) -> "OrderedDict[str, Tuple[int, ...]]":
+    """Field -> shape of one block's maps; nh = None: mean over the heads, else the head count; rows as map_query_rows returns them."""
+    lead = (B,) if nh is None else (B, nh)
+    out = OrderedDict()
+    if kind in ("D", "D2"):
+        out["image_from_meta"] = lead + (H, W, M)
+    if kind in ("C", "D", "D2"):
+        out["meta_from_image"] = lead + (M, H, W)
+    if kind in ("S", "Sx") and (rows is None or rows):
+        out["image_self"] = lead + (H * W if rows is None else len(rows), H, W)
+    if kind == "S":
+        out["meta_self"] = lead + (M, M)
+    return out
+
+
+class _MapRecorder:
+    """Visits every block of one forward pass (LeMeBlock.forward_tokens) and fills `maps` for the planned ones."""
+
+    def __init__(self, plan, head_mean: bool):
+        self.plan = {id(blk): (name, shapes) for name, blk, _, shapes in plan}
+        self.head_mean = head_mean
+        self.queries = None
+        self.maps: "OrderedDict[str, AttentionMaps]" = OrderedDict()
+
+    def _probs(self, viz: nn.Module, shape, q, k, lse, C_: int, scale: float) -> Tensor:
+        p = viz(ops.attn_probs(q, k, lse, C_, scale, head_mean=self.head_mean))          # [B, (h,) Lq, Lk]: what a hook on the reference's slow path sees (:63)
+        return p.reshape(shape)
+
+    def visit(self, blk: "LeMeBlock", x: Tensor, c: Tensor, H: int, W: int) -> None:
+        ent = self.plan.get(id(blk))
+        if ent is None:
+            return
+        name, shapes = ent
+        kind, viz, C_ = blk.kind, blk.attn.attn_viz, x.shape[-1]
+        rec = self.maps[name] = AttentionMaps(kind, (H, W))
+        if not shapes:          # an "Sx" block without image_queries
+            return
+        shapes = OrderedDict((f, (x.shape[0],) + tuple(s[1:])) for f, s in shapes.items())
+        cd = x.dtype
+        P = {n: compute_copy(p, cd if _is_matrix(n) else torch.float32) for n, p in blk._params().items()}
+        sa = attention_state(kind, x.contiguous(), c.contiguous(), H, W, P)
+        if kind == "C":
+            kv, q, lse = sa[6], sa[7], sa[9]
+            rec.meta_from_image = self._probs(viz, shapes["meta_from_image"], (q, 0), (kv, 0), lse, C_, ops.SDPA_SCALE)
+        elif kind in ("D", "D2"):
+            a, b2, lsex, lsec = sa[3], sa[4], sa[7], sa[8]          # D: qkv1, qkv2; D2: qv1, kv2
+            sx, sc = ops.dca_scales(x.shape[1], c.shape[1], C_)
+            kx, kc = ((b2, C_), (a, C_)) if kind == "D" else ((b2, 0), (a, 0))
+            rec.image_from_meta = self._probs(viz, shapes["image_from_meta"], (a, 0), kx, lsex, C_, sx)
+            rec.meta_from_image = self._probs(viz, shapes["meta_from_image"], (b2, 0), kc, lsec, C_, sc)
+        else:
+            qkv, lse = sa[3], sa[5]
+            if "image_self" in shapes:
+                rows = map_query_rows(self.queries, H, W)
+                if rows is None:
+                    qs, ls = qkv[0], lse[0]
+                else:          # the kernel has no row selection: gather the query rows and their log-sum-exps into small tensors
+                    idx = torch.tensor(rows, device=x.device, dtype=torch.long)
+                    qs = qkv[0][:, :, :C_].index_select(1, idx).contiguous()
+                    ls = lse[0].index_select(2, idx).contiguous()
+                rec.image_self = self._probs(viz, shapes["image_self"], (qs, 0), (qkv[0], C_), ls, C_, ops.SDPA_SCALE)
+            if kind == "S":
+                rec.meta_self = self._probs(viz, shapes["meta_self"], (qkv[1], 0), (qkv[1], C_), lse[1], C_, ops.SDPA_SCALE)
 
 
 class LeMeBlock(nn.Module):
@@ -1438,6 +1557,8 @@ class LeMeBlock(nn.Module):
 
     def forward_tokens(self, x: Tensor, c: Tensor, H: int, W: int, masks=None) -> Tuple[Tensor, Tensor]:
         """x [B, H*W, C] token-major, c [B, M, C]."""
+        if _map_pass.rec is not None:
+            _map_pass.rec.visit(self, x, c, H, W)
         if masks is None:
             masks = self._masks(x.shape[0], x.device)
             if any(m is not None for m in masks):
@@ -1704,14 +1825,15 @@ class LeMeViT(nn.Module):
         if hoist:
             c = self.meta_tokens.unsqueeze(0)
         infer = not (self.training or torch.is_grad_enabled())
+        mapping = _map_pass.rec is not None          # attention_maps: one stream, per-block schedule
         st = {"cd": cd, "masks": self._draw_drop_path(B, x.device), "head": head, "checked": False, "infer": infer,
               # inference concurrency inside ONE pass (round 6): the meta-token MLP of a stage next to its transition convolution, and the per-launch stages behind the last
               # persistent stage kernel as sub-batches on forked streams.  Off inside graph.split_forward (its sub-batches already fill the streams a process holds).
-              "side": infer and _INFER_SIDE and launches.concurrent == 1 and x.is_cuda,
-              "tail_parts": _INFER_TAIL_PARTS if (infer and launches.concurrent == 1 and x.is_cuda and B >= 32) else 1,
+              "side": infer and _INFER_SIDE and launches.concurrent == 1 and x.is_cuda and not mapping,
+              "tail_parts": _INFER_TAIL_PARTS if (infer and launches.concurrent == 1 and x.is_cuda and B >= 32 and not mapping) else 1,
               "key": (tuple(x.shape[1:]), cd), "whole": [False] * self.num_stages}
         out = self._stages_from(0, x, None, 0, 0, c, hoist, st)
-        if infer and launches.concurrent == 1:
+        if infer and launches.concurrent == 1 and not mapping:
             self.__dict__.setdefault("_whole_seen", {})[st["key"]] = tuple(st["whole"])          # which stages ran as persistent launches at this input shape: where the next pass may split
         return out
 
@@ -1831,6 +1953,68 @@ class LeMeViT(nn.Module):
         xn = _bn_train(bn, xn) if _bn_native(bn, xn) else bn(xn)
         xn = self.pre_logits(xn)
         return xn.flatten(2).mean(-1) + cn.mean(dim=1)
+
+    # ---- attention maps ---------------------------------------------------------------------------------
+    def _map_plan(self, img_shape, blocks=None, heads: str = "mean", image_queries=None):
+        """Host arithmetic of attention_maps: ([(name, block, (H, W), {field: shape})] in forward order, total bytes of the maps).  No device is touched."""
+        if heads not in ("mean", "all"):
+            raise ValueError(f"attention_maps: heads must be 'mean' or 'all', got {heads!r}")
+        if len(img_shape) != 4:
+            raise ValueError(f"attention_maps: the image must be [B, C, H, W], got shape {tuple(img_shape)}")
+        names = OrderedDict((f"stages.{i}.{j}", (i, blk)) for i, stage in enumerate(self.stages) for j, blk in enumerate(stage))
+        if blocks is None:
+            want = set(names)
+        else:
+            want = set([blocks] if isinstance(blocks, str) else blocks)
+            unknown = sorted(n for n in want if n not in names)
+            if unknown:
+                raise ValueError(f"attention_maps: unknown block name(s) {unknown}; blocks are named 'stages.<stage>.<block>', e.g. {list(names)[:3]}")
+        B, _, H, W = (int(v) for v in img_shape)
+        grids = []
+        for i in range(self.num_stages):          # 3 x 3 / stride 2 / padding 1: n -> (n + 1) // 2; the stem has two of them
+            if i == 0:
+                H, W = ((H + 1) // 2 + 1) // 2, ((W + 1) // 2 + 1) // 2
+            elif not isinstance(self.downsample_layers[i], nn.Identity):
+                H, W = (H + 1) // 2, (W + 1) // 2
+            grids.append((H, W))
+        plan, total = [], 0
+        for name, (i, blk) in names.items():
+            if name not in want:
+                continue
+            h, w = grids[i]
+            shapes = map_shapes(blk.kind, B, None if heads == "mean" else blk.attn.num_heads, self.queries_len, h, w, map_query_rows(image_queries, h, w))
+            total += 4 * sum(math.prod(s) for s in shapes.values())
+            plan.append((name, blk, (h, w), shapes))
+        return plan, total
+
+    def attention_maps(self, img: Tensor, blocks=None, heads: str = "mean", image_queries=None, max_bytes: int = 1 << 30):
+        """(out, maps): `out` is what forward(img) returns, `maps` an OrderedDict "stages.i.j" -> AttentionMaps in forward order with the attention
+        probabilities of those blocks -- which image regions each meta token looks at, and back (models/lemevit.py:106,181,249: the reference's attn_viz).
+        blocks: None = every block, else names "stages.i.j".  heads: "mean" (over the heads) or "all" (a head axis).  image_queries (S blocks): None = no
+        image-token self-attention maps, a list of (fy, fx) fractions in [0, 1) = those query positions on every stage's grid, "all" = the full N x N matrix.
+        Runs without autograd on the inference math whatever mode the module is in (which it keeps), on the per-block schedule of one stream; the maps of
+        a block come from a saving run of its attention half next to the ordinary forward, so `out` and each map do not depend on what else was asked for.
+        Every map goes through its attention module's `attn_viz` (an nn.Identity: register a forward hook there) as [B, (h,) Lq, Lk].
+        Maps larger than max_bytes in total are refused before anything is launched."""
+        plan, total = self._map_plan(tuple(img.shape), blocks, heads, image_queries)
+        if total > max_bytes:
+            raise ValueError(f"attention_maps: the requested maps take {total} bytes (max_bytes = {max_bytes}); pass blocks= to select blocks or image_queries= "
+                             "a short list of query positions instead of 'all', or raise max_bytes")
+        rec = _MapRecorder(plan, heads == "mean")
+        rec.queries = image_queries
+        training = [m for m in self.modules() if m.training]
+        prev = _map_pass.rec
+        try:
+            for m in training:
+                m.training = False
+            _map_pass.rec = rec
+            with torch.no_grad():
+                out = self(img)
+        finally:
+            _map_pass.rec = prev
+            for m in training:
+                m.training = True
+        return out, rec.maps
 
     def forward(self, x: Tensor) -> Tensor:
         head = self.head if isinstance(self.head, nn.Linear) else None

@@ -374,17 +374,24 @@ def dwconv_bwd_weight(dy: Tensor, x: Tensor, dweight: Tensor, dbias: Tensor, H: 
 # -------------------------------------------------------------------------------------------
 # attention cores; q/k/v are (tensor, column offset) views into packed projections [B, L, X*C]
 # -------------------------------------------------------------------------------------------
-def _desc(q: Tuple[Tensor, int], k: Tuple[Tensor, int], v: Tuple[Tensor, int], o: Tensor, lse: Optional[Tensor], C_: int, scale: float) -> AttnDesc:
-    qt, qo = q; kt, ko = k; vt, vo = v
+def _desc(q: Tuple[Tensor, int], k: Tuple[Tensor, int], v: Optional[Tuple[Tensor, int]], o: Optional[Tensor], lse: Optional[Tensor], C_: int,
+          scale: float) -> AttnDesc:
+    """v / o = None: the fields stay null (attn_probs reads q, k and lse only)."""
+    qt, qo = q; kt, ko = k
     es = qt.element_size()
     d = AttnDesc()
-    d.q, d.k, d.v = _ptr(qt) + qo * es, _ptr(kt) + ko * es, _ptr(vt) + vo * es
-    d.o, d.lse = _ptr(o), _f32(lse)
+    d.q, d.k = _ptr(qt) + qo * es, _ptr(kt) + ko * es
+    d.lse = _f32(lse)
     B, Lq, Lk = qt.shape[0], qt.shape[1], kt.shape[1]
     d.q_bs, d.q_rs = Lq * qt.shape[2], qt.shape[2]
     d.k_bs, d.k_rs = Lk * kt.shape[2], kt.shape[2]
-    d.v_bs, d.v_rs = Lk * vt.shape[2], vt.shape[2]
-    d.o_bs, d.o_rs = Lq * o.shape[2], o.shape[2]
+    if v is not None:
+        vt, vo = v
+        d.v = _ptr(vt) + vo * es
+        d.v_bs, d.v_rs = Lk * vt.shape[2], vt.shape[2]
+    if o is not None:
+        d.o = _ptr(o)
+        d.o_bs, d.o_rs = Lq * o.shape[2], o.shape[2]
     d.B, d.H, d.Lq, d.Lk, d.scale = B, C_ // HEAD_DIM, Lq, Lk, scale
     return d
 
@@ -414,6 +421,23 @@ def attn_bwd(q, k, v, o: Tensor, lse: Tensor, d_o: Tensor, dq, dk, dv, C_: int, 
     st = _stream() if stream is None else stream
     ws = _workspace(nb, o.device, st)
     check(lib.lmv_attn_bwd(C.byref(d), ws.data_ptr(), ws.numel(), dtype_code(o), st), "lmv_attn_bwd")
+
+
+def attn_probs(q, k, lse: Tensor, C_: int, scale: float, head_mean: bool = False, stream: Optional[int] = None) -> Tensor:
+    """The probabilities of the attn_fwd call with these q / k / scale whose log-sum-exp is `lse` [B, H, Lq] (lmv_attn_probs):
+    P = exp(scale q.k^T - lse), fp32 [B, H, Lq, Lk], or the mean over the heads [B, Lq, Lk] (summed h = 0 .. H-1: reproducible bit for bit).
+    q / k = (packed tensor [B,L,XC], column offset) as attn_fwd takes them.  One launch, written once, no workspace."""
+    qt, kt = q[0], k[0]
+    if kt.dtype != qt.dtype:
+        raise TypeError("lemevit_amd: attn_probs needs q and k of one dtype")
+    B, Lq, Lk, H = qt.shape[0], qt.shape[1], kt.shape[1], C_ // HEAD_DIM
+    if tuple(lse.shape) != (B, H, Lq):
+        raise ValueError(f"lemevit_amd: attn_probs needs lse of shape {(B, H, Lq)}, got {tuple(lse.shape)}")
+    d = _desc(q, k, None, None, lse, C_, scale)
+    p = torch.empty((B, Lq, Lk) if head_mean else (B, H, Lq, Lk), device=qt.device, dtype=torch.float32)
+    st = _stream() if stream is None else stream
+    check(lib.lmv_attn_probs(C.byref(d), p.data_ptr(), 1 if head_mean else 0, dtype_code(qt), st), "lmv_attn_probs")
+    return p
 
 
 def attn_fwd_pair(qkvs: Sequence[Tensor], C_: int, scale: float, want_lse: bool = False):
