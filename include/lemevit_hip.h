@@ -45,7 +45,7 @@ enum {
 int lmv_abi_version(void);
 const char* lmv_last_error(void);
 /* Run-time switches of alternative code paths (the GPU parity tests run both sides): these two change / read one.  Keys: "gemm_rs", "gemm_wn",
- * "mlp_rw96", "mlp_tm", "stage_ticket_skew" (test switch) (lemevit_amd/csrc/common.h: LmvConfig); an unknown key is LMV_ERR_SHAPE.  None is read from the
+ * "mlp_rw96", "mlp_tm", "mlp_dx_fused", "stage_ticket_skew" (test switch) (lemevit_amd/csrc/common.h: LmvConfig); an unknown key is LMV_ERR_SHAPE.  None is read from the
  * environment.  Process-wide, not synchronised: set them between launches. */
 int lmv_config_set(const char* key, int value);
 int lmv_config_get(const char* key, int* value);
@@ -149,6 +149,15 @@ int lmv_mlp_fused_supported(int C, int hidden, int dtype);
  * |y - GELU_erf(x)| <= 1.9e-4 absolute, exact 0 / identity beyond |x| >= 4), for x, y fp32 [n] on the device. */
 int lmv_gelu_poly_eval(const float* x, float* y, int64_t n, void* stream);
 int lmv_mlp_fused_fwd(const lmv_mlp_problem* p, int nproblems, const lmv_mlp_weights* w, int C, int hidden, float eps, int dtype, void* stream);
+/* The data gradient of the same MLP half in ONE launch (csrc/fused.hip, a variant of the forward kernel; bf16, the shapes of lmv_mlp_fused_supported):
+ *     dn2 = ((g fc2) * GELU'(u)) fc1      g [rows, C]: gradient of the MLP output, already DropPath-scaled; u [rows, hidden]: the saved fc1
+ *     pre-activations; fc2_wt = mlp.3.weight TRANSPOSED [hidden, C], fc1_wt = mlp.0.weight TRANSPOSED [C, hidden] (lmv_transpose_batch); dn2 [rows, C]:
+ *     gradient of norm2's output (no bias, no residual).  GELU' is the one LMV_ACT_GELU_GRAD evaluates, and du = (g fc2) * GELU'(u) is rounded to bf16
+ *     where lmv_linear_fwd(.., LMV_ACT_GELU_GRAD) rounds it -- but it stays on the chip: the two-launch form writes and re-reads rows x hidden x 2 B.
+ * Up to two problems per launch (image and meta rows).  For a backward pass that wants no weight gradient (nothing else reads du). */
+typedef struct { const void* g; const void* u; void* dn2; int64_t rows; } lmv_mlp_dx_problem;
+int lmv_mlp_dx_fused_supported(int C, int hidden, int dtype);
+int lmv_mlp_dx_fused(const lmv_mlp_dx_problem* p, int nproblems, const void* fc2_wt, const void* fc1_wt, int C, int hidden, int dtype, void* stream);
 int lmv_attn_out_proj_residual(const lmv_linear_problem* p, int nproblems, int C, int dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------------
@@ -181,13 +190,14 @@ int lmv_layernorm_fwd(const lmv_ln_segment* seg, int nseg, const float* gamma, c
 int lmv_layernorm_gelu_fwd(const lmv_ln_segment* seg, int nseg, const float* gamma, const float* beta, int C, float eps,
                            int dtype, void* stream);
 int lmv_layernorm_gelu_bwd(const lmv_ln_segment* seg, int nseg, const float* gamma, const float* beta, float* dgamma, float* dbeta, int C,
-                           void* workspace, size_t workspace_bytes, int dtype, void* stream);
+                           void* workspace, size_t workspace_bytes, int dtype, void* stream);      /* dgamma == dbeta == workspace == NULL: dx only */
 size_t lmv_layernorm_bwd_workspace_bytes(int64_t total_rows, int C, int dtype);
 int lmv_layernorm_bwd(const lmv_ln_segment* seg, int nseg, const float* gamma, float* dgamma, float* dbeta, int C,
                       void* workspace, size_t workspace_bytes, int dtype, void* stream);
 /* The same in two calls: _partial writes dx and leaves `*partial_rows` per-workgroup rows of (dgamma | dbeta) partial sums in
  * `workspace`; _reduce accumulates them into dgamma / dbeta -- on any stream that is ordered behind _partial (the block scheduler
- * keeps it off the critical path).  Results are bit-identical to lmv_layernorm_bwd. */
+ * keeps it off the critical path).  Results are bit-identical to lmv_layernorm_bwd.
+ * dx-only mode: workspace == NULL and partial_rows == NULL -- the same launch writes dx (and dx_scaled) and no partial rows (frozen affine). */
 int lmv_layernorm_bwd_partial(const lmv_ln_segment* seg, int nseg, const float* gamma, int C, void* workspace, size_t workspace_bytes,
                               int* partial_rows, int dtype, void* stream);
 int lmv_layernorm_bwd_reduce(const void* workspace, int partial_rows, int C, float* dgamma, float* dbeta, void* stream);
@@ -196,7 +206,8 @@ int lmv_layernorm_bwd_reduce(const void* workspace, int partial_rows, int C, flo
  *     dy = dY wt^T   (wt = the Linear's weight TRANSPOSED, [C, N]: lmv_transpose_batch),     dx = dres + LN'(dy),     dx_scaled = dx * dx_scale[sample]
  * p[i].a = dY [rows, N], p[i].w = wt; seg[i] as for lmv_layernorm_bwd_partial (x, stats, dres, dx, rows, dx_scale / dx_scaled /
  * rows_per_sample; seg[i].dy is ignored -- dy never reaches memory, the LayerNorm sees it in fp32).  `*partial_rows` rows of (dgamma | dbeta)
- * partial sums are left in `workspace` for lmv_layernorm_bwd_reduce / an LMV_REDUCE_ROWS segment of lmv_reduce_batch. */
+ * partial sums are left in `workspace` for lmv_layernorm_bwd_reduce / an LMV_REDUCE_ROWS segment of lmv_reduce_batch.
+ * dx-only mode: workspace == NULL and partial_rows == NULL -- dx (and dx_scaled) only, no partial rows. */
 /* The forward mirror: a Linear with the residual epilogue followed by the LayerNorm of its output (proj + norm2, models/lemevit.py:562-563,
  * 632-635) in one launch:  out = res + row_scale (a W^T + bias);  seg[i].y = LN(out) (of the ROUNDED out, as a separate launch would read
  * it), seg[i].stats = (mean, rstd) when non-NULL.  bf16, N = 384, K % 64 == 0 (lmv_linear_res_ln_fwd_supported). */
@@ -414,7 +425,7 @@ int lmv_ema_flat(float* ema, const float* param, int64_t n, float decay, void* s
  * half in one kernel); the training form keeps the per-layer launches, whose intermediates the backward pass reads.
  * ------------------------------------------------------------------------------------------ */
 enum { LMV_BLOCK_S = 0, LMV_BLOCK_D = 1, LMV_BLOCK_C = 2 };
-enum { LMV_BLOCK_NO_JOIN = 1, LMV_BLOCK_FUSED = 2 };
+enum { LMV_BLOCK_NO_JOIN = 1, LMV_BLOCK_FUSED = 2, LMV_BLOCK_DATA_ONLY = 4 };
 typedef struct lmv_block_desc {
   int32_t kind, dtype, B, H, W, M, C, hidden;      /* hidden: MLP width (0 = 4 C) */
   float eps;                                       /* LayerNorm eps of norm1 / norm2 (1e-6, models/lemevit.py:513,525) */
@@ -456,6 +467,26 @@ int lmv_block_fwd_range(const lmv_block_desc* d, const void* x, const void* c, v
 /* x, c: the block inputs of the forward call; dx_out / dc_out: gradients of x_out / c_out; dx / dc: gradients of x / c (written). */
 int lmv_block_bwd(const lmv_block_desc* d, const void* x, const void* c, const void* arena, size_t arena_bytes, const void* dx_out, const void* dc_out,
                   void* dx, void* dc, void* scratch, size_t scratch_bytes, void* stream, void* side_stream);
+/* flags & LMV_BLOCK_DATA_ONLY: the block's parameters are frozen, only dx / dc are wanted.  (Additions of ABI 14: detect them by symbol.)
+ *   - lmv_block_arena_bytes returns the reduced saved set xp, st1, pj, ao, lse, t2, st2, u + the attention workspace: the LayerNorm outputs n1 / n2 and the
+ *     GELU output h, which only weight-gradient launches read, are not kept (10 C instead of 16 C per token of an S / D block);
+ *   - a forward call still needs n1 / n2 / h while it runs: lmv_block_fwd_range_scratch takes them from `scratch` (lmv_block_fwd_scratch_bytes; one buffer
+ *     may serve every block).  The buffer is laid out for the whole batch and sliced by image like the arena, so calls over disjoint image ranges share no
+ *     byte of it.  lmv_block_fwd / lmv_block_fwd_range refuse the flag (no transient buffer); without the flag `scratch` is ignored;
+ *   - lmv_block_bwd ignores the g_* pointers (they may be NULL) and enqueues no lmv_linear_dw or slab reduce, no lmv_reduce_batch, no
+ *     lmv_dwconv3x3_bwd_weight_partial and nothing on side_stream -- `x`, which that launch alone reads, may be NULL, so the caller need not keep the
+ *     block's input for the backward pass; the LayerNorm backward launches run in their dx-only mode; with both fc2_wt and fc1_wt
+ *     present, bf16 and lmv_mlp_dx_fused_supported, the MLP half's two dX launches become one lmv_mlp_dx_fused where the "mlp_dx_fused" switch selects it
+ *     (0 off, 1 where it measured faster -- no shape so far --, 2 wherever it applies).  dx / dc are those of the full backward (bit for bit when
+ *     the same dX kernels are selected).
+ * Without the flag none of these functions changes what it enqueues. */
+size_t lmv_block_fwd_scratch_bytes(const lmv_block_desc* d);
+int lmv_block_fwd_range_scratch(const lmv_block_desc* d, const void* x, const void* c, void* x_out, void* c_out, void* arena, size_t arena_bytes, int save,
+                                int image0, int nimages, void* scratch, size_t scratch_bytes, void* stream);
+/* Weight-gradient launches (lmv_linear_dw calls), reduces (lmv_reduce_batch) and side-stream forks that lmv_block_bwd has enqueued since the library was
+ * loaded, plus its lmv_dwconv3x3_bwd_weight_partial launches: a host-side counter, a measurement aid like lmv_debug_launch_timing -- it makes "a data-only
+ * backward launched no weight-gradient work" testable. */
+long long lmv_debug_wgrad_launches(void);
 
 /* ------------------------------------------------------------------------------------------
  * A whole run of "S" blocks as ONE persistent launch (csrc/sstage.hip; inference form, bf16): stage 3 of LeMeViT-Base -- 18 x
@@ -568,7 +599,7 @@ int lmv_debug_stage_error_set(int value);
  * synchronisation lmv_debug_launch_timing_read returns the number of calls and fills their durations [ms], FLOPs and algorithmic HBM bytes; capacity = 0 frees the events.
  * Not for use inside a stream capture; single host thread.  (bench.py's roofline object.) */
 int lmv_debug_launch_timing(int capacity);
-int lmv_debug_launch_timing_read(float* ms, double* flops, double* bytes, int* kinds, int capacity);   /* kinds: 0 forward-form Linear, 1 lmv_sstage_fwd, 2 lmv_dstage_fwd, 3 lmv_stem_fwd */
+int lmv_debug_launch_timing_read(float* ms, double* flops, double* bytes, int* kinds, int capacity);   /* kinds: 0 forward-form Linear, 1 lmv_sstage_fwd, 2 lmv_dstage_fwd, 3 lmv_stem_fwd, ..., 12 lmv_mlp_dx_fused */
 void lmv_stem_debug_timing(void* buf);   /* tools/stem_timeline.py: NULL, or a device buffer of [workgroups][4 waves][8] uint64 s_memtime stamps filled by the next lmv_stem_fwd calls */
 
 #ifdef __cplusplus

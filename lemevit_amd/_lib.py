@@ -19,6 +19,7 @@ LMV_F32, LMV_BF16 = 0, 1
 ACT_NONE, ACT_GELU, ACT_GELU_GRAD, ACT_GELU_BWD = 0, 1, 2, 3
 FOLD_CI_TAP, FOLD_TAP_CI = 0, 1
 ABI_VERSION = 14
+BLOCK_NO_JOIN, BLOCK_FUSED, BLOCK_DATA_ONLY = 1, 2, 4          # lmv_block_desc.flags
 
 
 class LinearProblem(C.Structure):
@@ -29,6 +30,10 @@ class LinearProblem(C.Structure):
 
 class MlpProblem(C.Structure):
     _fields_ = [("x", C.c_void_p), ("out", C.c_void_p), ("row_scale", C.c_void_p), ("rows", C.c_int64), ("rows_per_sample", C.c_int32), ("_pad", C.c_int32)]
+
+
+class MlpDxProblem(C.Structure):
+    _fields_ = [("g", C.c_void_p), ("u", C.c_void_p), ("dn2", C.c_void_p), ("rows", C.c_int64)]
 
 
 class MlpWeights(C.Structure):
@@ -106,6 +111,8 @@ SIGNATURES = {
     "lmv_mlp_fused_supported": (_I, [_I, _I, _I]),
     "lmv_gelu_poly_eval": (_I, [_P, _P, C.c_int64, _P]),
     "lmv_mlp_fused_fwd": (_I, [C.POINTER(MlpProblem), _I, C.POINTER(MlpWeights), _I, _I, _F, _I, _P]),
+    "lmv_mlp_dx_fused_supported": (_I, [_I, _I, _I]),
+    "lmv_mlp_dx_fused": (_I, [C.POINTER(MlpDxProblem), _I, _P, _P, _I, _I, _I, _P]),
     "lmv_attn_out_proj_residual": (_I, [C.POINTER(LinearProblem), _I, _I, _I, _P]),
     "lmv_layernorm_fwd": (_I, [C.POINTER(LnSegment), _I, _P, _P, _I, _F, _I, _P]),
     "lmv_layernorm_gelu_fwd": (_I, [C.POINTER(LnSegment), _I, _P, _P, _I, _F, _I, _P]),
@@ -163,6 +170,9 @@ SIGNATURES = {
     "lmv_block_fwd": (_I, [C.POINTER(BlockDesc), _P, _P, _P, _P, _P, _Z, _I, _P]),
     "lmv_block_fwd_range": (_I, [C.POINTER(BlockDesc), _P, _P, _P, _P, _P, _Z, _I, _I, _I, _P]),
     "lmv_block_bwd": (_I, [C.POINTER(BlockDesc), _P, _P, _P, _Z, _P, _P, _P, _P, _P, _Z, _P, _P]),
+    "lmv_block_fwd_scratch_bytes": (_Z, [C.POINTER(BlockDesc)]),
+    "lmv_block_fwd_range_scratch": (_I, [C.POINTER(BlockDesc), _P, _P, _P, _P, _P, _Z, _I, _I, _I, _P, _Z, _P]),
+    "lmv_debug_wgrad_launches": (C.c_longlong, []),
     "lmv_sstage_supported": (_I, [_I, _I, _I, _I, _I, _I, _I]),
     "lmv_sstage_wpk_bytes": (_Z, [_I, _I]),
     "lmv_sstage_vec_floats": (_Z, [_I, _I]),

@@ -186,6 +186,24 @@ def _join() -> None:
         defer_join(refs[-1][0], refs)
 
 
+def _gn(G, norm: str):
+    """(dgamma, dbeta) accumulators of a LayerNorm; (None, None) in a data-only backward (G is None): ops.layernorm_bwd_multi then writes dx only."""
+    return (None, None) if G is None else (G[norm + ".weight"], G[norm + ".bias"])
+
+
+def _strip_saved(kind: str, saved):
+    """Data-only blocks (frozen parameters): the LayerNorm outputs and the GELU output are read by weight-gradient launches only -- dropped from the saved set."""
+    x0, sa, sm = saved
+    ts, st, _xn, u, _h = sm
+    sm = (ts, st, None, u, None)
+    if kind == "C":
+        xp, c, stx, stc, _xn, _cn, kv, q, ao, lse = sa
+        sa = (xp, c, stx, stc, None, None, kv, q, ao, lse)
+    else:
+        sa = tuple(sa[:2]) + (None,) + tuple(sa[3:])
+    return x0, sa, sm
+
+
 def _empty(rows_like: Tensor, cols: int) -> Tensor:
     return torch.empty(rows_like.shape[:-1] + (cols,), device=rows_like.device, dtype=rows_like.dtype)
 
@@ -223,13 +241,15 @@ def _mlp_bwd(P, G, saved, douts: Sequence[Tensor], ds: Sequence[Optional[Tensor]
     C = ts[0].shape[-1]
     Hd = P["mlp.0.weight"].shape[0]
     g = ops.row_scale_multi(douts, ds)
-    _dw([Prob(gi, hi, G["mlp.3.weight"], bias_grad=G["mlp.3.bias"]) for gi, hi in zip(g, h)], C, Hd)
+    if G is not None:
+        _dw([Prob(gi, hi, G["mlp.3.weight"], bias_grad=G["mlp.3.bias"]) for gi, hi in zip(g, h)], C, Hd)
     du = [torch.empty_like(ui) for ui in u]
     ops.linear_dx([Prob(gi, P["mlp.3.weight"], o, aux=ui) for gi, o, ui in zip(g, du, u)], C, Hd, ACT_GELU_GRAD)
-    _dw([Prob(dui, xi, G["mlp.0.weight"], bias_grad=G["mlp.0.bias"]) for dui, xi in zip(du, xn)], Hd, C)
+    if G is not None:
+        _dw([Prob(dui, xi, G["mlp.0.weight"], bias_grad=G["mlp.0.bias"]) for dui, xi in zip(du, xn)], Hd, C)
     dxn = [torch.empty_like(t) for t in ts]
     ops.linear_dx([Prob(dui, P["mlp.0.weight"], o) for dui, o in zip(du, dxn)], Hd, C)
-    return ops.layernorm_bwd_multi(dxn, ts, st, P["norm2.weight"], G["norm2.weight"], G["norm2.bias"], douts, next_scales=next_ds)
+    return ops.layernorm_bwd_multi(dxn, ts, st, P["norm2.weight"], *_gn(G, "norm2"), douts, next_scales=next_ds)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -265,7 +285,8 @@ def _attn_S_bwd(P, G, saved, douts, ds, g=None):
     ts, st, xn, qkv, ao, lse = saved
     C = ts[0].shape[-1]
     g = ops.row_scale_multi(douts, ds) if g is None else g
-    _dw([Prob(gi, ai, G["attn.proj.weight"], bias_grad=G["attn.proj.bias"]) for gi, ai in zip(g, ao)], C, C)
+    if G is not None:
+        _dw([Prob(gi, ai, G["attn.proj.weight"], bias_grad=G["attn.proj.bias"]) for gi, ai in zip(g, ao)], C, C)
     dao = [torch.empty_like(t) for t in ts]
     ops.linear_dx([Prob(gi, P["attn.proj.weight"], o) for gi, o in zip(g, dao)], C, C)
     dqkv = [torch.empty_like(q) for q in qkv]
@@ -274,10 +295,11 @@ def _attn_S_bwd(P, G, saved, douts, ds, g=None):
     else:                                                # "Sx": image tokens only
         q, dq = qkv[0], dqkv[0]
         ops.attn_bwd((q, 0), (q, C), (q, 2 * C), ao[0], lse[0], dao[0], (dq, 0), (dq, C), (dq, 2 * C), C, ops.SDPA_SCALE)
-    _dw([Prob(dq, xi, G["attn.qkv.weight"], bias_grad=G["attn.qkv.bias"]) for dq, xi in zip(dqkv, xn)], 3 * C, C)
+    if G is not None:
+        _dw([Prob(dq, xi, G["attn.qkv.weight"], bias_grad=G["attn.qkv.bias"]) for dq, xi in zip(dqkv, xn)], 3 * C, C)
     dxn = [torch.empty_like(t) for t in ts]
     ops.linear_dx([Prob(dq, P["attn.qkv.weight"], o) for dq, o in zip(dqkv, dxn)], 3 * C, C)
-    return ops.layernorm_bwd_multi(dxn, ts, st, P["norm1.weight"], G["norm1.weight"], G["norm1.bias"], douts)
+    return ops.layernorm_bwd_multi(dxn, ts, st, P["norm1.weight"], *_gn(G, "norm1"), douts)
 
 
 def _attn_D_fwd(P, ts, ds, save):
@@ -307,18 +329,20 @@ def _attn_D_bwd(P, G, saved, douts, ds, g=None):
     C, N, M = x.shape[-1], x.shape[1], c.shape[1]
     sx, sc = ops.dca_scales(N, M, C)
     g = ops.row_scale_multi(douts, ds) if g is None else g
-    _dw([Prob(g[0], aox, G["attn.proj_x.weight"], bias_grad=G["attn.proj_x.bias"]),
-                   Prob(g[1], aoc, G["attn.proj_c.weight"], bias_grad=G["attn.proj_c.bias"])], C, C)
+    if G is not None:
+        _dw([Prob(g[0], aox, G["attn.proj_x.weight"], bias_grad=G["attn.proj_x.bias"]),
+             Prob(g[1], aoc, G["attn.proj_c.weight"], bias_grad=G["attn.proj_c.bias"])], C, C)
     daox, daoc = torch.empty_like(x), torch.empty_like(c)
     ops.linear_dx([Prob(g[0], P["attn.proj_x.weight"], daox), Prob(g[1], P["attn.proj_c.weight"], daoc)], C, C)
     dq1, dq2 = torch.empty_like(q1), torch.empty_like(q2)
     ops.attn_bwd((q1, 0), (q2, C), (q2, 2 * C), aox, lsex, daox, (dq1, 0), (dq2, C), (dq2, 2 * C), C, sx)
     ops.attn_bwd((q2, 0), (q1, C), (q1, 2 * C), aoc, lsec, daoc, (dq2, 0), (dq1, C), (dq1, 2 * C), C, sc)
-    _dw([Prob(dq1, xn[0], G["attn.qkv1.weight"], bias_grad=G["attn.qkv1.bias"]),
-                   Prob(dq2, xn[1], G["attn.qkv2.weight"], bias_grad=G["attn.qkv2.bias"])], 3 * C, C)
+    if G is not None:
+        _dw([Prob(dq1, xn[0], G["attn.qkv1.weight"], bias_grad=G["attn.qkv1.bias"]),
+             Prob(dq2, xn[1], G["attn.qkv2.weight"], bias_grad=G["attn.qkv2.bias"])], 3 * C, C)
     dxn = [torch.empty_like(x), torch.empty_like(c)]
     ops.linear_dx([Prob(dq1, P["attn.qkv1.weight"], dxn[0]), Prob(dq2, P["attn.qkv2.weight"], dxn[1])], 3 * C, C)
-    return ops.layernorm_bwd_multi(dxn, ts, st, P["norm1.weight"], G["norm1.weight"], G["norm1.bias"], douts)
+    return ops.layernorm_bwd_multi(dxn, ts, st, P["norm1.weight"], *_gn(G, "norm1"), douts)
 
 
 def _attn_D2_fwd(P, ts, ds, save):
@@ -345,8 +369,9 @@ def _attn_D2_bwd(P, G, saved, douts, ds, g=None):
     C, N, M = x.shape[-1], x.shape[1], c.shape[1]
     sx, sc = ops.dca_scales(N, M, C)
     g = ops.row_scale_multi(douts, ds) if g is None else g
-    _dw([Prob(g[0], aox, G["attn.proj_x.weight"], bias_grad=G["attn.proj_x.bias"]),
-                   Prob(g[1], aoc, G["attn.proj_c.weight"], bias_grad=G["attn.proj_c.bias"])], C, C)
+    if G is not None:
+        _dw([Prob(g[0], aox, G["attn.proj_x.weight"], bias_grad=G["attn.proj_x.bias"]),
+             Prob(g[1], aoc, G["attn.proj_c.weight"], bias_grad=G["attn.proj_c.bias"])], C, C)
     daox, daoc = torch.empty_like(x), torch.empty_like(c)
     ops.linear_dx([Prob(g[0], P["attn.proj_x.weight"], daox), Prob(g[1], P["attn.proj_c.weight"], daoc)], C, C)
     dqv1, dkv2 = torch.empty_like(qv1), torch.empty_like(kv2)
@@ -357,11 +382,12 @@ def _attn_D2_bwd(P, G, saved, douts, ds, g=None):
     ops.attn_bwd((kv2, 0), (qv1, 0), (qv1, C), aoc, lsec, daoc, (t_kv2, 0), (t_qv1, 0), (dqv1, C), C, sc)
     dqv1[..., :C] += t_qv1[..., :C]
     dkv2[..., :C] += t_kv2[..., :C]
-    _dw([Prob(dqv1, xn[0], G["attn.qv1.weight"], bias_grad=G["attn.qv1.bias"]),
-                   Prob(dkv2, xn[1], G["attn.kv2.weight"], bias_grad=G["attn.kv2.bias"])], 2 * C, C)
+    if G is not None:
+        _dw([Prob(dqv1, xn[0], G["attn.qv1.weight"], bias_grad=G["attn.qv1.bias"]),
+             Prob(dkv2, xn[1], G["attn.kv2.weight"], bias_grad=G["attn.kv2.bias"])], 2 * C, C)
     dxn = [torch.empty_like(x), torch.empty_like(c)]
     ops.linear_dx([Prob(dqv1, P["attn.qv1.weight"], dxn[0]), Prob(dkv2, P["attn.kv2.weight"], dxn[1])], 2 * C, C)
-    return ops.layernorm_bwd_multi(dxn, ts, st, P["norm1.weight"], G["norm1.weight"], G["norm1.bias"], douts)
+    return ops.layernorm_bwd_multi(dxn, ts, st, P["norm1.weight"], *_gn(G, "norm1"), douts)
 
 
 def _attn_C_fwd(P, xp, c, ds, save):
@@ -385,17 +411,19 @@ def _attn_C_bwd(P, G, saved, dout, ds):
     xp, c, stx, stc, xn, cn, kv, q, ao, lse = saved
     C, M = c.shape[-1], c.shape[1]
     g = dout if ds is None else ops.row_scale(dout, ds, M)
-    _dw([Prob(g, ao, G["attn.proj.weight"], bias_grad=G["attn.proj.bias"])], C, C)
+    if G is not None:
+        _dw([Prob(g, ao, G["attn.proj.weight"], bias_grad=G["attn.proj.bias"])], C, C)
     dao = torch.empty_like(c)
     ops.linear_dx([Prob(g, P["attn.proj.weight"], dao)], C, C)
     dq, dkv = torch.empty_like(q), torch.empty_like(kv)
     ops.attn_bwd((q, 0), (kv, 0), (kv, C), ao, lse, dao, (dq, 0), (dkv, 0), (dkv, C), C, ops.SDPA_SCALE)
-    _dw([Prob(dq, cn, G["attn.q.weight"], bias_grad=G["attn.q.bias"])], C, C)
-    _dw([Prob(dkv, xn, G["attn.kv.weight"], bias_grad=G["attn.kv.bias"])], 2 * C, C)
+    if G is not None:
+        _dw([Prob(dq, cn, G["attn.q.weight"], bias_grad=G["attn.q.bias"])], C, C)
+        _dw([Prob(dkv, xn, G["attn.kv.weight"], bias_grad=G["attn.kv.bias"])], 2 * C, C)
     dcn, dxn = torch.empty_like(c), torch.empty_like(xp)
     ops.linear_dx([Prob(dq, P["attn.q.weight"], dcn)], C, C)
     ops.linear_dx([Prob(dkv, P["attn.kv.weight"], dxn)], 2 * C, C)
-    dc, dxp = ops.layernorm_bwd_multi([dcn, dxn], [c, xp], [stc, stx], P["norm1.weight"], G["norm1.weight"], G["norm1.bias"], [dout, None])
+    dc, dxp = ops.layernorm_bwd_multi([dcn, dxn], [c, xp], [stc, stx], P["norm1.weight"], *_gn(G, "norm1"), [dout, None])
     return dxp, dc
 
 
@@ -403,7 +431,15 @@ def _attn_C_bwd(P, G, saved, dout, ds):
 # whole blocks
 # ------------------------------------------------------------------------------------------------
 def block_forward(kind: str, x: Tensor, c: Tensor, H: int, W: int, P: Dict[str, Tensor],
-                  masks: Sequence[Optional[Tensor]], save: bool, folds=None):
+                  masks: Sequence[Optional[Tensor]], save: bool, folds=None, data_only: bool = False):
+    if data_only and save:
+        xo, co, saved = _block_forward(kind, x, c, H, W, P, masks, True, folds)
+        return xo, co, _strip_saved(kind, saved)
+    return _block_forward(kind, x, c, H, W, P, masks, save, folds)
+
+
+def _block_forward(kind: str, x: Tensor, c: Tensor, H: int, W: int, P: Dict[str, Tensor],
+                   masks: Sequence[Optional[Tensor]], save: bool, folds=None):
     """LeMeBlock.forward (models/lemevit.py:652-660) on token-major x [B,HW,C], c [B,M,C].
     masks: per-sample DropPath scales in the reference's draw order (D/S: x-attn, x-mlp, c-attn, c-mlp; C: c-attn, c-mlp)."""
     xp = ops.dwconv_residual_fwd(x, P["pos_embed.weight"], P["pos_embed.bias"], H, W)          # :546
@@ -448,26 +484,30 @@ def attention_state(kind: str, x: Tensor, c: Tensor, H: int, W: int, P: Dict[str
 
 def block_backward(kind: str, saved, dx: Tensor, dc: Tensor, H: int, W: int, P: Dict[str, Tensor], G: Dict[str, Tensor],
                    masks: Sequence[Optional[Tensor]]) -> Tuple[Tensor, Tensor]:
-    """Gradients wrt the block inputs; parameter gradients are accumulated (fp32) into G."""
+    """Gradients wrt the block inputs; parameter gradients are accumulated (fp32) into G.
+    G = None (a data-only backward: the block's parameters are frozen): no weight-gradient launch, no reduce, nothing on the side stream."""
     x0, sa, sm = saved
     if kind == "C":
         (dc1,) = _mlp_bwd(P, G, sm, [dc], [masks[1]])
         dxp, dc0 = _attn_C_bwd(P, G, sa, dc1, masks[0])
-        _dwconv_w(dxp, x0, G["pos_embed.weight"], G["pos_embed.bias"], H, W)
+        if G is not None:
+            _dwconv_w(dxp, x0, G["pos_embed.weight"], G["pos_embed.bias"], H, W)
         dx0 = ops.dwconv_residual_bwd_data(dxp, P["pos_embed.weight"], H, W)
         _join()
         return (dx0 if dx is None else dx0 + dx), dc0   # the untouched x's pass-through gradient is added by autograd
     if kind == "Sx":
         (dx2,), g_attn = _mlp_bwd(P, G, sm, [dx], [masks[1]], next_ds=[masks[0]])
         (dxp,) = _attn_S_bwd(P, G, sa, [dx2], [masks[0]], g=g_attn)
-        _dwconv_w(dxp, x0, G["pos_embed.weight"], G["pos_embed.bias"], H, W)
+        if G is not None:
+            _dwconv_w(dxp, x0, G["pos_embed.weight"], G["pos_embed.bias"], H, W)
         dx0 = ops.dwconv_residual_bwd_data(dxp, P["pos_embed.weight"], H, W)
         _join()
         return dx0, dc                                      # the meta tokens' gradient passes through
     (dx2, dc1), g_attn = _mlp_bwd(P, G, sm, [dx, dc], [masks[1], masks[3]], next_ds=[masks[0], masks[2]])
     bwd = {"S": _attn_S_bwd, "D": _attn_D_bwd, "D2": _attn_D2_bwd}[kind]
     dxp, dc0 = bwd(P, G, sa, [dx2, dc1], [masks[0], masks[2]], g=g_attn)
-    _dwconv_w(dxp, x0, G["pos_embed.weight"], G["pos_embed.bias"], H, W)
+    if G is not None:
+        _dwconv_w(dxp, x0, G["pos_embed.weight"], G["pos_embed.bias"], H, W)
     dx0 = ops.dwconv_residual_bwd_data(dxp, P["pos_embed.weight"], H, W)
     _join()
     return dx0, dc0

@@ -63,8 +63,40 @@ inline size_t fwd_ws_attn(const Dims& D, int b) {
 inline size_t fwd_ws_off(const Dims& D, int i0) { return i0 <= 0 ? 0 : fwd_ws_attn(D, i0) + (size_t)512 * i0; }
 inline size_t fwd_ws_bytes(const Dims& D, int b) { return fwd_ws_attn(D, b) + (size_t)512 * b + 256; }
 
-void layout_fwd(const Dims& D, Bump& a, Fwd* f) {
+// LMV_BLOCK_DATA_ONLY: n1, n2 and h -- read by weight-gradient launches only -- are not part of the saved set.  A forward call keeps them
+// in the caller's transient buffer `tr` for its own duration (layout_transient); the backward pass (tr == nullptr) never touches them.
+inline bool data_only(const lmv_block_desc* d) { return (d->flags & LMV_BLOCK_DATA_ONLY) != 0; }
+
+void layout_transient(const Dims& D, Bump& t, Fwd* f) {
   const bool cb = D.kind == LMV_BLOCK_C;
+  for (int s = 0; s < 2; ++s) {
+    const bool has = !(cb && s == 0);
+    f->n1[s] = t.take(D.rows[s] * D.C * D.es);
+    f->n2[s] = has ? t.take(D.rows[s] * D.C * D.es) : nullptr;
+    f->h[s] = has ? t.take(D.rows[s] * D.Hd * D.es) : nullptr;
+  }
+}
+
+void layout_fwd(const Dims& D, Bump& a, Fwd* f, bool dataonly = false, Bump* tr = nullptr) {
+  const bool cb = D.kind == LMV_BLOCK_C;
+  if (dataonly) {
+    for (int s = 0; s < 2; ++s) f->n1[s] = f->n2[s] = f->h[s] = nullptr;
+    if (tr) layout_transient(D, *tr, f);
+    f->xp = a.take(D.rows[0] * D.C * D.es);
+    for (int s = 0; s < 2; ++s) {
+      f->st1[s] = (float*)a.take(D.rows[s] * 2 * sizeof(float));
+      f->pj[s] = a.take(D.rows[s] * proj_w(D, s) * D.es);
+      const bool has = !(cb && s == 0);
+      f->ao[s] = has ? a.take(D.rows[s] * D.C * D.es) : nullptr;
+      f->lse[s] = has ? (float*)a.take((size_t)D.B * D.heads * (s == 0 ? D.N : D.M) * sizeof(float)) : nullptr;
+      f->t2[s] = has ? a.take(D.rows[s] * D.C * D.es) : nullptr;
+      f->st2[s] = has ? (float*)a.take(D.rows[s] * 2 * sizeof(float)) : nullptr;
+      f->u[s] = has ? a.take(D.rows[s] * D.Hd * D.es) : nullptr;
+    }
+    f->ws_bytes = fwd_ws_bytes(D, D.B);
+    f->ws = a.take(f->ws_bytes);
+    return;
+  }
   f->xp = a.take(D.rows[0] * D.C * D.es);
   for (int s = 0; s < 2; ++s) {
     f->n1[s] = a.take(D.rows[s] * D.C * D.es);
@@ -183,8 +215,10 @@ struct Side {
   // and +0.8 ms per train step (round 3).
   void* ws_tail; size_t ws_tail_bytes;         // region of the side workspace behind the weight-gradient slabs (dwconv tap sums)
   lmv_reduce_seg segs[LMV_REDUCE_MAX_SEGS]; int nsegs = 0;
+  bool dataonly = false;          // LMV_BLOCK_DATA_ONLY: no weight-gradient launch, no reduce, nothing on the side stream
   hipStream_t begin() {           // the stream a weight-gradient launch goes to, made to wait for everything enqueued on `main` so far
     if (!side) return main;
+    lmv_count_wgrad();
     (void)hipEventRecord(fork, main);
     (void)hipStreamWaitEvent(side, fork, 0);
     used = true;
@@ -239,6 +273,7 @@ struct EventPool {
 EventPool& event_pool() { static EventPool p; return p; }
 
 int dw(Side& sd, const lmv_linear_problem* p, int np, int N, int K, int dtype) {
+  lmv_count_wgrad();
   const size_t need = lmv_linear_dw_workspace_bytes(p, np, N, K, dtype);
   if (need > sd.ws_bytes) LMV_FAIL(LMV_ERR_WORKSPACE, "block_bwd: weight-gradient workspace %zu > %zu bytes", need, sd.ws_bytes);
   return lmv_linear_dw(p, np, N, K, sd.ws, sd.ws_bytes, dtype, sd.begin());
@@ -246,6 +281,7 @@ int dw(Side& sd, const lmv_linear_problem* p, int np, int N, int K, int dtype) {
 // every deferred reduction of the block in one launch, on the side stream behind the launches that produced the partial sums
 int flush_reduces(Side& sd) {
   if (!sd.nsegs) return LMV_OK;
+  lmv_count_wgrad();
   const int rc = lmv_reduce_batch(sd.segs, sd.nsegs, sd.begin());
   sd.nsegs = 0;
   return rc;
@@ -313,6 +349,7 @@ void layout_bwd(const Dims& D, Bump& a, Bwd* b) {
 // LayerNorm backward with the dgamma / dbeta reduce off the critical path: dx on the main stream, the ~5 us reduce launch behind a
 // fork on the weight-gradient side stream (in line when there is none)
 int ln_bwd(Side& sd, const lmv_ln_segment* seg, int nseg, const float* gamma, float* dgamma, float* dbeta, const Dims& D, void* ws, size_t ws_bytes) {
+  if (sd.dataonly) return lmv_layernorm_bwd_partial(seg, nseg, gamma, D.C, nullptr, 0, nullptr, D.dtype, sd.main);      // dx only
   int rows = 0;
   LMV_TRY(lmv_layernorm_bwd_partial(seg, nseg, gamma, D.C, ws, ws_bytes, &rows, D.dtype, sd.main));
   if (sd.nsegs + 1 > LMV_REDUCE_MAX_SEGS) LMV_FAIL(LMV_ERR_WORKSPACE, "block_bwd: too many deferred reductions");
@@ -331,6 +368,7 @@ inline bool dx_ln_fused_ok(const Dims& D, const void* wt, int N) {
 }
 int dx_ln_bwd(Side& sd, const lmv_linear_problem* p, const lmv_ln_segment* seg, int nseg, int N, const float* gamma, float* dgamma, float* dbeta, const Dims& D,
               void* ws, size_t ws_bytes) {
+  if (sd.dataonly) return lmv_linear_dx_ln_bwd(p, seg, nseg, D.C, N, gamma, nullptr, 0, nullptr, D.dtype, sd.main);      // dx only
   int rows = 0;
   LMV_TRY(lmv_linear_dx_ln_bwd(p, seg, nseg, D.C, N, gamma, ws, ws_bytes, &rows, D.dtype, sd.main));
   if (sd.nsegs + 1 > LMV_REDUCE_MAX_SEGS) LMV_FAIL(LMV_ERR_WORKSPACE, "block_bwd: too many deferred reductions");
@@ -339,6 +377,15 @@ int dx_ln_bwd(Side& sd, const lmv_linear_problem* p, const lmv_ln_segment* seg, 
   sg.ws = (const float*)ws; sg.out_w = dgamma; sg.out_b = dbeta; sg.slab_stride = 2 * D.C; sg.nw = D.C; sg.nslabs = rows; sg.nb = D.C;
   sg.kind = LMV_REDUCE_ROWS; sg.mode = 0;
   return LMV_OK;
+}
+
+// Data-only backward: the fused dX of the MLP half (lmv_mlp_dx_fused) instead of the two dX launches.  mlp_dx_fused = 1 (auto) takes it
+// only on shapes where it measured faster than the two launches by more than the run-to-run spread (tools/frozen_params_probe.py):
+// none so far -- it is built, tested and selected with mlp_dx_fused = 2.
+inline bool mlp_dx_fused_on(const lmv_block_desc* d, const Dims& D) {
+  const int mode = lmv_config().mlp_dx_fused;
+  if (mode == 0 || D.dtype != LMV_BF16 || !d->fc2_wt || !d->fc1_wt || !lmv_mlp_dx_fused_supported(D.C, D.Hd, D.dtype)) return false;
+  return mode == 2;
 }
 
 // MLP half backward (blocks.py::_mlp_bwd): douts = gradients of the block outputs, returns dt2 (gradient of the MLP half's input) and, where the
@@ -355,8 +402,24 @@ int mlp_bwd(const lmv_block_desc* d, const Dims& D, const Fwd& f, const Bwd& b, 
   }
   if (nrs) LMV_TRY(lmv_row_scale_multi(rs, nrs, D.C, D.dtype, st));
   lmv_linear_problem p[2];
-  for (int i = 0; i < ns; ++i) { const int s = s0 + i; p[i] = prob(g[s], f.h[s], d->g_fc2_w, D.rows[s]); p[i].bias_grad = d->g_fc2_b; }
-  LMV_TRY(dw(sd, p, ns, D.C, D.Hd, D.dtype));
+  lmv_ln_segment seg[2] = {};
+  for (int i = 0; i < ns; ++i) {
+    const int s = s0 + i;
+    seg[i].x = f.t2[s]; seg[i].dy = b.dn2[s]; seg[i].stats = f.st2[s]; seg[i].dres = douts[s]; seg[i].dx = b.dt2[s]; seg[i].rows = D.rows[s];
+    g2_out[s] = b.dt2[s];
+    if (nds && nds[s]) { seg[i].dx_scale = nds[s]; seg[i].dx_scaled = b.g2[s]; seg[i].rows_per_sample = s == 0 ? D.N : D.M; g2_out[s] = b.g2[s]; }
+  }
+  if (sd.dataonly && mlp_dx_fused_on(d, D)) {
+    // no weight gradient reads du: dn2 = ((g W2) * GELU'(u)) W1 in ONE launch, du never leaves the chip (csrc/fused.hip)
+    lmv_mlp_dx_problem q[2] = {};
+    for (int i = 0; i < ns; ++i) { const int s = s0 + i; q[i].g = g[s]; q[i].u = f.u[s]; q[i].dn2 = b.dn2[s]; q[i].rows = D.rows[s]; }
+    LMV_TRY(lmv_mlp_dx_fused(q, ns, d->fc2_wt, d->fc1_wt, D.C, D.Hd, D.dtype, st));
+    return ln_bwd(sd, seg, ns, d->n2_w, d->g_n2_w, d->g_n2_b, D, b.ws_ln[0], b.ws_ln_bytes);
+  }
+  if (!sd.dataonly) {
+    for (int i = 0; i < ns; ++i) { const int s = s0 + i; p[i] = prob(g[s], f.h[s], d->g_fc2_w, D.rows[s]); p[i].bias_grad = d->g_fc2_b; }
+    LMV_TRY(dw(sd, p, ns, D.C, D.Hd, D.dtype));
+  }
   if (d->fc2_wt && D.dtype == LMV_BF16) {
     // dX of fc2 as a forward-form GEMM on the transposed weight copy [hidden, C]: du = (g W2) * GELU'(u) = (g . fc2_wt^T) * GELU'(u)
     // (the register-stationary kernel takes it for C = 192 / 384: csrc/rsgemm.hip)
@@ -366,8 +429,10 @@ int mlp_bwd(const lmv_block_desc* d, const Dims& D, const Fwd& f, const Bwd& b, 
     for (int i = 0; i < ns; ++i) { const int s = s0 + i; p[i] = prob(g[s], d->fc2_w, b.du[s], D.rows[s]); p[i].aux = f.u[s]; }
     LMV_TRY(lmv_linear_dx(p, ns, D.C, D.Hd, LMV_ACT_GELU_GRAD, D.dtype, st));
   }
-  for (int i = 0; i < ns; ++i) { const int s = s0 + i; p[i] = prob(b.du[s], f.n2[s], d->g_fc1_w, D.rows[s]); p[i].bias_grad = d->g_fc1_b; }
-  LMV_TRY(dw(sd, p, ns, D.Hd, D.C, D.dtype));
+  if (!sd.dataonly) {
+    for (int i = 0; i < ns; ++i) { const int s = s0 + i; p[i] = prob(b.du[s], f.n2[s], d->g_fc1_w, D.rows[s]); p[i].bias_grad = d->g_fc1_b; }
+    LMV_TRY(dw(sd, p, ns, D.Hd, D.C, D.dtype));
+  }
   const bool fuse2 = dx_ln_fused_ok(D, d->fc1_wt, D.Hd);      // dX of fc1 + LayerNorm-2 backward in one kernel
   if (fuse2) {
   } else if (d->fc1_wt && D.dtype == LMV_BF16) {      // dX of fc1 as a forward-form GEMM on the transposed weight copy [C, hidden] (csrc/wngemm.hip at C = 384)
@@ -376,13 +441,6 @@ int mlp_bwd(const lmv_block_desc* d, const Dims& D, const Fwd& f, const Bwd& b, 
   } else {
     for (int i = 0; i < ns; ++i) { const int s = s0 + i; p[i] = prob(b.du[s], d->fc1_w, b.dn2[s], D.rows[s]); }
     LMV_TRY(lmv_linear_dx(p, ns, D.Hd, D.C, LMV_ACT_NONE, D.dtype, st));
-  }
-  lmv_ln_segment seg[2] = {};
-  for (int i = 0; i < ns; ++i) {
-    const int s = s0 + i;
-    seg[i].x = f.t2[s]; seg[i].dy = b.dn2[s]; seg[i].stats = f.st2[s]; seg[i].dres = douts[s]; seg[i].dx = b.dt2[s]; seg[i].rows = D.rows[s];
-    g2_out[s] = b.dt2[s];
-    if (nds && nds[s]) { seg[i].dx_scale = nds[s]; seg[i].dx_scaled = b.g2[s]; seg[i].rows_per_sample = s == 0 ? D.N : D.M; g2_out[s] = b.g2[s]; }
   }
   if (fuse2) {
     for (int i = 0; i < ns; ++i) { const int s = s0 + i; p[i] = prob(b.du[s], d->fc1_wt, b.dn2[s], D.rows[s]); }
@@ -413,8 +471,17 @@ extern "C" size_t lmv_block_arena_bytes(const lmv_block_desc* d) {
   if (dims_of(d, &D)) return 0;
   Bump a{nullptr, 0, 0};
   Fwd f;
-  layout_fwd(D, a, &f);
+  layout_fwd(D, a, &f, data_only(d));
   return a.off + 256;
+}
+
+extern "C" size_t lmv_block_fwd_scratch_bytes(const lmv_block_desc* d) {
+  Dims D;
+  if (dims_of(d, &D)) return 0;
+  Bump t{nullptr, 0, 0};
+  Fwd f;
+  layout_transient(D, t, &f);
+  return t.off + 256;
 }
 
 extern "C" size_t lmv_block_bwd_scratch_bytes(const lmv_block_desc* d) {
@@ -432,16 +499,25 @@ int block_fwd_body(const lmv_block_desc* d, const Dims& D, const Fwd& f, const v
 
 extern "C" int lmv_block_fwd_range(const lmv_block_desc* d, const void* x, const void* c, void* x_out, void* c_out, void* arena, size_t arena_bytes, int save,
                                    int image0, int nimages, void* stream) {
+  return lmv_block_fwd_range_scratch(d, x, c, x_out, c_out, arena, arena_bytes, save, image0, nimages, nullptr, 0, stream);
+}
+
+extern "C" int lmv_block_fwd_range_scratch(const lmv_block_desc* d, const void* x, const void* c, void* x_out, void* c_out, void* arena, size_t arena_bytes, int save,
+                                           int image0, int nimages, void* scratch, size_t scratch_bytes, void* stream) {
   Dims DF;
   LMV_TRY(dims_of(d, &DF));
   LMV_TRY(check_ptrs(d, false));
   const bool cb = DF.kind == LMV_BLOCK_C;
   if (!x || !c || !c_out || (!cb && !x_out) || !arena || !lmv_aligned16(arena)) LMV_FAIL(LMV_ERR_SHAPE, "block_fwd: null / misaligned tensor");
   if (image0 < 0 || nimages <= 0 || image0 + nimages > DF.B) LMV_FAIL(LMV_ERR_SHAPE, "block_fwd: images [%d, %d) outside the batch of %d", image0, image0 + nimages, DF.B);
+  const bool dataonly = data_only(d);
+  if (dataonly && (!scratch || !lmv_aligned16(scratch))) LMV_FAIL(LMV_ERR_SHAPE, "block_fwd: LMV_BLOCK_DATA_ONLY needs the transient buffer of lmv_block_fwd_range_scratch");
   Bump a{(unsigned char*)arena, 0, arena_bytes};
+  Bump t{(unsigned char*)scratch, 0, scratch_bytes};
   Fwd f;
-  layout_fwd(DF, a, &f);
+  layout_fwd(DF, a, &f, dataonly, &t);
   if (a.off > arena_bytes) LMV_FAIL(LMV_ERR_WORKSPACE, "block_fwd: arena %zu < %zu bytes", arena_bytes, a.off);
+  if (dataonly && t.off > scratch_bytes) LMV_FAIL(LMV_ERR_WORKSPACE, "block_fwd: transient buffer %zu < %zu bytes", scratch_bytes, t.off);
   if (image0 == 0 && nimages == DF.B) return block_fwd_body(d, DF, f, x, c, x_out, c_out, save, stream);
   // a range of images: every tensor of the arena is [rows, width] with the images outermost, so the range is a contiguous slice of each
   lmv_block_desc dr = *d;
@@ -552,12 +628,15 @@ extern "C" int lmv_block_bwd(const lmv_block_desc* d, const void* x, const void*
                              void* scratch, size_t scratch_bytes, void* stream, void* side_stream) {
   Dims D;
   LMV_TRY(dims_of(d, &D));
-  LMV_TRY(check_ptrs(d, true));
+  const bool dataonly = data_only(d);
+  LMV_TRY(check_ptrs(d, !dataonly));
   const bool cb = D.kind == LMV_BLOCK_C;
-  if (!x || !c || !arena || !dc_out || (!cb && !dx_out) || !dx || !dc || !scratch || !lmv_aligned16(scratch)) LMV_FAIL(LMV_ERR_SHAPE, "block_bwd: null / misaligned tensor");
+  if (dataonly) side_stream = nullptr;
+  // (x is read by the position convolution's weight gradient only: a data-only caller need not keep it and may pass NULL)
+  if ((!x && !dataonly) || !c || !arena || !dc_out || (!cb && !dx_out) || !dx || !dc || !scratch || !lmv_aligned16(scratch)) LMV_FAIL(LMV_ERR_SHAPE, "block_bwd: null / misaligned tensor");
   Bump a{(unsigned char*)const_cast<void*>(arena), 0, arena_bytes};
   Fwd f;
-  layout_fwd(D, a, &f);
+  layout_fwd(D, a, &f, dataonly);
   if (a.off > arena_bytes) LMV_FAIL(LMV_ERR_WORKSPACE, "block_bwd: arena %zu < %zu bytes", arena_bytes, a.off);
   Bump s{(unsigned char*)scratch, 0, scratch_bytes};
   Bwd b;
@@ -566,6 +645,7 @@ extern "C" int lmv_block_bwd(const lmv_block_desc* d, const void* x, const void*
   Side sd{};
   sd.main = (hipStream_t)stream; sd.side = (hipStream_t)side_stream; sd.ws = b.ws_side; sd.ws_bytes = b.ws_side_bytes;
   sd.ws_tail = b.ws_conv; sd.ws_tail_bytes = b.ws_conv_bytes;
+  sd.dataonly = dataonly;
   if (side_stream) LMV_TRY(event_pool().take(&sd.fork, &sd.join));
   hipStream_t st = sd.main;
   const int C = D.C, N = D.N, M = D.M;
@@ -581,17 +661,21 @@ extern "C" int lmv_block_bwd(const lmv_block_desc* d, const void* x, const void*
       const void* dc1 = b.dt2[1];
       const void* g = dc1;
       if (d->masks[0]) { LMV_TRY(lmv_row_scale(dc1, d->masks[0], b.g2[1], D.rows[1], C, M, D.dtype, st)); g = b.g2[1]; }
-      p[0] = prob(g, f.ao[1], d->g_attn_w[2], D.rows[1]); p[0].bias_grad = d->g_attn_b[2];
-      LMV_TRY(dw(sd, p, 1, C, C, D.dtype));
+      if (!dataonly) {
+        p[0] = prob(g, f.ao[1], d->g_attn_w[2], D.rows[1]); p[0].bias_grad = d->g_attn_b[2];
+        LMV_TRY(dw(sd, p, 1, C, C, D.dtype));
+      }
       p[0] = prob(g, d->attn_w[2], b.dao[1], D.rows[1]);
       LMV_TRY(lmv_linear_dx(p, 1, C, C, LMV_ACT_NONE, D.dtype, st));
       attn_desc(&ad[0], D, f.pj[1], C, 0, f.pj[0], 2 * C, 0, f.pj[0], 2 * C, C, f.ao[1], f.lse[1], M, N, SDPA_SCALE);
       attn_grads(&ad[0], D, b.dao[1], b.dpj[1], 0, b.dpj[0], 0, b.dpj[0], C);
       LMV_TRY(lmv_attn_bwd(&ad[0], b.ws_main, b.ws_main_bytes, D.dtype, st));
-      p[0] = prob(b.dpj[1], f.n1[1], d->g_attn_w[0], D.rows[1]); p[0].bias_grad = d->g_attn_b[0];
-      LMV_TRY(dw(sd, p, 1, C, C, D.dtype));
-      p[0] = prob(b.dpj[0], f.n1[0], d->g_attn_w[1], D.rows[0]); p[0].bias_grad = d->g_attn_b[1];
-      LMV_TRY(dw(sd, p, 1, 2 * C, C, D.dtype));
+      if (!dataonly) {
+        p[0] = prob(b.dpj[1], f.n1[1], d->g_attn_w[0], D.rows[1]); p[0].bias_grad = d->g_attn_b[0];
+        LMV_TRY(dw(sd, p, 1, C, C, D.dtype));
+        p[0] = prob(b.dpj[0], f.n1[0], d->g_attn_w[1], D.rows[0]); p[0].bias_grad = d->g_attn_b[1];
+        LMV_TRY(dw(sd, p, 1, 2 * C, C, D.dtype));
+      }
       p[0] = prob(b.dpj[1], d->attn_w[0], b.dn1[1], D.rows[1]);
       LMV_TRY(lmv_linear_dx(p, 1, C, C, LMV_ACT_NONE, D.dtype, st));
       p[0] = prob(b.dpj[0], d->attn_w[1], b.dn1[0], D.rows[0]);
@@ -606,8 +690,10 @@ extern "C" int lmv_block_bwd(const lmv_block_desc* d, const void* x, const void*
       const float* nds[2] = {d->masks[0], d->masks[2]};
       LMV_TRY(mlp_bwd(d, D, f, b, 0, douts, ds, nds, g2, sd));
       const bool sh = D.kind == LMV_BLOCK_S;
-      for (int s2 = 0; s2 < 2; ++s2) { p[s2] = prob(g2[s2], f.ao[s2], sh ? d->g_attn_w[1] : d->g_attn_w[2 + s2], D.rows[s2]); p[s2].bias_grad = sh ? d->g_attn_b[1] : d->g_attn_b[2 + s2]; }
-      LMV_TRY(dw(sd, p, 2, C, C, D.dtype));
+      if (!dataonly) {
+        for (int s2 = 0; s2 < 2; ++s2) { p[s2] = prob(g2[s2], f.ao[s2], sh ? d->g_attn_w[1] : d->g_attn_w[2 + s2], D.rows[s2]); p[s2].bias_grad = sh ? d->g_attn_b[1] : d->g_attn_b[2 + s2]; }
+        LMV_TRY(dw(sd, p, 2, C, C, D.dtype));
+      }
       if (sh && d->attn_wt[1] && D.dtype == LMV_BF16) {      // dX of proj / qkv on the transposed weight copies (forward-form GEMM, csrc/wngemm.hip)
         for (int s2 = 0; s2 < 2; ++s2) p[s2] = prob(g2[s2], d->attn_wt[1], b.dao[s2], D.rows[s2]);
         LMV_TRY(lmv_linear_fwd(p, 2, C, C, LMV_ACT_NONE, D.dtype, st));
@@ -632,8 +718,10 @@ extern "C" int lmv_block_bwd(const lmv_block_desc* d, const void* x, const void*
         LMV_TRY(lmv_attn_bwd(&ad[0], b.ws_main, b.ws_main_bytes, D.dtype, st));
         LMV_TRY(lmv_attn_bwd(&ad[1], b.ws_main, b.ws_main_bytes, D.dtype, st));
       }
-      for (int s2 = 0; s2 < 2; ++s2) { p[s2] = prob(b.dpj[s2], f.n1[s2], sh ? d->g_attn_w[0] : d->g_attn_w[s2], D.rows[s2]); p[s2].bias_grad = sh ? d->g_attn_b[0] : d->g_attn_b[s2]; }
-      LMV_TRY(dw(sd, p, 2, 3 * C, C, D.dtype));
+      if (!dataonly) {
+        for (int s2 = 0; s2 < 2; ++s2) { p[s2] = prob(b.dpj[s2], f.n1[s2], sh ? d->g_attn_w[0] : d->g_attn_w[s2], D.rows[s2]); p[s2].bias_grad = sh ? d->g_attn_b[0] : d->g_attn_b[s2]; }
+        LMV_TRY(dw(sd, p, 2, 3 * C, C, D.dtype));
+      }
       const bool fuse1 = sh && dx_ln_fused_ok(D, d->attn_wt[0], 3 * C);      // dX of qkv + LayerNorm-1 backward in one kernel
       if (fuse1) {
       } else if (sh && d->attn_wt[0] && D.dtype == LMV_BF16) {
@@ -653,10 +741,11 @@ extern "C" int lmv_block_bwd(const lmv_block_desc* d, const void* x, const void*
         LMV_TRY(ln_bwd(sd, seg, 2, d->n1_w, d->g_n1_w, d->g_n1_b, D, b.ws_ln[1], b.ws_ln_bytes));
       }
     }
-    {
+    if (!dataonly) {
       void* ws = sd.ws_tail;
       if (sd.nsegs + 1 > LMV_REDUCE_MAX_SEGS) LMV_FAIL(LMV_ERR_WORKSPACE, "block_bwd: too many deferred reductions");
       int rows = 0;
+      lmv_count_wgrad();
       LMV_TRY(lmv_dwconv3x3_bwd_weight_partial(b.dxp, x, D.B, D.H, D.W, C, ws, sd.ws_tail_bytes, &rows, D.dtype, sd.begin()));
       lmv_reduce_seg& sg = sd.segs[sd.nsegs++];
       sg = lmv_reduce_seg{};

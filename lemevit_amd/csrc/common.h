@@ -33,13 +33,15 @@ void lmv_timing_end(void* stream);
 void lmv_timing_set_kind(int kind);
 // launch kinds of the probe = kernels (bench.py names the kind with the largest total as roofline.kernel)
 enum { LMV_TK_GEMM_NT = 0, LMV_TK_SSTAGE = 1, LMV_TK_DSTAGE = 2, LMV_TK_STEM = 3, LMV_TK_GEMM_DX = 4, LMV_TK_GEMM_DW = 5, LMV_TK_SPLITK_REDUCE = 6, LMV_TK_ATTN_FWD = 7,
-       LMV_TK_RS_GEMM = 8, LMV_TK_WN_GEMM = 9, LMV_TK_ATTN_BWD = 10, LMV_TK_RSW_GEMM = 11 };
+       LMV_TK_RS_GEMM = 8, LMV_TK_WN_GEMM = 9, LMV_TK_ATTN_BWD = 10, LMV_TK_RSW_GEMM = 11, LMV_TK_MLP_DX = 12 };
 struct LmvTimedLaunch {          // RAII bracket of one entry point (or of one launch inside it)
   void* st; bool on;
   LmvTimedLaunch(void* stream, double flops, double bytes, int kind = 0) : st(stream), on(g_lmv_timing_on) { if (on) lmv_timing_begin(st, flops, bytes, kind); }
   void kind(int k) { if (on) lmv_timing_set_kind(k); }
   ~LmvTimedLaunch() { if (on) lmv_timing_end(st); }
 };
+// lmv_debug_wgrad_launches (misc.hip): one more weight-gradient launch, reduce or side-stream fork was enqueued
+void lmv_count_wgrad();
 #define LMV_CHECK_LAUNCH(name)                                                \
   do {                                                                        \
     hipError_t e__ = hipGetLastError();                                       \
@@ -97,6 +99,7 @@ struct LmvConfig {
   int gemm_wn = 1;            // 1: whole-width kernel (wngemm.hip) for the 384-wide forward-form launches where it measured faster; 0: off; 2: wherever it applies
   int mlp_rw96 = 1;           // 1: the C = 96 one-kernel MLP with both weight matrices resident in LDS (csrc/rwmlp.hip) instead of the tile-streaming form
   int mlp_tm = 0;             // 0 = auto: token rows per workgroup of the fused MLP kernel (64 / 128)
+  int mlp_dx_fused = 1;       // data-only block backward: the one-launch dX of the MLP half (lmv_mlp_dx_fused).  0: off; 1: where it measured faster (block.hip); 2: wherever it applies
   int stage_ticket_skew = 0;  // the persistent stage kernels ask ticket counter (XCC_ID + skew * hash(blockIdx)) & 7 first -- a simulated foreign workgroup -> XCD placement
 };
 LmvConfig& lmv_config();

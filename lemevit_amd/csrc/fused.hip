@@ -51,7 +51,7 @@ __global__ __launch_bounds__(256) void ln_fold_kernel(const float* __restrict__ 
 }
 
 // ---- mlp_fused_kernel ------------------------------------------------------------------------------------------------------------------
-struct MlpProb { const bf16_t* x; bf16_t* out; const float* row_scale; int rows, rps, tile_begin, pad_; };
+struct MlpProb { const bf16_t* x; bf16_t* out; const float* row_scale; int rows, rps, tile_begin, pad_; const bf16_t* u; };      // u: DX mode, the saved fc1 pre-activations [rows, Hd]
 struct MlpArgs {
   MlpProb p[2];
   const bf16_t* w1; const float* s1; const float* b1;      // folded fc1: [Hd, C], colsum [Hd], bias [Hd]
@@ -63,7 +63,7 @@ struct MlpArgs {
 #endif
 };
 
-template <int C, int TM> struct MlpCfg {
+template <int C, int TM, bool DX = false> struct MlpCfg {
   static_assert(C % 32 == 0 && C >= 64 && C <= 384, "mlp_fused: C must be a multiple of 32 in [64, 384]");
   static_assert(TM == 64 || TM == 128, "mlp_fused: 64 or 128 token rows per workgroup");
   static constexpr int NW = TM / 16;                         // waves: (TM / 32) x 2, each 32 rows x 64 columns of a 128-wide step
@@ -81,12 +81,13 @@ template <int C, int TM> struct MlpCfg {
   static constexpr int BUDGET = TM == 128 ? 160 * 1024 : 80 * 1024;
   // folded fc1 colsum | bias of the whole hidden dimension (<= 4 C) in LDS when it fits beside a 2-slot ring (else read from L2)
   static constexpr int SB_WANT = 2 * 4 * C * 4;
-  static constexpr bool SB = X_BYTES + 2 * HT + SB_WANT + 2 * SLOT <= BUDGET;
+  static constexpr bool SB = !DX && X_BYTES + 2 * HT + SB_WANT + 2 * SLOT <= BUDGET;      // (DX: no LayerNorm, no bias)
   static constexpr int SB_BYTES = SB ? SB_WANT : 0;
   static constexpr int ROOM = (BUDGET - X_BYTES - 2 * HT - SB_BYTES) / SLOT;
   static constexpr int NSLOT = ROOM > 4 ? 4 : ROOM;          // ring depth: NSLOT - 1 weight panels in flight under every step
   static_assert(NSLOT >= 2, "mlp_fused: no room for the weight ring");
   static constexpr int LDS = X_BYTES + 2 * HT + SB_BYTES + NSLOT * SLOT;      // X | H (2 k-tiles) | colsum, bias | ring
+  static_assert(LDS <= BUDGET && BUDGET <= 160 * 1024, "mlp_fused: the LDS image outgrew the CU's 160 KB (80 KB: two workgroups per CU)");
   static constexpr int NI1 = (PANEL * BK1 * 2 / 1024) / NW, NI2 = 16 / NW;    // LDS-DMA instructions per wave: GEMM1 / GEMM2 panel
   static constexpr int NIX = (TM * BK1 * 2 / 1024) / NW;                      // ... and per X k-tile
   static constexpr int nld(int t) { return (t % STEPS) < KT1 ? NI1 : NI2; }
@@ -149,9 +150,16 @@ __device__ __forceinline__ unsigned opaque(unsigned v) { asm volatile("" : "+v"(
 #ifndef LMV_DUAL_MAXC
 #define LMV_DUAL_MAXC 320      // widest C whose steps keep BOTH k-halves' fragments in registers (second half's reads under the first half's MFMAs)
 #endif
-template <int C, int TM>
+// DX = true (lmv_mlp_dx_fused): the SAME data flow computes the data gradient of the MLP half, dn2 = ((g W2) * GELU'(u)) W1 --
+//     X = the 128 rows of g (the DropPath-scaled gradient of the MLP output), no LayerNorm statistics;
+//     GEMM1 streams fc2_wt [Hd, C] in fc1's place: acc1 = g . fc2_wt[j]^T = (g W2)[:, chunk j];
+//     on the accumulators: du = acc1 * GELU'(u) with the u tile read from the saved set (the GELU' of LMV_ACT_GELU_GRAD, rounded to bf16
+//     where the two-launch path rounds du) -> H;
+//     GEMM2 streams fc1_wt [C, Hd] in fc2's place: acc2 += du . fc1_wt[:, j]^T;  epilogue: dn2 = acc2, no bias, no residual.
+// du [rows, 4C] never leaves the chip.
+template <int C, int TM, bool DX = false>
 __global__ __launch_bounds__(TM * 4) void mlp_fused_kernel(const MlpArgs g) {
-  using K = MlpCfg<C, TM>;
+  using K = MlpCfg<C, TM, DX>;
   using CF = Cfg<TM / 32, 2, 2>;                             // waves of 32 x 64 over a TM x 128 step tile
   constexpr int BK1 = K::BK1, KT1 = K::KT1, NP = K::NP, STEPS = K::STEPS, NW = K::NW, NTHR = TM * 4;
   constexpr bool DUAL = C <= LMV_DUAL_MAXC;                  // register budget: 256 per lane at 2 waves per SIMD (C = 384: no room beside the prefetched colsum / bias; measured equal anyway)
@@ -222,7 +230,8 @@ __global__ __launch_bounds__(TM * 4) void mlp_fused_kernel(const MlpArgs g) {
 
   // LayerNorm statistics of this wave's 32 rows: lane -> row (lane & 15) of row tile t, k-chunks of lane group lane >> 4 (the MFMA
   // fragment pattern, so every chunk of a row is read by exactly one lane); two passes over LDS, fp32
-  float mu[2], rs[2];
+  float mu[2] = {0.f, 0.f}, rs[2] = {1.f, 1.f};
+  if constexpr (!DX)
 #pragma unroll
   for (int t = 0; t < 2; ++t) {
     float s = 0.f;
@@ -280,10 +289,22 @@ __global__ __launch_bounds__(TM * 4) void mlp_fused_kernel(const MlpArgs g) {
       for (int q = 0; q < 4; ++q) acc1[i][q] = f32x4_t{0.f, 0.f, 0.f, 0.f};
     const bool more = j + 1 < nchunks;                        // wave-uniform: panels of the next chunk exist
     f32x4_t s4[4], b4[4];                                     // folded colsum / bias of this lane's 16 hidden columns of the chunk
+    uint2 ug[DX ? 2 : 1][DX ? 4 : 1];                         // DX: the lane's 2 x 4 x 4 values of the u tile of this chunk
     static_for<STEPS>([&](auto tc) {
       constexpr int t = decltype(tc)::value;
       STAMP(0);
-      if constexpr (t == KT1 - 1 && !K::SB) {
+      if constexpr (DX && t == 0) {
+        // requested ahead of the chunk's first panel, like colsum / bias below: older than every ring request the step's wait leaves in
+        // flight, so they have landed behind the barrier that closes GEMM1 (rows past the matrix are clamped, never masked)
+        const int n0 = j * 128 + wn * 64 + (lane >> 4) * 4;
+#pragma unroll
+        for (int ti = 0; ti < 2; ++ti) {
+          const bf16_t* ur = Q.u + (int64_t)min(m0 + wm * 32 + ti * 16 + (lane & 15), M - 1) * Hd + n0;
+#pragma unroll
+          for (int tj = 0; tj < 4; ++tj) ug[ti][tj] = *reinterpret_cast<const uint2*>(ur + tj * 16);
+        }
+      }
+      if constexpr (!DX && t == KT1 - 1 && !K::SB) {
         // no room for them in LDS (C = 384): requested from L2 one whole step before the GELU pass needs them -- at the point of use
         // the round trip (~2k cycles under load, s_memtime timeline) stood exposed in every chunk: 17 % of the kernel
         const int n0 = j * 128 + wn * 64 + (lane >> 4) * 4;
@@ -339,12 +360,19 @@ __global__ __launch_bounds__(TM * 4) void mlp_fused_kernel(const MlpArgs g) {
             const int r = wm * 32 + ti * 16 + (lane & 15);
             const float a = rs[ti], ms = mu[ti];
             const f32x4_t v = acc1[ti][tj];
+            const int kc = tj * 2 + (lane >> 5);
+            if constexpr (DX) {
+              const uint2 uu = ug[ti][tj];
+              const float d0 = v[0] * gelu_grad_fast_f(__uint_as_float(uu.x << 16)), d1 = v[1] * gelu_grad_fast_f(__uint_as_float(uu.x & 0xffff0000u));
+              const float d2 = v[2] * gelu_grad_fast_f(__uint_as_float(uu.y << 16)), d3 = v[3] * gelu_grad_fast_f(__uint_as_float(uu.y & 0xffff0000u));
+              lds_st_b64(lH + wn * K::HT + r * 128 + ((kc ^ swz_n<128>(r)) << 4) + ((lane >> 4) & 1) * 8, pack_bf2(d0, d1), pack_bf2(d2, d3));
+              continue;
+            }
             // u = rstd (acc - mean colsum) + bias' = rstd acc + (bias' - rstd mean colsum), two columns per packed instruction
             const f32x2_t a2 = {a, a}, nm = {-a * ms, -a * ms};
             const f32x2_t u01 = __builtin_elementwise_fma(a2, f32x2_t{v[0], v[1]}, __builtin_elementwise_fma(nm, f32x2_t{s4[tj][0], s4[tj][1]}, f32x2_t{b4[tj][0], b4[tj][1]}));
             const f32x2_t u23 = __builtin_elementwise_fma(a2, f32x2_t{v[2], v[3]}, __builtin_elementwise_fma(nm, f32x2_t{s4[tj][2], s4[tj][3]}, f32x2_t{b4[tj][2], b4[tj][3]}));
             const f32x2_t h01 = gelu_poly2(u01), h23 = gelu_poly2(u23);
-            const int kc = tj * 2 + (lane >> 5);
             lds_st_b64(lH + wn * K::HT + r * 128 + ((kc ^ swz_n<128>(r)) << 4) + ((lane >> 4) & 1) * 8, pack_bf2(h01[0], h01[1]), pack_bf2(h23[0], h23[1]));
           }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // (not __syncthreads: hipcc would drain the weight panels in flight with it)
@@ -359,7 +387,7 @@ __global__ __launch_bounds__(TM * 4) void mlp_fused_kernel(const MlpArgs g) {
   // HBM traffic is C in + C out per token.
   static_assert(K::LDS - K::X_BYTES >= NW * 8192, "mlp_fused: epilogue scratch does not fit behind the X images");
   Problem P{};
-  P.bias = g.b2; P.res = Q.x; P.row_scale = Q.row_scale; P.out = Q.out; P.M = M; P.rps = Q.rps > 0 ? Q.rps : 1;
+  P.bias = g.b2; P.res = DX ? nullptr : Q.x; P.row_scale = DX ? nullptr : Q.row_scale; P.out = Q.out; P.M = M; P.rps = Q.rps > 0 ? Q.rps : 1;      // (DX: g.b2 == nullptr)
   Problem Pn = P;
   Pn.res = nullptr;                                          // prefetch: bias and DropPath scales only
   Epi<bf16_t, CF, 8192> epi;
@@ -367,6 +395,7 @@ __global__ __launch_bounds__(TM * 4) void mlp_fused_kernel(const MlpArgs g) {
 #pragma unroll
   for (int p = 0; p < NP; ++p) {
     epi.prefetch(Pn, LMV_ACT_NONE, C, C, m0, p * 128, wm, wn, lane);
+    if constexpr (!DX)
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       constexpr int ROWB = BK1 * 2;
@@ -378,10 +407,10 @@ __global__ __launch_bounds__(TM * 4) void mlp_fused_kernel(const MlpArgs g) {
   }
 }
 
-template <int C, int TM>
+template <int C, int TM, bool DX = false>
 int launch_mlp(const MlpArgs& g, hipStream_t st) {
-  constexpr int lds = MlpCfg<C, TM>::LDS;
-  auto kern = mlp_fused_kernel<C, TM>;
+  constexpr int lds = MlpCfg<C, TM, DX>::LDS;
+  auto kern = mlp_fused_kernel<C, TM, DX>;
   static std::atomic<unsigned long long> attr_done{0};      // > 64 KiB of dynamic LDS: opt in once per kernel and device (idempotent)
   int dev = 0;
   (void)hipGetDevice(&dev);
@@ -398,14 +427,14 @@ int launch_mlp(const MlpArgs& g, hipStream_t st) {
   return LMV_OK;
 }
 // rows per workgroup: 64 (two workgroups per CU) where its LDS image fits 80 KB, else 128 (LMV_MLP_TM = 64 / 128 forces one: A/B runs)
-template <int C>
+template <int C, bool DX = false>
 int launch_mlp_c(const MlpArgs& g, hipStream_t st) {
   const int force = lmv_config().mlp_tm;     // (the parity tests run both tile heights in one process through lmv_config_set)
   constexpr bool fits64 = C <= 192;
   if constexpr (fits64) {
-    if (force != 128) return launch_mlp<C, 64>(g, st);
+    if (force != 128) return launch_mlp<C, 64, DX>(g, st);
   }
-  return launch_mlp<C, 128>(g, st);
+  return launch_mlp<C, 128, DX>(g, st);
 }
 
 }  // namespace
@@ -485,5 +514,45 @@ extern "C" int lmv_mlp_fused_fwd(const lmv_mlp_problem* p, int nproblems, const 
   }
   if (rc) return rc;
   LMV_CHECK_LAUNCH("mlp_fused");
+  return LMV_OK;
+}
+
+// dn2 = ((g W2) * GELU'(u)) W1: the data gradient of the MLP half in one launch (mlp_fused_kernel<.., DX = true>; include/lemevit_hip.h)
+extern "C" int lmv_mlp_dx_fused_supported(int C, int hidden, int dtype) { return lmv_mlp_fused_supported(C, hidden, dtype); }
+
+extern "C" int lmv_mlp_dx_fused(const lmv_mlp_dx_problem* p, int nproblems, const void* fc2_wt, const void* fc1_wt, int C, int hidden, int dtype, void* stream) {
+  if (dtype != LMV_BF16) LMV_FAIL(LMV_ERR_DTYPE, "mlp_dx_fused: bf16 only");
+  if (nproblems < 1 || nproblems > 2 || !p) LMV_FAIL(LMV_ERR_SHAPE, "mlp_dx_fused: nproblems must be 1 or 2");
+  if (!lmv_mlp_dx_fused_supported(C, hidden, dtype)) LMV_FAIL(LMV_ERR_SHAPE, "mlp_dx_fused: unsupported C=%d hidden=%d (C in {64,96,128,192,256,320,384}, hidden %% 128 == 0, hidden <= 4 C)", C, hidden);
+  if (!fc2_wt || !fc1_wt || !lmv_aligned16(fc2_wt) || !lmv_aligned16(fc1_wt)) LMV_FAIL(LMV_ERR_SHAPE, "mlp_dx_fused: null / misaligned transposed weight");
+  MlpArgs g{};
+  g.w1 = (const bf16_t*)fc2_wt; g.w2 = (const bf16_t*)fc1_wt;      // [hidden, C] streams in fc1's place, [C, hidden] in fc2's
+  g.nprob = nproblems; g.Hd = hidden;
+#ifdef LMV_MLP_TIMING
+  g.dbg = nullptr;
+#endif
+  for (int i = 0; i < nproblems; ++i) {
+    const lmv_mlp_dx_problem& q = p[i];
+    if (q.rows <= 0 || q.rows > 0x7fffffffLL / 4) LMV_FAIL(LMV_ERR_SHAPE, "mlp_dx_fused: bad rows %lld", (long long)q.rows);
+    if (!q.g || !q.u || !q.dn2 || !lmv_aligned16(q.g) || !lmv_aligned16(q.u) || !lmv_aligned16(q.dn2)) LMV_FAIL(LMV_ERR_SHAPE, "mlp_dx_fused: g / u / dn2 must be non-null and 16-byte aligned");
+    MlpProb& P = g.p[i];
+    P.x = (const bf16_t*)q.g; P.u = (const bf16_t*)q.u; P.out = (bf16_t*)q.dn2; P.rows = (int)q.rows; P.rps = 1;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  double trows = 0.;
+  for (int i = 0; i < nproblems; ++i) trows += (double)p[i].rows;
+  LmvTimedLaunch timed(stream, 4.0 * C * hidden * trows, 2.0 * trows * (2.0 * C + hidden) + 4.0 * C * hidden, LMV_TK_MLP_DX);      // (g in, dn2 out, u in; both weights once)
+  int rc;
+  switch (C) {
+    case 64:  rc = launch_mlp_c<64, true>(g, st); break;
+    case 96:  rc = launch_mlp_c<96, true>(g, st); break;
+    case 128: rc = launch_mlp_c<128, true>(g, st); break;
+    case 192: rc = launch_mlp_c<192, true>(g, st); break;
+    case 256: rc = launch_mlp_c<256, true>(g, st); break;
+    case 320: rc = launch_mlp_c<320, true>(g, st); break;
+    default:  rc = launch_mlp_c<384, true>(g, st); break;
+  }
+  if (rc) return rc;
+  LMV_CHECK_LAUNCH("mlp_dx_fused");
   return LMV_OK;
 }

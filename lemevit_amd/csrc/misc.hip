@@ -2,6 +2,7 @@
 // fused flat AdamW).  All are grid-stride, 16-byte-per-lane kernels bounded by HBM bandwidth.
 #include <stdarg.h>
 #include <string.h>
+#include <atomic>
 #include <mutex>
 #include <vector>
 #include "common.h"
@@ -113,13 +114,17 @@ extern "C" int lmv_debug_launch_timing_read(float* ms, double* flops, double* by
   return n;
 }
 
+namespace { std::atomic<long long> g_wgrad_launches{0}; }
+void lmv_count_wgrad() { g_wgrad_launches.fetch_add(1, std::memory_order_relaxed); }
+extern "C" long long lmv_debug_wgrad_launches(void) { return g_wgrad_launches.load(std::memory_order_relaxed); }
+
 extern "C" int lmv_abi_version(void) { return LMV_ABI_VERSION; }
 
 // ---- test switches (common.h: LmvConfig) ---------------------------------------------------------------------------------------
 namespace {
 struct ConfigKey { const char* key; int LmvConfig::*field; };
 const ConfigKey kConfigKeys[] = {
-    {"gemm_rs", &LmvConfig::gemm_rs}, {"gemm_wn", &LmvConfig::gemm_wn}, {"mlp_rw96", &LmvConfig::mlp_rw96}, {"mlp_tm", &LmvConfig::mlp_tm},
+    {"gemm_rs", &LmvConfig::gemm_rs}, {"gemm_wn", &LmvConfig::gemm_wn}, {"mlp_rw96", &LmvConfig::mlp_rw96}, {"mlp_tm", &LmvConfig::mlp_tm}, {"mlp_dx_fused", &LmvConfig::mlp_dx_fused},
     {"stage_ticket_skew", &LmvConfig::stage_ticket_skew},
 };
 LmvConfig g_config;

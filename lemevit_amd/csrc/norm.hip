@@ -182,6 +182,7 @@ __global__ __launch_bounds__(TPB) void ln_bwd_kernel(const Segs<T> sg, const flo
       }
     }
   }
+  if (!partial) return;      // dx-only mode (lmv_layernorm_bwd_partial with a NULL workspace): no (dgamma | dbeta) row
   // Column sums over the row groups of this workgroup, one chunk slot (`it`) at a time: every thread drops its
   // 2 x EPC sums into LDS as [row group][lane in row][dg | db]; output j of the slot is then the sum of `rpb` floats
   // a fixed stride apart (consecutive threads -> consecutive banks).  No atomics, no shuffles, fixed order.
@@ -274,15 +275,15 @@ int launch_fwd(const lmv_ln_segment* seg, int nseg, const float* gamma, const fl
 
 template <typename T, bool ACT>
 int launch_bwd(const lmv_ln_segment* seg, int nseg, const float* gamma, const float* beta, float* dgamma, float* dbeta, int C, void* ws, size_t ws_bytes,
-               hipStream_t st, int* partial_rows = nullptr) {
+               hipStream_t st, int* partial_rows = nullptr, bool dx_only = false) {
   Segs<T> sg;
   if (int rc = fill(&sg, seg, nseg, true, "layernorm_bwd")) return rc;
   int l2, nit;
   if (C > BWD_MAXC || !pick_geometry(C / DT<T>::EPC, sizeof(T) == 4 ? 8 : 6, &l2, &nit)) LMV_FAIL(LMV_ERR_SHAPE, "layernorm_bwd: C=%d too wide", C);
   const int blocks = bwd_blocks(sg.total, l2);
   const size_t need = (size_t)blocks * 2 * C * sizeof(float);
-  if (!ws || ws_bytes < need) LMV_FAIL(LMV_ERR_WORKSPACE, "layernorm_bwd: workspace %zu < %zu bytes", ws_bytes, need);
-  float* partial = reinterpret_cast<float*>(ws);
+  if (!dx_only && (!ws || ws_bytes < need)) LMV_FAIL(LMV_ERR_WORKSPACE, "layernorm_bwd: workspace %zu < %zu bytes", ws_bytes, need);
+  float* partial = dx_only ? nullptr : reinterpret_cast<float*>(ws);
   dim3 grid(blocks), block(TPB);
 #define LN_BWD_CASE(N) case N: hipLaunchKernelGGL((ln_bwd_kernel<T, N, ACT>), grid, block, 0, st, sg, gamma, beta, partial, C, l2); break;
   switch (nit) {
@@ -293,6 +294,7 @@ int launch_bwd(const lmv_ln_segment* seg, int nseg, const float* gamma, const fl
   }
 #undef LN_BWD_CASE
   LMV_CHECK_LAUNCH("layernorm_bwd");
+  if (dx_only) return LMV_OK;
   if (partial_rows) { *partial_rows = blocks; return LMV_OK; }      // the caller sums the per-workgroup rows (lmv_layernorm_bwd_reduce), e.g. on another stream
   return lmv_launch_partial_reduce(partial, blocks, 2 * C, dgamma, C, dbeta, 0, st);
 }
@@ -337,11 +339,12 @@ extern "C" int lmv_layernorm_bwd(const lmv_ln_segment* seg, int nseg, const floa
 // ~5 us reduce launch off the critical path (lmv_block_bwd enqueues it on the weight-gradient side stream).  Bit-identical results.
 extern "C" int lmv_layernorm_bwd_partial(const lmv_ln_segment* seg, int nseg, const float* gamma, int C, void* workspace, size_t workspace_bytes,
                                          int* partial_rows, int dtype, void* stream) {
-  if (!seg || !partial_rows) LMV_FAIL(LMV_ERR_SHAPE, "layernorm_bwd_partial: null segments / partial_rows");
+  const bool dx_only = !workspace && !partial_rows;      // dx only: the same launch, no (dgamma | dbeta) rows are written
+  if (!seg || (!partial_rows && !dx_only)) LMV_FAIL(LMV_ERR_SHAPE, "layernorm_bwd_partial: null segments / partial_rows");
   if (C <= 0 || (C % 8)) LMV_FAIL(LMV_ERR_SHAPE, "layernorm_bwd_partial: C=%d must be a positive multiple of 8", C);
   if (!gamma) LMV_FAIL(LMV_ERR_SHAPE, "layernorm_bwd_partial: null affine");
-  if (dtype == LMV_BF16) return launch_bwd<bf16_t, false>(seg, nseg, gamma, nullptr, nullptr, nullptr, C, workspace, workspace_bytes, (hipStream_t)stream, partial_rows);
-  if (dtype == LMV_F32) return launch_bwd<float, false>(seg, nseg, gamma, nullptr, nullptr, nullptr, C, workspace, workspace_bytes, (hipStream_t)stream, partial_rows);
+  if (dtype == LMV_BF16) return launch_bwd<bf16_t, false>(seg, nseg, gamma, nullptr, nullptr, nullptr, C, workspace, workspace_bytes, (hipStream_t)stream, partial_rows, dx_only);
+  if (dtype == LMV_F32) return launch_bwd<float, false>(seg, nseg, gamma, nullptr, nullptr, nullptr, C, workspace, workspace_bytes, (hipStream_t)stream, partial_rows, dx_only);
   LMV_FAIL(LMV_ERR_DTYPE, "layernorm_bwd_partial: unsupported dtype %d", dtype);
 }
 extern "C" int lmv_layernorm_bwd_reduce(const void* workspace, int partial_rows, int C, float* dgamma, float* dbeta, void* stream) {
@@ -353,8 +356,9 @@ extern "C" int lmv_layernorm_gelu_bwd(const lmv_ln_segment* seg, int nseg, const
                                       void* workspace, size_t workspace_bytes, int dtype, void* stream) {
   if (!seg) LMV_FAIL(LMV_ERR_SHAPE, "layernorm_gelu_bwd: null segments");
   if (C <= 0 || (C % 8)) LMV_FAIL(LMV_ERR_SHAPE, "layernorm_gelu_bwd: C=%d must be a positive multiple of 8", C);
-  if (!gamma || !beta || !dgamma || !dbeta) LMV_FAIL(LMV_ERR_SHAPE, "layernorm_gelu_bwd: null affine / gradient buffer");
-  if (dtype == LMV_BF16) return launch_bwd<bf16_t, true>(seg, nseg, gamma, beta, dgamma, dbeta, C, workspace, workspace_bytes, (hipStream_t)stream);
-  if (dtype == LMV_F32) return launch_bwd<float, true>(seg, nseg, gamma, beta, dgamma, dbeta, C, workspace, workspace_bytes, (hipStream_t)stream);
+  const bool dx_only = !dgamma && !dbeta && !workspace;      // frozen affine: the same launch writes dx and no partial rows
+  if (!gamma || !beta || (!dx_only && (!dgamma || !dbeta))) LMV_FAIL(LMV_ERR_SHAPE, "layernorm_gelu_bwd: null affine / gradient buffer");
+  if (dtype == LMV_BF16) return launch_bwd<bf16_t, true>(seg, nseg, gamma, beta, dgamma, dbeta, C, workspace, workspace_bytes, (hipStream_t)stream, nullptr, dx_only);
+  if (dtype == LMV_F32) return launch_bwd<float, true>(seg, nseg, gamma, beta, dgamma, dbeta, C, workspace, workspace_bytes, (hipStream_t)stream, nullptr, dx_only);
   LMV_FAIL(LMV_ERR_DTYPE, "layernorm_gelu_bwd: unsupported dtype %d", dtype);
 }

@@ -299,6 +299,7 @@ __global__ __launch_bounds__(512, 2) void wn_gemm_kernel(const WnArgs g) {
         }
       }
     }
+    if (!g.partial) return;      // dx-only mode (lmv_linear_dx_ln_bwd with a NULL workspace): workgroup-uniform
     // column sums: over the 16 rows of the lane group (shuffles), then over the two wave rows (LDS)
 #pragma unroll
     for (int p = 0; p < 3; ++p)
@@ -464,7 +465,7 @@ extern "C" size_t lmv_linear_dx_ln_bwd_workspace_bytes(int64_t total_rows, int C
 extern "C" int lmv_linear_dx_ln_bwd(const lmv_linear_problem* p, const lmv_ln_segment* seg, int nproblems, int C, int N, const float* gamma,
                                     void* workspace, size_t workspace_bytes, int* partial_rows, int dtype, void* stream) {
   if (!lmv_linear_dx_ln_bwd_supported(C, N, dtype)) LMV_FAIL(LMV_ERR_SHAPE, "linear_dx_ln_bwd: C=%d N=%d dtype=%d (bf16, C = 384, N %% 64 == 0)", C, N, dtype);
-  if (nproblems < 1 || nproblems > 2 || !p || !seg || !gamma || !workspace || !partial_rows) LMV_FAIL(LMV_ERR_SHAPE, "linear_dx_ln_bwd: null argument / nproblems must be 1 or 2");
+  if (nproblems < 1 || nproblems > 2 || !p || !seg || !gamma || (!workspace != !partial_rows)) LMV_FAIL(LMV_ERR_SHAPE, "linear_dx_ln_bwd: null argument / nproblems must be 1 or 2");
   WnArgs a{};
   int npan[2] = {0, 0};
   for (int i = 0; i < nproblems; ++i) {
@@ -481,7 +482,7 @@ extern "C" int lmv_linear_dx_ln_bwd(const lmv_linear_problem* p, const lmv_ln_se
     npan[i] = (int)((q.rows + WN_BM - 1) / WN_BM);
   }
   a.K = N; a.npanels0 = npan[0]; a.npanels = npan[0] + npan[1];
-  if (workspace_bytes < (size_t)a.npanels * 768 * sizeof(float) || !lmv_aligned16(workspace))
+  if (workspace && (workspace_bytes < (size_t)a.npanels * 768 * sizeof(float) || !lmv_aligned16(workspace)))
     LMV_FAIL(LMV_ERR_WORKSPACE, "linear_dx_ln_bwd: workspace %zu < %zu bytes", workspace_bytes, (size_t)a.npanels * 768 * sizeof(float));
   a.gamma = gamma; a.partial = (float*)workspace;
 #ifdef LMV_WN_TIMING
@@ -492,7 +493,7 @@ extern "C" int lmv_linear_dx_ln_bwd(const lmv_linear_problem* p, const lmv_ln_se
   LmvTimedLaunch timed(stream, 2.0 * C * N * trows_, 2.0 * trows_ * (N + 3.0 * C) + 2.0 * N * C, LMV_TK_WN_GEMM);          // (dY in; x, dres in, dx out; the transposed weight once)
   if (int rc = wn_launch<WN_LNBWD>(a, (hipStream_t)stream)) return rc;
   LMV_CHECK_LAUNCH("linear_dx_ln_bwd");
-  *partial_rows = a.npanels;
+  if (partial_rows) *partial_rows = a.npanels;
   return LMV_OK;
 }
 

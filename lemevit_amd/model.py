@@ -181,15 +181,19 @@ class _StemConv1Fn(torch.autograd.Function):
         g = dy.permute(0, 2, 3, 1).contiguous().view(-1, Co)
         if g.dtype != patches.dtype:
             g = g.to(patches.dtype)
-        dwm = torch.zeros(Co, KP, device=g.device, dtype=torch.float32)
-        db = torch.zeros(Co, device=g.device, dtype=torch.float32)
-        ops.linear_dw([Prob(g, patches, dwm, bias_grad=db)], Co, KP)
-        dw = dwm[:, :9 * wshape[1]].reshape(wshape).to(wdt)
+        need_w, need_b = ctx.needs_input_grad[1], bdt is not None and ctx.needs_input_grad[2]
+        dw = db = None
+        if need_w or need_b:          # (a frozen convolution: no accumulators, no weight-gradient launch)
+            dwm = torch.zeros(Co, KP, device=g.device, dtype=torch.float32)
+            db = torch.zeros(Co, device=g.device, dtype=torch.float32)
+            ops.linear_dw([Prob(g, patches, dwm, bias_grad=db)], Co, KP)
+            dw = dwm[:, :9 * wshape[1]].reshape(wshape).to(wdt) if need_w else None
+            db = db.to(bdt) if need_b else None
         dx = None
         if ctx.needs_input_grad[0]:
             _, Wm, x = ctx.saved_tensors
             dx = ops.conv3x3s2_nchw_dx(g, Wm, like=x)
-        return dx, dw, (None if bdt is None else db.to(bdt)), None, None
+        return dx, dw, db, None, None
 
 
 def _conv_matrix(weight: Tensor, dtype: torch.dtype, KP: int) -> Tensor:
@@ -237,19 +241,23 @@ class _Conv3x3s2Fn(torch.autograd.Function):
         g = dy.permute(0, 2, 3, 1).contiguous().view(-1, Co)
         if g.dtype != patches.dtype:
             g = g.to(patches.dtype)
-        dwm = torch.zeros(Co, KP, device=g.device, dtype=torch.float32)
-        db = torch.zeros(Co, device=g.device, dtype=torch.float32)
-        if implicit:
-            ops.conv3x3s2_dw(g, patches, dwm, db)          # (`patches` is the NHWC map here)
-        else:
-            ops.linear_dw([Prob(g, patches, dwm, bias_grad=db)], Co, KP)
-        dw = dwm[:, :9 * Ci].reshape(Co, 3, 3, Ci).permute(0, 3, 1, 2).to(wdt)
+        need_w, need_b = ctx.needs_input_grad[1], bdt is not None and ctx.needs_input_grad[2]
+        dw = db = None
+        if need_w or need_b:          # (a frozen convolution: no accumulators, no weight-gradient launch)
+            dwm = torch.zeros(Co, KP, device=g.device, dtype=torch.float32)
+            db = torch.zeros(Co, device=g.device, dtype=torch.float32)
+            if implicit:
+                ops.conv3x3s2_dw(g, patches, dwm, db)          # (`patches` is the NHWC map here)
+            else:
+                ops.linear_dw([Prob(g, patches, dwm, bias_grad=db)], Co, KP)
+            dw = dwm[:, :9 * Ci].reshape(Co, 3, 3, Ci).permute(0, 3, 1, 2).to(wdt) if need_w else None
+            db = db.to(bdt) if need_b else None
         dx = None
         if ctx.needs_input_grad[0]:
             dp = torch.empty(g.shape[0], KP, device=g.device, dtype=g.dtype)
             ops.linear_dx([Prob(g, Wm, dp)], Co, KP)
             dx = ops.col2im3x3s2_nhwc(dp, B, H, W, Ci).permute(0, 3, 1, 2).to(xdt)
-        return dx, dw, (None if bdt is None else db.to(bdt)), None
+        return dx, dw, db, None
 
 
 def _is_conv3x3s2(m: nn.Module, x: Tensor) -> bool:
@@ -464,26 +472,31 @@ class _MetaMLPFn(torch.autograd.Function):
         dy = dy.contiguous().view(-1, cout)
         if dy.dtype != x.dtype:
             dy = dy.to(x.dtype)
-        sizes = [int(torch.Size(sh).numel()) for sh, _ in pmeta]
+        need = ctx.needs_input_grad[1:9]
+        # accumulators per pair (weight, bias) / (gamma, beta) that one launch fills together: none for a pair that is frozen
+        pairs = [any(need[i:i + 2]) for i in (0, 2, 4, 6)]
+        sizes = [int(torch.Size(sh).numel()) if pairs[i // 2] else 0 for i, (sh, _) in enumerate(pmeta)]
         pad = [(n + 3) // 4 * 4 for n in sizes]
-        flat = torch.zeros(sum(pad), device=x.device, dtype=torch.float32)
+        flat = torch.zeros(sum(pad), device=x.device, dtype=torch.float32) if any(pairs) else None
         G, off = [], 0
         for (sh, _), n, pd in zip(pmeta, sizes, pad):
-            G.append(flat[off:off + n].view(sh)); off += pd
+            G.append(flat[off:off + n].view(sh) if n else None); off += pd
         dW1, db1, dg1, dbe1, dW2, db2, dg2, dbe2 = G
         (dh2,) = ops.layernorm_bwd_multi([dy], [h2], [st2], g2, dg2, dbe2, [None])
-        ops.linear_dw([Prob(dh2, a1, dW2, bias_grad=db2)], cout, hid)
+        if pairs[2]:
+            ops.linear_dw([Prob(dh2, a1, dW2, bias_grad=db2)], cout, hid)
         da1 = torch.empty_like(a1)
         ops.linear_dx([Prob(dh2, W2, da1)], cout, hid)
         (dh1,) = ops.layernorm_bwd_multi([da1], [h1], [st1], g1, dg1, dbe1, [None], gelu_beta=be1)
-        ops.linear_dw([Prob(dh1, x, dW1, bias_grad=db1)], hid, cin)
+        if pairs[0]:
+            ops.linear_dw([Prob(dh1, x, dW1, bias_grad=db1)], hid, cin)
         dc = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty_like(x)
             ops.linear_dx([Prob(dh1, W1, dx)], hid, cin)
             dc = dx.view(cshape).to(cdtype)
         ctx.saved = None
-        return (dc, *[g if dt == torch.float32 else g.to(dt) for g, (_, dt) in zip(G, pmeta)], None, None, None)
+        return (dc, *[None if not nd else (g if dt == torch.float32 else g.to(dt)) for g, (_, dt), nd in zip(G, pmeta, need)], None, None, None)
 
 
 class _TailFn(torch.autograd.Function):
@@ -545,12 +558,14 @@ class _TailFn(torch.autograd.Function):
             if Np != N:
                 dp = torch.zeros((d.shape[0], Np), device=d.device, dtype=d.dtype); dp[:, :N] = d
                 d = dp
-            dWf = torch.zeros((Np, K), device=d.device, dtype=torch.float32); dbf = torch.zeros((Np,), device=d.device, dtype=torch.float32)
-            ops.linear_dw([Prob(d, pooled, dWf, bias_grad=dbf)], Np, K)
+            need_w, need_b = ctx.needs_input_grad[5], hbdt is not None and ctx.needs_input_grad[6]
+            if need_w or need_b:          # (a frozen head: no accumulators, no weight-gradient launch)
+                dWf = torch.zeros((Np, K), device=d.device, dtype=torch.float32); dbf = torch.zeros((Np,), device=d.device, dtype=torch.float32)
+                ops.linear_dw([Prob(d, pooled, dWf, bias_grad=dbf)], Np, K)
+                dW = dWf[:N].to(hwdt) if need_w else None
+                db = dbf[:N].to(hbdt) if need_b else None
             dpooled = torch.empty_like(pooled)
             ops.linear_dx([Prob(d, Wp, dpooled)], Np, K)
-            dW = dWf[:N].to(hwdt)
-            db = None if hbdt is None else dbf[:N].to(hbdt)
         else:
             dpooled = dout.contiguous().to(cc.dtype)
         dbn_w = dbn_b = None
@@ -566,10 +581,14 @@ class _TailFn(torch.autograd.Function):
             ctx.bn = None
         else:
             dx, dcn = ops.token_mean2_bwd(dpooled, L, M)
-        dg = torch.zeros_like(g32); dbeta = torch.zeros_like(g32)
+        dg = dbeta = None
+        if ctx.needs_input_grad[2] or ctx.needs_input_grad[3]:
+            dg = torch.zeros_like(g32); dbeta = torch.zeros_like(g32)
         (dc,) = ops.layernorm_bwd_multi([dcn], [cc], [st], g32, dg, dbeta, [None])
         ctx.saved = None
-        return dx.to(xdt), dc.to(cdt), dg.to(gdt), dbeta.to(bdt), None, dW, db, None, dbn_w, dbn_b, None, None, None
+        dg = dg.to(gdt) if ctx.needs_input_grad[2] else None
+        dbeta = dbeta.to(bdt) if ctx.needs_input_grad[3] else None
+        return dx.to(xdt), dc.to(cdt), dg, dbeta, None, dW, db, None, dbn_w, dbn_b, None, None, None
 
 
 def _tail_infer(norm_c: nn.LayerNorm, bn: nn.BatchNorm2d, head: nn.Linear, xt: Tensor, c: Tensor, cd: torch.dtype) -> Tensor:
@@ -715,6 +734,43 @@ _scratch_cache: dict = {}
 _bwd_slot = 0
 
 
+# Frozen blocks (no parameter requires grad, but x or c does) run DATA-ONLY: LMV_BLOCK_DATA_ONLY drops n1 / n2 / h from the saved set and every
+# weight-gradient launch, reduce and side-stream fork from the backward pass (include/lemevit_hip.h).
+_DATA_ONLY = 4                # LMV_BLOCK_DATA_ONLY
+_FROZEN_DATA_ONLY = True      # False: frozen blocks take the full backward (accumulators allocated and discarded) -- the comparison side of the tests
+_FROZEN_WTS = True            # False: data-only blocks run without transposed weight copies, i.e. on the dX kernels a plain trainable block selects
+
+
+def _frozen_wts(names, params, P: Dict[str, Tensor], cd: torch.dtype) -> Dict[str, Tensor]:
+    """Transposed bf16 copies of a frozen block's weights: derived operands under the one invalidation rule, all of a block in ONE
+    lmv_transpose_batch launch.  Which ones: those FlatAdamW keeps for a trainable block of the same shape (mlp.3 at C = 192 / 384, mlp.0 /
+    attn.qkv / attn.proj at C = 384: the dX kernels that measured faster in forward form), so a frozen block selects the dX kernels its
+    trainable twin selects -- plus mlp.3 and mlp.0 wherever the fused dX kernel is forced (mlp_dx_fused = 2), which needs both."""
+    if not _FROZEN_WTS or cd != torch.bfloat16:
+        return {}
+    from ._lib import config_get
+    Hd, C_ = P["mlp.0.weight"].shape
+    fused = config_get("mlp_dx_fused") == 2 and ops.mlp_dx_fused_supported(C_, Hd, cd)
+    todo = []
+    for n in _WT_FIELDS:
+        if n not in names:
+            continue
+        w = P[n]
+        fc2 = n == "mlp.3.weight" and w.shape[0] in (192, 384) and w.shape[1] % 64 == 0 and w.shape[1] >= 512
+        wide = n != "mlp.3.weight" and w.shape[1] == 384 and w.shape[0] % 64 == 0
+        if fc2 or wide or (fused and n in ("mlp.3.weight", "mlp.0.weight")):
+            todo.append(n)
+    if not todo:
+        return {}
+    srcs = [params[names.index(n)] for n in todo]
+
+    def build():
+        outs = {n: torch.empty((P[n].shape[1], P[n].shape[0]), device=P[n].device, dtype=torch.bfloat16) for n in todo}
+        ops.transpose_batch([(P[n].detach().contiguous(), outs[n]) for n in todo])
+        return outs
+    return derived(srcs[0], ("frozen_wt", cd, tuple(todo)), srcs, build)
+
+
 def _native_ok(kind: str, x: Tensor, c: Tensor) -> bool:
     return (_NATIVE and kind in _KIND_CODE and x.is_cuda and x.dtype in (torch.bfloat16, torch.float32) and c.dtype == x.dtype
             and x.is_contiguous() and c.is_contiguous() and x.shape[-1] % 32 == 0)
@@ -774,7 +830,7 @@ def _block_desc(kind: str, x: Tensor, c: Tensor, H: int, W: int, names, P: Dict[
 
 
 def _sized(fn, d, kind, x, c, H, W) -> int:
-    key = (fn.__name__, kind, x.shape[0], H, W, c.shape[1], x.shape[2], x.dtype, d.hidden)
+    key = (fn.__name__, kind, x.shape[0], H, W, c.shape[1], x.shape[2], x.dtype, d.hidden, d.flags & _DATA_ONLY)
     n = _size_cache.get(key)
     if n is None:
         n = _size_cache[key] = int(fn(d))
@@ -783,11 +839,13 @@ def _sized(fn, d, kind, x, c, H, W) -> int:
     return n
 
 
-def _persistent(tag: str, nbytes: int, device) -> Tensor:
-    """Stream-ordered scratch that outlives the call (one per device, stream and use)."""
+def _persistent(tag: str, nbytes: int, device, shrink: bool = False) -> Tensor:
+    """Stream-ordered scratch that outlives the call (one per device, stream and use).  shrink: a buffer more than twice the size asked
+    for is replaced by a smaller one (the forward transient: sized by the widest stage, it would otherwise sit in the peak at the end of
+    the forward pass, where the last stage needs a tenth of it)."""
     key = (tag, device, ops._stream())
     t = _scratch_cache.get(key)
-    if t is None or t.numel() < nbytes:
+    if t is None or t.numel() < nbytes or (shrink and t.numel() > 2 * (int(nbytes * 1.1) + 4096)):
         t = _scratch_cache[key] = torch.empty(int(nbytes * 1.1) + 4096, device=device, dtype=torch.uint8)
     return t
 
@@ -799,7 +857,7 @@ def _persistent(tag: str, nbytes: int, device) -> Tensor:
 # over the whole batch, models/lemevit.py:663-676) and the backward pass see whole-batch tensors: image_ranges() joins at the stage's end.
 TRAIN_PARTS = int(os.environ.get("LMV_TRAIN_PARTS", "2"))
 TRAIN_PARTS_MIN_BATCH = 32          # smaller batches are launch-bound: more, smaller launches do not pay
-_range_state: dict = {}             # device index -> [streams, forked?]
+_range_state: dict = {}             # device index -> [streams, forked?, cache fills seen, tensors released at the join]
 
 
 class image_ranges:
@@ -814,16 +872,17 @@ class image_ranges:
         if self.on:
             from . import blocks as _blocks
             streams = _blocks.aux_streams(self.dev, self.parts - 1)      # [0] = the weight-gradient side stream, idle during the forward pass
-            _range_state[self.dev.index] = [streams, False, -1]
+            _range_state[self.dev.index] = [streams, False, -1, []]
         return self
 
     def __exit__(self, *exc):
         if self.on:
-            streams, forked, _ = _range_state.pop(self.dev.index)
+            streams, forked, _, held = _range_state.pop(self.dev.index)
             if forked:
                 cur = torch.cuda.current_stream(self.dev)
                 for s in streams:
                     cur.wait_stream(s)
+            del held                        # (block inputs that no backward keeps: back to the allocator behind the join, not inside the stage loop)
         return False
 
 
@@ -838,14 +897,31 @@ def _join_ranges(device) -> None:
         rs[1] = False
 
 
+def _block_fwd_call(d, xp, cp, xop, cop, arena: Tensor, i0: int, n: int, st: int, device) -> None:
+    """One forward call over the images [i0, i0 + n); a data-only descriptor takes its transient n1 / n2 / h from the per-device buffer."""
+    from ._lib import lib, check
+    if d.flags & _DATA_ONLY:
+        tr = d._transient
+        check(lib.lmv_block_fwd_range_scratch(d, xp, cp, xop, cop, arena.data_ptr(), arena.numel(), 1, i0, n, tr.data_ptr(), tr.numel(), st), "lmv_block_fwd_range_scratch")
+    else:
+        check(lib.lmv_block_fwd_range(d, xp, cp, xop, cop, arena.data_ptr(), arena.numel(), 1, i0, n, st), "lmv_block_fwd_range")
+
+
 def native_block_forward(kind: str, x: Tensor, c: Tensor, H: int, W: int, names, P: Dict[str, Tensor], masks, save: bool, folds=None, wts=None,
-                         ckpt: bool = False):
+                         ckpt: bool = False, data_only: bool = False):
     """lmv_block_fwd: returns (x_out, c_out, state) with state = (descriptor, arena) for native_block_backward (save=True).
     Inside image_ranges() (training): one lmv_block_fwd_range call per range of images, each on its own stream.
     ckpt (save=True, a checkpointed block): the same calls write a reused per-device arena, state = (descriptor, None), and the
     descriptor keeps the range cuts (d._cuts) -- native_block_backward recomputes the arena with them."""
     from ._lib import lib, check
     d = _block_desc(kind, x, c, H, W, names, P, masks, None if save else folds, wts if save else None)
+    d._transient = None
+    if data_only and save:
+        # n1 / n2 / h live for the duration of a forward call only: ONE buffer per device and stream serves every block (laid out for the
+        # whole batch and sliced by image, so concurrent image ranges share no byte; like the "ckpt" arena it is only replaced -- grown, or
+        # shrunk for a much narrower stage -- at a stage's first block, behind the join of the previous stage's range streams)
+        d.flags |= _DATA_ONLY
+        d._transient = _persistent("fwd_transient", _sized(lib.lmv_block_fwd_scratch_bytes, d, kind, x, c, H, W), x.device, shrink=True)
     nbytes = _sized(lib.lmv_block_arena_bytes, d, kind, x, c, H, W)
     if ckpt:
         # (the blocks of a stage share one size, so the arena only grows at a stage's first block -- behind image_ranges' join of the
@@ -857,7 +933,9 @@ def native_block_forward(kind: str, x: Tensor, c: Tensor, H: int, W: int, names,
     xo = torch.empty_like(x) if kind != "C" else None
     co = torch.empty_like(c)
     rs = _range_state.get(x.device.index) if save else None
-    if rs is None:
+    if rs is None and d.flags & _DATA_ONLY:
+        _block_fwd_call(d, x.data_ptr(), c.data_ptr(), None if xo is None else xo.data_ptr(), co.data_ptr(), arena, 0, x.shape[0], ops._stream(), x.device)
+    elif rs is None:
         check(lib.lmv_block_fwd(d, x.data_ptr(), c.data_ptr(), None if xo is None else xo.data_ptr(), co.data_ptr(), arena.data_ptr(), arena.numel(), 1 if save else 0,
                                 ops._stream()), "lmv_block_fwd")
     else:
@@ -877,10 +955,10 @@ def native_block_forward(kind: str, x: Tensor, c: Tensor, H: int, W: int, names,
             st = cur if i == 0 else streams[i - 1]
             if i and ev is not None:
                 st.wait_event(ev)
-            check(lib.lmv_block_fwd_range(d, x.data_ptr(), c.data_ptr(), None if xo is None else xo.data_ptr(), co.data_ptr(), arena.data_ptr(), arena.numel(), 1,
-                                          cuts[i], cuts[i + 1] - cuts[i], st.cuda_stream), "lmv_block_fwd_range")
+            _block_fwd_call(d, x.data_ptr(), c.data_ptr(), None if xo is None else xo.data_ptr(), co.data_ptr(), arena, cuts[i], cuts[i + 1] - cuts[i], st.cuda_stream, x.device)
         rs[1] = True
         d._cuts = cuts
+    d._transient = None                  # (the descriptor lives until the backward pass: it must not keep a replaced transient buffer alive)
     return (x if xo is None else xo), co, ((d, None if ckpt else arena) if save else None)
 
 
@@ -899,23 +977,42 @@ def _recompute_arena(kind: str, d, x: Tensor, c: Tensor, H: int, W: int) -> Tens
     arena = torch.empty(nbytes, device=x.device, dtype=torch.uint8)
     xo = torch.empty_like(x) if kind != "C" else None
     co = torch.empty_like(c)
-    d.flags = 0
+    d.flags &= _DATA_ONLY                # (a data-only block recomputes its reduced saved set with the same flag)
     st = ops._stream()
     xp, cp, xop, cop = x.data_ptr(), c.data_ptr(), None if xo is None else xo.data_ptr(), co.data_ptr()
-    if d._cuts is None:
+    if d.flags & _DATA_ONLY:
+        d._transient = _persistent("fwd_transient", _sized(lib.lmv_block_fwd_scratch_bytes, d, kind, x, c, H, W), x.device, shrink=True)
+    if d._cuts is None and not d.flags & _DATA_ONLY:
         check(lib.lmv_block_fwd(d, xp, cp, xop, cop, arena.data_ptr(), arena.numel(), 1, st), "lmv_block_fwd")
     else:
-        cuts = d._cuts
+        cuts = d._cuts if d._cuts is not None else [0, x.shape[0]]
         for i in range(len(cuts) - 1):
-            check(lib.lmv_block_fwd_range(d, xp, cp, xop, cop, arena.data_ptr(), arena.numel(), 1, cuts[i], cuts[i + 1] - cuts[i], st), "lmv_block_fwd_range")
+            _block_fwd_call(d, xp, cp, xop, cop, arena, cuts[i], cuts[i + 1] - cuts[i], st, x.device)
+    d._transient = None
     return arena
 
 
-def native_block_backward(kind: str, state, x: Tensor, c: Tensor, dx: Optional[Tensor], dc: Tensor, H: int, W: int, names, G: Dict[str, Tensor]):
+def native_block_backward(kind: str, state, x: Tensor, c: Tensor, dx: Optional[Tensor], dc: Tensor, H: int, W: int, names, G: Optional[Dict[str, Tensor]]):
     from ._lib import lib, check
     from . import blocks as blocks_mod
     from .blocks import side_stream_handle
     d, arena = state
+    if d.flags & _DATA_ONLY:
+        # a frozen block: G is None, nothing goes to the side stream and no join is deferred.  Weight-gradient launches of the trainable
+        # blocks differentiated before this one may still read the backward scratch on the side stream: the main stream waits for them first
+        # (at the boundary between trainable and frozen blocks; the queue is empty from then on)
+        # x is read by the position convolution's weight gradient only: an unchecked frozen block did not keep it (x is a meta tensor
+        # that carries the shape, and lmv_block_bwd gets NULL)
+        blocks_mod._wait_pending(0, c.device.index)
+        if arena is None:
+            arena = _recompute_arena(kind, d, x, c, H, W)
+        nbytes = _sized(lib.lmv_block_bwd_scratch_bytes, d, kind, x, c, H, W)
+        scratch = _persistent(("bwd", 0), nbytes, c.device)
+        dx0, dc0 = torch.empty(x.shape, device=c.device, dtype=x.dtype), torch.empty_like(c)
+        d.flags = _DATA_ONLY
+        check(lib.lmv_block_bwd(d, None if x.is_meta else x.data_ptr(), c.data_ptr(), arena.data_ptr(), arena.numel(), None if dx is None else dx.data_ptr(), dc.data_ptr(), dx0.data_ptr(),
+                                dc0.data_ptr(), scratch.data_ptr(), scratch.numel(), ops._stream(), None), "lmv_block_bwd")
+        return dx0, dc0
     if arena is None:                    # a checkpointed block (native_block_forward(ckpt=True))
         arena = _recompute_arena(kind, d, x, c, H, W)
     for n in names:
@@ -950,6 +1047,8 @@ class _BlockFn(torch.autograd.Function):
         cd = x.dtype
         P = {n: compute_copy(p, cd if _is_matrix(n) else torch.float32) for n, p in zip(names, params)}
         ctx.native = _native_ok(kind, x, c)
+        # data-only: decided here and kept -- no parameter of the block requires grad (a block with SOME frozen parameters runs the full backward)
+        ctx.data_only = data_only = _FROZEN_DATA_ONLY and not any(ctx.needs_input_grad[8:])
         if ctx.native:
             # a transposed copy is only valid next to the shadow it was made from (FlatAdamW refreshes both in one step)
             wts = {}
@@ -959,19 +1058,29 @@ class _BlockFn(torch.autograd.Function):
                     sh, wt = getattr(w, "_lmv_shadow", None), getattr(w, "_lmv_shadow_t", None)
                     if wt is not None and sh is not None and (P[n] is sh or P[n].data_ptr() == sh.data_ptr()):
                         wts[n] = wt
-            xo, co, state = native_block_forward(kind, x, c, H, W, names, P, masks, save=True, wts=wts, ckpt=ckpt)
-            saved = (x, c, state)
+            if data_only:                   # FlatAdamW manages trainable parameters only: a frozen block's copies are derived operands
+                wts = _frozen_wts(names, params, P, cd)
+            xo, co, state = native_block_forward(kind, x, c, H, W, names, P, masks, save=True, wts=wts, ckpt=ckpt, data_only=data_only)
+            # a frozen block's backward never reads x (only the position convolution's WEIGHT gradient does): unless it is checkpointed,
+            # which recomputes from x, it keeps the shape alone and the producer's tensor is free once the next block has run
+            if data_only and not ckpt:
+                rs = _range_state.get(x.device.index)
+                if rs is not None:
+                    rs[3].append(x)         # the range streams still read it: nothing goes back to the allocator inside the stage loop
+                saved = (x.new_empty(x.shape, device="meta"), c, state)
+            else:
+                saved = (x, c, state)
         else:
             if x.is_cuda:
                 _join_ranges(x.device)
-            xo, co, saved = block_forward(kind, x, c, H, W, P, masks, save=True)
+            xo, co, saved = block_forward(kind, x, c, H, W, P, masks, save=True, data_only=data_only)
             if ckpt:
                 saved = (x, c)              # the same calls as the unchecked block (save=True); their saved set is dropped here
         ctx.kind, ctx.H, ctx.W, ctx.masks, ctx.names, ctx.ckpt = kind, H, W, masks, names, ckpt
         ctx.saved, ctx.P = saved, P
         ctx.pmeta = [(p.shape, p.dtype) for p in params]
         ctx.params = params
-        ctx.cshape = c.shape
+        ctx.cshape, ctx.dev = c.shape, c.device
         if kind == "C":
             return co                      # x passes through unchanged outside the node (models/lemevit.py:610)
         if kind == "Sx":
@@ -987,11 +1096,24 @@ class _BlockFn(torch.autograd.Function):
             dx, dc = grads[0], None
         else:
             dx, dc = grads
-        x0 = ctx.saved[0]
+        x0, dev = ctx.saved[0], ctx.dev                      # (x0 may be a meta tensor: a frozen block keeps the shape of x only)
         if dc is None and kind != "Sx":
-            dc = torch.zeros(ctx.cshape, device=x0.device, dtype=x0.dtype)
+            dc = torch.zeros(ctx.cshape, device=dev, dtype=x0.dtype)
         if dx is None and kind != "C":
-            dx = torch.zeros_like(x0)
+            dx = torch.zeros(x0.shape, device=dev, dtype=x0.dtype)
+        if ctx.data_only:
+            # frozen parameters: no gradient accumulators, no side stream, no deferred join, no chunk callback -- autograd is handed None
+            if ctx.native:
+                xin, cin, state = ctx.saved
+                dx0, dc0 = native_block_backward(kind, state, xin, cin, None if dx is None else dx.contiguous(), dc.contiguous(), ctx.H, ctx.W, names, None)
+                if kind == "C" and dx is not None:
+                    dx0 = dx0 + dx
+            else:
+                saved = block_forward(kind, ctx.saved[0], ctx.saved[1], ctx.H, ctx.W, P, ctx.masks, save=True, data_only=True)[2] if ctx.ckpt else ctx.saved
+                dx0, dc0 = block_backward(kind, saved, None if dx is None else dx.contiguous(), None if dc is None else dc.contiguous(), ctx.H, ctx.W, P, None, ctx.masks)
+                del saved
+            ctx.saved = ctx.params = None
+            return (dx0, dc0, None, None, None, None, None, None, *([None] * len(names)))
         # lemevit_amd.optim.FlatAdamW keeps every block parameter's .grad as a slice of one flat fp32 buffer: the kernels then
         # accumulate straight into it and autograd is handed None (no per-parameter accumulation launches)
         inplace = all(getattr(p, "_lmv_flat_grad", False) and p.grad is not None and p.grad.dtype == torch.float32 and p.grad.is_contiguous()
@@ -1001,7 +1123,7 @@ class _BlockFn(torch.autograd.Function):
         else:
             sizes = [int(torch.Size(s).numel()) for s, _ in ctx.pmeta]
             pad = [(n + 3) // 4 * 4 for n in sizes]                 # keep every slice 16-byte aligned
-            flat = torch.zeros(sum(pad), device=x0.device, dtype=torch.float32)
+            flat = torch.zeros(sum(pad), device=dev, dtype=torch.float32)
             G, off = {}, 0
             for n, (shape, _), sz, pd in zip(names, ctx.pmeta, sizes, pad):
                 G[n] = flat[off:off + sz].view(shape)
@@ -1021,7 +1143,7 @@ class _BlockFn(torch.autograd.Function):
             # the parameter gradients leave this node now (all-reduce of the chunk / autograd's accumulation on the current stream):
             # the deferred joins of the weight-gradient side stream (blocks.defer_join) are due
             from . import blocks as _blocks
-            _blocks._wait_pending(0, x0.device.index)
+            _blocks._wait_pending(0, dev.index)
         if cb is not None:
             cb()                     # lemevit_amd.dist.FlatGradSync: this block closes a chunk of the flat gradient buffer -> start its all-reduce
         if inplace:

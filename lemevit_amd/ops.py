@@ -157,6 +157,32 @@ def mlp_fused_fwd(xs: Sequence[Tensor], fc1: Folded, w2: Tensor, b2: Tensor, eps
     return outs
 
 
+def mlp_dx_fused_supported(C_: int, hidden: int, dtype: torch.dtype) -> bool:
+    return dtype == torch.bfloat16 and bool(lib.lmv_mlp_dx_fused_supported(C_, hidden, _lib.LMV_BF16))
+
+
+def mlp_dx_fused(gs: Sequence[Tensor], us: Sequence[Tensor], fc2_wt: Tensor, fc1_wt: Tensor) -> List[Tensor]:
+    """dn2_i = ((g_i W2) * GELU'(u_i)) W1 for up to two row matrices in ONE launch (lmv_mlp_dx_fused): the data gradient of a block's MLP
+    half with du kept on the chip.  g_i [.., C]: gradient of the MLP output (DropPath-scaled); u_i [.., hidden]: the saved fc1
+    pre-activations; fc2_wt [hidden, C], fc1_wt [C, hidden]: the transposed bf16 weight copies."""
+    Hd, C_ = fc2_wt.shape
+    if fc1_wt.shape != (C_, Hd) or not fc2_wt.is_contiguous() or not fc1_wt.is_contiguous():
+        raise TypeError("mlp_dx_fused: fc2_wt [hidden, C] and fc1_wt [C, hidden], contiguous")
+    outs = [torch.empty_like(g) for g in gs]
+    arr = (_lib.MlpDxProblem * len(gs))()
+    for s, g, u, o in zip(arr, gs, us, outs):
+        if not g.is_contiguous() or not u.is_contiguous() or u.numel() // Hd != g.numel() // C_:
+            raise TypeError("mlp_dx_fused: contiguous g [rows, C] and u [rows, hidden]")
+        s.g, s.u, s.dn2, s.rows = _ptr(g), _ptr(u), _ptr(o), g.numel() // C_
+    check(lib.lmv_mlp_dx_fused(arr, len(gs), _ptr(fc2_wt), _ptr(fc1_wt), C_, Hd, dtype_code(gs[0]), _stream()), "lmv_mlp_dx_fused")
+    return outs
+
+
+def wgrad_launches() -> int:
+    """lmv_debug_wgrad_launches: weight-gradient launches, reduces and side-stream forks the native block backward has enqueued so far."""
+    return int(lib.lmv_debug_wgrad_launches())
+
+
 def attn_out_proj_residual(probs: Sequence[Prob], C_: int) -> None:
     """out = res + row_scale * (a @ W^T + b): attention output projection with the block's residual / DropPath in the epilogue."""
     check(lib.lmv_attn_out_proj_residual(_pack(probs), len(probs), C_, dtype_code(probs[0].a), _stream()), "lmv_attn_out_proj_residual")
@@ -248,6 +274,12 @@ def layernorm_bwd_multi(dys: Sequence[Tensor], xs: Sequence[Tensor], stats: Sequ
         total += s.rows
         dxs.append(dx)
     code = dtype_code(xs[0])
+    if dgamma is None and dbeta is None:      # frozen affine: dx only -- no partial rows, no workspace, no reduce launch
+        if gelu_beta is not None:
+            check(lib.lmv_layernorm_gelu_bwd(seg, len(xs), _f32(gamma), _f32(gelu_beta), None, None, C_, None, 0, code, _stream()), "lmv_layernorm_gelu_bwd")
+        else:
+            check(lib.lmv_layernorm_bwd_partial(seg, len(xs), _f32(gamma), C_, None, 0, None, code, _stream()), "lmv_layernorm_bwd_partial")
+        return dxs if next_scales is None else (dxs, scaled)
     ws = _workspace(lib.lmv_layernorm_bwd_workspace_bytes(total, C_, code), xs[0].device)
     if split_reduce:               # the two-call form the native block scheduler uses (reduce on another stream there); same stream here
         rows = C.c_int(0)
