@@ -404,6 +404,34 @@ int lmv_token_mean2_affine_fwd(const void* x, int L, const void* c, int M, int C
 int lmv_adamw_flat(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, const float* wd_mask, void* shadow_bf16,
                    int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay, int step, const int* step_dev,
                    void* stream);
+/* Global L2 norm of a list of fp32 gradient segments, and the clipping coefficient derived from it, all on the device (engine.py:82-95
+ * dispatch_clip_grad / utils/__init__.py:311-331 NativeScalerWithGradNormCount; torch.nn.utils.clip_grad_norm_ with norm_type 2).
+ * Any number of segments, each of any length >= 0 and 4-byte alignment (a segment whose start is 16-byte aligned is read with 16-byte loads).
+ * Stage 1: every segment is cut into chunks of LMV_NORM_CHUNK elements, one workgroup sums the squares of one chunk in fp32 and writes one partial
+ * into `ws` (the table goes to the kernel by value, one launch per run of segments that fits it); stage 2 (one more launch, one workgroup) adds the partials in a fixed order in double.
+ * Which element meets which accumulator depends on the segment lengths alone -- not on the grid, the device, the stream or a pointer's
+ * alignment -- and there are no floating-point atomics: two calls, and all ranks of a data-parallel job, agree bit for bit.
+ * stat (device, 16-byte aligned, LMV_GRAD_STAT_FLOATS floats):
+ *   [0] norm   [1] coef = min(1, max_norm / (norm + 1e-6)), 1 when max_norm <= 0 (measure only)   [2] 1 / coef
+ *   [3] found_inf: 1.0 when the norm is inf or NaN, else 0.0   [4] running count of skipped steps (read, then written: zero it once)
+ *   [5..7] reserved, written as 0.
+ * flags & LMV_NORM_SKIP_NONFINITE: when found_inf is set, [1] = 0 and [4] += 1 (lmv_adamw_flat_clip then leaves everything alone); without
+ * the flag a non-finite norm flows through as in torch (coef 0 for inf, NaN for NaN).
+ * step_dev (nullable): device int step count, advanced by one here unless the step is skipped.
+ * ws: lmv_grad_norm_workspace_bytes(segs, nsegs) bytes (one float per chunk), 4-byte aligned; no pre-zeroing. */
+typedef struct { const float* ptr; int64_t n; } lmv_norm_seg;
+#define LMV_GRAD_STAT_FLOATS 8
+#define LMV_NORM_CHUNK 16384
+enum { LMV_NORM_SKIP_NONFINITE = 1 };
+size_t lmv_grad_norm_workspace_bytes(const lmv_norm_seg* segs, int nsegs);
+int lmv_grad_norm(const lmv_norm_seg* segs, int nsegs, float max_norm, int flags, float* stat, int* step_dev, void* ws, size_t ws_bytes,
+                  void* stream);
+/* lmv_adamw_flat with the gradient scaled or clamped on the fly -- the gradients in memory are not rewritten:
+ * stat (nullable; what lmv_grad_norm wrote): g * stat[1] enters the update; stat[3] != 0 && stat[1] == 0 is a skipped step -- nothing is written
+ * (parameters, both moments and the bf16 copy stay as they are).  clip_value > 0: g is clamped to [-clip_value, clip_value] (clip mode 'value'). */
+int lmv_adamw_flat_clip(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, const float* wd_mask, void* shadow_bf16,
+                        int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay, int step, const int* step_dev,
+                        const float* stat, float clip_value, void* stream);
 /* Exponential moving average of the weights over the same flat buffer (timm.utils.ModelEmaV2: main.py:316, engine.py model_ema.update(model)):
  * ema[i] = decay * ema[i] + (1 - decay) * param[i], n % 4 == 0, one launch (lemevit_amd.optim.ModelEma). */
 int lmv_ema_flat(float* ema, const float* param, int64_t n, float decay, void* stream);

@@ -20,6 +20,7 @@ ACT_NONE, ACT_GELU, ACT_GELU_GRAD, ACT_GELU_BWD = 0, 1, 2, 3
 FOLD_CI_TAP, FOLD_TAP_CI = 0, 1
 ABI_VERSION = 14
 BLOCK_NO_JOIN, BLOCK_FUSED, BLOCK_DATA_ONLY = 1, 2, 4          # lmv_block_desc.flags
+GRAD_STAT_FLOATS, NORM_CHUNK, NORM_SKIP_NONFINITE = 8, 16384, 1          # LMV_GRAD_STAT_FLOATS, LMV_NORM_CHUNK, LMV_NORM_SKIP_NONFINITE
 
 
 class LinearProblem(C.Structure):
@@ -90,6 +91,10 @@ class DStageBlockParams(C.Structure):
 
 class TransposeSeg(C.Structure):
     _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("rows", C.c_int32), ("cols", C.c_int32)]
+
+
+class NormSeg(C.Structure):
+    _fields_ = [("ptr", C.c_void_p), ("n", C.c_int64)]
 
 
 _P, _I, _L, _F, _Z = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_size_t
@@ -164,6 +169,9 @@ SIGNATURES = {
     "lmv_token_mean2_affine_fwd": (_I, [_P, _I, _P, _I, _I, _I, _P, _P, _P, _I, _P]),
     "lmv_token_mean2_bwd": (_I, [_P, _P, _I, _P, _I, _I, _I, _I, _P]),
     "lmv_adamw_flat": (_I, [_P, _P, _P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _I, _P, _P]),
+    "lmv_grad_norm_workspace_bytes": (_Z, [C.POINTER(NormSeg), _I]),
+    "lmv_grad_norm": (_I, [C.POINTER(NormSeg), _I, _F, _I, _P, _P, _P, _Z, _P]),
+    "lmv_adamw_flat_clip": (_I, [_P, _P, _P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _I, _P, _P, _F, _P]),
     "lmv_ema_flat": (_I, [_P, _P, _L, _F, _P]),
     "lmv_block_arena_bytes": (_Z, [C.POINTER(BlockDesc)]),
     "lmv_block_bwd_scratch_bytes": (_Z, [C.POINTER(BlockDesc)]),

@@ -334,15 +334,25 @@ __global__ __launch_bounds__(TPB) void col2im_nhwc_kernel(const T* __restrict__ 
   }
 }
 
-__global__ __launch_bounds__(TPB) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                   float* __restrict__ v, const float* __restrict__ wd_mask, bf16_t* __restrict__ shadow,
-                                                   const int* __restrict__ step_dev, int64_t n, float lr, float b1, float b2, float eps, float wd,
-                                                   float bc1, float bc2_sqrt) {
+// One body for both optimizer kernels.  CLIP = false is adamw_kernel, the unclipped step; CLIP = true (adamw_clip_kernel) scales the gradient by the device
+// coefficient stat[1] and / or clamps it to +-clip_value as it is read, and a skipped step (stat[3] != 0 and stat[1] == 0: lmv_grad_norm under
+// LMV_NORM_SKIP_NONFINITE) writes nothing.
+template <bool CLIP>
+__device__ __forceinline__ void adamw_body(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                           const float* __restrict__ wd_mask, bf16_t* __restrict__ shadow, const int* __restrict__ step_dev, int64_t n,
+                                           float lr, float b1, float b2, float eps, float wd, float bc1, float bc2_sqrt, const float* __restrict__ stat,
+                                           float clip_value) {
+  float coef = 1.f;
+  if (CLIP && stat) {
+    coef = stat[1];
+    if (stat[3] != 0.f && coef == 0.f) return;
+  }
   if (step_dev) {                                   // step count lives on the device (captured graphs replay the launch unchanged)
     const float t = (float)*step_dev;
     bc1 = 1.f - powf(b1, t);
     bc2_sqrt = sqrtf(1.f - powf(b2, t));
   }
+  const bool clamp = CLIP && clip_value > 0.f;
   const int64_t n4 = n >> 2;
   for (int64_t i = blockIdx.x * (int64_t)TPB + threadIdx.x; i < n4; i += (int64_t)gridDim.x * TPB) {
     float4 P = reinterpret_cast<float4*>(p)[i], G = reinterpret_cast<const float4*>(g)[i];
@@ -351,15 +361,34 @@ __global__ __launch_bounds__(TPB) void adamw_kernel(float* __restrict__ p, const
     float* pp = &P.x; const float* gg = &G.x; float* mm = &M.x; float* vv = &V.x; const float* ww = &W.x;
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
+      float gq = gg[q];
+      if (CLIP) {
+        gq *= coef;
+        if (clamp) gq = gq < -clip_value ? -clip_value : (gq > clip_value ? clip_value : gq);      // NaN stays NaN, as torch.clamp
+      }
       pp[q] *= 1.f - lr * wd * ww[q];                       // decoupled weight decay
-      mm[q] = b1 * mm[q] + (1.f - b1) * gg[q];
-      vv[q] = b2 * vv[q] + (1.f - b2) * gg[q] * gg[q];
+      mm[q] = b1 * mm[q] + (1.f - b1) * gq;
+      vv[q] = b2 * vv[q] + (1.f - b2) * gq * gq;
       const float denom = sqrtf(vv[q]) / bc2_sqrt + eps;
       pp[q] -= (lr / bc1) * mm[q] / denom;
     }
     reinterpret_cast<float4*>(p)[i] = P; reinterpret_cast<float4*>(m)[i] = M; reinterpret_cast<float4*>(v)[i] = V;
     if (shadow) reinterpret_cast<uint2*>(shadow)[i] = make_uint2(pack_bf2(P.x, P.y), pack_bf2(P.z, P.w));      // bf16 operand copy, refreshed in the same pass
   }
+}
+
+__global__ __launch_bounds__(TPB) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                   float* __restrict__ v, const float* __restrict__ wd_mask, bf16_t* __restrict__ shadow,
+                                                   const int* __restrict__ step_dev, int64_t n, float lr, float b1, float b2, float eps, float wd,
+                                                   float bc1, float bc2_sqrt) {
+  adamw_body<false>(p, g, m, v, wd_mask, shadow, step_dev, n, lr, b1, b2, eps, wd, bc1, bc2_sqrt, nullptr, 0.f);
+}
+
+__global__ __launch_bounds__(TPB) void adamw_clip_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                        float* __restrict__ v, const float* __restrict__ wd_mask, bf16_t* __restrict__ shadow,
+                                                        const int* __restrict__ step_dev, int64_t n, float lr, float b1, float b2, float eps, float wd,
+                                                        float bc1, float bc2_sqrt, const float* __restrict__ stat, float clip_value) {
+  adamw_body<true>(p, g, m, v, wd_mask, shadow, step_dev, n, lr, b1, b2, eps, wd, bc1, bc2_sqrt, stat, clip_value);
 }
 
 // exponential moving average of a flat fp32 parameter buffer: ema = decay * ema + (1 - decay) * param (timm.utils.ModelEmaV2, main.py:316 / engine.py: model_ema.update)
@@ -371,6 +400,90 @@ __global__ __launch_bounds__(TPB) void ema_kernel(float* __restrict__ ema, const
     const float4 P = reinterpret_cast<const float4*>(p)[i];
     E.x = fmaf(decay, E.x, w * P.x); E.y = fmaf(decay, E.y, w * P.y); E.z = fmaf(decay, E.z, w * P.z); E.w = fmaf(decay, E.w, w * P.w);
     reinterpret_cast<float4*>(ema)[i] = E;
+  }
+}
+
+// ---- global gradient norm and clipped update (lmv_grad_norm / lmv_adamw_flat_clip) -------------------------------------------------------
+// Stage 1: one workgroup per LMV_NORM_CHUNK elements of one segment.  Thread t owns the 16-byte groups t, t + 256, ... of its chunk (ascending), one
+// fp32 accumulator per component; the 1..3 elements behind the last whole group go to threads 0..2.  That mapping is a function of the chunk's length
+// alone, and a segment whose start is not 16-byte aligned runs the SAME mapping on 4-byte loads: the partial sums -- and with them the norm -- do not
+// depend on where a gradient happens to live.
+constexpr int NORM_MAX_SEGS = 96;                                            // segments per by-value table, i.e. per first-stage launch
+struct NormSegDev { const float* p; int64_t n; int64_t chunk0; };          // chunk0: the segment's first chunk within this launch
+struct NormTable { NormSegDev s[NORM_MAX_SEGS]; int n; int part0; };   // part0: this launch's first partial in the workspace
+constexpr int NORM_G = LMV_NORM_CHUNK / 4 / TPB;                           // 16-byte groups per thread of a full chunk
+static_assert(LMV_NORM_CHUNK % (4 * TPB) == 0, "a full chunk is a whole number of 16-byte groups per thread");
+
+template <bool VEC>
+__device__ __forceinline__ float4 norm_ld4(const float* q) {
+  if (VEC) return *reinterpret_cast<const float4*>(q);
+  return make_float4(q[0], q[1], q[2], q[3]);
+}
+__device__ __forceinline__ void norm_acc(float4& a, const float4 v) {
+  a.x = fmaf(v.x, v.x, a.x); a.y = fmaf(v.y, v.y, a.y); a.z = fmaf(v.z, v.z, a.z); a.w = fmaf(v.w, v.w, a.w);
+}
+template <bool VEC>
+__device__ __forceinline__ float4 norm_chunk(const float* __restrict__ q, int len) {
+  float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
+  const int t = threadIdx.x;
+  if (len == LMV_NORM_CHUNK) {                      // every chunk but a segment's last: all loads of the thread in flight at once
+    float4 v[NORM_G];
+#pragma unroll
+    for (int k = 0; k < NORM_G; ++k) v[k] = norm_ld4<VEC>(q + 4 * (t + k * TPB));
+#pragma unroll
+    for (int k = 0; k < NORM_G; ++k) norm_acc(a, v[k]);
+  } else {
+    const int n4 = len >> 2;
+    for (int j = t; j < n4; j += TPB) norm_acc(a, norm_ld4<VEC>(q + 4 * j));
+    if (t < (len & 3)) { const float e = q[4 * n4 + t]; a.x = fmaf(e, e, a.x); }
+  }
+  return a;
+}
+
+__global__ __launch_bounds__(TPB) void grad_norm_partial_kernel(const NormTable tb, float* __restrict__ partial) {
+  __shared__ float red[TPB / LMV_WAVE];
+  int si = 0;
+#pragma unroll 1
+  for (int k = 1; k < tb.n; ++k) if ((int64_t)blockIdx.x >= tb.s[k].chunk0) si = k;
+  const NormSegDev g = tb.s[si];
+  const int64_t start = ((int64_t)blockIdx.x - g.chunk0) * LMV_NORM_CHUNK;
+  const int64_t left = g.n - start;
+  const int len = left < LMV_NORM_CHUNK ? (int)left : LMV_NORM_CHUNK;
+  const float* q = g.p + start;
+  const float4 a = (((uintptr_t)g.p) & 15u) == 0 ? norm_chunk<true>(q, len) : norm_chunk<false>(q, len);
+  const float w = wave_sum((a.x + a.y) + (a.z + a.w));
+  if ((threadIdx.x & (LMV_WAVE - 1)) == 0) red[threadIdx.x / LMV_WAVE] = w;
+  __syncthreads();
+  if (threadIdx.x == 0) partial[tb.part0 + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+static_assert(TPB / LMV_WAVE == 4, "grad_norm_partial_kernel combines four waves");
+
+// Stage 2: one workgroup adds the partials in double, in an order fixed by their count, and writes stat (include/lemevit_hip.h)
+__global__ __launch_bounds__(TPB) void grad_norm_final_kernel(const float* __restrict__ partial, int nparts, float max_norm, int flags,
+                                                             float* __restrict__ stat, int* __restrict__ step_dev) {
+  __shared__ double red[TPB];
+  double a = 0.0;
+  for (int i = threadIdx.x; i < nparts; i += TPB) a += (double)partial[i];
+  red[threadIdx.x] = a;
+  __syncthreads();
+  for (int s = TPB / 2; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    const float norm = (float)sqrt(red[0]);
+    const bool bad = (__float_as_uint(norm) & 0x7f800000u) == 0x7f800000u;          // inf or NaN
+    float coef = 1.f;
+    if (max_norm > 0.f) {                                                          // torch.nn.utils.clip_grad_norm_: clamp(max_norm / (norm + 1e-6), max=1), NaN stays NaN
+      const float c = max_norm / (norm + 1e-6f);
+      coef = c < 1.f ? c : (c != c ? c : 1.f);
+    }
+    const bool skip = bad && (flags & LMV_NORM_SKIP_NONFINITE);
+    if (skip) coef = 0.f;
+    const float skipped = stat[4] + (skip ? 1.f : 0.f);
+    stat[0] = norm; stat[1] = coef; stat[2] = 1.f / coef; stat[3] = bad ? 1.f : 0.f; stat[4] = skipped;
+    stat[5] = 0.f; stat[6] = 0.f; stat[7] = 0.f;
+    if (step_dev && !skip) *step_dev += 1;
   }
 }
 
@@ -575,6 +688,73 @@ extern "C" int lmv_adamw_flat(float* param, const float* grad, float* exp_avg, f
   hipLaunchKernelGGL(adamw_kernel, dim3(grid_for(n / 4)), dim3(TPB), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, wd_mask,
                      reinterpret_cast<bf16_t*>(shadow_bf16), step_dev, n, lr, beta1, beta2, eps, weight_decay, bc1, bc2_sqrt);
   LMV_CHECK_LAUNCH("adamw_flat");
+  return LMV_OK;
+}
+
+// chunks of the table (one partial each), or -1 with the error set
+static int64_t grad_norm_chunks(const lmv_norm_seg* segs, int nsegs) {
+  if (!segs) LMV_FAIL(-1, "grad_norm: segs is NULL");
+  if (nsegs < 1) LMV_FAIL(-1, "grad_norm: nsegs=%d must be >= 1", nsegs);
+  int64_t chunks = 0;
+  for (int i = 0; i < nsegs; ++i) {
+    if (segs[i].n < 0) LMV_FAIL(-1, "grad_norm: segment %d has negative length %lld", i, (long long)segs[i].n);
+    if (segs[i].n > 0 && (!segs[i].ptr || ((uintptr_t)segs[i].ptr & 3u))) LMV_FAIL(-1, "grad_norm: segment %d is null or not 4-byte aligned", i);
+    chunks += (segs[i].n + LMV_NORM_CHUNK - 1) / LMV_NORM_CHUNK;
+  }
+  if (chunks >= (int64_t)1 << 31) LMV_FAIL(-1, "grad_norm: too many elements");
+  return chunks;
+}
+
+extern "C" size_t lmv_grad_norm_workspace_bytes(const lmv_norm_seg* segs, int nsegs) {
+  const int64_t chunks = grad_norm_chunks(segs, nsegs);
+  return chunks < 0 ? 0 : (size_t)chunks * sizeof(float);
+}
+
+extern "C" int lmv_grad_norm(const lmv_norm_seg* segs, int nsegs, float max_norm, int flags, float* stat, int* step_dev, void* ws, size_t ws_bytes,
+                             void* stream) {
+  const int64_t chunks = grad_norm_chunks(segs, nsegs);
+  if (chunks < 0) return LMV_ERR_SHAPE;
+  if (!stat || !lmv_aligned16(stat)) LMV_FAIL(LMV_ERR_SHAPE, "grad_norm: stat is null or not 16-byte aligned");
+  if (max_norm != max_norm) LMV_FAIL(LMV_ERR_SHAPE, "grad_norm: max_norm is NaN");
+  if (ws_bytes < (size_t)chunks * sizeof(float) || (chunks > 0 && (!ws || ((uintptr_t)ws & 3u))))
+    LMV_FAIL(LMV_ERR_SHAPE, "grad_norm: workspace of %zu bytes is null, misaligned or shorter than the %zu bytes of lmv_grad_norm_workspace_bytes", ws_bytes,
+             (size_t)chunks * sizeof(float));
+  hipStream_t st = (hipStream_t)stream;
+  float* partial = reinterpret_cast<float*>(ws);
+  int64_t part0 = 0;
+  for (int s0 = 0; s0 < nsegs; s0 += NORM_MAX_SEGS) {
+    NormTable tb{};
+    tb.n = nsegs - s0 < NORM_MAX_SEGS ? nsegs - s0 : NORM_MAX_SEGS;
+    tb.part0 = (int)part0;
+    int64_t c = 0;
+    for (int i = 0; i < tb.n; ++i) {
+      tb.s[i].p = segs[s0 + i].ptr; tb.s[i].n = segs[s0 + i].n; tb.s[i].chunk0 = c;
+      c += (segs[s0 + i].n + LMV_NORM_CHUNK - 1) / LMV_NORM_CHUNK;
+    }
+    if (c > 0) hipLaunchKernelGGL(grad_norm_partial_kernel, dim3((unsigned)c), dim3(TPB), 0, st, tb, partial);
+    part0 += c;
+  }
+  hipLaunchKernelGGL(grad_norm_final_kernel, dim3(1), dim3(TPB), 0, st, partial, (int)chunks, max_norm, flags, stat, step_dev);
+  LMV_CHECK_LAUNCH("grad_norm");
+  return LMV_OK;
+}
+
+extern "C" int lmv_adamw_flat_clip(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, const float* wd_mask, void* shadow_bf16,
+                                   int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay, int step, const int* step_dev,
+                                   const float* stat, float clip_value, void* stream) {
+  if (n <= 0) return LMV_OK;
+  if (n % 4) LMV_FAIL(LMV_ERR_SHAPE, "adamw_flat_clip: n=%lld must be a multiple of 4 (pad the flat buffer)", (long long)n);
+  if (!step_dev && step < 1) LMV_FAIL(LMV_ERR_SHAPE, "adamw_flat_clip: step must be >= 1");
+  if (!param || !grad || !exp_avg || !exp_avg_sq || !lmv_aligned16(param) || !lmv_aligned16(grad) || !lmv_aligned16(exp_avg) || !lmv_aligned16(exp_avg_sq) ||
+      !lmv_aligned16(wd_mask) || ((uintptr_t)shadow_bf16 & 7u) || ((uintptr_t)stat & 3u))
+    LMV_FAIL(LMV_ERR_SHAPE, "adamw_flat_clip: null or misaligned buffer");
+  if (!(clip_value >= 0.f)) LMV_FAIL(LMV_ERR_SHAPE, "adamw_flat_clip: clip_value must be >= 0 (0: no clamp)");
+  const float t = step_dev ? 1.f : (float)step;
+  const float bc1 = 1.f - powf(beta1, t);
+  const float bc2_sqrt = sqrtf(1.f - powf(beta2, t));
+  hipLaunchKernelGGL(adamw_clip_kernel, dim3(grid_for(n / 4)), dim3(TPB), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, wd_mask,
+                     reinterpret_cast<bf16_t*>(shadow_bf16), step_dev, n, lr, beta1, beta2, eps, weight_decay, bc1, bc2_sqrt, stat, clip_value);
+  LMV_CHECK_LAUNCH("adamw_flat_clip");
   return LMV_OK;
 }
 

@@ -89,6 +89,10 @@ class FlatGradSync:
         sync = attach_flat_grad_sync(model, opt)     # once; broadcasts rank 0's parameters and buffers
         ...
         opt.zero_grad(); loss.backward(); sync.finish(); opt.step()
+
+    Gradient clipping (``FlatAdamW(clip_grad=...)``, ``opt.clip_grad_norm_()``) needs nothing here: ``finish()`` runs before ``opt.step()``, so the
+    norm is taken on the AVERAGED gradients, which are bit-identical on every rank after the all-reduce, and ``ops.grad_norm`` sums in an order
+    fixed by the segment lengths alone -- every rank derives the same coefficient (and the same skip decision) with no extra collective.
     """
 
     def __init__(self, flat_grad: torch.Tensor, chunk_bounds, rest_params, group=None, force: bool = False, compress: Optional[str] = None, opt=None):

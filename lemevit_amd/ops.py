@@ -705,13 +705,46 @@ def transpose_batch(pairs: Sequence[Tuple[Tensor, Tensor]]) -> None:
 
 
 def adamw_flat(param: Tensor, grad: Tensor, exp_avg: Tensor, exp_avg_sq: Tensor, wd_mask: Optional[Tensor], lr: float, beta1: float,
-               beta2: float, eps: float, weight_decay: float, step: int, shadow: Optional[Tensor] = None, step_dev: Optional[Tensor] = None) -> None:
+               beta2: float, eps: float, weight_decay: float, step: int, shadow: Optional[Tensor] = None, step_dev: Optional[Tensor] = None,
+               stat: Optional[Tensor] = None, clip_value: float = 0.0) -> None:
+    """One launch of lmv_adamw_flat.  ``stat`` (what ``grad_norm`` wrote) and / or ``clip_value`` > 0 select lmv_adamw_flat_clip: the gradient enters the
+    update as ``g * stat[1]`` / clamped to ``[-clip_value, clip_value]`` (the gradients in memory are not rewritten), and a skipped step writes nothing."""
     if shadow is not None and (shadow.dtype != torch.bfloat16 or shadow.numel() != param.numel()):
         raise TypeError("adamw_flat: shadow must be a bfloat16 tensor of the parameter buffer's length")
     if step_dev is not None and step_dev.dtype != torch.int32:
         raise TypeError("adamw_flat: step_dev must be an int32 device scalar")
+    if stat is not None or clip_value:
+        if stat is not None and (stat.dtype != torch.float32 or stat.numel() < GRAD_STAT_FLOATS):
+            raise TypeError(f"adamw_flat: stat must be a float32 tensor of {GRAD_STAT_FLOATS} elements")
+        check(lib.lmv_adamw_flat_clip(_f32(param), _f32(grad), _f32(exp_avg), _f32(exp_avg_sq), _f32(wd_mask), _ptr(shadow), param.numel(), lr, beta1, beta2, eps,
+                                      weight_decay, step, _ptr(step_dev), _ptr(stat), float(clip_value), _stream()), "lmv_adamw_flat_clip")
+        return
     check(lib.lmv_adamw_flat(_f32(param), _f32(grad), _f32(exp_avg), _f32(exp_avg_sq), _f32(wd_mask), _ptr(shadow), param.numel(), lr, beta1, beta2, eps,
                              weight_decay, step, _ptr(step_dev), _stream()), "lmv_adamw_flat")
+
+
+GRAD_STAT_FLOATS = _lib.GRAD_STAT_FLOATS
+NORM_CHUNK = _lib.NORM_CHUNK          # elements per partial sum of grad_norm (LMV_NORM_CHUNK)
+
+
+def grad_norm(segments: Sequence[Tensor], max_norm: float, stat: Tensor, skip_nonfinite: bool = False, step_dev: Optional[Tensor] = None) -> Tensor:
+    """Global L2 norm of the fp32 tensors ``segments`` and the clipping coefficient for ``max_norm`` (<= 0: measure only), written to the device tensor
+    ``stat`` (lmv_grad_norm: [0] norm, [1] coef, [2] 1 / coef, [3] found_inf, [4] skipped steps) without a host synchronisation; returns ``stat``.
+    The summation order depends on the segment lengths alone, so two calls -- and all ranks of a data-parallel job -- agree bit for bit.
+    ``step_dev``: int32 device step count, advanced here unless the step is skipped (``skip_nonfinite`` and a non-finite norm)."""
+    if stat.dtype != torch.float32 or stat.numel() != GRAD_STAT_FLOATS:
+        raise TypeError(f"grad_norm: stat must be a float32 tensor of {GRAD_STAT_FLOATS} elements")
+    if step_dev is not None and step_dev.dtype != torch.int32:
+        raise TypeError("grad_norm: step_dev must be an int32 device scalar")
+    if not segments:
+        raise ValueError("grad_norm: no segments")
+    arr = (_lib.NormSeg * len(segments))()
+    for sg, t in zip(arr, segments):
+        sg.ptr, sg.n = _f32(t), t.numel()
+    ws = _workspace(int(lib.lmv_grad_norm_workspace_bytes(arr, len(arr))), stat.device)          # the partials: the scratch of this (device, stream)
+    check(lib.lmv_grad_norm(arr, len(arr), float(max_norm), _lib.NORM_SKIP_NONFINITE if skip_nonfinite else 0, _ptr(stat), _ptr(step_dev), _ptr(ws),
+                            ws.numel(), _stream()), "lmv_grad_norm")
+    return stat
 
 
 def ema_flat(ema: Tensor, param: Tensor, decay: float) -> None:

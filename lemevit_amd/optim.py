@@ -63,12 +63,36 @@ class FlatAdamW:
 
     Interface: ``step()``, ``zero_grad()``, ``param_groups`` (one dict per group with ``lr`` -- schedulers may edit it),
     ``state_dict()`` / ``load_state_dict()``, ``refresh()`` (re-derive the bf16 copies after the parameters were
-    changed by something else; done automatically after ``model.load_state_dict``)."""
+    changed by something else; done automatically after ``model.load_state_dict``).
+
+    Gradient clipping (engine.py:82-95 ``--clip-grad`` / ``--clip-mode``; the detection schedules' ``grad_clip=dict(max_norm=35, norm_type=2)``), all on the
+    device and without rewriting the block gradients:
+
+    * ``clip_grad=c, clip_mode="norm"``: every ``step()`` takes the global L2 norm of all gradients in one reduction (``ops.grad_norm``) and the updates
+      multiply the coefficient ``min(1, c / (norm + 1e-6))`` -- ``torch.nn.utils.clip_grad_norm_`` -- in as they read the gradients.
+    * ``clip_mode="value"``: the gradients are clamped to ``[-c, c]`` inside the flat update (no reduction).
+    * ``skip_nonfinite=True``: a step whose gradient norm is inf or NaN changes nothing -- parameters, moments, bf16 copies and the step count stay bit
+      for bit (what ``GradScaler`` does for the reference's reduced-precision runs); ``skipped_steps`` counts them
+      (it counts reductions that found a non-finite norm: one per ``step()``, or one per ``clip_grad_norm_()`` call where that is used -- call it once per step).
+    * ``track_grad_norm=True``: the norm is computed every step, clipped or not (``NativeScalerWithGradNormCount``, utils/__init__.py:311-331).
+
+    ``grad_norm`` / ``skipped_steps`` are 0-dim device tensors (views of the kernel's status words): reading them is the only synchronisation.
+    ``clip_grad`` is a host float like ``lr``: a captured graph bakes it in.  With none of these set, ``step()`` launches what it always did."""
 
     def __init__(self, model: nn.Module, lr: float = 1e-3, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8,
-                 weight_decay: float = 1e-2, no_decay: Callable[[str, Tensor], bool] = _default_no_decay, capturable: bool = True):
+                 weight_decay: float = 1e-2, no_decay: Callable[[str, Tensor], bool] = _default_no_decay, capturable: bool = True,
+                 clip_grad: Optional[float] = None, clip_mode: str = "norm", skip_nonfinite: bool = False, track_grad_norm: bool = False):
         from .model import LeMeBlock, _is_matrix
         self.betas, self.eps, self.weight_decay = betas, eps, weight_decay
+        if clip_mode == "agc":
+            raise NotImplementedError("FlatAdamW: clip_mode='agc' has no native form; timm's adaptive_clip_grad still works on the parameters of param_groups")
+        if clip_mode not in ("norm", "value"):
+            raise ValueError(f"FlatAdamW: unknown clip_mode {clip_mode!r} ('norm' or 'value')")
+        if clip_grad is not None and not float(clip_grad) > 0:
+            raise ValueError("FlatAdamW: clip_grad must be > 0 (None: no clipping)")
+        self.clip_grad, self.clip_mode = (None if clip_grad is None else float(clip_grad)), clip_mode
+        self.skip_nonfinite, self.track_grad_norm = bool(skip_nonfinite), bool(track_grad_norm)
+        self._armed = False               # clip_grad_norm_() has left the coefficient of the next step() in self._stat
         flat_named: List[Tuple[str, nn.Parameter, bool]] = []        # (name, param, wants bf16 copy)
         seen = set()
         for mname, mod in model.named_modules():
@@ -91,6 +115,8 @@ class FlatAdamW:
         self._wd_mask = torch.zeros(total, device=dev)
         self._shadow = torch.zeros(total, device=dev, dtype=torch.bfloat16)
         self._step_dev = torch.zeros((), device=dev, dtype=torch.int32)
+        self._stat = torch.zeros(ops.GRAD_STAT_FLOATS, device=dev)          # lmv_grad_norm: norm, coef, 1 / coef, found_inf, skipped steps
+        self.grad_norm, self.skipped_steps = self._stat[0], self._stat[4]
         self._slices: List[Tuple[str, nn.Parameter, int, int]] = []
         self._grad_views: List[Tensor] = []
         with torch.no_grad():
@@ -153,17 +179,51 @@ class FlatAdamW:
         return touched
 
     def zero_grad(self, set_to_none: bool = True) -> None:
+        self._armed = False
         self._flat_g.zero_()                                           # the flat gradients stay allocated: the kernels accumulate into them
         self._rebind(keep=False)
         if self._rest is not None:
             self._rest.zero_grad(set_to_none=set_to_none)
 
-    def _apply(self, s: int, e: int) -> None:
+    def _apply(self, s: int, e: int, stat: Optional[Tensor] = None, clip_value: float = 0.0) -> None:
         g0 = self.param_groups[0]          # schedulers / users may edit any of these (as for torch.optim.AdamW)
         b1, b2 = g0["betas"]
         wd = self._wd_mask[s:e]
         ops.adamw_flat(self._flat_p[s:e], self._flat_g[s:e], self._exp_avg[s:e], self._exp_avg_sq[s:e], wd, float(g0["lr"]),
-                       float(b1), float(b2), float(g0["eps"]), float(g0["weight_decay"]), 0, shadow=self._shadow[s:e], step_dev=self._step_dev)
+                       float(b1), float(b2), float(g0["eps"]), float(g0["weight_decay"]), 0, shadow=self._shadow[s:e], step_dev=self._step_dev,
+                       stat=stat, clip_value=clip_value)
+
+    def _rest_grads(self) -> List[Tensor]:
+        """Every present gradient of the parameters torch.optim.AdamW keeps."""
+        grads = [p.grad for g in (self._rest.param_groups if self._rest is not None else ()) for p in g["params"] if p.grad is not None]
+        if any(g.dtype != torch.float32 or g.is_sparse for g in grads):
+            raise TypeError("FlatAdamW: native clipping takes dense float32 gradients")
+        return grads
+
+    def _reduce(self, max_norm: float, step_dev: Optional[Tensor]) -> None:
+        """ONE reduction over the flat gradient buffer and every present gradient of the remaining parameters -> self._stat."""
+        rest = [g if g.is_contiguous() else g.contiguous() for g in self._rest_grads()]          # (a copy changes nothing here: the norm only reads)
+        ops.grad_norm([self._flat_g] + rest, max_norm, self._stat, skip_nonfinite=self.skip_nonfinite, step_dev=step_dev)
+
+    @torch.no_grad()
+    def clip_grad_norm_(self, max_norm: Optional[float] = None, norm_type: float = 2.0) -> Tensor:
+        """For loops that clip as a call of its own (timm's ``dispatch_clip_grad`` position, mmcv's ``OptimizerHook.clip_grads``): computes the global L2
+        norm of all gradients NOW, returns it (0-dim device tensor, no synchronisation) and arms the coefficient ``min(1, max_norm / (norm + 1e-6))`` for
+        the next ``step()``, which does not reduce again; ``zero_grad()`` disarms it.  ``max_norm=None`` takes the constructor's ``clip_grad`` (measure
+        only when that is unset or ``clip_mode='value'``).
+
+        Unlike ``torch.nn.utils.clip_grad_norm_`` this does NOT rescale the gradients in memory: the scaling happens inside the update.  Code that reads
+        ``p.grad`` after the call sees the unclipped values."""
+        if float(norm_type) != 2.0:
+            raise ValueError("FlatAdamW.clip_grad_norm_: only the L2 norm (norm_type=2) is computed natively")
+        if max_norm is None:
+            max_norm = self.clip_grad if self.clip_mode == "norm" else None
+        from . import blocks as _blocks
+        _blocks.drain_deferred()
+        self._rebind(keep=True)
+        self._reduce(0.0 if max_norm is None else float(max_norm), None)
+        self._armed = True
+        return self.grad_norm
 
     def rebind_grads(self) -> list:
         """Public form of ``_rebind(keep=True)``: call before anything reads the flat gradient buffer directly (FlatGradSync.finish does).  Returns the (offset, length)
@@ -175,10 +235,31 @@ class FlatAdamW:
         from . import blocks as _blocks
         _blocks.drain_deferred()           # backstop: the weight-gradient side stream must have been joined before the update reads the gradients
         self._rebind(keep=True)
+        by_norm = self.clip_grad is not None and self.clip_mode == "norm"
+        reduce = self._armed or by_norm or self.skip_nonfinite or self.track_grad_norm          # the update reads self._stat
+        value = self.clip_grad if self.clip_grad is not None and self.clip_mode == "value" else 0.0
+        counted = reduce and not self._armed
+        if counted:
+            self._reduce(self.clip_grad if by_norm else 0.0, self._step_dev)          # stage 2 advances the step count unless it skips the step
         if self._rest is not None:
-            self._rest.step()
-        self._step_dev += 1
-        self._apply(0, self._flat_p.numel())
+            grads = self._rest_grads() if value else []
+            if grads:                      # (the multi-tensor ops refuse an empty list)
+                torch._foreach_clamp_min_(grads, -value)
+                torch._foreach_clamp_max_(grads, value)
+            # torch's fused AdamW divides the gradients by `grad_scale` and leaves moments and step counts alone when `found_inf` is set (what GradScaler
+            # hands it): the same coefficient and the same skip decision as the flat update, with no pass of their own
+            if reduce:
+                self._rest.grad_scale = self._stat[2]
+                self._rest.found_inf = self._stat[3] if self.skip_nonfinite else None
+            try:
+                self._rest.step()
+            finally:
+                if reduce:
+                    self._rest.grad_scale = self._rest.found_inf = None
+        if not counted:                    # (armed: the norm was taken by clip_grad_norm_(), which leaves the step count alone)
+            self._step_dev += (self._stat[3] == 0).to(torch.int32) if self._armed and self.skip_nonfinite else 1
+        self._armed = False
+        self._apply(0, self._flat_p.numel(), self._stat if reduce else None, value)
         ops.transpose_batch(self._tpairs)
 
     @torch.no_grad()
