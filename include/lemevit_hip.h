@@ -432,6 +432,21 @@ int lmv_grad_norm(const lmv_norm_seg* segs, int nsegs, float max_norm, int flags
 int lmv_adamw_flat_clip(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, const float* wd_mask, void* shadow_bf16,
                         int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay, int step, const int* step_dev,
                         const float* stat, float clip_value, void* stream);
+/* lmv_adamw_flat_clip with the learning rate and the weight decay of every element read from DEVICE memory by the running kernel: element i takes
+ * groups[group_of_unit[i / LMV_ADAMW_UNIT]] (layer-wise rate decay, lr_mult by prefix), and a captured hipGraph replays with whatever the table holds
+ * at replay time (a scheduled rate; lemevit_amd.optim.FlatAdamW(layer_decay= / lr_scale= / device_lr=), sync_hyper()).  There is no wd_mask: a group
+ * that does not decay has weight_decay = 0.  group_of_unit: device, n / LMV_ADAMW_UNIT bytes; a byte >= ngroups reads the last entry.  groups: device,
+ * 8-byte aligned, ngroups entries (1 .. LMV_ADAMW_MAX_GROUPS).  n % LMV_ADAMW_UNIT == 0.  stat (nullable) / clip_value (0: none) / step / step_dev:
+ * as lmv_adamw_flat_clip; with neither stat nor clip_value the launch is lmv_adamw_flat's arithmetic.  On a sub-range whose elements share one group
+ * the result equals, bit for bit, what lmv_adamw_flat (neither stat nor clip_value) or lmv_adamw_flat_clip (either) computes there with that group's
+ * lr and weight_decay.  Refused with LMV_ERR_SHAPE before any launch: n % LMV_ADAMW_UNIT, ngroups outside 1 .. LMV_ADAMW_MAX_GROUPS, a null or
+ * misaligned buffer (the fp32 buffers to 16 bytes, groups to 8), step < 1 without step_dev, clip_value < 0 or NaN. */
+#define LMV_ADAMW_UNIT 8
+#define LMV_ADAMW_MAX_GROUPS 256
+typedef struct { float lr; float weight_decay; } lmv_adamw_group;
+int lmv_adamw_flat_groups(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, void* shadow_bf16, int64_t n,
+                          const uint8_t* group_of_unit, const lmv_adamw_group* groups, int ngroups, float beta1, float beta2, float eps, int step,
+                          const int* step_dev, const float* stat, float clip_value, void* stream);
 /* Exponential moving average of the weights over the same flat buffer (timm.utils.ModelEmaV2: main.py:316, engine.py model_ema.update(model)):
  * ema[i] = decay * ema[i] + (1 - decay) * param[i], n % 4 == 0, one launch (lemevit_amd.optim.ModelEma). */
 int lmv_ema_flat(float* ema, const float* param, int64_t n, float decay, void* stream);

@@ -21,6 +21,7 @@ FOLD_CI_TAP, FOLD_TAP_CI = 0, 1
 ABI_VERSION = 14
 BLOCK_NO_JOIN, BLOCK_FUSED, BLOCK_DATA_ONLY = 1, 2, 4          # lmv_block_desc.flags
 GRAD_STAT_FLOATS, NORM_CHUNK, NORM_SKIP_NONFINITE = 8, 16384, 1          # LMV_GRAD_STAT_FLOATS, LMV_NORM_CHUNK, LMV_NORM_SKIP_NONFINITE
+ADAMW_UNIT, ADAMW_MAX_GROUPS = 8, 256          # LMV_ADAMW_UNIT, LMV_ADAMW_MAX_GROUPS
 
 
 class LinearProblem(C.Structure):
@@ -95,6 +96,10 @@ class TransposeSeg(C.Structure):
 
 class NormSeg(C.Structure):
     _fields_ = [("ptr", C.c_void_p), ("n", C.c_int64)]
+
+
+class AdamWGroup(C.Structure):
+    _fields_ = [("lr", C.c_float), ("weight_decay", C.c_float)]
 
 
 _P, _I, _L, _F, _Z = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_size_t
@@ -172,6 +177,7 @@ SIGNATURES = {
     "lmv_grad_norm_workspace_bytes": (_Z, [C.POINTER(NormSeg), _I]),
     "lmv_grad_norm": (_I, [C.POINTER(NormSeg), _I, _F, _I, _P, _P, _P, _Z, _P]),
     "lmv_adamw_flat_clip": (_I, [_P, _P, _P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _I, _P, _P, _F, _P]),
+    "lmv_adamw_flat_groups": (_I, [_P, _P, _P, _P, _P, _L, _P, _P, _I, _F, _F, _F, _I, _P, _P, _F, _P]),
     "lmv_ema_flat": (_I, [_P, _P, _L, _F, _P]),
     "lmv_block_arena_bytes": (_Z, [C.POINTER(BlockDesc)]),
     "lmv_block_bwd_scratch_bytes": (_Z, [C.POINTER(BlockDesc)]),

@@ -334,14 +334,20 @@ __global__ __launch_bounds__(TPB) void col2im_nhwc_kernel(const T* __restrict__ 
   }
 }
 
-// One body for both optimizer kernels.  CLIP = false is adamw_kernel, the unclipped step; CLIP = true (adamw_clip_kernel) scales the gradient by the device
+// One body for all optimizer kernels.  CLIP = false is adamw_kernel, the unclipped step; CLIP = true (adamw_clip_kernel) scales the gradient by the device
 // coefficient stat[1] and / or clamps it to +-clip_value as it is read, and a skipped step (stat[3] != 0 and stat[1] == 0: lmv_grad_norm under
-// LMV_NORM_SKIP_NONFINITE) writes nothing.
-template <bool CLIP>
+// LMV_NORM_SKIP_NONFINITE) writes nothing.  GROUPS = true (adamw_groups_kernel / adamw_groups_clip_kernel, lmv_adamw_flat_groups): lr and weight_decay of
+// a 16-byte group of elements come from a table in DEVICE memory, groups[group_of_unit[i / LMV_ADAMW_UNIT]], read by the running kernel -- a replayed
+// graph sees the table of the replay -- and staged in LDS (`tab`, one float4 per group: lr, weight_decay, the 0 / 1 decay factor that stands where
+// wd_mask stands, so that `1 - lr * wd * w` keeps its shape and contracts as in the scalar kernels; bit-identity with them is tested).  Both values of
+// CLIP exist with GROUPS because the compiler contracts the first-moment update differently in the two scalar kernels (fma(1 - b1, g, b1 * m) without
+// CLIP, fma(b1, m, (1 - b1) * g) with): one grouped kernel could not match both bit for bit.
+template <bool CLIP, bool GROUPS = false>
 __device__ __forceinline__ void adamw_body(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
                                            const float* __restrict__ wd_mask, bf16_t* __restrict__ shadow, const int* __restrict__ step_dev, int64_t n,
                                            float lr, float b1, float b2, float eps, float wd, float bc1, float bc2_sqrt, const float* __restrict__ stat,
-                                           float clip_value) {
+                                           float clip_value, const uint8_t* __restrict__ group_of_unit = nullptr,
+                                           const lmv_adamw_group* __restrict__ groups = nullptr, int ngroups = 0, float4* tab = nullptr) {
   float coef = 1.f;
   if (CLIP && stat) {
     coef = stat[1];
@@ -352,12 +358,28 @@ __device__ __forceinline__ void adamw_body(float* __restrict__ p, const float* _
     bc1 = 1.f - powf(b1, t);
     bc2_sqrt = sqrtf(1.f - powf(b2, t));
   }
+  if (GROUPS) {                                     // (behind the skip test, which is uniform: every thread of the workgroup reaches the barrier or none does)
+    static_assert(LMV_ADAMW_MAX_GROUPS <= TPB, "one table entry per thread");
+    if ((int)threadIdx.x < ngroups) {
+      const lmv_adamw_group e = groups[threadIdx.x];
+      tab[threadIdx.x] = make_float4(e.lr, e.weight_decay, e.weight_decay != 0.f ? 1.f : 0.f, 0.f);
+    }
+    __syncthreads();
+  }
   const bool clamp = CLIP && clip_value > 0.f;
   const int64_t n4 = n >> 2;
   for (int64_t i = blockIdx.x * (int64_t)TPB + threadIdx.x; i < n4; i += (int64_t)gridDim.x * TPB) {
     float4 P = reinterpret_cast<float4*>(p)[i], G = reinterpret_cast<const float4*>(g)[i];
     float4 M = reinterpret_cast<float4*>(m)[i], V = reinterpret_cast<float4*>(v)[i];
-    float4 W = wd_mask ? reinterpret_cast<const float4*>(wd_mask)[i] : make_float4(1.f, 1.f, 1.f, 1.f);
+    float4 W;
+    if (GROUPS) {                                   // one group byte per LMV_ADAMW_UNIT elements = two 16-byte groups: neighbouring lanes share it
+      int gi = group_of_unit[i / (LMV_ADAMW_UNIT / 4)];
+      gi = gi < ngroups ? gi : ngroups - 1;         // the host never writes one out of range; the table is not read past its end either way
+      const float4 e = tab[gi];
+      lr = e.x; wd = e.y; W = make_float4(e.z, e.z, e.z, e.z);
+    } else {
+      W = wd_mask ? reinterpret_cast<const float4*>(wd_mask)[i] : make_float4(1.f, 1.f, 1.f, 1.f);
+    }
     float* pp = &P.x; const float* gg = &G.x; float* mm = &M.x; float* vv = &V.x; const float* ww = &W.x;
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
@@ -389,6 +411,23 @@ __global__ __launch_bounds__(TPB) void adamw_clip_kernel(float* __restrict__ p, 
                                                         const int* __restrict__ step_dev, int64_t n, float lr, float b1, float b2, float eps, float wd,
                                                         float bc1, float bc2_sqrt, const float* __restrict__ stat, float clip_value) {
   adamw_body<true>(p, g, m, v, wd_mask, shadow, step_dev, n, lr, b1, b2, eps, wd, bc1, bc2_sqrt, stat, clip_value);
+}
+
+__global__ __launch_bounds__(TPB) void adamw_groups_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                          float* __restrict__ v, bf16_t* __restrict__ shadow, const int* __restrict__ step_dev, int64_t n,
+                                                          const uint8_t* __restrict__ group_of_unit, const lmv_adamw_group* __restrict__ groups,
+                                                          int ngroups, float b1, float b2, float eps, float bc1, float bc2_sqrt) {
+  __shared__ float4 tab[LMV_ADAMW_MAX_GROUPS];
+  adamw_body<false, true>(p, g, m, v, nullptr, shadow, step_dev, n, 0.f, b1, b2, eps, 0.f, bc1, bc2_sqrt, nullptr, 0.f, group_of_unit, groups, ngroups, tab);
+}
+
+__global__ __launch_bounds__(TPB) void adamw_groups_clip_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                               float* __restrict__ v, bf16_t* __restrict__ shadow, const int* __restrict__ step_dev,
+                                                               int64_t n, const uint8_t* __restrict__ group_of_unit,
+                                                               const lmv_adamw_group* __restrict__ groups, int ngroups, float b1, float b2, float eps,
+                                                               float bc1, float bc2_sqrt, const float* __restrict__ stat, float clip_value) {
+  __shared__ float4 tab[LMV_ADAMW_MAX_GROUPS];
+  adamw_body<true, true>(p, g, m, v, nullptr, shadow, step_dev, n, 0.f, b1, b2, eps, 0.f, bc1, bc2_sqrt, stat, clip_value, group_of_unit, groups, ngroups, tab);
 }
 
 // exponential moving average of a flat fp32 parameter buffer: ema = decay * ema + (1 - decay) * param (timm.utils.ModelEmaV2, main.py:316 / engine.py: model_ema.update)
@@ -755,6 +794,31 @@ extern "C" int lmv_adamw_flat_clip(float* param, const float* grad, float* exp_a
   hipLaunchKernelGGL(adamw_clip_kernel, dim3(grid_for(n / 4)), dim3(TPB), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, wd_mask,
                      reinterpret_cast<bf16_t*>(shadow_bf16), step_dev, n, lr, beta1, beta2, eps, weight_decay, bc1, bc2_sqrt, stat, clip_value);
   LMV_CHECK_LAUNCH("adamw_flat_clip");
+  return LMV_OK;
+}
+
+extern "C" int lmv_adamw_flat_groups(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, void* shadow_bf16, int64_t n,
+                                     const uint8_t* group_of_unit, const lmv_adamw_group* groups, int ngroups, float beta1, float beta2, float eps,
+                                     int step, const int* step_dev, const float* stat, float clip_value, void* stream) {
+  if (n <= 0) return LMV_OK;
+  if (n % LMV_ADAMW_UNIT) LMV_FAIL(LMV_ERR_SHAPE, "adamw_flat_groups: n=%lld must be a multiple of %d (one group byte per %d elements)", (long long)n, LMV_ADAMW_UNIT, LMV_ADAMW_UNIT);
+  if (ngroups < 1 || ngroups > LMV_ADAMW_MAX_GROUPS) LMV_FAIL(LMV_ERR_SHAPE, "adamw_flat_groups: ngroups=%d must be 1..%d", ngroups, LMV_ADAMW_MAX_GROUPS);
+  if (!step_dev && step < 1) LMV_FAIL(LMV_ERR_SHAPE, "adamw_flat_groups: step must be >= 1");
+  if (!param || !grad || !exp_avg || !exp_avg_sq || !group_of_unit || !groups || !lmv_aligned16(param) || !lmv_aligned16(grad) || !lmv_aligned16(exp_avg) ||
+      !lmv_aligned16(exp_avg_sq) || ((uintptr_t)groups & 7u) || ((uintptr_t)shadow_bf16 & 7u) || ((uintptr_t)stat & 3u) || ((uintptr_t)step_dev & 3u))
+    LMV_FAIL(LMV_ERR_SHAPE, "adamw_flat_groups: null or misaligned buffer");
+  if (!(clip_value >= 0.f)) LMV_FAIL(LMV_ERR_SHAPE, "adamw_flat_groups: clip_value must be >= 0 (0: no clamp)");
+  const float t = step_dev ? 1.f : (float)step;
+  const float bc1 = 1.f - powf(beta1, t);
+  const float bc2_sqrt = sqrtf(1.f - powf(beta2, t));
+  // the same choice lemevit_amd.ops.adamw_flat makes between lmv_adamw_flat and lmv_adamw_flat_clip, so that either pair agrees bit for bit
+  if (stat || clip_value > 0.f)
+    hipLaunchKernelGGL(adamw_groups_clip_kernel, dim3(grid_for(n / 4)), dim3(TPB), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq,
+                       reinterpret_cast<bf16_t*>(shadow_bf16), step_dev, n, group_of_unit, groups, ngroups, beta1, beta2, eps, bc1, bc2_sqrt, stat, clip_value);
+  else
+    hipLaunchKernelGGL(adamw_groups_kernel, dim3(grid_for(n / 4)), dim3(TPB), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq,
+                       reinterpret_cast<bf16_t*>(shadow_bf16), step_dev, n, group_of_unit, groups, ngroups, beta1, beta2, eps, bc1, bc2_sqrt);
+  LMV_CHECK_LAUNCH("adamw_flat_groups");
   return LMV_OK;
 }
 

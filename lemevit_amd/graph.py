@@ -22,10 +22,15 @@ class GraphedStep:
 
     Requirements on ``step_fn``: static shapes, no host synchronisation (``.item()``, prints of tensors), optimizers
     constructed with ``capturable=True``.  Outputs the caller wants to read must be written to tensors the closure
-    owns (they are overwritten on every replay)."""
+    owns (they are overwritten on every replay).
 
-    def __init__(self, step_fn: Callable[[], None], warmup: int = 3, pre_capture: Optional[Callable[[], None]] = None):
+    ``before_replay``: called ahead of every replay, on the host -- the place for work the captured launches cannot do themselves, such as
+    ``FlatAdamW.sync_hyper`` (uploads the learning rates a scheduler wrote into ``param_groups`` to the device table the captured update reads)."""
+
+    def __init__(self, step_fn: Callable[[], None], warmup: int = 3, pre_capture: Optional[Callable[[], None]] = None,
+                 before_replay: Optional[Callable[[], None]] = None):
         self._fn = step_fn
+        self._before_replay = before_replay
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
@@ -47,6 +52,8 @@ class GraphedStep:
         # hand-off is an exception on the next call at the latest.  Callers that consume the outputs of the LAST replay run ops.check_stage_errors(sync=True) first.
         from . import ops as _ops
         _ops.check_stage_errors("graph replay", sync=False)
+        if self._before_replay is not None:
+            self._before_replay()
         self.graph.replay()
 
 
@@ -101,10 +108,11 @@ def split_forward(model: Callable, x: torch.Tensor, parts: int, outs: Optional[l
     return torch.cat(ys)
 
 
-def try_graphed(step_fn: Callable[[], None], warmup: int = 3, pre_capture: Optional[Callable[[], None]] = None):
+def try_graphed(step_fn: Callable[[], None], warmup: int = 3, pre_capture: Optional[Callable[[], None]] = None,
+                before_replay: Optional[Callable[[], None]] = None):
     """GraphedStep if capture succeeds, else the eager callable (with the reason)."""
     try:
-        return GraphedStep(step_fn, warmup, pre_capture), None
+        return GraphedStep(step_fn, warmup, pre_capture, before_replay), None
     except Exception as e:  # capture can fail on ops that synchronise; fall back to eager
         torch.cuda.synchronize()
         if "lost an in-launch hand-off" in str(e):

@@ -723,7 +723,34 @@ def adamw_flat(param: Tensor, grad: Tensor, exp_avg: Tensor, exp_avg_sq: Tensor,
                              weight_decay, step, _ptr(step_dev), _stream()), "lmv_adamw_flat")
 
 
+def adamw_flat_groups(param: Tensor, grad: Tensor, exp_avg: Tensor, exp_avg_sq: Tensor, group_of_unit: Tensor, groups: Tensor, beta1: float, beta2: float,
+                      eps: float, step: int, shadow: Optional[Tensor] = None, step_dev: Optional[Tensor] = None, stat: Optional[Tensor] = None,
+                      clip_value: float = 0.0) -> None:
+    """One launch of lmv_adamw_flat_groups: ``adamw_flat`` with the learning rate and the weight decay of every run of ``ADAMW_UNIT`` elements taken from
+    the device table ``groups`` (float32 ``[G, 2]``: lr, weight_decay; G <= ``ADAMW_MAX_GROUPS``) at the index ``group_of_unit`` (uint8, ``n / ADAMW_UNIT``
+    elements) holds for it.  The running kernel reads the table: rewriting it on the device changes the next launch -- and the next replay of a captured
+    one -- with the same host arguments.  No ``wd_mask``: a group that does not decay carries weight_decay 0."""
+    n = param.numel()
+    if n % ADAMW_UNIT:
+        raise ValueError(f"adamw_flat_groups: the buffer length {n} must be a multiple of {ADAMW_UNIT}")
+    if group_of_unit.dtype != torch.uint8 or group_of_unit.numel() != n // ADAMW_UNIT:
+        raise TypeError(f"adamw_flat_groups: group_of_unit must be a uint8 tensor of n / {ADAMW_UNIT} = {n // ADAMW_UNIT} elements")
+    if groups.dtype != torch.float32 or groups.dim() != 2 or groups.shape[1] != 2 or not 1 <= groups.shape[0] <= ADAMW_MAX_GROUPS:
+        raise TypeError(f"adamw_flat_groups: groups must be a float32 tensor [G, 2] (lr, weight_decay) with 1 <= G <= {ADAMW_MAX_GROUPS}")
+    if any(t.numel() != n for t in (grad, exp_avg, exp_avg_sq)):
+        raise TypeError("adamw_flat_groups: grad, exp_avg and exp_avg_sq must have the parameter buffer's length")
+    if shadow is not None and (shadow.dtype != torch.bfloat16 or shadow.numel() != n):
+        raise TypeError("adamw_flat_groups: shadow must be a bfloat16 tensor of the parameter buffer's length")
+    if step_dev is not None and step_dev.dtype != torch.int32:
+        raise TypeError("adamw_flat_groups: step_dev must be an int32 device scalar")
+    if stat is not None and (stat.dtype != torch.float32 or stat.numel() < GRAD_STAT_FLOATS):
+        raise TypeError(f"adamw_flat_groups: stat must be a float32 tensor of {GRAD_STAT_FLOATS} elements")
+    check(lib.lmv_adamw_flat_groups(_f32(param), _f32(grad), _f32(exp_avg), _f32(exp_avg_sq), _ptr(shadow), n, _ptr(group_of_unit), _ptr(groups),
+                                    groups.shape[0], beta1, beta2, eps, step, _ptr(step_dev), _ptr(stat), float(clip_value), _stream()), "lmv_adamw_flat_groups")
+
+
 GRAD_STAT_FLOATS = _lib.GRAD_STAT_FLOATS
+ADAMW_UNIT, ADAMW_MAX_GROUPS = _lib.ADAMW_UNIT, _lib.ADAMW_MAX_GROUPS
 NORM_CHUNK = _lib.NORM_CHUNK          # elements per partial sum of grad_norm (LMV_NORM_CHUNK)
 
 

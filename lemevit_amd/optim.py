@@ -13,6 +13,8 @@ gradients written in place -- wrap the model in DDP with a regular optimizer ins
 """
 from __future__ import annotations
 
+import math
+import re
 import weakref
 from typing import Callable, Dict, Iterable, List, Optional, Tuple
 
@@ -58,6 +60,46 @@ def _default_no_decay(name: str, p: Tensor) -> bool:
     return p.ndim <= 1          # biases, LayerNorm / BatchNorm affine, as benchmark.py's create_optimizer_v2 (filter_bias_and_bn)
 
 
+_STAGE_RE = re.compile(r"(?:^|\.)(downsample_layers|meta_token_downsample)\.(\d+)\.")
+_BLOCK_STAGE_RE = re.compile(r"(?:^|\.)stages\.(\d+)\.\d+$")
+
+
+def layer_ids(model: nn.Module) -> Dict[str, int]:
+    """Layer id of every parameter of a ``LeMeViT`` / ``LeMeViTBackbone`` for layer-wise learning-rate decay (``utils/parser.py:107`` ``--layer-decay`` ->
+    timm's ``param_groups_layer_decay``), with L = the number of ``LeMeBlock`` s in forward order:
+
+    * 0: ``meta_tokens``, ``downsample_layers.0.*``, ``meta_token_downsample.0.*`` (the stem);
+    * k + 1: the k-th block (0-based);
+    * ``downsample_layers.s.*`` / ``meta_token_downsample.s.*``, s >= 1: the id of the first block of stage s (they feed it);
+    * L + 1: everything else (``norm``, ``norm_c``, ``head``, ``extra_norms``, names this function does not know).
+
+    The rate scale of id i is ``layer_decay ** (L + 1 - i)``: 1 for the head, the smallest for the stem.  Pure host code: works on a model built on the CPU."""
+    from .model import LeMeBlock
+    blocks = [name for name, mod in model.named_modules() if isinstance(mod, LeMeBlock)]
+    top = len(blocks) + 1
+    block_id = {name: k + 1 for k, name in enumerate(blocks)}
+    stage_first: Dict[int, int] = {}
+    for name in blocks:
+        m = _BLOCK_STAGE_RE.search(name)
+        if m:
+            stage_first.setdefault(int(m.group(1)), block_id[name])
+    prefixes = sorted(blocks, key=len, reverse=True)
+    ids: Dict[str, int] = {}
+    for name, _ in model.named_parameters():
+        owner = next((b for b in prefixes if name.startswith(b + ".")), None)
+        m = _STAGE_RE.search(name)
+        if owner is not None:
+            ids[name] = block_id[owner]
+        elif name == "meta_tokens" or name.endswith(".meta_tokens"):
+            ids[name] = 0
+        elif m:
+            s = int(m.group(2))
+            ids[name] = 0 if s == 0 else stage_first.get(s, top)
+        else:
+            ids[name] = top
+    return ids
+
+
 class FlatAdamW:
     """AdamW over ``model``: block parameters flat + fused into one launch, everything else ``torch.optim.AdamW(fused=True)``.
 
@@ -77,12 +119,31 @@ class FlatAdamW:
     * ``track_grad_norm=True``: the norm is computed every step, clipped or not (``NativeScalerWithGradNormCount``, utils/__init__.py:311-331).
 
     ``grad_norm`` / ``skipped_steps`` are 0-dim device tensors (views of the kernel's status words): reading them is the only synchronisation.
-    ``clip_grad`` is a host float like ``lr``: a captured graph bakes it in.  With none of these set, ``step()`` launches what it always did."""
+    ``clip_grad`` is a host float: a captured graph bakes it in.  With none of these set, ``step()`` launches what it always did.
+
+    Per-group and scheduled learning rates (table mode; all three keywords default to off, and then nothing below exists: ``_hyper`` is None):
+
+    * ``layer_decay=d`` (0 < d <= 1): layer-wise rate decay, ``lr * d ** (L + 1 - layer_ids(model)[name])`` (``--layer-decay``, timm's rule).
+    * ``lr_scale=f``: ``f(name, param)`` is the parameter's rate multiplier (mmcv's ``lr_mult`` by prefix).  Not together with ``layer_decay``.
+    * ``device_lr=True``: table mode with unit scales -- for a scheduled rate under graph capture.  Implied by the other two.
+
+    The flat layout does not change.  Parameters with the same (scale, decays or not) form a group; ``param_groups`` holds one dict per group of flat
+    parameters (``lr`` = base rate x ``lr_scale``, the timm convention: schedulers write ``g['lr'] = value * g['lr_scale']``), then one per group of the
+    remaining parameters.  The (lr, weight_decay) of the flat groups live in a device table that ONE ``lmv_adamw_flat_groups`` launch reads as it runs;
+    ``sync_hyper()`` uploads the host values when one of them changed (``step()`` calls it, except under capture: a captured step reads the table and
+    the device rates of the remaining groups, so ``GraphedStep(step, before_replay=opt.sync_hyper)`` follows a schedule).  What a capture still bakes
+    in: ``clip_grad``, ``betas``, ``eps`` and the weight decay of the remaining (torch-held) groups."""
 
     def __init__(self, model: nn.Module, lr: float = 1e-3, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8,
                  weight_decay: float = 1e-2, no_decay: Callable[[str, Tensor], bool] = _default_no_decay, capturable: bool = True,
-                 clip_grad: Optional[float] = None, clip_mode: str = "norm", skip_nonfinite: bool = False, track_grad_norm: bool = False):
+                 clip_grad: Optional[float] = None, clip_mode: str = "norm", skip_nonfinite: bool = False, track_grad_norm: bool = False,
+                 layer_decay: Optional[float] = None, lr_scale: Optional[Callable[[str, Tensor], float]] = None, device_lr: bool = False):
         from .model import LeMeBlock, _is_matrix
+        if layer_decay is not None and lr_scale is not None:
+            raise ValueError("FlatAdamW: layer_decay and lr_scale are mutually exclusive (fold the layer rule into lr_scale)")
+        if layer_decay is not None and not 0.0 < float(layer_decay) <= 1.0:
+            raise ValueError(f"FlatAdamW: layer_decay={layer_decay!r} must be in (0, 1]")
+        table = bool(device_lr) or layer_decay is not None or lr_scale is not None
         self.betas, self.eps, self.weight_decay = betas, eps, weight_decay
         if clip_mode == "agc":
             raise NotImplementedError("FlatAdamW: clip_mode='agc' has no native form; timm's adaptive_clip_grad still works on the parameters of param_groups")
@@ -112,7 +173,7 @@ class FlatAdamW:
         self._flat_g = torch.zeros(total, device=dev)
         self._exp_avg = torch.zeros(total, device=dev)
         self._exp_avg_sq = torch.zeros(total, device=dev)
-        self._wd_mask = torch.zeros(total, device=dev)
+        self._wd_mask = None if table else torch.zeros(total, device=dev)          # table mode: the group's weight_decay (0 for a group that does not decay) stands in
         self._shadow = torch.zeros(total, device=dev, dtype=torch.bfloat16)
         self._step_dev = torch.zeros((), device=dev, dtype=torch.int32)
         self._stat = torch.zeros(ops.GRAD_STAT_FLOATS, device=dev)          # lmv_grad_norm: norm, coef, 1 / coef, found_inf, skipped steps
@@ -127,7 +188,7 @@ class FlatAdamW:
                 p.grad = self._flat_g[off:off + n].view(p.shape)
                 self._grad_views.append(p.grad)
                 p._lmv_flat_grad = True                               # _BlockFn.backward accumulates into p.grad in place
-                if not no_decay(name, p):
+                if not table and not no_decay(name, p):
                     self._wd_mask[off:off + n] = 1.0
                 if matrix:
                     p._lmv_shadow = self._shadow[off:off + n].view(p.shape)
@@ -144,15 +205,87 @@ class FlatAdamW:
                 p._lmv_shadow_t = wt
                 self._tpairs.append((p._lmv_shadow, wt))
         self.refresh()
-        rest_decay = [p for n, p in model.named_parameters() if p.requires_grad and id(p) not in seen and not no_decay(n, p)]
-        rest_plain = [p for n, p in model.named_parameters() if p.requires_grad and id(p) not in seen and no_decay(n, p)]
-        groups = [g for g in (dict(params=rest_decay, weight_decay=weight_decay), dict(params=rest_plain, weight_decay=0.0)) if g["params"]]
-        self._rest = torch.optim.AdamW(groups, lr=lr, betas=betas, eps=eps, fused=True, capturable=capturable) if groups else None
-        # 'params' lists the flat-managed parameters so that code walking param_groups (GradScaler.unscale_, timm's clipping,
-        # schedulers) sees every parameter; their .grad tensors are views of the flat gradient buffer
-        self.param_groups = [dict(params=[p for _, p, _, _ in self._slices], lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
-                                  name="lemevit_blocks_flat")] + (self._rest.param_groups if self._rest else [])
+        rest_decay = [(n, p) for n, p in model.named_parameters() if p.requires_grad and id(p) not in seen and not no_decay(n, p)]
+        rest_plain = [(n, p) for n, p in model.named_parameters() if p.requires_grad and id(p) not in seen and no_decay(n, p)]
+        self._group_of_unit: Optional[Tensor] = None          # table mode only: uint8, one group index per _ALIGN elements of the flat buffers
+        self._hyper: Optional[Tensor] = None                  # table mode only: float32 [G, 2] on the device, (lr, weight_decay) of every flat group
+        if table:
+            self._init_table(model, lr, betas, eps, weight_decay, no_decay, layer_decay, lr_scale, rest_decay + rest_plain, total, dev, capturable)
+        else:
+            groups = [g for g in (dict(params=[p for _, p in rest_decay], weight_decay=weight_decay), dict(params=[p for _, p in rest_plain], weight_decay=0.0))
+                      if g["params"]]
+            self._rest = torch.optim.AdamW(groups, lr=lr, betas=betas, eps=eps, fused=True, capturable=capturable) if groups else None
+            # 'params' lists the flat-managed parameters so that code walking param_groups (GradScaler.unscale_, timm's clipping,
+            # schedulers) sees every parameter; their .grad tensors are views of the flat gradient buffer
+            self.param_groups = [dict(params=[p for _, p, _, _ in self._slices], lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
+                                      name="lemevit_blocks_flat")] + (self._rest.param_groups if self._rest else [])
         self._hook = model.register_load_state_dict_post_hook(lambda *_: self.refresh())
+
+    # ---- table mode: per-group and scheduled rates ------------------------------------------------------------------
+    def _init_table(self, model, lr, betas, eps, weight_decay, no_decay, layer_decay, lr_scale, rest_named, total, dev, capturable) -> None:
+        if layer_decay is not None:
+            from .model import LeMeBlock
+            ids = layer_ids(model)
+            top = sum(isinstance(mod, LeMeBlock) for mod in model.modules()) + 1
+            label = {n: f"layer_{i}" for n, i in ids.items()}
+            scale_of = lambda n, p: float(layer_decay) ** (top - ids[n])          # noqa: E731
+        else:
+            label = {}
+            scale_of = (lambda n, p: 1.0) if lr_scale is None else (lambda n, p: float(lr_scale(n, p)))          # noqa: E731
+
+        def collect(named, prefix):
+            """parameters with the same (scale, decays or not) -> one user-facing group, in order of first appearance; returns (groups, group index per parameter)"""
+            keys, out, index = {}, [], []
+            for n, p in named:
+                sc = scale_of(n, p)
+                if not (math.isfinite(sc) and sc >= 0.0):
+                    raise ValueError(f"FlatAdamW: the learning-rate scale of {n!r} is {sc!r}; scales must be finite and >= 0")
+                decays = not no_decay(n, p)
+                k = (sc, decays)
+                if k not in keys:
+                    keys[k] = len(out)
+                    out.append(dict(params=[], lr=lr * sc, lr_scale=sc, betas=betas, eps=eps, weight_decay=weight_decay if decays else 0.0,
+                                    name=f"{prefix}.{label.get(n, f'scale_{sc:g}')}_{'decay' if decays else 'no_decay'}"))
+                out[keys[k]]["params"].append(p)
+                index.append(keys[k])
+            return out, index
+        self._flat_groups, of_slice = collect([(n, p) for n, p, _, _ in self._slices], "blocks")
+        if len(self._flat_groups) > ops.ADAMW_MAX_GROUPS:
+            raise ValueError(f"FlatAdamW: {len(self._flat_groups)} distinct (lr_scale, decay) groups of block parameters; the device table holds {ops.ADAMW_MAX_GROUPS}")
+        units = torch.zeros(total // _ALIGN, dtype=torch.uint8)
+        for (_, _, off, n), gi in zip(self._slices, of_slice):
+            units[off // _ALIGN:(off + n + _ALIGN - 1) // _ALIGN] = gi          # every slice starts on a unit boundary; its padding takes its group
+        self._rest_groups, _ = collect(rest_named, "rest")
+        nf, nr = len(self._flat_groups), len(self._rest_groups)
+        self._group_of_unit = units.to(dev)
+        self._hyper_dev = torch.zeros(2 * nf + nr, device=dev)          # ONE upload: the flat table, then the rate of every remaining group
+        self._hyper = self._hyper_dev[:2 * nf].view(nf, 2)
+        self._rest_lr = [self._hyper_dev[2 * nf + j] for j in range(nr)]          # 0-dim float32 device views: what a CAPTURED torch step reads
+        self._hyper_host: Optional[Tuple[float, ...]] = None                  # what the device holds
+        # the internal torch optimizer: its groups mirror self._rest_groups; step() hands them the host rate (eager) or the device rate (capture)
+        self._rest = torch.optim.AdamW([dict(params=g["params"], weight_decay=g["weight_decay"], lr=g["lr"]) for g in self._rest_groups], lr=lr,
+                                       betas=betas, eps=eps, fused=True, capturable=capturable) if nr else None
+        self.param_groups = self._flat_groups + self._rest_groups
+        self.sync_hyper()
+
+    def _hyper_values(self) -> Tuple[float, ...]:
+        vals: List[float] = []
+        for g in self._flat_groups:
+            vals += [float(g["lr"]), float(g["weight_decay"])]
+        return tuple(vals + [float(g["lr"]) for g in self._rest_groups])
+
+    def sync_hyper(self) -> None:
+        """Table mode: upload the (lr, weight_decay) of every flat group and the lr of every remaining group -- if a host value changed since the last upload;
+        otherwise nothing is launched or copied.  Stream-ordered on the current stream, from a fresh host tensor (a replay still in flight keeps reading what
+        it was given).  ``step()`` calls it; under capture it does nothing (a captured step reads the device values): call it ahead of every replay,
+        ``GraphedStep(step, before_replay=opt.sync_hyper)``.  Without table mode there is nothing to upload."""
+        if self._hyper is None or torch.cuda.is_current_stream_capturing():
+            return
+        vals = self._hyper_values()
+        if vals == self._hyper_host:
+            return
+        self._hyper_dev.copy_(torch.tensor(vals, dtype=torch.float32), non_blocking=True)
+        self._hyper_host = vals
 
     # ---- the optimizer interface ---------------------------------------------------------------------------------
     def _rebind(self, keep: bool) -> list:
@@ -188,6 +321,11 @@ class FlatAdamW:
     def _apply(self, s: int, e: int, stat: Optional[Tensor] = None, clip_value: float = 0.0) -> None:
         g0 = self.param_groups[0]          # schedulers / users may edit any of these (as for torch.optim.AdamW)
         b1, b2 = g0["betas"]
+        if self._hyper is not None:        # table mode: lr and weight_decay come from the device table (betas / eps stay global: the first group's)
+            ops.adamw_flat_groups(self._flat_p[s:e], self._flat_g[s:e], self._exp_avg[s:e], self._exp_avg_sq[s:e], self._group_of_unit[s // _ALIGN:e // _ALIGN],
+                                  self._hyper, float(b1), float(b2), float(g0["eps"]), 0, shadow=self._shadow[s:e], step_dev=self._step_dev, stat=stat,
+                                  clip_value=clip_value)
+            return
         wd = self._wd_mask[s:e]
         ops.adamw_flat(self._flat_p[s:e], self._flat_g[s:e], self._exp_avg[s:e], self._exp_avg_sq[s:e], wd, float(g0["lr"]),
                        float(b1), float(b2), float(g0["eps"]), float(g0["weight_decay"]), 0, shadow=self._shadow[s:e], step_dev=self._step_dev,
@@ -235,6 +373,16 @@ class FlatAdamW:
         from . import blocks as _blocks
         _blocks.drain_deferred()           # backstop: the weight-gradient side stream must have been joined before the update reads the gradients
         self._rebind(keep=True)
+        if self._hyper is not None:
+            self.sync_hyper()
+            if self._rest is not None:
+                # an eager step hands torch the host rate, exactly as the optimizer without table mode does (torch's fused update computes with the double it is
+                # given); a captured step hands it the device scalar sync_hyper() keeps current -- the same rate rounded to float32
+                capturing = torch.cuda.is_current_stream_capturing()
+                for ig, ug, dev_lr in zip(self._rest.param_groups, self._rest_groups, self._rest_lr):
+                    ig["lr"] = dev_lr if capturing else float(ug["lr"])
+                    if not capturing:
+                        ig["weight_decay"], ig["betas"], ig["eps"] = float(ug["weight_decay"]), tuple(ug["betas"]), float(ug["eps"])
         by_norm = self.clip_grad is not None and self.clip_mode == "norm"
         reduce = self._armed or by_norm or self.skip_nonfinite or self.track_grad_norm          # the update reads self._stat
         value = self.clip_grad if self.clip_grad is not None and self.clip_mode == "value" else 0.0
@@ -268,23 +416,53 @@ class FlatAdamW:
         self._shadow.copy_(self._flat_p)
         ops.transpose_batch(self._tpairs)
 
+    def _base_lr(self) -> float:
+        g = next((g for g in self.param_groups if g.get("lr_scale", 1.0) > 0), self.param_groups[0])
+        return float(g["lr"]) / float(g.get("lr_scale", 1.0) or 1.0)
+
     def state_dict(self) -> Dict[str, object]:
-        return dict(step=int(self._step_dev.item()), exp_avg=self._exp_avg.clone(), exp_avg_sq=self._exp_avg_sq.clone(),
-                    names=[(n, off, k) for n, _, off, k in self._slices], lr=self.param_groups[0]["lr"], betas=tuple(self.param_groups[0]["betas"]),
-                    eps=self.param_groups[0]["eps"], weight_decay=self.param_groups[0]["weight_decay"],
-                    rest=None if self._rest is None else self._rest.state_dict())
+        g0 = self.param_groups[0]
+        sd = dict(step=int(self._step_dev.item()), exp_avg=self._exp_avg.clone(), exp_avg_sq=self._exp_avg_sq.clone(),
+                  names=[(n, off, k) for n, _, off, k in self._slices], lr=g0["lr"], betas=tuple(g0["betas"]), eps=g0["eps"], weight_decay=g0["weight_decay"],
+                  rest=None if self._rest is None else self._rest.state_dict())
+        if self._hyper is not None:
+            # the scalar form, what an optimizer without the table would read: the base rate and the decay of the groups that decay
+            sd["lr"], sd["weight_decay"] = self._base_lr(), next((g["weight_decay"] for g in self.param_groups if g["weight_decay"] != 0.0), 0.0)
+            sd["groups"] = [dict(name=g["name"], lr=float(g["lr"]), lr_scale=float(g["lr_scale"]), weight_decay=float(g["weight_decay"])) for g in self.param_groups]
+            if sd["rest"] is not None:
+                for pg, ug in zip(sd["rest"]["param_groups"], self._rest_groups):
+                    pg["lr"] = float(ug["lr"])          # never the device view
+        return sd
 
     def load_state_dict(self, sd: Dict[str, object]) -> None:
         if [(n, off, k) for n, _, off, k in self._slices] != list(sd["names"]):
             raise ValueError("FlatAdamW.load_state_dict: parameter layout differs")
         self._step_dev.fill_(int(sd["step"]))
         self._exp_avg.copy_(sd["exp_avg"]); self._exp_avg_sq.copy_(sd["exp_avg_sq"])
-        self.param_groups[0]["lr"] = sd["lr"]
-        for k in ("betas", "eps", "weight_decay"):
-            if k in sd:
-                self.param_groups[0][k] = sd[k]
         if self._rest is not None and sd.get("rest") is not None:
             self._rest.load_state_dict(sd["rest"])
+        if self._hyper is None:
+            self.param_groups[0]["lr"] = sd["lr"]
+            for k in ("betas", "eps", "weight_decay"):
+                if k in sd:
+                    self.param_groups[0][k] = sd[k]
+            return
+        saved = sd.get("groups")
+        same = saved is not None and [(g["name"], float(g["lr_scale"])) for g in saved] == [(g["name"], float(g["lr_scale"])) for g in self.param_groups]
+        if saved is not None and not same:
+            import warnings
+            warnings.warn("FlatAdamW.load_state_dict: the saved learning-rate groups differ from this optimizer's; taking the saved base rate with this optimizer's scales")
+        for i, g in enumerate(self.param_groups):
+            if same:
+                g["lr"], g["weight_decay"] = float(saved[i]["lr"]), float(saved[i]["weight_decay"])
+            else:                          # a dict written without the group list (or with another grouping): its scalar rate and decay, this optimizer's scales
+                g["lr"] = float(sd["lr"]) * g["lr_scale"]
+                if "weight_decay" in sd and g["weight_decay"] != 0.0:
+                    g["weight_decay"] = float(sd["weight_decay"])
+            for k in ("betas", "eps"):
+                if k in sd:
+                    g[k] = sd[k]
+        self.sync_hyper()
 
 
 class ModelEma:
