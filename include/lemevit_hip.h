@@ -33,7 +33,7 @@ extern "C" {
 
 #define LMV_ABI_VERSION 14
 
-enum { LMV_F32 = 0, LMV_BF16 = 1 };
+enum { LMV_F32 = 0, LMV_BF16 = 1, LMV_U8 = 2 /* images handed to lmv_mix_images only */ };
 enum {
   LMV_OK = 0,
   LMV_ERR_SHAPE = -1,      /* bad shape / alignment */
@@ -450,6 +450,46 @@ int lmv_adamw_flat_groups(float* param, const float* grad, float* exp_avg, float
 /* Exponential moving average of the weights over the same flat buffer (timm.utils.ModelEmaV2: main.py:316, engine.py model_ema.update(model)):
  * ema[i] = decay * ema[i] + (1 - decay) * param[i], n % 4 == 0, one launch (lemevit_amd.optim.ModelEma). */
 int lmv_ema_flat(float* ema, const float* param, int64_t n, float decay, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * The two ends of the reference's training step (csrc/recipe.hip): batch mixing in front of the forward pass and the loss behind it.
+ *
+ * lmv_mix_record: one per image, in DEVICE memory -- the running kernels read it, so a captured hipGraph mixes (and weighs its targets) with whatever the
+ * table holds at replay time.  A pixel inside [yl, yh) x [xl, xh) takes the partner's value; elsewhere out = w * self + (1 - w) * partner.  Mixup: empty box,
+ * w = lam.  Cutmix: w = 1 and a box.  No mixing: w = 1, empty box.  lam_t is the weight of the image's OWN label in its target (mixup: lam; cutmix: the
+ * corrected 1 - area / (H W)); lmv_soft_ce reads nothing else of a record.
+ *
+ * lmv_mix_images (timm.data.Mixup._mix_batch / _mix_elem / _mix_pair on the images: main.py:375-389, engine.py:61-62; with scale / shift also the
+ * PrefetchLoader normalisation): x [B, C, H, W], LMV_U8 / LMV_F32 / LMV_BF16, ELEMENT strides sb, sc, sh, sw (any: NCHW, channels-last, a sliced view) ->
+ * out, contiguous NCHW, LMV_F32 / LMV_BF16, in ONE launch.  Image b is mixed with image B - 1 - b (x.flip(0)); an odd B pairs the middle image with
+ * itself.  One workgroup serves both images of a pair: every input element is loaded once, every output element stored once (no atomics: bit-identical
+ * from run to run); 16-byte stores where C H W is a multiple of the 16-byte element count and `out` is 16-byte aligned (with element stores for the head
+ * and tail of a row), loads as wide as the addresses allow when sw == 1.  x is not modified and must not overlap out.
+ * scale / shift (nullable, together; fp32 [C], device): out = mixed * scale[c] + shift[c] in fp32.  Without them, with equal dtypes, a pixel that takes
+ * one image as it is (inside the box, or w == 1) is a bit-exact copy.
+ * host_records (nullable): a HOST copy of the table, validated before the launch.  Refused with LMV_ERR_SHAPE and a message, before any launch: a null
+ * image buffer or table, B / C / H / W < 1, a dtype pair other than the above, scale without shift, a misaligned buffer, and -- given host_records -- a
+ * box outside the image, yl > yh, xl > xh, a NaN factor.  (A box outside the image in the DEVICE table cannot cause an access outside the buffers: the
+ * box is only ever compared with pixel coordinates.)
+ *
+ * lmv_soft_ce (timm.loss.SoftTargetCrossEntropy / LabelSmoothingCrossEntropy, F.cross_entropy: main.py:456-466; the target of timm.data.mixup.mixup_target
+ * without building it): logits [B, N] fp32 / bf16, row stride `row_stride` elements (>= N: the [:, :N] view of padded logits is legal), any N >= 1.
+ *   sparse form (labels != NULL, target == NULL): labels int64 [B]; t = lam_t oh(labels[b]) + (1 - lam_t) oh(labels[B - 1 - b]), oh = 1 - s + s / N on
+ *     the label and s / N elsewhere, s = smoothing in [0, 1); table == NULL: lam_t = 1 (plain / label-smoothed cross-entropy; the partner is not read).
+ *     A label outside [0, N) carries no one-hot mass and is never used as an index.  Labels are NOT validated (that would need a host synchronisation).
+ *   dense form (target != NULL, labels == NULL): target [B, N] fp32 / bf16 (target_dtype), row stride target_stride.
+ *   row_loss[b] = -sum_j t_j log softmax(x)_j (fp32 [B], always written); *mean_loss = (sum_b row_loss[b]) / B (fp32 device scalar);
+ *   dlogits (nullable: loss only; else contiguous [B, N] in the logits dtype) = d mean_loss / d logits = (p_j sum(t) - t_j) / B, sum(t) = 1 for a proper target.
+ * Two launches: one wave per row (max, log-sum-exp and sums in fp32, three sweeps over the cached row), then ONE wave that adds the B row losses in a
+ * fixed order -- no floating-point atomics, two calls agree bit for bit.  Refused with LMV_ERR_SHAPE before any launch: B < 1, N < 1, a dtype code other
+ * than LMV_F32 / LMV_BF16, null logits / row_loss / mean_loss, both or neither of labels and target, a table with the dense form, row strides < N,
+ * smoothing outside [0, 1), a misaligned buffer.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct lmv_mix_record { float w; int32_t yl, yh, xl, xh; float lam_t; } lmv_mix_record;
+int lmv_mix_images(const void* x, int x_dtype, int64_t sb, int64_t sc, int64_t sh, int64_t sw, void* out, int out_dtype, int B, int C, int H, int W,
+                   const lmv_mix_record* table, const lmv_mix_record* host_records, const float* scale, const float* shift, void* stream);
+int lmv_soft_ce(const void* logits, int dtype, int64_t row_stride, int B, int N, const int64_t* labels, const lmv_mix_record* table, float smoothing,
+                const void* target, int target_dtype, int64_t target_stride, float* row_loss, float* mean_loss, void* dlogits, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Whole-block schedules: ONE call enqueues every launch of a LeMeBlock (models/lemevit.py:500-660) on token-major tensors

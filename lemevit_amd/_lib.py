@@ -15,7 +15,7 @@ import torch  # noqa: F401  -- FIRST: PyTorch-ROCm ships its own HIP runtime; th
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LMV_LIB_PATH") or os.path.join(_HERE, "csrc", "liblemevit_hip.so")          # LMV_LIB_PATH: another build of the same library (A/B runs of kernel variants inside one gpurun call)
 
-LMV_F32, LMV_BF16 = 0, 1
+LMV_F32, LMV_BF16, LMV_U8 = 0, 1, 2          # LMV_U8: images handed to lmv_mix_images only
 ACT_NONE, ACT_GELU, ACT_GELU_GRAD, ACT_GELU_BWD = 0, 1, 2, 3
 FOLD_CI_TAP, FOLD_TAP_CI = 0, 1
 ABI_VERSION = 14
@@ -102,6 +102,10 @@ class AdamWGroup(C.Structure):
     _fields_ = [("lr", C.c_float), ("weight_decay", C.c_float)]
 
 
+class MixRecord(C.Structure):
+    _fields_ = [("w", C.c_float), ("yl", C.c_int32), ("yh", C.c_int32), ("xl", C.c_int32), ("xh", C.c_int32), ("lam_t", C.c_float)]
+
+
 _P, _I, _L, _F, _Z = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_size_t
 
 # name -> (restype, argtypes); the complete export list of include/lemevit_hip.h
@@ -179,6 +183,8 @@ SIGNATURES = {
     "lmv_adamw_flat_clip": (_I, [_P, _P, _P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _I, _P, _P, _F, _P]),
     "lmv_adamw_flat_groups": (_I, [_P, _P, _P, _P, _P, _L, _P, _P, _I, _F, _F, _F, _I, _P, _P, _F, _P]),
     "lmv_ema_flat": (_I, [_P, _P, _L, _F, _P]),
+    "lmv_mix_images": (_I, [_P, _I, _L, _L, _L, _L, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "lmv_soft_ce": (_I, [_P, _I, _L, _I, _I, _P, _P, _F, _P, _I, _L, _P, _P, _P, _P]),
     "lmv_block_arena_bytes": (_Z, [C.POINTER(BlockDesc)]),
     "lmv_block_bwd_scratch_bytes": (_Z, [C.POINTER(BlockDesc)]),
     "lmv_block_fwd": (_I, [C.POINTER(BlockDesc), _P, _P, _P, _P, _P, _Z, _I, _P]),

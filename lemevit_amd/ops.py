@@ -782,6 +782,100 @@ def ema_flat(ema: Tensor, param: Tensor, decay: float) -> None:
 
 
 # -------------------------------------------------------------------------------------------
+# mixup / cutmix and the soft-target loss (csrc/recipe.hip; lemevit_amd.recipe holds the user-facing classes)
+# -------------------------------------------------------------------------------------------
+MIX_RECORD_WORDS = C.sizeof(_lib.MixRecord) // 4          # a table is an int32 tensor [B, 6]: w, yl, yh, xl, xh, lam_t (the two floats as their bits)
+
+
+def _mix_table(table: Tensor, B: int, fn: str) -> int:
+    if table.dtype != torch.int32 or table.dim() != 2 or tuple(table.shape) != (B, MIX_RECORD_WORDS):
+        raise TypeError(f"{fn}: table must be an int32 tensor [{B}, {MIX_RECORD_WORDS}] (lemevit_amd.recipe.pack_records), got {tuple(table.shape)} {table.dtype}")
+    return _ptr(table)
+
+
+def mix_images(x: Tensor, table: Tensor, out_dtype: Optional[torch.dtype] = None, scale: Optional[Tensor] = None, shift: Optional[Tensor] = None,
+               records: Optional[Tensor] = None) -> Tensor:
+    """One launch of lmv_mix_images: images ``x`` [B, C, H, W] (uint8, float32 or bfloat16; any strides -- nothing is copied) mixed with ``x.flip(0)`` under
+    the per-image records of the DEVICE ``table`` (int32 [B, 6], ``recipe.pack_records``) -> a new contiguous NCHW tensor of ``out_dtype`` (float32 /
+    bfloat16; default: the input's, float32 for uint8).  ``scale`` / ``shift`` (float32 [C], together): ``out = mixed * scale[c] + shift[c]``.  ``x`` is not
+    modified.  ``records``: a host copy of the table (int32 [B, 6] on the CPU) -- given, the boxes are validated against the image before the launch."""
+    if x.dim() != 4:
+        raise ValueError(f"mix_images: [B, C, H, W] images expected, got {tuple(x.shape)}")
+    if not x.is_cuda:
+        raise RuntimeError("lemevit_amd: tensors must be on the GPU (no CPU fallback exists)")
+    codes = {torch.float32: _lib.LMV_F32, torch.bfloat16: _lib.LMV_BF16, torch.uint8: _lib.LMV_U8}
+    if x.dtype not in codes:
+        raise TypeError(f"mix_images: unsupported image dtype {x.dtype} (uint8, float32 and bfloat16 only)")
+    if out_dtype is None:
+        out_dtype = torch.float32 if x.dtype == torch.uint8 else x.dtype
+    if out_dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"mix_images: unsupported output dtype {out_dtype} (float32 and bfloat16 only)")
+    B, C_, H, W = x.shape
+    if (scale is None) != (shift is None):
+        raise ValueError("mix_images: scale and shift come together")
+    if scale is not None and (scale.numel() != C_ or shift.numel() != C_):
+        raise ValueError(f"mix_images: scale and shift must have one element per channel ({C_})")
+    tp = _mix_table(table, B, "mix_images")
+    hp = None
+    if records is not None:
+        if records.is_cuda or not records.is_contiguous() or records.dtype != torch.int32 or tuple(records.shape) != (B, MIX_RECORD_WORDS):
+            raise TypeError(f"mix_images: records must be a contiguous int32 CPU tensor [{B}, {MIX_RECORD_WORDS}]")
+        hp = records.data_ptr()
+    out = torch.empty((B, C_, H, W), device=x.device, dtype=out_dtype)
+    sb, sc, sh, sw = x.stride()
+    check(lib.lmv_mix_images(x.data_ptr(), codes[x.dtype], sb, sc, sh, sw, _ptr(out), codes[out_dtype], B, C_, H, W, tp, hp, _f32(scale), _f32(shift), _stream()),
+          "lmv_mix_images")
+    return out
+
+
+def soft_ce(logits: Tensor, labels: Optional[Tensor] = None, table: Optional[Tensor] = None, smoothing: float = 0.0, target: Optional[Tensor] = None,
+            want_grad: bool = True) -> Tuple[Tensor, Tensor, Optional[Tensor]]:
+    """lmv_soft_ce: cross-entropy of ``logits`` [B, N] (float32 / bfloat16; unit column stride, ANY row stride: a ``[:, :N]`` view of padded logits is read in
+    place) against soft targets, and its logit gradient, in one pass.  Returns ``(loss, row_loss, dlogits)``: the batch mean (0-dim float32), the per-row
+    losses (float32 [B]) and ``d loss / d logits`` (contiguous [B, N] in the logits dtype; None with ``want_grad=False``).
+
+    * sparse form: ``labels`` int64 [B], optional ``table`` (the mixing table: row b's target is ``lam_t`` of its own label and ``1 - lam_t`` of
+      ``labels[B - 1 - b]``; None: its own label only) and ``smoothing`` -- timm's ``mixup_target``, never materialised;
+    * dense form: ``target`` [B, N], float32 / bfloat16.
+
+    Labels are NOT checked (that would synchronise the host): a label outside ``[0, N)`` contributes no one-hot mass.  Deterministic: no atomics."""
+    if logits.dim() != 2:
+        raise ValueError(f"soft_ce: [B, N] logits expected, got {tuple(logits.shape)}")
+    if not logits.is_cuda:
+        raise RuntimeError("lemevit_amd: tensors must be on the GPU (no CPU fallback exists)")
+    code = dtype_code(logits)
+    B, N = logits.shape
+    if N > 1 and logits.stride(1) != 1:
+        raise ValueError("soft_ce: the logits must have unit stride along the classes")
+    ls = logits.stride(0) if B > 1 else N
+    if ls < N:
+        raise ValueError("soft_ce: overlapping logit rows")
+    if (labels is None) == (target is None):
+        raise ValueError("soft_ce: exactly one of labels (sparse form) and target (dense form) must be given")
+    lp = tp = gp = None
+    tcode, ts = 0, 0
+    if labels is not None:
+        if labels.dtype != torch.int64 or tuple(labels.shape) != (B,):
+            raise TypeError(f"soft_ce: labels must be an int64 tensor [{B}], got {tuple(labels.shape)} {labels.dtype}")
+        if not 0.0 <= float(smoothing) < 1.0:
+            raise ValueError("soft_ce: smoothing must be in [0, 1)")
+        lp = _ptr(labels)
+        if table is not None:
+            tp = _mix_table(table, B, "soft_ce")
+    else:
+        if table is not None:
+            raise ValueError("soft_ce: the table belongs to the sparse form")
+        if tuple(target.shape) != (B, N) or (N > 1 and target.stride(1) != 1) or not target.is_cuda:
+            raise ValueError(f"soft_ce: target must be a [{B}, {N}] GPU tensor with unit stride along the classes")
+        tcode, ts, gp = dtype_code(target), (target.stride(0) if B > 1 else N), target.data_ptr()
+    row = torch.empty((B,), device=logits.device, dtype=torch.float32)
+    loss = torch.empty((), device=logits.device, dtype=torch.float32)
+    dlog = torch.empty((B, N), device=logits.device, dtype=logits.dtype) if want_grad else None
+    check(lib.lmv_soft_ce(logits.data_ptr(), code, ls, B, N, lp, tp, float(smoothing), gp, tcode, ts, _ptr(row), _ptr(loss), _ptr(dlog), _stream()), "lmv_soft_ce")
+    return loss, row, dlog
+
+
+# -------------------------------------------------------------------------------------------
 # A run of "S" blocks as one persistent launch (csrc/sstage.hip; inference, bf16)
 # -------------------------------------------------------------------------------------------
 def sstage_supported(C_: int, heads: int, hidden: int, H: int, W: int, M: int, dtype: torch.dtype) -> bool:
