@@ -492,6 +492,47 @@ int lmv_soft_ce(const void* logits, int dtype, int64_t row_stride, int B, int N,
                 const void* target, int target_dtype, int64_t target_stride, float* row_loss, float* mean_loss, void* dlogits, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Random erasing fused into the batch-mixing launch (csrc/recipe.hip; timm.data.random_erasing.RandomErasing as timm's PrefetchLoader runs it behind the
+ * normalisation: configs/lemevit.yaml:74-76 reprob 0.25, remode pixel, recount 1; main.py:406-409).  An addition to ABI 14: callers detect it by symbol.
+ *
+ * lmv_erase_record: one per image, in DEVICE memory: up to LMV_ERASE_MAX_BOXES boxes box[i] = {yl, yh, xl, xh}, i.e. [yl, yh) x [xl, xh); 16 int32 words.  An
+ * empty box (yl >= yh or xl >= xh, e.g. all zero) erases nothing.  The boxes are only ever compared with pixel coordinates: a bad box in the DEVICE table
+ * cannot cause an access outside the buffers.  The noise key is two 32-bit words in DEVICE memory.  The running kernel reads table and key, so a captured
+ * hipGraph erases with whatever they hold at replay time.
+ *
+ * lmv_augment_images: x, the strides, out, B, C, H, W, the dtypes, host_records, scale / shift and stream as in lmv_mix_images.  Per pixel: mix under
+ * mix_table (NULL: every image stays as it is), then * scale[c] + shift[c], then erase: a pixel (y, x) of image b inside any box of erase_table[b] is the
+ * FILL VALUE instead (rounded to the output dtype; what the mix would have given there is not used), so the boxes of image b apply to OUTPUT image b, after
+ * the mixing -- collate-time mixup, normalise, erase: the reference's order.  erase_table == NULL: the output equals lmv_mix_images' bit for bit; both tables
+ * NULL: the plain PrefetchLoader normalise-and-cast.  One launch, the kernel of lmv_mix_images with the fill behind it: every input element loaded once, every
+ * output element stored once, 16-byte stores where the phase allows, no atomics, no workspace; two launches with one key agree bit for bit.
+ *
+ * Fill values, erase_mode (timm's `mode`):
+ *   LMV_ERASE_CONST  0.
+ *   LMV_ERASE_PIXEL  one standard normal per element, a pure function of (key, b, c, y, x) -- not of the layout of x, the alignment of out or the path the
+ *                    kernel takes.  (r0, r1, r2, r3) = Philox4x32-10 (Salmon et al., SC'11; Random123 philox4x32_R(10, ctr, key)) with the counter words
+ *                    ctr = (x >> 2, y, c, b) and the key words (erase_key[0], erase_key[1]): ten rounds of
+ *                      (c0, c1, c2, c3) <- (hi(M1 c2) ^ c1 ^ k0, lo(M1 c2), hi(M0 c0) ^ c3 ^ k1, lo(M0 c0)),  M0 = 0xD2511F53, M1 = 0xCD9E8D57,
+ *                    hi / lo the halves of the 64-bit product, with (k0, k1) += (0x9E3779B9, 0xBB67AE85) (mod 2^32) between rounds; known answer:
+ *                    ctr = 0, key = 0 -> 6627e8d5 e169c58d bc57ac4c 9b00dbd8.  Two Box-Muller pairs: from words (ra, rb) = (r0, r1) the lanes x & 3 = 0, 1 and
+ *                    from (r2, r3) the lanes 2, 3: u1 = ((ra >> 9) + 1) 2^-23 in (0, 1], u2 = (rb >> 8) 2^-24 in [0, 1) (both exact in fp32),
+ *                    rad = sqrt(-2 ln u1), the even lane rad cos(2 pi u2), the odd lane rad sin(2 pi u2); |value| <= sqrt(46 ln 2) = 5.6467.  Evaluated in
+ *                    fp32 with the accurate logarithm and sincospi(2 u2): within 1e-5 of the exact value.  Overlapping boxes write the same noise.
+ *   LMV_ERASE_RAND   one normal per (box i, channel c): lane 0 of the counter (i, 0xffffffff, c, b).  Where boxes overlap, the box of the highest index wins.
+ * Noise is generated only by threads whose chunk meets a box: a launch with an all-empty table runs no Philox round.
+ *
+ * host_erase_records (nullable): a HOST copy of erase_table, validated before the launch.  Refused with LMV_ERR_SHAPE and a message, before any launch:
+ * everything lmv_mix_images refuses (except a null mix_table), an unknown erase_mode, an erase_table without erase_key in the RAND / PIXEL mode, a
+ * misaligned table or key, and -- given host_erase_records -- a box outside the image or with yl > yh, xl > xh.
+ * ------------------------------------------------------------------------------------------ */
+#define LMV_ERASE_MAX_BOXES 4
+enum { LMV_ERASE_CONST = 0, LMV_ERASE_RAND = 1, LMV_ERASE_PIXEL = 2 };
+typedef struct lmv_erase_record { int32_t box[LMV_ERASE_MAX_BOXES][4]; } lmv_erase_record;
+int lmv_augment_images(const void* x, int x_dtype, int64_t sb, int64_t sc, int64_t sh, int64_t sw, void* out, int out_dtype, int B, int C, int H, int W,
+                       const lmv_mix_record* mix_table, const lmv_mix_record* host_records, const lmv_erase_record* erase_table, const uint32_t* erase_key,
+                       int erase_mode, const lmv_erase_record* host_erase_records, const float* scale, const float* shift, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Whole-block schedules: ONE call enqueues every launch of a LeMeBlock (models/lemevit.py:500-660) on token-major tensors
  * x [B, H*W, C], c [B, M, C] -- `LeMeBlock.forward_with_x` ("S", :615-650), `forward_with_xc` ("D", :542-582), `forward_with_c`
  * ("C", :584-613; x is returned untouched by the caller, x_out / dx_out may be NULL).  Replaces the ~12 / ~30 per-op calls a Python

@@ -22,6 +22,8 @@ ABI_VERSION = 14
 BLOCK_NO_JOIN, BLOCK_FUSED, BLOCK_DATA_ONLY = 1, 2, 4          # lmv_block_desc.flags
 GRAD_STAT_FLOATS, NORM_CHUNK, NORM_SKIP_NONFINITE = 8, 16384, 1          # LMV_GRAD_STAT_FLOATS, LMV_NORM_CHUNK, LMV_NORM_SKIP_NONFINITE
 ADAMW_UNIT, ADAMW_MAX_GROUPS = 8, 256          # LMV_ADAMW_UNIT, LMV_ADAMW_MAX_GROUPS
+ERASE_MAX_BOXES = 4          # LMV_ERASE_MAX_BOXES
+ERASE_CONST, ERASE_RAND, ERASE_PIXEL = 0, 1, 2          # lmv_augment_images: erase_mode
 
 
 class LinearProblem(C.Structure):
@@ -106,6 +108,10 @@ class MixRecord(C.Structure):
     _fields_ = [("w", C.c_float), ("yl", C.c_int32), ("yh", C.c_int32), ("xl", C.c_int32), ("xh", C.c_int32), ("lam_t", C.c_float)]
 
 
+class EraseRecord(C.Structure):
+    _fields_ = [("box", (C.c_int32 * 4) * ERASE_MAX_BOXES)]          # box[i] = yl, yh, xl, xh
+
+
 _P, _I, _L, _F, _Z = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_size_t
 
 # name -> (restype, argtypes); the complete export list of include/lemevit_hip.h
@@ -185,6 +191,7 @@ SIGNATURES = {
     "lmv_ema_flat": (_I, [_P, _P, _L, _F, _P]),
     "lmv_mix_images": (_I, [_P, _I, _L, _L, _L, _L, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "lmv_soft_ce": (_I, [_P, _I, _L, _I, _I, _P, _P, _F, _P, _I, _L, _P, _P, _P, _P]),
+    "lmv_augment_images": (_I, [_P, _I, _L, _L, _L, _L, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P]),
     "lmv_block_arena_bytes": (_Z, [C.POINTER(BlockDesc)]),
     "lmv_block_bwd_scratch_bytes": (_Z, [C.POINTER(BlockDesc)]),
     "lmv_block_fwd": (_I, [C.POINTER(BlockDesc), _P, _P, _P, _P, _P, _Z, _I, _P]),

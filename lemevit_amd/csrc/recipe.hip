@@ -2,8 +2,11 @@
 // engine.py:61-62 mixup_fn(input, target)):
 //   lmv_mix_images: mixup / cutmix of a batch with its flipped self in ONE out-of-place launch, the per-image factors and boxes read from a DEVICE table
 //                   (so a captured step mixes with whatever the table holds at replay time), the PrefetchLoader normalisation and the cast fused in;
+//   lmv_augment_images: the same launch with timm's RandomErasing (PrefetchLoader: normalise, then erase) fused in behind the normalisation: per-image boxes from a
+//                   second DEVICE table, the fill noise generated on the chip (Philox4x32-10 keyed by pixel coordinates and a DEVICE key), every output element
+//                   still written once;
 //   lmv_soft_ce   : soft-target / label-smoothed cross-entropy and its logit gradient in one pass over the logits, the mixed target never materialised.
-// Both are bandwidth-trivial; neither uses an atomic, and every output element has exactly one writer: two runs agree bit for bit.
+// All are bandwidth-trivial; none uses an atomic, and every output element has exactly one writer: two runs agree bit for bit.
 #include <math.h>
 #include "common.h"
 
@@ -57,9 +60,92 @@ template <typename TOUT, int V> __device__ __forceinline__ void mix_store(TOUT* 
     if (j < len) DT<TOUT>::st(p + j, f[j]);
 }
 
+// ---- random erasing: the fill values (include/lemevit_hip.h states them; lemevit_amd/recipe.py restates them in float64) -------------------------------
+struct EraseArgs { const lmv_erase_record* table; const uint32_t* key; int mode; };
+
+// Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11; Random123's philox4x32_R(10, ...))
+__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t* r) {
+  constexpr uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
+#pragma unroll
+  for (int i = 0; i < 10; ++i) {
+    const uint32_t h0 = __umulhi(M0, c0), l0 = M0 * c0, h1 = __umulhi(M1, c2), l1 = M1 * c2;
+    c0 = h1 ^ c1 ^ k0; c1 = l1; c2 = h0 ^ c3 ^ k1; c3 = l0;
+    k0 += W0; k1 += W1;
+  }
+  r[0] = c0; r[1] = c1; r[2] = c2; r[3] = c3;
+}
+
+// One Box-Muller pair from two words: u1 = ((ra >> 9) + 1) 2^-23 in (0, 1], u2 = (rb >> 8) 2^-24 in [0, 1) (both exact in fp32); rad = sqrt(-2 ln u1),
+// the pair is rad cos(2 pi u2), rad sin(2 pi u2).  sincospif takes 2 u2 (exact): the angle is never rounded.  Accurate logf: near u1 = 1 the square root
+// amplifies an absolute error of the logarithm.
+__device__ __forceinline__ void erase_pair(uint32_t ra, uint32_t rb, float* zc, float* zs) {
+  const float u1 = (float)((ra >> 9) + 1u) * 0x1p-23f, u2x2 = (float)(rb >> 8) * 0x1p-23f;
+  const float rad = sqrtf(-2.f * logf(u1));
+  float sn, cs;
+  sincospif(u2x2, &sn, &cs);
+  *zc = rad * cs; *zs = rad * sn;
+}
+
+// Overwrites, in o[0 .. len), the elements x0 + j of row (c, y) of image b that lie inside a box of record e with the fill value.  No Philox round runs unless
+// the chunk meets a box.  The noise is a function of (key, b, c, y, x) alone: it does not know where the chunk starts.
+template <int V> __device__ __forceinline__ void erase_chunk(const lmv_erase_record& e, const EraseArgs& g, int b, int c, int y, int x0, int len, float* o) {
+  unsigned inbox[LMV_ERASE_MAX_BOXES], any = 0u;          // bit j: element x0 + j lies in box i
+#pragma unroll
+  for (int i = 0; i < LMV_ERASE_MAX_BOXES; ++i) {
+    const int yl = e.box[i][0], yh = e.box[i][1], xl = e.box[i][2], xh = e.box[i][3];
+    unsigned m = 0u;
+    if (y >= yl && y < yh && x0 < xh && x0 + len > xl) {
+#pragma unroll
+      for (int j = 0; j < V; ++j) m |= (j < len && x0 + j >= xl && x0 + j < xh) ? (1u << j) : 0u;
+    }
+    inbox[i] = m; any |= m;
+  }
+  if (any == 0u) return;
+  if (g.mode == LMV_ERASE_CONST) {
+#pragma unroll
+    for (int j = 0; j < V; ++j) o[j] = ((any >> j) & 1u) ? 0.f : o[j];
+    return;
+  }
+  const uint32_t k0 = g.key[0], k1 = g.key[1];
+  uint32_t r[4];
+  if (g.mode == LMV_ERASE_RAND) {          // one value per (box, channel); the box of the highest index wins where boxes overlap (timm erases them in order)
+#pragma unroll 1
+    for (int i = 0; i < LMV_ERASE_MAX_BOXES; ++i) {
+      const unsigned m = i == 0 ? inbox[0] : i == 1 ? inbox[1] : i == 2 ? inbox[2] : inbox[3];
+      if (m == 0u) continue;
+      philox4x32_10((uint32_t)i, 0xffffffffu, (uint32_t)c, (uint32_t)b, k0, k1, r);
+      float z, unused;
+      erase_pair(r[0], r[1], &z, &unused);
+#pragma unroll
+      for (int j = 0; j < V; ++j) o[j] = ((m >> j) & 1u) ? z : o[j];
+    }
+    return;
+  }
+  // LMV_ERASE_PIXEL: the chunk meets at most V / 4 + 1 groups of four pixels (one Philox counter each)
+  const int g0 = x0 >> 2;
+#pragma unroll 1
+  for (int gi = 0; gi <= V / 4; ++gi) {
+    const int first = 4 * (g0 + gi) - x0;          // the element index of the group's lane 0 (negative: the group starts in front of the chunk)
+    const unsigned gm = first >= 0 ? (any >> first) & 0xfu : (any << -first) & 0xfu;          // bit l: lane l of the group is erased
+    if (gm == 0u) continue;
+    philox4x32_10((uint32_t)(g0 + gi), (uint32_t)y, (uint32_t)c, (uint32_t)b, k0, k1, r);
+    float z0 = 0.f, z1 = 0.f, z2 = 0.f, z3 = 0.f;
+    if (gm & 3u) erase_pair(r[0], r[1], &z0, &z1);
+    if (gm & 12u) erase_pair(r[2], r[3], &z2, &z3);
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+      const int l = j - first;
+      const bool hit = l >= 0 && l < 4 && ((any >> j) & 1u);
+      const float z = l == 0 ? z0 : l == 1 ? z1 : l == 2 ? z2 : z3;
+      o[j] = hit ? z : o[j];
+    }
+  }
+}
+
 // One thread: one chunk of up to V = 16 / sizeof(TOUT) elements of row (c, y) -- of image b = blockIdx.y AND of its partner B - 1 - b, so every input element is
 // loaded once and serves both outputs.  A record's box takes the partner's pixel as it is; elsewhere w * self + (1 - w) * partner, w == 1 being a plain copy.
-template <typename TIN, typename TOUT> __global__ __launch_bounds__(MIX_TPB) void mix_images_kernel(const MixArgs a) {
+// AUG (lmv_augment_images): the mix table may be absent (identity records) and, behind the normalisation, the erase boxes of both images are filled.
+template <typename TIN, typename TOUT, bool AUG> __device__ __forceinline__ void mix_body(const MixArgs& a, const EraseArgs& g) {
   constexpr int V = 16 / sizeof(TOUT);
   const int64_t t = (int64_t)blockIdx.x * MIX_TPB + threadIdx.x;
   const int r = (int)(t / a.K), k = (int)(t - (int64_t)r * a.K);
@@ -72,7 +158,8 @@ template <typename TIN, typename TOUT> __global__ __launch_bounds__(MIX_TPB) voi
   const int x1 = min(k == 0 ? head : x0 + V, a.W);
   const int len = x1 - x0;
   if (len <= 0) return;
-  const lmv_mix_record rs = a.table[b], rp = a.table[pb];
+  lmv_mix_record rs = {1.f, 0, 0, 0, 0, 1.f}, rp = rs;
+  if (!AUG || a.table) { rs = a.table[b]; rp = a.table[pb]; }
   const TIN* xs = reinterpret_cast<const TIN*>(a.x) + b * a.sb + c * a.sc + y * a.sh + x0 * a.sw;
   const TIN* xp = reinterpret_cast<const TIN*>(a.x) + pb * a.sb + c * a.sc + y * a.sh + x0 * a.sw;
   float fs[V], fp[V], os[V], op[V];
@@ -94,6 +181,12 @@ template <typename TIN, typename TOUT> __global__ __launch_bounds__(MIX_TPB) voi
     if (affine) { vs = fmaf(vs, sc, sf); vp = fmaf(vp, sc, sf); }
     os[j] = vs; op[j] = vp;
   }
+  if constexpr (AUG) {
+    if (g.table) {
+      erase_chunk<V>(g.table[b], g, b, c, y, x0, len, os);
+      if (pb != b) erase_chunk<V>(g.table[pb], g, pb, c, y, x0, len, op);
+    }
+  }
   const bool whole = a.vec && k > 0 && len == V;
   const int64_t img = (int64_t)a.C * a.H * a.W;
   TOUT* o = reinterpret_cast<TOUT*>(a.out);
@@ -101,46 +194,90 @@ template <typename TIN, typename TOUT> __global__ __launch_bounds__(MIX_TPB) voi
   if (pb != b) mix_store<TOUT, V>(o + pb * img + row + x0, len, whole, op);
 }
 
+template <typename TIN, typename TOUT> __global__ __launch_bounds__(MIX_TPB) void mix_images_kernel(const MixArgs a) { mix_body<TIN, TOUT, false>(a, EraseArgs{}); }
+template <typename TIN, typename TOUT> __global__ __launch_bounds__(MIX_TPB) void augment_images_kernel(const MixArgs a, const EraseArgs g) { mix_body<TIN, TOUT, true>(a, g); }
+
 template <typename TIN> int mix_launch(const MixArgs& a, int out_dtype, dim3 grid, hipStream_t st) {
   if (out_dtype == LMV_F32) hipLaunchKernelGGL((mix_images_kernel<TIN, float>), grid, dim3(MIX_TPB), 0, st, a);
   else hipLaunchKernelGGL((mix_images_kernel<TIN, bf16_t>), grid, dim3(MIX_TPB), 0, st, a);
   LMV_CHECK_LAUNCH("mix_images");
   return LMV_OK;
 }
-}  // namespace
 
-extern "C" int lmv_mix_images(const void* x, int x_dtype, int64_t sb, int64_t sc, int64_t sh, int64_t sw, void* out, int out_dtype, int B, int C, int H, int W,
-                              const lmv_mix_record* table, const lmv_mix_record* host_records, const float* scale, const float* shift, void* stream) {
-  if (!x || !out) LMV_FAIL(LMV_ERR_SHAPE, "mix_images: null image buffer");
-  if (!table) LMV_FAIL(LMV_ERR_SHAPE, "mix_images: null table (one lmv_mix_record per image, in device memory)");
+template <typename TIN> int augment_launch(const MixArgs& a, const EraseArgs& g, int out_dtype, dim3 grid, hipStream_t st) {
+  if (out_dtype == LMV_F32) hipLaunchKernelGGL((augment_images_kernel<TIN, float>), grid, dim3(MIX_TPB), 0, st, a, g);
+  else hipLaunchKernelGGL((augment_images_kernel<TIN, bf16_t>), grid, dim3(MIX_TPB), 0, st, a, g);
+  LMV_CHECK_LAUNCH("augment_images");
+  return LMV_OK;
+}
+
+// what both entry points refuse, and the launch geometry they share; `fn` names the caller in the message
+int mix_prepare(const char* fn, const void* x, int x_dtype, int64_t sb, int64_t sc, int64_t sh, int64_t sw, void* out, int out_dtype, int B, int C, int H, int W,
+                const lmv_mix_record* table, const lmv_mix_record* host_records, const float* scale, const float* shift, MixArgs* a, dim3* grid) {
+  if (!x || !out) LMV_FAIL(LMV_ERR_SHAPE, "%s: null image buffer", fn);
   if (B < 1 || C < 1 || H < 1 || W < 1 || (int64_t)B * C * H * W > ((int64_t)1 << 40) || (int64_t)C * H * (W / 4 + 3) > ((int64_t)1 << 30))
-    LMV_FAIL(LMV_ERR_SHAPE, "mix_images: bad shape [%d, %d, %d, %d]", B, C, H, W);
+    LMV_FAIL(LMV_ERR_SHAPE, "%s: bad shape [%d, %d, %d, %d]", fn, B, C, H, W);
   if ((x_dtype != LMV_F32 && x_dtype != LMV_BF16 && x_dtype != LMV_U8) || (out_dtype != LMV_F32 && out_dtype != LMV_BF16))
-    LMV_FAIL(LMV_ERR_SHAPE, "mix_images: unsupported dtype pair (input %d -> output %d): uint8 / fp32 / bf16 images, fp32 / bf16 output", x_dtype, out_dtype);
-  if ((scale == nullptr) != (shift == nullptr)) LMV_FAIL(LMV_ERR_SHAPE, "mix_images: scale and shift come together");
+    LMV_FAIL(LMV_ERR_SHAPE, "%s: unsupported dtype pair (input %d -> output %d): uint8 / fp32 / bf16 images, fp32 / bf16 output", fn, x_dtype, out_dtype);
+  if ((scale == nullptr) != (shift == nullptr)) LMV_FAIL(LMV_ERR_SHAPE, "%s: scale and shift come together", fn);
   if ((((uintptr_t)table) & 3u) || (((uintptr_t)out) & (out_dtype == LMV_F32 ? 3u : 1u)) || (((uintptr_t)x) & (x_dtype == LMV_F32 ? 3u : x_dtype == LMV_BF16 ? 1u : 0u)))
-    LMV_FAIL(LMV_ERR_SHAPE, "mix_images: misaligned buffer");
+    LMV_FAIL(LMV_ERR_SHAPE, "%s: misaligned buffer", fn);
   if (host_records)
     for (int b = 0; b < B; ++b) {
       const lmv_mix_record& r = host_records[b];
       if (r.yl < 0 || r.yl > r.yh || r.yh > H || r.xl < 0 || r.xl > r.xh || r.xh > W)
-        LMV_FAIL(LMV_ERR_SHAPE, "mix_images: record %d: box [%d, %d) x [%d, %d) outside the %d x %d image (or yl > yh, xl > xh)", b, r.yl, r.yh, r.xl, r.xh, H, W);
-      if (!(r.w == r.w) || !(r.lam_t == r.lam_t)) LMV_FAIL(LMV_ERR_SHAPE, "mix_images: record %d: NaN factor", b);
+        LMV_FAIL(LMV_ERR_SHAPE, "%s: record %d: box [%d, %d) x [%d, %d) outside the %d x %d image (or yl > yh, xl > xh)", fn, b, r.yl, r.yh, r.xl, r.xh, H, W);
+      if (!(r.w == r.w) || !(r.lam_t == r.lam_t)) LMV_FAIL(LMV_ERR_SHAPE, "%s: record %d: NaN factor", fn, b);
     }
   const int V = out_dtype == LMV_F32 ? 4 : 8;
+  a->x = x; a->out = out; a->table = table; a->scale = scale; a->shift = shift;
+  a->sb = sb; a->sc = sc; a->sh = sh; a->sw = sw;
+  a->B = B; a->C = C; a->H = H; a->W = W;
+  a->K = (W + V - 1) / V + 2;
+  a->vec = (((int64_t)C * H * W) % V == 0 && lmv_aligned16(out)) ? 1 : 0;
+  const int64_t threads = (int64_t)C * H * a->K;
+  *grid = dim3((unsigned)((threads + MIX_TPB - 1) / MIX_TPB), (unsigned)((B + 1) / 2));
+  if (grid->y > 65535u) LMV_FAIL(LMV_ERR_SHAPE, "%s: B = %d exceeds 131070 images", fn, B);
+  return LMV_OK;
+}
+}  // namespace
+
+extern "C" int lmv_mix_images(const void* x, int x_dtype, int64_t sb, int64_t sc, int64_t sh, int64_t sw, void* out, int out_dtype, int B, int C, int H, int W,
+                              const lmv_mix_record* table, const lmv_mix_record* host_records, const float* scale, const float* shift, void* stream) {
+  if (x && out && !table) LMV_FAIL(LMV_ERR_SHAPE, "mix_images: null table (one lmv_mix_record per image, in device memory)");
   MixArgs a;
-  a.x = x; a.out = out; a.table = table; a.scale = scale; a.shift = shift;
-  a.sb = sb; a.sc = sc; a.sh = sh; a.sw = sw;
-  a.B = B; a.C = C; a.H = H; a.W = W;
-  a.K = (W + V - 1) / V + 2;
-  a.vec = (((int64_t)C * H * W) % V == 0 && lmv_aligned16(out)) ? 1 : 0;
-  const int64_t threads = (int64_t)C * H * a.K;
-  const dim3 grid((unsigned)((threads + MIX_TPB - 1) / MIX_TPB), (unsigned)((B + 1) / 2));
-  if (grid.y > 65535u) LMV_FAIL(LMV_ERR_SHAPE, "mix_images: B = %d exceeds 131070 images", B);
+  dim3 grid;
+  if (int rc = mix_prepare("mix_images", x, x_dtype, sb, sc, sh, sw, out, out_dtype, B, C, H, W, table, host_records, scale, shift, &a, &grid)) return rc;
   hipStream_t st = (hipStream_t)stream;
   if (x_dtype == LMV_F32) return mix_launch<float>(a, out_dtype, grid, st);
   if (x_dtype == LMV_BF16) return mix_launch<bf16_t>(a, out_dtype, grid, st);
   return mix_launch<uint8_t>(a, out_dtype, grid, st);
+}
+
+extern "C" int lmv_augment_images(const void* x, int x_dtype, int64_t sb, int64_t sc, int64_t sh, int64_t sw, void* out, int out_dtype, int B, int C, int H, int W,
+                                  const lmv_mix_record* mix_table, const lmv_mix_record* host_records, const lmv_erase_record* erase_table, const uint32_t* erase_key,
+                                  int erase_mode, const lmv_erase_record* host_erase_records, const float* scale, const float* shift, void* stream) {
+  MixArgs a;
+  dim3 grid;
+  if (int rc = mix_prepare("augment_images", x, x_dtype, sb, sc, sh, sw, out, out_dtype, B, C, H, W, mix_table, host_records, scale, shift, &a, &grid)) return rc;
+  if (erase_mode != LMV_ERASE_CONST && erase_mode != LMV_ERASE_RAND && erase_mode != LMV_ERASE_PIXEL)
+    LMV_FAIL(LMV_ERR_SHAPE, "augment_images: unknown erase mode %d (LMV_ERASE_CONST, LMV_ERASE_RAND or LMV_ERASE_PIXEL)", erase_mode);
+  if (erase_table && erase_mode != LMV_ERASE_CONST && !erase_key)
+    LMV_FAIL(LMV_ERR_SHAPE, "augment_images: an erase table in the rand / pixel mode needs a key (two 32-bit words in device memory)");
+  if ((((uintptr_t)erase_table) & 3u) || (((uintptr_t)erase_key) & 3u)) LMV_FAIL(LMV_ERR_SHAPE, "augment_images: misaligned erase table or key");
+  if (host_erase_records)
+    for (int b = 0; b < B; ++b)
+      for (int i = 0; i < LMV_ERASE_MAX_BOXES; ++i) {
+        const int32_t* r = host_erase_records[b].box[i];
+        if (r[0] < 0 || r[0] > r[1] || r[1] > H || r[2] < 0 || r[2] > r[3] || r[3] > W)
+          LMV_FAIL(LMV_ERR_SHAPE, "augment_images: erase record %d, box %d: [%d, %d) x [%d, %d) outside the %d x %d image (or yl > yh, xl > xh)", b, i, r[0], r[1], r[2], r[3], H, W);
+      }
+  EraseArgs g;
+  g.table = erase_table; g.key = erase_key; g.mode = erase_mode;
+  hipStream_t st = (hipStream_t)stream;
+  if (x_dtype == LMV_F32) return augment_launch<float>(a, g, out_dtype, grid, st);
+  if (x_dtype == LMV_BF16) return augment_launch<bf16_t>(a, g, out_dtype, grid, st);
+  return augment_launch<uint8_t>(a, g, out_dtype, grid, st);
 }
 
 // ---- soft-target cross-entropy -----------------------------------------------------------------------------------------------------------------

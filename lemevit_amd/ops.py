@@ -828,6 +828,61 @@ def mix_images(x: Tensor, table: Tensor, out_dtype: Optional[torch.dtype] = None
     return out
 
 
+ERASE_RECORD_WORDS = C.sizeof(_lib.EraseRecord) // 4          # an erase table is an int32 tensor [B, 16]: four boxes of yl, yh, xl, xh per image
+ERASE_MODES = {"const": _lib.ERASE_CONST, "rand": _lib.ERASE_RAND, "pixel": _lib.ERASE_PIXEL}          # timm's RandomErasing modes
+
+
+def augment_images(x: Tensor, mix_table: Optional[Tensor], erase_table: Optional[Tensor], erase_key: Optional[Tensor], mode: str = "const",
+                   out_dtype: Optional[torch.dtype] = None, scale: Optional[Tensor] = None, shift: Optional[Tensor] = None, records: Optional[Tensor] = None,
+                   erase_records: Optional[Tensor] = None) -> Tensor:
+    """One launch of lmv_augment_images: ``mix_images`` with random erasing behind the normalisation.  ``mix_table`` (None: no mixing), ``x``, ``out_dtype``,
+    ``scale`` / ``shift`` and ``records`` as in ``mix_images``.  ``erase_table``: DEVICE int32 [B, 16], four boxes ``yl, yh, xl, xh`` per image (None: nothing is
+    erased and the result equals ``mix_images``' bit for bit); ``erase_key``: DEVICE int32 [2], the two key words of the noise (needed by 'rand' and 'pixel');
+    ``mode``: 'const' (0), 'rand' (one normal per box and channel) or 'pixel' (one normal per element: ``recipe.erase_noise``).  ``erase_records``: a host copy
+    of the erase table, validated against the image before the launch.  ``x`` is not modified."""
+    if x.dim() != 4:
+        raise ValueError(f"augment_images: [B, C, H, W] images expected, got {tuple(x.shape)}")
+    if not x.is_cuda:
+        raise RuntimeError("lemevit_amd: tensors must be on the GPU (no CPU fallback exists)")
+    codes = {torch.float32: _lib.LMV_F32, torch.bfloat16: _lib.LMV_BF16, torch.uint8: _lib.LMV_U8}
+    if x.dtype not in codes:
+        raise TypeError(f"augment_images: unsupported image dtype {x.dtype} (uint8, float32 and bfloat16 only)")
+    if out_dtype is None:
+        out_dtype = torch.float32 if x.dtype == torch.uint8 else x.dtype
+    if out_dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"augment_images: unsupported output dtype {out_dtype} (float32 and bfloat16 only)")
+    if mode not in ERASE_MODES:
+        raise ValueError(f"augment_images: unknown mode {mode!r} ('const', 'rand' or 'pixel')")
+    B, C_, H, W = x.shape
+    if (scale is None) != (shift is None):
+        raise ValueError("augment_images: scale and shift come together")
+    if scale is not None and (scale.numel() != C_ or shift.numel() != C_):
+        raise ValueError(f"augment_images: scale and shift must have one element per channel ({C_})")
+    tp = _mix_table(mix_table, B, "augment_images") if mix_table is not None else None
+    ep = kp = None
+    if erase_table is not None:
+        if erase_table.dtype != torch.int32 or tuple(erase_table.shape) != (B, ERASE_RECORD_WORDS) or not erase_table.is_contiguous() or not erase_table.is_cuda:
+            raise TypeError(f"augment_images: erase_table must be a contiguous int32 GPU tensor [{B}, {ERASE_RECORD_WORDS}], got {tuple(erase_table.shape)} {erase_table.dtype}")
+        ep = erase_table.data_ptr()
+    if erase_key is not None:
+        if erase_key.dtype != torch.int32 or erase_key.numel() != 2 or not erase_key.is_contiguous() or not erase_key.is_cuda:
+            raise TypeError("augment_images: erase_key must be a contiguous int32 GPU tensor of two words")
+        kp = erase_key.data_ptr()
+
+    def host(t, words, name):
+        if t is None:
+            return None
+        if t.is_cuda or not t.is_contiguous() or t.dtype != torch.int32 or tuple(t.shape) != (B, words):
+            raise TypeError(f"augment_images: {name} must be a contiguous int32 CPU tensor [{B}, {words}]")
+        return t.data_ptr()
+    hp, hep = host(records, MIX_RECORD_WORDS, "records"), host(erase_records, ERASE_RECORD_WORDS, "erase_records")
+    out = torch.empty((B, C_, H, W), device=x.device, dtype=out_dtype)
+    sb, sc, sh, sw = x.stride()
+    check(lib.lmv_augment_images(x.data_ptr(), codes[x.dtype], sb, sc, sh, sw, _ptr(out), codes[out_dtype], B, C_, H, W, tp, hp, ep, kp, ERASE_MODES[mode], hep,
+                                 _f32(scale), _f32(shift), _stream()), "lmv_augment_images")
+    return out
+
+
 def soft_ce(logits: Tensor, labels: Optional[Tensor] = None, table: Optional[Tensor] = None, smoothing: float = 0.0, target: Optional[Tensor] = None,
             want_grad: bool = True) -> Tuple[Tensor, Tensor, Optional[Tensor]]:
     """lmv_soft_ce: cross-entropy of ``logits`` [B, N] (float32 / bfloat16; unit column stride, ANY row stride: a ``[:, :N]`` view of padded logits is read in
