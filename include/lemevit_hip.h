@@ -533,6 +533,46 @@ int lmv_augment_images(const void* x, int x_dtype, int64_t sb, int64_t sc, int64
                        int erase_mode, const lmv_erase_record* host_erase_records, const float* scale, const float* shift, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Validation metrics (csrc/metrics.hip; the metrics tail of the reference's evaluation loop, engine.py:177-247 validate and validate.py:330-377:
+ * nn.CrossEntropyLoss, utils.accuracy(output, target, topk=(1, 5)), the --tta reduction, three reduce_tensor, a synchronize and three .item() per batch).
+ * An addition to ABI 14: callers detect it by symbol.  Neither call synchronises the host; both can be captured in a hipGraph.
+ *
+ * lmv_eval_logits: logits [B, N] fp32 / bf16, unit column stride, row stride `row_stride` elements (>= N: the [:, :N] view of padded logits is read in place;
+ * what lies behind column N is never read), any N >= 1 (every class value is recomputed per sweep, nothing is staged).  reduce_factor r >= 1, B % r == 0 (the
+ * reference's --tta: output.unfold(0, r, r).mean(dim=2), target[0::r]); labels int64 [B / r].  Output row g, g < B / r, evaluates the values
+ *     v_j = (((x[g r, j] + x[g r + 1, j]) + ...) + x[g r + r - 1, j]) * (1.0f / r)        in fp32, in this order, the product never fused into its consumer;
+ * r == 1: v_j = x[g, j], no arithmetic touches it.  Per output row, each element written by exactly one thread, no atomics, two launches agree bit for bit:
+ *   row_loss[g] (fp32) = lse - v_y, lse = max_j v_j + log(sum_j exp(v_j - max)), y = labels[g]: plain cross-entropy.  A NaN logit makes the row's loss NaN.
+ *   rank[g] (int32)    = the number of classes ordered BEFORE class y in this total order: class j is before class i iff v_j > v_i, or v_j == v_i and j < i;
+ *                        NaN orders before every number (as torch.topk does) and NaNs among themselves by index; -0.0 == +0.0.  The comparison at j == y is
+ *                        decided by the index, never by the value.  rank < k  <=>  the label is among the first k classes: top-k accuracy.
+ *   pred[g, 0 .. K)    (int32 [B / r, K], K <= LMV_EVAL_MAX_PRED, K <= N; K == 0: pred may be NULL) = the first K classes of the same order.
+ * The order is that of the 64-bit word (key(v_j), ~j), key = the value's bits flipped on sign, every NaN the top key, -0 the key of +0.
+ * A row whose label is outside [0, N) is IGNORED: row_loss = 0, rank = -1, pred still written; the label is never used as an index.  A padded last batch or a
+ * distributed sampler's duplicates are marked so (label -1).  This differs ON PURPOSE from lmv_soft_ce, where such a label merely carries no one-hot mass and
+ * the row still contributes lse * (remaining mass): there the row is a training sample with a partner, here it is not a sample at all.
+ * One wave per output row, 2 + K sweeps over the cached row.  Refused with LMV_ERR_SHAPE and a message, before any launch: null logits / labels / row_loss /
+ * rank, B < 1, N < 1, reduce_factor < 1 or not a divisor of B, row_stride < N, a dtype code other than LMV_F32 / LMV_BF16, K outside 0 .. 16, K > N, K > 0
+ * with a null pred, a misaligned buffer.
+ *
+ * lmv_meter_add: ONE wave adds a batch into the persistent DEVICE accumulator `state`, float64 [2 + nk] = {loss_sum, rows_counted, hits(ks[0]), ...,
+ * hits(ks[nk - 1])}, nk <= LMV_METER_MAX_K; the thresholds ks are read on the HOST and passed to the kernel by value.
+ *   per-row mode (row_loss, rank != NULL, loss == NULL): over the `rows` results of lmv_eval_logits, rows with rank < 0 (ignored) adding nothing:
+ *     state[0] += sum row_loss, state[1] += number of rows, state[2 + i] += number of rows with 0 <= rank < ks[i].  Lane l adds rows l, l + 64, ... in order,
+ *     then a butterfly, all in double -- a fixed tree; one thread then updates the state.
+ *   scalar mode (loss != NULL, row_loss == rank == NULL): state[0] += (double)*loss * n, state[1] += n (loss: fp32 DEVICE scalar; the train loop's
+ *     losses_m.update(loss.item(), n) without the .item()); the hit entries are not touched.
+ * Stream order serialises successive updates: two runs give the same bits.  Doubles hold the counts exactly (< 2^53) and one dtype keeps the merge across
+ * ranks to ONE sum all-reduce of the state.  Refused with LMV_ERR_SHAPE before any launch: a null state, nk outside 0 .. 8, null ks with nk > 0, a threshold
+ * < 1, both or neither mode's operands, row_loss without rank, rows < 1 (per-row mode), n < 1 (scalar mode), a misaligned buffer.
+ * ------------------------------------------------------------------------------------------ */
+#define LMV_EVAL_MAX_PRED 16
+#define LMV_METER_MAX_K 8
+int lmv_eval_logits(const void* logits, int dtype, int64_t row_stride, int B, int N, const int64_t* labels, int reduce_factor, float* row_loss, int32_t* rank,
+                    int32_t* pred, int K, void* stream);
+int lmv_meter_add(double* state, const float* row_loss, const int32_t* rank, int rows, const int32_t* ks, int nk, const float* loss, int64_t n, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Whole-block schedules: ONE call enqueues every launch of a LeMeBlock (models/lemevit.py:500-660) on token-major tensors
  * x [B, H*W, C], c [B, M, C] -- `LeMeBlock.forward_with_x` ("S", :615-650), `forward_with_xc` ("D", :542-582), `forward_with_c`
  * ("C", :584-613; x is returned untouched by the caller, x_out / dx_out may be NULL).  Replaces the ~12 / ~30 per-op calls a Python

@@ -24,6 +24,7 @@ GRAD_STAT_FLOATS, NORM_CHUNK, NORM_SKIP_NONFINITE = 8, 16384, 1          # LMV_G
 ADAMW_UNIT, ADAMW_MAX_GROUPS = 8, 256          # LMV_ADAMW_UNIT, LMV_ADAMW_MAX_GROUPS
 ERASE_MAX_BOXES = 4          # LMV_ERASE_MAX_BOXES
 ERASE_CONST, ERASE_RAND, ERASE_PIXEL = 0, 1, 2          # lmv_augment_images: erase_mode
+EVAL_MAX_PRED, METER_MAX_K = 16, 8          # LMV_EVAL_MAX_PRED, LMV_METER_MAX_K
 
 
 class LinearProblem(C.Structure):
@@ -192,6 +193,8 @@ SIGNATURES = {
     "lmv_mix_images": (_I, [_P, _I, _L, _L, _L, _L, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "lmv_soft_ce": (_I, [_P, _I, _L, _I, _I, _P, _P, _F, _P, _I, _L, _P, _P, _P, _P]),
     "lmv_augment_images": (_I, [_P, _I, _L, _L, _L, _L, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P]),
+    "lmv_eval_logits": (_I, [_P, _I, _L, _I, _I, _P, _I, _P, _P, _P, _I, _P]),
+    "lmv_meter_add": (_I, [_P, _P, _P, _I, C.POINTER(C.c_int32), _I, _P, _L, _P]),
     "lmv_block_arena_bytes": (_Z, [C.POINTER(BlockDesc)]),
     "lmv_block_bwd_scratch_bytes": (_Z, [C.POINTER(BlockDesc)]),
     "lmv_block_fwd": (_I, [C.POINTER(BlockDesc), _P, _P, _P, _P, _P, _Z, _I, _P]),

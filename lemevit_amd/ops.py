@@ -931,6 +931,85 @@ def soft_ce(logits: Tensor, labels: Optional[Tensor] = None, table: Optional[Ten
 
 
 # -------------------------------------------------------------------------------------------
+# validation metrics (csrc/metrics.hip; lemevit_amd.metrics holds the user-facing names)
+# -------------------------------------------------------------------------------------------
+def eval_logits(logits: Tensor, labels: Tensor, reduce_factor: int = 1, k_pred: int = 0,
+                out: Optional[Tuple[Tensor, Tensor, Optional[Tensor]]] = None) -> Tuple[Tensor, Tensor, Optional[Tensor]]:
+    """One launch of lmv_eval_logits: ``logits`` [B, N] (float32 / bfloat16; unit column stride, ANY row stride >= N: a ``[:, :N]`` view of padded logits is
+    read in place, nothing is copied), ``labels`` int64 [B / reduce_factor].  Output row g evaluates the fp32 mean of the logits rows ``g r .. g r + r - 1``
+    (the reference's ``--tta``).  Returns ``(row_loss, rank, pred)``: the plain cross-entropy (float32 [B / r]), the number of classes ordered before the
+    label's (int32 [B / r]; ``rank < k`` is a top-k hit) and the first ``k_pred`` classes of that order (int32 [B / r, k_pred]; None with ``k_pred == 0``).
+    The order: greater value first, then smaller index; NaN before everything; ``-0.0 == +0.0``.  A row whose label is outside ``[0, N)`` is ignored:
+    ``row_loss = 0``, ``rank = -1``.  ``out``: the three result buffers of an earlier call with the same shapes, written in place of new ones."""
+    if logits.dim() != 2:
+        raise ValueError(f"eval_logits: [B, N] logits expected, got {tuple(logits.shape)}")
+    if not logits.is_cuda:
+        raise RuntimeError("lemevit_amd: tensors must be on the GPU (no CPU fallback exists)")
+    code = dtype_code(logits)
+    B, N = logits.shape
+    r, K = int(reduce_factor), int(k_pred)
+    if B < 1 or N < 1:
+        raise ValueError(f"eval_logits: empty logits {tuple(logits.shape)}")
+    if r < 1 or B % r:
+        raise ValueError(f"eval_logits: reduce_factor {r} must be >= 1 and divide B = {B}")
+    if not 0 <= K <= _lib.EVAL_MAX_PRED or K > N:
+        raise ValueError(f"eval_logits: k_pred = {K} outside 0 .. min({_lib.EVAL_MAX_PRED}, N = {N})")
+    if N > 1 and logits.stride(1) != 1:
+        raise ValueError("eval_logits: the logits must have unit stride along the classes")
+    ls = logits.stride(0) if B > 1 else N
+    if ls < N:
+        raise ValueError("eval_logits: overlapping logit rows")
+    G = B // r
+    if labels.dtype != torch.int64 or tuple(labels.shape) != (G,) or labels.device != logits.device:
+        raise TypeError(f"eval_logits: labels must be an int64 tensor [{G}] on the logits' device, got {tuple(labels.shape)} {labels.dtype}")
+    if out is None:
+        row = torch.empty((G,), device=logits.device, dtype=torch.float32)
+        rank = torch.empty((G,), device=logits.device, dtype=torch.int32)
+        pred = torch.empty((G, K), device=logits.device, dtype=torch.int32) if K else None
+    else:
+        row, rank, pred = out
+        if (row.dtype != torch.float32 or tuple(row.shape) != (G,) or rank.dtype != torch.int32 or tuple(rank.shape) != (G,) or row.device != logits.device or
+                rank.device != logits.device or (K and (pred is None or pred.dtype != torch.int32 or tuple(pred.shape) != (G, K) or pred.device != logits.device))):
+            raise TypeError(f"eval_logits: out must be (float32 [{G}], int32 [{G}], int32 [{G}, {K}]) on the logits' device")
+    check(lib.lmv_eval_logits(logits.data_ptr(), code, ls, B, N, _ptr(labels), r, _ptr(row), _ptr(rank), _ptr(pred) if K else None, K, _stream()), "lmv_eval_logits")
+    return row, rank, (pred if K else None)
+
+
+def meter_add(state: Tensor, row_loss: Optional[Tensor] = None, rank: Optional[Tensor] = None, ks: Sequence[int] = (), loss: Optional[Tensor] = None, n: int = 0) -> None:
+    """One launch of lmv_meter_add: adds a batch into ``state``, the float64 GPU vector ``[loss_sum, rows_counted, hits(ks[0]), ...]`` (``2 + len(ks)`` entries,
+    at most 8 thresholds).  Per-row mode: ``row_loss`` (float32 [rows]) and ``rank`` (int32 [rows]) of ``eval_logits``; rows with ``rank < 0`` add nothing,
+    ``hits(k)`` counts ``0 <= rank < k``.  Scalar mode: ``loss`` (0-dim float32 GPU tensor) and ``n``: ``loss_sum += loss * n``, ``rows_counted += n``.  One
+    wave, a fixed summation tree in double, no atomics; no host synchronisation."""
+    ks = [int(k) for k in ks]
+    if len(ks) > _lib.METER_MAX_K:
+        raise ValueError(f"meter_add: {len(ks)} thresholds, at most {_lib.METER_MAX_K}")
+    if any(k < 1 for k in ks):
+        raise ValueError(f"meter_add: thresholds must be >= 1, got {ks}")
+    if state.dtype != torch.float64 or state.dim() != 1 or state.numel() != 2 + len(ks):
+        raise TypeError(f"meter_add: state must be a float64 vector of {2 + len(ks)} entries, got {tuple(state.shape)} {state.dtype}")
+    per_row = row_loss is not None or rank is not None
+    if per_row == (loss is not None):
+        raise ValueError("meter_add: exactly one of (row_loss, rank) and loss must be given")
+    rows = 0
+    if per_row:
+        if row_loss is None or rank is None:
+            raise ValueError("meter_add: row_loss and rank come together")
+        rows = row_loss.numel()
+        if row_loss.dtype != torch.float32 or rank.dtype != torch.int32 or row_loss.dim() != 1 or tuple(rank.shape) != (rows,) or rows < 1:
+            raise TypeError(f"meter_add: row_loss must be float32 [rows] and rank int32 [rows], rows >= 1; got {tuple(row_loss.shape)} {row_loss.dtype}, {tuple(rank.shape)} {rank.dtype}")
+    else:
+        if loss.dtype != torch.float32 or loss.numel() != 1:
+            raise TypeError(f"meter_add: loss must be a float32 scalar tensor, got {tuple(loss.shape)} {loss.dtype}")
+        if int(n) < 1:
+            raise ValueError(f"meter_add: n = {n} < 1")
+    for t in (row_loss, rank, loss):
+        if t is not None and t.device != state.device:
+            raise RuntimeError("meter_add: the operands must be on the state's device")
+    kv = (C.c_int32 * max(len(ks), 1))(*ks)
+    check(lib.lmv_meter_add(_ptr(state), _ptr(row_loss), _ptr(rank), rows, kv, len(ks), _ptr(loss), int(n), _stream()), "lmv_meter_add")
+
+
+# -------------------------------------------------------------------------------------------
 # A run of "S" blocks as one persistent launch (csrc/sstage.hip; inference, bf16)
 # -------------------------------------------------------------------------------------------
 def sstage_supported(C_: int, heads: int, hidden: int, H: int, W: int, M: int, dtype: torch.dtype) -> bool:
