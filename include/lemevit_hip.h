@@ -573,6 +573,65 @@ int lmv_eval_logits(const void* logits, int dtype, int64_t row_stride, int B, in
 int lmv_meter_add(double* state, const float* row_loss, const int32_t* rank, int rows, const int32_t* ks, int nk, const float* loss, int64_t n, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Dense-prediction losses and metrics (csrc/dense.hip; the reference's change_detection/utils/metrics.py FocalLoss / dice_loss / jaccard_loss, utils/losses.py
+ * hybrid_loss, the per-batch torch.max / eq / sum of train.py:154-260, sklearn's confusion_matrix of eval.py:39-66, and the segmentation heads' per-pixel
+ * cross-entropy with an ignore index and mIoU histogram).  An addition to ABI 14: callers detect it by symbol.  No call synchronises the host; all can be captured.
+ *
+ * Inputs.  logits [B, K, H, W] fp32 / bf16: pixel stride 1, ELEMENT strides batch_stride and class_stride (a class-sliced view buf[:, 1:K+1] is read in place;
+ * nothing outside the K planes of H W pixels is read), 2 <= K <= LMV_DENSE_MAX_CLASSES, B H W < 2^31 (HW = H W).  labels [B, H W], contiguous,
+ * LMV_DENSE_LABEL_I64 or LMV_DENSE_LABEL_U8.  A pixel is IGNORED when its label equals ignore_index or lies outside [0, K): it is never used as an index and
+ * contributes to no sum, count or gradient -- the rule of lmv_eval_logits (a row that is not a sample at all), not that of lmv_soft_ce.  Pass ignore_index = -1
+ * for "none".  alpha: float32 DEVICE vector [K] or NULL (= all ones); float32 by definition (the reference builds it with torch.Tensor([...])).
+ *
+ * Per valid pixel i, in fp32 with the maximum subtracted (logits of +-80 work): p = softmax(z_i), y = label,
+ *     f_i = alpha[y] (1 - p_y)^gamma        a CONSTANT of the backward pass (the reference detaches pt, utils/metrics.py:35); gamma == 0: f_i = alpha[y].
+ * Per class k over the valid pixels of the call:  I_k = sum p_k [y = k],  P_k = sum p_k,  T_k = sum [y = k].
+ *     ce      = (sum_i f_i (-log p_{i,y})) / D,   D by avg_mode:  LMV_DENSE_AVG_VALID  the number of valid pixels (F.cross_entropy(ignore_index=));
+ *                                                                 LMV_DENSE_AVG_ALL    B H W (the reference's .mean());
+ *                                                                 LMV_DENSE_AVG_WEIGHT sum_k alpha_k T_k (F.cross_entropy(weight=));      D == 0: ce = 0, gradient 0
+ *     dice    = 1 - (1 / K) sum_k 2 I_k / (P_k + T_k + eps)
+ *     jaccard = 1 - (1 / K) sum_k I_k / (P_k + T_k - I_k + eps)
+ *     loss    = w_ce ce + w_dice dice + w_jac jaccard
+ * Gradient: with C_k = P_k + T_k + eps, U_k = P_k + T_k - I_k + eps,
+ *     u_k = -w_dice 2 / (K C_k) - w_jac (1 / U_k + I_k / U_k^2) / K,     v_k = w_dice 2 I_k / (K C_k^2) + w_jac I_k / (K U_k^2),     g_ik = u_k [y_i = k] + v_k,
+ *     dz_ik = gout ( p_ik (g_ik - sum_j p_ij g_ij) + w_ce f_i (p_ik - [y_i = k]) / D );          an ignored pixel gets exact zeros.
+ *
+ * lmv_dense_loss_fwd -- two launches.  (a) a grid-stride pass: a thread owns chunks of 16 bytes of consecutive pixels of one image (4 fp32 / 8 bf16) and reads one
+ * 16-byte word per class plane when the logits pointer is 16-byte aligned and both strides are multiples of the chunk, element loads otherwise -- the chunks, the
+ * arithmetic and every summation order are the same on both paths, so the result does not depend on which ran.  Each thread keeps fp32 partial sums; they are added
+ * by a butterfly within the wave and over the waves in order, and each workgroup writes one row of 3 K + 3 floats into `workspace`
+ * (lmv_dense_loss_workspace_bytes(B, K, HW)).  pred (nullable): uint8 [B, H W], the argmax of EVERY pixel, ignored ones included: the first index of the maximum,
+ * a NaN greater than every number (the first NaN wins), -0 == +0.  conf (nullable): a persistent int64 [K, K] DEVICE matrix, conf[y, pred] += 1 per valid pixel
+ * (an LDS histogram per workgroup, then integer atomics: integer adds commute).  No floating-point atomic anywhere: two calls agree bit for bit.
+ * (b) ONE workgroup adds the rows in double in a fixed order and writes `stats`, float32 [LMV_DENSE_STATS_FLOATS(K)]:
+ *     stats[0 .. 6) = loss, ce, dice, jaccard, n_valid, 1 / D (0 when D == 0);  then u[K], v[K], I[K], P[K], T[K]
+ * (n_valid and T_k are exact below 2^24).  meter (nullable): a persistent float64 [2] DEVICE accumulator, meter[0] += sum_valid -log p_y (unweighted),
+ * meter[1] += n_valid, both exact in double; stream order serialises successive calls.
+ *
+ * lmv_dense_loss_bwd -- one launch: re-reads logits and labels, reads u, v and 1 / D from `stats` in DEVICE memory and gout through a DEVICE pointer to a float
+ * (NULL = 1), and writes dlogits, contiguous [B, K, H, W] in the logits dtype, every element exactly once (no pre-zeroed buffer).  gamma, the weights, alpha,
+ * ignore_index and avg_mode are the arguments of the forward call that produced `stats`.
+ *
+ * Refused with LMV_ERR_SHAPE and a message that starts "dense_loss", before any launch: null logits / labels / workspace / stats / dlogits; a misaligned buffer
+ * (logits and dlogits to their element, int64 labels, conf and meter to 8 bytes, workspace, stats, alpha and gout to 4); K outside 2 .. 64; B < 1, H W < 1 or
+ * B H W >= 2^31; a dtype code other than LMV_F32 / LMV_BF16 or a label dtype code other than the two above; class_stride < H W or
+ * batch_stride < (K - 1) class_stride + H W (strides smaller than the extent they skip); a workspace smaller than lmv_dense_loss_workspace_bytes; a negative (or
+ * NaN) w_ce / w_dice / w_jac, gamma < 0, eps <= 0; an unknown avg_mode.
+ * ------------------------------------------------------------------------------------------ */
+#define LMV_DENSE_MAX_CLASSES 64
+#define LMV_DENSE_STATS_HEAD 6
+#define LMV_DENSE_STATS_FLOATS(K) (LMV_DENSE_STATS_HEAD + 5 * (K))
+enum { LMV_DENSE_LABEL_I64 = 0, LMV_DENSE_LABEL_U8 = 1 };
+enum { LMV_DENSE_AVG_VALID = 0, LMV_DENSE_AVG_ALL = 1, LMV_DENSE_AVG_WEIGHT = 2 };
+size_t lmv_dense_loss_workspace_bytes(int B, int K, int64_t HW);
+int lmv_dense_loss_fwd(const void* logits, int dtype, int64_t batch_stride, int64_t class_stride, int B, int K, int64_t HW, const void* labels, int label_dtype,
+                       int64_t ignore_index, const float* alpha, float gamma, float w_ce, float w_dice, float w_jac, float eps, int avg_mode, void* workspace,
+                       size_t workspace_bytes, float* stats, uint8_t* pred, int64_t* conf, double* meter, void* stream);
+int lmv_dense_loss_bwd(const void* logits, int dtype, int64_t batch_stride, int64_t class_stride, int B, int K, int64_t HW, const void* labels, int label_dtype,
+                       int64_t ignore_index, const float* alpha, float gamma, float w_ce, float w_dice, float w_jac, float eps, int avg_mode, const float* stats,
+                       const float* gout, void* dlogits, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Whole-block schedules: ONE call enqueues every launch of a LeMeBlock (models/lemevit.py:500-660) on token-major tensors
  * x [B, H*W, C], c [B, M, C] -- `LeMeBlock.forward_with_x` ("S", :615-650), `forward_with_xc` ("D", :542-582), `forward_with_c`
  * ("C", :584-613; x is returned untouched by the caller, x_out / dx_out may be NULL).  Replaces the ~12 / ~30 per-op calls a Python

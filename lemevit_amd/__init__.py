@@ -14,6 +14,8 @@ from . import recipe  # noqa: F401
 from .recipe import LabelSmoothingCrossEntropy, MixedTarget, Mixup, RandomErasing, SoftTargetCrossEntropy  # noqa: F401
 from . import metrics  # noqa: F401
 from .metrics import EvalMeter, accuracy, reference_metrics, validate  # noqa: F401
+from . import dense  # noqa: F401
+from .dense import DenseCrossEntropy, DenseLoss, FocalLoss, SegMeter, dice_loss, hybrid_loss, jaccard_loss, reference_dense  # noqa: F401
 from . import dist  # noqa: F401  (wrap_ddp, FlatGradSync, attach_flat_grad_sync)
 from .registry import create_model, is_model, list_models, load_checkpoint, register_model  # noqa: F401
 from .registry import lemevit_base, lemevit_small, lemevit_small_v2, lemevit_tiny, lemevit_tiny_v2, vit_tiny  # noqa: F401
@@ -21,4 +23,5 @@ from .registry import lemevit_base, lemevit_small, lemevit_small_v2, lemevit_tin
 __all__ = ["create_model", "register_model", "list_models", "is_model", "load_checkpoint", "LeMeViT", "LeMeViTBackbone", "LeMeBlock",
            "StandardAttention", "DualCrossAttention", "DualCrossAttention_v2", "CrossAttention", "lemevit_tiny", "lemevit_small", "lemevit_base",
            "lemevit_small_v2", "lemevit_tiny_v2", "vit_tiny", "ops", "FlatAdamW", "ModelEma", "layer_ids", "recipe", "Mixup", "MixedTarget", "RandomErasing",
-           "SoftTargetCrossEntropy", "LabelSmoothingCrossEntropy", "metrics", "EvalMeter", "accuracy", "validate", "reference_metrics"]
+           "SoftTargetCrossEntropy", "LabelSmoothingCrossEntropy", "metrics", "EvalMeter", "accuracy", "validate", "reference_metrics",
+           "dense", "DenseLoss", "SegMeter", "hybrid_loss", "dice_loss", "jaccard_loss", "FocalLoss", "DenseCrossEntropy", "reference_dense"]

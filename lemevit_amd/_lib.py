@@ -25,6 +25,9 @@ ADAMW_UNIT, ADAMW_MAX_GROUPS = 8, 256          # LMV_ADAMW_UNIT, LMV_ADAMW_MAX_G
 ERASE_MAX_BOXES = 4          # LMV_ERASE_MAX_BOXES
 ERASE_CONST, ERASE_RAND, ERASE_PIXEL = 0, 1, 2          # lmv_augment_images: erase_mode
 EVAL_MAX_PRED, METER_MAX_K = 16, 8          # LMV_EVAL_MAX_PRED, LMV_METER_MAX_K
+DENSE_MAX_CLASSES, DENSE_STATS_HEAD = 64, 6          # LMV_DENSE_MAX_CLASSES, LMV_DENSE_STATS_HEAD (stats: 6 + 5 K floats)
+DENSE_LABEL_I64, DENSE_LABEL_U8 = 0, 1
+DENSE_AVG_VALID, DENSE_AVG_ALL, DENSE_AVG_WEIGHT = 0, 1, 2
 
 
 class LinearProblem(C.Structure):
@@ -195,6 +198,9 @@ SIGNATURES = {
     "lmv_augment_images": (_I, [_P, _I, _L, _L, _L, _L, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P]),
     "lmv_eval_logits": (_I, [_P, _I, _L, _I, _I, _P, _I, _P, _P, _P, _I, _P]),
     "lmv_meter_add": (_I, [_P, _P, _P, _I, C.POINTER(C.c_int32), _I, _P, _L, _P]),
+    "lmv_dense_loss_workspace_bytes": (_Z, [_I, _I, _L]),
+    "lmv_dense_loss_fwd": (_I, [_P, _I, _L, _L, _I, _I, _L, _P, _I, _L, _P, _F, _F, _F, _F, _F, _I, _P, _Z, _P, _P, _P, _P, _P]),
+    "lmv_dense_loss_bwd": (_I, [_P, _I, _L, _L, _I, _I, _L, _P, _I, _L, _P, _F, _F, _F, _F, _F, _I, _P, _P, _P, _P]),
     "lmv_block_arena_bytes": (_Z, [C.POINTER(BlockDesc)]),
     "lmv_block_bwd_scratch_bytes": (_Z, [C.POINTER(BlockDesc)]),
     "lmv_block_fwd": (_I, [C.POINTER(BlockDesc), _P, _P, _P, _P, _P, _Z, _I, _P]),

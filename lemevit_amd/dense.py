@@ -1,0 +1,357 @@
+"""Losses and metrics behind a dense-prediction head on the native path (csrc/dense.hip: lmv_dense_loss_fwd / lmv_dense_loss_bwd): the reference's
+change-detection criterion (change_detection/utils/losses.py ``hybrid_loss`` = ``FocalLoss(gamma=0)`` + ``dice_loss``, utils/metrics.py; train.py:154-260 follows
+every batch with ``torch.max`` / ``eq`` / ``sum`` and three ``.item()``, eval.py:39-66 copies every prediction map to the host for sklearn's
+``confusion_matrix``) and the segmentation heads' per-pixel cross-entropy with an ignore index and the mIoU histogram.
+
+    crit = DenseLoss(ce=1.0, dice=1.0, avg="all")               # = hybrid_loss; DenseLoss(ignore_index=255) = F.cross_entropy(ignore_index=255)
+    loss = crit(cd_preds, labels, meter=train_meter)            # a tensor or a list of predictions; 2 launches per prediction, the meter rides along
+    (loss + 0.4 * aux_crit(aux_logits, labels)).backward()      # ONE launch per prediction: grad_output is read through its pointer
+
+    meter = SegMeter(num_classes=2)
+    for img1, img2, labels in loader:
+        meter.update(model(img1, img2)[-1], labels)             # 2 launches: no allocation, no synchronisation, no copy of the prediction map
+    meter.all_reduce()
+    m = meter.compute()                                         # the only synchronisation: loss, aAcc, IoU / Acc / Precision / F1 per class, mIoU, mAcc, tn / fp / fn / tp ...
+
+One pass over NCHW logits (float32 / bfloat16, any batch and class strides) and a label map (int64 / uint8) gives, per class over the valid pixels,
+``I_k = sum p_k [y = k]``, ``P_k = sum p_k``, ``T_k = sum [y = k]`` and the focal / plain negative log-likelihood; include/lemevit_hip.h states the formulas and the
+closed-form gradient, ``reference_dense`` restates them in numpy float64 (the oracle of the tests).  A pixel whose label equals ``ignore_index`` or lies outside
+``[0, K)`` is not a sample: it contributes to no sum, count or gradient.  No floating-point atomics: two runs agree bit for bit.
+"""
+from __future__ import annotations
+
+from collections import OrderedDict
+from typing import Dict, Iterable, Optional, Sequence, Tuple, Union
+
+import numpy as np
+import torch
+from torch import Tensor, nn
+
+from . import _lib, ops
+
+__all__ = ["DenseLoss", "SegMeter", "hybrid_loss", "dice_loss", "jaccard_loss", "FocalLoss", "DenseCrossEntropy", "reference_dense", "seg_metrics"]
+
+
+def _alpha32(alpha, K: Optional[int] = None) -> Optional[Tensor]:
+    """alpha as the reference's FocalLoss builds it: a number a -> [a, 1 - a], a list -> ``torch.Tensor(list)``; float32 by definition"""
+    if alpha is None:
+        return None
+    if isinstance(alpha, (float, int)):
+        alpha = [alpha, 1 - alpha]
+    t = alpha.detach().to(torch.float32).reshape(-1) if isinstance(alpha, Tensor) else torch.tensor([float(a) for a in alpha], dtype=torch.float32)
+    if K is not None and t.numel() != K:
+        raise ValueError(f"alpha holds {t.numel()} class weights, the logits {K} classes")
+    return t.contiguous()
+
+
+class _DenseLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits: Tensor, target: Tensor, crit: "DenseLoss", meter: Optional["SegMeter"]):
+        alpha = crit._alpha_on(logits.device, logits.shape[1] if logits.dim() == 4 else None)
+        pred = conf = state = None
+        if meter is not None:
+            if logits.dim() == 4:
+                meter._check(logits.shape[1], crit.ignore_index)
+            pred, conf, state = meter._outputs(logits)
+        stats = ops.dense_loss_fwd(logits, target, crit.ignore_index, alpha, crit.gamma, crit.ce, crit.dice, crit.jaccard, crit.eps, crit.avg,
+                                   pred=pred, conf=conf, meter=state)
+        if meter is not None:
+            meter.pred = pred
+        ctx.save_for_backward(logits, target, stats)
+        ctx.crit, ctx.alpha = crit, alpha
+        crit.last = dict(ce=stats[1], dice=stats[2], jaccard=stats[3], n_valid=stats[4])
+        return stats[0]
+
+    @staticmethod
+    def backward(ctx, grad_out: Tensor):
+        logits, target, stats = ctx.saved_tensors
+        crit = ctx.crit
+        if grad_out.dtype != torch.float32:
+            grad_out = grad_out.float()
+        dl = ops.dense_loss_bwd(logits, target, stats, crit.ignore_index, ctx.alpha, crit.gamma, crit.ce, crit.dice, crit.jaccard, crit.eps, crit.avg, gout=grad_out)
+        return dl, None, None, None
+
+
+class DenseLoss(nn.Module):
+    """``loss = ce * CE + dice * Dice + jaccard * Jaccard`` of NCHW logits against a label map, under autograd.
+
+    ``crit(logits_or_list, target, meter=None)``: ``logits`` [B, K, H, W] float32 / bfloat16 with unit pixel stride (any batch / class strides, read in place;
+    channels-last logits raise), ``target`` [B, H, W] or [B, 1, H, W], int64 or uint8.  Returns a 0-dim float32 tensor.  The forward is two launches
+    (``lmv_dense_loss_fwd``), the backward ONE (``lmv_dense_loss_bwd``) that reads ``grad_output`` through its pointer, so a loss weight (``0.4 * aux``) or a later
+    sum costs no pass over ``dlogits``.  A list of predictions is evaluated one by one and summed, as the reference's ``hybrid_loss`` does.
+
+    ``ce``: the focal cross-entropy ``sum_i alpha[y] (1 - p_y)^gamma (-log p_y) / D`` with the focal factor a constant of the backward pass (the reference detaches
+    it); ``avg``: ``"valid"`` (D = the valid pixels: ``F.cross_entropy(ignore_index=)``), ``"all"`` (D = B H W: the reference's ``.mean()``) or ``"weight"``
+    (D = sum of ``alpha[y]``: ``F.cross_entropy(weight=)``).  ``dice`` / ``jaccard``: the reference's ``dice_loss`` / ``jaccard_loss`` over the valid pixels.
+    ``crit.last``: the components of the last prediction evaluated (``ce``, ``dice``, ``jaccard``, ``n_valid``) as device scalars.  ``meter``: a ``SegMeter``
+    that the same forward launch updates with the (last) prediction -- the train loop's ``cd_corrects`` for free."""
+
+    def __init__(self, ce: float = 1.0, dice: float = 0.0, jaccard: float = 0.0, gamma: float = 0.0, alpha=None, ignore_index: Optional[int] = None,
+                 avg: str = "valid", eps: float = 1e-7):
+        super().__init__()
+        self.ce, self.dice, self.jaccard, self.gamma, self.eps = float(ce), float(dice), float(jaccard), float(gamma), float(eps)
+        if not (self.ce >= 0.0 and self.dice >= 0.0 and self.jaccard >= 0.0):
+            raise ValueError(f"DenseLoss: negative loss weight ({ce}, {dice}, {jaccard})")
+        if not self.gamma >= 0.0:
+            raise ValueError(f"DenseLoss: gamma = {gamma} < 0")
+        if not self.eps > 0.0:
+            raise ValueError(f"DenseLoss: eps = {eps} <= 0")
+        if avg not in ops.DENSE_AVG:
+            raise ValueError(f"DenseLoss: avg must be one of {sorted(ops.DENSE_AVG)}, got {avg!r}")
+        self.avg = avg
+        self.ignore_index = None if ignore_index is None else int(ignore_index)
+        self.alpha = _alpha32(alpha)
+        self._alpha_dev: Dict[torch.device, Tensor] = {}
+        self.last: Dict[str, Tensor] = {}
+
+    def _alpha_on(self, device, K: Optional[int]) -> Optional[Tensor]:
+        if self.alpha is None:
+            return None
+        if K is not None and self.alpha.numel() != K:
+            raise ValueError(f"DenseLoss: alpha holds {self.alpha.numel()} class weights, the logits {K} classes")
+        a = self._alpha_dev.get(device)
+        if a is None:
+            if device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("DenseLoss: under graph capture alpha must be on the device already -- run one eager call first")
+            a = self._alpha_dev[device] = self.alpha.to(device)
+        return a
+
+    def forward(self, logits: Union[Tensor, Sequence[Tensor]], target: Tensor, meter: Optional["SegMeter"] = None) -> Tensor:
+        preds = list(logits) if isinstance(logits, (list, tuple)) else [logits]
+        if not preds:
+            raise ValueError("DenseLoss: an empty list of predictions")
+        total = None
+        for i, x in enumerate(preds):
+            loss = _DenseLossFn.apply(x, target, self, meter if i == len(preds) - 1 else None)
+            total = loss if total is None else total + loss
+        return total
+
+
+# ---- drop-ins under the reference's names and signatures (change_detection/utils/losses.py, utils/metrics.py; utils/helpers.py:214-237 binds them) ----
+_crit_cache: Dict[tuple, DenseLoss] = {}
+
+
+def _crit(**kw) -> DenseLoss:
+    key = tuple(sorted(kw.items()))
+    c = _crit_cache.get(key)
+    if c is None:
+        c = _crit_cache[key] = DenseLoss(**kw)
+    return c
+
+
+def hybrid_loss(predictions, target) -> Tensor:
+    """The reference's ``hybrid_loss``: for every prediction of the list ``FocalLoss(gamma=0, alpha=None)`` (plain cross-entropy, mean over all pixels) plus ``dice_loss``."""
+    if isinstance(predictions, Tensor):          # (the reference would iterate over the images of the batch and sum per-image losses)
+        raise TypeError("hybrid_loss: a list or tuple of [B, K, H, W] predictions expected; wrap a single prediction in a list")
+    return _crit(ce=1.0, dice=1.0, avg="all")(list(predictions), target)
+
+
+def dice_loss(logits: Tensor, true: Tensor, eps: float = 1e-7) -> Tensor:
+    return _crit(ce=0.0, dice=1.0, eps=float(eps))(logits, true)
+
+
+def jaccard_loss(logits: Tensor, true: Tensor, eps: float = 1e-7) -> Tensor:
+    return _crit(ce=0.0, jaccard=1.0, eps=float(eps))(logits, true)
+
+
+class FocalLoss(nn.Module):
+    """The reference's ``FocalLoss(gamma=0, alpha=None, size_average=True)`` on [B, K, H, W] logits: ``alpha`` a number a (-> [a, 1 - a]) or a list of class weights;
+    ``size_average=False`` returns the sum (the mean times B H W: one scalar multiply, no pass over the gradient)."""
+
+    def __init__(self, gamma=0, alpha=None, size_average=True):
+        super().__init__()
+        self.gamma, self.alpha, self.size_average = gamma, alpha, size_average
+        self.crit = DenseLoss(ce=1.0, gamma=float(gamma), alpha=alpha, avg="all")
+
+    def forward(self, input: Tensor, target: Tensor) -> Tensor:
+        loss = self.crit(input, target)
+        return loss if self.size_average else loss * float(input.shape[0] * input.shape[2] * input.shape[3])
+
+
+class DenseCrossEntropy(nn.Module):
+    """The segmentation heads' ``CrossEntropyLoss(use_sigmoid=False)``: per-pixel cross-entropy with ``ignore_index``, optional ``class_weight`` and ``loss_weight``;
+    ``avg_non_ignore=True`` averages over the valid pixels, ``False`` over all of them (the older behaviour).  ``forward(cls_score, label)``."""
+
+    def __init__(self, ignore_index: int = -100, loss_weight: float = 1.0, class_weight=None, avg_non_ignore: bool = True):
+        super().__init__()
+        self.ignore_index, self.loss_weight, self.class_weight, self.avg_non_ignore = ignore_index, loss_weight, class_weight, avg_non_ignore
+        self.crit = DenseLoss(ce=float(loss_weight), alpha=class_weight, ignore_index=ignore_index, avg="valid" if avg_non_ignore else "all")
+
+    def forward(self, cls_score: Tensor, label: Tensor, **kwargs) -> Tensor:
+        return self.crit(cls_score, label)
+
+
+# ---- the meter ------------------------------------------------------------------------------------------------------------------------------------
+def seg_metrics(conf, loss_state=(0.0, 0.0)) -> "OrderedDict[str, object]":
+    """The numbers of ``SegMeter.compute()`` from a [K, K] confusion matrix ``conf[label, prediction]`` and ``(loss_sum, n)``, on the host in float64.  A ratio with
+    a zero denominator (a class that never occurs) is NaN and is left out of the means (``nanmean``)."""
+    c = np.asarray(conf, dtype=np.float64)
+    K = c.shape[0]
+    tp, lab, prd, tot = np.diag(c), c.sum(1), c.sum(0), c.sum()
+    with np.errstate(divide="ignore", invalid="ignore"):
+        iou, acc, prec = tp / (lab + prd - tp), tp / lab, tp / prd
+        f1 = 2 * prec * acc / (prec + acc)
+        out = OrderedDict(loss=float(loss_state[0]) / float(loss_state[1]) if float(loss_state[1]) else float("nan"),
+                          aAcc=float(tp.sum() / tot) if tot else float("nan"))
+        out["IoU"], out["Acc"], out["Precision"], out["F1"] = iou, acc, prec, f1
+        out["mIoU"] = float(np.nanmean(iou)) if np.isfinite(iou).any() else float("nan")
+        out["mAcc"] = float(np.nanmean(acc)) if np.isfinite(acc).any() else float("nan")
+        if K == 2:          # eval.py:56-66: tn, fp, fn, tp = confusion_matrix(labels, preds, labels=[0, 1]).ravel()
+            tn, fp, fn, tp1 = (int(v) for v in np.asarray(conf).reshape(-1))
+            P = tp1 / (tp1 + fp) if tp1 + fp else float("nan")
+            R = tp1 / (tp1 + fn) if tp1 + fn else float("nan")
+            out.update(tn=tn, fp=fp, fn=fn, tp=tp1, precision=P, recall=R, f1=2 * P * R / (R + P) if R + P else float("nan"))
+    out["count"] = int(tot)
+    return out
+
+
+class SegMeter:
+    """Confusion matrix and mean loss of a dense evaluation, accumulated on the DEVICE: ``conf`` int64 [K, K] (``conf[label, prediction]``) and ``loss``
+    float64 ``[sum of -log p_y, valid pixels]``.
+
+    ``update(logits, target)``: the forward pass of ``lmv_dense_loss_fwd`` in metrics mode (two launches, no synchronisation, no allocation after the first call
+    for a shape); ``pred`` keeps the last batch's argmax map (uint8 [B, H, W]).  ``DenseLoss(...)(x, y, meter=m)`` leaves the same state from the loss's own pass.
+    Capture: ``update`` can be captured once the state and the buffers of that shape exist (one eager ``update``, then ``reset()``); under capture it raises when
+    they do not.  ``compute()`` is the only synchronisation."""
+
+    def __init__(self, num_classes: int, ignore_index: Optional[int] = None):
+        self.num_classes = int(num_classes)
+        if not 2 <= self.num_classes <= _lib.DENSE_MAX_CLASSES:
+            raise ValueError(f"SegMeter: num_classes = {num_classes} outside 2 .. {_lib.DENSE_MAX_CLASSES}")
+        self.ignore_index = None if ignore_index is None else int(ignore_index)
+        self.conf: Optional[Tensor] = None
+        self.loss: Optional[Tensor] = None
+        self.pred: Optional[Tensor] = None
+        self._buffers: Dict[tuple, Tuple[Tensor, Tensor, Tensor]] = {}
+
+    @property
+    def state(self) -> Tuple[Optional[Tensor], Optional[Tensor]]:
+        return self.conf, self.loss
+
+    def _check(self, K: int, ignore_index: Optional[int]) -> None:
+        if K != self.num_classes:
+            raise ValueError(f"SegMeter: {K} classes in the logits, the meter counts {self.num_classes}")
+        if ignore_index != self.ignore_index:
+            raise ValueError(f"SegMeter: the loss ignores label {ignore_index}, the meter {self.ignore_index} -- one pass serves both, they must agree")
+
+    def _outputs(self, logits: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
+        """(pred, conf, loss state) for a batch of this shape; allocated on first use, never under capture"""
+        if logits.dim() != 4:
+            raise ValueError(f"SegMeter: [B, K, H, W] logits expected, got {tuple(logits.shape)}")
+        if not logits.is_cuda:
+            raise RuntimeError("lemevit_amd: tensors must be on the GPU (no CPU fallback exists)")
+        capturing = torch.cuda.is_current_stream_capturing()
+        dev = logits.device
+        if self.conf is None:
+            if capturing:
+                raise RuntimeError("SegMeter: under graph capture the state must exist -- run one eager update first")
+            K = self.num_classes
+            self.conf, self.loss = torch.zeros((K, K), device=dev, dtype=torch.int64), torch.zeros((2,), device=dev, dtype=torch.float64)
+        B, K, H, W = logits.shape
+        key = (B, H, W, dev)
+        buf = self._buffers.get(key)
+        if buf is None:
+            if capturing:
+                raise RuntimeError("SegMeter: under graph capture the buffers must exist for this batch shape -- run one eager update first")
+            buf = (torch.empty((B, H, W), device=dev, dtype=torch.uint8), torch.empty((ops.dense_stats_floats(K),), device=dev, dtype=torch.float32),
+                   ops.dense_workspace(B, K, H * W, dev))
+            self._buffers[key] = buf
+        return buf[0], self.conf, self.loss
+
+    def update(self, logits: Tensor, target: Tensor) -> None:
+        if logits.dim() == 4:
+            self._check(logits.shape[1], self.ignore_index)
+        pred, conf, loss = self._outputs(logits)
+        _, stats, ws = self._buffers[(logits.shape[0], logits.shape[2], logits.shape[3], logits.device)]
+        ops.dense_loss_fwd(logits.detach(), target, self.ignore_index, workspace=ws, stats=stats, pred=pred, conf=conf, meter=loss)
+        self.pred = pred
+
+    def merge(self, states: Iterable[Tuple[Tensor, Tensor]]) -> "SegMeter":
+        """Adds other meters' ``state`` pairs ``(conf int64 [K, K], loss float64 [2])``, on any device, into this one: what ``all_reduce`` does across ranks."""
+        K = self.num_classes
+        for conf, loss in states:
+            if conf.dtype != torch.int64 or tuple(conf.shape) != (K, K) or loss.dtype != torch.float64 or tuple(loss.shape) != (2,):
+                raise TypeError(f"SegMeter.merge: (int64 [{K}, {K}], float64 [2]) states expected, got {tuple(conf.shape)} {conf.dtype}, {tuple(loss.shape)} {loss.dtype}")
+            if self.conf is None:
+                self.conf, self.loss = torch.zeros_like(conf), torch.zeros_like(loss)
+            self.conf += conf.to(self.conf.device)
+            self.loss += loss.to(self.loss.device)
+        return self
+
+    def all_reduce(self, group=None) -> None:
+        """ONE sum all-reduce per state tensor, once per evaluation; a no-op outside a process group."""
+        import torch.distributed as dist
+        if dist.is_available() and dist.is_initialized() and self.conf is not None:
+            dist.all_reduce(self.conf, op=dist.ReduceOp.SUM, group=group)
+            dist.all_reduce(self.loss, op=dist.ReduceOp.SUM, group=group)
+
+    def compute(self) -> "OrderedDict[str, object]":
+        """The only host synchronisation: ``loss`` (mean -log p_y), ``aAcc``, per-class arrays ``IoU``, ``Acc`` (recall), ``Precision``, ``F1``, their ``nanmean``s
+        ``mIoU`` / ``mAcc``, ``count``; with two classes also ``tn, fp, fn, tp, precision, recall, f1`` of class 1 (eval.py:56-66)."""
+        if self.conf is None:
+            raise RuntimeError("SegMeter.compute: nothing has been accumulated")
+        return seg_metrics(self.conf.cpu().numpy(), self.loss.cpu().tolist())
+
+    def reset(self) -> None:
+        if self.conf is not None:
+            self.conf.zero_()
+            self.loss.zero_()
+
+
+# ---- the oracle -----------------------------------------------------------------------------------------------------------------------------------
+def reference_dense(logits, labels, ce: float = 1.0, dice: float = 0.0, jaccard: float = 0.0, gamma: float = 0.0, alpha=None, ignore_index: Optional[int] = None,
+                    avg: str = "valid", eps: float = 1e-7, gout: float = 1.0) -> dict:
+    """The host restatement of ``lmv_dense_loss_fwd`` / ``lmv_dense_loss_bwd`` in numpy float64 -- the oracle of the tests.  ``logits`` [B, K, H, W] (a float32 /
+    bfloat16 / float64 tensor or an array: evaluated ON THE ALREADY ROUNDED values), ``labels`` [B, H, W] / [B, 1, H, W] of any integer type, ``alpha`` passed
+    through float32.  Returns ``dict(loss, ce, dice, jaccard, n_valid, D, inv_D, I, P, T, u, v, stats (float64 [6 + 5 K], the device layout), dlogits
+    (float64 [B, K, H, W]), pred (uint8 [B, H, W]), conf (int64 [K, K]), nll_sum)``."""
+    if isinstance(logits, Tensor):
+        x = logits.detach().cpu().to(torch.float64).numpy()
+    else:
+        x = np.asarray(logits, dtype=np.float64)
+    y = labels.detach().cpu().numpy() if isinstance(labels, Tensor) else np.asarray(labels)
+    if x.ndim != 4 or avg not in ops.DENSE_AVG:
+        raise ValueError("reference_dense: bad arguments")
+    B, K, H, W = x.shape
+    HW = H * W
+    x = x.reshape(B, K, HW)
+    y = y.astype(np.int64).reshape(B, HW)
+    valid = (y >= 0) & (y < K)
+    if ignore_index is not None:
+        valid &= y != int(ignore_index)
+    ys = np.where(valid, y, 0)
+    a = np.ones(K) if alpha is None else _alpha32(alpha, K).numpy().astype(np.float64)
+    with np.errstate(all="ignore"):
+        mx = x.max(1, keepdims=True)
+        e = np.exp(x - mx)
+        se = e.sum(1, keepdims=True)
+        p = e / se
+        idx = ys[:, None, :]
+        nll = np.log(se[:, 0]) - np.take_along_axis(x - mx, idx, 1)[:, 0]
+        py = np.take_along_axis(p, idx, 1)[:, 0]
+        f = a[ys] * ((1.0 - py) ** gamma if gamma > 0 else 1.0)
+    onehot = (idx == np.arange(K)[None, :, None]) & valid[:, None, :]
+    vm = valid[:, None, :]
+    I, P, T = (p * onehot).sum((0, 2)), (p * vm).sum((0, 2)), onehot.sum((0, 2)).astype(np.float64)
+    n_valid = float(valid.sum())
+    D = {"valid": n_valid, "all": float(B * HW), "weight": float((a * T).sum())}[avg]
+    inv_D = 1.0 / D if D > 0 else 0.0
+    nll_v = np.where(valid, nll, 0.0)
+    ce_v = float((np.where(valid, f * nll, 0.0)).sum() * inv_D)
+    C, U = P + T + eps, P + T - I + eps
+    dice_v, jac_v = float(1.0 - (2.0 * I / C).mean()), float(1.0 - (I / U).mean())
+    u = -dice * 2.0 / (K * C) - jaccard * (1.0 / U + I / U ** 2) / K
+    v = dice * 2.0 * I / (K * C ** 2) + jaccard * I / (K * U ** 2)
+    g = u[None, :, None] * onehot + v[None, :, None]
+    s = (p * g).sum(1, keepdims=True)
+    dz = gout * (p * (g - s) + ce * np.where(valid, f, 0.0)[:, None, :] * (p - onehot) * inv_D) * vm
+    # the argmax rule: the first index of the maximum, a NaN greater than every number, -0 == +0
+    nanm = np.isnan(x)
+    with np.errstate(all="ignore"):
+        pred = np.where(nanm.any(1), nanm.argmax(1), np.where(nanm, -np.inf, x).argmax(1)).astype(np.uint8)
+    conf = np.zeros((K, K), dtype=np.int64)
+    np.add.at(conf, (y[valid], pred[valid].astype(np.int64)), 1)
+    loss = ce * ce_v + dice * dice_v + jaccard * jac_v
+    stats = np.concatenate([[loss, ce_v, dice_v, jac_v, n_valid, inv_D], u, v, I, P, T])
+    return dict(loss=loss, ce=ce_v, dice=dice_v, jaccard=jac_v, n_valid=int(n_valid), D=D, inv_D=inv_D, I=I, P=P, T=T.astype(np.int64), u=u, v=v, stats=stats,
+                dlogits=dz.reshape(B, K, H, W), pred=pred.reshape(B, H, W), conf=conf, nll_sum=float(nll_v.sum()))

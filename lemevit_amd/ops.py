@@ -1010,6 +1010,116 @@ def meter_add(state: Tensor, row_loss: Optional[Tensor] = None, rank: Optional[T
 
 
 # -------------------------------------------------------------------------------------------
+# dense-prediction losses and metrics (csrc/dense.hip; lemevit_amd.dense holds the user-facing names)
+# -------------------------------------------------------------------------------------------
+DENSE_AVG = {"valid": _lib.DENSE_AVG_VALID, "all": _lib.DENSE_AVG_ALL, "weight": _lib.DENSE_AVG_WEIGHT}
+
+
+def dense_stats_floats(K: int) -> int:
+    """LMV_DENSE_STATS_FLOATS(K): ``loss, ce, dice, jaccard, n_valid, 1 / D``, then ``u[K], v[K], I[K], P[K], T[K]``."""
+    return _lib.DENSE_STATS_HEAD + 5 * int(K)
+
+
+def dense_workspace(B: int, K: int, HW: int, device) -> Tensor:
+    """A workspace of lmv_dense_loss_workspace_bytes(B, K, HW) for ``dense_loss_fwd`` (one row of partial sums per workgroup of the pass)."""
+    n = lib.lmv_dense_loss_workspace_bytes(int(B), int(K), int(HW))
+    if n == 0:
+        raise ValueError(f"dense_workspace: bad shape B = {B}, K = {K}, H W = {HW} (B >= 1, 2 <= K <= {_lib.DENSE_MAX_CLASSES}, B H W < 2^31)")
+    return torch.empty((n,), device=device, dtype=torch.uint8)
+
+
+def _dense_args(fn: str, logits: Tensor, labels: Tensor, ignore_index, alpha, gamma, w_ce, w_dice, w_jac, eps, avg):
+    if logits.dim() != 4:
+        raise ValueError(f"{fn}: [B, K, H, W] logits expected, got {tuple(logits.shape)}")
+    if not logits.is_cuda or not labels.is_cuda:
+        raise RuntimeError("lemevit_amd: tensors must be on the GPU (no CPU fallback exists)")
+    code = dtype_code(logits)
+    B, K, H, W = logits.shape
+    HW = H * W
+    if not 2 <= K <= _lib.DENSE_MAX_CLASSES:
+        raise ValueError(f"{fn}: K = {K} classes outside 2 .. {_lib.DENSE_MAX_CLASSES}")
+    if B < 1 or HW < 1 or B * HW >= 1 << 31:
+        raise ValueError(f"{fn}: bad shape {tuple(logits.shape)} (B >= 1, H W >= 1, B H W < 2^31)")
+    if (W > 1 and logits.stride(3) != 1) or (H > 1 and logits.stride(2) != W):
+        raise ValueError(f"{fn}: the logits must have unit pixel stride (NCHW planes; channels-last logits are not supported)")
+    sc = logits.stride(1)
+    sb = logits.stride(0) if B > 1 else (K - 1) * sc + HW
+    if sc < HW or sb < (K - 1) * sc + HW:
+        raise ValueError(f"{fn}: overlapping class planes or images (strides {logits.stride()})")
+    if labels.dtype not in (torch.int64, torch.uint8):
+        raise TypeError(f"{fn}: labels must be int64 or uint8, got {labels.dtype}")
+    if tuple(labels.shape) not in ((B, H, W), (B, 1, H, W), (B, HW)) or labels.device != logits.device:
+        raise ValueError(f"{fn}: labels must be [B, H, W], [B, 1, H, W] or [B, H W] on the logits' device, got {tuple(labels.shape)}")
+    if not labels.is_contiguous():
+        raise ValueError(f"{fn}: the label map must be contiguous")
+    if alpha is not None and (alpha.dtype != torch.float32 or tuple(alpha.shape) != (K,) or alpha.device != logits.device or not alpha.is_contiguous()):
+        raise TypeError(f"{fn}: alpha must be a contiguous float32 vector [{K}] on the logits' device")
+    if not (float(w_ce) >= 0.0 and float(w_dice) >= 0.0 and float(w_jac) >= 0.0):
+        raise ValueError(f"{fn}: negative loss weight ({w_ce}, {w_dice}, {w_jac})")
+    if not float(gamma) >= 0.0:
+        raise ValueError(f"{fn}: gamma = {gamma} < 0")
+    if not float(eps) > 0.0:
+        raise ValueError(f"{fn}: eps = {eps} <= 0")
+    if avg not in DENSE_AVG:
+        raise ValueError(f"{fn}: avg must be one of {sorted(DENSE_AVG)}, got {avg!r}")
+    ign = -1 if ignore_index is None else int(ignore_index)
+    head = (logits.data_ptr(), code, sb, sc, B, K, HW, labels.data_ptr(), _lib.DENSE_LABEL_I64 if labels.dtype == torch.int64 else _lib.DENSE_LABEL_U8, ign,
+            None if alpha is None else alpha.data_ptr(), float(gamma), float(w_ce), float(w_dice), float(w_jac), float(eps), DENSE_AVG[avg])
+    return head, B, K, HW
+
+
+def dense_loss_fwd(logits: Tensor, labels: Tensor, ignore_index: Optional[int] = None, alpha: Optional[Tensor] = None, gamma: float = 0.0, w_ce: float = 1.0,
+                   w_dice: float = 0.0, w_jac: float = 0.0, eps: float = 1e-7, avg: str = "valid", workspace: Optional[Tensor] = None, stats: Optional[Tensor] = None,
+                   pred: Optional[Tensor] = None, conf: Optional[Tensor] = None, meter: Optional[Tensor] = None) -> Tensor:
+    """lmv_dense_loss_fwd (two launches): ``logits`` [B, K, H, W] float32 / bfloat16 with unit pixel stride and ANY batch / class strides (a ``buf[:, 1:K+1]`` view is
+    read in place), ``labels`` [B, H, W] / [B, 1, H, W] int64 or uint8.  A pixel whose label equals ``ignore_index`` or lies outside ``[0, K)`` is ignored.  Returns
+    ``stats``, float32 [6 + 5 K]: ``loss, ce, dice, jaccard, n_valid, 1 / D, u[K], v[K], I[K], P[K], T[K]`` (include/lemevit_hip.h has the formulas).  Optional
+    outputs, written by the same pass: ``pred`` uint8 [B, H W] (the argmax of every pixel), ``conf`` int64 [K, K] (``conf[y, pred] += 1``, persistent) and ``meter``
+    float64 [2] (``+= sum -log p_y, n_valid``, persistent).  ``workspace`` (``dense_workspace``) and ``stats``: caller-supplied buffers, so that a captured call
+    allocates nothing; None: allocated here.  Deterministic: no floating-point atomics."""
+    head, B, K, HW = _dense_args("dense_loss_fwd", logits, labels, ignore_index, alpha, gamma, w_ce, w_dice, w_jac, eps, avg)
+    dev = logits.device
+    need = lib.lmv_dense_loss_workspace_bytes(B, K, HW)
+    if workspace is None:
+        workspace = _workspace(need, dev)
+    elif workspace.device != dev or not workspace.is_contiguous() or workspace.numel() * workspace.element_size() < need:
+        raise ValueError(f"dense_loss_fwd: the workspace must hold {need} bytes on the logits' device (ops.dense_workspace)")
+    if stats is None:
+        stats = torch.empty((dense_stats_floats(K),), device=dev, dtype=torch.float32)
+    elif stats.dtype != torch.float32 or tuple(stats.shape) != (dense_stats_floats(K),) or stats.device != dev or not stats.is_contiguous():
+        raise TypeError(f"dense_loss_fwd: stats must be a contiguous float32 vector [{dense_stats_floats(K)}] on the logits' device")
+    if pred is not None and (pred.dtype != torch.uint8 or pred.numel() != B * HW or pred.device != dev or not pred.is_contiguous()):
+        raise TypeError(f"dense_loss_fwd: pred must be a contiguous uint8 tensor of {B} x {HW} entries on the logits' device")
+    if conf is not None and (conf.dtype != torch.int64 or tuple(conf.shape) != (K, K) or conf.device != dev or not conf.is_contiguous()):
+        raise TypeError(f"dense_loss_fwd: conf must be a contiguous int64 matrix [{K}, {K}] on the logits' device")
+    if meter is not None and (meter.dtype != torch.float64 or tuple(meter.shape) != (2,) or meter.device != dev):
+        raise TypeError("dense_loss_fwd: meter must be a float64 vector [2] on the logits' device")
+    check(lib.lmv_dense_loss_fwd(*head, workspace.data_ptr(), workspace.numel() * workspace.element_size(), stats.data_ptr(), _ptr(pred), _ptr(conf), _ptr(meter),
+                                 _stream()), "lmv_dense_loss_fwd")
+    return stats
+
+
+def dense_loss_bwd(logits: Tensor, labels: Tensor, stats: Tensor, ignore_index: Optional[int] = None, alpha: Optional[Tensor] = None, gamma: float = 0.0,
+                   w_ce: float = 1.0, w_dice: float = 0.0, w_jac: float = 0.0, eps: float = 1e-7, avg: str = "valid", gout: Optional[Tensor] = None,
+                   out: Optional[Tensor] = None) -> Tensor:
+    """lmv_dense_loss_bwd (one launch): ``d loss / d logits`` times ``gout`` from the ``stats`` of the forward call with the same arguments; ``gout`` is a float32
+    GPU scalar read through its pointer (None: 1).  Returns ``dlogits``, contiguous [B, K, H, W] in the logits dtype, every element written once (``out``: a buffer
+    to write instead of a new one); ignored pixels get exact zeros."""
+    head, B, K, HW = _dense_args("dense_loss_bwd", logits, labels, ignore_index, alpha, gamma, w_ce, w_dice, w_jac, eps, avg)
+    dev = logits.device
+    if stats.dtype != torch.float32 or tuple(stats.shape) != (dense_stats_floats(K),) or stats.device != dev or not stats.is_contiguous():
+        raise TypeError(f"dense_loss_bwd: stats must be a contiguous float32 vector [{dense_stats_floats(K)}] on the logits' device")
+    if gout is not None and (gout.dtype != torch.float32 or gout.numel() != 1 or gout.device != dev):
+        raise TypeError("dense_loss_bwd: gout must be a float32 scalar tensor on the logits' device")
+    if out is None:
+        out = torch.empty(tuple(logits.shape), device=dev, dtype=logits.dtype)
+    elif out.dtype != logits.dtype or tuple(out.shape) != tuple(logits.shape) or out.device != dev or not out.is_contiguous():
+        raise TypeError("dense_loss_bwd: out must be a contiguous tensor of the logits' shape, dtype and device")
+    check(lib.lmv_dense_loss_bwd(*head, stats.data_ptr(), None if gout is None else gout.data_ptr(), out.data_ptr(), _stream()), "lmv_dense_loss_bwd")
+    return out
+
+
+# -------------------------------------------------------------------------------------------
 # A run of "S" blocks as one persistent launch (csrc/sstage.hip; inference, bf16)
 # -------------------------------------------------------------------------------------------
 def sstage_supported(C_: int, heads: int, hidden: int, H: int, W: int, M: int, dtype: torch.dtype) -> bool:
