@@ -33,7 +33,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import ops
-from .blocks import BLOCK_LN_EPS, PARAM_NAMES, attention_state, block_backward, block_forward
+from .blocks import ATTN_BWD, ATTN_FWD, BLOCK_LN_EPS, PARAM_NAMES, attention_state, block_backward, block_forward
 from .ops import Prob
 
 Tensor = torch.Tensor
@@ -1173,13 +1173,6 @@ def run_block(kind: str, x: Tensor, c: Tensor, H: int, W: int, params: "OrderedD
 
 
 # ------------------------------------------------------------------------------------------------
-# attention modules (parameter containers with the reference's names + inference forward)
-# ------------------------------------------------------------------------------------------------
-def _lin_probs(pairs, dtype):
-    return [Prob(a, compute_copy(m.weight, dtype), o, bias=compute_copy(m.bias, torch.float32)) for a, m, o in pairs]
-
-
-# ------------------------------------------------------------------------------------------------
 # a whole stage of "S" blocks as one persistent launch (csrc/sstage.hip; inference)
 # ------------------------------------------------------------------------------------------------
 _SSTAGE = os.environ.get("LMV_SSTAGE", "1") != "0"        # 0: the per-block inference schedule (A/B runs)
@@ -1267,248 +1260,115 @@ def _needs_grad(*ts) -> bool:
     return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in ts)
 
 
+def _attn_module_run(kind: str, x: Tensor, c: Optional[Tensor], params, save: bool):
+    """The attention half of kind `kind` (lemevit_amd/blocks.py) on a module's own data: no norm1, no residual.  Returns (outputs, saved set, operands)."""
+    cd = x.dtype
+    names = [n for n in PARAM_NAMES[kind] if n.startswith("attn.")]          # the module's (weight, bias) pairs in declaration order
+    P = {n: compute_copy(p, cd if _is_matrix(n) else torch.float32) for n, p in zip(names, params)}
+    ts = [x.contiguous()] if c is None else [x.contiguous(), c.contiguous()]
+    outs, saved = ATTN_FWD[kind](P, ts, None, save)
+    return outs, saved, P
+
+
 class _AttnModuleFn(torch.autograd.Function):
     """kind "S": (x) -> x'; "D" / "D2": (x, c) -> (x', c'); "C": (x, c) -> c'.  params: (weight, bias) of the module's Linears in declaration order."""
 
     @staticmethod
     def forward(ctx, kind, x, c, *params):
         new_training_pass()                      # parameters may have been updated in place since the last call (see derived)
-        cd = x.dtype
-        x = x.contiguous()
-        c = None if c is None else c.contiguous()
-        W = [compute_copy(params[2 * i], cd) for i in range(len(params) // 2)]
-        Bv = [compute_copy(params[2 * i + 1], torch.float32) for i in range(len(params) // 2)]
-        C = x.shape[-1]
-        emp = lambda like, cols: torch.empty(like.shape[:-1] + (cols,), device=like.device, dtype=cd)
-        if kind == "S":
-            qkv = emp(x, 3 * C)
-            ops.linear_fwd([Prob(x, W[0], qkv, bias=Bv[0])], 3 * C, C)
-            ao, lse = ops.attn_fwd((qkv, 0), (qkv, C), (qkv, 2 * C), C, ops.SDPA_SCALE, want_lse=True)
-            out = torch.empty_like(x)
-            ops.linear_fwd([Prob(ao, W[1], out, bias=Bv[1])], C, C)
-            saved, outs = (x, qkv, ao, lse), (out,)
-        elif kind in ("D", "D2"):
-            N, M = x.shape[1], c.shape[1]
-            sx, sc = ops.dca_scales(N, M, C)
-            wd = 3 * C if kind == "D" else 2 * C
-            p1, p2 = emp(x, wd), emp(c, wd)
-            ops.linear_fwd([Prob(x, W[0], p1, bias=Bv[0]), Prob(c, W[1], p2, bias=Bv[1])], wd, C)
-            if kind == "D":      # models/lemevit.py:297,300
-                aox, lsex = ops.attn_fwd((p1, 0), (p2, C), (p2, 2 * C), C, sx, want_lse=True)
-                aoc, lsec = ops.attn_fwd((p2, 0), (p1, C), (p1, 2 * C), C, sc, want_lse=True)
-            else:                # models/lemevit.py:402,405: the same q / k serve both directions
-                aox, lsex = ops.attn_fwd((p1, 0), (p2, 0), (p2, C), C, sx, want_lse=True)
-                aoc, lsec = ops.attn_fwd((p2, 0), (p1, 0), (p1, C), C, sc, want_lse=True)
-            ox, oc = torch.empty_like(x), torch.empty_like(c)
-            ops.linear_fwd([Prob(aox, W[2], ox, bias=Bv[2]), Prob(aoc, W[3], oc, bias=Bv[3])], C, C)
-            saved, outs = (x, c, p1, p2, aox, aoc, lsex, lsec), (ox, oc)
-        else:                    # "C": q from the meta tokens, kv from the image tokens (models/lemevit.py:477-486)
-            q, kv = torch.empty_like(c), emp(x, 2 * C)
-            ops.linear_fwd([Prob(c, W[0], q, bias=Bv[0])], C, C)
-            ops.linear_fwd([Prob(x, W[1], kv, bias=Bv[1])], 2 * C, C)
-            ao, lse = ops.attn_fwd((q, 0), (kv, 0), (kv, C), C, ops.SDPA_SCALE, want_lse=True)
-            out = torch.empty_like(c)
-            ops.linear_fwd([Prob(ao, W[2], out, bias=Bv[2])], C, C)
-            saved, outs = (x, c, q, kv, ao, lse), (out,)
-        ctx.kind, ctx.W, ctx.acts, ctx.shapes = kind, W, saved, [(p.shape, p.dtype) for p in params]
+        outs, ctx.acts, ctx.P = _attn_module_run(kind, x, c, params, save=True)
+        ctx.kind, ctx.shapes = kind, [(p.shape, p.dtype) for p in params]
         ctx.out_like = [(o.shape, o.dtype, o.device) for o in outs]
-        return outs if len(outs) > 1 else outs[0]
+        return tuple(outs) if len(outs) > 1 else outs[0]
 
     @staticmethod
     def backward(ctx, *gs):
-        kind, W, S = ctx.kind, ctx.W, ctx.acts
         # (an output the caller did not use arrives as None: its gradient is zero)
         gs = [torch.zeros(sh, dtype=dt, device=dv) if g is None else g.contiguous() for g, (sh, dt, dv) in zip(gs, ctx.out_like)]
-        dev = gs[0].device
-        G = [torch.zeros(s, device=dev, dtype=torch.float32) for s, _ in ctx.shapes]      # fp32 accumulators: (weight, bias) pairs
-        dw = lambda probs, N, K: ops.linear_dw(probs, N, K)
-        if kind == "S":
-            x, qkv, ao, lse = S
-            C = x.shape[-1]
-            dw([Prob(gs[0], ao, G[2], bias_grad=G[3])], C, C)
-            dao = torch.empty_like(x)
-            ops.linear_dx([Prob(gs[0], W[1], dao)], C, C)
-            dqkv = torch.empty_like(qkv)
-            ops.attn_bwd((qkv, 0), (qkv, C), (qkv, 2 * C), ao, lse, dao, (dqkv, 0), (dqkv, C), (dqkv, 2 * C), C, ops.SDPA_SCALE)
-            dw([Prob(dqkv, x, G[0], bias_grad=G[1])], 3 * C, C)
-            dx = torch.empty_like(x)
-            ops.linear_dx([Prob(dqkv, W[0], dx)], 3 * C, C)
-            dc = None
-        elif kind in ("D", "D2"):
-            x, c, p1, p2, aox, aoc, lsex, lsec = S
-            C, N, M = x.shape[-1], x.shape[1], c.shape[1]
-            sx, sc = ops.dca_scales(N, M, C)
-            wd = p1.shape[-1]
-            dw([Prob(gs[0], aox, G[4], bias_grad=G[5]), Prob(gs[1], aoc, G[6], bias_grad=G[7])], C, C)
-            daox, daoc = torch.empty_like(x), torch.empty_like(c)
-            ops.linear_dx([Prob(gs[0], W[2], daox), Prob(gs[1], W[3], daoc)], C, C)
-            d1, d2 = torch.empty_like(p1), torch.empty_like(p2)
-            if kind == "D":
-                ops.attn_bwd((p1, 0), (p2, C), (p2, 2 * C), aox, lsex, daox, (d1, 0), (d2, C), (d2, 2 * C), C, sx)
-                ops.attn_bwd((p2, 0), (p1, C), (p1, 2 * C), aoc, lsec, daoc, (d2, 0), (d1, C), (d1, 2 * C), C, sc)
-            else:                # k is the query of the second direction, q its key: their gradients add to the first direction's
-                ops.attn_bwd((p1, 0), (p2, 0), (p2, C), aox, lsex, daox, (d1, 0), (d2, 0), (d2, C), C, sx)
-                t2, t1 = torch.empty_like(p2), torch.empty_like(p1)
-                ops.attn_bwd((p2, 0), (p1, 0), (p1, C), aoc, lsec, daoc, (t2, 0), (t1, 0), (d1, C), C, sc)
-                d1[..., :C] += t1[..., :C]
-                d2[..., :C] += t2[..., :C]
-            dw([Prob(d1, x, G[0], bias_grad=G[1]), Prob(d2, c, G[2], bias_grad=G[3])], wd, C)
-            dx, dc = torch.empty_like(x), torch.empty_like(c)
-            ops.linear_dx([Prob(d1, W[0], dx), Prob(d2, W[1], dc)], wd, C)
-        else:
-            x, c, q, kv, ao, lse = S
-            C = x.shape[-1]
-            dw([Prob(gs[0], ao, G[4], bias_grad=G[5])], C, C)
-            dao = torch.empty_like(c)
-            ops.linear_dx([Prob(gs[0], W[2], dao)], C, C)
-            dq, dkv = torch.empty_like(q), torch.empty_like(kv)
-            ops.attn_bwd((q, 0), (kv, 0), (kv, C), ao, lse, dao, (dq, 0), (dkv, 0), (dkv, C), C, ops.SDPA_SCALE)
-            dw([Prob(dq, c, G[0], bias_grad=G[1])], C, C)
-            dw([Prob(dkv, x, G[2], bias_grad=G[3])], 2 * C, C)
-            dc, dx = torch.empty_like(c), torch.empty_like(x)
-            ops.linear_dx([Prob(dq, W[0], dc)], C, C)
-            ops.linear_dx([Prob(dkv, W[1], dx)], 2 * C, C)
-        grads = [g.to(dt) for g, (_, dt) in zip(G, ctx.shapes)]
-        return (None, dx, dc) + tuple(grads)
+        G = {n: torch.zeros(s, device=gs[0].device, dtype=torch.float32) for n, (s, _) in zip(ctx.P, ctx.shapes)}      # fp32 accumulators
+        # weight gradients in line on the current stream: nothing is left on the side stream, no join is deferred
+        din = ATTN_BWD[ctx.kind](ctx.P, G, ctx.acts, gs, None, dw=ops.linear_dw)
+        grads = [g.to(dt) for g, (_, dt) in zip(G.values(), ctx.shapes)]
+        return (None, din[0], din[1] if len(din) > 1 else None) + tuple(grads)
 
 
-def _attn_params(*linears):
-    out = []
-    for m in linears:
-        out += [m.weight, m.bias]
-    return out
+class _AttentionModule(nn.Module):
+    """What the four attention modules share.  `_kind` selects the attention half; the Linears are declared in the order of blocks.PARAM_NAMES[_kind]."""
+    _kind: str
 
-
-class StandardAttention(nn.Module):
-    """models/lemevit.py:156-217.  forward(x [B,L,C]) -> [B,L,C] (inference path; training runs inside the block node)."""
-
-    def __init__(self, dim, num_heads, scale=None, bias=False, attn_drop=0.0, proj_drop=0.0, **kwargs):
+    def __init__(self, dim: int, num_heads: int):
         super().__init__()
         assert dim % num_heads == 0, f"dim {dim} not divisible by num_heads {num_heads}"
         assert dim // num_heads == ops.HEAD_DIM, "lemevit_amd kernels are built for head_dim 32 (all registered variants)"
         self.num_heads = num_heads
-        self.qkv = nn.Linear(dim, 3 * dim)
-        self.proj = nn.Linear(dim, dim)
         self.attn_viz = nn.Identity()          # models/lemevit.py:181,249,355,451: the hook point of LeMeViT.attention_maps
 
-    def forward(self, x):
-        P = _attn_params(self.qkv, self.proj)
-        if _needs_grad(x, *P):
-            return _AttnModuleFn.apply("S", x, None, *P)
+    def _run(self, x, c=None):
+        params = list(self.parameters())
+        if _needs_grad(x, c, *params):
+            return _AttnModuleFn.apply(self._kind, x, c, *params)
         with torch.no_grad():
-            return self._forward_nograd(x)
-
-    def _forward_nograd(self, x):
-        x = x.contiguous()
-        C = x.shape[-1]
-        qkv = torch.empty(x.shape[:-1] + (3 * C,), device=x.device, dtype=x.dtype)
-        ops.linear_fwd(_lin_probs([(x, self.qkv, qkv)], x.dtype), 3 * C, C)
-        ao, _ = ops.attn_fwd((qkv, 0), (qkv, C), (qkv, 2 * C), C, ops.SDPA_SCALE)
-        out = torch.empty_like(x)
-        ops.linear_fwd(_lin_probs([(ao, self.proj, out)], x.dtype), C, C)
-        return out
+            outs = _attn_module_run(self._kind, x, c, params, save=False)[0]
+        return tuple(outs) if len(outs) > 1 else outs[0]
 
 
-class DualCrossAttention(nn.Module):
-    """models/lemevit.py:220-324.  forward(x [B,N,C], c [B,M,C]) -> (x', c')."""
+class StandardAttention(_AttentionModule):
+    """models/lemevit.py:156-217.  forward(x [B,L,C]) -> [B,L,C]."""
+    _kind = "S"
 
     def __init__(self, dim, num_heads, scale=None, bias=False, attn_drop=0.0, proj_drop=0.0, **kwargs):
-        super().__init__()
-        assert dim % num_heads == 0 and dim // num_heads == ops.HEAD_DIM
-        self.num_heads = num_heads
+        super().__init__(dim, num_heads)
+        self.qkv = nn.Linear(dim, 3 * dim)
+        self.proj = nn.Linear(dim, dim)
+
+    def forward(self, x):
+        return self._run(x)
+
+
+class DualCrossAttention(_AttentionModule):
+    """models/lemevit.py:220-324.  forward(x [B,N,C], c [B,M,C]) -> (x', c')."""
+    _kind = "D"
+
+    def __init__(self, dim, num_heads, scale=None, bias=False, attn_drop=0.0, proj_drop=0.0, **kwargs):
+        super().__init__(dim, num_heads)
         self.scale = scale or dim ** (-0.5)
         self.qkv1 = nn.Linear(dim, 3 * dim)
         self.qkv2 = nn.Linear(dim, 3 * dim)
         self.proj_x = nn.Linear(dim, dim)
         self.proj_c = nn.Linear(dim, dim)
-        self.attn_viz = nn.Identity()          # models/lemevit.py:181,249,355,451: the hook point of LeMeViT.attention_maps
 
     def forward(self, x, c):
-        P = _attn_params(self.qkv1, self.qkv2, self.proj_x, self.proj_c)
-        if _needs_grad(x, c, *P):
-            return _AttnModuleFn.apply("D", x, c, *P)
-        with torch.no_grad():
-            return self._forward_nograd(x, c)
-
-    def _forward_nograd(self, x, c):
-        x, c = x.contiguous(), c.contiguous()
-        C, N, M = x.shape[-1], x.shape[1], c.shape[1]
-        sx, sc = ops.dca_scales(N, M, C)
-        q1 = torch.empty(x.shape[:-1] + (3 * C,), device=x.device, dtype=x.dtype)
-        q2 = torch.empty(c.shape[:-1] + (3 * C,), device=x.device, dtype=x.dtype)
-        ops.linear_fwd(_lin_probs([(x, self.qkv1, q1), (c, self.qkv2, q2)], x.dtype), 3 * C, C)
-        aox, _ = ops.attn_fwd((q1, 0), (q2, C), (q2, 2 * C), C, sx)
-        aoc, _ = ops.attn_fwd((q2, 0), (q1, C), (q1, 2 * C), C, sc)
-        ox, oc = torch.empty_like(x), torch.empty_like(c)
-        ops.linear_fwd(_lin_probs([(aox, self.proj_x, ox), (aoc, self.proj_c, oc)], x.dtype), C, C)
-        return ox, oc
+        return self._run(x, c)
 
 
-class DualCrossAttention_v2(nn.Module):
+class DualCrossAttention_v2(_AttentionModule):
     """models/lemevit.py:326-423 ("D2", lemevit_tiny_v2): q, v1 = qv1(x); k, v2 = kv2(c); x' = sdpa(q,k,v2), c' = sdpa(k,q,v1)."""
+    _kind = "D2"
 
     def __init__(self, dim, num_heads, scale=None, bias=False, attn_drop=0.0, proj_drop=0.0, **kwargs):
-        super().__init__()
-        assert dim % num_heads == 0 and dim // num_heads == ops.HEAD_DIM
-        self.num_heads = num_heads
+        super().__init__(dim, num_heads)
         self.scale = scale or dim ** (-0.5)
         self.qv1 = nn.Linear(dim, 2 * dim)
         self.kv2 = nn.Linear(dim, 2 * dim)
         self.proj_x = nn.Linear(dim, dim)
         self.proj_c = nn.Linear(dim, dim)
-        self.attn_viz = nn.Identity()          # models/lemevit.py:181,249,355,451: the hook point of LeMeViT.attention_maps
 
     def forward(self, x, c):
-        P = _attn_params(self.qv1, self.kv2, self.proj_x, self.proj_c)
-        if _needs_grad(x, c, *P):
-            return _AttnModuleFn.apply("D2", x, c, *P)
-        with torch.no_grad():
-            return self._forward_nograd(x, c)
-
-    def _forward_nograd(self, x, c):
-        x, c = x.contiguous(), c.contiguous()
-        C, N, M = x.shape[-1], x.shape[1], c.shape[1]
-        sx, sc = ops.dca_scales(N, M, C)
-        qv1 = torch.empty(x.shape[:-1] + (2 * C,), device=x.device, dtype=x.dtype)
-        kv2 = torch.empty(c.shape[:-1] + (2 * C,), device=x.device, dtype=x.dtype)
-        ops.linear_fwd(_lin_probs([(x, self.qv1, qv1), (c, self.kv2, kv2)], x.dtype), 2 * C, C)
-        aox, _ = ops.attn_fwd((qv1, 0), (kv2, 0), (kv2, C), C, sx)
-        aoc, _ = ops.attn_fwd((kv2, 0), (qv1, 0), (qv1, C), C, sc)
-        ox, oc = torch.empty_like(x), torch.empty_like(c)
-        ops.linear_fwd(_lin_probs([(aox, self.proj_x, ox), (aoc, self.proj_c, oc)], x.dtype), C, C)
-        return ox, oc
+        return self._run(x, c)
 
 
-class CrossAttention(nn.Module):
+class CrossAttention(_AttentionModule):
     """models/lemevit.py:425-497.  forward(x [B,N,C], c [B,M,C]) -> c'."""
+    _kind = "C"
 
     def __init__(self, dim, num_heads, scale=None, bias=False, attn_drop=0.0, proj_drop=0.0, **kwargs):
-        super().__init__()
-        assert dim % num_heads == 0 and dim // num_heads == ops.HEAD_DIM
-        self.num_heads = num_heads
+        super().__init__(dim, num_heads)
         self.q = nn.Linear(dim, dim)
         self.kv = nn.Linear(dim, 2 * dim)
         self.proj = nn.Linear(dim, dim)
-        self.attn_viz = nn.Identity()          # models/lemevit.py:181,249,355,451: the hook point of LeMeViT.attention_maps
 
     def forward(self, x, c):
-        P = _attn_params(self.q, self.kv, self.proj)
-        if _needs_grad(x, c, *P):
-            return _AttnModuleFn.apply("C", x, c, *P)
-        with torch.no_grad():
-            return self._forward_nograd(x, c)
-
-    def _forward_nograd(self, x, c):
-        x, c = x.contiguous(), c.contiguous()
-        C = x.shape[-1]
-        kv = torch.empty(x.shape[:-1] + (2 * C,), device=x.device, dtype=x.dtype)
-        q = torch.empty_like(c)
-        ops.linear_fwd(_lin_probs([(x, self.kv, kv)], x.dtype), 2 * C, C)
-        ops.linear_fwd(_lin_probs([(c, self.q, q)], x.dtype), C, C)
-        ao, _ = ops.attn_fwd((q, 0), (kv, 0), (kv, C), C, ops.SDPA_SCALE)
-        out = torch.empty_like(c)
-        ops.linear_fwd(_lin_probs([(ao, self.proj, out)], x.dtype), C, C)
-        return out
+        return self._run(x, c)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1600,16 +1460,16 @@ class _MapRecorder:
         P = {n: compute_copy(p, cd if _is_matrix(n) else torch.float32) for n, p in blk._params().items()}
         sa = attention_state(kind, x.contiguous(), c.contiguous(), H, W, P)
         if kind == "C":
-            kv, q, lse = sa[6], sa[7], sa[9]
-            rec.meta_from_image = self._probs(viz, shapes["meta_from_image"], (q, 0), (kv, 0), lse, C_, ops.SDPA_SCALE)
+            kv, q = sa.proj
+            rec.meta_from_image = self._probs(viz, shapes["meta_from_image"], (q, 0), (kv, 0), sa.lse[0], C_, ops.SDPA_SCALE)
         elif kind in ("D", "D2"):
-            a, b2, lsex, lsec = sa[3], sa[4], sa[7], sa[8]          # D: qkv1, qkv2; D2: qv1, kv2
+            (a, b2), (lsex, lsec) = sa.proj, sa.lse          # D: qkv1, qkv2; D2: qv1, kv2
             sx, sc = ops.dca_scales(x.shape[1], c.shape[1], C_)
             kx, kc = ((b2, C_), (a, C_)) if kind == "D" else ((b2, 0), (a, 0))
             rec.image_from_meta = self._probs(viz, shapes["image_from_meta"], (a, 0), kx, lsex, C_, sx)
             rec.meta_from_image = self._probs(viz, shapes["meta_from_image"], (b2, 0), kc, lsec, C_, sc)
         else:
-            qkv, lse = sa[3], sa[5]
+            qkv, lse = sa.proj, sa.lse
             if "image_self" in shapes:
                 rows = map_query_rows(self.queries, H, W)
                 if rows is None:

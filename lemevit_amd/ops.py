@@ -1143,31 +1143,43 @@ SSTAGE_NAMES = ("attn.qkv.weight", "attn.proj.weight", "mlp.0.weight", "mlp.3.we
                 "norm2.weight", "norm2.bias", "mlp.0.bias", "mlp.3.bias", "pos_embed.weight", "pos_embed.bias")
 
 
-def sstage_pack(blocks: Sequence[dict], heads: int) -> SStagePacked:
-    """blocks: per block a dict name -> tensor (SSTAGE_NAMES; matrices bf16, vectors fp32, reference layouts, on the GPU)."""
-    w0 = blocks[0]["attn.qkv.weight"]
+_SSTAGE_FIELDS = ("qkv_w", "proj_w", "fc1_w", "fc2_w", "n1_w", "n1_b", "qkv_b", "proj_b", "n2_w", "n2_b", "fc1_b", "fc2_b", "pos_w", "pos_b")
+
+
+def _stage_pack(layout: str, blocks: Sequence[dict], heads: int) -> SStagePacked:
+    """One launch of the layout's pack entry point per block; _STAGE_LAYOUTS[layout] pairs the fields of its parameter struct with the parameter names."""
+    struct, fields, names, wpk_bytes, vec_floats, pack = _STAGE_LAYOUTS[layout]
+    w0 = blocks[0][names[0]]
     C_ = w0.shape[1]
     hidden = blocks[0]["mlp.0.weight"].shape[0]
-    wb, vf = int(lib.lmv_sstage_wpk_bytes(C_, hidden)), int(lib.lmv_sstage_vec_floats(C_, hidden))
+    wb, vf = int(wpk_bytes(C_, hidden)), int(vec_floats(C_, hidden))
+    if wb == 0:
+        raise ValueError(f"lemevit_amd: {layout}_pack does not support C = {C_}")
     P = SStagePacked()
-    P.nblocks, P.C, P.heads, P.hidden, P.layout = len(blocks), C_, heads, hidden, "sstage"
+    P.nblocks, P.C, P.heads, P.hidden, P.layout = len(blocks), C_, heads, hidden, layout
     P.wpk = torch.empty(len(blocks) * wb, device=w0.device, dtype=torch.uint8)
     P.vec = torch.empty(len(blocks) * vf, device=w0.device, dtype=torch.float32)
     keep = []
     for j, blk in enumerate(blocks):
-        bp = _lib.SStageBlockParams()
+        bp = struct()
         bp.C, bp.heads, bp.hidden = C_, heads, hidden
-        for field, name in zip(("qkv_w", "proj_w", "fc1_w", "fc2_w"), SSTAGE_NAMES[:4]):
+        for field, name in zip(fields, names):
             t = blk[name]
-            if t.dtype != torch.bfloat16:
-                raise TypeError("lemevit_amd: sstage_pack takes bf16 matrices")
-            t = t.contiguous(); keep.append(t)
+            if name.endswith(".weight") and name.startswith(("attn.", "mlp.")):          # a matrix
+                if t.dtype != torch.bfloat16:
+                    raise TypeError(f"lemevit_amd: {layout}_pack takes bf16 matrices")
+                t = t.contiguous()
+            else:
+                t = t.detach().float().contiguous()
+            keep.append(t)
             setattr(bp, field, _ptr(t))
-        for field, name in zip(("n1_w", "n1_b", "qkv_b", "proj_b", "n2_w", "n2_b", "fc1_b", "fc2_b", "pos_w", "pos_b"), SSTAGE_NAMES[4:]):
-            t = blk[name].detach().float().contiguous(); keep.append(t)
-            setattr(bp, field, _ptr(t))
-        check(lib.lmv_sstage_pack(C.byref(bp), P.wpk.data_ptr() + j * wb, P.vec.data_ptr() + j * vf * 4, _stream()), "lmv_sstage_pack")
+        check(pack(C.byref(bp), P.wpk.data_ptr() + j * wb, P.vec.data_ptr() + j * vf * 4, _stream()), f"lmv_{layout}_pack")
     return P
+
+
+def sstage_pack(blocks: Sequence[dict], heads: int) -> SStagePacked:
+    """blocks: per block a dict name -> tensor (SSTAGE_NAMES; matrices bf16, vectors fp32, reference layouts, on the GPU)."""
+    return _stage_pack("sstage", blocks, heads)
 
 
 def sstage_max_concurrent(C_: int) -> int:
@@ -1181,16 +1193,23 @@ def _check_concurrent(concurrent: int, limit: int, fn: str) -> None:
                            "(their incomplete slots would fill the chip and the in-launch hand-offs could starve): use the per-block schedule or fewer sub-batches")
 
 
+def _stage_desc(x: Tensor, c: Tensor, P: SStagePacked, H: int, W: int, eps: float, timing: Optional[Tensor], timing_block: int, kind: int = 0) -> "_lib.SStageDesc":
+    """The descriptor both stage kernels read (kind: dstage_fwd's block kind)."""
+    d = _lib.SStageDesc()
+    d.kind = kind
+    d.B, d.H, d.W, d.M, d.C, d.heads, d.hidden, d.nblocks, d.dtype, d.eps = x.shape[0], H, W, c.shape[1], x.shape[2], P.heads, P.hidden, P.nblocks, dtype_code(x), eps
+    d.wpk, d.vec = P.wpk.data_ptr(), P.vec.data_ptr()
+    d.timing, d.timing_block = (None if timing is None else timing.data_ptr()), timing_block
+    return d
+
+
 def sstage_fwd(x: Tensor, c: Tensor, P: SStagePacked, H: int, W: int, eps: float, timing: Optional[Tensor] = None, timing_block: int = 0,
                concurrent: int = 1) -> Tuple[Tensor, Tensor]:
     """concurrent: how many stage launches the caller keeps in flight on the device at once, this one included (graph.split_forward's sub-batches)."""
     B, N, C_ = x.shape
     _check_packed(P, "sstage", C_, "sstage_fwd")
     _check_concurrent(concurrent, sstage_max_concurrent(C_), "sstage_fwd")
-    d = _lib.SStageDesc()
-    d.B, d.H, d.W, d.M, d.C, d.heads, d.hidden, d.nblocks, d.dtype, d.eps = B, H, W, c.shape[1], C_, P.heads, P.hidden, P.nblocks, dtype_code(x), eps
-    d.wpk, d.vec = P.wpk.data_ptr(), P.vec.data_ptr()
-    d.timing, d.timing_block = (None if timing is None else timing.data_ptr()), timing_block
+    d = _stage_desc(x, c, P, H, W, eps, timing, timing_block)
     xo, co = torch.empty_like(x), torch.empty_like(c)
     nbytes = int(lib.lmv_sstage_workspace_bytes(min(B, int(lib.lmv_sstage_max_images(C_))), C_))
     ws = _workspace(nbytes, x.device)
@@ -1219,34 +1238,15 @@ _DSTAGE_FIELDS = ("qkv1_w", "qkv2_w", "projx_w", "projc_w", "fc1_w", "fc2_w", "n
                   "pos_w", "pos_b")
 
 
+_STAGE_LAYOUTS = {"sstage": (_lib.SStageBlockParams, _SSTAGE_FIELDS, SSTAGE_NAMES, lib.lmv_sstage_wpk_bytes, lib.lmv_sstage_vec_floats, lib.lmv_sstage_pack),
+                  "dstage": (_lib.DStageBlockParams, _DSTAGE_FIELDS, DSTAGE_NAMES, lib.lmv_dstage_wpk_bytes, lib.lmv_dstage_vec_floats, lib.lmv_dstage_pack)}
+# what the packers of the other block kinds hand to dstage_pack unchanged
+_STAGE_SHARED = ("mlp.0.weight", "mlp.3.weight", "norm1.weight", "norm1.bias", "norm2.weight", "norm2.bias", "mlp.0.bias", "mlp.3.bias", "pos_embed.weight", "pos_embed.bias")
+
+
 def dstage_pack(blocks: Sequence[dict], heads: int) -> SStagePacked:
     """blocks: per block a dict name -> tensor (DSTAGE_NAMES; matrices bf16, vectors fp32, reference layouts, on the GPU)."""
-    w0 = blocks[0]["attn.qkv1.weight"]
-    C_ = w0.shape[1]
-    hidden = blocks[0]["mlp.0.weight"].shape[0]
-    wb, vf = int(lib.lmv_dstage_wpk_bytes(C_, hidden)), int(lib.lmv_dstage_vec_floats(C_, hidden))
-    if wb == 0:
-        raise ValueError(f"lemevit_amd: dstage_pack does not support C = {C_}")
-    P = SStagePacked()
-    P.nblocks, P.C, P.heads, P.hidden, P.layout = len(blocks), C_, heads, hidden, "dstage"
-    P.wpk = torch.empty(len(blocks) * wb, device=w0.device, dtype=torch.uint8)
-    P.vec = torch.empty(len(blocks) * vf, device=w0.device, dtype=torch.float32)
-    keep = []
-    for j, blk in enumerate(blocks):
-        bp = _lib.DStageBlockParams()
-        bp.C, bp.heads, bp.hidden = C_, heads, hidden
-        for k, (field, name) in enumerate(zip(_DSTAGE_FIELDS, DSTAGE_NAMES)):
-            t = blk[name]
-            if k < 6:
-                if t.dtype != torch.bfloat16:
-                    raise TypeError("lemevit_amd: dstage_pack takes bf16 matrices")
-                t = t.contiguous()
-            else:
-                t = t.detach().float().contiguous()
-            keep.append(t)
-            setattr(bp, field, _ptr(t))
-        check(lib.lmv_dstage_pack(C.byref(bp), P.wpk.data_ptr() + j * wb, P.vec.data_ptr() + j * vf * 4, _stream()), "lmv_dstage_pack")
-    return P
+    return _stage_pack("dstage", blocks, heads)
 
 
 CSTAGE_NAMES = ("attn.q.weight", "attn.kv.weight", "attn.proj.weight", "mlp.0.weight", "mlp.3.weight", "norm1.weight", "norm1.bias", "attn.q.bias", "attn.kv.bias", "attn.proj.bias",
@@ -1262,7 +1262,7 @@ def cstage_pack(blocks: Sequence[dict], heads: int) -> SStagePacked:
         C_ = q.shape[0]
         z = torch.zeros_like(q)
         zb = torch.zeros(C_, device=q.device, dtype=torch.float32)
-        d = {n: blk[n] for n in ("mlp.0.weight", "mlp.3.weight", "norm1.weight", "norm1.bias", "norm2.weight", "norm2.bias", "mlp.0.bias", "mlp.3.bias", "pos_embed.weight", "pos_embed.bias")}
+        d = {n: blk[n] for n in _STAGE_SHARED}
         d["attn.qkv1.weight"] = torch.cat([z, kv], 0)
         d["attn.qkv2.weight"] = torch.cat([q, z, z], 0)
         d["attn.qkv1.bias"] = torch.cat([zb, blk["attn.kv.bias"].float()], 0)
@@ -1278,7 +1278,7 @@ def s2stage_pack(blocks: Sequence[dict], heads: int) -> SStagePacked:
     (qkv1 = qkv2, proj_x = proj_c).  Stage 3 of LeMeViT-Base at 384 x 384 (576 + 16 tokens: too long for sstage_fwd's two workgroups per image)."""
     out = []
     for blk in blocks:
-        d = {n: blk[n] for n in ("mlp.0.weight", "mlp.3.weight", "norm1.weight", "norm1.bias", "norm2.weight", "norm2.bias", "mlp.0.bias", "mlp.3.bias", "pos_embed.weight", "pos_embed.bias")}
+        d = {n: blk[n] for n in _STAGE_SHARED}
         d["attn.qkv1.weight"] = d["attn.qkv2.weight"] = blk["attn.qkv.weight"]
         d["attn.qkv1.bias"] = d["attn.qkv2.bias"] = blk["attn.qkv.bias"]
         d["attn.proj_x.weight"] = d["attn.proj_c.weight"] = blk["attn.proj.weight"]
@@ -1299,8 +1299,7 @@ def d2stage_pack(blocks: Sequence[dict], heads: int) -> SStagePacked:
         qv1, kv2 = blk["attn.qv1.weight"], blk["attn.kv2.weight"]
         C_ = qv1.shape[1]
         b1, b2 = blk["attn.qv1.bias"].float(), blk["attn.kv2.bias"].float()
-        d = {n: blk[n] for n in ("attn.proj_x.weight", "attn.proj_c.weight", "attn.proj_x.bias", "attn.proj_c.bias", "mlp.0.weight", "mlp.3.weight", "norm1.weight", "norm1.bias",
-                                 "norm2.weight", "norm2.bias", "mlp.0.bias", "mlp.3.bias", "pos_embed.weight", "pos_embed.bias")}
+        d = {n: blk[n] for n in ("attn.proj_x.weight", "attn.proj_c.weight", "attn.proj_x.bias", "attn.proj_c.bias") + _STAGE_SHARED}
         d["attn.qkv1.weight"] = torch.cat([qv1[:C_], qv1[:C_], qv1[C_:]], 0)
         d["attn.qkv2.weight"] = torch.cat([kv2[:C_], kv2[:C_], kv2[C_:]], 0)
         d["attn.qkv1.bias"] = torch.cat([b1[:C_], b1[:C_], b1[C_:]], 0)
@@ -1316,11 +1315,7 @@ def dstage_fwd(x: Tensor, c: Tensor, P: SStagePacked, H: int, W: int, eps: float
     B, N, C_ = x.shape
     _check_packed(P, "dstage", C_, "dstage_fwd")
     _check_concurrent(concurrent, dstage_max_concurrent(C_, H, kind), "dstage_fwd")
-    d = _lib.SStageDesc()
-    d.kind = kind
-    d.B, d.H, d.W, d.M, d.C, d.heads, d.hidden, d.nblocks, d.dtype, d.eps = B, H, W, c.shape[1], C_, P.heads, P.hidden, P.nblocks, dtype_code(x), eps
-    d.wpk, d.vec = P.wpk.data_ptr(), P.vec.data_ptr()
-    d.timing, d.timing_block = (None if timing is None else timing.data_ptr()), timing_block
+    d = _stage_desc(x, c, P, H, W, eps, timing, timing_block, kind)
     xo, co = (x if kind == 1 else torch.empty_like(x)), torch.empty_like(c)
     ws = _workspace(int(lib.lmv_dstage_workspace_bytes(B, C_)), x.device)
     check(lib.lmv_dstage_fwd(C.byref(d), _ptr(x), _ptr(c), _ptr(xo), _ptr(co), ws.data_ptr(), ws.numel(), _stream()), "lmv_dstage_fwd")

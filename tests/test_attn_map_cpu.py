@@ -213,3 +213,29 @@ def test_attn_viz_hook_points_leave_the_state_dict_alone():
     plan, _ = bb._map_plan((1, 3, 64, 64), image_queries=[(0.5, 0.5)])
     assert [dict(p[3]).keys() for p in plan][3:] == [{"image_self"}, {"image_self"}], "the dense backbone's S blocks have no meta_self"
     assert [len(p[3]) for p in bb._map_plan((1, 3, 64, 64))[0]] == [1, 2, 2, 0, 0]
+
+
+# ------------------------------------------------------------------------------------------------
+# the wiring the stand-alone attention modules and the map recorder share with the block schedules (lemevit_amd/blocks.py)
+def test_attention_halves_share_parameter_names_and_saved_fields(monkeypatch):
+    """The modules hand their (weight, bias) pairs to the attention halves by the block's parameter names, and LeMeViT.attention_maps reads the saved set by
+    field name: a module whose Linears are declared in another order than blocks.PARAM_NAMES, or a kind whose saved set has other fields, would feed a kernel
+    the wrong operand.  The launches are stubbed (no GPU): only the host wiring runs, on a module's data (no norm1, no residual)."""
+    from lemevit_amd import blocks, model, ops
+    classes = {"S": model.StandardAttention, "D": model.DualCrossAttention, "D2": model.DualCrossAttention_v2, "C": model.CrossAttention}
+    monkeypatch.setattr(ops, "linear_fwd", lambda probs, N, K, act=0: None)
+    monkeypatch.setattr(ops, "attn_fwd", lambda q, k, v, C_, scale, want_lse=False, stream=None: (q[0].new_empty(q[0].shape[:-1] + (C_,)), q[0].new_empty(1)))
+    C, x, c = 64, torch.zeros(2, 9, 64), torch.zeros(2, 4, 64)
+    for kind, cls in classes.items():
+        m = cls(dim=C, num_heads=C // 32)
+        names = [n for n in blocks.PARAM_NAMES[kind] if n.startswith("attn.")]
+        assert names == ["attn." + n for n, _ in m.named_parameters()], kind
+        assert names == ["attn." + n for n in m.state_dict()], kind
+        P = {n: p.detach() for n, p in zip(names, m.parameters())}
+        ts = [x] if kind == "S" else [x, c]
+        outs, saved = blocks.ATTN_FWD[kind](P, ts, None, True)
+        assert type(saved) is blocks.AttnSaved and saved._fields == ("ts", "st", "xn", "proj", "ao", "lse"), kind
+        assert all(isinstance(getattr(saved, f), list) for f in saved._fields), kind
+        assert len(saved.ts) == len(saved.st) == len(saved.xn) == len(saved.proj) == len(ts) and len(saved.ao) == len(saved.lse) == len(outs), kind
+        assert all(a is b for a, b in zip(saved.xn, ts)), "without norm1 the in-projections read the streams themselves"
+    assert set(blocks.ATTN_FWD) == set(blocks.ATTN_BWD) == set(blocks.PARAM_NAMES)
