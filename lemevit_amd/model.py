@@ -93,8 +93,11 @@ def derived(owner, tag, sources: Sequence[Optional[Tensor]], build):
 
 
 def _cache_filled() -> None:
-    """A lazily built operand cache was (re)filled by kernels on the CURRENT stream: image_ranges() re-forks its range streams behind them and
-    graph.split_forward orders its other sub-batch streams behind the sub-batch that filled it."""
+    """A lazily built operand cache was (re)filled by kernels on the stream that is current AT THE FILL: image_ranges() re-forks its range streams behind them, and
+    graph.split_forward and LeMeViT._tail_split order their other sub-batch streams behind the sub-batch that filled it.  That stream is not always the caller's: the
+    inference side path (LeMeViT._stages_from, _INFER_SIDE) runs the meta-token MLP of a stage -- and builds its casts -- on blocks.aux_streams(dev, 1)[0] and joins that
+    stream into the caller's before the pass goes on.  A counter that moved therefore means "a fill was issued on the current stream or on a stream that has since been
+    joined into it": waiting for the current stream covers both."""
     global _casts_launched
     _casts_launched += 1
 
@@ -1877,7 +1880,9 @@ class LeMeViT(nn.Module):
     def _tail_split(self, i: int, xt: Tensor, H: int, W: int, c: Tensor, st: dict) -> Tensor:
         """Inference: stages i .. end run per launch (no persistent stage kernel takes them: stage 4 of every variant) -- short launches that under-fill the chip, each paying its ramp
         and its tail.  The images of a batch do not interact in eval mode, so the rest of the pass runs as sub-batches on forked streams (graph.split_forward's argument, applied only
-        where it pays: behind the last persistent launch)."""
+        where it pays: behind the last persistent launch).  While the sub-batches are issued, launches.concurrent says how many of them there are (as in graph.split_forward):
+        where to split comes from the PREVIOUS pass (_whole_seen), so a stage in here may have become eligible for a persistent kernel since (a block's training flag, _masks,
+        LMV_SSTAGE, a custom depth or width) -- _sstage_applies and the ops then judge it as one of len(xs) launches side by side, not as a single one."""
         from .blocks import aux_streams
         parts = max(1, min(st["tail_parts"], xt.shape[0]))
         cur = torch.cuda.current_stream(xt.device)
@@ -1886,16 +1891,20 @@ class LeMeViT(nn.Module):
         sub = dict(st, tail_parts=1, side=False)
         fork = cur.record_event()
         fills = cache_fills()
-        ys = [self._stages_from(i, None, xs[0].contiguous(), H, W, cs[0].contiguous(), False, sub)]
-        cold = cache_fills() != fills          # sub-batch 0 filled an operand cache on the current stream: the others wait for all of it (graph.split_forward)
-        for k, s in enumerate(streams):
-            if cold:
-                s.wait_stream(cur)
-            else:
-                s.wait_event(fork)
-            with torch.cuda.stream(s):
-                ys.append(self._stages_from(i, None, xs[k + 1].contiguous(), H, W, cs[k + 1].contiguous(), False, sub))
-            xt.record_stream(s); c.record_stream(s)
+        was, launches.concurrent = launches.concurrent, len(xs)
+        try:
+            ys = [self._stages_from(i, None, xs[0].contiguous(), H, W, cs[0].contiguous(), False, sub)]
+            cold = cache_fills() != fills          # sub-batch 0 filled an operand cache on the current stream: the others wait for all of it (graph.split_forward)
+            for k, s in enumerate(streams):
+                if cold:
+                    s.wait_stream(cur)
+                else:
+                    s.wait_event(fork)
+                with torch.cuda.stream(s):
+                    ys.append(self._stages_from(i, None, xs[k + 1].contiguous(), H, W, cs[k + 1].contiguous(), False, sub))
+                xt.record_stream(s); c.record_stream(s)
+        finally:
+            launches.concurrent = was
         for s, y in zip(streams, ys[1:]):
             cur.wait_stream(s)
             y.record_stream(cur)
