@@ -632,6 +632,44 @@ int lmv_dense_loss_bwd(const void* logits, int dtype, int64_t batch_stride, int6
                        const float* gout, void* dlogits, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The dense losses on LOW-RESOLUTION logits: the bilinear upsampling in front of every dense loss of the reference (change_detection/models/Models.py:221
+ * F.interpolate(scale_factor=4, align_corners=True); the segmentation heads' resize(seg_logit, size=seg_label.shape[2:], mode='bilinear'), 4x / 16x) is evaluated
+ * inside the pass, so the [B, K, H, W] map and its gradient never exist.  An addition to ABI 14: callers detect it by symbol.  Everything of the block above holds
+ * unless stated: the formulas, the ignore rule, the argmax rule, the `stats` layout, the workspace row layout, launch (b), no floating-point atomics, capture.
+ *
+ * Geometry.  logits [B, K, h, w] fp32 / bf16 (pixel stride 1, rows of a plane contiguous, ELEMENT strides batch_stride / class_stride as above), labels [B, H W],
+ * H >= h, W >= w, B H W < 2^31.  The logit of output pixel (Y, X) is PyTorch's upsample_bilinear2d in its `size=` form (the scale comes from the sizes; equal to
+ * scale_factor=s for an integer s), per axis, in fp32:
+ *     align_corners = 0:  src = max(0, (dst + 0.5) in / out - 0.5)          align_corners = 1:  src = dst (in - 1) / (out - 1),  0 when out == 1
+ *     i0 = floor(src),  i1 = min(i0 + 1, in - 1),  l = src - i0
+ *     z = (1 - ly) ((1 - lx) z00 + lx z01) + ly ((1 - lx) z10 + lx z11)          per class
+ * A bf16 input is NOT rounded back to bf16 after the interpolation (the stock path rounds the map it stores): this path is the more accurate one.  One device
+ * function computes (i0, i1, l) for every kernel, and the backward pass finds the output pixels that touch an input pixel by bisection on that same function.
+ *
+ * lmv_dense_up_loss_fwd -- what lmv_dense_loss_fwd computes, on the interpolated logits.  A thread owns chunks of 4 consecutive output pixels of ONE output row
+ * (a chunk never crosses a row); the labels of a chunk are loaded as one word where the address allows, element-wise otherwise (the same bits); the four input
+ * values per class come from the 16 x smaller, cache-resident logits.  workspace: lmv_dense_up_loss_workspace_bytes(B, K, H, W).  pred: uint8 [B, H W].
+ * labels == NULL with pred != NULL is PREDICTION ONLY (resize + argmax at inference): no sums, launch (b) is skipped, workspace / stats / conf / meter are not
+ * touched and may be NULL.
+ *
+ * lmv_dense_up_loss_bwd -- one launch.  dlogits, contiguous [B, K, h, w] in the logits dtype:
+ *     d z_low[b, k, y, x] = sum over (Y, X) of wy(Y, y) wx(X, x) dz_high[b, k, Y, X],          dz_high: the closed form above (exact zero at an ignored pixel)
+ * accumulated in fp32, rounded once, every element written exactly once (no pre-zeroed buffer, no floating-point atomic in global memory or LDS): a workgroup owns a
+ * tile of input pixels, evaluates the softmax of every output pixel of the tile's footprint once per block of the footprint, and gathers per class from an LDS
+ * plane in a fixed order.  Two calls agree bit for bit.
+ *
+ * Refused with LMV_ERR_SHAPE and a message that starts "dense_up_loss", before any launch: everything the block above refuses (with h w in the place of H W for
+ * the strides); h < 1, w < 1, H < h or W < w; B H W >= 2^31; an align_corners other than 0 / 1; labels == NULL with pred == NULL (backward: labels == NULL).
+ * ------------------------------------------------------------------------------------------ */
+size_t lmv_dense_up_loss_workspace_bytes(int B, int K, int H, int W);
+int lmv_dense_up_loss_fwd(const void* logits, int dtype, int64_t batch_stride, int64_t class_stride, int B, int K, int h, int w, int H, int W, int align_corners,
+                          const void* labels, int label_dtype, int64_t ignore_index, const float* alpha, float gamma, float w_ce, float w_dice, float w_jac,
+                          float eps, int avg_mode, void* workspace, size_t workspace_bytes, float* stats, uint8_t* pred, int64_t* conf, double* meter, void* stream);
+int lmv_dense_up_loss_bwd(const void* logits, int dtype, int64_t batch_stride, int64_t class_stride, int B, int K, int h, int w, int H, int W, int align_corners,
+                          const void* labels, int label_dtype, int64_t ignore_index, const float* alpha, float gamma, float w_ce, float w_dice, float w_jac,
+                          float eps, int avg_mode, const float* stats, const float* gout, void* dlogits, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Whole-block schedules: ONE call enqueues every launch of a LeMeBlock (models/lemevit.py:500-660) on token-major tensors
  * x [B, H*W, C], c [B, M, C] -- `LeMeBlock.forward_with_x` ("S", :615-650), `forward_with_xc` ("D", :542-582), `forward_with_c`
  * ("C", :584-613; x is returned untouched by the caller, x_out / dx_out may be NULL).  Replaces the ~12 / ~30 per-op calls a Python

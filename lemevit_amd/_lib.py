@@ -201,6 +201,9 @@ SIGNATURES = {
     "lmv_dense_loss_workspace_bytes": (_Z, [_I, _I, _L]),
     "lmv_dense_loss_fwd": (_I, [_P, _I, _L, _L, _I, _I, _L, _P, _I, _L, _P, _F, _F, _F, _F, _F, _I, _P, _Z, _P, _P, _P, _P, _P]),
     "lmv_dense_loss_bwd": (_I, [_P, _I, _L, _L, _I, _I, _L, _P, _I, _L, _P, _F, _F, _F, _F, _F, _I, _P, _P, _P, _P]),
+    "lmv_dense_up_loss_workspace_bytes": (_Z, [_I, _I, _I, _I]),
+    "lmv_dense_up_loss_fwd": (_I, [_P, _I, _L, _L, _I, _I, _I, _I, _I, _I, _I, _P, _I, _L, _P, _F, _F, _F, _F, _F, _I, _P, _Z, _P, _P, _P, _P, _P]),
+    "lmv_dense_up_loss_bwd": (_I, [_P, _I, _L, _L, _I, _I, _I, _I, _I, _I, _I, _P, _I, _L, _P, _F, _F, _F, _F, _F, _I, _P, _P, _P, _P]),
     "lmv_block_arena_bytes": (_Z, [C.POINTER(BlockDesc)]),
     "lmv_block_bwd_scratch_bytes": (_Z, [C.POINTER(BlockDesc)]),
     "lmv_block_fwd": (_I, [C.POINTER(BlockDesc), _P, _P, _P, _P, _P, _Z, _I, _P]),

@@ -9,6 +9,7 @@
 // No floating-point atomics: per-thread partials, a butterfly per wave, waves in order, rows in order.  Counts that go through atomics are integers.
 #include <math.h>
 #include <algorithm>
+#include <type_traits>
 #include "common.h"
 
 // one expression must give one value wherever the compiler places it (the vector and the element path share the code behind the loads)
@@ -116,6 +117,51 @@ __device__ __forceinline__ DnChunk dn_chunk(const DenseArgs& a, int64_t ch, int 
   return c;
 }
 
+// ---- the workgroup's row: butterfly per wave, waves in order (the tail of both forward kernels) ----
+template <int KT> __device__ __forceinline__ void dn_write_row(float* ws, unsigned long long* gconf, int K, float* smem, float* red, const int* cntT, const int* conf,
+                                                               const float* rP, const float* rI, const int* rT, float ce_sum, float nll_sum, int nvalid) {
+  const int NT = blockDim.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nw = NT >> 6;
+  float* row = ws + (int64_t)blockIdx.x * (3 * K + 3);
+  ce_sum = wave_sum(ce_sum); nll_sum = wave_sum(nll_sum); nvalid = wave_sum_int(nvalid);
+  if constexpr (KT > 0) {
+    constexpr int NA = 3 * KT + 3;
+#pragma unroll
+    for (int k = 0; k < KT; ++k) {
+      const float p = wave_sum(rP[k]), i = wave_sum(rI[k]);
+      const int t = wave_sum_int(rT[k]);
+      if (lane == 0) { red[wave * NA + k] = p; red[wave * NA + KT + k] = i; red[wave * NA + 2 * KT + k] = (float)t; }
+    }
+    if (lane == 0) { red[wave * NA + 3 * KT] = ce_sum; red[wave * NA + 3 * KT + 1] = nll_sum; red[wave * NA + 3 * KT + 2] = (float)nvalid; }
+    __syncthreads();
+    if (tid < NA) {
+      float s = red[tid];
+      for (int w = 1; w < nw; ++w) s += red[w * NA + tid];
+      row[tid] = s;
+    }
+  } else {
+    if (lane == 0) { red[wave * 3] = ce_sum; red[wave * 3 + 1] = nll_sum; red[wave * 3 + 2] = (float)nvalid; }
+    __syncthreads();
+    for (int col = wave; col < 2 * K; col += nw) {          // accP | accI are one [2 K][threads] array
+      float s = smem[col * NT + lane];
+      for (int i = 64; i < NT; i += 64) s += smem[col * NT + lane + i];
+      s = wave_sum(s);
+      if (lane == 0) row[col] = s;
+    }
+    for (int k = tid; k < K; k += NT) row[2 * K + k] = (float)cntT[k];
+    if (tid < 3) {
+      float s = red[tid];
+      for (int w = 1; w < nw; ++w) s += red[w * 3 + tid];
+      row[3 * K + tid] = s;
+    }
+  }
+  if (gconf) {          // (after a __syncthreads on either path) integer adds commute: the matrix does not depend on their order
+    for (int i = tid; i < K * K; i += NT) {
+      const int cnt = conf[i];
+      if (cnt) atomicAdd(&gconf[i], (unsigned long long)cnt);
+    }
+  }
+}
+
 // ---- (a) the forward pass ---------------------------------------------------------------------------------------------------------------------------
 // LDS (dynamic): KT > 0: red [waves][3 KT + 3] floats | conf [K K] ints;  KT == 0: accP [K][threads] | accI [K][threads] floats | cntT [K] ints | red [waves][3] | conf
 template <typename T, typename LT, int KT> __global__ __launch_bounds__(256) void dense_fwd_kernel(const DenseArgs a) {
@@ -123,7 +169,7 @@ template <typename T, typename LT, int KT> __global__ __launch_bounds__(256) voi
   constexpr int KR = KT > 0 ? KT : 1;
   extern __shared__ float smem[];
   const int K = KT > 0 ? KT : a.K;
-  const int NT = blockDim.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nw = NT >> 6;
+  const int NT = blockDim.x, tid = threadIdx.x, nw = NT >> 6;
   float* accP = smem;
   float* accI = smem + (KT > 0 ? 0 : K * NT);
   int* cntT = reinterpret_cast<int*>(smem + (KT > 0 ? 0 : 2 * K * NT));
@@ -251,46 +297,7 @@ template <typename T, typename LT, int KT> __global__ __launch_bounds__(256) voi
     }
   }
 
-  // ---- the workgroup's row: butterfly per wave, waves in order ----
-  float* row = a.ws + (int64_t)blockIdx.x * (3 * K + 3);
-  ce_sum = wave_sum(ce_sum); nll_sum = wave_sum(nll_sum); nvalid = wave_sum_int(nvalid);
-  if constexpr (KT > 0) {
-    constexpr int NA = 3 * KT + 3;
-#pragma unroll
-    for (int k = 0; k < KT; ++k) {
-      const float p = wave_sum(rP[k]), i = wave_sum(rI[k]);
-      const int t = wave_sum_int(rT[k]);
-      if (lane == 0) { red[wave * NA + k] = p; red[wave * NA + KT + k] = i; red[wave * NA + 2 * KT + k] = (float)t; }
-    }
-    if (lane == 0) { red[wave * NA + 3 * KT] = ce_sum; red[wave * NA + 3 * KT + 1] = nll_sum; red[wave * NA + 3 * KT + 2] = (float)nvalid; }
-    __syncthreads();
-    if (tid < NA) {
-      float s = red[tid];
-      for (int w = 1; w < nw; ++w) s += red[w * NA + tid];
-      row[tid] = s;
-    }
-  } else {
-    if (lane == 0) { red[wave * 3] = ce_sum; red[wave * 3 + 1] = nll_sum; red[wave * 3 + 2] = (float)nvalid; }
-    __syncthreads();
-    for (int col = wave; col < 2 * K; col += nw) {          // accP | accI are one [2 K][threads] array
-      float s = smem[col * NT + lane];
-      for (int i = 64; i < NT; i += 64) s += smem[col * NT + lane + i];
-      s = wave_sum(s);
-      if (lane == 0) row[col] = s;
-    }
-    for (int k = tid; k < K; k += NT) row[2 * K + k] = (float)cntT[k];
-    if (tid < 3) {
-      float s = red[tid];
-      for (int w = 1; w < nw; ++w) s += red[w * 3 + tid];
-      row[3 * K + tid] = s;
-    }
-  }
-  if (a.conf) {          // (after a __syncthreads on either path) integer adds commute: the matrix does not depend on their order
-    for (int i = tid; i < K * K; i += NT) {
-      const int cnt = conf[i];
-      if (cnt) atomicAdd(&a.conf[i], (unsigned long long)cnt);
-    }
-  }
+  dn_write_row<KT>(a.ws, a.conf, K, smem, red, cntT, conf, rP, rI, rT, ce_sum, nll_sum, nvalid);
 }
 
 // ---- (b) rows -> stats ------------------------------------------------------------------------------------------------------------------------------
@@ -446,6 +453,344 @@ template <typename T, typename LT, int KT> __global__ __launch_bounds__(256) voi
   }
 }
 
+// ---- the same losses on bilinearly upsampled logits -------------------------------------------------------------------------------------------------
+// logits [B, K, h, w] -> PyTorch's upsample_bilinear2d to the label map's [H, W] (the `size=` form: the scale comes from the sizes), evaluated per output pixel in
+// fp32 and never stored.  A bf16 input is NOT rounded back to bf16 after the interpolation (the stock path rounds the [B, K, H, W] map it writes): more accurate.
+struct UpArgs {
+  const void* logits; const void* labels; const float* alpha;
+  float* ws; uint8_t* pred; unsigned long long* conf;
+  const float* stats; const float* gout; void* dlogits;
+  int64_t sb, sc, ignore, nchunks;
+  int B, K, h, w, H, W, cpr, align;          // cpr: chunks per output row
+  float sy, sx;          // input / output (align_corners: (in - 1) / (out - 1), 0 when out == 1), in float as PyTorch computes it
+  float gamma, w_ce;
+  int shape_terms;
+  int TH, TW, FBH, FBW, tiles_y, tiles_x, G;          // backward: the tile of input pixels, the block of output pixels in LDS, threads per input pixel of the gather
+};
+
+constexpr int UP_V = 4;          // output pixels of a chunk (both dtypes: the labels of a chunk are one 32-bit / two 16-byte words, its pred one 32-bit word)
+constexpr int UP_FB = 40;          // the backward's block of output pixels is at most UP_FB x UP_FB
+
+// THE index function of every kernel here: output coordinate -> the two taps and the weight of the second.  i0 is non-decreasing in dst (a product with a positive
+// constant, rounded), which is what up_first / up_end rely on.
+struct UpAxis { int i0, i1; float l; };
+__device__ __forceinline__ UpAxis up_axis(int dst, int in, float scale, int align) {
+  const float src = align ? (float)dst * scale : fmaxf(((float)dst + 0.5f) * scale - 0.5f, 0.f);
+  UpAxis a;
+  a.i0 = min((int)src, in - 1);
+  a.i1 = min(a.i0 + 1, in - 1);
+  a.l = src - (float)a.i0;
+  return a;
+}
+// the weight of input index i in the output coordinate behind ax (both taps on one index at the clamped border: both count, as in the forward pass)
+__device__ __forceinline__ float up_weight(int i0, int i1, float l, int i) { return (i == i0 ? 1.f - l : 0.f) + (i == i1 ? l : 0.f); }
+// the output coordinates that touch input indices [t0, t1]: [up_first(t0), up_end(t1)), found by bisection on up_axis itself -- no inverse map, nothing to round
+__device__ __forceinline__ int up_first(int t, int in, int out, float scale, int align) {
+  int lo = 0, hi = out;
+  while (lo < hi) { const int mid = (lo + hi) >> 1; if (up_axis(mid, in, scale, align).i1 >= t) hi = mid; else lo = mid + 1; }
+  return lo;
+}
+__device__ __forceinline__ int up_end(int t, int in, int out, float scale, int align) {
+  int lo = 0, hi = out;
+  while (lo < hi) { const int mid = (lo + hi) >> 1; if (up_axis(mid, in, scale, align).i0 > t) hi = mid; else lo = mid + 1; }
+  return lo;
+}
+// one class plane at one output pixel: r0 / r1 are the row offsets of the two input rows
+template <typename T> __device__ __forceinline__ float up_tap(const T* p, int r0, int r1, int c0, int c1, float ly, float lx) {
+  const float z00 = DT<T>::ld(p + r0 + c0), z01 = DT<T>::ld(p + r0 + c1), z10 = DT<T>::ld(p + r1 + c0), z11 = DT<T>::ld(p + r1 + c1);
+  return (1.f - ly) * ((1.f - lx) * z00 + lx * z01) + ly * ((1.f - lx) * z10 + lx * z11);
+}
+
+// ---- forward: a thread owns chunks of UP_V consecutive output pixels of ONE output row; the LDS layout, the row and the summation discipline of dense_fwd_kernel ----
+// labels == NULL: prediction only (argmax map, no sums, no row).  The softmax of an ignored pixel is not evaluated: it contributes to nothing.
+template <typename T, typename LT, int KT> __global__ __launch_bounds__(256) void dense_up_fwd_kernel(const UpArgs a) {
+  constexpr int V = UP_V;
+  constexpr int KR = KT > 0 ? KT : 1;
+  extern __shared__ float smem[];
+  const int K = KT > 0 ? KT : a.K;
+  const int NT = blockDim.x, tid = threadIdx.x, nw = NT >> 6;
+  float* accP = smem;
+  float* accI = smem + (KT > 0 ? 0 : K * NT);
+  int* cntT = reinterpret_cast<int*>(smem + (KT > 0 ? 0 : 2 * K * NT));
+  float* red = smem + (KT > 0 ? 0 : 2 * K * NT + K);
+  int* conf = reinterpret_cast<int*>(red + (KT > 0 ? nw * (3 * KT + 3) : nw * 3));
+  const bool sums = a.labels != nullptr;
+  if (sums) {
+    if (KT == 0) {
+      for (int i = tid; i < 2 * K * NT; i += NT) smem[i] = 0.f;
+      for (int i = tid; i < K; i += NT) cntT[i] = 0;
+    }
+    if (a.conf)
+      for (int i = tid; i < K * K; i += NT) conf[i] = 0;
+    __syncthreads();
+  }
+  float rP[KR], rI[KR];
+  int rT[KR];
+#pragma unroll
+  for (int k = 0; k < KR; ++k) { rP[k] = 0.f; rI[k] = 0.f; rT[k] = 0; }
+  float ce_sum = 0.f, nll_sum = 0.f;
+  int nvalid = 0;
+  const T* X = reinterpret_cast<const T*>(a.logits);
+  const LT* L = reinterpret_cast<const LT*>(a.labels);
+
+  for (int64_t ch = (int64_t)blockIdx.x * NT + tid; ch < a.nchunks; ch += (int64_t)gridDim.x * NT) {
+    const int64_t orow = ch / a.cpr;          // b H + Y
+    const int X0 = (int)(ch - orow * a.cpr) * V;
+    const int b = (int)(orow / a.H), Y = (int)(orow - (int64_t)b * a.H);
+    const int n = min(V, a.W - X0);
+    const int64_t poff = orow * a.W + X0;
+    const T* x = X + (int64_t)b * a.sb;
+    const UpAxis ay = up_axis(Y, a.h, a.sy, a.align);
+    const int r0 = ay.i0 * a.w, r1 = ay.i1 * a.w;
+    int y[V], bi[V];
+    if (sums) {
+      const LT* lp = L + poff;
+      dn_labels<V>(lp, n == V && (((uintptr_t)lp) & (sizeof(LT) == 8 ? 15u : 3u)) == 0, n, a.ignore, K, y);
+    } else {
+#pragma unroll
+      for (int j = 0; j < V; ++j) y[j] = -1;
+    }
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+      bi[j] = 0;
+      if (j >= n) continue;
+      const UpAxis ax = up_axis(X0 + j, a.w, a.sx, a.align);
+      const bool on = y[j] >= 0;
+      float se = 1.f, zy = 0.f, py = 0.f;
+      if constexpr (KT > 0) {
+        float z[KT];
+#pragma unroll
+        for (int k = 0; k < KT; ++k) z[k] = up_tap<T>(x + k * a.sc, r0, r1, ax.i0, ax.i1, ay.l, ax.l);
+        float best = z[0], m = z[0];
+        int bb = 0;
+#pragma unroll
+        for (int k = 1; k < KT; ++k) {
+          if (dn_better(z[k], best)) { best = z[k]; bb = k; }
+          m = fmaxf(m, z[k]);
+        }
+        bi[j] = bb;
+        if (on) {
+          float s = 0.f;
+#pragma unroll
+          for (int k = 0; k < KT; ++k) {          // z now holds the exponentials
+            const float dz = z[k] - m;
+            if (y[j] == k) zy = dz;
+            z[k] = expf(dz); s += z[k];
+          }
+          se = s;
+          const float inv = 1.f / s;
+#pragma unroll
+          for (int k = 0; k < KT; ++k) {
+            const float p = z[k] * inv;
+            rP[k] += p;
+            if (y[j] == k) { rI[k] += p; rT[k] += 1; py = p; }
+          }
+        }
+      } else {
+        float best = up_tap<T>(x, r0, r1, ax.i0, ax.i1, ay.l, ax.l), m = best;
+        int bb = 0;
+        for (int k = 1; k < K; ++k) {
+          const float z = up_tap<T>(x + k * a.sc, r0, r1, ax.i0, ax.i1, ay.l, ax.l);
+          if (dn_better(z, best)) { best = z; bb = k; }
+          m = fmaxf(m, z);
+        }
+        bi[j] = bb;
+        if (on) {
+          float s = 0.f;
+          for (int k = 0; k < K; ++k) s += expf(up_tap<T>(x + k * a.sc, r0, r1, ax.i0, ax.i1, ay.l, ax.l) - m);
+          se = s;
+          const float inv = 1.f / s;
+          for (int k = 0; k < K; ++k) {
+            const float dz = up_tap<T>(x + k * a.sc, r0, r1, ax.i0, ax.i1, ay.l, ax.l) - m;
+            const float p = expf(dz) * inv;
+            accP[k * NT + tid] += p;
+            if (y[j] == k) { accI[k * NT + tid] += p; atomicAdd(&cntT[k], 1); zy = dz; py = p; }
+          }
+        }
+      }
+      if (on) {
+        const float nll = logf(se) - zy;          // -log p_y = log(sum exp(z - max)) - (z_y - max)
+        ce_sum += dn_focal(a.alpha, a.gamma, y[j], py) * nll;
+        nll_sum += nll;
+        nvalid += 1;
+        if (a.conf) atomicAdd(&conf[y[j] * K + bi[j]], 1);
+      }
+    }
+    if (a.pred) {
+      uint8_t* pp = a.pred + poff;
+      if (n == V && (((uintptr_t)pp) & 3u) == 0) {
+        *reinterpret_cast<uint32_t*>(pp) = (uint32_t)bi[0] | ((uint32_t)bi[1] << 8) | ((uint32_t)bi[2] << 16) | ((uint32_t)bi[3] << 24);
+      } else {
+#pragma unroll
+        for (int j = 0; j < V; ++j)
+          if (j < n) pp[j] = (uint8_t)bi[j];
+      }
+    }
+  }
+  if (sums) dn_write_row<KT>(a.ws, a.conf, K, smem, red, cntT, conf, rP, rI, rT, ce_sum, nll_sum, nvalid);
+}
+
+// ---- backward: ONE launch, every element of dlogits [B, K, h, w] written once, no atomics ----
+// A workgroup owns a tile of TH x TW input pixels of one image.  The output pixels that touch the tile (its footprint: a rectangle, found with up_first / up_end)
+// are taken in blocks of at most FBH x FBW.  Per block: (1) one sweep leaves every output pixel's max, 1 / sum, sum_j p_j g_j, the CE factor and the label in
+// LDS; (2) per class, the block's dz_high plane goes to LDS (two buffers: one barrier per class) and G threads per input pixel gather
+// wy wx dz_high (weights from two small per-block tables) over that pixel's rows of the block in a fixed order, a butterfly over the G threads, and the group's first thread adds the block's sum to the
+// pixel's accumulator in LDS.  The softmax is evaluated once per output pixel and block; the fixed orders make two calls agree bit for bit.
+// LDS (dynamic, floats): max | 1/sum | sg | cf | label [FB] each | plane [2][FB] | acc [K][TH TW] | axis tables y: i0, i1, l [FBH], x: i0, i1, l [FBW] | weights [TH][FBH], [TW][FBW] | ranges [32] | STAGE: logits [K][TH + 2][TW + 2]
+template <typename T, typename LT, bool STAGE> __global__ __launch_bounds__(256) void dense_up_bwd_kernel(const UpArgs a) {
+  extern __shared__ float smem[];
+  const int K = a.K, tid = threadIdx.x, NT = 256;
+  const int FB = a.FBH * a.FBW, TP = a.TH * a.TW;
+  float* sM = smem;
+  float* sInv = sM + FB;
+  float* sSg = sInv + FB;
+  float* sCf = sSg + FB;
+  int* sY = reinterpret_cast<int*>(sCf + FB);
+  float* plane = reinterpret_cast<float*>(sY + FB);
+  float* acc = plane + 2 * FB;
+  int* yI0 = reinterpret_cast<int*>(acc + K * TP);
+  int* yI1 = yI0 + a.FBH;
+  float* yL = reinterpret_cast<float*>(yI1 + a.FBH);
+  int* xI0 = reinterpret_cast<int*>(yL + a.FBH);
+  int* xI1 = xI0 + a.FBW;
+  float* xL = reinterpret_cast<float*>(xI1 + a.FBW);
+  float* wyT = xL + a.FBW;          // [TH][FBH]: the weight of tile row t in block row i
+  float* wxT = wyT + a.TH * a.FBH;          // [TW][FBW]
+  int* rng = reinterpret_cast<int*>(wxT + a.TW * a.FBW);          // rLo [8] | rHi [8] | cLo [8] | cHi [8]
+  float* stage = reinterpret_cast<float*>(rng + 32);          // STAGE: [K][sh][sw], the tile's logits and a halo of one input pixel, as floats
+
+  const int tx_i = blockIdx.x % a.tiles_x, ty_i = (blockIdx.x / a.tiles_x) % a.tiles_y, b = blockIdx.x / (a.tiles_x * a.tiles_y);
+  const int ty0 = ty_i * a.TH, tx0 = tx_i * a.TW;
+  const int th = min(a.TH, a.h - ty0), tw = min(a.TW, a.w - tx0);
+  const int Ylo = up_first(ty0, a.h, a.H, a.sy, a.align), Yhi = up_end(ty0 + th - 1, a.h, a.H, a.sy, a.align);
+  const int Xlo = up_first(tx0, a.w, a.W, a.sx, a.align), Xhi = up_end(tx0 + tw - 1, a.w, a.W, a.sx, a.align);
+
+  const T* x = reinterpret_cast<const T*>(a.logits) + (int64_t)b * a.sb;
+  // every output pixel of the footprint has its taps in input rows [ty0 - 1, ty0 + th] and columns [tx0 - 1, tx0 + tw] (i1 <= i0 + 1), clamped to the image.
+  // STAGE (the host's choice: it fits into LDS): these logits are read from global memory once; otherwise every tap is a cached global load.  The values are the same.
+  const int y0s = STAGE ? max(ty0 - 1, 0) : 0, x0s = STAGE ? max(tx0 - 1, 0) : 0;
+  const int sh = min(ty0 + th, a.h - 1) - y0s + 1, sw = min(tx0 + tw, a.w - 1) - x0s + 1;
+  using ZT = typename std::conditional<STAGE, float, T>::type;
+  const ZT* zb = STAGE ? reinterpret_cast<const ZT*>(stage) : reinterpret_cast<const ZT*>(x);
+  const int zpitch = STAGE ? sw : a.w;
+  const int64_t zk = STAGE ? (int64_t)sh * sw : a.sc;
+  if (STAGE) {
+    for (int e = tid; e < K * sh * sw; e += NT) {
+      const int k = e / (sh * sw), r = e - k * (sh * sw);
+      const int yy = r / sw, xx = r - yy * sw;
+      stage[e] = DT<T>::ld(x + k * a.sc + (int64_t)(y0s + yy) * a.w + (x0s + xx));
+    }
+  }
+  const LT* L = reinterpret_cast<const LT*>(a.labels) + (int64_t)b * a.H * a.W;
+  const float gout = a.gout ? *a.gout : 1.f;
+  const float invD = a.stats[5];
+  const float* U = a.stats + LMV_DENSE_STATS_HEAD;
+  const float* Vt = U + K;
+  // the gather's thread -> (input pixel, part)
+  const int gp = tid / a.G, part = tid - gp * a.G;
+  const int gy = gp / a.TW, gx = gp - gy * a.TW;
+  const bool gather = gp < TP && gy < th && gx < tw;
+
+  for (int i = tid; i < K * TP; i += NT) acc[i] = 0.f;
+  // the footprint in equal blocks of at most FBH x FBW (no sliver at the end)
+  const int nby = (Yhi - Ylo + a.FBH - 1) / a.FBH, nbx = (Xhi - Xlo + a.FBW - 1) / a.FBW;
+  const int sby = (Yhi - Ylo + nby - 1) / nby, sbx = (Xhi - Xlo + nbx - 1) / nbx;
+  for (int Yb = Ylo; Yb < Yhi; Yb += sby) {
+    const int bh = min(sby, Yhi - Yb);
+    for (int Xb = Xlo; Xb < Xhi; Xb += sbx) {
+      const int bw = min(sbx, Xhi - Xb);
+      __syncthreads();          // the previous block's gather is over: tables, scalars and planes may be overwritten
+      for (int i = tid; i < bh + bw; i += NT) {
+        if (i < bh) {
+          const UpAxis ax = up_axis(Yb + i, a.h, a.sy, a.align);
+          yI0[i] = ax.i0; yI1[i] = ax.i1; yL[i] = ax.l;
+          for (int t = 0; t < a.TH; ++t) wyT[t * a.FBH + i] = up_weight(ax.i0, ax.i1, ax.l, ty0 + t);
+        } else {
+          const int j = i - bh;
+          const UpAxis ax = up_axis(Xb + j, a.w, a.sx, a.align);
+          xI0[j] = ax.i0; xI1[j] = ax.i1; xL[j] = ax.l;
+          for (int t = 0; t < a.TW; ++t) wxT[t * a.FBW + j] = up_weight(ax.i0, ax.i1, ax.l, tx0 + t);
+        }
+      }
+      __syncthreads();
+      if (tid < 16) {          // the rows (tid < 8) / columns of the block that touch tile row / column tid & 7: contiguous, possibly empty
+        const int t = tid & 7, isx = tid >> 3;
+        const int idx = (isx ? tx0 : ty0) + t, cnt = isx ? bw : bh;
+        const int* I0 = isx ? xI0 : yI0;
+        const int* I1 = isx ? xI1 : yI1;
+        int lo = cnt, hi = 0;
+        for (int i = 0; i < cnt; ++i)
+          if (I0[i] == idx || I1[i] == idx) { lo = min(lo, i); hi = i + 1; }
+        if (lo > hi) lo = hi;
+        rng[isx * 16 + t] = lo; rng[isx * 16 + 8 + t] = hi;
+      }
+      // (1) the scalars of every output pixel of the block
+      for (int f = tid; f < bh * bw; f += NT) {
+        const int Yr = f / bw, Xr = f - Yr * bw;
+        int yv;
+        dn_labels<1>(L + (int64_t)(Yb + Yr) * a.W + (Xb + Xr), false, 1, a.ignore, K, &yv);
+        sY[f] = yv;
+        if (yv < 0) continue;
+        const int r0 = (yI0[Yr] - y0s) * zpitch, r1 = (yI1[Yr] - y0s) * zpitch, c0 = xI0[Xr] - x0s, c1 = xI1[Xr] - x0s;
+        const float ly = yL[Yr], lx = xL[Xr];
+        float m = up_tap<ZT>(zb, r0, r1, c0, c1, ly, lx);
+        for (int k = 1; k < K; ++k) m = fmaxf(m, up_tap<ZT>(zb + k * zk, r0, r1, c0, c1, ly, lx));
+        float s = 0.f, ey = 0.f, sgu = 0.f;
+        for (int k = 0; k < K; ++k) {
+          const float e = expf(up_tap<ZT>(zb + k * zk, r0, r1, c0, c1, ly, lx) - m);
+          const bool hit = yv == k;
+          s += e;
+          if (hit) ey = e;
+          if (a.shape_terms) sgu += e * (Vt[k] + (hit ? U[k] : 0.f));
+        }
+        const float inv = 1.f / s;
+        sM[f] = m; sInv[f] = inv; sSg[f] = sgu * inv;
+        sCf[f] = a.w_ce * dn_focal(a.alpha, a.gamma, yv, ey * inv) * invD;
+      }
+      __syncthreads();
+      const int rl = gather ? rng[gy] : 0, rh = gather ? rng[8 + gy] : 0, cl = gather ? rng[16 + gx] : 0, chh = gather ? rng[24 + gx] : 0;
+      const float* wyG = wyT + gy * a.FBH;
+      const float* wxG = wxT + gx * a.FBW;
+      // (2) per class: plane, barrier, gather
+      for (int k = 0; k < K; ++k) {
+        float* pl = plane + (k & 1) * FB;
+        const float uk = U[k], vk = Vt[k];
+        for (int f = tid; f < bh * bw; f += NT) {
+          const int yv = sY[f];
+          float g = 0.f;
+          if (yv >= 0) {
+            const int Yr = f / bw, Xr = f - Yr * bw;
+            const float z = up_tap<ZT>(zb + k * zk, (yI0[Yr] - y0s) * zpitch, (yI1[Yr] - y0s) * zpitch, xI0[Xr] - x0s, xI1[Xr] - x0s, yL[Yr], xL[Xr]);
+            const float p = expf(z - sM[f]) * sInv[f];
+            const bool hit = yv == k;
+            g = sCf[f] * (p - (hit ? 1.f : 0.f));
+            if (a.shape_terms) g = p * ((vk + (hit ? uk : 0.f)) - sSg[f]) + g;
+            g = gout * g;
+          }
+          pl[f] = g;
+        }
+        __syncthreads();
+        float s = 0.f;
+        for (int Yr = rl + part; Yr < rh; Yr += a.G) {          // the group's threads take the pixel's block rows in turn, each row left to right
+          const float* pr = pl + Yr * bw;
+          float sr = 0.f;
+          for (int Xr = cl; Xr < chh; ++Xr) sr += wxG[Xr] * pr[Xr];
+          s += wyG[Yr] * sr;
+        }
+        for (int o = a.G >> 1; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+        if (gather && part == 0) acc[k * TP + gp] += s;
+      }
+    }
+  }
+  __syncthreads();
+  T* DL = reinterpret_cast<T*>(a.dlogits);
+  for (int e = tid; e < K * TP; e += NT) {
+    const int k = e / TP, p = e - k * TP;
+    const int py = p / a.TW, px = p - py * a.TW;
+    if (py < th && px < tw) DT<T>::st(DL + (((int64_t)b * K + k) * a.h + (ty0 + py)) * a.w + (tx0 + px), acc[e]);
+  }
+}
+
 // ---- host -----------------------------------------------------------------------------------------------------------------------------------------
 static int dn_rows(int B, int K, int64_t HW, int V, int cap) {
   const int64_t nchunks = (int64_t)B * dn_cdiv(HW, V);
@@ -548,5 +893,121 @@ extern "C" int lmv_dense_loss_bwd(const void* logits, int dtype, int64_t batch_s
   const int NT = 256, rows = (int)std::min<int64_t>(dn_cdiv(a.nchunks, NT), DN_MAX_WG_BWD);
   DN_DISPATCH(dense_bwd_kernel, dim3(rows), dim3(NT), 0, (hipStream_t)stream, a);
   LMV_CHECK_LAUNCH("dense_loss_bwd");
+  return LMV_OK;
+}
+
+// ---- the upsampling entry points ----
+namespace {
+static int up_rows(int B, int K, int H, int W) {
+  const int64_t nchunks = (int64_t)B * H * dn_cdiv(W, UP_V);
+  return (int)std::min<int64_t>(dn_cdiv(nchunks, dn_threads(K)), DN_MAX_WG);
+}
+
+static int up_validate(const char* fn, const void* logits, int dtype, int64_t sb, int64_t sc, int B, int K, int h, int w, int H, int W, int align_corners,
+                       const void* labels, bool need_labels, int label_dtype, const float* alpha, float gamma, float w_ce, float w_dice, float w_jac, float eps,
+                       int avg_mode) {
+  if (h < 1 || w < 1 || H < h || W < w)
+    LMV_FAIL(LMV_ERR_SHAPE, "%s: bad sizes %d x %d -> %d x %d (h >= 1, w >= 1, H >= h, W >= w: upsampling only)", fn, h, w, H, W);
+  if (B >= 1 && (int64_t)B * H * W >= (1ll << 31)) LMV_FAIL(LMV_ERR_SHAPE, "%s: bad shape B = %d, H W = %lld (B H W < 2^31)", fn, B, (long long)H * W);
+  if (align_corners != 0 && align_corners != 1) LMV_FAIL(LMV_ERR_SHAPE, "%s: align_corners = %d is neither 0 nor 1", fn, align_corners);
+  if (!labels && !need_labels) { labels = logits; label_dtype = LMV_DENSE_LABEL_U8; }          // prediction only: no label map to check
+  return dn_validate(fn, logits, dtype, sb, sc, B, K, (int64_t)h * w, labels, label_dtype,
+                     alpha, gamma, w_ce, w_dice, w_jac, eps, avg_mode);
+}
+
+static float up_scale(int in, int out, int align) { return align ? (out > 1 ? (float)(in - 1) / (float)(out - 1) : 0.f) : (float)in / (float)out; }
+
+// one axis of the backward's tiling: the largest tile of 8, 4, 2, 1 input indices whose footprint of about (T + 1) out / in output indices is at most two blocks
+// of UP_FB (the softmax of the footprint's margin is evaluated by the neighbouring tiles too: (T + 1)^2 / T^2 of the work, so a larger tile in more blocks wins)
+static void up_tile(int in, int out, int* T, int* FBd) {
+  const int r = (out + in - 1) / in;
+  int t = 8;
+  while (t > 1 && ((t + 1) * r > 2 * UP_FB || t >= 2 * in)) t >>= 1;
+  *T = t;
+  *FBd = std::min(std::min(UP_FB, (t + 1) * r + 2), out);
+}
+
+static UpArgs up_args(const void* logits, int64_t sb, int64_t sc, int B, int K, int h, int w, int H, int W, int align, const void* labels, int64_t ignore,
+                      const float* alpha, float gamma, float w_ce, float w_dice, float w_jac) {
+  UpArgs a = {};
+  a.logits = logits; a.labels = labels; a.alpha = alpha;
+  a.sb = sb; a.sc = sc; a.ignore = ignore;
+  a.B = B; a.K = K; a.h = h; a.w = w; a.H = H; a.W = W; a.align = align;
+  a.cpr = (int)dn_cdiv(W, UP_V); a.nchunks = (int64_t)B * H * a.cpr;
+  a.sy = up_scale(h, H, align); a.sx = up_scale(w, W, align);
+  a.gamma = gamma; a.w_ce = w_ce; a.shape_terms = (w_dice != 0.f || w_jac != 0.f) ? 1 : 0;
+  return a;
+}
+
+#define UP_DISPATCH_BWD(STAGE, ...)                                                                                                 \
+  do {                                                                                                                              \
+    if (dtype == LMV_F32) {                                                                                                         \
+      if (label_dtype == LMV_DENSE_LABEL_I64) hipLaunchKernelGGL((dense_up_bwd_kernel<float, int64_t, STAGE>), __VA_ARGS__);        \
+      else hipLaunchKernelGGL((dense_up_bwd_kernel<float, uint8_t, STAGE>), __VA_ARGS__);                                           \
+    } else {                                                                                                                        \
+      if (label_dtype == LMV_DENSE_LABEL_I64) hipLaunchKernelGGL((dense_up_bwd_kernel<bf16_t, int64_t, STAGE>), __VA_ARGS__);       \
+      else hipLaunchKernelGGL((dense_up_bwd_kernel<bf16_t, uint8_t, STAGE>), __VA_ARGS__);                                          \
+    }                                                                                                                               \
+  } while (0)
+}  // namespace
+
+extern "C" size_t lmv_dense_up_loss_workspace_bytes(int B, int K, int H, int W) {
+  if (B < 1 || H < 1 || W < 1 || K < 2 || K > LMV_DENSE_MAX_CLASSES || (int64_t)B * H * W >= (1ll << 31)) return 0;
+  return (size_t)up_rows(B, K, H, W) * (size_t)(3 * K + 3) * sizeof(float);
+}
+
+extern "C" int lmv_dense_up_loss_fwd(const void* logits, int dtype, int64_t batch_stride, int64_t class_stride, int B, int K, int h, int w, int H, int W,
+                                     int align_corners, const void* labels, int label_dtype, int64_t ignore_index, const float* alpha, float gamma, float w_ce,
+                                     float w_dice, float w_jac, float eps, int avg_mode, void* workspace, size_t workspace_bytes, float* stats, uint8_t* pred,
+                                     int64_t* conf, double* meter, void* stream) {
+  const char* fn = "dense_up_loss_fwd";
+  if (!labels && !pred && logits) LMV_FAIL(LMV_ERR_SHAPE, "%s: null labels and null pred: nothing to compute", fn);
+  if (int rc = up_validate(fn, logits, dtype, batch_stride, class_stride, B, K, h, w, H, W, align_corners, labels, pred == nullptr, label_dtype, alpha, gamma, w_ce,
+                           w_dice, w_jac, eps, avg_mode)) return rc;
+  const int rows = up_rows(B, K, H, W), NT = dn_threads(K);
+  if (labels) {
+    if (!workspace || !stats) LMV_FAIL(LMV_ERR_SHAPE, "%s: null workspace / stats", fn);
+    if ((((uintptr_t)workspace) & 3u) || (((uintptr_t)stats) & 3u) || (((uintptr_t)conf) & 7u) || (((uintptr_t)meter) & 7u)) LMV_FAIL(LMV_ERR_SHAPE, "%s: misaligned buffer", fn);
+    if (workspace_bytes < (size_t)rows * (size_t)(3 * K + 3) * sizeof(float))
+      LMV_FAIL(LMV_ERR_SHAPE, "%s: workspace of %zu bytes, %zu needed (lmv_dense_up_loss_workspace_bytes)", fn, workspace_bytes, (size_t)rows * (size_t)(3 * K + 3) * sizeof(float));
+  }
+  UpArgs a = up_args(logits, batch_stride, class_stride, B, K, h, w, H, W, align_corners, labels, ignore_index, alpha, gamma, w_ce, w_dice, w_jac);
+  a.ws = reinterpret_cast<float*>(workspace); a.pred = pred; a.conf = labels ? reinterpret_cast<unsigned long long*>(conf) : nullptr;
+  if (!labels) label_dtype = LMV_DENSE_LABEL_U8;
+  const int nw = NT / 64;
+  const size_t lds = (K <= DN_KREG ? (size_t)nw * (3 * K + 3) : (size_t)2 * K * NT + K + (size_t)nw * 3) * sizeof(float) + (a.conf ? (size_t)K * K * sizeof(int) : 0);
+  hipStream_t st = (hipStream_t)stream;
+  DN_DISPATCH(dense_up_fwd_kernel, dim3(rows), dim3(NT), lds, st, a);
+  LMV_CHECK_LAUNCH("dense_up_loss_fwd");
+  if (!labels) return LMV_OK;
+  DenseFinArgs f;
+  f.ws = a.ws; f.alpha = alpha; f.stats = stats; f.meter = meter; f.rows = rows; f.K = K; f.avg_mode = avg_mode;
+  f.npix = (double)B * (double)H * (double)W; f.w_ce = w_ce; f.w_dice = w_dice; f.w_jac = w_jac; f.eps = eps;
+  hipLaunchKernelGGL(dense_finalize_kernel, dim3(1), dim3(256), 0, st, f);
+  LMV_CHECK_LAUNCH("dense_up_loss_fwd (finalize)");
+  return LMV_OK;
+}
+
+extern "C" int lmv_dense_up_loss_bwd(const void* logits, int dtype, int64_t batch_stride, int64_t class_stride, int B, int K, int h, int w, int H, int W,
+                                     int align_corners, const void* labels, int label_dtype, int64_t ignore_index, const float* alpha, float gamma, float w_ce,
+                                     float w_dice, float w_jac, float eps, int avg_mode, const float* stats, const float* gout, void* dlogits, void* stream) {
+  const char* fn = "dense_up_loss_bwd";
+  if (int rc = up_validate(fn, logits, dtype, batch_stride, class_stride, B, K, h, w, H, W, align_corners, labels, true, label_dtype, alpha, gamma, w_ce, w_dice,
+                           w_jac, eps, avg_mode)) return rc;
+  if (!stats || !dlogits) LMV_FAIL(LMV_ERR_SHAPE, "%s: null stats / dlogits", fn);
+  if ((((uintptr_t)stats) & 3u) || (((uintptr_t)gout) & 3u) || (((uintptr_t)dlogits) & (dtype == LMV_F32 ? 3u : 1u))) LMV_FAIL(LMV_ERR_SHAPE, "%s: misaligned buffer", fn);
+  UpArgs a = up_args(logits, batch_stride, class_stride, B, K, h, w, H, W, align_corners, labels, ignore_index, alpha, gamma, w_ce, w_dice, w_jac);
+  a.stats = stats; a.gout = gout; a.dlogits = dlogits;
+  up_tile(h, H, &a.TH, &a.FBH);
+  up_tile(w, W, &a.TW, &a.FBW);
+  a.tiles_y = (int)dn_cdiv(h, a.TH); a.tiles_x = (int)dn_cdiv(w, a.TW);
+  const int TP = a.TH * a.TW;
+  a.G = std::min(64, 256 / TP);
+  const size_t lds = ((size_t)7 * a.FBH * a.FBW + (size_t)K * TP + 3 * (size_t)(a.FBH + a.FBW) + (size_t)a.TH * a.FBH + (size_t)a.TW * a.FBW + 32) * sizeof(float);
+  const size_t lds_stage = lds + (size_t)K * (a.TH + 2) * (a.TW + 2) * sizeof(float);          // the logits tile too, where the default 64 KB of LDS hold it
+  const dim3 grid((unsigned)((int64_t)B * a.tiles_y * a.tiles_x));
+  if (lds_stage <= 65536) UP_DISPATCH_BWD(true, grid, dim3(256), lds_stage, (hipStream_t)stream, a);
+  else UP_DISPATCH_BWD(false, grid, dim3(256), lds, (hipStream_t)stream, a);
+  LMV_CHECK_LAUNCH("dense_up_loss_bwd");
   return LMV_OK;
 }

@@ -17,6 +17,15 @@ One pass over NCHW logits (float32 / bfloat16, any batch and class strides) and 
 ``I_k = sum p_k [y = k]``, ``P_k = sum p_k``, ``T_k = sum [y = k]`` and the focal / plain negative log-likelihood; include/lemevit_hip.h states the formulas and the
 closed-form gradient, ``reference_dense`` restates them in numpy float64 (the oracle of the tests).  A pixel whose label equals ``ignore_index`` or lies outside
 ``[0, K)`` is not a sample: it contributes to no sum, count or gradient.  No floating-point atomics: two runs agree bit for bit.
+
+Low-resolution logits (``upsample=True``): every head of the reference upsamples its logits bilinearly in front of the loss (change_detection/models/Models.py:221,
+``scale_factor=4, align_corners=True``; the segmentation heads' ``resize(seg_logit, size=seg_label.shape[2:])``, ``align_corners=False``, 4x / 16x).  With
+``upsample=True`` a prediction smaller than the label map goes through lmv_dense_up_loss_fwd / _bwd, which interpolate inside the pass: the [B, K, H, W] map and its
+gradient never exist, and the gradient arrives at [B, K, h, w] from one launch.  ``predict`` is the label-free form (resize + argmax at inference).
+
+    crit = DenseLoss(ignore_index=255, upsample=True)           # decode head: loss on the 4x smaller logits, as mmseg's resize + CrossEntropyLoss
+    cd = DenseLoss(ce=1.0, dice=1.0, avg="all", upsample=True, align_corners=True)          # hybrid_loss on the logits in front of Models.py:221's interpolate
+    seg = predict(logits, size=img.shape[-2:])                  # uint8 [B, H, W]
 """
 from __future__ import annotations
 
@@ -29,7 +38,7 @@ from torch import Tensor, nn
 
 from . import _lib, ops
 
-__all__ = ["DenseLoss", "SegMeter", "hybrid_loss", "dice_loss", "jaccard_loss", "FocalLoss", "DenseCrossEntropy", "reference_dense", "seg_metrics"]
+__all__ = ["DenseLoss", "SegMeter", "hybrid_loss", "dice_loss", "jaccard_loss", "FocalLoss", "DenseCrossEntropy", "reference_dense", "seg_metrics", "predict"]
 
 
 def _alpha32(alpha, K: Optional[int] = None) -> Optional[Tensor]:
@@ -44,21 +53,31 @@ def _alpha32(alpha, K: Optional[int] = None) -> Optional[Tensor]:
     return t.contiguous()
 
 
+def _size_differs(logits: Tensor, target: Tensor) -> bool:
+    """[B, K, h, w] logits whose (h, w) is not the label map's (H, W): the upsampling kernels' case (they refuse H < h or W < w)"""
+    return logits.dim() == 4 and target.dim() in (3, 4) and tuple(target.shape[-2:]) != tuple(logits.shape[-2:])
+
+
 class _DenseLossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits: Tensor, target: Tensor, crit: "DenseLoss", meter: Optional["SegMeter"]):
         alpha = crit._alpha_on(logits.device, logits.shape[1] if logits.dim() == 4 else None)
+        up = crit.upsample and _size_differs(logits, target)          # a prediction of the target's size takes the plain kernels
         pred = conf = state = None
         if meter is not None:
             if logits.dim() == 4:
                 meter._check(logits.shape[1], crit.ignore_index)
-            pred, conf, state = meter._outputs(logits)
-        stats = ops.dense_loss_fwd(logits, target, crit.ignore_index, alpha, crit.gamma, crit.ce, crit.dice, crit.jaccard, crit.eps, crit.avg,
-                                   pred=pred, conf=conf, meter=state)
+            pred, conf, state = meter._outputs(logits, tuple(target.shape[-2:]) if up else None)
+        if up:
+            stats = ops.dense_up_loss_fwd(logits, target, crit.align_corners, crit.ignore_index, alpha, crit.gamma, crit.ce, crit.dice, crit.jaccard, crit.eps,
+                                          crit.avg, pred=pred, conf=conf, meter=state)
+        else:
+            stats = ops.dense_loss_fwd(logits, target, crit.ignore_index, alpha, crit.gamma, crit.ce, crit.dice, crit.jaccard, crit.eps, crit.avg,
+                                       pred=pred, conf=conf, meter=state)
         if meter is not None:
             meter.pred = pred
         ctx.save_for_backward(logits, target, stats)
-        ctx.crit, ctx.alpha = crit, alpha
+        ctx.crit, ctx.alpha, ctx.up = crit, alpha, up
         crit.last = dict(ce=stats[1], dice=stats[2], jaccard=stats[3], n_valid=stats[4])
         return stats[0]
 
@@ -68,7 +87,11 @@ class _DenseLossFn(torch.autograd.Function):
         crit = ctx.crit
         if grad_out.dtype != torch.float32:
             grad_out = grad_out.float()
-        dl = ops.dense_loss_bwd(logits, target, stats, crit.ignore_index, ctx.alpha, crit.gamma, crit.ce, crit.dice, crit.jaccard, crit.eps, crit.avg, gout=grad_out)
+        if ctx.up:
+            dl = ops.dense_up_loss_bwd(logits, target, stats, crit.align_corners, crit.ignore_index, ctx.alpha, crit.gamma, crit.ce, crit.dice, crit.jaccard, crit.eps,
+                                       crit.avg, gout=grad_out)
+        else:
+            dl = ops.dense_loss_bwd(logits, target, stats, crit.ignore_index, ctx.alpha, crit.gamma, crit.ce, crit.dice, crit.jaccard, crit.eps, crit.avg, gout=grad_out)
         return dl, None, None, None
 
 
@@ -84,11 +107,17 @@ class DenseLoss(nn.Module):
     it); ``avg``: ``"valid"`` (D = the valid pixels: ``F.cross_entropy(ignore_index=)``), ``"all"`` (D = B H W: the reference's ``.mean()``) or ``"weight"``
     (D = sum of ``alpha[y]``: ``F.cross_entropy(weight=)``).  ``dice`` / ``jaccard``: the reference's ``dice_loss`` / ``jaccard_loss`` over the valid pixels.
     ``crit.last``: the components of the last prediction evaluated (``ce``, ``dice``, ``jaccard``, ``n_valid``) as device scalars.  ``meter``: a ``SegMeter``
-    that the same forward launch updates with the (last) prediction -- the train loop's ``cd_corrects`` for free."""
+    that the same forward launch updates with the (last) prediction -- the train loop's ``cd_corrects`` for free.
+
+    ``upsample=True``: a prediction [B, K, h, w] smaller than the target's (H, W) is evaluated as ``F.interpolate(logits, size=(H, W), mode="bilinear",
+    align_corners=align_corners)`` would be, inside the pass (``lmv_dense_up_loss_fwd`` / ``_bwd``, the same launch counts): the gradient has the prediction's own
+    shape, ``meter.pred`` the target's resolution.  Every prediction of a list may have its own size; one of the target's size takes the plain kernels.  A larger
+    prediction raises (no downsampling).  ``upsample=False`` (the default): a size mismatch raises, as before."""
 
     def __init__(self, ce: float = 1.0, dice: float = 0.0, jaccard: float = 0.0, gamma: float = 0.0, alpha=None, ignore_index: Optional[int] = None,
-                 avg: str = "valid", eps: float = 1e-7):
+                 avg: str = "valid", eps: float = 1e-7, upsample: bool = False, align_corners: bool = False):
         super().__init__()
+        self.upsample, self.align_corners = bool(upsample), bool(align_corners)
         self.ce, self.dice, self.jaccard, self.gamma, self.eps = float(ce), float(dice), float(jaccard), float(gamma), float(eps)
         if not (self.ce >= 0.0 and self.dice >= 0.0 and self.jaccard >= 0.0):
             raise ValueError(f"DenseLoss: negative loss weight ({ce}, {dice}, {jaccard})")
@@ -139,11 +168,14 @@ def _crit(**kw) -> DenseLoss:
     return c
 
 
-def hybrid_loss(predictions, target) -> Tensor:
-    """The reference's ``hybrid_loss``: for every prediction of the list ``FocalLoss(gamma=0, alpha=None)`` (plain cross-entropy, mean over all pixels) plus ``dice_loss``."""
+def hybrid_loss(predictions, target, upsample: bool = False, align_corners: bool = False) -> Tensor:
+    """The reference's ``hybrid_loss``: for every prediction of the list ``FocalLoss(gamma=0, alpha=None)`` (plain cross-entropy, mean over all pixels) plus ``dice_loss``.
+    ``upsample=True, align_corners=True``: on the logits in front of Models.py:221's ``F.interpolate``, which the training path then drops."""
     if isinstance(predictions, Tensor):          # (the reference would iterate over the images of the batch and sum per-image losses)
         raise TypeError("hybrid_loss: a list or tuple of [B, K, H, W] predictions expected; wrap a single prediction in a list")
-    return _crit(ce=1.0, dice=1.0, avg="all")(list(predictions), target)
+    if not upsample:
+        return _crit(ce=1.0, dice=1.0, avg="all")(list(predictions), target)
+    return _crit(ce=1.0, dice=1.0, avg="all", upsample=True, align_corners=bool(align_corners))(list(predictions), target)
 
 
 def dice_loss(logits: Tensor, true: Tensor, eps: float = 1e-7) -> Tensor:
@@ -170,12 +202,15 @@ class FocalLoss(nn.Module):
 
 class DenseCrossEntropy(nn.Module):
     """The segmentation heads' ``CrossEntropyLoss(use_sigmoid=False)``: per-pixel cross-entropy with ``ignore_index``, optional ``class_weight`` and ``loss_weight``;
-    ``avg_non_ignore=True`` averages over the valid pixels, ``False`` over all of them (the older behaviour).  ``forward(cls_score, label)``."""
+    ``avg_non_ignore=True`` averages over the valid pixels, ``False`` over all of them (the older behaviour).  ``forward(cls_score, label)``.
+    ``upsample=True``: ``cls_score`` is the head's low-resolution logit map and mmseg's ``resize(seg_logit, size=seg_label.shape[2:])`` happens inside the pass."""
 
-    def __init__(self, ignore_index: int = -100, loss_weight: float = 1.0, class_weight=None, avg_non_ignore: bool = True):
+    def __init__(self, ignore_index: int = -100, loss_weight: float = 1.0, class_weight=None, avg_non_ignore: bool = True, upsample: bool = False,
+                 align_corners: bool = False):
         super().__init__()
         self.ignore_index, self.loss_weight, self.class_weight, self.avg_non_ignore = ignore_index, loss_weight, class_weight, avg_non_ignore
-        self.crit = DenseLoss(ce=float(loss_weight), alpha=class_weight, ignore_index=ignore_index, avg="valid" if avg_non_ignore else "all")
+        self.crit = DenseLoss(ce=float(loss_weight), alpha=class_weight, ignore_index=ignore_index, avg="valid" if avg_non_ignore else "all", upsample=upsample,
+                              align_corners=align_corners)
 
     def forward(self, cls_score: Tensor, label: Tensor, **kwargs) -> Tensor:
         return self.crit(cls_score, label)
@@ -212,9 +247,13 @@ class SegMeter:
     ``update(logits, target)``: the forward pass of ``lmv_dense_loss_fwd`` in metrics mode (two launches, no synchronisation, no allocation after the first call
     for a shape); ``pred`` keeps the last batch's argmax map (uint8 [B, H, W]).  ``DenseLoss(...)(x, y, meter=m)`` leaves the same state from the loss's own pass.
     Capture: ``update`` can be captured once the state and the buffers of that shape exist (one eager ``update``, then ``reset()``); under capture it raises when
-    they do not.  ``compute()`` is the only synchronisation."""
+    they do not.  ``compute()`` is the only synchronisation.
 
-    def __init__(self, num_classes: int, ignore_index: Optional[int] = None):
+    ``upsample=True``: ``update(low_res_logits, target)`` interpolates inside the pass (``lmv_dense_up_loss_fwd``) when the sizes differ; ``pred`` has the target's
+    resolution.  The same rules for allocation and capture; the buffers are kept per ``(B, h, w, H, W)``."""
+
+    def __init__(self, num_classes: int, ignore_index: Optional[int] = None, upsample: bool = False, align_corners: bool = False):
+        self.upsample, self.align_corners = bool(upsample), bool(align_corners)
         self.num_classes = int(num_classes)
         if not 2 <= self.num_classes <= _lib.DENSE_MAX_CLASSES:
             raise ValueError(f"SegMeter: num_classes = {num_classes} outside 2 .. {_lib.DENSE_MAX_CLASSES}")
@@ -234,8 +273,9 @@ class SegMeter:
         if ignore_index != self.ignore_index:
             raise ValueError(f"SegMeter: the loss ignores label {ignore_index}, the meter {self.ignore_index} -- one pass serves both, they must agree")
 
-    def _outputs(self, logits: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
-        """(pred, conf, loss state) for a batch of this shape; allocated on first use, never under capture"""
+    def _outputs(self, logits: Tensor, size: Optional[Tuple[int, int]] = None) -> Tuple[Tensor, Tensor, Tensor]:
+        """(pred, conf, loss state) for a batch of this shape; allocated on first use, never under capture.  ``size``: the label map's (H, W) when the logits are
+        upsampled to it inside the pass"""
         if logits.dim() != 4:
             raise ValueError(f"SegMeter: [B, K, H, W] logits expected, got {tuple(logits.shape)}")
         if not logits.is_cuda:
@@ -247,23 +287,29 @@ class SegMeter:
                 raise RuntimeError("SegMeter: under graph capture the state must exist -- run one eager update first")
             K = self.num_classes
             self.conf, self.loss = torch.zeros((K, K), device=dev, dtype=torch.int64), torch.zeros((2,), device=dev, dtype=torch.float64)
-        B, K, H, W = logits.shape
-        key = (B, H, W, dev)
+        B, K, h, w = logits.shape
+        H, W = (h, w) if size is None else (int(size[0]), int(size[1]))
+        key = (B, h, w, H, W, dev)
         buf = self._buffers.get(key)
         if buf is None:
             if capturing:
                 raise RuntimeError("SegMeter: under graph capture the buffers must exist for this batch shape -- run one eager update first")
             buf = (torch.empty((B, H, W), device=dev, dtype=torch.uint8), torch.empty((ops.dense_stats_floats(K),), device=dev, dtype=torch.float32),
-                   ops.dense_workspace(B, K, H * W, dev))
+                   ops.dense_workspace(B, K, H * W, dev) if size is None else ops.dense_up_workspace(B, K, H, W, dev))
             self._buffers[key] = buf
         return buf[0], self.conf, self.loss
 
     def update(self, logits: Tensor, target: Tensor) -> None:
         if logits.dim() == 4:
             self._check(logits.shape[1], self.ignore_index)
-        pred, conf, loss = self._outputs(logits)
-        _, stats, ws = self._buffers[(logits.shape[0], logits.shape[2], logits.shape[3], logits.device)]
-        ops.dense_loss_fwd(logits.detach(), target, self.ignore_index, workspace=ws, stats=stats, pred=pred, conf=conf, meter=loss)
+        size = tuple(target.shape[-2:]) if self.upsample and _size_differs(logits, target) else None
+        pred, conf, loss = self._outputs(logits, size)
+        B, _, h, w = logits.shape
+        _, stats, ws = self._buffers[(B, h, w) + ((h, w) if size is None else (int(size[0]), int(size[1]))) + (logits.device,)]
+        if size is None:
+            ops.dense_loss_fwd(logits.detach(), target, self.ignore_index, workspace=ws, stats=stats, pred=pred, conf=conf, meter=loss)
+        else:
+            ops.dense_up_loss_fwd(logits.detach(), target, self.align_corners, self.ignore_index, workspace=ws, stats=stats, pred=pred, conf=conf, meter=loss)
         self.pred = pred
 
     def merge(self, states: Iterable[Tuple[Tensor, Tensor]]) -> "SegMeter":
@@ -298,13 +344,42 @@ class SegMeter:
             self.loss.zero_()
 
 
+def predict(logits: Tensor, size: Optional[Tuple[int, int]] = None, align_corners: bool = False) -> Tensor:
+    """The label-free form, mmseg's ``resize(seg_logit, size=img_size, mode="bilinear")`` + ``argmax(dim=1)`` at inference in ONE launch without the resized map:
+    ``logits`` [B, K, h, w] float32 / bfloat16 -> uint8 [B, H, W] (``size=None``: the logits' own size), by the argmax rule of the loss pass."""
+    if logits.dim() != 4:
+        raise ValueError(f"predict: [B, K, h, w] logits expected, got {tuple(logits.shape)}")
+    H, W = (int(logits.shape[2]), int(logits.shape[3])) if size is None else (int(size[0]), int(size[1]))
+    pred = torch.empty((logits.shape[0], H, W), device=logits.device, dtype=torch.uint8)
+    ops.dense_up_loss_fwd(logits.detach(), None, align_corners, pred=pred, size=(H, W))
+    return pred
+
+
+def _up_matrix(out: int, inn: int, align_corners: bool) -> np.ndarray:
+    """[out, in] float64: row ``dst`` holds the two bilinear weights of PyTorch's upsample_bilinear2d (include/lemevit_hip.h states the index formulas)"""
+    d = np.arange(out, dtype=np.float64)
+    if align_corners:
+        src = d * ((inn - 1) / (out - 1)) if out > 1 else np.zeros(out)
+    else:
+        src = np.maximum(0.0, (d + 0.5) * inn / out - 0.5)
+    i0 = np.minimum(np.floor(src).astype(np.int64), inn - 1)
+    i1 = np.minimum(i0 + 1, inn - 1)
+    l = src - i0
+    m = np.zeros((out, inn), dtype=np.float64)
+    np.add.at(m, (np.arange(out), i0), 1.0 - l)
+    np.add.at(m, (np.arange(out), i1), l)
+    return m
+
+
 # ---- the oracle -----------------------------------------------------------------------------------------------------------------------------------
 def reference_dense(logits, labels, ce: float = 1.0, dice: float = 0.0, jaccard: float = 0.0, gamma: float = 0.0, alpha=None, ignore_index: Optional[int] = None,
-                    avg: str = "valid", eps: float = 1e-7, gout: float = 1.0) -> dict:
+                    avg: str = "valid", eps: float = 1e-7, gout: float = 1.0, upsample: Optional[Tuple[int, int]] = None, align_corners: bool = False) -> dict:
     """The host restatement of ``lmv_dense_loss_fwd`` / ``lmv_dense_loss_bwd`` in numpy float64 -- the oracle of the tests.  ``logits`` [B, K, H, W] (a float32 /
     bfloat16 / float64 tensor or an array: evaluated ON THE ALREADY ROUNDED values), ``labels`` [B, H, W] / [B, 1, H, W] of any integer type, ``alpha`` passed
     through float32.  Returns ``dict(loss, ce, dice, jaccard, n_valid, D, inv_D, I, P, T, u, v, stats (float64 [6 + 5 K], the device layout), dlogits
-    (float64 [B, K, H, W]), pred (uint8 [B, H, W]), conf (int64 [K, K]), nll_sum)``."""
+    (float64 [B, K, H, W]), pred (uint8 [B, H, W]), conf (int64 [K, K]), nll_sum, margin (float64 [B, H, W]: the largest minus the second largest logit))``.
+    ``upsample=(H, W)``: the logits [B, K, h, w] are first interpolated bilinearly to (H, W) in float64 (``z`` of the result, [B, K, H, W]); everything is then
+    evaluated at that resolution except ``dlogits``, which is the transposed interpolation of the high-resolution gradient, [B, K, h, w]."""
     if isinstance(logits, Tensor):
         x = logits.detach().cpu().to(torch.float64).numpy()
     else:
@@ -312,8 +387,15 @@ def reference_dense(logits, labels, ce: float = 1.0, dice: float = 0.0, jaccard:
     y = labels.detach().cpu().numpy() if isinstance(labels, Tensor) else np.asarray(labels)
     if x.ndim != 4 or avg not in ops.DENSE_AVG:
         raise ValueError("reference_dense: bad arguments")
+    up = None
+    if upsample is not None and (int(upsample[0]), int(upsample[1])) != tuple(x.shape[2:]):
+        if int(upsample[0]) < x.shape[2] or int(upsample[1]) < x.shape[3]:
+            raise ValueError("reference_dense: upsampling only")
+        up = (_up_matrix(int(upsample[0]), x.shape[2], align_corners), _up_matrix(int(upsample[1]), x.shape[3], align_corners))
+        x = np.matmul(np.matmul(up[0], x), up[1].T)          # [H, h] [B, K, h, w] [w, W]
     B, K, H, W = x.shape
     HW = H * W
+    z_hi = x
     x = x.reshape(B, K, HW)
     y = y.astype(np.int64).reshape(B, HW)
     valid = (y >= 0) & (y < K)
@@ -351,7 +433,13 @@ def reference_dense(logits, labels, ce: float = 1.0, dice: float = 0.0, jaccard:
         pred = np.where(nanm.any(1), nanm.argmax(1), np.where(nanm, -np.inf, x).argmax(1)).astype(np.uint8)
     conf = np.zeros((K, K), dtype=np.int64)
     np.add.at(conf, (y[valid], pred[valid].astype(np.int64)), 1)
+    with np.errstate(all="ignore"):
+        top = np.sort(np.where(nanm, np.inf, x), axis=1)
+        margin = (top[:, -1] - top[:, -2]).reshape(B, H, W)
+    dz = dz.reshape(B, K, H, W)
+    if up is not None:
+        dz = np.matmul(np.matmul(up[0].T, dz), up[1])          # the transposed interpolation
     loss = ce * ce_v + dice * dice_v + jaccard * jac_v
     stats = np.concatenate([[loss, ce_v, dice_v, jac_v, n_valid, inv_D], u, v, I, P, T])
     return dict(loss=loss, ce=ce_v, dice=dice_v, jaccard=jac_v, n_valid=int(n_valid), D=D, inv_D=inv_D, I=I, P=P, T=T.astype(np.int64), u=u, v=v, stats=stats,
-                dlogits=dz.reshape(B, K, H, W), pred=pred.reshape(B, H, W), conf=conf, nll_sum=float(nll_v.sum()))
+                dlogits=dz, pred=pred.reshape(B, H, W), conf=conf, nll_sum=float(nll_v.sum()), margin=margin, z=z_hi)

@@ -1119,6 +1119,119 @@ def dense_loss_bwd(logits: Tensor, labels: Tensor, stats: Tensor, ignore_index: 
     return out
 
 
+def dense_up_workspace(B: int, K: int, H: int, W: int, device) -> Tensor:
+    """A workspace of lmv_dense_up_loss_workspace_bytes(B, K, H, W) for ``dense_up_loss_fwd``; (H, W) is the label map's size."""
+    n = lib.lmv_dense_up_loss_workspace_bytes(int(B), int(K), int(H), int(W))
+    if n == 0:
+        raise ValueError(f"dense_up_workspace: bad shape B = {B}, K = {K}, H = {H}, W = {W} (B >= 1, 2 <= K <= {_lib.DENSE_MAX_CLASSES}, B H W < 2^31)")
+    return torch.empty((n,), device=device, dtype=torch.uint8)
+
+
+def _dense_up_args(fn: str, logits: Tensor, labels: Optional[Tensor], size, align_corners, ignore_index, alpha, gamma, w_ce, w_dice, w_jac, eps, avg):
+    """The checks of ``_dense_args`` for low-resolution logits; ``(H, W)`` comes from the labels, or from ``size`` when there are none (prediction only)."""
+    if logits.dim() != 4:
+        raise ValueError(f"{fn}: [B, K, h, w] logits expected, got {tuple(logits.shape)}")
+    B, K, h, w = logits.shape
+    if not 2 <= K <= _lib.DENSE_MAX_CLASSES:
+        raise ValueError(f"{fn}: K = {K} classes outside 2 .. {_lib.DENSE_MAX_CLASSES}")
+    if labels is not None:
+        if labels.dtype not in (torch.int64, torch.uint8):
+            raise TypeError(f"{fn}: labels must be int64 or uint8, got {labels.dtype}")
+        if labels.dim() not in (3, 4) or labels.shape[0] != B or (labels.dim() == 4 and labels.shape[1] != 1) or labels.device != logits.device:
+            raise ValueError(f"{fn}: labels must be [B, H, W] or [B, 1, H, W] on the logits' device, got {tuple(labels.shape)}")
+        if not labels.is_contiguous():
+            raise ValueError(f"{fn}: the label map must be contiguous")
+        H, W = int(labels.shape[-2]), int(labels.shape[-1])
+        if size is not None and (int(size[0]), int(size[1])) != (H, W):
+            raise ValueError(f"{fn}: size = {tuple(size)} is not the label map's {(H, W)}")
+    else:
+        if size is None:
+            raise ValueError(f"{fn}: without labels the output size must be given")
+        H, W = int(size[0]), int(size[1])
+    if B < 1 or h < 1 or w < 1 or H < h or W < w or B * H * W >= 1 << 31:
+        raise ValueError(f"{fn}: bad sizes {tuple(logits.shape)} -> {(H, W)} (B >= 1, h >= 1, w >= 1, H >= h, W >= w: upsampling only, B H W < 2^31)")
+    if (w > 1 and logits.stride(3) != 1) or (h > 1 and logits.stride(2) != w):
+        raise ValueError(f"{fn}: the logits must have unit pixel stride (NCHW planes; channels-last logits are not supported)")
+    sc = logits.stride(1)
+    sb = logits.stride(0) if B > 1 else (K - 1) * sc + h * w
+    if sc < h * w or sb < (K - 1) * sc + h * w:
+        raise ValueError(f"{fn}: overlapping class planes or images (strides {logits.stride()})")
+    if not logits.is_cuda or (labels is not None and not labels.is_cuda):          # (after the sizes and the layout: those refusals need no device)
+        raise RuntimeError("lemevit_amd: tensors must be on the GPU (no CPU fallback exists)")
+    code = dtype_code(logits)
+    if alpha is not None and (alpha.dtype != torch.float32 or tuple(alpha.shape) != (K,) or alpha.device != logits.device or not alpha.is_contiguous()):
+        raise TypeError(f"{fn}: alpha must be a contiguous float32 vector [{K}] on the logits' device")
+    if not (float(w_ce) >= 0.0 and float(w_dice) >= 0.0 and float(w_jac) >= 0.0):
+        raise ValueError(f"{fn}: negative loss weight ({w_ce}, {w_dice}, {w_jac})")
+    if not float(gamma) >= 0.0:
+        raise ValueError(f"{fn}: gamma = {gamma} < 0")
+    if not float(eps) > 0.0:
+        raise ValueError(f"{fn}: eps = {eps} <= 0")
+    if avg not in DENSE_AVG:
+        raise ValueError(f"{fn}: avg must be one of {sorted(DENSE_AVG)}, got {avg!r}")
+    ign = -1 if ignore_index is None else int(ignore_index)
+    ldt = _lib.DENSE_LABEL_U8 if labels is None or labels.dtype == torch.uint8 else _lib.DENSE_LABEL_I64
+    head = (logits.data_ptr(), code, sb, sc, B, K, h, w, H, W, 1 if align_corners else 0, _ptr(labels), ldt, ign,
+            None if alpha is None else alpha.data_ptr(), float(gamma), float(w_ce), float(w_dice), float(w_jac), float(eps), DENSE_AVG[avg])
+    return head, B, K, H, W
+
+
+def dense_up_loss_fwd(logits: Tensor, labels: Optional[Tensor], align_corners: bool = False, ignore_index: Optional[int] = None, alpha: Optional[Tensor] = None,
+                      gamma: float = 0.0, w_ce: float = 1.0, w_dice: float = 0.0, w_jac: float = 0.0, eps: float = 1e-7, avg: str = "valid",
+                      workspace: Optional[Tensor] = None, stats: Optional[Tensor] = None, pred: Optional[Tensor] = None, conf: Optional[Tensor] = None,
+                      meter: Optional[Tensor] = None, size: Optional[Tuple[int, int]] = None) -> Optional[Tensor]:
+    """lmv_dense_up_loss_fwd: ``dense_loss_fwd`` on ``F.interpolate(logits, size=labels.shape[-2:], mode="bilinear", align_corners=)`` without that map:
+    ``logits`` [B, K, h, w], ``labels`` [B, H, W] / [B, 1, H, W] with H >= h, W >= w.  The other arguments, ``stats`` and the optional outputs are those of
+    ``dense_loss_fwd``; ``pred`` has the LABEL map's resolution, ``workspace`` comes from ``dense_up_workspace``.  ``labels=None`` with ``pred`` and ``size=(H, W)``
+    is prediction only (one launch, returns None)."""
+    head, B, K, H, W = _dense_up_args("dense_up_loss_fwd", logits, labels, size, align_corners, ignore_index, alpha, gamma, w_ce, w_dice, w_jac, eps, avg)
+    dev = logits.device
+    if pred is not None and (pred.dtype != torch.uint8 or pred.numel() != B * H * W or pred.device != dev or not pred.is_contiguous()):
+        raise TypeError(f"dense_up_loss_fwd: pred must be a contiguous uint8 tensor of {B} x {H * W} entries on the logits' device")
+    if labels is None:
+        if pred is None:
+            raise ValueError("dense_up_loss_fwd: neither labels nor pred: nothing to compute")
+        check(lib.lmv_dense_up_loss_fwd(*head, None, 0, None, pred.data_ptr(), None, None, _stream()), "lmv_dense_up_loss_fwd")
+        return None
+    need = lib.lmv_dense_up_loss_workspace_bytes(B, K, H, W)
+    if workspace is None:
+        workspace = _workspace(need, dev)
+    elif workspace.device != dev or not workspace.is_contiguous() or workspace.numel() * workspace.element_size() < need:
+        raise ValueError(f"dense_up_loss_fwd: the workspace must hold {need} bytes on the logits' device (ops.dense_up_workspace)")
+    if stats is None:
+        stats = torch.empty((dense_stats_floats(K),), device=dev, dtype=torch.float32)
+    elif stats.dtype != torch.float32 or tuple(stats.shape) != (dense_stats_floats(K),) or stats.device != dev or not stats.is_contiguous():
+        raise TypeError(f"dense_up_loss_fwd: stats must be a contiguous float32 vector [{dense_stats_floats(K)}] on the logits' device")
+    if conf is not None and (conf.dtype != torch.int64 or tuple(conf.shape) != (K, K) or conf.device != dev or not conf.is_contiguous()):
+        raise TypeError(f"dense_up_loss_fwd: conf must be a contiguous int64 matrix [{K}, {K}] on the logits' device")
+    if meter is not None and (meter.dtype != torch.float64 or tuple(meter.shape) != (2,) or meter.device != dev):
+        raise TypeError("dense_up_loss_fwd: meter must be a float64 vector [2] on the logits' device")
+    check(lib.lmv_dense_up_loss_fwd(*head, workspace.data_ptr(), workspace.numel() * workspace.element_size(), stats.data_ptr(), _ptr(pred), _ptr(conf), _ptr(meter),
+                                    _stream()), "lmv_dense_up_loss_fwd")
+    return stats
+
+
+def dense_up_loss_bwd(logits: Tensor, labels: Tensor, stats: Tensor, align_corners: bool = False, ignore_index: Optional[int] = None, alpha: Optional[Tensor] = None,
+                      gamma: float = 0.0, w_ce: float = 1.0, w_dice: float = 0.0, w_jac: float = 0.0, eps: float = 1e-7, avg: str = "valid",
+                      gout: Optional[Tensor] = None, out: Optional[Tensor] = None) -> Tensor:
+    """lmv_dense_up_loss_bwd (one launch): ``d loss / d logits`` at the LOW resolution, contiguous [B, K, h, w] in the logits dtype -- the transposed interpolation of
+    the high-resolution gradient, which is never stored.  ``stats`` from ``dense_up_loss_fwd`` with the same arguments; ``gout`` and ``out`` as in ``dense_loss_bwd``."""
+    if labels is None:
+        raise ValueError("dense_up_loss_bwd: a label map is required")
+    head, B, K, H, W = _dense_up_args("dense_up_loss_bwd", logits, labels, None, align_corners, ignore_index, alpha, gamma, w_ce, w_dice, w_jac, eps, avg)
+    dev = logits.device
+    if stats.dtype != torch.float32 or tuple(stats.shape) != (dense_stats_floats(K),) or stats.device != dev or not stats.is_contiguous():
+        raise TypeError(f"dense_up_loss_bwd: stats must be a contiguous float32 vector [{dense_stats_floats(K)}] on the logits' device")
+    if gout is not None and (gout.dtype != torch.float32 or gout.numel() != 1 or gout.device != dev):
+        raise TypeError("dense_up_loss_bwd: gout must be a float32 scalar tensor on the logits' device")
+    if out is None:
+        out = torch.empty(tuple(logits.shape), device=dev, dtype=logits.dtype)
+    elif out.dtype != logits.dtype or tuple(out.shape) != tuple(logits.shape) or out.device != dev or not out.is_contiguous():
+        raise TypeError("dense_up_loss_bwd: out must be a contiguous tensor of the logits' shape, dtype and device")
+    check(lib.lmv_dense_up_loss_bwd(*head, stats.data_ptr(), None if gout is None else gout.data_ptr(), out.data_ptr(), _stream()), "lmv_dense_up_loss_bwd")
+    return out
+
+
 # -------------------------------------------------------------------------------------------
 # A run of "S" blocks as one persistent launch (csrc/sstage.hip; inference, bf16)
 # -------------------------------------------------------------------------------------------
