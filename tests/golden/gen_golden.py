@@ -7,6 +7,7 @@ unmodified with its absent third-party imports (timm, fairscale) replaced by min
 expected *outputs* only, inputs and weights are regenerated from ``detfill.py``.
 
     python tests/golden/gen_golden.py            # writes tests/golden/*.npz
+    python tests/golden/gen_golden.py --only train_small_96,blockgrad_D2      # only these model / train / block fixtures; the others stay untouched
 """
 from __future__ import annotations
 
@@ -159,6 +160,8 @@ def _block(ref, t, C, h, dp=0.0):
 
 def gen_blocks(ref):
     for name, t, C, h, Hs, B in [("block_C", "C", 64, 2, 28, 2), ("block_D", "D", 96, 3, 28, 2), ("block_S", "S", 192, 6, 14, 2)]:
+        if ONLY and name not in ONLY:
+            continue
         m = _load(_block(ref, t, C, h).eval(), "blk.", 21)
         x = det_tensor((B, C, Hs, Hs), name + ".x", 2); c = det_tensor((B, 16, C), name + ".c", 2)
         with torch.no_grad():
@@ -166,7 +169,11 @@ def gen_blocks(ref):
         _save(name, dict(kind="block", type=t, C=C, h=h, H=Hs, W=Hs, B=B, seed=21),
               dict(x_out=sample(xo, 16384), c_out=co.numpy()))
     # forward + backward (grads wrt inputs and every parameter; checks shared-weight accumulation)
-    for name, t, C, h, Hs, B in [("blockgrad_D", "D", 64, 2, 12, 2), ("blockgrad_S", "S", 64, 2, 7, 2), ("blockgrad_C", "C", 64, 2, 12, 2)]:
+    # (blockgrad_D2: one q / k pair serves both attention directions -- its gradient is the sum of two attention backward passes)
+    for name, t, C, h, Hs, B in [("blockgrad_D", "D", 64, 2, 12, 2), ("blockgrad_S", "S", 64, 2, 7, 2), ("blockgrad_C", "C", 64, 2, 12, 2),
+                                 ("blockgrad_D2", "D2", 64, 2, 12, 2)]:
+        if ONLY and name not in ONLY:
+            continue
         m = _load(_block(ref, t, C, h).eval(), "blk.", 22)
         x = det_tensor((B, C, Hs, Hs), name + ".x", 3).requires_grad_(True)
         c = det_tensor((B, 16, C), name + ".c", 3).requires_grad_(True)
@@ -210,10 +217,35 @@ def gen_models(ref):
                          nkeys=len(m.state_dict())), arr)
 
 
+# Full gradients stored per training fixture (every parameter's gradient NORM is stored as well): the parts that only that variant has.
+_TINY_GRADS = ["meta_tokens", "head.weight", "stages.1.0.attn.qkv1.weight", "stages.3.2.mlp.0.weight", "stages.0.0.attn.kv.weight",
+               "stages.2.1.norm1.weight", "stages.4.1.pos_embed.weight", "downsample_layers.0.0.weight", "stages.3.0.attn.qkv.bias"]
+# lemevit_small: stage 3 is six "S" blocks at C = 320 (no persistent kernel, its own GEMM tile tails), stage 4 is C = 384
+_SMALL_GRADS = ["meta_tokens", "head.weight", "stages.3.3.attn.proj.weight", "stages.3.0.attn.qkv.bias", "stages.3.5.mlp.0.bias", "stages.3.1.norm2.weight",
+                "stages.4.1.pos_embed.weight", "stages.4.0.attn.qkv.bias", "stages.1.0.attn.qkv1.weight", "stages.0.0.attn.kv.weight", "downsample_layers.0.0.weight"]
+# lemevit_small_v2: MLP ratio 3 at every width (hidden 192 / 384 / 768 / 1536)
+_SMALL_V2_GRADS = ["meta_tokens", "head.weight", "stages.2.0.mlp.0.weight", "stages.2.1.mlp.3.weight", "stages.1.1.mlp.0.weight", "stages.1.0.mlp.3.weight",
+                   "stages.0.0.mlp.0.weight", "stages.3.2.mlp.0.bias", "stages.3.7.mlp.3.bias", "stages.3.0.norm2.weight", "stages.4.1.mlp.0.bias",
+                   "stages.4.0.norm2.bias", "stages.3.4.attn.qkv.bias", "downsample_layers.0.0.weight"]
+# lemevit_tiny_v2: "D2" blocks -- q comes out of qv1 (image tokens), k out of kv2 (meta tokens), and each serves both attention directions
+_TINY_V2_GRADS = ["meta_tokens", "head.weight", "stages.1.0.attn.qv1.weight", "stages.1.0.attn.qv1.bias", "stages.1.0.attn.kv2.weight", "stages.1.0.attn.kv2.bias",
+                  "stages.1.1.attn.proj_c.weight", "stages.2.1.attn.qv1.weight", "stages.2.1.attn.kv2.bias", "stages.2.0.norm1.weight", "stages.0.1.attn.kv.weight",
+                  "stages.4.1.pos_embed.weight", "downsample_layers.0.0.weight"]
+# vit_tiny: four stages, every block "S"; stage 0 is self-attention over 576 + 16 tokens at C = 96
+_VIT_TINY_GRADS = ["meta_tokens", "head.weight", "stages.0.0.attn.qkv.weight", "stages.0.0.attn.qkv.bias", "stages.0.1.mlp.0.weight", "stages.0.1.norm1.weight",
+                   "stages.1.0.attn.proj.weight", "stages.2.3.attn.qkv.bias", "stages.3.1.pos_embed.weight", "meta_token_downsample.1.0.weight",
+                   "downsample_layers.0.0.weight"]
+
+
 def gen_train(ref):
-    for name, dpr in [("train_tiny_96", 0.0), ("train_tiny_96_dp", 0.3)]:
+    for name, variant, dpr, grads in [("train_tiny_96", "lemevit_tiny", 0.0, _TINY_GRADS), ("train_tiny_96_dp", "lemevit_tiny", 0.3, _TINY_GRADS),
+                                      ("train_small_96", "lemevit_small", 0.0, _SMALL_GRADS), ("train_small_v2_96", "lemevit_small_v2", 0.0, _SMALL_V2_GRADS),
+                                      ("train_tiny_v2_96", "lemevit_tiny_v2", 0.0, _TINY_V2_GRADS), ("train_vit_tiny_96", "vit_tiny", 0.0, _VIT_TINY_GRADS),
+                                      ("train_tiny_v2_96_dp", "lemevit_tiny_v2", 0.3, _TINY_V2_GRADS)]:      # DropPath row masks on all four branches of the D2 blocks
+        if ONLY and name not in ONLY:
+            continue
         torch.manual_seed(0)
-        m = REG["lemevit_tiny"](num_classes=10, drop_path_rate=dpr)
+        m = REG[variant](num_classes=10, drop_path_rate=dpr)
         _load(m, "", 41)
         m.train()
         DP_LOG.clear()
@@ -228,15 +260,14 @@ def gen_train(ref):
         for k, p in m.named_parameters():
             names.append(k); gn.append(float(p.grad.norm()) if p.grad is not None else 0.0)
         arr["grad_norms"] = np.asarray(gn, dtype=np.float32)
-        for k in ["meta_tokens", "head.weight", "stages.1.0.attn.qkv1.weight", "stages.3.2.mlp.0.weight", "stages.0.0.attn.kv.weight",
-                  "stages.2.1.norm1.weight", "stages.4.1.pos_embed.weight", "downsample_layers.0.0.weight", "stages.3.0.attn.qkv.bias"]:
+        for k in grads:
             arr["grad." + k] = dict(m.named_parameters())[k].grad.numpy()
         for k, v in m.state_dict().items():
             if k.endswith(("running_mean", "running_var")):
                 arr["stat." + k] = v.numpy()
         if DP_LOG:
             arr["dp_masks"] = torch.stack(DP_LOG).numpy()
-        _save(name, dict(kind="train", variant="lemevit_tiny", res=96, B=4, num_classes=10, seed=41, drop_path_rate=dpr,
+        _save(name, dict(kind="train", variant=variant, res=96, B=4, num_classes=10, seed=41, drop_path_rate=dpr,
                          target=target.tolist(), param_names=names), arr)
 
 
@@ -275,8 +306,10 @@ def main():
     torch.set_num_threads(os.cpu_count() or 1)
     ref = _import_reference()
     assert ref.has_torchfunc and not ref.has_flash_attn and not ref.has_xformers
-    if ONLY:                       # --only model_base_384[,...]: add a model fixture without rewriting the others
+    if ONLY:                       # --only model_base_384[,...]: add model / train / block fixtures without rewriting the others
+        gen_blocks(ref)
         gen_models(ref)
+        gen_train(ref)
         return
     if "--dense-only" in sys.argv:
         gen_dense(_import_dense_reference())

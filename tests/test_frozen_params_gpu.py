@@ -54,8 +54,8 @@ def load(module, prefix, seed):
     return module.to(DEV)
 
 
-def _block(t, C, h, dense=False):
-    return L().LeMeBlock(dim=C, attn_drop=0.0, proj_drop=0.0, drop_path=0.0, attn_type=t, num_heads=h, **(dict(dense=True) if dense else {}))
+def _block(t, C, h, dense=False, mlp_ratio=4):
+    return L().LeMeBlock(dim=C, attn_drop=0.0, proj_drop=0.0, drop_path=0.0, attn_type=t, num_heads=h, mlp_ratio=mlp_ratio, **(dict(dense=True) if dense else {}))
 
 
 def _model(variant, num_classes, seed, **kw):
@@ -123,8 +123,8 @@ def test_frozen_block_backward_fp32(golden, name):
 
 # ------------------------------------------------------------------------------------------------
 # (2) bf16 against the float64 oracle
-def _bf16_vs_oracle(t, C, h, Hs, B=3):
-    m = load(_block(t, C, h), "blk.", 5).eval().requires_grad_(False)
+def _bf16_vs_oracle(t, C, h, Hs, B=3, mlp_ratio=4):
+    m = load(_block(t, C, h, mlp_ratio=mlp_ratio), "blk.", 5).eval().requires_grad_(False)
     sd = {"blk." + k: v.detach().to(torch.bfloat16).double().cpu() if ("attn." in k or "mlp." in k) and k.endswith("weight") else v.detach().double().cpu()
           for k, v in m.state_dict().items()}
     xb = det_tensor((B, C, Hs, Hs), "x", 9).to(torch.bfloat16); cb = det_tensor((B, 16, C), "c", 9).to(torch.bfloat16)
@@ -162,6 +162,19 @@ def test_frozen_block_backward_bf16_fused_dx_vs_oracle(cfg, t, C, h, Hs):
     cfg("mlp_dx_fused", 0)
     with _Kinds() as k:
         _bf16_vs_oracle(t, C, h, Hs)
+    assert 12 not in k.kinds
+
+
+def test_frozen_block_backward_bf16_fused_dx_ratio3_vs_oracle(cfg):
+    """... and at MLP ratio 3 (lemevit_small_v2's stage 2: D, C = 128, hidden 384): the fused dX kernel walks three 128-wide hidden chunks instead of four, reached from
+    a block as _frozen_wts sets it up."""
+    cfg("mlp_dx_fused", 2)
+    with _Kinds() as k:
+        _bf16_vs_oracle("D", 128, 4, 12, mlp_ratio=3)
+    assert k.kinds.count(12) == 1, k.kinds
+    cfg("mlp_dx_fused", 0)
+    with _Kinds() as k:
+        _bf16_vs_oracle("D", 128, 4, 12, mlp_ratio=3)
     assert 12 not in k.kinds
 
 
@@ -255,9 +268,15 @@ def _gelu_grad64(u):
     return 0.5 * (1.0 + torch.erf(u / math.sqrt(2.0))) + u * torch.exp(-0.5 * u * u) / math.sqrt(2.0 * math.pi)
 
 
+# (C, hidden, row counts of the one or two problems): hidden = 4 C at every width the kernel admits, then the 3 C of lemevit_small_v2 (three / six 128-wide chunks) and 2 C
+MLP_DX_CASES = [(64, 256, (1000, 37)), (96, 384, (777,)), (96, 384, (3136 * 2 + 5, 32)), (192, 768, (1571, 48)), (384, 1536, (1029, 130)), (384, 1536, (64,)),
+                (128, 512, (1029, 130)), (256, 1024, (1029, 130)), (320, 1280, (1029, 130)), (128, 384, (1029, 130)), (256, 768, (64,)), (256, 768, (1029, 130)),
+                (192, 384, (64,)), (128, 384, (64,))]
+
+
 @pytest.mark.parametrize("tm", [0, 128])
-@pytest.mark.parametrize("C,rows", [(64, (1000, 37)), (96, (777,)), (96, (3136 * 2 + 5, 32)), (192, (1571, 48)), (384, (1029, 130)), (384, (64,))])
-def test_mlp_dx_fused_kernel(cfg, C, rows, tm):
+@pytest.mark.parametrize("C,Hd,rows", MLP_DX_CASES, ids=[f"{C}-rows{i}" if i < 6 else f"{C}-{Hd}-rows{i}" for i, (C, Hd, _) in enumerate(MLP_DX_CASES)])
+def test_mlp_dx_fused_kernel(cfg, C, Hd, rows, tm):
     """lmv_mlp_dx_fused against float64 math on the bf16-rounded operands.  The tolerance is not invented: the existing two-launch form
     (lmv_linear_fwd(.., LMV_ACT_GELU_GRAD) on fc2_wt, then the forward-form dX on fc1_wt) runs on the same inputs, its max-abs error against the float64
     result is measured, and the fused kernel is allowed 1.5 x that -- it rounds du at the same point and differs only in summation order."""
@@ -265,7 +284,6 @@ def test_mlp_dx_fused_kernel(cfg, C, rows, tm):
         pytest.skip("C > 192 has the 128-row form only: covered by tm = 0")
     from lemevit_amd.ops import Prob, ACT_GELU_GRAD
     cfg("mlp_tm", tm)
-    Hd = 4 * C
     gen = torch.Generator().manual_seed(1000 + C + len(rows))
     bf = lambda t: t.to(torch.bfloat16)
     w2 = bf(torch.randn(C, Hd, generator=gen) * Hd ** -0.5)          # mlp.3.weight [C, hidden]
@@ -288,9 +306,9 @@ def test_mlp_dx_fused_kernel(cfg, C, rows, tm):
         mx = float(ref.abs().max())
         e2 = float((two[i].double().cpu() - ref).abs().max())
         ef = float((fused[i].double().cpu() - ref).abs().max())
-        print(f"mlp_dx_fused C={C} rows={rows[i]} tm={tm}: two-launch err {e2:.3e}, fused err {ef:.3e} (max-abs {mx:.3e})")
+        print(f"mlp_dx_fused C={C} hidden={Hd} rows={rows[i]} tm={tm}: two-launch err {e2:.3e}, fused err {ef:.3e} (max-abs {mx:.3e})")
         assert torch.isfinite(fused[i]).all()
-        assert ef <= 1.5 * e2, f"C={C} rows={rows[i]}: fused {ef:.3e} > 1.5 x two-launch {e2:.3e}"
+        assert ef <= 1.5 * e2, f"C={C} hidden={Hd} rows={rows[i]}: fused {ef:.3e} > 1.5 x two-launch {e2:.3e}"
     again = ops().mlp_dx_fused(gd, ud, fc2_wt, fc1_wt)
     assert all(torch.equal(a, b) for a, b in zip(fused, again))
 

@@ -207,9 +207,9 @@ def test_mlp_fused_c96_resident_and_streaming_forms(rows, rows_c, request):
         assert_close(a, b.double().cpu(), dtype, "resident vs streaming form", tol16=4e-3)
 
 
-@pytest.mark.parametrize("C,Hd,rows", [(64, 128, 1), (128, 256, 63), (96, 384, 65), (192, 384, 129), (384, 1536, 127), (320, 640, 257)])
+@pytest.mark.parametrize("C,Hd,rows", [(64, 128, 1), (128, 256, 63), (96, 384, 65), (192, 384, 129), (384, 1536, 127), (320, 640, 257), (128, 384, 63), (256, 768, 257)])
 def test_mlp_fused_edges(C, Hd, rows):
-    """row counts around the tile heights (1, 63 / 65, 127 / 129, 257) and MLP widths below 4 C (hidden = 2 C)"""
+    """row counts around the tile heights (1, 63 / 65, 127 / 129, 257) and MLP widths below 4 C (hidden = 2 C; hidden = 3 C: lemevit_small_v2's stages 2 and 3)"""
     dtype = torch.bfloat16
     o, F, masters, w2, b2 = _mlp_case(C, Hd)
     x, x64 = _tokens(rows, C, "x", dtype)

@@ -10,7 +10,7 @@ pytestmark = pytest.mark.gpu
 
 from detfill import det_tensor, fill_state_dict, sample
 from oracle import lemevit_oracle as O
-from test_oracle_golden import block_spec
+from test_oracle_golden import TRAIN_FIXTURES, block_spec, drop_path_plan
 
 DEV = "cuda:0"
 
@@ -72,8 +72,8 @@ def test_ca_module(golden, name, dtype, tol):
     close(m(x, c), g["c_out"], tol, name)
 
 
-def _block(t, C, h, dp=0.0):
-    return L().LeMeBlock(dim=C, attn_drop=0.0, proj_drop=0.0, drop_path=dp, attn_type=t, num_heads=h)
+def _block(t, C, h, dp=0.0, mlp_ratio=4):
+    return L().LeMeBlock(dim=C, attn_drop=0.0, proj_drop=0.0, drop_path=dp, attn_type=t, num_heads=h, mlp_ratio=mlp_ratio)
 
 
 @pytest.mark.parametrize("dtype,tol", MODES)
@@ -94,7 +94,7 @@ def test_block_forward(golden, name, dtype, tol):
     close(xo, O.to_nchw(xr, H, W).numpy(), tol, name + ".x (full tensor vs oracle)"); close(co, cr.numpy(), tol, name + ".c (full tensor vs oracle)")
 
 
-@pytest.mark.parametrize("name", ["blockgrad_D", "blockgrad_S", "blockgrad_C"])
+@pytest.mark.parametrize("name", ["blockgrad_D", "blockgrad_S", "blockgrad_C", "blockgrad_D2"])
 def test_block_backward_fp32(golden, name):
     meta, g = golden(name)
     t, C, h, H, W, B = meta["type"], meta["C"], meta["h"], meta["H"], meta["W"], meta["B"]
@@ -113,32 +113,106 @@ def test_block_backward_fp32(golden, name):
             close(p.grad, ref, 3e-5, "grad " + k)
 
 
-def test_block_backward_bf16_vs_oracle():
-    """bf16 kernels: gradients of a D and an S block vs the fp64 oracle on the same bf16-rounded inputs
-    and weights; 3e-2 of each gradient's max-abs (bf16 activations inside the block)."""
-    for t, C, h, Hs in [("D", 96, 3, 14), ("S", 192, 6, 7), ("C", 64, 2, 14), ("D2", 96, 3, 14)]:
-        B = 3
-        m = load(_block(t, C, h), "blk.", 5).eval()
-        sd = {"blk." + k: v.detach().to(torch.bfloat16).double().cpu().requires_grad_(True) if ("attn." in k or "mlp." in k) and k.endswith("weight")
-              else v.detach().double().cpu().requires_grad_(True) for k, v in m.state_dict().items()}
-        xb = det_tensor((B, C, Hs, Hs), "x", 9).to(torch.bfloat16); cb = det_tensor((B, 16, C), "c", 9).to(torch.bfloat16)
-        gx = det_tensor((B, C, Hs, Hs), "gx", 9).to(torch.bfloat16); gc = det_tensor((B, 16, C), "gc", 9).to(torch.bfloat16)
-        x = xb.to(DEV).requires_grad_(True); c = cb.to(DEV).requires_grad_(True)
-        with torch.autocast("cuda", torch.bfloat16):
-            xo, co = m(x, c)
-        ((xo.float() * gx.to(DEV).float()).sum() + (co.float() * gc.to(DEV).float()).sum()).backward()
-        xr = xb.double().requires_grad_(True); cr = cb.double().requires_grad_(True)
+def _rel(out, ref):
+    """max-abs error of a tensor against its reference, relative to the reference's max-abs"""
+    out = out.detach().double().cpu() if torch.is_tensor(out) else torch.as_tensor(np.asarray(out, dtype=np.float64))
+    ref = ref.detach().double().cpu() if torch.is_tensor(ref) else torch.as_tensor(np.asarray(ref, dtype=np.float64))
+    assert out.shape == ref.shape, (out.shape, ref.shape)
+    assert torch.isfinite(out).all()
+    return float((out - ref).abs().max() / ref.abs().max().clamp_min(1e-30))
+
+
+def _oracle_block(sd, t, h, Hs, xb, cb, gx, gc, autocast=False):
+    """The oracle's LeMeBlock forward + backward in float64 (autocast: the same torch code from fp32 operands under stock torch.autocast(bfloat16) -- the
+    yardstick of what bf16 operands cost this block; it never runs the library).  -> outputs and gradients, keyed like the native side."""
+    dt = torch.float32 if autocast else torch.float64
+    sd = {k: v.detach().to(dt).requires_grad_(True) for k, v in sd.items()}
+    xr = xb.to(dt).requires_grad_(True); cr = cb.to(dt).requires_grad_(True)
+    with torch.autocast("cpu", torch.bfloat16, enabled=autocast):
         xt, _, _ = O.to_tokens(xr)
-        xo_r, co_r = O.leme_block(sd, "blk.", t, xt, cr, Hs, Hs, h)
-        xo_r = O.to_nchw(xo_r, Hs, Hs)
-        ((xo_r * gx.double()).sum() + (co_r * gc.double()).sum()).backward()
-        close(xo, xo_r.detach().numpy(), 2e-2, t + " x_out"); close(co, co_r.detach().numpy(), 2e-2, t + " c_out")
-        close(x.grad, xr.grad.numpy(), 3e-2, t + " dx"); close(c.grad, cr.grad.numpy(), 3e-2, t + " dc")
-        for k, p in m.named_parameters():
-            ref = sd["blk." + k].grad
-            if ref is None or float(ref.abs().max()) == 0:
-                continue
-            close(p.grad, ref.numpy(), 3e-2, f"{t} grad {k}")
+        xo, co = O.leme_block(sd, "blk.", t, xt, cr, Hs, Hs, h)
+        xo = O.to_nchw(xo, Hs, Hs)
+    ((xo.to(dt) * gx.to(dt)).sum() + (co.to(dt) * gc.to(dt)).sum()).backward()
+    res = {"x_out": xo.detach().double(), "c_out": co.detach().double(), "dx": xr.grad.double(), "dc": cr.grad.double()}
+    for k, v in sd.items():
+        if v.grad is not None and float(v.grad.abs().max()) > 0:
+            res["grad " + k[len("blk."):]] = v.grad.double()
+    return res
+
+
+# (attention type, C, heads, token grid side, mlp_ratio): the four first cases are the widths the bf16 block backward has always been held to; the others are the shapes only
+# lemevit_small_v2 (MLP ratio 3: hidden 384 / 768 through the fused MLP kernels in three / six 128-wide chunks, hidden 192 / 1536 through the per-launch GEMMs), lemevit_small
+# (C = 320), lemevit_tiny_v2 (D2 at C = 192) and vit_tiny (self-attention over 576 + 16 tokens at C = 96: the whole-row long-key kernels) reach
+BLOCK_CASES_OLD = [("D", 96, 3, 14, 4), ("S", 192, 6, 7, 4), ("C", 64, 2, 14, 4), ("D2", 96, 3, 14, 4)]
+BLOCK_CASES_NEW = [("D", 128, 4, 12, 3), ("D", 64, 2, 12, 3), ("S", 256, 8, 6, 3), ("S", 512, 16, 3, 3), ("S", 320, 10, 3, 4), ("D2", 192, 6, 6, 4), ("S", 96, 3, 24, 4)]
+
+
+def _block_case(t, C, h, Hs, ratio, dtype):
+    """One block, forward + backward on the GPU in `dtype`, and the float64 oracle on the operands the kernels read -> (native, oracle, inputs for a yardstick run)."""
+    B = 3
+    bf = dtype == torch.bfloat16
+    m = load(_block(t, C, h, mlp_ratio=ratio), "blk.", 5).eval()
+    sd = {"blk." + k: v.detach().to(torch.bfloat16).float().cpu() if bf and ("attn." in k or "mlp." in k) and k.endswith("weight") else v.detach().float().cpu()
+          for k, v in m.state_dict().items()}
+    rnd = (lambda v: v.to(torch.bfloat16)) if bf else (lambda v: v)
+    xb = rnd(det_tensor((B, C, Hs, Hs), "x", 9)); cb = rnd(det_tensor((B, 16, C), "c", 9))
+    gx = rnd(det_tensor((B, C, Hs, Hs), "gx", 9)); gc = rnd(det_tensor((B, 16, C), "gc", 9))
+    x = xb.to(DEV).requires_grad_(True); c = cb.to(DEV).requires_grad_(True)
+    with torch.autocast("cuda", torch.bfloat16, enabled=bf):
+        xo, co = m(x, c)
+    ((xo.float() * gx.to(DEV).float()).sum() + (co.float() * gc.to(DEV).float()).sum()).backward()
+    got = {"x_out": xo, "c_out": co, "dx": x.grad, "dc": c.grad}
+    for k, p in m.named_parameters():
+        got["grad " + k] = p.grad
+    return got, _oracle_block(sd, t, h, Hs, xb, cb, gx, gc), (sd, xb, cb, gx, gc)
+
+
+def _block_bf16_vs_oracle(t, C, h, Hs, ratio=4, admit=False):
+    """-> the tensors over the budget, [(what, native error, yardstick error)]: 2e-2 of max-abs for the outputs, 3e-2 for every gradient.  admit: a tensor over it still passes
+    inside 1.5 x the error of the oracle block's own torch code under stock bf16 autocast (differently rounded arithmetic of the same block, tests/test_train_dispatch_gpu.py)."""
+    got, ref, (sd, xb, cb, gx, gc) = _block_case(t, C, h, Hs, ratio, torch.bfloat16)
+    tag, over, yard = f"{t} C={C} {Hs}x{Hs} ratio {ratio}", [], None
+    for k, r in ref.items():
+        tol = 2e-2 if k in ("x_out", "c_out") else 3e-2
+        e = _rel(got[k], r)
+        print(f"bf16 block {tag}: {k} {e:.2e}")
+        if e > tol:
+            if yard is None:
+                yard = _oracle_block(sd, t, h, Hs, xb, cb, gx, gc, autocast=True)
+            ey = _rel(yard[k], r)
+            print(f"bf16 block {tag}: {k} over {tol:.0e}; autocast oracle block {ey:.2e}")
+            if not admit or e > 1.5 * ey:
+                over.append((f"{tag} {k}", e, ey))
+    return over
+
+
+def test_block_backward_bf16_vs_oracle():
+    """bf16 kernels: gradients of a D, S, C and D2 block vs the fp64 oracle on the same bf16-rounded inputs and weights; 2e-2 of each output's and 3e-2 of each gradient's
+    max-abs (bf16 activations inside the block).  After the four widths this has always run come the shapes only the other registered variants reach (BLOCK_CASES_NEW).
+    A tensor of those new shapes over the budget is admitted only within 1.5 x the error of the oracle block under stock bf16 autocast (_block_bf16_vs_oracle); none needs that so far."""
+    over = []
+    for case in BLOCK_CASES_OLD:
+        over += _block_bf16_vs_oracle(*case)
+    for case in BLOCK_CASES_NEW:
+        over += _block_bf16_vs_oracle(*case, admit=True)
+    assert not over, over
+
+
+@pytest.mark.parametrize("t,C,h,Hs,ratio", BLOCK_CASES_NEW)
+def test_block_backward_fp32_vs_oracle(t, C, h, Hs, ratio):
+    """The fp32 block backward at the shapes no blockgrad_* fixture has (widths 96 .. 512, MLP ratio 3, D2 at C = 192, 592 keys), against the float64 oracle on the same
+    weights and inputs, at the bounds of test_block_backward_fp32: outputs 1e-5, dx / dc 2e-5, parameter gradients 3e-5 of each tensor's max-abs."""
+    got, ref, _ = _block_case(t, C, h, Hs, ratio, torch.float32)
+    bad = []
+    for k, r in ref.items():
+        tol = 1e-5 if k in ("x_out", "c_out") else 2e-5 if k in ("dx", "dc") else 3e-5
+        e = _rel(got[k], r)
+        print(f"fp32 block {t} C={C} {Hs}x{Hs} ratio {ratio}: {k} {e:.2e}")
+        if e > tol:
+            bad.append((k, e, tol))
+    assert not bad, bad
+    for k, v in got.items():          # a parameter the oracle gives no gradient has none here either
+        assert k in ref or v is None or float(v.abs().max()) == 0.0, k
 
 
 def _model(variant, num_classes, seed, **kw):
@@ -529,24 +603,23 @@ def test_launch_context_is_thread_local():
         M.launches.concurrent = 1
 
 
-@pytest.mark.parametrize("name", ["train_tiny_96", "train_tiny_96_dp"])
+@pytest.mark.parametrize("name", TRAIN_FIXTURES)
 def test_train_step_fp32(golden, name):
-    """Train-mode step (BatchNorm batch statistics, DropPath with the reference's recorded masks): loss, logits, every
-    parameter's gradient norm, selected full gradients and the updated BN running statistics."""
+    """Train-mode step of every registered variant but Base (BatchNorm batch statistics, DropPath with the reference's recorded masks): loss, logits, every
+    parameter's gradient norm, selected full gradients and the updated BN running statistics against the reference's fixture; and -- a norm cannot see a permuted or
+    sign-flipped gradient -- EVERY parameter's full gradient against the float64 oracle's autograd on the same weights, image and masks (the oracle is pinned to the
+    same fixtures by tests/test_oracle_golden.py::test_train_step)."""
     meta, g = golden(name)
     cfg = O.VARIANTS[meta["variant"]]
     m = _model(meta["variant"], meta["num_classes"], meta["seed"], drop_path_rate=meta["drop_path_rate"]).train()
-    if "dp_masks" in g:
-        rows, r, first = torch.from_numpy(g["dp_masks"]).to(DEV), 0, True
-        for i, (d, t) in enumerate(zip(cfg["depth"], cfg["attn_type"])):
-            for j in range(d):
-                if first:
-                    first = False
-                    continue
-                n = 2 if t == "C" else 4
-                fixed = [rows[r + q].contiguous() for q in range(n)] + [None] * (4 - n)
-                m.stages[i][j]._masks = (lambda f: (lambda B, dev: f))(fixed)
-                r += n
+    plan = drop_path_plan(cfg, torch.from_numpy(g["dp_masks"])) if "dp_masks" in g else None
+    if plan:
+        assert len(m.stages) == len(cfg["depth"]) and [len(st) for st in m.stages] == list(cfg["depth"])
+        for (i, j), rows in plan.items():          # two masks for a "C" block, four for "D" / "D2" / "S"
+            assert m.stages[i][j].kind == cfg["attn_type"][i] and m.stages[i][j].drop_prob > 0.0
+            fixed = [r.to(DEV).contiguous() for r in rows] + [None] * (4 - len(rows))
+            m.stages[i][j]._masks = (lambda f: (lambda B, dev: f))(fixed)
+        assert m.stages[0][0].drop_prob == 0.0 and (0, 0) not in plan
     img = det_tensor((meta["B"], 3, meta["res"], meta["res"]), name + ".img", 5).to(DEV)
     logits = m(img)
     loss = torch.nn.functional.cross_entropy(logits, torch.tensor(meta["target"], device=DEV))
@@ -562,6 +635,84 @@ def test_train_step_fp32(golden, name):
             close(params[k[5:]].grad, g[k], 2e-4, k)
         if k.startswith("stat."):
             close(m.state_dict()[k[5:]], g[k], 1e-5, k)
+    # every full gradient against the float64 oracle: 2e-4 of each tensor's max-abs (the bound of the listed gradients above); only tensors whose oracle gradient is
+    # <= 1e-5 of the largest gradient max-abs are left out (mathematically zero: a conv bias in front of a train-mode BatchNorm, a k bias inside a softmax)
+    sd = {k: v.double() for k, v in fill_state_dict(O.state_dict_spec(cfg, meta["num_classes"]), meta["seed"]).items()}
+    for k, v in sd.items():
+        if not k.endswith(("running_mean", "running_var", "num_batches_tracked")):
+            v.requires_grad_(True)
+    dplan = {key: [r.double() for r in rows] for key, rows in plan.items()} if plan else None
+    ref_logits = O.lemevit_forward(sd, cfg, img.cpu().double(), train=True, dp_masks=dplan)
+    torch.nn.functional.cross_entropy(ref_logits, torch.tensor(meta["target"])).backward()
+    gmax = max(float(sd[k].grad.abs().max()) for k in params if sd[k].grad is not None)
+    n, worst, over = 0, ("", 0.0), []
+    for k, p in params.items():
+        r = sd[k].grad
+        if r is None or float(r.abs().max()) <= 1e-5 * gmax:
+            continue
+        assert p.grad is not None, k
+        e = float((p.grad.detach().double().cpu() - r).abs().max() / r.abs().max())
+        n += 1
+        if e > worst[1]:
+            worst = (k, e)
+        if not e <= 2e-4:
+            over.append((k, e))
+    print(f"{name}: {n} of {len(params)} gradients vs the float64 oracle, worst {worst[1]:.2e} ({worst[0]})")
+    assert not over, over[:8]
+    assert n >= 0.95 * len(params), (n, len(params))
+
+
+def _grad_stats(grads, ref, loss, ref_loss):
+    """The statistics the bf16 end-to-end gradient tests assert on: `grads` {name: gradient} against the oracle gradients `ref` (the same keys; None = no gradient).  Tensors
+    whose oracle gradient is <= 1e-5 of the largest gradient max-abs are left out of the per-tensor figures (mathematically zero gradients -- a conv bias in front of a
+    train-mode BatchNorm, a k bias inside a softmax: rounding noise on both sides)."""
+    worst_cos, errs = ("", 1.0), []
+    gmax = max(float(r.abs().max()) for r in ref.values() if r is not None)
+    for k, gq in grads.items():
+        r = ref[k]
+        if r is None or float(r.abs().max()) <= 1e-5 * gmax:
+            continue
+        gq = gq.detach().float().cpu()
+        assert torch.isfinite(gq).all(), k
+        e = float((gq - r).abs().max() / r.abs().max())
+        c = float(torch.nn.functional.cosine_similarity(gq.flatten().double(), r.flatten().double(), dim=0))
+        errs.append((e, float((gq - r).norm() / r.norm()), c, k))
+        if c < worst_cos[1]:
+            worst_cos = (k, c)
+    errs.sort(reverse=True)
+    gall = torch.cat([gq.detach().float().cpu().flatten() for k, gq in grads.items() if ref[k] is not None]).double()
+    rall = torch.cat([ref[k].flatten() for k in grads if ref[k] is not None]).double()
+    return dict(n=len(errs), errs=errs, loss=abs(loss - ref_loss) / abs(ref_loss), gl2=float((gall - rall).norm() / rall.norm()),
+                gcos=float(torch.nn.functional.cosine_similarity(gall, rall, dim=0)), med=sorted(x[0] for x in errs)[len(errs) // 2],
+                p90=sorted(x[0] for x in errs)[len(errs) * 9 // 10], worst_cos=worst_cos[1], worst_cos_name=worst_cos[0])
+
+
+def _oracle_train_grads(cfg, sd, img, tgt, dtype, autocast=False):
+    """loss and {name: gradient or None} of the oracle's train-mode step on the state dict `sd` (the module's forward has already moved the BatchNorm running statistics
+    in it: the oracle's train-mode forward uses batch statistics, so that does not matter).  autocast: the same torch code under stock torch.autocast(bfloat16)."""
+    ref_sd = {k: (v.detach().to(dtype).clone().requires_grad_(True) if v.dtype.is_floating_point and "running" not in k else v) for k, v in sd.items()}
+    with torch.autocast("cpu", torch.bfloat16, enabled=autocast):
+        logits = O.lemevit_forward(ref_sd, cfg, img.to(dtype), train=True)
+    loss = torch.nn.functional.cross_entropy(logits.to(dtype), tgt)
+    loss.backward()
+    return loss.item(), {k: v.grad for k, v in ref_sd.items() if v.dtype.is_floating_point and "running" not in k}
+
+
+def _bf16_train_grads(variant, num_classes, img, tgt):
+    """One bf16-autocast train-mode step of the native model from the reference's own initialisation (models/lemevit.py:789-796: trunc_normal(0.02) Linears, LayerNorm (1, 0))
+    -- what bench.py trains.  (The goldens' hash-filled weights are non-degenerate on purpose -- the residual stream reaches 6e4 there -- which is the right stress for forward
+    parity and the wrong operating point for a bf16 gradient budget: with them 31 of 545 Base tensors exceed 5e-2, all column sums over the stage-3 residual-stream gradient.)
+    -> loss, {name: gradient}, the CPU state dict."""
+    torch.manual_seed(0)
+    m = L().create_model(variant, num_classes=num_classes, drop_path_rate=0.0).to(DEV).train()
+    with torch.autocast("cuda", torch.bfloat16):
+        loss = torch.nn.functional.cross_entropy(m(img.to(DEV)), tgt.to(DEV))
+    loss.backward()
+    return loss.item(), {k: p.grad for k, p in m.named_parameters()}, {k: v.detach().cpu().clone() for k, v in m.state_dict().items()}
+
+
+# the project's accepted end-to-end bf16 budget (test_base_224_bf16_gradients_vs_oracle): loss, whole-gradient rel-L2 and cosine, per-tensor median and 90th percentile, worst cosine
+BF16_BUDGET = dict(loss=3e-2, gl2=3e-2, gcos=0.9995, med=2e-2, p90=8e-2, worst_cos=0.90)
 
 
 def test_base_224_bf16_gradients_vs_oracle():
@@ -570,56 +721,53 @@ def test_base_224_bf16_gradients_vs_oracle():
     relative to that tensor's gradient max-abs; the bound is the end-to-end bf16 budget (30 blocks of bf16 operands in both passes: measured ~1e-2 on the large tensors, a few
     1e-2 on the 16-token meta path), and the cosine against the oracle's gradient must be ~1 for every tensor that carries a gradient."""
     cfg = O.VARIANTS["lemevit_base"]
-    # the reference's own initialisation (models/lemevit.py:789-796: trunc_normal(0.02) Linears, LayerNorm (1, 0)) -- what bench.py trains.  (The goldens' hash-filled weights are
-    # non-degenerate on purpose -- the residual stream reaches 6e4 there -- which is the right stress for forward parity and the wrong operating point for a bf16 gradient budget:
-    # with them 31 of 545 tensors exceed 5e-2, all column sums over the stage-3 residual-stream gradient.)
-    torch.manual_seed(0)
-    m = L().create_model("lemevit_base", num_classes=1000, drop_path_rate=0.0).to(DEV).train()
-    B = 4
-    img = det_tensor((B, 3, 224, 224), "basegrad.img", 5)
+    img = det_tensor((4, 3, 224, 224), "basegrad.img", 5)
     tgt = torch.tensor([3, 141, 592, 653])
-    with torch.autocast("cuda", torch.bfloat16):
-        loss = torch.nn.functional.cross_entropy(m(img.to(DEV)), tgt.to(DEV))
-    loss.backward()
-    sd = {k: v.detach().cpu().clone() for k, v in m.state_dict().items()}
-    ref_sd = {k: (v.requires_grad_(True) if v.dtype.is_floating_point and "running" not in k else v) for k, v in sd.items()}
-    # (the module's forward has already moved the BatchNorm running statistics: the oracle's train-mode forward uses batch statistics, so that does not matter)
-    ref_loss = torch.nn.functional.cross_entropy(O.lemevit_forward(ref_sd, cfg, img, train=True), tgt)
-    ref_loss.backward()
-    assert abs(loss.item() - ref_loss.item()) <= 3e-2 * abs(ref_loss.item()), (loss.item(), ref_loss.item())
-    worst, worst_cos, n, errs = ("", 0.0), ("", 1.0), 0, []
-    gmax = max(float(v.grad.abs().max()) for v in ref_sd.values() if getattr(v, "grad", None) is not None)
-    for k, p in m.named_parameters():
-        r = ref_sd[k].grad
-        if r is None or float(r.abs().max()) <= 1e-5 * gmax:          # mathematically zero gradients (a conv bias in front of a train-mode BatchNorm, a k bias inside a softmax): rounding noise on both sides
-            continue
-        gq = p.grad.detach().float().cpu()
-        assert torch.isfinite(gq).all(), k
-        e = float((gq - r).abs().max() / r.abs().max())
-        c = float(torch.nn.functional.cosine_similarity(gq.flatten().double(), r.flatten().double(), dim=0))
-        n += 1
-        errs.append((e, float((gq - r).norm() / r.norm()), c, k))
-        if e > worst[1]:
-            worst = (k, e)
-        if c < worst_cos[1]:
-            worst_cos = (k, c)
-    errs.sort(reverse=True)
-    med = sorted(x[0] for x in errs)[len(errs) // 2]
-    p90 = sorted(x[0] for x in errs)[len(errs) * 9 // 10]
-    gall = torch.cat([p.grad.detach().float().cpu().flatten() for k, p in m.named_parameters() if ref_sd[k].grad is not None]).double()
-    rall = torch.cat([ref_sd[k].grad.flatten() for k, p in m.named_parameters() if ref_sd[k].grad is not None]).double()
-    gl2 = float((gall - rall).norm() / rall.norm())
-    gcos = float(torch.nn.functional.cosine_similarity(gall, rall, dim=0))
-    print("largest per-tensor errors (max-abs, rel-L2, cosine):", [(k, round(e, 3), round(l2, 3), round(c, 4)) for e, l2, c, k in errs[:8]])
-    print(f"Base 224 bf16 gradients vs oracle, {n} tensors: whole-gradient rel-L2 {gl2:.2e}, cosine {gcos:.5f}; per tensor median {med:.2e}, 90th percentile {p90:.2e}, worst cosine {worst_cos[1]:.4f} ({worst_cos[0]})")
-    assert n >= 520
+    loss, grads, sd = _bf16_train_grads("lemevit_base", 1000, img, tgt)
+    ref_loss, ref = _oracle_train_grads(cfg, sd, img, tgt, torch.float32)
+    assert abs(loss - ref_loss) <= 3e-2 * abs(ref_loss), (loss, ref_loss)
+    st = _grad_stats(grads, ref, loss, ref_loss)
+    print("largest per-tensor errors (max-abs, rel-L2, cosine):", [(k, round(e, 3), round(l2, 3), round(c, 4)) for e, l2, c, k in st["errs"][:8]])
+    print(f"Base 224 bf16 gradients vs oracle, {st['n']} tensors: whole-gradient rel-L2 {st['gl2']:.2e}, cosine {st['gcos']:.5f}; per tensor median {st['med']:.2e}, "
+          f"90th percentile {st['p90']:.2e}, worst cosine {st['worst_cos']:.4f} ({st['worst_cos_name']})")
+    assert st["n"] >= 520
     # The step the optimizer takes: the whole gradient.  Per tensor the budget holds for the bulk; the tail is made of COLUMN SUMS OVER TOKENS of the residual-stream gradient
     # (pos_embed.bias = sum_t dx; proj_x.weight ~ (sum_t g) v-bar while the attention is still uniform at initialisation; the BatchNorm affine behind a stage): the train-mode
     # BatchNorm at the top makes that gradient sum to ~0 over tokens, so these entries are differences of cancelling terms and carry the bf16 rounding noise of ~N tokens against a
     # small true value -- in the reference's own autocast as well.  They are held to a direction test (cosine), not to the element budget.
-    assert gl2 <= 3e-2 and gcos >= 0.9995, (gl2, gcos)
-    assert med <= 2e-2 and p90 <= 8e-2, (med, p90)
-    assert worst_cos[1] >= 0.90, worst_cos
+    assert st["gl2"] <= 3e-2 and st["gcos"] >= 0.9995, (st["gl2"], st["gcos"])
+    assert st["med"] <= 2e-2 and st["p90"] <= 8e-2, (st["med"], st["p90"])
+    assert st["worst_cos"] >= 0.90, (st["worst_cos_name"], st["worst_cos"])
+
+
+@pytest.mark.parametrize("variant", ["lemevit_tiny", "lemevit_small", "lemevit_small_v2", "lemevit_tiny_v2", "vit_tiny"])
+def test_variant_96_bf16_gradients_vs_oracle(variant):
+    """The bf16 train step of every other registered variant (96 x 96, B = 4, the reference's own initialisation, no DropPath, bf16 autocast) against the float64 oracle's
+    autograd on the same weights and images: the statistics of the Base test.  Nobody had measured them at 9 .. 576 tokens, so each statistic passes inside the Base
+    test's bound (BF16_BUDGET) OR inside 1.5 x the same statistic of a yardstick -- the oracle's own torch code under stock torch.autocast(bfloat16) on the CPU, against the
+    same float64 gradients (cosines: 1.5 x its deficit from 1).  1.5 is the margin tests/test_train_dispatch_gpu.py grants a differently rounded form of the same arithmetic;
+    the yardstick never runs the library.  One run is recorded in profiles/train_variants_parity.txt."""
+    cfg = O.VARIANTS[variant]
+    img = det_tensor((4, 3, 96, 96), "variantgrad.img", 5)
+    tgt = torch.tensor([1, 7, 3, 3])
+    loss, grads, sd = _bf16_train_grads(variant, 10, img, tgt)
+    ref_loss, ref = _oracle_train_grads(cfg, sd, img, tgt, torch.float64)
+    yloss, ygrads = _oracle_train_grads(cfg, sd, img, tgt, torch.float32, autocast=True)
+    nat = _grad_stats(grads, ref, loss, ref_loss)
+    yard = _grad_stats({k: ygrads[k] for k in grads}, ref, yloss, ref_loss)
+    assert nat["n"] == yard["n"] and nat["n"] >= 0.95 * len(grads), (nat["n"], yard["n"], len(grads))
+    print(f"{variant} 96 bf16 gradients vs the float64 oracle, {nat['n']} of {len(grads)} tensors (native | autocast-oracle yardstick):")
+    failed = []
+    for key, bound in BF16_BUDGET.items():
+        cos = key in ("gcos", "worst_cos")
+        ok = nat[key] >= bound if cos else nat[key] <= bound
+        ok_y = (1.0 - nat[key]) <= 1.5 * (1.0 - yard[key]) if cos else nat[key] <= 1.5 * yard[key]
+        name = f" ({nat['worst_cos_name']} | {yard['worst_cos_name']})" if key == "worst_cos" else ""
+        print(f"  {key:9s} {nat[key]:.5g} | {yard[key]:.5g}   bound {bound:g}: {'within' if ok else 'OVER'}; 1.5 x yardstick: {'within' if ok_y else 'over'}{name}")
+        if not (ok or ok_y):
+            failed.append((key, nat[key], yard[key], bound))
+    print("  largest per-tensor errors (max-abs, rel-L2, cosine):", [(k, round(e, 3), round(l2, 3), round(c, 4)) for e, l2, c, k in nat["errs"][:6]])
+    assert not failed, failed
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])

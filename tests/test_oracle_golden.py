@@ -74,7 +74,7 @@ def test_block_forward(golden, name):
     _close(sample(O.to_nchw(xo, H, W), 16384), g["x_out"], what=name + ".x"); _close(co, g["c_out"], what=name + ".c")
 
 
-@pytest.mark.parametrize("name", ["blockgrad_D", "blockgrad_S", "blockgrad_C"])
+@pytest.mark.parametrize("name", ["blockgrad_D", "blockgrad_S", "blockgrad_C", "blockgrad_D2"])
 def test_block_backward(golden, name):
     meta, g = golden(name)
     t, C, h, H, W, B = meta["type"], meta["C"], meta["h"], meta["H"], meta["W"], meta["B"]
@@ -122,7 +122,28 @@ def test_known_answers():
     assert abs(sx - 0.035149) < 1e-6 and abs(sc - 0.102062) < 1e-6
 
 
-@pytest.mark.parametrize("name", ["train_tiny_96", "train_tiny_96_dp"])
+def drop_path_plan(cfg, rows):
+    """The recorded DropPath masks of a training fixture, (stage, block) -> that block's masks.  Reference draw order: per block, over cfg["depth"] /
+    cfg["attn_type"] (four or five stages), skipping the model's very first block (its rate is 0 -> nn.Identity), the DropPath calls in source order
+    (D / D2 / S: x-attn, x-mlp, c-attn, c-mlp; C: c-attn, c-mlp)."""
+    masks, r = {}, 0
+    first = True
+    for i, (d, t) in enumerate(zip(cfg["depth"], cfg["attn_type"])):
+        for j in range(d):
+            if first:
+                first = False
+                continue
+            n = 2 if t == "C" else 4
+            masks[(i, j)] = [rows[r + q] for q in range(n)]
+            r += n
+    assert r == rows.shape[0], (r, rows.shape)
+    return masks
+
+
+TRAIN_FIXTURES = ["train_tiny_96", "train_tiny_96_dp", "train_small_96", "train_small_v2_96", "train_tiny_v2_96", "train_vit_tiny_96", "train_tiny_v2_96_dp"]
+
+
+@pytest.mark.parametrize("name", TRAIN_FIXTURES)
 def test_train_step(golden, name):
     meta, g = golden(name)
     cfg = O.VARIANTS[meta["variant"]]
@@ -131,21 +152,7 @@ def test_train_step(golden, name):
         if v.dtype.is_floating_point and not k.endswith(("running_mean", "running_var")):
             v.requires_grad_(True)
     img = det_tensor((meta["B"], 3, meta["res"], meta["res"]), name + ".img", 5)
-    masks = None
-    if "dp_masks" in g:
-        # reference draw order: per block (skipping block 0 whose rate is 0 -> Identity), the
-        # DropPath calls in source order (D/S: x-attn, x-mlp, c-attn, c-mlp; C: c-attn, c-mlp)
-        masks, rows, r = {}, torch.from_numpy(g["dp_masks"]), 0
-        first = True
-        for i, (d, t) in enumerate(zip(cfg["depth"], cfg["attn_type"])):
-            for j in range(d):
-                if first:
-                    first = False
-                    continue
-                n = 2 if t == "C" else 4
-                masks[(i, j)] = [rows[r + q] for q in range(n)]
-                r += n
-        assert r == rows.shape[0]
+    masks = drop_path_plan(cfg, torch.from_numpy(g["dp_masks"])) if "dp_masks" in g else None
     stats = {}
     logits = O.lemevit_forward(sd, cfg, img, train=True, dp_masks=masks, new_stats=stats)
     loss = torch.nn.functional.cross_entropy(logits, torch.tensor(meta["target"]))
