@@ -20,15 +20,25 @@ constexpr int DN_MAX_WG = 1024;          // workgroups of the forward pass: more
 constexpr int DN_MAX_WG_BWD = 2048;
 constexpr int DN_KREG = 5;               // K <= DN_KREG: class values and partial sums in registers; above: values re-read from cache, partial sums in LDS
 
-struct DenseArgs {
+// what every kernel here is told, whatever the resolution of the logits.  dn_head fills the inputs; the entry points add the buffers of their direction
+// (ws / pred / conf, or stats / gout / dlogits) and dn_args / up_args the chunk count.
+struct DenseHead {
   const void* logits; const void* labels; const float* alpha;
   float* ws; uint8_t* pred; unsigned long long* conf;
   const float* stats; const float* gout; void* dlogits;
   int64_t sb, sc, ignore, nchunks;
-  int B, K, HW, cpi;          // cpi: chunks per image
-  int xvec, lvec, pvec, dvec;          // 16-byte logits loads / vector label loads / vector pred stores / 16-byte dlogits stores are possible for FULL chunks
+  int B, K;
+};
+// The loss terms the kernels need.  A member BEHIND the sizes of either argument struct, not part of the head: dense_up_bwd_kernel sits at the SGPR limit, and
+// with these three in front of its sizes the kernel-argument loads regroup and it spills more scalars (profiles/dense_refactor_resources.txt).
+struct DenseTerms {
   float gamma, w_ce;
   int shape_terms;          // w_dice or w_jac is not 0: the u / v table matters
+};
+struct DenseArgs : DenseHead {
+  int HW, cpi;          // cpi: chunks per image
+  int xvec, lvec, pvec, dvec;          // 16-byte logits loads / vector label loads / vector pred stores / 16-byte dlogits stores are possible for FULL chunks
+  DenseTerms t;
 };
 
 static inline int dn_threads(int K) { return K <= 16 ? 256 : (K <= 32 ? 128 : 64); }          // K > DN_KREG: 2 K threads floats of LDS stay at 32 KB
@@ -104,6 +114,107 @@ __device__ __forceinline__ int wave_sum_int(int v) {
   return v;
 }
 
+// ---- the pieces that the native and the upsampling kernels share: each rule of the loss is stated here once ----
+// The forward LDS (dynamic), one layout for both forward kernels:
+//   KT > 0: red [waves][3 KT + 3] floats | conf [K K] ints;  KT == 0: accP [K][threads] | accI [K][threads] floats | cntT [K] ints | red [waves][3] | conf
+struct DnLds { float* accP; float* accI; int* cntT; float* red; int* conf; };
+static inline size_t dn_lds_bytes(int K, int NT, bool has_conf) {
+  const size_t nw = NT / 64;
+  return (K <= DN_KREG ? nw * (3 * K + 3) : (size_t)2 * K * NT + K + nw * 3) * sizeof(float) + (has_conf ? (size_t)K * K * sizeof(int) : 0);
+}
+// sums: the pass accumulates (the upsampling kernel's prediction-only form does not: nothing to zero, no barrier)
+template <int KT> __device__ __forceinline__ DnLds dn_lds(float* smem, int K, bool sums, bool has_conf) {
+  const int NT = blockDim.x, tid = threadIdx.x, nw = NT >> 6;
+  DnLds s;
+  s.accP = smem;
+  s.accI = smem + (KT > 0 ? 0 : K * NT);
+  s.cntT = reinterpret_cast<int*>(smem + (KT > 0 ? 0 : 2 * K * NT));
+  s.red = smem + (KT > 0 ? 0 : 2 * K * NT + K);
+  s.conf = reinterpret_cast<int*>(s.red + nw * (KT > 0 ? 3 * KT + 3 : 3));
+  if (sums) {
+    if (KT == 0) {
+      for (int i = tid; i < 2 * K * NT; i += NT) smem[i] = 0.f;
+      for (int i = tid; i < K; i += NT) s.cntT[i] = 0;
+    }
+    if (has_conf)
+      for (int i = tid; i < K * K; i += NT) s.conf[i] = 0;
+    __syncthreads();
+  }
+  return s;
+}
+
+// The register path's pixel (KT > 0), stated once for both forward kernels.  Z(k): the lvalue of the pixel's k-th logit, reused for the exponentials (no second
+// set of registers).  Leaves the argmax, sum exp(z - max), z_y - max and p_y in bi, se, zy, py and adds the pixel to the thread's partial sums rP, rI, rT.  An
+// ignored pixel (y < 0) contributes to nothing; SKIP (a constant at both sites, which say why): its softmax is branched around, not evaluated and discarded.
+// A macro and not a __forceinline__ function: as a function, in every form tried (pointers, references, a struct returned by value), the compiler turns the
+// conditional updates of dense_fwd_kernel into selects, whose lane masks cost that kernel about 20 scalar registers and, for fp32 logits with int64 labels
+// at K = 2, 3, a wave of occupancy.  The text below compiles to the registers the kernels had (profiles/dense_refactor_resources.txt).
+#define DN_PIXEL(KT, Z, y, SKIP, bi, se, zy, py, rP, rI, rT)                      \
+  do {                                                                            \
+    float best_ = Z(0), m_ = Z(0);                                                \
+    int b_ = 0;                                                                   \
+    _Pragma("unroll") for (int k = 1; k < KT; ++k) {                              \
+      if (dn_better(Z(k), best_)) { best_ = Z(k); b_ = k; }                       \
+      m_ = fmaxf(m_, Z(k));                                                       \
+    }                                                                             \
+    bi = b_; se = 1.f; zy = 0.f; py = 0.f;                                        \
+    const bool on_ = (y) >= 0;                                                    \
+    if (on_ || !(SKIP)) {                                                         \
+      float s_ = 0.f;                                                             \
+      _Pragma("unroll") for (int k = 0; k < KT; ++k) {                            \
+        const float dz_ = Z(k) - m_;                                              \
+        if ((y) == k) zy = dz_;          /* z_y - max */                          \
+        Z(k) = expf(dz_); s_ += Z(k);                                             \
+      }                                                                           \
+      se = s_;                                                                    \
+      const float inv_ = 1.f / s_;                                                \
+      _Pragma("unroll") for (int k = 0; k < KT; ++k) {                            \
+        const float p_ = Z(k) * inv_;                                             \
+        if (on_) rP[k] += p_;                                                     \
+        if ((y) == k) { rI[k] += p_; rT[k] += 1; py = p_; }                       \
+      }                                                                           \
+    }                                                                             \
+  } while (0)
+
+// the tail of a pixel on either path: its negative log-likelihood, plain and focal-weighted, the valid count and the workgroup's confusion counts in LDS
+__device__ __forceinline__ void dn_pixel_tail(const DenseHead& a, const DenseTerms& t, int K, int* conf, int y, int bi, float se, float zy, float py, float& ce_sum, float& nll_sum,
+                                              int& nvalid) {
+  if (y >= 0) {
+    const float nll = logf(se) - zy;          // -log p_y = log(sum exp(z - max)) - (z_y - max)
+    ce_sum += dn_focal(a.alpha, t.gamma, y, py) * nll;
+    nll_sum += nll;
+    nvalid += 1;
+    if (a.conf) atomicAdd(&conf[y * K + bi], 1);
+  }
+}
+
+// the argmax of a chunk's V pixels: one 32-bit / 64-bit word where the caller found pp aligned and the chunk whole, bytes otherwise
+template <int V> __device__ __forceinline__ void dn_store_pred(uint8_t* pp, bool vec, int n, const int* bi) {
+  if (vec) {
+    uint32_t w[V / 4] = {};
+#pragma unroll
+    for (int j = 0; j < V; ++j) w[j >> 2] |= (uint32_t)bi[j] << (8 * (j & 3));
+    if constexpr (V == 4) *reinterpret_cast<uint32_t*>(pp) = w[0];
+    else *reinterpret_cast<uint2*>(pp) = make_uint2(w[0], w[1]);
+  } else {
+#pragma unroll
+    for (int j = 0; j < V; ++j)
+      if (j < n) pp[j] = (uint8_t)bi[j];
+  }
+}
+
+// The gradient of a valid pixel's class k from the u / v table: g = cf (p - [hit]) + p ((v + [hit] u) - sg).  p, sg = sum_k p_k (v_k + [hit] u_k) and the CE
+// factor cf are the caller's: the two backward passes form p and sg in different orders (see dense_up_bwd_kernel), and those bits stay as they are.
+// dn_grad reads the table row through pointers, inside the branch (dense_bwd_kernel's register form pays VGPRs for loads hoisted out of it), and writes
+// dn_shape's expression out: with the call nested here dense_up_bwd_kernel, which sits at the SGPR limit, spills more scalars.
+__device__ __forceinline__ float dn_shape(bool hit, float uk, float vk) { return vk + (hit ? uk : 0.f); }
+__device__ __forceinline__ float dn_cf(const DenseHead& a, const DenseTerms& t, float invD, int y, float py) { return t.w_ce * dn_focal(a.alpha, t.gamma, y, py) * invD; }
+__device__ __forceinline__ float dn_grad(const DenseTerms& t, float p, bool hit, float cf, const float* U, const float* Vt, int k, float sg, float gout) {
+  float g = cf * (p - (hit ? 1.f : 0.f));
+  if (t.shape_terms) g = p * ((Vt[k] + (hit ? U[k] : 0.f)) - sg) + g;
+  return gout * g;
+}
+
 // chunk -> image, offsets and length
 struct DnChunk { int64_t xoff, poff, doff; int n; };          // element offsets into the logits, into labels / pred, into dlogits (class 0)
 __device__ __forceinline__ DnChunk dn_chunk(const DenseArgs& a, int64_t ch, int V) {
@@ -163,25 +274,15 @@ template <int KT> __device__ __forceinline__ void dn_write_row(float* ws, unsign
 }
 
 // ---- (a) the forward pass ---------------------------------------------------------------------------------------------------------------------------
-// LDS (dynamic): KT > 0: red [waves][3 KT + 3] floats | conf [K K] ints;  KT == 0: accP [K][threads] | accI [K][threads] floats | cntT [K] ints | red [waves][3] | conf
 template <typename T, typename LT, int KT> __global__ __launch_bounds__(256) void dense_fwd_kernel(const DenseArgs a) {
   constexpr int V = DT<T>::EPC;
   constexpr int KR = KT > 0 ? KT : 1;
   extern __shared__ float smem[];
   const int K = KT > 0 ? KT : a.K;
-  const int NT = blockDim.x, tid = threadIdx.x, nw = NT >> 6;
-  float* accP = smem;
-  float* accI = smem + (KT > 0 ? 0 : K * NT);
-  int* cntT = reinterpret_cast<int*>(smem + (KT > 0 ? 0 : 2 * K * NT));
-  float* red = smem + (KT > 0 ? 0 : 2 * K * NT + K);
-  int* conf = reinterpret_cast<int*>(red + (KT > 0 ? nw * (3 * KT + 3) : nw * 3));
-  if (KT == 0) {
-    for (int i = tid; i < 2 * K * NT; i += NT) smem[i] = 0.f;
-    for (int i = tid; i < K; i += NT) cntT[i] = 0;
-  }
-  if (a.conf)
-    for (int i = tid; i < K * K; i += NT) conf[i] = 0;
-  __syncthreads();
+  const int NT = blockDim.x, tid = threadIdx.x;
+  const DnLds s = dn_lds<KT>(smem, K, true, a.conf != nullptr);
+  float* accP = s.accP;
+  float* accI = s.accI;
 
   float rP[KR], rI[KR];
   int rT[KR];
@@ -198,43 +299,21 @@ template <typename T, typename LT, int KT> __global__ __launch_bounds__(256) voi
     const T* x = X + c.xoff;
     int y[V];
     dn_labels<V>(L + c.poff, a.lvec && full, c.n, a.ignore, K, y);
-    float mx[V], se[V], zy[V], py[V];
+    float se[V], zy[V], py[V];
     int bi[V];
     if constexpr (KT > 0) {
       float z[KT][V];
 #pragma unroll
       for (int k = 0; k < KT; ++k) dn_load<T>(x + k * a.sc, a.xvec && full, c.n, z[k]);
+      // column j of z.  Ignored pixels are NOT branched around here: V branches per chunk cost this pass scalar registers and, at K = 3, a wave of occupancy
+#define DN_Z(k) z[k][j]
 #pragma unroll
-      for (int j = 0; j < V; ++j) {
-        float best = z[0][j], m = z[0][j];
-        int b = 0;
-#pragma unroll
-        for (int k = 1; k < KT; ++k) {
-          if (dn_better(z[k][j], best)) { best = z[k][j]; b = k; }
-          m = fmaxf(m, z[k][j]);
-        }
-        bi[j] = b; mx[j] = m;
-        float s = 0.f;
-        zy[j] = 0.f; py[j] = 0.f;
-#pragma unroll
-        for (int k = 0; k < KT; ++k) {          // z now holds the exponentials
-          const float dz = z[k][j] - m;
-          if (y[j] == k) zy[j] = dz;          // z_y - max
-          z[k][j] = expf(dz); s += z[k][j];
-        }
-        se[j] = s;
-        const float inv = 1.f / s;
-        const bool on = y[j] >= 0;
-#pragma unroll
-        for (int k = 0; k < KT; ++k) {
-          const float p = z[k][j] * inv;
-          const bool hit = y[j] == k;
-          if (on) rP[k] += p;
-          if (hit) { rI[k] += p; rT[k] += 1; py[j] = p; }
-        }
-      }
+      for (int j = 0; j < V; ++j) DN_PIXEL(KT, DN_Z, y[j], false, bi[j], se[j], zy[j], py[j], rP, rI, rT);
+#undef DN_Z
     } else {
-      float f[V];
+      // DELIBERATELY not the upsampling kernel's generic path: class-major over the chunk, ONE 16-byte load per class plane for V pixels (this pass is the
+      // memory-bound one), and the softmax of an ignored pixel is evaluated and discarded rather than branched around
+      float f[V], mx[V];
       dn_load<T>(x, a.xvec && full, c.n, f);
 #pragma unroll
       for (int j = 0; j < V; ++j) { mx[j] = f[j]; se[j] = f[j]; bi[j] = 0; }          // se: the best value so far
@@ -263,41 +342,17 @@ template <typename T, typename LT, int KT> __global__ __launch_bounds__(256) voi
           const float e = expf(f[j] - mx[j]);
           const float p = e * (1.f / se[j]);
           if (y[j] >= 0) sp += p;
-          if (y[j] == k) { accI[k * NT + tid] += p; atomicAdd(&cntT[k], 1); zy[j] = f[j] - mx[j]; py[j] = p; }
+          if (y[j] == k) { accI[k * NT + tid] += p; atomicAdd(&s.cntT[k], 1); zy[j] = f[j] - mx[j]; py[j] = p; }
         }
         accP[k * NT + tid] = sp;
       }
     }
 #pragma unroll
-    for (int j = 0; j < V; ++j) {
-      if (y[j] >= 0) {
-        const float nll = logf(se[j]) - zy[j];          // -log p_y = log(sum exp(z - max)) - (z_y - max)
-        ce_sum += dn_focal(a.alpha, a.gamma, y[j], py[j]) * nll;
-        nll_sum += nll;
-        nvalid += 1;
-        if (a.conf) atomicAdd(&conf[y[j] * K + bi[j]], 1);
-      }
-    }
-    if (a.pred) {
-      uint8_t* pp = a.pred + c.poff;
-      if (a.pvec && full) {
-        if (V == 4) {
-          *reinterpret_cast<uint32_t*>(pp) = (uint32_t)bi[0] | ((uint32_t)bi[1] << 8) | ((uint32_t)bi[2] << 16) | ((uint32_t)bi[3] << 24);
-        } else {
-          uint32_t w[2] = {0u, 0u};
-#pragma unroll
-          for (int j = 0; j < V; ++j) w[j >> 2] |= (uint32_t)bi[j] << (8 * (j & 3));
-          *reinterpret_cast<uint2*>(pp) = make_uint2(w[0], w[1]);
-        }
-      } else {
-#pragma unroll
-        for (int j = 0; j < V; ++j)
-          if (j < c.n) pp[j] = (uint8_t)bi[j];
-      }
-    }
+    for (int j = 0; j < V; ++j) dn_pixel_tail(a, a.t, K, s.conf, y[j], bi[j], se[j], zy[j], py[j], ce_sum, nll_sum, nvalid);
+    if (a.pred) dn_store_pred<V>(a.pred + c.poff, a.pvec && full, c.n, bi);
   }
 
-  dn_write_row<KT>(a.ws, a.conf, K, smem, red, cntT, conf, rP, rI, rT, ce_sum, nll_sum, nvalid);
+  dn_write_row<KT>(a.ws, a.conf, K, smem, s.red, s.cntT, s.conf, rP, rI, rT, ce_sum, nll_sum, nvalid);
 }
 
 // ---- (b) rows -> stats ------------------------------------------------------------------------------------------------------------------------------
@@ -386,23 +441,18 @@ template <typename T, typename LT, int KT> __global__ __launch_bounds__(256) voi
 #pragma unroll
         for (int k = 0; k < KT; ++k) { z[k][j] = expf(z[k][j] - m); s += z[k][j]; }
         const float inv = 1.f / s;
-        float py = 0.f, sg = 0.f;
+        float py = 0.f, sg = 0.f;          // sg = sum_k p_k (v_k + [hit] u_k) with p_k = e_k inv: NOT the upsampling backward's (sum_k e_k (..)) inv
 #pragma unroll
         for (int k = 0; k < KT; ++k) {
           z[k][j] = z[k][j] * inv;          // p_k
           const bool hit = y[j] == k;
           if (hit) py = z[k][j];
-          if (a.shape_terms) sg += z[k][j] * (Vt[k] + (hit ? U[k] : 0.f));
+          if (a.t.shape_terms) sg += z[k][j] * dn_shape(hit, U[k], Vt[k]);
         }
         const bool on = y[j] >= 0;
-        const float cf = on ? a.w_ce * dn_focal(a.alpha, a.gamma, y[j], py) * invD : 0.f;
+        const float cf = on ? dn_cf(a, a.t, invD, y[j], py) : 0.f;
 #pragma unroll
-        for (int k = 0; k < KT; ++k) {
-          const bool hit = y[j] == k;
-          float g = cf * (z[k][j] - (hit ? 1.f : 0.f));
-          if (a.shape_terms) g = z[k][j] * ((Vt[k] + (hit ? U[k] : 0.f)) - sg) + g;
-          z[k][j] = on ? gout * g : 0.f;
-        }
+        for (int k = 0; k < KT; ++k) z[k][j] = on ? dn_grad(a.t, z[k][j], y[j] == k, cf, U, Vt, k, sg, gout) : 0.f;
       }
 #pragma unroll
       for (int k = 0; k < KT; ++k) dn_store<T>(d + k * plane, a.dvec && full, c.n, z[k]);
@@ -431,21 +481,17 @@ template <typename T, typename LT, int KT> __global__ __launch_bounds__(256) voi
           const float p = expf(f[j] - mx[j]) * (1.f / se[j]);
           const bool hit = y[j] == k;
           if (hit) py[j] = p;
-          if (a.shape_terms) sg[j] += p * (vk + (hit ? uk : 0.f));
+          if (a.t.shape_terms) sg[j] += p * dn_shape(hit, uk, vk);
         }
       }
 #pragma unroll
-      for (int j = 0; j < V; ++j) cf[j] = y[j] >= 0 ? a.w_ce * dn_focal(a.alpha, a.gamma, y[j], py[j]) * invD : 0.f;
+      for (int j = 0; j < V; ++j) cf[j] = y[j] >= 0 ? dn_cf(a, a.t, invD, y[j], py[j]) : 0.f;
       for (int k = 0; k < K; ++k) {
         dn_load<T>(x + k * a.sc, a.xvec && full, c.n, f);
-        const float uk = U[k], vk = Vt[k];
 #pragma unroll
         for (int j = 0; j < V; ++j) {
           const float p = expf(f[j] - mx[j]) * (1.f / se[j]);
-          const bool hit = y[j] == k;
-          float g = cf[j] * (p - (hit ? 1.f : 0.f));
-          if (a.shape_terms) g = p * ((vk + (hit ? uk : 0.f)) - sg[j]) + g;
-          f[j] = y[j] >= 0 ? gout * g : 0.f;
+          f[j] = y[j] >= 0 ? dn_grad(a.t, p, y[j] == k, cf[j], U, Vt, k, sg[j], gout) : 0.f;
         }
         dn_store<T>(d + k * plane, a.dvec && full, c.n, f);
       }
@@ -456,15 +502,10 @@ template <typename T, typename LT, int KT> __global__ __launch_bounds__(256) voi
 // ---- the same losses on bilinearly upsampled logits -------------------------------------------------------------------------------------------------
 // logits [B, K, h, w] -> PyTorch's upsample_bilinear2d to the label map's [H, W] (the `size=` form: the scale comes from the sizes), evaluated per output pixel in
 // fp32 and never stored.  A bf16 input is NOT rounded back to bf16 after the interpolation (the stock path rounds the [B, K, H, W] map it writes): more accurate.
-struct UpArgs {
-  const void* logits; const void* labels; const float* alpha;
-  float* ws; uint8_t* pred; unsigned long long* conf;
-  const float* stats; const float* gout; void* dlogits;
-  int64_t sb, sc, ignore, nchunks;
-  int B, K, h, w, H, W, cpr, align;          // cpr: chunks per output row
+struct UpArgs : DenseHead {
+  int h, w, H, W, cpr, align;          // cpr: chunks per output row
   float sy, sx;          // input / output (align_corners: (in - 1) / (out - 1), 0 when out == 1), in float as PyTorch computes it
-  float gamma, w_ce;
-  int shape_terms;
+  DenseTerms t;
   int TH, TW, FBH, FBW, tiles_y, tiles_x, G;          // backward: the tile of input pixels, the block of output pixels in LDS, threads per input pixel of the gather
 };
 
@@ -501,29 +542,16 @@ template <typename T> __device__ __forceinline__ float up_tap(const T* p, int r0
   return (1.f - ly) * ((1.f - lx) * z00 + lx * z01) + ly * ((1.f - lx) * z10 + lx * z11);
 }
 
-// ---- forward: a thread owns chunks of UP_V consecutive output pixels of ONE output row; the LDS layout, the row and the summation discipline of dense_fwd_kernel ----
-// labels == NULL: prediction only (argmax map, no sums, no row).  The softmax of an ignored pixel is not evaluated: it contributes to nothing.
+// ---- forward: a thread owns chunks of UP_V consecutive output pixels of ONE output row; the LDS layout, the pixel, the row and the summation discipline of dense_fwd_kernel ----
+// labels == NULL: prediction only (argmax map, no sums, no row).
 template <typename T, typename LT, int KT> __global__ __launch_bounds__(256) void dense_up_fwd_kernel(const UpArgs a) {
   constexpr int V = UP_V;
   constexpr int KR = KT > 0 ? KT : 1;
   extern __shared__ float smem[];
   const int K = KT > 0 ? KT : a.K;
-  const int NT = blockDim.x, tid = threadIdx.x, nw = NT >> 6;
-  float* accP = smem;
-  float* accI = smem + (KT > 0 ? 0 : K * NT);
-  int* cntT = reinterpret_cast<int*>(smem + (KT > 0 ? 0 : 2 * K * NT));
-  float* red = smem + (KT > 0 ? 0 : 2 * K * NT + K);
-  int* conf = reinterpret_cast<int*>(red + (KT > 0 ? nw * (3 * KT + 3) : nw * 3));
+  const int NT = blockDim.x, tid = threadIdx.x;
   const bool sums = a.labels != nullptr;
-  if (sums) {
-    if (KT == 0) {
-      for (int i = tid; i < 2 * K * NT; i += NT) smem[i] = 0.f;
-      for (int i = tid; i < K; i += NT) cntT[i] = 0;
-    }
-    if (a.conf)
-      for (int i = tid; i < K * K; i += NT) conf[i] = 0;
-    __syncthreads();
-  }
+  const DnLds s = dn_lds<KT>(smem, K, sums, a.conf != nullptr);
   float rP[KR], rI[KR];
   int rT[KR];
 #pragma unroll
@@ -555,38 +583,17 @@ template <typename T, typename LT, int KT> __global__ __launch_bounds__(256) voi
       bi[j] = 0;
       if (j >= n) continue;
       const UpAxis ax = up_axis(X0 + j, a.w, a.sx, a.align);
-      const bool on = y[j] >= 0;
       float se = 1.f, zy = 0.f, py = 0.f;
       if constexpr (KT > 0) {
         float z[KT];
 #pragma unroll
         for (int k = 0; k < KT; ++k) z[k] = up_tap<T>(x + k * a.sc, r0, r1, ax.i0, ax.i1, ay.l, ax.l);
-        float best = z[0], m = z[0];
-        int bb = 0;
-#pragma unroll
-        for (int k = 1; k < KT; ++k) {
-          if (dn_better(z[k], best)) { best = z[k]; bb = k; }
-          m = fmaxf(m, z[k]);
-        }
-        bi[j] = bb;
-        if (on) {
-          float s = 0.f;
-#pragma unroll
-          for (int k = 0; k < KT; ++k) {          // z now holds the exponentials
-            const float dz = z[k] - m;
-            if (y[j] == k) zy = dz;
-            z[k] = expf(dz); s += z[k];
-          }
-          se = s;
-          const float inv = 1.f / s;
-#pragma unroll
-          for (int k = 0; k < KT; ++k) {
-            const float p = z[k] * inv;
-            rP[k] += p;
-            if (y[j] == k) { rI[k] += p; rT[k] += 1; py = p; }
-          }
-        }
+#define DN_Z(k) z[k]
+        DN_PIXEL(KT, DN_Z, y[j], true, bi[j], se, zy, py, rP, rI, rT);          // ignored pixels ARE branched around: in the prediction-only form every pixel is one
+#undef DN_Z
       } else {
+        // DELIBERATELY not dense_fwd_kernel's generic path: pixel-major over the taps (a class plane's four taps are not a 16-byte word), and an ignored
+        // pixel is branched around, as above
         float best = up_tap<T>(x, r0, r1, ax.i0, ax.i1, ay.l, ax.l), m = best;
         int bb = 0;
         for (int k = 1; k < K; ++k) {
@@ -595,39 +602,24 @@ template <typename T, typename LT, int KT> __global__ __launch_bounds__(256) voi
           m = fmaxf(m, z);
         }
         bi[j] = bb;
-        if (on) {
-          float s = 0.f;
-          for (int k = 0; k < K; ++k) s += expf(up_tap<T>(x + k * a.sc, r0, r1, ax.i0, ax.i1, ay.l, ax.l) - m);
-          se = s;
-          const float inv = 1.f / s;
+        if (y[j] >= 0) {
+          float sum = 0.f;
+          for (int k = 0; k < K; ++k) sum += expf(up_tap<T>(x + k * a.sc, r0, r1, ax.i0, ax.i1, ay.l, ax.l) - m);
+          se = sum;
+          const float inv = 1.f / sum;
           for (int k = 0; k < K; ++k) {
             const float dz = up_tap<T>(x + k * a.sc, r0, r1, ax.i0, ax.i1, ay.l, ax.l) - m;
             const float p = expf(dz) * inv;
-            accP[k * NT + tid] += p;
-            if (y[j] == k) { accI[k * NT + tid] += p; atomicAdd(&cntT[k], 1); zy = dz; py = p; }
+            s.accP[k * NT + tid] += p;
+            if (y[j] == k) { s.accI[k * NT + tid] += p; atomicAdd(&s.cntT[k], 1); zy = dz; py = p; }
           }
         }
       }
-      if (on) {
-        const float nll = logf(se) - zy;          // -log p_y = log(sum exp(z - max)) - (z_y - max)
-        ce_sum += dn_focal(a.alpha, a.gamma, y[j], py) * nll;
-        nll_sum += nll;
-        nvalid += 1;
-        if (a.conf) atomicAdd(&conf[y[j] * K + bi[j]], 1);
-      }
+      dn_pixel_tail(a, a.t, K, s.conf, y[j], bi[j], se, zy, py, ce_sum, nll_sum, nvalid);
     }
-    if (a.pred) {
-      uint8_t* pp = a.pred + poff;
-      if (n == V && (((uintptr_t)pp) & 3u) == 0) {
-        *reinterpret_cast<uint32_t*>(pp) = (uint32_t)bi[0] | ((uint32_t)bi[1] << 8) | ((uint32_t)bi[2] << 16) | ((uint32_t)bi[3] << 24);
-      } else {
-#pragma unroll
-        for (int j = 0; j < V; ++j)
-          if (j < n) pp[j] = (uint8_t)bi[j];
-      }
-    }
+    if (a.pred) dn_store_pred<V>(a.pred + poff, n == V && (((uintptr_t)(a.pred + poff)) & 3u) == 0, n, bi);          // rows start anywhere (W = 37): alignment per chunk
   }
-  if (sums) dn_write_row<KT>(a.ws, a.conf, K, smem, red, cntT, conf, rP, rI, rT, ce_sum, nll_sum, nvalid);
+  if (sums) dn_write_row<KT>(a.ws, a.conf, K, smem, s.red, s.cntT, s.conf, rP, rI, rT, ce_sum, nll_sum, nvalid);
 }
 
 // ---- backward: ONE launch, every element of dlogits [B, K, h, w] written once, no atomics ----
@@ -741,11 +733,12 @@ template <typename T, typename LT, bool STAGE> __global__ __launch_bounds__(256)
           const bool hit = yv == k;
           s += e;
           if (hit) ey = e;
-          if (a.shape_terms) sgu += e * (Vt[k] + (hit ? U[k] : 0.f));
+          if (a.t.shape_terms) sgu += e * dn_shape(hit, U[k], Vt[k]);
         }
         const float inv = 1.f / s;
+        // DELIBERATELY not dense_bwd_kernel's order: sg = (sum_k e_k (v_k + [hit] u_k)) inv and p_y = e_y inv, one multiply per pixel instead of one per class
         sM[f] = m; sInv[f] = inv; sSg[f] = sgu * inv;
-        sCf[f] = a.w_ce * dn_focal(a.alpha, a.gamma, yv, ey * inv) * invD;
+        sCf[f] = dn_cf(a, a.t, invD, yv, ey * inv);
       }
       __syncthreads();
       const int rl = gather ? rng[gy] : 0, rh = gather ? rng[8 + gy] : 0, cl = gather ? rng[16 + gx] : 0, chh = gather ? rng[24 + gx] : 0;
@@ -754,18 +747,14 @@ template <typename T, typename LT, bool STAGE> __global__ __launch_bounds__(256)
       // (2) per class: plane, barrier, gather
       for (int k = 0; k < K; ++k) {
         float* pl = plane + (k & 1) * FB;
-        const float uk = U[k], vk = Vt[k];
+        const float uk = U[k], vk = Vt[k];          // once per class, in front of the pixel loop: this kernel has no scalar register to spare for reads inside it
         for (int f = tid; f < bh * bw; f += NT) {
           const int yv = sY[f];
           float g = 0.f;
           if (yv >= 0) {
             const int Yr = f / bw, Xr = f - Yr * bw;
             const float z = up_tap<ZT>(zb + k * zk, (yI0[Yr] - y0s) * zpitch, (yI1[Yr] - y0s) * zpitch, xI0[Xr] - x0s, xI1[Xr] - x0s, yL[Yr], xL[Xr]);
-            const float p = expf(z - sM[f]) * sInv[f];
-            const bool hit = yv == k;
-            g = sCf[f] * (p - (hit ? 1.f : 0.f));
-            if (a.shape_terms) g = p * ((vk + (hit ? uk : 0.f)) - sSg[f]) + g;
-            g = gout * g;
+            g = dn_grad(a.t, expf(z - sM[f]) * sInv[f], yv == k, sCf[f], &uk, &vk, 0, sSg[f], gout);
           }
           pl[f] = g;
         }
@@ -815,20 +804,61 @@ static int dn_validate(const char* fn, const void* logits, int dtype, int64_t sb
   return LMV_OK;
 }
 
+// the common head of both argument structs
+static void dn_head(DenseHead& a, DenseTerms& t, const void* logits, int64_t sb, int64_t sc, int B, int K, const void* labels, int64_t ignore, const float* alpha, float gamma,
+                    float w_ce, float w_dice, float w_jac) {
+  a.logits = logits; a.labels = labels; a.alpha = alpha;
+  a.sb = sb; a.sc = sc; a.ignore = ignore;
+  a.B = B; a.K = K;
+  t.gamma = gamma; t.w_ce = w_ce; t.shape_terms = (w_dice != 0.f || w_jac != 0.f) ? 1 : 0;
+}
+
 static DenseArgs dn_args(const void* logits, int dtype, int64_t sb, int64_t sc, int B, int K, int64_t HW, const void* labels, int label_dtype, int64_t ignore,
                          const float* alpha, float gamma, float w_ce, float w_dice, float w_jac) {
   const int V = dtype == LMV_F32 ? 4 : 8;
   DenseArgs a = {};
-  a.logits = logits; a.labels = labels; a.alpha = alpha;
-  a.sb = sb; a.sc = sc; a.ignore = ignore;
-  a.B = B; a.K = K; a.HW = (int)HW; a.cpi = (int)dn_cdiv(HW, V);
+  dn_head(a, a.t, logits, sb, sc, B, K, labels, ignore, alpha, gamma, w_ce, w_dice, w_jac);
+  a.HW = (int)HW; a.cpi = (int)dn_cdiv(HW, V);
   a.nchunks = (int64_t)B * a.cpi;
   a.xvec = lmv_aligned16(logits) && sb % V == 0 && sc % V == 0;
   a.lvec = lmv_aligned16(labels) && HW % V == 0;
-  a.gamma = gamma; a.w_ce = w_ce; a.shape_terms = (w_dice != 0.f || w_jac != 0.f) ? 1 : 0;
   return a;
 }
 
+// ---- the checks and the second launch that the four entry points share; fn: the entry point's name, the head of every message ----
+static int dn_check_fwd(const char* fn, const char* sizer, const void* workspace, size_t workspace_bytes, int rows, int K, const float* stats, const int64_t* conf, const double* meter) {
+  if (!workspace || !stats) LMV_FAIL(LMV_ERR_SHAPE, "%s: null workspace / stats", fn);
+  if ((((uintptr_t)workspace) & 3u) || (((uintptr_t)stats) & 3u) || (((uintptr_t)conf) & 7u) || (((uintptr_t)meter) & 7u)) LMV_FAIL(LMV_ERR_SHAPE, "%s: misaligned buffer", fn);
+  const size_t need = (size_t)rows * (size_t)(3 * K + 3) * sizeof(float);
+  if (workspace_bytes < need) LMV_FAIL(LMV_ERR_SHAPE, "%s: workspace of %zu bytes, %zu needed (%s)", fn, workspace_bytes, need, sizer);
+  return LMV_OK;
+}
+
+static int dn_check_bwd(const char* fn, int dtype, const float* stats, const float* gout, const void* dlogits) {
+  if (!stats || !dlogits) LMV_FAIL(LMV_ERR_SHAPE, "%s: null stats / dlogits", fn);
+  if ((((uintptr_t)stats) & 3u) || (((uintptr_t)gout) & 3u) || (((uintptr_t)dlogits) & (dtype == LMV_F32 ? 3u : 1u))) LMV_FAIL(LMV_ERR_SHAPE, "%s: misaligned buffer", fn);
+  return LMV_OK;
+}
+
+static int dn_finalize(const char* fn, const float* ws, int rows, int K, double npix, const float* alpha, float w_ce, float w_dice, float w_jac, float eps,
+                       int avg_mode, float* stats, double* meter, hipStream_t st) {
+  DenseFinArgs f;
+  f.ws = ws; f.alpha = alpha; f.stats = stats; f.meter = meter; f.rows = rows; f.K = K; f.avg_mode = avg_mode;
+  f.npix = npix; f.w_ce = w_ce; f.w_dice = w_dice; f.w_jac = w_jac; f.eps = eps;
+  hipLaunchKernelGGL(dense_finalize_kernel, dim3(1), dim3(256), 0, st, f);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) LMV_FAIL(LMV_ERR_LAUNCH, "%s (finalize): %s", fn, hipGetErrorString(e));
+  return LMV_OK;
+}
+
+// THE type switch of every launch here: f(T(), LT()) with the logits' and the labels' element types as (value-less) tags
+template <typename F> static void dn_for_types(int dtype, int label_dtype, F&& f) {
+  if (dtype == LMV_F32) {
+    if (label_dtype == LMV_DENSE_LABEL_I64) f(float(), int64_t()); else f(float(), uint8_t());
+  } else {
+    if (label_dtype == LMV_DENSE_LABEL_I64) f(bf16_t(), int64_t()); else f(bf16_t(), uint8_t());
+  }
+}
 #define DN_FOR_K(KERNEL, T, LT, ...)                                                              \
   switch (a.K <= DN_KREG ? a.K : 0) {                                                             \
     case 2: hipLaunchKernelGGL((KERNEL<T, LT, 2>), __VA_ARGS__); break;                           \
@@ -837,16 +867,8 @@ static DenseArgs dn_args(const void* logits, int dtype, int64_t sb, int64_t sc, 
     case 5: hipLaunchKernelGGL((KERNEL<T, LT, 5>), __VA_ARGS__); break;                           \
     default: hipLaunchKernelGGL((KERNEL<T, LT, 0>), __VA_ARGS__); break;                          \
   }
-#define DN_DISPATCH(KERNEL, ...)                                                                  \
-  do {                                                                                            \
-    if (dtype == LMV_F32) {                                                                       \
-      if (label_dtype == LMV_DENSE_LABEL_I64) { DN_FOR_K(KERNEL, float, int64_t, __VA_ARGS__) }   \
-      else { DN_FOR_K(KERNEL, float, uint8_t, __VA_ARGS__) }                                      \
-    } else {                                                                                      \
-      if (label_dtype == LMV_DENSE_LABEL_I64) { DN_FOR_K(KERNEL, bf16_t, int64_t, __VA_ARGS__) }  \
-      else { DN_FOR_K(KERNEL, bf16_t, uint8_t, __VA_ARGS__) }                                     \
-    }                                                                                             \
-  } while (0)
+#define DN_DISPATCH(KERNEL, ...) \
+  dn_for_types(dtype, label_dtype, [&](auto t, auto l) { DN_FOR_K(KERNEL, decltype(t), decltype(l), __VA_ARGS__) })
 }  // namespace
 
 extern "C" size_t lmv_dense_loss_workspace_bytes(int B, int K, int64_t HW) {
@@ -857,42 +879,33 @@ extern "C" size_t lmv_dense_loss_workspace_bytes(int B, int K, int64_t HW) {
 extern "C" int lmv_dense_loss_fwd(const void* logits, int dtype, int64_t batch_stride, int64_t class_stride, int B, int K, int64_t HW, const void* labels,
                                   int label_dtype, int64_t ignore_index, const float* alpha, float gamma, float w_ce, float w_dice, float w_jac, float eps,
                                   int avg_mode, void* workspace, size_t workspace_bytes, float* stats, uint8_t* pred, int64_t* conf, double* meter, void* stream) {
-  if (int rc = dn_validate("dense_loss_fwd", logits, dtype, batch_stride, class_stride, B, K, HW, labels, label_dtype, alpha, gamma, w_ce, w_dice, w_jac, eps, avg_mode)) return rc;
-  if (!workspace || !stats) LMV_FAIL(LMV_ERR_SHAPE, "dense_loss_fwd: null workspace / stats");
-  if ((((uintptr_t)workspace) & 3u) || (((uintptr_t)stats) & 3u) || (((uintptr_t)conf) & 7u) || (((uintptr_t)meter) & 7u)) LMV_FAIL(LMV_ERR_SHAPE, "dense_loss_fwd: misaligned buffer");
+  const char* fn = "dense_loss_fwd";
+  if (int rc = dn_validate(fn, logits, dtype, batch_stride, class_stride, B, K, HW, labels, label_dtype, alpha, gamma, w_ce, w_dice, w_jac, eps, avg_mode)) return rc;
   const int V = dtype == LMV_F32 ? 4 : 8;
   const int rows = dn_rows(B, K, HW, V, DN_MAX_WG), NT = dn_threads(K);
-  if (workspace_bytes < (size_t)rows * (size_t)(3 * K + 3) * sizeof(float))
-    LMV_FAIL(LMV_ERR_SHAPE, "dense_loss_fwd: workspace of %zu bytes, %zu needed (lmv_dense_loss_workspace_bytes)", workspace_bytes, (size_t)rows * (size_t)(3 * K + 3) * sizeof(float));
+  if (int rc = dn_check_fwd(fn, "lmv_dense_loss_workspace_bytes", workspace, workspace_bytes, rows, K, stats, conf, meter)) return rc;
   DenseArgs a = dn_args(logits, dtype, batch_stride, class_stride, B, K, HW, labels, label_dtype, ignore_index, alpha, gamma, w_ce, w_dice, w_jac);
   a.ws = reinterpret_cast<float*>(workspace); a.pred = pred; a.conf = reinterpret_cast<unsigned long long*>(conf);
   a.pvec = pred && (((uintptr_t)pred) & 7u) == 0 && HW % V == 0;
-  const int nw = NT / 64;
-  const size_t lds = (K <= DN_KREG ? (size_t)nw * (3 * K + 3) : (size_t)2 * K * NT + K + (size_t)nw * 3) * sizeof(float) + (conf ? (size_t)K * K * sizeof(int) : 0);
   hipStream_t st = (hipStream_t)stream;
-  DN_DISPATCH(dense_fwd_kernel, dim3(rows), dim3(NT), lds, st, a);
-  LMV_CHECK_LAUNCH("dense_loss_fwd");
-  DenseFinArgs f;
-  f.ws = a.ws; f.alpha = alpha; f.stats = stats; f.meter = meter; f.rows = rows; f.K = K; f.avg_mode = avg_mode;
-  f.npix = (double)B * (double)HW; f.w_ce = w_ce; f.w_dice = w_dice; f.w_jac = w_jac; f.eps = eps;
-  hipLaunchKernelGGL(dense_finalize_kernel, dim3(1), dim3(256), 0, st, f);
-  LMV_CHECK_LAUNCH("dense_loss_fwd (finalize)");
-  return LMV_OK;
+  DN_DISPATCH(dense_fwd_kernel, dim3(rows), dim3(NT), dn_lds_bytes(K, NT, conf != nullptr), st, a);
+  LMV_CHECK_LAUNCH(fn);
+  return dn_finalize(fn, a.ws, rows, K, (double)B * (double)HW, alpha, w_ce, w_dice, w_jac, eps, avg_mode, stats, meter, st);
 }
 
 extern "C" int lmv_dense_loss_bwd(const void* logits, int dtype, int64_t batch_stride, int64_t class_stride, int B, int K, int64_t HW, const void* labels,
                                   int label_dtype, int64_t ignore_index, const float* alpha, float gamma, float w_ce, float w_dice, float w_jac, float eps,
                                   int avg_mode, const float* stats, const float* gout, void* dlogits, void* stream) {
-  if (int rc = dn_validate("dense_loss_bwd", logits, dtype, batch_stride, class_stride, B, K, HW, labels, label_dtype, alpha, gamma, w_ce, w_dice, w_jac, eps, avg_mode)) return rc;
-  if (!stats || !dlogits) LMV_FAIL(LMV_ERR_SHAPE, "dense_loss_bwd: null stats / dlogits");
-  if ((((uintptr_t)stats) & 3u) || (((uintptr_t)gout) & 3u) || (((uintptr_t)dlogits) & (dtype == LMV_F32 ? 3u : 1u))) LMV_FAIL(LMV_ERR_SHAPE, "dense_loss_bwd: misaligned buffer");
+  const char* fn = "dense_loss_bwd";
+  if (int rc = dn_validate(fn, logits, dtype, batch_stride, class_stride, B, K, HW, labels, label_dtype, alpha, gamma, w_ce, w_dice, w_jac, eps, avg_mode)) return rc;
+  if (int rc = dn_check_bwd(fn, dtype, stats, gout, dlogits)) return rc;
   const int V = dtype == LMV_F32 ? 4 : 8;
   DenseArgs a = dn_args(logits, dtype, batch_stride, class_stride, B, K, HW, labels, label_dtype, ignore_index, alpha, gamma, w_ce, w_dice, w_jac);
   a.stats = stats; a.gout = gout; a.dlogits = dlogits;
   a.dvec = lmv_aligned16(dlogits) && HW % V == 0;
   const int NT = 256, rows = (int)std::min<int64_t>(dn_cdiv(a.nchunks, NT), DN_MAX_WG_BWD);
   DN_DISPATCH(dense_bwd_kernel, dim3(rows), dim3(NT), 0, (hipStream_t)stream, a);
-  LMV_CHECK_LAUNCH("dense_loss_bwd");
+  LMV_CHECK_LAUNCH(fn);
   return LMV_OK;
 }
 
@@ -930,25 +943,12 @@ static void up_tile(int in, int out, int* T, int* FBd) {
 static UpArgs up_args(const void* logits, int64_t sb, int64_t sc, int B, int K, int h, int w, int H, int W, int align, const void* labels, int64_t ignore,
                       const float* alpha, float gamma, float w_ce, float w_dice, float w_jac) {
   UpArgs a = {};
-  a.logits = logits; a.labels = labels; a.alpha = alpha;
-  a.sb = sb; a.sc = sc; a.ignore = ignore;
-  a.B = B; a.K = K; a.h = h; a.w = w; a.H = H; a.W = W; a.align = align;
+  dn_head(a, a.t, logits, sb, sc, B, K, labels, ignore, alpha, gamma, w_ce, w_dice, w_jac);
+  a.h = h; a.w = w; a.H = H; a.W = W; a.align = align;
   a.cpr = (int)dn_cdiv(W, UP_V); a.nchunks = (int64_t)B * H * a.cpr;
   a.sy = up_scale(h, H, align); a.sx = up_scale(w, W, align);
-  a.gamma = gamma; a.w_ce = w_ce; a.shape_terms = (w_dice != 0.f || w_jac != 0.f) ? 1 : 0;
   return a;
 }
-
-#define UP_DISPATCH_BWD(STAGE, ...)                                                                                                 \
-  do {                                                                                                                              \
-    if (dtype == LMV_F32) {                                                                                                         \
-      if (label_dtype == LMV_DENSE_LABEL_I64) hipLaunchKernelGGL((dense_up_bwd_kernel<float, int64_t, STAGE>), __VA_ARGS__);        \
-      else hipLaunchKernelGGL((dense_up_bwd_kernel<float, uint8_t, STAGE>), __VA_ARGS__);                                           \
-    } else {                                                                                                                        \
-      if (label_dtype == LMV_DENSE_LABEL_I64) hipLaunchKernelGGL((dense_up_bwd_kernel<bf16_t, int64_t, STAGE>), __VA_ARGS__);       \
-      else hipLaunchKernelGGL((dense_up_bwd_kernel<bf16_t, uint8_t, STAGE>), __VA_ARGS__);                                          \
-    }                                                                                                                               \
-  } while (0)
 }  // namespace
 
 extern "C" size_t lmv_dense_up_loss_workspace_bytes(int B, int K, int H, int W) {
@@ -965,27 +965,16 @@ extern "C" int lmv_dense_up_loss_fwd(const void* logits, int dtype, int64_t batc
   if (int rc = up_validate(fn, logits, dtype, batch_stride, class_stride, B, K, h, w, H, W, align_corners, labels, pred == nullptr, label_dtype, alpha, gamma, w_ce,
                            w_dice, w_jac, eps, avg_mode)) return rc;
   const int rows = up_rows(B, K, H, W), NT = dn_threads(K);
-  if (labels) {
-    if (!workspace || !stats) LMV_FAIL(LMV_ERR_SHAPE, "%s: null workspace / stats", fn);
-    if ((((uintptr_t)workspace) & 3u) || (((uintptr_t)stats) & 3u) || (((uintptr_t)conf) & 7u) || (((uintptr_t)meter) & 7u)) LMV_FAIL(LMV_ERR_SHAPE, "%s: misaligned buffer", fn);
-    if (workspace_bytes < (size_t)rows * (size_t)(3 * K + 3) * sizeof(float))
-      LMV_FAIL(LMV_ERR_SHAPE, "%s: workspace of %zu bytes, %zu needed (lmv_dense_up_loss_workspace_bytes)", fn, workspace_bytes, (size_t)rows * (size_t)(3 * K + 3) * sizeof(float));
-  }
+  if (labels)
+    if (int rc = dn_check_fwd(fn, "lmv_dense_up_loss_workspace_bytes", workspace, workspace_bytes, rows, K, stats, conf, meter)) return rc;
   UpArgs a = up_args(logits, batch_stride, class_stride, B, K, h, w, H, W, align_corners, labels, ignore_index, alpha, gamma, w_ce, w_dice, w_jac);
   a.ws = reinterpret_cast<float*>(workspace); a.pred = pred; a.conf = labels ? reinterpret_cast<unsigned long long*>(conf) : nullptr;
   if (!labels) label_dtype = LMV_DENSE_LABEL_U8;
-  const int nw = NT / 64;
-  const size_t lds = (K <= DN_KREG ? (size_t)nw * (3 * K + 3) : (size_t)2 * K * NT + K + (size_t)nw * 3) * sizeof(float) + (a.conf ? (size_t)K * K * sizeof(int) : 0);
   hipStream_t st = (hipStream_t)stream;
-  DN_DISPATCH(dense_up_fwd_kernel, dim3(rows), dim3(NT), lds, st, a);
-  LMV_CHECK_LAUNCH("dense_up_loss_fwd");
+  DN_DISPATCH(dense_up_fwd_kernel, dim3(rows), dim3(NT), dn_lds_bytes(K, NT, a.conf != nullptr), st, a);
+  LMV_CHECK_LAUNCH(fn);
   if (!labels) return LMV_OK;
-  DenseFinArgs f;
-  f.ws = a.ws; f.alpha = alpha; f.stats = stats; f.meter = meter; f.rows = rows; f.K = K; f.avg_mode = avg_mode;
-  f.npix = (double)B * (double)H * (double)W; f.w_ce = w_ce; f.w_dice = w_dice; f.w_jac = w_jac; f.eps = eps;
-  hipLaunchKernelGGL(dense_finalize_kernel, dim3(1), dim3(256), 0, st, f);
-  LMV_CHECK_LAUNCH("dense_up_loss_fwd (finalize)");
-  return LMV_OK;
+  return dn_finalize(fn, a.ws, rows, K, (double)B * (double)H * (double)W, alpha, w_ce, w_dice, w_jac, eps, avg_mode, stats, meter, st);
 }
 
 extern "C" int lmv_dense_up_loss_bwd(const void* logits, int dtype, int64_t batch_stride, int64_t class_stride, int B, int K, int h, int w, int H, int W,
@@ -994,8 +983,7 @@ extern "C" int lmv_dense_up_loss_bwd(const void* logits, int dtype, int64_t batc
   const char* fn = "dense_up_loss_bwd";
   if (int rc = up_validate(fn, logits, dtype, batch_stride, class_stride, B, K, h, w, H, W, align_corners, labels, true, label_dtype, alpha, gamma, w_ce, w_dice,
                            w_jac, eps, avg_mode)) return rc;
-  if (!stats || !dlogits) LMV_FAIL(LMV_ERR_SHAPE, "%s: null stats / dlogits", fn);
-  if ((((uintptr_t)stats) & 3u) || (((uintptr_t)gout) & 3u) || (((uintptr_t)dlogits) & (dtype == LMV_F32 ? 3u : 1u))) LMV_FAIL(LMV_ERR_SHAPE, "%s: misaligned buffer", fn);
+  if (int rc = dn_check_bwd(fn, dtype, stats, gout, dlogits)) return rc;
   UpArgs a = up_args(logits, batch_stride, class_stride, B, K, h, w, H, W, align_corners, labels, ignore_index, alpha, gamma, w_ce, w_dice, w_jac);
   a.stats = stats; a.gout = gout; a.dlogits = dlogits;
   up_tile(h, H, &a.TH, &a.FBH);
@@ -1006,8 +994,11 @@ extern "C" int lmv_dense_up_loss_bwd(const void* logits, int dtype, int64_t batc
   const size_t lds = ((size_t)7 * a.FBH * a.FBW + (size_t)K * TP + 3 * (size_t)(a.FBH + a.FBW) + (size_t)a.TH * a.FBH + (size_t)a.TW * a.FBW + 32) * sizeof(float);
   const size_t lds_stage = lds + (size_t)K * (a.TH + 2) * (a.TW + 2) * sizeof(float);          // the logits tile too, where the default 64 KB of LDS hold it
   const dim3 grid((unsigned)((int64_t)B * a.tiles_y * a.tiles_x));
-  if (lds_stage <= 65536) UP_DISPATCH_BWD(true, grid, dim3(256), lds_stage, (hipStream_t)stream, a);
-  else UP_DISPATCH_BWD(false, grid, dim3(256), lds, (hipStream_t)stream, a);
-  LMV_CHECK_LAUNCH("dense_up_loss_bwd");
+  const bool stage = lds_stage <= 65536;
+  dn_for_types(dtype, label_dtype, [&](auto t, auto l) {
+    if (stage) hipLaunchKernelGGL((dense_up_bwd_kernel<decltype(t), decltype(l), true>), grid, dim3(256), lds_stage, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL((dense_up_bwd_kernel<decltype(t), decltype(l), false>), grid, dim3(256), lds, (hipStream_t)stream, a);
+  });
+  LMV_CHECK_LAUNCH(fn);
   return LMV_OK;
 }

@@ -58,6 +58,21 @@ def _size_differs(logits: Tensor, target: Tensor) -> bool:
     return logits.dim() == 4 and target.dim() in (3, 4) and tuple(target.shape[-2:]) != tuple(logits.shape[-2:])
 
 
+def _dense_fwd(logits: Tensor, target: Tensor, up: bool, align_corners: bool, *terms, **buffers) -> Tensor:
+    """THE forward call: ``up`` picks lmv_dense_up_loss_fwd (interpolation inside the pass) over lmv_dense_loss_fwd; ``terms``: ``ignore_index, alpha, gamma, ce, dice,
+    jaccard, eps, avg`` from the front, ``buffers``: the ops' ``workspace, stats, pred, conf, meter``"""
+    if up:
+        return ops.dense_up_loss_fwd(logits, target, align_corners, *terms, **buffers)
+    return ops.dense_loss_fwd(logits, target, *terms, **buffers)
+
+
+def _dense_bwd(logits: Tensor, target: Tensor, stats: Tensor, up: bool, align_corners: bool, *terms, **buffers) -> Tensor:
+    """THE backward call, with the ``up``, ``align_corners`` and ``terms`` of the forward call that left ``stats``"""
+    if up:
+        return ops.dense_up_loss_bwd(logits, target, stats, align_corners, *terms, **buffers)
+    return ops.dense_loss_bwd(logits, target, stats, *terms, **buffers)
+
+
 class _DenseLossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits: Tensor, target: Tensor, crit: "DenseLoss", meter: Optional["SegMeter"]):
@@ -67,32 +82,22 @@ class _DenseLossFn(torch.autograd.Function):
         if meter is not None:
             if logits.dim() == 4:
                 meter._check(logits.shape[1], crit.ignore_index)
-            pred, conf, state = meter._outputs(logits, tuple(target.shape[-2:]) if up else None)
-        if up:
-            stats = ops.dense_up_loss_fwd(logits, target, crit.align_corners, crit.ignore_index, alpha, crit.gamma, crit.ce, crit.dice, crit.jaccard, crit.eps,
-                                          crit.avg, pred=pred, conf=conf, meter=state)
-        else:
-            stats = ops.dense_loss_fwd(logits, target, crit.ignore_index, alpha, crit.gamma, crit.ce, crit.dice, crit.jaccard, crit.eps, crit.avg,
-                                       pred=pred, conf=conf, meter=state)
+            pred, conf, state = meter._outputs(logits, tuple(target.shape[-2:]) if up else None)[:3]          # (stats goes to the backward pass: a tensor of this call's own)
+        terms = (crit.ignore_index, alpha, crit.gamma, crit.ce, crit.dice, crit.jaccard, crit.eps, crit.avg)
+        stats = _dense_fwd(logits, target, up, crit.align_corners, *terms, pred=pred, conf=conf, meter=state)
         if meter is not None:
             meter.pred = pred
         ctx.save_for_backward(logits, target, stats)
-        ctx.crit, ctx.alpha, ctx.up = crit, alpha, up
+        ctx.up, ctx.align_corners, ctx.terms = up, crit.align_corners, terms
         crit.last = dict(ce=stats[1], dice=stats[2], jaccard=stats[3], n_valid=stats[4])
         return stats[0]
 
     @staticmethod
     def backward(ctx, grad_out: Tensor):
         logits, target, stats = ctx.saved_tensors
-        crit = ctx.crit
         if grad_out.dtype != torch.float32:
             grad_out = grad_out.float()
-        if ctx.up:
-            dl = ops.dense_up_loss_bwd(logits, target, stats, crit.align_corners, crit.ignore_index, ctx.alpha, crit.gamma, crit.ce, crit.dice, crit.jaccard, crit.eps,
-                                       crit.avg, gout=grad_out)
-        else:
-            dl = ops.dense_loss_bwd(logits, target, stats, crit.ignore_index, ctx.alpha, crit.gamma, crit.ce, crit.dice, crit.jaccard, crit.eps, crit.avg, gout=grad_out)
-        return dl, None, None, None
+        return _dense_bwd(logits, target, stats, ctx.up, ctx.align_corners, *ctx.terms, gout=grad_out), None, None, None
 
 
 class DenseLoss(nn.Module):
@@ -261,7 +266,7 @@ class SegMeter:
         self.conf: Optional[Tensor] = None
         self.loss: Optional[Tensor] = None
         self.pred: Optional[Tensor] = None
-        self._buffers: Dict[tuple, Tuple[Tensor, Tensor, Tensor]] = {}
+        self._buffers: Dict[tuple, Tuple[Tensor, Tensor, Tensor]] = {}          # (B, h, w, H, W, device) -> (pred, stats, workspace)
 
     @property
     def state(self) -> Tuple[Optional[Tensor], Optional[Tensor]]:
@@ -273,9 +278,9 @@ class SegMeter:
         if ignore_index != self.ignore_index:
             raise ValueError(f"SegMeter: the loss ignores label {ignore_index}, the meter {self.ignore_index} -- one pass serves both, they must agree")
 
-    def _outputs(self, logits: Tensor, size: Optional[Tuple[int, int]] = None) -> Tuple[Tensor, Tensor, Tensor]:
-        """(pred, conf, loss state) for a batch of this shape; allocated on first use, never under capture.  ``size``: the label map's (H, W) when the logits are
-        upsampled to it inside the pass"""
+    def _outputs(self, logits: Tensor, size: Optional[Tuple[int, int]] = None) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+        """(pred, conf, loss state, stats, workspace) for a batch of this shape; allocated on first use, never under capture.  ``size``: the label map's (H, W) when
+        the logits are upsampled to it inside the pass"""
         if logits.dim() != 4:
             raise ValueError(f"SegMeter: [B, K, H, W] logits expected, got {tuple(logits.shape)}")
         if not logits.is_cuda:
@@ -297,19 +302,14 @@ class SegMeter:
             buf = (torch.empty((B, H, W), device=dev, dtype=torch.uint8), torch.empty((ops.dense_stats_floats(K),), device=dev, dtype=torch.float32),
                    ops.dense_workspace(B, K, H * W, dev) if size is None else ops.dense_up_workspace(B, K, H, W, dev))
             self._buffers[key] = buf
-        return buf[0], self.conf, self.loss
+        return buf[0], self.conf, self.loss, buf[1], buf[2]
 
     def update(self, logits: Tensor, target: Tensor) -> None:
         if logits.dim() == 4:
             self._check(logits.shape[1], self.ignore_index)
         size = tuple(target.shape[-2:]) if self.upsample and _size_differs(logits, target) else None
-        pred, conf, loss = self._outputs(logits, size)
-        B, _, h, w = logits.shape
-        _, stats, ws = self._buffers[(B, h, w) + ((h, w) if size is None else (int(size[0]), int(size[1]))) + (logits.device,)]
-        if size is None:
-            ops.dense_loss_fwd(logits.detach(), target, self.ignore_index, workspace=ws, stats=stats, pred=pred, conf=conf, meter=loss)
-        else:
-            ops.dense_up_loss_fwd(logits.detach(), target, self.align_corners, self.ignore_index, workspace=ws, stats=stats, pred=pred, conf=conf, meter=loss)
+        pred, conf, loss, stats, ws = self._outputs(logits, size)
+        _dense_fwd(logits.detach(), target, size is not None, self.align_corners, self.ignore_index, workspace=ws, stats=stats, pred=pred, conf=conf, meter=loss)
         self.pred = pred
 
     def merge(self, states: Iterable[Tuple[Tensor, Tensor]]) -> "SegMeter":

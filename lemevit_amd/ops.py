@@ -1028,30 +1028,60 @@ def dense_workspace(B: int, K: int, HW: int, device) -> Tensor:
     return torch.empty((n,), device=device, dtype=torch.uint8)
 
 
-def _dense_args(fn: str, logits: Tensor, labels: Tensor, ignore_index, alpha, gamma, w_ce, w_dice, w_jac, eps, avg):
+def _dense_args(fn: str, logits: Tensor, labels: Optional[Tensor], size, align_corners, ignore_index, alpha, gamma, w_ce, w_dice, w_jac, eps, avg):
+    """The argument checks of the four dense ops and the leading arguments of their ABI calls.  ``align_corners is None``: the native form (labels [B, H, W],
+    [B, 1, H, W] or [B, H W] of the logits' own size; 17 values).  Otherwise the upsampling form (21 values): ``(H, W)`` comes from the labels, or from ``size``
+    when there are none (prediction only).  Returns ``(head, B, K, H, W)``.  The order of refusals is each form's own (the native form looks at its labels after
+    the logits' layout, the upsampling form before the sizes, which it takes from them), but for one point: both ask about the device after sizes and layout."""
+    up = align_corners is not None
     if logits.dim() != 4:
-        raise ValueError(f"{fn}: [B, K, H, W] logits expected, got {tuple(logits.shape)}")
-    if not logits.is_cuda or not labels.is_cuda:
-        raise RuntimeError("lemevit_amd: tensors must be on the GPU (no CPU fallback exists)")
-    code = dtype_code(logits)
-    B, K, H, W = logits.shape
-    HW = H * W
+        raise ValueError(f"{fn}: [B, K, {'h, w' if up else 'H, W'}] logits expected, got {tuple(logits.shape)}")
+    B, K, h, w = logits.shape
     if not 2 <= K <= _lib.DENSE_MAX_CLASSES:
         raise ValueError(f"{fn}: K = {K} classes outside 2 .. {_lib.DENSE_MAX_CLASSES}")
-    if B < 1 or HW < 1 or B * HW >= 1 << 31:
-        raise ValueError(f"{fn}: bad shape {tuple(logits.shape)} (B >= 1, H W >= 1, B H W < 2^31)")
-    if (W > 1 and logits.stride(3) != 1) or (H > 1 and logits.stride(2) != W):
+
+    def check_labels():
+        if labels.dtype not in (torch.int64, torch.uint8):
+            raise TypeError(f"{fn}: labels must be int64 or uint8, got {labels.dtype}")
+        if up:
+            fits, shapes = labels.dim() in (3, 4) and labels.shape[0] == B and (labels.dim() == 3 or labels.shape[1] == 1), "[B, H, W] or [B, 1, H, W]"
+        else:
+            fits, shapes = tuple(labels.shape) in ((B, h, w), (B, 1, h, w), (B, h * w)), "[B, H, W], [B, 1, H, W] or [B, H W]"
+        # (one tensor on the CPU is the device refusal's, below, in the native form; the upsampling form has always named it here)
+        if not fits or (labels.device != logits.device and (up or (labels.is_cuda and logits.is_cuda))):
+            raise ValueError(f"{fn}: labels must be {shapes} on the logits' device, got {tuple(labels.shape)}")
+        if not labels.is_contiguous():
+            raise ValueError(f"{fn}: the label map must be contiguous")
+
+    H, W = h, w
+    if not up:
+        if labels is None:
+            raise ValueError(f"{fn}: a label map is required")
+        if B < 1 or h * w < 1 or B * h * w >= 1 << 31:
+            raise ValueError(f"{fn}: bad shape {tuple(logits.shape)} (B >= 1, H W >= 1, B H W < 2^31)")
+    else:
+        if labels is not None:
+            check_labels()
+            H, W = int(labels.shape[-2]), int(labels.shape[-1])
+            if size is not None and (int(size[0]), int(size[1])) != (H, W):
+                raise ValueError(f"{fn}: size = {tuple(size)} is not the label map's {(H, W)}")
+        elif size is None:
+            raise ValueError(f"{fn}: without labels the output size must be given")
+        else:
+            H, W = int(size[0]), int(size[1])
+        if B < 1 or h < 1 or w < 1 or H < h or W < w or B * H * W >= 1 << 31:
+            raise ValueError(f"{fn}: bad sizes {tuple(logits.shape)} -> {(H, W)} (B >= 1, h >= 1, w >= 1, H >= h, W >= w: upsampling only, B H W < 2^31)")
+    if (w > 1 and logits.stride(3) != 1) or (h > 1 and logits.stride(2) != w):
         raise ValueError(f"{fn}: the logits must have unit pixel stride (NCHW planes; channels-last logits are not supported)")
     sc = logits.stride(1)
-    sb = logits.stride(0) if B > 1 else (K - 1) * sc + HW
-    if sc < HW or sb < (K - 1) * sc + HW:
+    sb = logits.stride(0) if B > 1 else (K - 1) * sc + h * w
+    if sc < h * w or sb < (K - 1) * sc + h * w:
         raise ValueError(f"{fn}: overlapping class planes or images (strides {logits.stride()})")
-    if labels.dtype not in (torch.int64, torch.uint8):
-        raise TypeError(f"{fn}: labels must be int64 or uint8, got {labels.dtype}")
-    if tuple(labels.shape) not in ((B, H, W), (B, 1, H, W), (B, HW)) or labels.device != logits.device:
-        raise ValueError(f"{fn}: labels must be [B, H, W], [B, 1, H, W] or [B, H W] on the logits' device, got {tuple(labels.shape)}")
-    if not labels.is_contiguous():
-        raise ValueError(f"{fn}: the label map must be contiguous")
+    if not up:
+        check_labels()
+    if not logits.is_cuda or (labels is not None and not labels.is_cuda):
+        raise RuntimeError("lemevit_amd: tensors must be on the GPU (no CPU fallback exists)")
+    code = dtype_code(logits)
     if alpha is not None and (alpha.dtype != torch.float32 or tuple(alpha.shape) != (K,) or alpha.device != logits.device or not alpha.is_contiguous()):
         raise TypeError(f"{fn}: alpha must be a contiguous float32 vector [{K}] on the logits' device")
     if not (float(w_ce) >= 0.0 and float(w_dice) >= 0.0 and float(w_jac) >= 0.0):
@@ -1062,10 +1092,47 @@ def _dense_args(fn: str, logits: Tensor, labels: Tensor, ignore_index, alpha, ga
         raise ValueError(f"{fn}: eps = {eps} <= 0")
     if avg not in DENSE_AVG:
         raise ValueError(f"{fn}: avg must be one of {sorted(DENSE_AVG)}, got {avg!r}")
-    ign = -1 if ignore_index is None else int(ignore_index)
-    head = (logits.data_ptr(), code, sb, sc, B, K, HW, labels.data_ptr(), _lib.DENSE_LABEL_I64 if labels.dtype == torch.int64 else _lib.DENSE_LABEL_U8, ign,
-            None if alpha is None else alpha.data_ptr(), float(gamma), float(w_ce), float(w_dice), float(w_jac), float(eps), DENSE_AVG[avg])
-    return head, B, K, HW
+    geometry = (h, w, H, W, 1 if align_corners else 0) if up else (h * w,)
+    ldt = _lib.DENSE_LABEL_U8 if labels is None or labels.dtype == torch.uint8 else _lib.DENSE_LABEL_I64
+    head = (logits.data_ptr(), code, sb, sc, B, K) + geometry + (_ptr(labels), ldt, -1 if ignore_index is None else int(ignore_index), _ptr(alpha), float(gamma),
+                                                                 float(w_ce), float(w_dice), float(w_jac), float(eps), DENSE_AVG[avg])
+    return head, B, K, H, W
+
+
+def _dense_fwd_buffers(fn: str, sizer: str, dev, B: int, K: int, npix: int, need: int, workspace, stats, pred, conf, meter):
+    """The buffers of a forward call over ``B`` maps of ``npix`` pixels: checks ``pred``, ``conf`` and ``meter``, checks or allocates ``workspace`` (``need`` bytes)
+    and ``stats``, and returns those two.  ``need = 0``: prediction only, ``pred`` is all there is"""
+    if pred is not None and (pred.dtype != torch.uint8 or pred.numel() != B * npix or pred.device != dev or not pred.is_contiguous()):
+        raise TypeError(f"{fn}: pred must be a contiguous uint8 tensor of {B} x {npix} entries on the logits' device")
+    if not need:
+        return None, None
+    if workspace is None:
+        workspace = _workspace(need, dev)
+    elif workspace.device != dev or not workspace.is_contiguous() or workspace.numel() * workspace.element_size() < need:
+        raise ValueError(f"{fn}: the workspace must hold {need} bytes on the logits' device (ops.{sizer})")
+    if stats is None:
+        stats = torch.empty((dense_stats_floats(K),), device=dev, dtype=torch.float32)
+    elif stats.dtype != torch.float32 or tuple(stats.shape) != (dense_stats_floats(K),) or stats.device != dev or not stats.is_contiguous():
+        raise TypeError(f"{fn}: stats must be a contiguous float32 vector [{dense_stats_floats(K)}] on the logits' device")
+    if conf is not None and (conf.dtype != torch.int64 or tuple(conf.shape) != (K, K) or conf.device != dev or not conf.is_contiguous()):
+        raise TypeError(f"{fn}: conf must be a contiguous int64 matrix [{K}, {K}] on the logits' device")
+    if meter is not None and (meter.dtype != torch.float64 or tuple(meter.shape) != (2,) or meter.device != dev):
+        raise TypeError(f"{fn}: meter must be a float64 vector [2] on the logits' device")
+    return workspace, stats
+
+
+def _dense_bwd_buffers(fn: str, logits: Tensor, K: int, stats, gout, out) -> Tensor:
+    """The buffers of a backward call: checks ``stats`` and ``gout``, checks or allocates ``out`` and returns it"""
+    dev = logits.device
+    if stats.dtype != torch.float32 or tuple(stats.shape) != (dense_stats_floats(K),) or stats.device != dev or not stats.is_contiguous():
+        raise TypeError(f"{fn}: stats must be a contiguous float32 vector [{dense_stats_floats(K)}] on the logits' device")
+    if gout is not None and (gout.dtype != torch.float32 or gout.numel() != 1 or gout.device != dev):
+        raise TypeError(f"{fn}: gout must be a float32 scalar tensor on the logits' device")
+    if out is None:
+        out = torch.empty(tuple(logits.shape), device=dev, dtype=logits.dtype)
+    elif out.dtype != logits.dtype or tuple(out.shape) != tuple(logits.shape) or out.device != dev or not out.is_contiguous():
+        raise TypeError(f"{fn}: out must be a contiguous tensor of the logits' shape, dtype and device")
+    return out
 
 
 def dense_loss_fwd(logits: Tensor, labels: Tensor, ignore_index: Optional[int] = None, alpha: Optional[Tensor] = None, gamma: float = 0.0, w_ce: float = 1.0,
@@ -1077,23 +1144,8 @@ def dense_loss_fwd(logits: Tensor, labels: Tensor, ignore_index: Optional[int] =
     outputs, written by the same pass: ``pred`` uint8 [B, H W] (the argmax of every pixel), ``conf`` int64 [K, K] (``conf[y, pred] += 1``, persistent) and ``meter``
     float64 [2] (``+= sum -log p_y, n_valid``, persistent).  ``workspace`` (``dense_workspace``) and ``stats``: caller-supplied buffers, so that a captured call
     allocates nothing; None: allocated here.  Deterministic: no floating-point atomics."""
-    head, B, K, HW = _dense_args("dense_loss_fwd", logits, labels, ignore_index, alpha, gamma, w_ce, w_dice, w_jac, eps, avg)
-    dev = logits.device
-    need = lib.lmv_dense_loss_workspace_bytes(B, K, HW)
-    if workspace is None:
-        workspace = _workspace(need, dev)
-    elif workspace.device != dev or not workspace.is_contiguous() or workspace.numel() * workspace.element_size() < need:
-        raise ValueError(f"dense_loss_fwd: the workspace must hold {need} bytes on the logits' device (ops.dense_workspace)")
-    if stats is None:
-        stats = torch.empty((dense_stats_floats(K),), device=dev, dtype=torch.float32)
-    elif stats.dtype != torch.float32 or tuple(stats.shape) != (dense_stats_floats(K),) or stats.device != dev or not stats.is_contiguous():
-        raise TypeError(f"dense_loss_fwd: stats must be a contiguous float32 vector [{dense_stats_floats(K)}] on the logits' device")
-    if pred is not None and (pred.dtype != torch.uint8 or pred.numel() != B * HW or pred.device != dev or not pred.is_contiguous()):
-        raise TypeError(f"dense_loss_fwd: pred must be a contiguous uint8 tensor of {B} x {HW} entries on the logits' device")
-    if conf is not None and (conf.dtype != torch.int64 or tuple(conf.shape) != (K, K) or conf.device != dev or not conf.is_contiguous()):
-        raise TypeError(f"dense_loss_fwd: conf must be a contiguous int64 matrix [{K}, {K}] on the logits' device")
-    if meter is not None and (meter.dtype != torch.float64 or tuple(meter.shape) != (2,) or meter.device != dev):
-        raise TypeError("dense_loss_fwd: meter must be a float64 vector [2] on the logits' device")
+    head, B, K, H, W = _dense_args("dense_loss_fwd", logits, labels, None, None, ignore_index, alpha, gamma, w_ce, w_dice, w_jac, eps, avg)
+    workspace, stats = _dense_fwd_buffers("dense_loss_fwd", "dense_workspace", logits.device, B, K, H * W, lib.lmv_dense_loss_workspace_bytes(B, K, H * W), workspace, stats, pred, conf, meter)
     check(lib.lmv_dense_loss_fwd(*head, workspace.data_ptr(), workspace.numel() * workspace.element_size(), stats.data_ptr(), _ptr(pred), _ptr(conf), _ptr(meter),
                                  _stream()), "lmv_dense_loss_fwd")
     return stats
@@ -1105,17 +1157,9 @@ def dense_loss_bwd(logits: Tensor, labels: Tensor, stats: Tensor, ignore_index: 
     """lmv_dense_loss_bwd (one launch): ``d loss / d logits`` times ``gout`` from the ``stats`` of the forward call with the same arguments; ``gout`` is a float32
     GPU scalar read through its pointer (None: 1).  Returns ``dlogits``, contiguous [B, K, H, W] in the logits dtype, every element written once (``out``: a buffer
     to write instead of a new one); ignored pixels get exact zeros."""
-    head, B, K, HW = _dense_args("dense_loss_bwd", logits, labels, ignore_index, alpha, gamma, w_ce, w_dice, w_jac, eps, avg)
-    dev = logits.device
-    if stats.dtype != torch.float32 or tuple(stats.shape) != (dense_stats_floats(K),) or stats.device != dev or not stats.is_contiguous():
-        raise TypeError(f"dense_loss_bwd: stats must be a contiguous float32 vector [{dense_stats_floats(K)}] on the logits' device")
-    if gout is not None and (gout.dtype != torch.float32 or gout.numel() != 1 or gout.device != dev):
-        raise TypeError("dense_loss_bwd: gout must be a float32 scalar tensor on the logits' device")
-    if out is None:
-        out = torch.empty(tuple(logits.shape), device=dev, dtype=logits.dtype)
-    elif out.dtype != logits.dtype or tuple(out.shape) != tuple(logits.shape) or out.device != dev or not out.is_contiguous():
-        raise TypeError("dense_loss_bwd: out must be a contiguous tensor of the logits' shape, dtype and device")
-    check(lib.lmv_dense_loss_bwd(*head, stats.data_ptr(), None if gout is None else gout.data_ptr(), out.data_ptr(), _stream()), "lmv_dense_loss_bwd")
+    head, B, K, H, W = _dense_args("dense_loss_bwd", logits, labels, None, None, ignore_index, alpha, gamma, w_ce, w_dice, w_jac, eps, avg)
+    out = _dense_bwd_buffers("dense_loss_bwd", logits, K, stats, gout, out)
+    check(lib.lmv_dense_loss_bwd(*head, stats.data_ptr(), _ptr(gout), out.data_ptr(), _stream()), "lmv_dense_loss_bwd")
     return out
 
 
@@ -1127,55 +1171,6 @@ def dense_up_workspace(B: int, K: int, H: int, W: int, device) -> Tensor:
     return torch.empty((n,), device=device, dtype=torch.uint8)
 
 
-def _dense_up_args(fn: str, logits: Tensor, labels: Optional[Tensor], size, align_corners, ignore_index, alpha, gamma, w_ce, w_dice, w_jac, eps, avg):
-    """The checks of ``_dense_args`` for low-resolution logits; ``(H, W)`` comes from the labels, or from ``size`` when there are none (prediction only)."""
-    if logits.dim() != 4:
-        raise ValueError(f"{fn}: [B, K, h, w] logits expected, got {tuple(logits.shape)}")
-    B, K, h, w = logits.shape
-    if not 2 <= K <= _lib.DENSE_MAX_CLASSES:
-        raise ValueError(f"{fn}: K = {K} classes outside 2 .. {_lib.DENSE_MAX_CLASSES}")
-    if labels is not None:
-        if labels.dtype not in (torch.int64, torch.uint8):
-            raise TypeError(f"{fn}: labels must be int64 or uint8, got {labels.dtype}")
-        if labels.dim() not in (3, 4) or labels.shape[0] != B or (labels.dim() == 4 and labels.shape[1] != 1) or labels.device != logits.device:
-            raise ValueError(f"{fn}: labels must be [B, H, W] or [B, 1, H, W] on the logits' device, got {tuple(labels.shape)}")
-        if not labels.is_contiguous():
-            raise ValueError(f"{fn}: the label map must be contiguous")
-        H, W = int(labels.shape[-2]), int(labels.shape[-1])
-        if size is not None and (int(size[0]), int(size[1])) != (H, W):
-            raise ValueError(f"{fn}: size = {tuple(size)} is not the label map's {(H, W)}")
-    else:
-        if size is None:
-            raise ValueError(f"{fn}: without labels the output size must be given")
-        H, W = int(size[0]), int(size[1])
-    if B < 1 or h < 1 or w < 1 or H < h or W < w or B * H * W >= 1 << 31:
-        raise ValueError(f"{fn}: bad sizes {tuple(logits.shape)} -> {(H, W)} (B >= 1, h >= 1, w >= 1, H >= h, W >= w: upsampling only, B H W < 2^31)")
-    if (w > 1 and logits.stride(3) != 1) or (h > 1 and logits.stride(2) != w):
-        raise ValueError(f"{fn}: the logits must have unit pixel stride (NCHW planes; channels-last logits are not supported)")
-    sc = logits.stride(1)
-    sb = logits.stride(0) if B > 1 else (K - 1) * sc + h * w
-    if sc < h * w or sb < (K - 1) * sc + h * w:
-        raise ValueError(f"{fn}: overlapping class planes or images (strides {logits.stride()})")
-    if not logits.is_cuda or (labels is not None and not labels.is_cuda):          # (after the sizes and the layout: those refusals need no device)
-        raise RuntimeError("lemevit_amd: tensors must be on the GPU (no CPU fallback exists)")
-    code = dtype_code(logits)
-    if alpha is not None and (alpha.dtype != torch.float32 or tuple(alpha.shape) != (K,) or alpha.device != logits.device or not alpha.is_contiguous()):
-        raise TypeError(f"{fn}: alpha must be a contiguous float32 vector [{K}] on the logits' device")
-    if not (float(w_ce) >= 0.0 and float(w_dice) >= 0.0 and float(w_jac) >= 0.0):
-        raise ValueError(f"{fn}: negative loss weight ({w_ce}, {w_dice}, {w_jac})")
-    if not float(gamma) >= 0.0:
-        raise ValueError(f"{fn}: gamma = {gamma} < 0")
-    if not float(eps) > 0.0:
-        raise ValueError(f"{fn}: eps = {eps} <= 0")
-    if avg not in DENSE_AVG:
-        raise ValueError(f"{fn}: avg must be one of {sorted(DENSE_AVG)}, got {avg!r}")
-    ign = -1 if ignore_index is None else int(ignore_index)
-    ldt = _lib.DENSE_LABEL_U8 if labels is None or labels.dtype == torch.uint8 else _lib.DENSE_LABEL_I64
-    head = (logits.data_ptr(), code, sb, sc, B, K, h, w, H, W, 1 if align_corners else 0, _ptr(labels), ldt, ign,
-            None if alpha is None else alpha.data_ptr(), float(gamma), float(w_ce), float(w_dice), float(w_jac), float(eps), DENSE_AVG[avg])
-    return head, B, K, H, W
-
-
 def dense_up_loss_fwd(logits: Tensor, labels: Optional[Tensor], align_corners: bool = False, ignore_index: Optional[int] = None, alpha: Optional[Tensor] = None,
                       gamma: float = 0.0, w_ce: float = 1.0, w_dice: float = 0.0, w_jac: float = 0.0, eps: float = 1e-7, avg: str = "valid",
                       workspace: Optional[Tensor] = None, stats: Optional[Tensor] = None, pred: Optional[Tensor] = None, conf: Optional[Tensor] = None,
@@ -1184,30 +1179,15 @@ def dense_up_loss_fwd(logits: Tensor, labels: Optional[Tensor], align_corners: b
     ``logits`` [B, K, h, w], ``labels`` [B, H, W] / [B, 1, H, W] with H >= h, W >= w.  The other arguments, ``stats`` and the optional outputs are those of
     ``dense_loss_fwd``; ``pred`` has the LABEL map's resolution, ``workspace`` comes from ``dense_up_workspace``.  ``labels=None`` with ``pred`` and ``size=(H, W)``
     is prediction only (one launch, returns None)."""
-    head, B, K, H, W = _dense_up_args("dense_up_loss_fwd", logits, labels, size, align_corners, ignore_index, alpha, gamma, w_ce, w_dice, w_jac, eps, avg)
-    dev = logits.device
-    if pred is not None and (pred.dtype != torch.uint8 or pred.numel() != B * H * W or pred.device != dev or not pred.is_contiguous()):
-        raise TypeError(f"dense_up_loss_fwd: pred must be a contiguous uint8 tensor of {B} x {H * W} entries on the logits' device")
+    head, B, K, H, W = _dense_args("dense_up_loss_fwd", logits, labels, size, bool(align_corners), ignore_index, alpha, gamma, w_ce, w_dice, w_jac, eps, avg)
+    need = 0 if labels is None else lib.lmv_dense_up_loss_workspace_bytes(B, K, H, W)          # no labels: prediction only, one launch, returns None
+    workspace, stats = _dense_fwd_buffers("dense_up_loss_fwd", "dense_up_workspace", logits.device, B, K, H * W, need, workspace, stats, pred, conf, meter)
     if labels is None:
         if pred is None:
             raise ValueError("dense_up_loss_fwd: neither labels nor pred: nothing to compute")
-        check(lib.lmv_dense_up_loss_fwd(*head, None, 0, None, pred.data_ptr(), None, None, _stream()), "lmv_dense_up_loss_fwd")
-        return None
-    need = lib.lmv_dense_up_loss_workspace_bytes(B, K, H, W)
-    if workspace is None:
-        workspace = _workspace(need, dev)
-    elif workspace.device != dev or not workspace.is_contiguous() or workspace.numel() * workspace.element_size() < need:
-        raise ValueError(f"dense_up_loss_fwd: the workspace must hold {need} bytes on the logits' device (ops.dense_up_workspace)")
-    if stats is None:
-        stats = torch.empty((dense_stats_floats(K),), device=dev, dtype=torch.float32)
-    elif stats.dtype != torch.float32 or tuple(stats.shape) != (dense_stats_floats(K),) or stats.device != dev or not stats.is_contiguous():
-        raise TypeError(f"dense_up_loss_fwd: stats must be a contiguous float32 vector [{dense_stats_floats(K)}] on the logits' device")
-    if conf is not None and (conf.dtype != torch.int64 or tuple(conf.shape) != (K, K) or conf.device != dev or not conf.is_contiguous()):
-        raise TypeError(f"dense_up_loss_fwd: conf must be a contiguous int64 matrix [{K}, {K}] on the logits' device")
-    if meter is not None and (meter.dtype != torch.float64 or tuple(meter.shape) != (2,) or meter.device != dev):
-        raise TypeError("dense_up_loss_fwd: meter must be a float64 vector [2] on the logits' device")
-    check(lib.lmv_dense_up_loss_fwd(*head, workspace.data_ptr(), workspace.numel() * workspace.element_size(), stats.data_ptr(), _ptr(pred), _ptr(conf), _ptr(meter),
-                                    _stream()), "lmv_dense_up_loss_fwd")
+        conf = meter = None
+    check(lib.lmv_dense_up_loss_fwd(*head, _ptr(workspace), workspace.numel() * workspace.element_size() if need else 0, _ptr(stats), _ptr(pred), _ptr(conf),
+                                    _ptr(meter), _stream()), "lmv_dense_up_loss_fwd")
     return stats
 
 
@@ -1218,17 +1198,9 @@ def dense_up_loss_bwd(logits: Tensor, labels: Tensor, stats: Tensor, align_corne
     the high-resolution gradient, which is never stored.  ``stats`` from ``dense_up_loss_fwd`` with the same arguments; ``gout`` and ``out`` as in ``dense_loss_bwd``."""
     if labels is None:
         raise ValueError("dense_up_loss_bwd: a label map is required")
-    head, B, K, H, W = _dense_up_args("dense_up_loss_bwd", logits, labels, None, align_corners, ignore_index, alpha, gamma, w_ce, w_dice, w_jac, eps, avg)
-    dev = logits.device
-    if stats.dtype != torch.float32 or tuple(stats.shape) != (dense_stats_floats(K),) or stats.device != dev or not stats.is_contiguous():
-        raise TypeError(f"dense_up_loss_bwd: stats must be a contiguous float32 vector [{dense_stats_floats(K)}] on the logits' device")
-    if gout is not None and (gout.dtype != torch.float32 or gout.numel() != 1 or gout.device != dev):
-        raise TypeError("dense_up_loss_bwd: gout must be a float32 scalar tensor on the logits' device")
-    if out is None:
-        out = torch.empty(tuple(logits.shape), device=dev, dtype=logits.dtype)
-    elif out.dtype != logits.dtype or tuple(out.shape) != tuple(logits.shape) or out.device != dev or not out.is_contiguous():
-        raise TypeError("dense_up_loss_bwd: out must be a contiguous tensor of the logits' shape, dtype and device")
-    check(lib.lmv_dense_up_loss_bwd(*head, stats.data_ptr(), None if gout is None else gout.data_ptr(), out.data_ptr(), _stream()), "lmv_dense_up_loss_bwd")
+    head, B, K, H, W = _dense_args("dense_up_loss_bwd", logits, labels, None, bool(align_corners), ignore_index, alpha, gamma, w_ce, w_dice, w_jac, eps, avg)
+    out = _dense_bwd_buffers("dense_up_loss_bwd", logits, K, stats, gout, out)
+    check(lib.lmv_dense_up_loss_bwd(*head, stats.data_ptr(), _ptr(gout), out.data_ptr(), _stream()), "lmv_dense_up_loss_bwd")
     return out
 
 

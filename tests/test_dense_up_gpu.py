@@ -316,3 +316,30 @@ def test_upsample_captured():
         assert torch.equal(sloss.detach().view(torch.int32), eloss.view(torch.int32)) and torch.equal(sx.grad.view(torch.int32), egrad.view(torch.int32))
     assert torch.equal(meter.conf, eager_meter.conf) and torch.equal(meter.loss.view(torch.int64), eager_meter.loss.view(torch.int64))
     assert int(meter.conf.sum()) == int(meter.loss[1]) > 0
+
+
+@pytest.mark.parametrize("shape", [(2, 3, 8, 8), (1, 7, 6, 12)], ids=["register-path", "generic-path"])
+def test_equal_size_up_forward_is_the_plain_forward(shape):
+    """At ``size == (h, w)``, ``align_corners=False`` and ``W % 4 == 0`` the upsampling forward IS the plain forward, bit for bit, in ``stats``, ``pred``, ``conf``
+    and ``meter``: both taps of either axis fall on the pixel itself with weight 1 and 0, so the interpolation returns the logit exactly; both kernels cut the
+    same chunks of 4 pixels into the same workgroup rows; and per pixel both go through the same code (csrc/dense.hip: DN_PIXEL on the register path, dn_pixel_tail,
+    dn_store_pred, dn_write_row) in the same order.  fp32 only (a bf16 chunk is 8 pixels in the plain kernel, 4 here: another partition of the sums) and the
+    forward only (the two backward passes form ``sum_k p_k g_k`` in different orders on purpose)."""
+    ops = Lm().ops
+    B, K, h, w = shape
+    assert w % 4 == 0
+    g = torch.Generator().manual_seed(K * 131 + h * 17 + w)
+    xd = (torch.randn(shape, generator=g) * 3).to(DEV)
+    y = torch.randint(0, K, (B, h, w), generator=g)
+    y[torch.rand((B, h, w), generator=g) < 0.1] = 255
+    yd = y.to(torch.uint8).to(DEV)
+    for mode, kw, _ in modes(K):
+        okw = op_kwargs(kw, K)
+        got = []
+        for fwd in (lambda **out: ops.dense_up_loss_fwd(xd, yd, False, size=(h, w), **okw, **out), lambda **out: ops.dense_loss_fwd(xd, yd, **okw, **out)):
+            out = dict(pred=torch.full((B, h * w), 77, dtype=torch.uint8, device=DEV), conf=torch.zeros((K, K), dtype=torch.int64, device=DEV),
+                       meter=torch.zeros(2, dtype=torch.float64, device=DEV))
+            got.append(dict(out, stats=fwd(**out)))
+        for name in ("stats", "pred", "conf", "meter"):
+            assert torch.equal(bits(got[0][name]), bits(got[1][name])), (mode, name)
+        assert int(got[0]["conf"].sum()) == int(got[0]["meter"][1]) > 0
