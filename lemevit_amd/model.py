@@ -140,132 +140,151 @@ def block_folds(kind: str, params: "Dict[str, Tensor]", dtype: torch.dtype):
     return attn, _ln_fold_cached(params["mlp.0.weight"], params.get("mlp.0.bias"), g2, b2, dtype)
 
 
-def _conv1_matrix(weight: Tensor, dtype: torch.dtype) -> Tensor:
-    """[Cout, Cin, 3, 3] stem weight -> the [Cout, KP] GEMM operand of ops.im2col3x3s2_c3 / _nchw (column ci * 9 + ky * 3 + kx: the weight's own order; KP = 9 Cin rounded up to
-    a multiple of 32, the columns behind 9 Cin zero; Cin == 3: [Cout, 32]), a derived operand."""
-    def build():
-        K = 9 * weight.shape[1]
-        m = torch.zeros(weight.shape[0], (K + 31) // 32 * 32, device=weight.device, dtype=dtype)
-        m[:, :K] = weight.detach().reshape(weight.shape[0], K)
-        return m
-    return derived(weight, ("conv1", dtype), (weight,), build)
+def _conv_geometry(Ci: int, cd: torch.dtype) -> Tuple[bool, int, int]:
+    """(image form?, KP, column layout) of Conv2d(Ci, Cout, 3, stride 2, padding 1) as a GEMM over [rows, KP] patches.
+    Image form (Ci not a multiple of 8: the first stem convolution on an image of 1 .. 32 channels): column ci * 9 + ky * 3 + kx, the weight's own order, KP = 9 Ci rounded up
+    to a multiple of 32 (Ci == 3: 32).  Map form (a channels-last feature map): column (ky * 3 + kx) * Ci + ci.  The columns behind 9 Ci are zero."""
+    if Ci % 8:
+        return True, (9 * Ci + 31) // 32 * 32, ops.FOLD_CI_TAP
+    return False, ((9 * Ci + 63) // 64 * 64 if cd == torch.bfloat16 else 9 * Ci), ops.FOLD_TAP_CI      # bf16: whole 64-deep k-steps (the GEMM's LDS-DMA path)
 
 
-class _StemConv1Fn(torch.autograd.Function):
-    """First convolution of the stem (models/lemevit.py:713: in_chans -> C/2 channels, 3x3, stride 2, padding 1) as im2col + the
-    block GEMM kernels: y[NHWC] = patches @ W^T + b, dW = dY^T @ patches; three channels take the 32-wide patch kernel, any other count
-    (1 .. 32, not a multiple of 8) ops.im2col3x3s2_nchw.  An image that requires grad gets dX from ONE ops.conv3x3s2_nchw_dx launch (no patch-gradient
-    matrix); one that does not costs nothing extra.  (MIOpen's implicit-GEMM kernel for the 27-deep reduction takes 455 us at B = 128; this is ~5x
-    faster, weight gradient included.)"""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias, cd, gelu=False):
-        """gelu=True (inference only, BatchNorm folded into the weights): the GELU behind the first stem BatchNorm rides the GEMM epilogue."""
-        B, Ci, H, W = x.shape
-        Ho, Wo, Co = (H + 1) // 2, (W + 1) // 2, weight.shape[0]
-        Wm = _conv1_matrix(weight, cd)
-        patches = ops.im2col3x3s2_c3(x, cd) if Ci == 3 else ops.im2col3x3s2_nchw(x, cd, Wm.shape[1])
-        y = torch.empty(B * Ho * Wo, Co, device=x.device, dtype=cd)
-        b32 = None if bias is None else compute_copy(bias, torch.float32)
-        ops.linear_fwd([Prob(patches, Wm, y, bias=b32)], Co, Wm.shape[1], ops.ACT_GELU if gelu else ops.ACT_NONE)
-        assert not (gelu and torch.is_grad_enabled() and weight.requires_grad), "the fused GELU epilogue has no backward"
-        if ctx.needs_input_grad[0]:
-            ctx.save_for_backward(patches, Wm, x)
-        else:
-            ctx.save_for_backward(patches)
-        ctx.meta = (weight.shape, weight.dtype, None if bias is None else bias.dtype)
-        return y.view(B, Ho, Wo, Co).permute(0, 3, 1, 2)            # NCHW-shaped, channels-last-strided: no copy
-
-    @staticmethod
-    def backward(ctx, dy):
-        patches = ctx.saved_tensors[0]
-        wshape, wdt, bdt = ctx.meta
-        Co, KP = wshape[0], patches.shape[1]
-        g = dy.permute(0, 2, 3, 1).contiguous().view(-1, Co)
-        if g.dtype != patches.dtype:
-            g = g.to(patches.dtype)
-        need_w, need_b = ctx.needs_input_grad[1], bdt is not None and ctx.needs_input_grad[2]
-        dw = db = None
-        if need_w or need_b:          # (a frozen convolution: no accumulators, no weight-gradient launch)
-            dwm = torch.zeros(Co, KP, device=g.device, dtype=torch.float32)
-            db = torch.zeros(Co, device=g.device, dtype=torch.float32)
-            ops.linear_dw([Prob(g, patches, dwm, bias_grad=db)], Co, KP)
-            dw = dwm[:, :9 * wshape[1]].reshape(wshape).to(wdt) if need_w else None
-            db = db.to(bdt) if need_b else None
-        dx = None
-        if ctx.needs_input_grad[0]:
-            _, Wm, x = ctx.saved_tensors
-            dx = ops.conv3x3s2_nchw_dx(g, Wm, like=x)
-        return dx, dw, db, None, None
+def _conv_matrix(w: Tensor, dtype: torch.dtype, KP: int, layout: int) -> Tensor:
+    """[Cout, Cin, 3, 3] weight -> the [Cout, KP] GEMM operand in the column order of _conv_geometry (what ops.im2col3x3s2_c3 / _nchw, respectively ops.im2col3x3s2_nhwc and
+    the implicit GEMM, gather)."""
+    Co, Ci = w.shape[0], w.shape[1]
+    m = torch.zeros(Co, KP, device=w.device, dtype=dtype)
+    m[:, :9 * Ci] = (w if layout == ops.FOLD_CI_TAP else w.permute(0, 2, 3, 1)).reshape(Co, 9 * Ci)
+    return m
 
 
-def _conv_matrix(weight: Tensor, dtype: torch.dtype, KP: int) -> Tensor:
-    """[Cout, Cin, 3, 3] weight -> the [Cout, KP] GEMM operand of ops.im2col3x3s2_nhwc: column (ky * 3 + kx) * Cin + ci, zero padding
-    behind 9 Cin.  A derived operand: that of an eval-mode conv + BatchNorm fold goes with the folded weight."""
-    def build():
-        Co, Ci = weight.shape[0], weight.shape[1]
-        m = torch.zeros(Co, KP, device=weight.device, dtype=dtype)
-        m[:, :9 * Ci] = weight.detach().permute(0, 2, 3, 1).reshape(Co, 9 * Ci)
-        return m
-    return derived(weight, ("conv", dtype, KP), (weight,), build)
+def _conv_operand(weight: Tensor, bias: Optional[Tensor], bn: Optional[tuple], infer: bool, cd: torch.dtype, KP: int, layout: int) -> Tuple[Tensor, Optional[Tensor]]:
+    """(Wm [Cout, KP] in cd, fp32 bias) that the convolution GEMM reads, a derived operand owned by the weight: the plain weight (fp32 or bf16 masters), or its fold with a
+    BatchNorm bn = (gamma, beta, running_mean, running_var, eps) that is a fixed affine map -- in inference (`infer`) by torch arithmetic (_fold_conv_bn), under autograd by
+    ops.conv_bn_fold (fp32 masters, _conv_bn_pairs; ONE launch, and ops.conv_bn_fold_bwd carries the gradients back).  The two folds round differently."""
+    if bn is None:
+        Wm = derived(weight, ("conv", cd, KP, layout), (weight,), lambda: _conv_matrix(weight, cd, KP, layout))
+        return Wm, None if bias is None else compute_copy(bias, torch.float32)
+    gamma, beta, mean, var, eps = bn
+    src = (weight, bias, gamma, beta, mean, var)
+    if infer:
+        def build():
+            w, _, b32 = _fold_conv_bn(weight, bias, gamma, beta, mean, var, eps, cd)
+            return _conv_matrix(w, cd, KP, layout), b32
+        return derived(weight, ("conv_bn", cd, KP, layout, eps), src, build)
+    return derived(weight, ("conv_bn_train", cd, KP, layout, eps), src, lambda: ops.conv_bn_fold(weight, bias, gamma, beta, mean, var, eps, cd, KP, layout)[:2])
+
+
+def _dy_rows(dy: Tensor, dtype: torch.dtype) -> Tensor:
+    """The gradient of an NCHW-shaped map as NHWC rows [B H W, C] in `dtype` (no copy for a channels-last gradient of that type)."""
+    g = dy.permute(0, 2, 3, 1).contiguous().view(-1, dy.shape[1])
+    return g if g.dtype == dtype else g.to(dtype)
+
+
+def _rows_nchw(rows: Tensor, B: int, H: int, W: int) -> Tensor:
+    return rows.view(B, H, W, -1).permute(0, 3, 1, 2)            # NCHW-shaped, channels-last-strided: no copy
 
 
 class _Conv3x3s2Fn(torch.autograd.Function):
-    """Conv2d(Cin, Cout, kernel 3, stride 2, padding 1) on a channels-last map as im2col + the block GEMM kernels (SURVEY section 8,
-    row f1; models/lemevit.py:701-703, :714-717): y = patches @ Wm^T + b, dW = dY^T @ patches, dX = col2im(dY @ Wm).  No MIOpen
-    solver search, no run-to-run differences in the gradients (the library's weight-gradient kernels are not reproducible)."""
+    """Conv2d(Cin, Cout, kernel 3, stride 2, padding 1) of the stem and the stage transitions (models/lemevit.py:701-703, :713-717) as a gather + the
+    block GEMM kernels: y[NHWC] = patches @ Wm^T + b, dW = dY^T @ patches.  No MIOpen solver search, no run-to-run differences in the gradients (the library's
+    weight-gradient kernels are not reproducible).  Geometry (_conv_geometry), chosen by Cin:
+    * image form: ops.im2col3x3s2_c3 (three channels: the 32-wide patch kernel) / _nchw write the patch matrix; an image that requires grad gets dX from ONE
+      ops.conv3x3s2_nchw_dx launch (no patch-gradient matrix), one that does not costs nothing extra.  (MIOpen's implicit-GEMM kernel for the 27-deep reduction takes 455 us
+      at B = 128; this is ~5x faster, weight gradient included.)
+    * map form: the implicit GEMM where ops.conv3x3s2_implicit_ok admits the NHWC map (round 6: the GEMM gathers the patch elements from the map -- no patch matrix is
+      written, read back, or kept for the backward pass), otherwise ops.im2col3x3s2_nhwc; dX = col2im(dY @ Wm).
+    Operand (_conv_operand): the plain weight, or its fold with a frozen BatchNorm (mean given):  y = act(conv(x; W s, (b - mu) s + beta)), s = gamma / sqrt(var + eps), so no
+    pass over the feature map is spent on the BatchNorm and no map is saved for it;  dW = dW' s, db = db' s, dgamma = r (sum_k dW'_k W_k + db' (b - mu)), dbeta = db' from the
+    folded gradients dW', db' of the weight-gradient GEMM (ops.conv_bn_fold_bwd, on the tensors the forward call was given).  gelu (image form, folded operand: the exact GELU
+    behind the first stem BatchNorm) rides the forward GEMM's epilogue; its backward recomputes the pre-activation from the saved patch rows (ops.linear_fwd(ACT_GELU_BWD)).
+    Kept for the backward pass: the gather only where a parameter gradient or the GELU recompute needs it, the operand only where dX or the GELU recompute does, the image only
+    for the image form's dX.  The weight-gradient GEMM runs only where a parameter requires grad, dX only where x does.  `form` names the path taken."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, cd):
+    def forward(ctx, x, weight, bias, cd, gamma=None, beta=None, mean=None, var=None, eps=None, gelu=False, infer=False):
         B, Ci, H, W = x.shape
-        Co = weight.shape[0]
-        xh = x.detach().permute(0, 2, 3, 1).to(cd).contiguous()            # NHWC; no copy for channels-last input of the right dtype
-        KP = (9 * Ci + 63) // 64 * 64 if cd == torch.bfloat16 else 9 * Ci  # bf16: whole 64-deep k-steps (the GEMM's LDS-DMA path)
-        Wm = _conv_matrix(weight, cd, KP)
-        Ho, Wo = (H + 1) // 2, (W + 1) // 2
-        b32 = None if bias is None else compute_copy(bias, torch.float32)
-        implicit = _CONV_IMPLICIT and ops.conv3x3s2_implicit_ok(xh, Co, KP)
-        if implicit:          # round 6: the GEMM gathers the patch elements from the map -- no patch matrix is written, read back, or kept for the backward pass
-            y = ops.conv3x3s2_fwd(xh, Wm, b32)
-            ctx.save_for_backward(xh, Wm)
+        Co, Ho, Wo = weight.shape[0], (H + 1) // 2, (W + 1) // 2
+        image, KP, layout = _conv_geometry(Ci, cd)
+        folded = mean is not None
+        need_x, need_p = ctx.needs_input_grad[0], any(ctx.needs_input_grad[1:6])
+        if gelu and not image:
+            raise NotImplementedError("lemevit_amd: the GELU epilogue is built for the image form of the convolution only")
+        Wm, b32 = _conv_operand(weight, bias, (gamma, beta, mean, var, eps) if folded else None, infer, cd, KP, layout)
+        if image:
+            ctx.form, gathered = "image", (ops.im2col3x3s2_c3(x, cd) if Ci == 3 else ops.im2col3x3s2_nchw(x, cd, KP))
         else:
-            patches = ops.im2col3x3s2_nhwc(xh, KP)
+            xh = x.detach().permute(0, 2, 3, 1).to(cd).contiguous()            # NHWC; no copy for channels-last input of the right dtype
+            ctx.form = "implicit" if _CONV_IMPLICIT and ops.conv3x3s2_implicit_ok(xh, Co, KP) else "patch"
+            gathered = xh if ctx.form == "implicit" else ops.im2col3x3s2_nhwc(xh, KP)
+        if ctx.form == "implicit":
+            y = ops.conv3x3s2_fwd(gathered, Wm, b32)
+        else:
             y = torch.empty(B * Ho * Wo, Co, device=x.device, dtype=cd)
-            ops.linear_fwd([Prob(patches, Wm, y, bias=b32)], Co, KP)
-            ctx.save_for_backward(patches, Wm)
-        ctx.meta = (x.shape, x.dtype, weight.shape, weight.dtype, None if bias is None else bias.dtype, implicit)
-        return y.view(B, Ho, Wo, Co).permute(0, 3, 1, 2)                    # NCHW-shaped, channels-last-strided: no copy
+            ops.linear_fwd([Prob(gathered, Wm, y, bias=b32)], Co, KP, ops.ACT_GELU if gelu else ops.ACT_NONE)
+        regelu = gelu and (need_x or need_p)          # the GELU backward wants the patch rows AND the operand
+        # kept, in this order: [gather] [Wm, b32] [image] [the fold's sources]
+        ctx.save_for_backward(*([gathered] if need_p or regelu else []), *([Wm, b32] if need_x or regelu else []), *([x] if need_x and image else []),
+                              *([weight, bias, gamma, mean, var] if need_p and folded else []))
+        ctx.meta = (tuple(x.shape), x.dtype, weight.shape, weight.dtype, None if bias is None else bias.dtype, image, KP, layout, folded, gelu, eps, cd)
+        return _rows_nchw(y, B, Ho, Wo)
 
     @staticmethod
     def backward(ctx, dy):
-        patches, Wm = ctx.saved_tensors
-        (B, Ci, H, W), xdt, wshape, wdt, bdt, implicit = ctx.meta
-        Co, KP = Wm.shape
-        g = dy.permute(0, 2, 3, 1).contiguous().view(-1, Co)
-        if g.dtype != patches.dtype:
-            g = g.to(patches.dtype)
-        need_w, need_b = ctx.needs_input_grad[1], bdt is not None and ctx.needs_input_grad[2]
-        dw = db = None
-        if need_w or need_b:          # (a frozen convolution: no accumulators, no weight-gradient launch)
+        (B, Ci, H, W), xdt, wshape, wdt, bdt, image, KP, layout, folded, gelu, eps, cd = ctx.meta
+        n = tuple(ctx.needs_input_grad) + (False, False)          # (apply(x, weight, bias, cd) without a BatchNorm: four inputs)
+        need_x, need = n[0], (n[1], n[2], n[4], n[5])
+        sv = list(ctx.saved_tensors)
+        gathered = sv.pop(0) if any(need) or gelu else None          # the patch matrix, or the NHWC map of the implicit form
+        Wm, b32 = (sv.pop(0), sv.pop(0)) if need_x or gelu else (None, None)
+        Co = wshape[0]
+        g = _dy_rows(dy, cd)
+        if gelu:          # dz = da * GELU'(z), z recomputed from the patch rows in the same launch
+            dz = torch.empty_like(g)
+            ops.linear_fwd([Prob(gathered, Wm, dz, bias=b32, aux=g)], Co, KP, ops.ACT_GELU_BWD)
+            g = dz
+        dx, grads = None, [None, None, None, None]
+        if any(need):          # (a frozen convolution: no accumulators, no weight-gradient launch)
             dwm = torch.zeros(Co, KP, device=g.device, dtype=torch.float32)
-            db = torch.zeros(Co, device=g.device, dtype=torch.float32)
-            if implicit:
-                ops.conv3x3s2_dw(g, patches, dwm, db)          # (`patches` is the NHWC map here)
+            dbf = torch.zeros(Co, device=g.device, dtype=torch.float32)
+            if ctx.form == "implicit":
+                ops.conv3x3s2_dw(g, gathered, dwm, dbf)
             else:
-                ops.linear_dw([Prob(g, patches, dwm, bias_grad=db)], Co, KP)
-            dw = dwm[:, :9 * Ci].reshape(Co, 3, 3, Ci).permute(0, 3, 1, 2).to(wdt) if need_w else None
-            db = db.to(bdt) if need_b else None
-        dx = None
-        if ctx.needs_input_grad[0]:
+                ops.linear_dw([Prob(g, gathered, dwm, bias_grad=dbf)], Co, KP)
+            if folded:
+                weight, bias, gamma, mean, var = sv[-5:]
+                grads = list(ops.conv_bn_fold_bwd(dwm, dbf, weight, bias, gamma, mean, var, eps, layout, [bool(n) for n in need]))
+            else:
+                dw = dwm[:, :9 * Ci]
+                dw = dw.reshape(wshape) if image else dw.reshape(Co, 3, 3, Ci).permute(0, 3, 1, 2)
+                grads[:2] = (dw.to(wdt) if need[0] else None), (dbf.to(bdt) if need[1] else None)
+        if need_x and image:
+            dx = ops.conv3x3s2_nchw_dx(g, Wm, like=sv[0])
+        elif need_x:
             dp = torch.empty(g.shape[0], KP, device=g.device, dtype=g.dtype)
             ops.linear_dx([Prob(g, Wm, dp)], Co, KP)
             dx = ops.col2im3x3s2_nhwc(dp, B, H, W, Ci).permute(0, 3, 1, 2).to(xdt)
-        return dx, dw, db, None
+        return (dx, grads[0], grads[1], None, grads[2], grads[3], None, None, None, None, None)
+
+
+def _conv3x3s2(x: Tensor, weight: Tensor, bias: Optional[Tensor], cd: torch.dtype, bn: Optional[tuple] = None, gelu: bool = False, infer: bool = False) -> Tensor:
+    """The 3 x 3 / stride-2 / padding-1 convolution of x [B, Cin, H, W] on the native kernels (_Conv3x3s2Fn) -> [B, Cout, Ho, Wo], channels-last-strided, in cd.
+    bn = (gamma, beta, running_mean, running_var, eps): a frozen BatchNorm folded into the operand (`infer`: the no-grad inference fold); gelu: the exact GELU behind it too."""
+    if (infer or (gelu and bn is None)) and torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, weight, bias)):
+        raise NotImplementedError("lemevit_amd: the inference fold and the fused GELU epilogue on a plain operand have no backward")
+    gamma, beta, mean, var, eps = (None, None, None, None, None) if bn is None else bn
+    return _Conv3x3s2Fn.apply(x, weight, bias, cd, gamma, beta, mean, var, eps, gelu, infer)
+
+
+def _is_conv3x3s2p1(m: nn.Module) -> bool:
+    """A 3 x 3 / stride-2 / padding-1 / dense / zero-padded Conv2d."""
+    return (isinstance(m, nn.Conv2d) and m.kernel_size == (3, 3) and m.stride == (2, 2) and m.padding == (1, 1) and m.dilation == (1, 1) and m.groups == 1
+            and m.padding_mode == "zeros")
 
 
 def _is_conv3x3s2(m: nn.Module, x: Tensor) -> bool:
-    return (isinstance(m, nn.Conv2d) and m.kernel_size == (3, 3) and m.stride == (2, 2) and m.padding == (1, 1) and m.dilation == (1, 1)
-            and m.groups == 1 and m.in_channels % 8 == 0 and m.out_channels % 8 == 0 and m.padding_mode == "zeros" and x.is_cuda
+    """The map form: a convolution of a feature map whose channels are a multiple of 8."""
+    return (_is_conv3x3s2p1(m) and m.in_channels % 8 == 0 and m.out_channels % 8 == 0 and x.is_cuda
             and x.dtype in (torch.float32, torch.bfloat16) and m.weight.dtype in (torch.float32, torch.bfloat16))          # (bf16 weights: benchmark.py's --precision bfloat16 whole-model cast)
 
 
@@ -282,90 +301,9 @@ def _bn_frozen(m: Optional[nn.Module]) -> bool:
 
 
 def _conv_bn_pairs(m: nn.Module, bn: Optional[nn.Module], x: Tensor, cd: torch.dtype) -> bool:
-    """Conv2d + frozen BatchNorm2d that run as ONE autograd node (_ConvBNFn) on the native convolution paths."""
+    """Conv2d + frozen BatchNorm2d that run as ONE autograd node (_Conv3x3s2Fn on the fold with gradients) on the native convolution paths."""
     return (_bn_frozen(bn) and cd in (torch.float32, torch.bfloat16) and x.is_cuda and (_is_stem_conv1(m, x) or _is_conv3x3s2(m, x)) and m.weight.dtype == torch.float32
             and (m.bias is None or m.bias.dtype == torch.float32) and m.weight.is_contiguous() and bn.num_features == m.out_channels)
-
-
-class _ConvBNFn(torch.autograd.Function):
-    """Conv2d(Cin, Cout, 3, stride 2, padding 1) -> frozen BatchNorm2d (-> exact GELU, behind the first stem convolution) as one node on the convolution paths of
-    _StemConv1Fn (image: im2col + GEMM, one-launch dX) and _Conv3x3s2Fn (channels-last map: implicit or patch-matrix GEMM).  The BatchNorm is folded into the GEMM
-    operand with gradients (ops.conv_bn_fold / conv_bn_fold_bwd: one launch each per pass), so no pass over the feature map is spent on it and no map is saved for
-    it:  y = act(conv(x; W s, (b - mu) s + beta)), s = gamma / sqrt(var + eps);  dW = dW' s, db = db' s, dgamma = r (sum_k dW'_k W_k + db' (b - mu)), dbeta = db'
-    from the folded gradients dW', db' of the weight-gradient GEMM.  The GELU rides the forward GEMM's epilogue; its backward recomputes the pre-activation from the
-    saved patch rows (ops.linear_fwd(ACT_GELU_BWD)).  The weight-gradient GEMM runs only where W, b, gamma or beta requires grad, dX only where x does."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias, gamma, beta, conv, bn, cd, gelu):
-        B, Ci, H, W = x.shape
-        Co = weight.shape[0]
-        Ho, Wo = (H + 1) // 2, (W + 1) // 2
-        stem1 = _is_stem_conv1(conv, x)
-        if stem1:
-            KP, layout = (9 * Ci + 31) // 32 * 32, ops.FOLD_CI_TAP
-        else:
-            KP, layout = ((9 * Ci + 63) // 64 * 64 if cd == torch.bfloat16 else 9 * Ci), ops.FOLD_TAP_CI      # bf16: whole 64-deep k-steps (the GEMM's LDS-DMA path)
-        eps = float(bn.eps)
-        Wm, bf, _ = derived(conv, ("conv_bn_train", cd, KP, layout), _conv_bn_sources(conv, bn),
-                            lambda: ops.conv_bn_fold(weight.detach(), None if bias is None else bias.detach(), gamma.detach(), beta.detach(), bn.running_mean, bn.running_var,
-                                                     eps, cd, KP, layout))
-        act = ops.ACT_GELU if gelu else ops.ACT_NONE
-        implicit = False
-        if stem1:
-            saved = ops.im2col3x3s2_c3(x, cd) if Ci == 3 else ops.im2col3x3s2_nchw(x, cd, KP)
-        else:
-            assert not gelu
-            xh = x.detach().permute(0, 2, 3, 1).to(cd).contiguous()            # NHWC; no copy for channels-last input of the right dtype
-            implicit = _CONV_IMPLICIT and ops.conv3x3s2_implicit_ok(xh, Co, KP)
-            saved = xh if implicit else ops.im2col3x3s2_nhwc(xh, KP)
-        if implicit:
-            y = ops.conv3x3s2_fwd(saved, Wm, bf)
-        else:
-            y = torch.empty(B * Ho * Wo, Co, device=x.device, dtype=cd)
-            ops.linear_fwd([Prob(saved, Wm, y, bias=bf)], Co, KP, act)
-        need_x, need_p = ctx.needs_input_grad[0], any(ctx.needs_input_grad[1:5])
-        regelu = gelu and (need_x or need_p)          # the GELU backward wants the patch rows AND the folded operand
-        ctx.save_for_backward(*([saved] if need_p or regelu else []), *([Wm, bf] if need_x or regelu else []), *([x] if need_x and stem1 else []))
-        ctx.meta = (tuple(x.shape), x.dtype, stem1, implicit, layout, gelu, eps, need_p, KP, cd)
-        ctx.mods = (conv, bn)
-        return y.view(B, Ho, Wo, Co).permute(0, 3, 1, 2)                    # NCHW-shaped, channels-last-strided: no copy
-
-    @staticmethod
-    def backward(ctx, dy):
-        (B, Ci, H, W), xdt, stem1, implicit, layout, gelu, eps, need_p, KP, cd = ctx.meta
-        conv, bn = ctx.mods
-        need_x = ctx.needs_input_grad[0]
-        sv = list(ctx.saved_tensors)
-        saved = sv.pop(0) if need_p or gelu else None          # the patch matrix, or the NHWC map of the implicit form
-        Wm, bf = (sv.pop(0), sv.pop(0)) if need_x or gelu else (None, None)
-        Co = conv.weight.shape[0]
-        g = dy.permute(0, 2, 3, 1).contiguous().view(-1, Co)
-        if g.dtype != cd:
-            g = g.to(cd)
-        if gelu:          # dz = da * GELU'(z), z recomputed from the patch rows in the same launch
-            dz = torch.empty_like(g)
-            ops.linear_fwd([Prob(saved, Wm, dz, bias=bf, aux=g)], Co, KP, ops.ACT_GELU_BWD)
-            g = dz
-        grads = [None, None, None, None]
-        if need_p:
-            dwm = torch.zeros(Co, KP, device=g.device, dtype=torch.float32)
-            dbf = torch.zeros(Co, device=g.device, dtype=torch.float32)
-            if implicit:
-                ops.conv3x3s2_dw(g, saved, dwm, dbf)
-            else:
-                ops.linear_dw([Prob(g, saved, dwm, bias_grad=dbf)], Co, KP)
-            want = [bool(n) for n in ctx.needs_input_grad[1:5]]
-            want[1] = want[1] and conv.bias is not None
-            grads = list(ops.conv_bn_fold_bwd(dwm, dbf, conv.weight.detach(), None if conv.bias is None else conv.bias.detach(), bn.weight.detach(), bn.running_mean,
-                                              bn.running_var, eps, layout, want))
-        dx = None
-        if need_x and stem1:
-            dx = ops.conv3x3s2_nchw_dx(g, Wm, like=sv.pop(0))
-        elif need_x:
-            dp = torch.empty(g.shape[0], KP, device=g.device, dtype=g.dtype)
-            ops.linear_dx([Prob(g, Wm, dp)], Co, KP)
-            dx = ops.col2im3x3s2_nhwc(dp, B, H, W, Ci).permute(0, 3, 1, 2).to(xdt)
-        return (dx, *grads, None, None, None, None)
 
 
 class _BNActFn(torch.autograd.Function):
@@ -385,23 +323,25 @@ class _BNActFn(torch.autograd.Function):
         return _bn_bwd(ctx, dy) + (None, None, None, None, None)
 
 
-def _bn_train_fwd(x, weight, bias, running_mean, running_var, momentum, eps, gelu):
-    """-> (y NCHW-shaped channels-last view, x2d, batch statistics [2, C], fp32 gamma, fp32 beta); running statistics updated in place."""
+def _bn_operands(x, weight, bias):
+    """-> (x as NHWC rows [B H W, C], fp32 gamma, fp32 beta)"""
     B, C, H, W = x.shape
     x2d = x.detach().permute(0, 2, 3, 1).contiguous().view(B * H * W, C)        # no copy for channels-last input
-    g32, b32 = compute_copy(weight, torch.float32), compute_copy(bias, torch.float32)
+    return x2d, compute_copy(weight, torch.float32), compute_copy(bias, torch.float32)
+
+
+def _bn_train_fwd(x, weight, bias, running_mean, running_var, momentum, eps, gelu):
+    """-> (y NCHW-shaped channels-last view, x2d, batch statistics [2, C], fp32 gamma, fp32 beta); running statistics updated in place."""
+    x2d, g32, b32 = _bn_operands(x, weight, bias)
     y, stats = ops.batchnorm_train_fwd(x2d, g32, b32, running_mean, running_var, momentum, eps, gelu)
-    return y.view(B, H, W, C).permute(0, 3, 1, 2), x2d, stats, g32, b32
+    return _rows_nchw(y, x.shape[0], x.shape[2], x.shape[3]), x2d, stats, g32, b32
 
 
 def _bn_bwd(ctx, dy):
     x2d, stats, g32, b32 = ctx.saved_tensors
     gelu, (B, C, H, W), wdt, bdt = ctx.meta
-    g = dy.permute(0, 2, 3, 1).contiguous().view(B * H * W, C)
-    if g.dtype != x2d.dtype:
-        g = g.to(x2d.dtype)
-    dx, dgamma, dbeta = ops.batchnorm_train_bwd(g, x2d, g32, b32, stats, gelu)
-    return dx.view(B, H, W, C).permute(0, 3, 1, 2), dgamma.to(wdt), dbeta.to(bdt)
+    dx, dgamma, dbeta = ops.batchnorm_train_bwd(_dy_rows(dy, x2d.dtype), x2d, g32, b32, stats, gelu)
+    return _rows_nchw(dx, B, H, W), dgamma.to(wdt), dbeta.to(bdt)
 
 
 class _BNApplyFn(torch.autograd.Function):
@@ -411,18 +351,15 @@ class _BNApplyFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, stats, gelu):
-        B, C, H, W = x.shape
-        x2d = x.detach().permute(0, 2, 3, 1).contiguous().view(B * H * W, C)
-        g32, b32 = compute_copy(weight, torch.float32), compute_copy(bias, torch.float32)
+        x2d, g32, b32 = _bn_operands(x, weight, bias)
         y = ops.batchnorm_apply_fwd(x2d, g32, b32, stats, gelu)
         ctx.save_for_backward(x2d, stats, g32, b32)
-        ctx.meta = (gelu, (B, C, H, W), weight.dtype, bias.dtype)
-        return y.view(B, H, W, C).permute(0, 3, 1, 2)
+        ctx.meta = (gelu, tuple(x.shape), weight.dtype, bias.dtype)
+        return _rows_nchw(y, x.shape[0], x.shape[2], x.shape[3])
 
     @staticmethod
     def backward(ctx, dy):
         return _bn_bwd(ctx, dy) + (None, None)
-
 
 
 def _bn_native(m: nn.Module, x: Tensor) -> bool:
@@ -649,32 +586,25 @@ def _meta_mlp(mlp: nn.Module, c: Tensor, cd: torch.dtype) -> Tensor:
 
 
 def _is_stem_conv1(m: nn.Module, x: Tensor) -> bool:
-    """The stem's first convolution on an image: 1 .. 32 input channels, not a multiple of 8 (those are channels-last feature maps to _Conv3x3s2Fn)."""
-    return (isinstance(m, nn.Conv2d) and 1 <= m.in_channels <= 32 and m.in_channels % 8 != 0 and m.kernel_size == (3, 3) and m.stride == (2, 2) and m.padding == (1, 1)
-            and m.dilation == (1, 1) and m.groups == 1 and m.out_channels % 8 == 0 and m.padding_mode == "zeros"
-            and x.dtype in (torch.float32, torch.bfloat16))
+    """The stem's first convolution on an image: 1 .. 32 input channels, not a multiple of 8 (those are channels-last feature maps: the map form)."""
+    return _is_conv3x3s2p1(m) and 1 <= m.in_channels <= 32 and m.in_channels % 8 != 0 and m.out_channels % 8 == 0 and x.dtype in (torch.float32, torch.bfloat16)
 
 
-def _conv_bn_sources(conv: nn.Conv2d, bn: nn.BatchNorm2d):
-    return conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var
+def _bn_tensors(bn: nn.BatchNorm2d):
+    return bn.weight, bn.bias, bn.running_mean, bn.running_var, float(bn.eps)
 
 
-def _fold_conv_bn(conv: nn.Conv2d, bn: nn.BatchNorm2d, dtype: torch.dtype):
-    """(weight, bias, fp32 bias) of conv followed by eval-mode BatchNorm (no autograd)."""
-    s = (bn.running_var.float() + bn.eps).rsqrt()
-    if bn.weight is not None:
-        s = s * bn.weight.float()
-    w = conv.weight.float() * s[:, None, None, None]
-    b0 = conv.bias.float() if conv.bias is not None else torch.zeros_like(s)
-    b = (b0 - bn.running_mean.float()) * s
-    if bn.bias is not None:
-        b = b + bn.bias.float()
+def _fold_conv_bn(weight: Tensor, bias: Optional[Tensor], gamma: Optional[Tensor], beta: Optional[Tensor], mean: Tensor, var: Tensor, eps: float, dtype: torch.dtype):
+    """(weight, bias, fp32 bias) of a convolution followed by an eval-mode BatchNorm (no autograd)."""
+    s = (var.float() + eps).rsqrt()
+    if gamma is not None:
+        s = s * gamma.float()
+    w = weight.float() * s[:, None, None, None]
+    b0 = bias.float() if bias is not None else torch.zeros_like(s)
+    b = (b0 - mean.float()) * s
+    if beta is not None:
+        b = b + beta.float()
     return w.to(dtype).contiguous(memory_format=torch.channels_last), b.to(dtype), b.contiguous()
-
-
-def _folded_conv_bn(conv: nn.Conv2d, bn: nn.BatchNorm2d, dtype: torch.dtype):
-    """_fold_conv_bn as a derived operand."""
-    return derived(conv, ("conv_bn", dtype), _conv_bn_sources(conv, bn), lambda: _fold_conv_bn(conv, bn, dtype))
 
 
 _STEM = os.environ.get("LMV_STEM", "1") != "0"          # 0: the stem as im2col + GEMM launches (A/B runs)
@@ -685,11 +615,10 @@ def _stem_applies(mods, x: Tensor, cd: torch.dtype) -> bool:
     if not (_STEM and len(mods) == 5 and x.is_cuda and x.dim() == 4 and x.shape[1] == 3 and cd == torch.bfloat16 and x.dtype in (torch.float32, torch.bfloat16)):
         return False
     c1, b1, act, c2, b2 = mods
-    ok = lambda c, ci, co: (isinstance(c, nn.Conv2d) and c.kernel_size == (3, 3) and c.stride == (2, 2) and c.padding == (1, 1) and c.dilation == (1, 1) and c.groups == 1
-                            and c.padding_mode == "zeros" and c.in_channels == ci and c.out_channels == co and c.weight.dtype == torch.float32)
-    if not (isinstance(c1, nn.Conv2d) and isinstance(c2, nn.Conv2d) and ok(c1, 3, c1.out_channels) and ok(c2, c1.out_channels, c2.out_channels)):
+    ok = lambda c, ci: _is_conv3x3s2p1(c) and c.in_channels == ci and c.weight.dtype == torch.float32
+    if not (ok(c1, 3) and ok(c2, c1.out_channels)):
         return False
-    if not all(isinstance(b, nn.BatchNorm2d) and b.track_running_stats for b in (b1, b2)) or not (isinstance(act, nn.GELU) and getattr(act, "approximate", "none") == "none"):
+    if not all(isinstance(b, nn.BatchNorm2d) and b.track_running_stats for b in (b1, b2)) or not _gelu_follows(mods, 2):
         return False
     return ops.stem_supported(x.shape[2], x.shape[3], c1.out_channels, c2.out_channels, cd)
 
@@ -698,13 +627,13 @@ def _stem_fused(mods, x: Tensor, cd: torch.dtype) -> Tensor:
     c1, b1, _, c2, b2 = mods
 
     def build():
-        (w1, _, b1f), (w2, _, b2f) = _fold_conv_bn(c1, b1, cd), _fold_conv_bn(c2, b2, cd)
+        (w1, _, b1f), (w2, _, b2f) = _fold_conv_bn(c1.weight, c1.bias, *_bn_tensors(b1), cd), _fold_conv_bn(c2.weight, c2.bias, *_bn_tensors(b2), cd)
         Cm = w1.shape[0]
         w1m = torch.zeros(Cm, 32, device=w1.device, dtype=cd)
         w1m[:, :27] = w1.reshape(Cm, 27)
         w2m = w2.permute(0, 2, 3, 1).reshape(w2.shape[0], 9 * Cm).contiguous()
         return ops.stem_pack(w1m, w2m), b1f, b2f, Cm, w2.shape[0]
-    wpk, b1f, b2f, Cm, Co = derived(c1, ("stem", cd), _conv_bn_sources(c1, b1) + _conv_bn_sources(c2, b2), build)
+    wpk, b1f, b2f, Cm, Co = derived(c1, ("stem", cd), (c1.weight, c1.bias) + _bn_tensors(b1)[:4] + (c2.weight, c2.bias) + _bn_tensors(b2)[:4], build)
     y = ops.stem_fwd(x, wpk, b1f, b2f, Cm, Co)
     return y.permute(0, 3, 1, 2)                     # NCHW-shaped, channels-last-strided: _to_tokens takes it without a copy
 
@@ -1565,47 +1494,39 @@ def _no_conv_kernel(m: nn.Module, x: Tensor) -> str:
             "stage transitions: 1 .. 32 input channels for the image, otherwise channels a multiple of 8, fp32 / bf16)")
 
 
+def _gelu_follows(mods: Sequence[nn.Module], j: int) -> bool:
+    """mods[j] is the exact GELU (the one the GEMM and BatchNorm epilogues compute; the tanh form is glue)."""
+    return j < len(mods) and isinstance(mods[j], nn.GELU) and getattr(mods[j], "approximate", "none") == "none"
+
+
 def _downsample_mods(mods: List[nn.Module], x: Tensor, cd: torch.dtype, fold: bool, ck: Optional[dict] = None) -> Tensor:
     """The layers of LeMeViT._run_downsample on the native kernels.  ck: see _bn_train (the backward recompute takes the training-mode
     BatchNorms its forward pass took, by module index)."""
+    recompute = ck is not None and ck["recompute"]
     i = 0
     while i < len(mods):
         m = mods[i]
-        bn = mods[i + 1] if i + 1 < len(mods) and isinstance(mods[i + 1], nn.BatchNorm2d) and mods[i + 1].track_running_stats else None
-        if fold and isinstance(m, nn.Conv2d) and bn is not None:
-            w, b, b32 = _folded_conv_bn(m, bn, cd)
-            if _is_stem_conv1(m, x):
-                gelu = i + 2 < len(mods) and isinstance(mods[i + 2], nn.GELU) and getattr(mods[i + 2], "approximate", "none") == "none"
-                x = _StemConv1Fn.apply(x, w, b32, cd, gelu)
-                i += 3 if gelu else 2
-            elif _is_conv3x3s2(m, x) and cd in (torch.float32, torch.bfloat16):
-                x = _Conv3x3s2Fn.apply(x, w, b32, cd)
-                i += 2
-            else:
+        if isinstance(m, nn.Conv2d):
+            image = _is_stem_conv1(m, x)
+            if not ((image or _is_conv3x3s2(m, x)) and cd in (torch.float32, torch.bfloat16)):
                 # (no vendor-library convolution behind the native ones: the stock PyTorch-ROCm column lives in tools/stock_eager.py)
                 raise NotImplementedError(_no_conv_kernel(m, x))
-        elif _conv_bn_pairs(m, bn, x, cd) and not (ck is not None and ck["recompute"] and (i + 1) in ck["stats"]):
-            # a frozen BatchNorm under autograd (the dense backbones' train(), an eval-mode classifier with an image that requires grad): folded into the convolution
-            gelu = _is_stem_conv1(m, x) and i + 2 < len(mods) and isinstance(mods[i + 2], nn.GELU) and getattr(mods[i + 2], "approximate", "none") == "none"
-            x = _ConvBNFn.apply(x, m.weight, m.bias, bn.weight, bn.bias, m, bn, cd, gelu)
-            i += 3 if gelu else 2
-        elif _is_stem_conv1(m, x) and cd in (torch.float32, torch.bfloat16):
-            x = _StemConv1Fn.apply(x, m.weight, m.bias, cd)
-            i += 1
-        elif _is_conv3x3s2(m, x) and cd in (torch.float32, torch.bfloat16):
-            x = _Conv3x3s2Fn.apply(x, m.weight, m.bias, cd)
-            i += 1
-        elif (i in ck["stats"]) if (ck is not None and ck["recompute"]) else _bn_native(m, x):
-            gelu = i + 1 < len(mods) and isinstance(mods[i + 1], nn.GELU) and getattr(mods[i + 1], "approximate", "none") == "none"
+            bn = mods[i + 1] if i + 1 < len(mods) and isinstance(mods[i + 1], nn.BatchNorm2d) and mods[i + 1].track_running_stats else None
+            infer = fold and bn is not None
+            # a frozen BatchNorm under autograd (the dense backbones' train(), an eval-mode classifier with an image that requires grad) is folded into the convolution too,
+            # with gradients -- but not in the recompute of a pass that ran it in training mode
+            folded = infer or (_conv_bn_pairs(m, bn, x, cd) and not (recompute and (i + 1) in ck["stats"]))
+            gelu = folded and image and _gelu_follows(mods, i + 2)
+            x = _conv3x3s2(x, m.weight, m.bias, cd, _bn_tensors(bn) if folded else None, gelu, infer)
+            i += 1 + int(folded) + int(gelu)
+        elif (i in ck["stats"]) if recompute else _bn_native(m, x):
+            gelu = _gelu_follows(mods, i + 1)
             x = _bn_train(m, x, gelu, ck, i)
             i += 2 if gelu else 1
         else:
-            if isinstance(m, nn.Conv2d):
-                raise NotImplementedError(_no_conv_kernel(m, x))
             x = m(x)          # (element-wise glue of a caller-built Sequential: activation, Identity, an eval-mode normalisation under autograd)
             i += 1
     return x
-
 
 
 class _CkptDownsampleFn(torch.autograd.Function):

@@ -582,7 +582,7 @@ def conv3x3s2_implicit_ok(x: Tensor, Cout: int, KP: int) -> bool:
 
 def conv3x3s2_fwd(x: Tensor, wm: Tensor, bias: Optional[Tensor], act: int = ACT_NONE) -> Tensor:
     """Conv2d(Cin, Cout, 3, stride 2, padding 1) of the NHWC map x [B, H, W, Cin] as an implicit GEMM (no patch matrix): -> [B * Ho * Wo, Cout].
-    wm [Cout, KP]: column (ky * 3 + kx) * Cin + ci (model._conv_matrix)."""
+    wm [Cout, KP]: column (ky * 3 + kx) * Cin + ci (model._conv_matrix with FOLD_TAP_CI; the map form of model._Conv3x3s2Fn)."""
     B, H, W, C_ = x.shape
     Co, KP = wm.shape
     y = torch.empty(B * ((H + 1) // 2) * ((W + 1) // 2), Co, device=x.device, dtype=x.dtype)

@@ -162,7 +162,7 @@ def test_stem_conv1_node_with_and_without_image_grad(monkeypatch, cin):
         b = det_tensor((Co,), "b", 3, 0.1).to(DEV).requires_grad_(True)
         xi = x.clone().requires_grad_(need)
         M.new_training_pass()
-        y = M._StemConv1Fn.apply(xi, w, b, torch.bfloat16)
+        y = M._conv3x3s2(xi, w, b, torch.bfloat16)
         n0 = len(calls)
         y.backward(gy)
         assert len(calls) - n0 == (1 if need else 0), "exactly one data-gradient launch, and only when the image asks for it"
@@ -173,6 +173,43 @@ def test_stem_conv1_node_with_and_without_image_grad(monkeypatch, cin):
     wq = det_tensor((Co, cin, 3, 3), "w", 3, 0.3).to(torch.bfloat16).double()
     ref = torch.nn.grad.conv2d_input(x.shape, wq, gy.double().cpu(), stride=2, padding=1)
     kernel_close(dx1, ref, torch.bfloat16, "node dx")
+
+
+@pytest.mark.parametrize("shape,Co,form", [((3, 3, 50, 38), 48, "image"), ((3, 4, 50, 38), 48, "image"), ((2, 8, 5, 6), 16, "patch"), ((64, 64, 9, 7), 128, "implicit")])
+def test_frozen_plain_convolution_keeps_no_gather(monkeypatch, shape, Co, form):
+    """One saved-set rule for every form of the convolution node: a plain convolution whose weight and bias are frozen gives the same y and dX bit for bit, launches no
+    weight-gradient GEMM and keeps neither its patch matrix nor (implicit form) its NHWC map for the backward pass; a trainable one keeps it."""
+    import lemevit_amd.model as M
+    o = ops()
+    dw_calls = []
+    for name in ("linear_dw", "conv3x3s2_dw"):
+        monkeypatch.setattr(o, name, lambda *a, _real=getattr(o, name), **k: (dw_calls.append(1), _real(*a, **k))[1])
+    B, cin, H, W = shape
+    Ho, Wo = (H + 1) // 2, (W + 1) // 2
+    KP = kp_of(cin) if cin % 8 else (9 * cin + 63) // 64 * 64
+    x = det_tensor(shape, "x", 3).to(DEV)
+    if form != "image":
+        assert o.conv3x3s2_implicit_ok(x.permute(0, 2, 3, 1).to(torch.bfloat16).contiguous(), Co, KP) == (form == "implicit")
+    gather = (B, H, W, cin) if form == "implicit" else (B * Ho * Wo, KP)
+    gy = det_tensor((B, Co, Ho, Wo), "gy", 3).to(DEV).to(torch.bfloat16)
+    res = []
+    for trainable in (True, False):
+        w = det_tensor((Co, cin, 3, 3), "w", 3, 0.3).to(DEV).requires_grad_(trainable)
+        b = det_tensor((Co,), "b", 3, 0.1).to(DEV).requires_grad_(trainable)
+        xi = x.clone().requires_grad_(True)
+        M.new_training_pass()
+        y = M._conv3x3s2(xi, w, b, torch.bfloat16)
+        assert y.grad_fn.form == form
+        kept = [tuple(t.shape) for t in y.grad_fn.saved_tensors if t is not None]
+        n0 = len(dw_calls)
+        y.backward(gy)
+        res.append((y.detach(), xi.grad, w.grad, b.grad, kept, len(dw_calls) - n0))
+    (y1, dx1, dw1, db1, kept1, n1), (y0, dx0, dw0, db0, kept0, n0) = res
+    assert gather in kept1 and n1 == 1 and dw1 is not None and db1 is not None, "the trainable convolution keeps its gather for ONE weight-gradient launch"
+    assert torch.equal(y0, y1) and torch.equal(dx0, dx1) and dx0.shape == x.shape
+    assert n0 == 0, "a frozen convolution launches no weight-gradient GEMM"
+    assert gather not in kept0, f"a frozen convolution keeps its gather: {kept0}"
+    assert dw0 is None and db0 is None
 
 
 # ------------------------------------------------------------------------------------------------

@@ -541,12 +541,12 @@ def test_conv3x3s2_native(dtype, B, Ci, Co, H, W):
     """Row f1: the second stem convolution and the three stage transitions of LeMeViT-Base (models/lemevit.py:701-703, :714-717) as
     im2col + the block GEMM -- forward, data gradient (col2im gather) and weight / bias gradient vs float64 F.conv2d on the same
     (rounded) operands; odd map sizes exercise the padding and the ragged last output row / column."""
-    from lemevit_amd.model import _Conv3x3s2Fn
+    from lemevit_amd.model import _conv3x3s2
     x, x64 = rnd((B, Ci, H, W), "cx", dtype); w32 = det_tensor((Co, Ci, 3, 3), "cw", 7, 1.0 / math.sqrt(9 * Ci)); b32 = det_tensor((Co,), "cb", 7, 0.3)
     wq = w32.to(dtype).double() if dtype == torch.bfloat16 else w32.double()
     xg = x.contiguous(memory_format=torch.channels_last).requires_grad_(True)
     wg = w32.to(dev()).requires_grad_(True); bg = b32.to(dev()).requires_grad_(True)
-    y = _Conv3x3s2Fn.apply(xg, wg, bg, dtype)
+    y = _conv3x3s2(xg, wg, bg, dtype)
     x64 = x64.requires_grad_(True); w64 = wq.clone().requires_grad_(True); b64 = b32.double().requires_grad_(True)
     ref = torch.nn.functional.conv2d(x64, w64, b64, stride=2, padding=1)
     assert_close(y, ref.detach(), dtype, "conv fwd")
@@ -568,7 +568,7 @@ def test_conv3x3s2_implicit(B, Ci, Co, H, W):
     weight / bias gradient against float64 F.conv2d on the rounded operands, and BIT-identical to the patch-matrix form (the same panel images reach the same kernel); odd maps
     exercise the padding taps, the ragged last row / column and the zero columns behind 9 Cin (Cin = 8, 24: several taps per 16-byte-chunk row; Cin = 24: taps straddle k-tiles)."""
     import lemevit_amd.model as M
-    from lemevit_amd.model import _Conv3x3s2Fn
+    from lemevit_amd.model import _conv3x3s2
     dtype = torch.bfloat16
     x, x64 = rnd((B, Ci, H, W), "cix", dtype); w32 = det_tensor((Co, Ci, 3, 3), "ciw", 7, 1.0 / math.sqrt(9 * Ci)); b32 = det_tensor((Co,), "cib", 7, 0.3)
     wq = w32.to(dtype).double()
@@ -578,7 +578,7 @@ def test_conv3x3s2_implicit(B, Ci, Co, H, W):
         try:
             xg = x.contiguous(memory_format=torch.channels_last).requires_grad_(True)
             wg = w32.to(dev()).requires_grad_(True); bg = b32.to(dev()).requires_grad_(True)
-            y = _Conv3x3s2Fn.apply(xg, wg, bg, dtype)
+            y = _conv3x3s2(xg, wg, bg, dtype)
             assert ops().conv3x3s2_implicit_ok(xg.detach().permute(0, 2, 3, 1), Co, (9 * Ci + 63) // 64 * 64), "the shape list is meant to take the implicit form"
             gy, gy64 = rnd(tuple(y.shape), "cigy", dtype)
             (y.float() * gy.float()).sum().backward()
@@ -655,7 +655,7 @@ def test_conv3x3s2_outside_implicit_bounds_takes_patch_form():
     """A map with Ho Wo >= 2^19 (B = 1, 1536 x 1536) is refused by the implicit conv's conv_geo (csrc/gemm.hip): conv3x3s2_implicit_ok must say so, so that
     _Conv3x3s2Fn takes the patch-matrix form (im2col + GEMM) forward and backward instead of raising LMV_ERR_SHAPE.  Against float64 F.conv2d: forward and dX on
     sampled rows, dW and db in full."""
-    from lemevit_amd.model import _Conv3x3s2Fn
+    from lemevit_amd.model import _conv3x3s2
     B, Ci, Co, H, W = 1, 8, 16, 1536, 1536
     KP = (9 * Ci + 63) // 64 * 64
     assert (B * ((H + 1) // 2) * ((W + 1) // 2)) % 64 == 0 and ((H + 1) // 2) * ((W + 1) // 2) >= (1 << 19)
@@ -663,9 +663,9 @@ def test_conv3x3s2_outside_implicit_bounds_takes_patch_form():
     w32 = det_tensor((Co, Ci, 3, 3), "cbig.w", 7, 1.0 / math.sqrt(9 * Ci)); b32 = det_tensor((Co,), "cbig.b", 7, 0.3)
     xg = x.contiguous(memory_format=torch.channels_last).requires_grad_(True)
     wg = w32.to(dev()).requires_grad_(True); bg = b32.to(dev()).requires_grad_(True)
-    y = _Conv3x3s2Fn.apply(xg, wg, bg, torch.bfloat16)
+    y = _conv3x3s2(xg, wg, bg, torch.bfloat16)
     assert not ops().conv3x3s2_implicit_ok(xg.detach().permute(0, 2, 3, 1), Co, KP)
-    assert y.grad_fn.meta[-1] is False, "the patch-matrix form was expected"
+    assert y.grad_fn.form == "patch", "the patch-matrix form was expected"
     gy, gy64 = rnd(tuple(y.shape), "cbig.gy", torch.bfloat16)
     (y.float() * gy.float()).sum().backward()
     x64 = x64.requires_grad_(True); w64 = w32.to(torch.bfloat16).double().requires_grad_(True); b64 = b32.double().requires_grad_(True)
