@@ -670,6 +670,39 @@ int lmv_dense_up_loss_bwd(const void* logits, int dtype, int64_t batch_stride, i
                           float eps, int avg_mode, const float* stats, const float* gout, void* dlogits, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Sliding-window dense inference (mmseg's EncoderDecoder.slide_inference, which all three segmentation configs of the reference select:
+ * test_cfg=dict(mode='slide', stride=(384, 384), crop_size=(512, 512))): stitch, resize and argmax in ONE pass.  An addition to ABI 14: callers detect it by
+ * symbol.  The stock loop resizes every window's logits to the crop, pads them to a full [B, K, H, W] fp32 map, adds that into `preds`, bumps a count map, and
+ * divides at the end; here none of those maps exists.  Everything of the two blocks above holds unless stated: the interpolation formulas, the ignore rule, the
+ * argmax rule, the `stats` and workspace row layouts, launch (b), no floating-point atomics (two calls agree bit for bit), capture.
+ *
+ * Geometry.  logits [G, B, K, h, w] fp32 / bf16: the stack of window logits, G = gy gx windows in mmseg's order (window iy gx + ix), ELEMENT strides
+ * window_stride / batch_stride / class_stride, the h x w planes contiguous.  The window set is separable: window (iy, ix) covers the wh x ww image pixels at
+ * origin (ys[iy], xs[ix]); ys [gy] and xs [gx] are HOST int arrays, copied into the kernel arguments (1 <= gy, gx <= LMV_DENSE_SLIDE_MAX_GRID).  The image is
+ * H x W, labels [B, H W], B H W < 2^31; h <= wh, w <= ww.  Per image pixel (Y, X) and class k, in fp32:
+ *     z_k = (v_1 + v_2 + ... ) / (float)count        over the windows with ys[iy] <= Y < ys[iy] + wh and xs[ix] <= X < xs[ix] + ww, in ascending (iy, ix) order,
+ *     v   = the bilinear interpolation of that window's class plane, h x w -> wh x ww (the scales from those sizes), at (Y - ys[iy], X - xs[ix])
+ * which is `preds += F.pad(resize(logits))` in window order followed by `preds / count_mat`; the division is carried out.  From z on it is the pixel of
+ * lmv_dense_up_loss_fwd; the loss terms are fixed to plain cross-entropy averaged over the valid pixels (w_ce = 1, no alpha, gamma = 0, LMV_DENSE_AVG_VALID).
+ *
+ * Outputs, each nullable: pred uint8 [B, H W]; mean_logits fp32 [B, K, H, W], contiguous (the stitched map, for callers that average over augmentations
+ * themselves); conf int64 [K, K] and meter float64 [2], persistent; stats float32 [LMV_DENSE_STATS_FLOATS(K)].  labels == NULL is PREDICTION ONLY (pred and / or
+ * mean_logits; workspace / stats / conf / meter are not touched and may be NULL).  workspace: lmv_dense_slide_workspace_bytes(B, K, H, W).
+ *
+ * Refused with LMV_ERR_SHAPE and a message that starts "dense_slide", before any launch: everything lmv_dense_up_loss_fwd refuses (with wh x ww in the place of
+ * its H x W: h > wh or w > ww is downsampling); gy or gx outside 1 .. 64, null origins; origins that are not strictly increasing; ys[0] != 0 or xs[0] != 0; a last
+ * window that does not end at the image's edge (ys[gy - 1] + wh != H, xs[gx - 1] + ww != W); neighbouring origins further apart than the window (an uncovered
+ * pixel: mmseg's assert (count_mat == 0).sum() == 0); H < 1, W < 1 or B H W >= 2^31; a window stride smaller than the B images it skips; a misaligned
+ * mean_logits; labels == NULL with pred == NULL and mean_logits == NULL.
+ * ------------------------------------------------------------------------------------------ */
+#define LMV_DENSE_SLIDE_MAX_GRID 64
+size_t lmv_dense_slide_workspace_bytes(int B, int K, int H, int W);
+int lmv_dense_slide_fwd(const void* logits, int dtype, int64_t window_stride, int64_t batch_stride, int64_t class_stride, int B, int K, int h, int w,
+                        const int* ys, int gy, const int* xs, int gx, int wh, int ww, int H, int W, int align_corners, const void* labels, int label_dtype,
+                        int64_t ignore_index, void* workspace, size_t workspace_bytes, float* stats, uint8_t* pred, float* mean_logits, int64_t* conf,
+                        double* meter, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Whole-block schedules: ONE call enqueues every launch of a LeMeBlock (models/lemevit.py:500-660) on token-major tensors
  * x [B, H*W, C], c [B, M, C] -- `LeMeBlock.forward_with_x` ("S", :615-650), `forward_with_xc` ("D", :542-582), `forward_with_c`
  * ("C", :584-613; x is returned untouched by the caller, x_out / dx_out may be NULL).  Replaces the ~12 / ~30 per-op calls a Python

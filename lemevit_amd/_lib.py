@@ -28,6 +28,7 @@ EVAL_MAX_PRED, METER_MAX_K = 16, 8          # LMV_EVAL_MAX_PRED, LMV_METER_MAX_K
 DENSE_MAX_CLASSES, DENSE_STATS_HEAD = 64, 6          # LMV_DENSE_MAX_CLASSES, LMV_DENSE_STATS_HEAD (stats: 6 + 5 K floats)
 DENSE_LABEL_I64, DENSE_LABEL_U8 = 0, 1
 DENSE_AVG_VALID, DENSE_AVG_ALL, DENSE_AVG_WEIGHT = 0, 1, 2
+DENSE_SLIDE_MAX_GRID = 64          # LMV_DENSE_SLIDE_MAX_GRID: windows per axis
 
 
 class LinearProblem(C.Structure):
@@ -204,6 +205,8 @@ SIGNATURES = {
     "lmv_dense_up_loss_workspace_bytes": (_Z, [_I, _I, _I, _I]),
     "lmv_dense_up_loss_fwd": (_I, [_P, _I, _L, _L, _I, _I, _I, _I, _I, _I, _I, _P, _I, _L, _P, _F, _F, _F, _F, _F, _I, _P, _Z, _P, _P, _P, _P, _P]),
     "lmv_dense_up_loss_bwd": (_I, [_P, _I, _L, _L, _I, _I, _I, _I, _I, _I, _I, _P, _I, _L, _P, _F, _F, _F, _F, _F, _I, _P, _P, _P, _P]),
+    "lmv_dense_slide_workspace_bytes": (_Z, [_I, _I, _I, _I]),
+    "lmv_dense_slide_fwd": (_I, [_P, _I, _L, _L, _L, _I, _I, _I, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P, _I, _L, _P, _Z, _P, _P, _P, _P, _P, _P]),
     "lmv_block_arena_bytes": (_Z, [C.POINTER(BlockDesc)]),
     "lmv_block_bwd_scratch_bytes": (_Z, [C.POINTER(BlockDesc)]),
     "lmv_block_fwd": (_I, [C.POINTER(BlockDesc), _P, _P, _P, _P, _P, _Z, _I, _P]),

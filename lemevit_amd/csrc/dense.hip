@@ -4,6 +4,8 @@
 //                       negative log-likelihood, the valid count), optionally the argmax map and the confusion counts; (b) ONE workgroup adds the rows in double
 //                       and writes the `stats` vector (losses, 1 / D and the gradient table u_k, v_k);
 //   lmv_dense_loss_bwd: ONE pass that re-reads logits and labels and writes every element of dlogits once from that table.
+//   lmv_dense_up_loss_fwd / _bwd: the same on bilinearly upsampled low-resolution logits, interpolated inside the pass;
+//   lmv_dense_slide_fwd: the forward pass on the mean of overlapping windows' upsampled logits (sliding-window inference: stitch, resize and argmax in one pass).
 // A pixel's classes are K planes a whole image apart: a thread owns a CHUNK of 16 bytes of consecutive pixels (4 fp32 / 8 bf16) and reads one 16-byte word per class
 // plane where base and strides allow, element loads otherwise.  The chunks, the arithmetic behind the loads and every summation order are the same on both paths.
 // No floating-point atomics: per-thread partials, a butterfly per wave, waves in order, rows in order.  Counts that go through atomics are integers.
@@ -118,9 +120,9 @@ __device__ __forceinline__ int wave_sum_int(int v) {
 // The forward LDS (dynamic), one layout for both forward kernels:
 //   KT > 0: red [waves][3 KT + 3] floats | conf [K K] ints;  KT == 0: accP [K][threads] | accI [K][threads] floats | cntT [K] ints | red [waves][3] | conf
 struct DnLds { float* accP; float* accI; int* cntT; float* red; int* conf; };
-static inline size_t dn_lds_bytes(int K, int NT, bool has_conf) {
+static inline size_t dn_lds_bytes(int K, int NT, bool has_conf, int kreg = DN_KREG) {          // kreg: the largest K of the launched kernel's register instances
   const size_t nw = NT / 64;
-  return (K <= DN_KREG ? nw * (3 * K + 3) : (size_t)2 * K * NT + K + nw * 3) * sizeof(float) + (has_conf ? (size_t)K * K * sizeof(int) : 0);
+  return (K <= kreg ? nw * (3 * K + 3) : (size_t)2 * K * NT + K + nw * 3) * sizeof(float) + (has_conf ? (size_t)K * K * sizeof(int) : 0);
 }
 // sums: the pass accumulates (the upsampling kernel's prediction-only form does not: nothing to zero, no barrier)
 template <int KT> __device__ __forceinline__ DnLds dn_lds(float* smem, int K, bool sums, bool has_conf) {
@@ -622,6 +624,152 @@ template <typename T, typename LT, int KT> __global__ __launch_bounds__(256) voi
   if (sums) dn_write_row<KT>(a.ws, a.conf, K, smem, s.red, s.cntT, s.conf, rP, rI, rT, ce_sum, nll_sum, nvalid);
 }
 
+// ---- sliding-window inference: stitch, resize and argmax in one pass -----------------------------------------------------------------------------------
+// window logits [G, B, K, h, w] (G = gy gx windows of wh x ww image pixels, origins ys x xs, mmseg's order) -> per image pixel the MEAN over the covering windows
+// of each window's bilinearly interpolated logits (mmseg's slide_inference: preds += pad(resize(logits)); preds / count_mat), evaluated per output pixel in fp32;
+// from there it is dense_up_fwd_kernel's pixel.  The full-resolution map, the count map and the padded temporaries exist only if the caller asks for `mean`.
+constexpr int SL_KREG = 8;          // K <= SL_KREG: the pixel's class means in registers (Potsdam / Vaihingen: 6, LoveDA: 7)
+struct SlideArgs : DenseHead {
+  int h, w, wh, ww, H, W, cpr, align, gy, gx;          // logits and window size, image size, chunks per image row
+  int stash;          // generic path: the pixel's K means are kept in LDS ([K][threads] floats behind the forward layout) and not interpolated again per sweep
+  float sy, sx;          // up_scale(h, wh), up_scale(w, ww)
+  int64_t sg;          // window stride
+  float* mean;          // nullable: fp32 [B, K, H, W]
+  DenseTerms t;
+  int ys[LMV_DENSE_SLIDE_MAX_GRID], xs[LMV_DENSE_SLIDE_MAX_GRID];
+};
+
+// THE stitching rule: f(window, r0, r1, c0, c1, ly, lx) for every window that covers image pixel (Y, X), in ascending (iy, ix) order -- mmseg's loop order, the
+// order of its `preds +=`; returns their number (mmseg's count_mat).  The origins ascend: the first one behind the pixel ends the scan of an axis.
+template <typename F> __device__ __forceinline__ int sl_windows(const SlideArgs& a, int Y, int X, F&& f) {
+  int n = 0;
+  for (int iy = 0; iy < a.gy; ++iy) {
+    const int oy = Y - a.ys[iy];
+    if (oy < 0) break;
+    if (oy >= a.wh) continue;
+    const UpAxis ay = up_axis(oy, a.h, a.sy, a.align);
+    for (int ix = 0; ix < a.gx; ++ix) {
+      const int ox = X - a.xs[ix];
+      if (ox < 0) break;
+      if (ox >= a.ww) continue;
+      const UpAxis ax = up_axis(ox, a.w, a.sx, a.align);
+      f(iy * a.gx + ix, ay.i0 * a.w, ay.i1 * a.w, ax.i0, ax.i1, ay.l, ax.l);
+      ++n;
+    }
+  }
+  return n;
+}
+// one class at one image pixel: the sum in window order, then THE division (a quotient can merge two sums into a tie that the first-index rule resolves)
+template <typename T> __device__ __forceinline__ float sl_mean(const SlideArgs& a, const T* xk, int Y, int X) {
+  float s = 0.f;
+  const int n = sl_windows(a, Y, X, [&](int g, int r0, int r1, int c0, int c1, float ly, float lx) { s += up_tap<T>(xk + g * a.sg, r0, r1, c0, c1, ly, lx); });
+  return s / (float)n;
+}
+
+// chunks, labels, LDS layout, pixel, row and summation discipline of dense_up_fwd_kernel; the covering set may change inside a chunk: it is evaluated per pixel.
+// labels == NULL: prediction only (argmax map and / or the mean logits, no sums, no row).
+template <typename T, typename LT, int KT> __global__ __launch_bounds__(256) void dense_slide_fwd_kernel(const SlideArgs a) {
+  constexpr int V = UP_V;
+  constexpr int KR = KT > 0 ? KT : 1;
+  extern __shared__ float smem[];
+  const int K = KT > 0 ? KT : a.K;
+  const int NT = blockDim.x, tid = threadIdx.x;
+  const bool sums = a.labels != nullptr;
+  const DnLds s = dn_lds<KT>(smem, K, sums, a.conf != nullptr);
+  float* st = (sums ? reinterpret_cast<float*>(s.conf + (a.conf ? K * K : 0)) : smem) + tid;          // the stash: st[k NT]
+  float rP[KR], rI[KR];
+  int rT[KR];
+#pragma unroll
+  for (int k = 0; k < KR; ++k) { rP[k] = 0.f; rI[k] = 0.f; rT[k] = 0; }
+  float ce_sum = 0.f, nll_sum = 0.f;
+  int nvalid = 0;
+  const T* X = reinterpret_cast<const T*>(a.logits);
+  const LT* L = reinterpret_cast<const LT*>(a.labels);
+  const int64_t HW = (int64_t)a.H * a.W;
+
+  for (int64_t ch = (int64_t)blockIdx.x * NT + tid; ch < a.nchunks; ch += (int64_t)gridDim.x * NT) {
+    const int64_t orow = ch / a.cpr;          // b H + Y
+    const int X0 = (int)(ch - orow * a.cpr) * V;
+    const int b = (int)(orow / a.H), Y = (int)(orow - (int64_t)b * a.H);
+    const int n = min(V, a.W - X0);
+    const int64_t poff = orow * a.W + X0;
+    const T* x = X + (int64_t)b * a.sb;
+    int y[V], bi[V];
+    if (sums) {
+      const LT* lp = L + poff;
+      dn_labels<V>(lp, n == V && (((uintptr_t)lp) & (sizeof(LT) == 8 ? 15u : 3u)) == 0, n, a.ignore, K, y);
+    } else {
+#pragma unroll
+      for (int j = 0; j < V; ++j) y[j] = -1;
+    }
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+      bi[j] = 0;
+      if (j >= n) continue;
+      const int Xp = X0 + j;
+      float* ml = a.mean ? a.mean + ((int64_t)b * K * HW + (int64_t)Y * a.W + Xp) : nullptr;          // class 0 of this pixel; one writer per element
+      float se = 1.f, zy = 0.f, py = 0.f;
+      if constexpr (KT > 0) {
+        float z[KT];
+#pragma unroll
+        for (int k = 0; k < KT; ++k) z[k] = 0.f;
+        const int cnt = sl_windows(a, Y, Xp, [&](int g, int r0, int r1, int c0, int c1, float ly, float lx) {
+          const T* xw = x + g * a.sg;
+#pragma unroll
+          for (int k = 0; k < KT; ++k) z[k] += up_tap<T>(xw + k * a.sc, r0, r1, c0, c1, ly, lx);
+        });
+        const float fc = (float)cnt;
+#pragma unroll
+        for (int k = 0; k < KT; ++k) {
+          z[k] = z[k] / fc;          // sl_mean's sum and division, all classes in one scan of the windows
+          if (ml) ml[k * HW] = z[k];
+        }
+#define DN_Z(k) z[k]
+        DN_PIXEL(KT, DN_Z, y[j], true, bi[j], se, zy, py, rP, rI, rT);          // ignored pixels ARE branched around, as in dense_up_fwd_kernel
+#undef DN_Z
+      } else {
+        // dense_up_fwd_kernel's generic pixel over zk(k).  With the stash the windows are scanned once and each class interpolated once per window (sl_mean's sum
+        // and division, through LDS); without it (the host's choice: K = 64 with sums and a confusion matrix leaves no room) every sweep interpolates again.
+        if (a.stash) {
+          for (int k = 0; k < K; ++k) st[k * NT] = 0.f;
+          const int cnt = sl_windows(a, Y, Xp, [&](int g, int r0, int r1, int c0, int c1, float ly, float lx) {
+            const T* xw = x + g * a.sg;
+            for (int k = 0; k < K; ++k) st[k * NT] += up_tap<T>(xw + k * a.sc, r0, r1, c0, c1, ly, lx);
+          });
+          const float fc = (float)cnt;
+          for (int k = 0; k < K; ++k) st[k * NT] = st[k * NT] / fc;
+        }
+        auto zk = [&](int k) { return a.stash ? st[k * NT] : sl_mean<T>(a, x + k * a.sc, Y, Xp); };
+        float best = zk(0), m = best;
+        int bb = 0;
+        if (ml) ml[0] = best;
+        for (int k = 1; k < K; ++k) {
+          const float z = zk(k);
+          if (ml) ml[k * HW] = z;
+          if (dn_better(z, best)) { best = z; bb = k; }
+          m = fmaxf(m, z);
+        }
+        bi[j] = bb;
+        if (y[j] >= 0) {
+          float sum = 0.f;
+          for (int k = 0; k < K; ++k) sum += expf(zk(k) - m);
+          se = sum;
+          const float inv = 1.f / sum;
+          for (int k = 0; k < K; ++k) {
+            const float dz = zk(k) - m;
+            const float p = expf(dz) * inv;
+            s.accP[k * NT + tid] += p;
+            if (y[j] == k) { s.accI[k * NT + tid] += p; atomicAdd(&s.cntT[k], 1); zy = dz; py = p; }
+          }
+        }
+      }
+      dn_pixel_tail(a, a.t, K, s.conf, y[j], bi[j], se, zy, py, ce_sum, nll_sum, nvalid);
+    }
+    if (a.pred) dn_store_pred<V>(a.pred + poff, n == V && (((uintptr_t)(a.pred + poff)) & 3u) == 0, n, bi);
+  }
+  if (sums) dn_write_row<KT>(a.ws, a.conf, K, smem, s.red, s.cntT, s.conf, rP, rI, rT, ce_sum, nll_sum, nvalid);
+}
+
 // ---- backward: ONE launch, every element of dlogits [B, K, h, w] written once, no atomics ----
 // A workgroup owns a tile of TH x TW input pixels of one image.  The output pixels that touch the tile (its footprint: a rectangle, found with up_first / up_end)
 // are taken in blocks of at most FBH x FBW.  Per block: (1) one sweep leaves every output pixel's max, 1 / sum, sum_j p_j g_j, the CE factor and the label in
@@ -1001,4 +1149,69 @@ extern "C" int lmv_dense_up_loss_bwd(const void* logits, int dtype, int64_t batc
   });
   LMV_CHECK_LAUNCH(fn);
   return LMV_OK;
+}
+
+// ---- the sliding-window entry points ----
+extern "C" size_t lmv_dense_slide_workspace_bytes(int B, int K, int H, int W) { return lmv_dense_up_loss_workspace_bytes(B, K, H, W); }          // the same chunks, the same rows
+
+namespace {
+static int sl_check_axis(const char* fn, const char* axis, const int* o, int g, int win, int img) {
+  if (g < 1 || g > LMV_DENSE_SLIDE_MAX_GRID) LMV_FAIL(LMV_ERR_SHAPE, "%s: %d windows along %s outside 1 .. %d", fn, g, axis, LMV_DENSE_SLIDE_MAX_GRID);
+  if (!o) LMV_FAIL(LMV_ERR_SHAPE, "%s: null window origins along %s", fn, axis);
+  for (int i = 1; i < g; ++i)
+    if (o[i] <= o[i - 1]) LMV_FAIL(LMV_ERR_SHAPE, "%s: window origins along %s are not strictly increasing (%d after %d)", fn, axis, o[i], o[i - 1]);
+  if (o[0] != 0) LMV_FAIL(LMV_ERR_SHAPE, "%s: the first window along %s starts at %d, not at 0", fn, axis, o[0]);
+  if ((int64_t)o[g - 1] + win != img) LMV_FAIL(LMV_ERR_SHAPE, "%s: the last window along %s ends at %lld, the image at %d", fn, axis, (long long)o[g - 1] + win, img);
+  for (int i = 1; i < g; ++i)
+    if (o[i] - o[i - 1] > win) LMV_FAIL(LMV_ERR_SHAPE, "%s: a gap along %s: windows of %d at %d and %d leave pixels uncovered", fn, axis, win, o[i - 1], o[i]);
+  return LMV_OK;
+}
+#define SL_FOR_K(T, LT, ...)                                                                                  \
+  switch (a.K <= SL_KREG ? a.K : 0) {                                                                         \
+    case 2: hipLaunchKernelGGL((dense_slide_fwd_kernel<T, LT, 2>), __VA_ARGS__); break;                       \
+    case 3: hipLaunchKernelGGL((dense_slide_fwd_kernel<T, LT, 3>), __VA_ARGS__); break;                       \
+    case 4: hipLaunchKernelGGL((dense_slide_fwd_kernel<T, LT, 4>), __VA_ARGS__); break;                       \
+    case 5: hipLaunchKernelGGL((dense_slide_fwd_kernel<T, LT, 5>), __VA_ARGS__); break;                       \
+    case 6: hipLaunchKernelGGL((dense_slide_fwd_kernel<T, LT, 6>), __VA_ARGS__); break;                       \
+    case 7: hipLaunchKernelGGL((dense_slide_fwd_kernel<T, LT, 7>), __VA_ARGS__); break;                       \
+    case 8: hipLaunchKernelGGL((dense_slide_fwd_kernel<T, LT, 8>), __VA_ARGS__); break;                       \
+    default: hipLaunchKernelGGL((dense_slide_fwd_kernel<T, LT, 0>), __VA_ARGS__); break;                      \
+  }
+}  // namespace
+
+extern "C" int lmv_dense_slide_fwd(const void* logits, int dtype, int64_t window_stride, int64_t batch_stride, int64_t class_stride, int B, int K, int h, int w,
+                                   const int* ys, int gy, const int* xs, int gx, int wh, int ww, int H, int W, int align_corners, const void* labels,
+                                   int label_dtype, int64_t ignore_index, void* workspace, size_t workspace_bytes, float* stats, uint8_t* pred,
+                                   float* mean_logits, int64_t* conf, double* meter, void* stream) {
+  const char* fn = "dense_slide_fwd";
+  if (!labels && !pred && !mean_logits && logits) LMV_FAIL(LMV_ERR_SHAPE, "%s: null labels, null pred and null mean_logits: nothing to compute", fn);
+  // per window it is the upsampling forward, h x w -> wh x ww (h > wh or w > ww: downsampling, refused there)
+  if (int rc = up_validate(fn, logits, dtype, batch_stride, class_stride, B, K, h, w, wh, ww, align_corners, labels, !pred && !mean_logits, label_dtype, nullptr, 0.f,
+                           1.f, 0.f, 0.f, 1e-7f, LMV_DENSE_AVG_VALID)) return rc;
+  if (H < 1 || W < 1 || (int64_t)B * H * W >= (1ll << 31)) LMV_FAIL(LMV_ERR_SHAPE, "%s: bad image size %d x %d (H >= 1, W >= 1, B H W < 2^31)", fn, H, W);
+  if (int rc = sl_check_axis(fn, "y", ys, gy, wh, H)) return rc;
+  if (int rc = sl_check_axis(fn, "x", xs, gx, ww, W)) return rc;
+  if (window_stride < (int64_t)(B - 1) * batch_stride + (int64_t)(K - 1) * class_stride + (int64_t)h * w)
+    LMV_FAIL(LMV_ERR_SHAPE, "%s: window stride %lld < the %d images it skips", fn, (long long)window_stride, B);
+  if (((uintptr_t)mean_logits) & 3u) LMV_FAIL(LMV_ERR_SHAPE, "%s: misaligned buffer", fn);
+  const int rows = up_rows(B, K, H, W), NT = dn_threads(K);
+  if (labels)
+    if (int rc = dn_check_fwd(fn, "lmv_dense_slide_workspace_bytes", workspace, workspace_bytes, rows, K, stats, conf, meter)) return rc;
+  SlideArgs a = {};
+  dn_head(a, a.t, logits, batch_stride, class_stride, B, K, labels, ignore_index, nullptr, 0.f, 1.f, 0.f, 0.f);          // an evaluation pass: plain cross-entropy
+  a.h = h; a.w = w; a.wh = wh; a.ww = ww; a.H = H; a.W = W; a.align = align_corners; a.gy = gy; a.gx = gx; a.sg = window_stride;
+  a.cpr = (int)dn_cdiv(W, UP_V); a.nchunks = (int64_t)B * H * a.cpr;
+  a.sy = up_scale(h, wh, align_corners); a.sx = up_scale(w, ww, align_corners);
+  std::copy(ys, ys + gy, a.ys); std::copy(xs, xs + gx, a.xs);
+  a.ws = reinterpret_cast<float*>(workspace); a.pred = pred; a.mean = mean_logits; a.conf = labels ? reinterpret_cast<unsigned long long*>(conf) : nullptr;
+  if (!labels) label_dtype = LMV_DENSE_LABEL_U8;
+  size_t lds = labels ? dn_lds_bytes(K, NT, a.conf != nullptr, SL_KREG) : 0;
+  const size_t stash = K > SL_KREG ? (size_t)K * NT * sizeof(float) : 0;
+  a.stash = stash && lds + stash <= 65536;
+  if (a.stash) lds += stash;
+  hipStream_t st = (hipStream_t)stream;
+  dn_for_types(dtype, label_dtype, [&](auto t, auto l) { SL_FOR_K(decltype(t), decltype(l), dim3(rows), dim3(NT), lds, st, a) });
+  LMV_CHECK_LAUNCH(fn);
+  if (!labels) return LMV_OK;
+  return dn_finalize(fn, a.ws, rows, K, (double)B * (double)H * (double)W, nullptr, 1.f, 0.f, 0.f, 1e-7f, LMV_DENSE_AVG_VALID, stats, meter, st);
 }

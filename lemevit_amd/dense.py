@@ -26,11 +26,20 @@ gradient never exist, and the gradient arrives at [B, K, h, w] from one launch. 
     crit = DenseLoss(ignore_index=255, upsample=True)           # decode head: loss on the 4x smaller logits, as mmseg's resize + CrossEntropyLoss
     cd = DenseLoss(ce=1.0, dice=1.0, avg="all", upsample=True, align_corners=True)          # hybrid_loss on the logits in front of Models.py:221's interpolate
     seg = predict(logits, size=img.shape[-2:])                  # uint8 [B, H, W]
+
+Sliding-window inference (what all three segmentation configs of the reference select: ``test_cfg=dict(mode='slide', stride=(384, 384), crop_size=(512, 512))``,
+mmseg's ``EncoderDecoder.slide_inference``): ``slide_inference`` runs the user's backbone + head on every crop, keeps the low-resolution window logits in one
+stack and makes ONE lmv_dense_slide_fwd call that resizes, stitches (the mean over the covering windows, in mmseg's order of additions), takes the argmax and, with
+a meter, updates the confusion matrix and the loss -- the full-resolution ``preds``, the count map and the padded temporaries never exist.
+
+    seg = slide_inference(lambda crop: head(backbone(crop)), img, crop_size=512, stride=384)                       # uint8 [B, H, W]
+    slide_inference(fn, img, 512, 384, meter=meter, target=labels)                                                # evaluation: meter.update_slide inside
 """
 from __future__ import annotations
 
+import ctypes
 from collections import OrderedDict
-from typing import Dict, Iterable, Optional, Sequence, Tuple, Union
+from typing import Callable, Dict, Iterable, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
@@ -38,7 +47,8 @@ from torch import Tensor, nn
 
 from . import _lib, ops
 
-__all__ = ["DenseLoss", "SegMeter", "hybrid_loss", "dice_loss", "jaccard_loss", "FocalLoss", "DenseCrossEntropy", "reference_dense", "seg_metrics", "predict"]
+__all__ = ["DenseLoss", "SegMeter", "hybrid_loss", "dice_loss", "jaccard_loss", "FocalLoss", "DenseCrossEntropy", "reference_dense", "seg_metrics", "predict",
+           "SlideGrid", "slide_grid", "slide_predict", "slide_inference", "reference_slide"]
 
 
 def _alpha32(alpha, K: Optional[int] = None) -> Optional[Tensor]:
@@ -255,7 +265,10 @@ class SegMeter:
     they do not.  ``compute()`` is the only synchronisation.
 
     ``upsample=True``: ``update(low_res_logits, target)`` interpolates inside the pass (``lmv_dense_up_loss_fwd``) when the sizes differ; ``pred`` has the target's
-    resolution.  The same rules for allocation and capture; the buffers are kept per ``(B, h, w, H, W)``."""
+    resolution.  The same rules for allocation and capture; the buffers are kept per ``(B, h, w, H, W)``.
+
+    ``update_slide(window_logits, grid, target)``: the same update from the window logits of a sliding-window evaluation (``lmv_dense_slide_fwd``), stitched inside
+    the pass; ``align_corners`` is the meter's, with or without ``upsample``."""
 
     def __init__(self, num_classes: int, ignore_index: Optional[int] = None, upsample: bool = False, align_corners: bool = False):
         self.upsample, self.align_corners = bool(upsample), bool(align_corners)
@@ -312,6 +325,18 @@ class SegMeter:
         _dense_fwd(logits.detach(), target, size is not None, self.align_corners, self.ignore_index, workspace=ws, stats=stats, pred=pred, conf=conf, meter=loss)
         self.pred = pred
 
+    def update_slide(self, window_logits: Tensor, grid: "SlideGrid", target: Tensor, mean_logits: Optional[Tensor] = None) -> None:
+        """``update`` on the stitched sliding-window prediction (``lmv_dense_slide_fwd``, two launches): ``window_logits`` [G, B, K, h, w], the logits of ``grid``'s
+        windows in its order, at any resolution up to the window's; ``target`` [B, H, W] / [B, 1, H, W].  Uses the meter's ``align_corners``; buffers, capture rules
+        and ``pred`` as in ``update`` (kept per ``(B, h, w, H, W)``).  ``mean_logits``: a float32 [B, K, H, W] buffer that receives the stitched map."""
+        if window_logits.dim() != 5:
+            raise ValueError(f"SegMeter: [G, B, K, h, w] window logits expected, got {tuple(window_logits.shape)}")
+        self._check(window_logits.shape[2], self.ignore_index)
+        pred, conf, loss, stats, ws = self._outputs(window_logits[0], (grid.H, grid.W))
+        ops.dense_slide_fwd(window_logits.detach(), grid.c_ys, grid.c_xs, grid.window, (grid.H, grid.W), target, self.align_corners, self.ignore_index, workspace=ws,
+                            stats=stats, pred=pred, mean_logits=mean_logits, conf=conf, meter=loss)
+        self.pred = pred
+
     def merge(self, states: Iterable[Tuple[Tensor, Tensor]]) -> "SegMeter":
         """Adds other meters' ``state`` pairs ``(conf int64 [K, K], loss float64 [2])``, on any device, into this one: what ``all_reduce`` does across ranks."""
         K = self.num_classes
@@ -353,6 +378,131 @@ def predict(logits: Tensor, size: Optional[Tuple[int, int]] = None, align_corner
     pred = torch.empty((logits.shape[0], H, W), device=logits.device, dtype=torch.uint8)
     ops.dense_up_loss_fwd(logits.detach(), None, align_corners, pred=pred, size=(H, W))
     return pred
+
+
+# ---- sliding-window inference -----------------------------------------------------------------------------------------------------------------------
+def _pair(v) -> Tuple[int, int]:
+    return (int(v), int(v)) if isinstance(v, (int, np.integer)) else (int(v[0]), int(v[1]))
+
+
+class SlideGrid:
+    """The windows of mmseg's ``slide_inference`` over an ``H x W`` image: origins ``ys`` x ``xs`` (separable), every window ``window = (wh, ww)`` pixels
+    (``min(crop, image)`` per axis), ``boxes()`` = ``(y1, y2, x1, x2)`` in mmseg's order (``h_idx`` outer, ``w_idx`` inner)."""
+
+    def __init__(self, H: int, W: int, ys: Sequence[int], xs: Sequence[int], window: Tuple[int, int]):
+        self.H, self.W, self.ys, self.xs, self.window = int(H), int(W), tuple(int(v) for v in ys), tuple(int(v) for v in xs), (int(window[0]), int(window[1]))
+        if not (1 <= len(self.ys) <= _lib.DENSE_SLIDE_MAX_GRID and 1 <= len(self.xs) <= _lib.DENSE_SLIDE_MAX_GRID):
+            raise ValueError(f"SlideGrid: {len(self.ys)} x {len(self.xs)} windows, 1 .. {_lib.DENSE_SLIDE_MAX_GRID} per axis are supported")
+        self.c_ys, self.c_xs = (ctypes.c_int * len(self.ys))(*self.ys), (ctypes.c_int * len(self.xs))(*self.xs)          # what the ABI call reads
+
+    def __len__(self) -> int:
+        return len(self.ys) * len(self.xs)
+
+    def boxes(self) -> List[Tuple[int, int, int, int]]:
+        return [(y, y + self.window[0], x, x + self.window[1]) for y in self.ys for x in self.xs]
+
+    def __repr__(self) -> str:
+        return f"SlideGrid(H={self.H}, W={self.W}, ys={self.ys}, xs={self.xs}, window={self.window})"
+
+
+def slide_grid(size, crop_size, stride) -> SlideGrid:
+    """mmseg's window rule per axis: ``grids = max(img - crop + stride - 1, 0) // stride + 1``; ``y1 = idx * stride; y2 = min(y1 + crop, img);
+    y1 = max(y2 - crop, 0)`` (the last window is shifted back inside the image; an image below the crop gives one window of the image's size)."""
+    (H, W), crop, st = _pair(size), _pair(crop_size), _pair(stride)
+    if min(H, W) < 1 or min(crop) < 1 or min(st) < 1:
+        raise ValueError(f"slide_grid: size {(H, W)}, crop_size {crop} and stride {st} must be positive")
+    if st[0] > crop[0] or st[1] > crop[1]:
+        raise ValueError(f"slide_grid: a stride {st} above the crop {crop} leaves pixels uncovered")
+    origins = []
+    for img, c, s in ((H, crop[0], st[0]), (W, crop[1], st[1])):
+        origins.append([max(min(idx * s + c, img) - c, 0) for idx in range(max(img - c + s - 1, 0) // s + 1)])
+    return SlideGrid(H, W, origins[0], origins[1], (min(crop[0], H), min(crop[1], W)))
+
+
+def _check_stack(fn: str, window_logits: Tensor, grid: SlideGrid) -> Tuple[int, int]:
+    if window_logits.dim() != 5 or window_logits.shape[0] != len(grid):
+        raise ValueError(f"{fn}: [G, B, K, h, w] logits of the grid's {len(grid)} windows expected, got {tuple(window_logits.shape)}")
+    return int(window_logits.shape[1]), int(window_logits.shape[2])
+
+
+def slide_predict(window_logits: Tensor, grid: SlideGrid, align_corners: bool = False, return_logits: bool = False):
+    """The stitched prediction of ``grid``'s window logits [G, B, K, h, w] (float32 / bfloat16, any resolution up to the window's) in ONE launch: uint8 [B, H, W],
+    the argmax of the mean over the covering windows of the bilinearly resized logits -- mmseg's ``preds / count_mat`` and ``argmax(dim=1)``; with
+    ``return_logits`` also that mean, float32 [B, K, H, W] (for callers that average over augmentations themselves)."""
+    B, K = _check_stack("slide_predict", window_logits, grid)
+    dev = window_logits.device
+    pred = torch.empty((B, grid.H, grid.W), device=dev, dtype=torch.uint8)
+    mean = torch.empty((B, K, grid.H, grid.W), device=dev, dtype=torch.float32) if return_logits else None
+    ops.dense_slide_fwd(window_logits.detach(), grid.c_ys, grid.c_xs, grid.window, (grid.H, grid.W), None, align_corners, pred=pred, mean_logits=mean)
+    return (pred, mean) if return_logits else pred
+
+
+_slide_stacks: Dict[tuple, Tensor] = {}          # (G, B, K, h, w, dtype, device) -> the stack of window logits, allocated once per shape
+
+
+def slide_inference(fn: Callable[[Tensor], Tensor], img: Tensor, crop_size, stride, align_corners: bool = False, windows_per_call: int = 1,
+                    meter: Optional[SegMeter] = None, target: Optional[Tensor] = None, return_logits: bool = False):
+    """mmseg's ``EncoderDecoder.slide_inference`` on the native path.  ``fn``: crops [n B, C, wh, ww] -> logits [n B, K, h, w] at any resolution up to the crop's
+    (the backbone plus whatever head the user has); it is called on ``img[:, :, y1:y2, x1:x2]`` per window, or on ``windows_per_call`` windows concatenated along
+    the batch.  Every result is copied into one stack [G, B, K, h, w] (allocated once per shape and kept; under graph capture it must exist) and ONE
+    ``lmv_dense_slide_fwd`` call stitches, resizes and takes the argmax.  Returns uint8 [B, H, W] (with ``return_logits`` also the float32 mean logits
+    [B, K, H, W]); with ``meter`` and ``target`` the same call updates the meter (``meter.update_slide``, the meter's ``align_corners``)."""
+    if img.dim() != 4:
+        raise ValueError(f"slide_inference: a [B, C, H, W] image batch expected, got {tuple(img.shape)}")
+    if (meter is None) != (target is None):
+        raise ValueError("slide_inference: meter and target come together")
+    n_per = int(windows_per_call)
+    if n_per < 1:
+        raise ValueError(f"slide_inference: windows_per_call = {windows_per_call} < 1")
+    grid = slide_grid(img.shape[-2:], crop_size, stride)
+    boxes, B = grid.boxes(), int(img.shape[0])
+    stack = None
+    for g0 in range(0, len(boxes), n_per):
+        group = boxes[g0:g0 + n_per]
+        crops = [img[:, :, y1:y2, x1:x2] for y1, y2, x1, x2 in group]
+        out = fn(crops[0] if len(crops) == 1 else torch.cat(crops, 0)).detach()
+        if out.dim() != 4 or out.shape[0] != len(group) * B:
+            raise ValueError(f"slide_inference: fn returned {tuple(out.shape)} for {len(group)} windows of {B} images; [n B, K, h, w] expected")
+        if stack is None:
+            key = (len(boxes), B) + tuple(out.shape[1:]) + (out.dtype, out.device)
+            stack = _slide_stacks.get(key)
+            if stack is None:
+                if out.is_cuda and torch.cuda.is_current_stream_capturing():
+                    raise RuntimeError("slide_inference: under graph capture the stack of window logits must exist for this shape -- run one eager call first")
+                stack = _slide_stacks[key] = torch.empty((len(boxes), B) + tuple(out.shape[1:]), device=out.device, dtype=out.dtype)
+        elif tuple(out.shape[1:]) != tuple(stack.shape[2:]) or out.dtype != stack.dtype:
+            raise ValueError(f"slide_inference: fn returned {tuple(out.shape)} {out.dtype} after {tuple(stack.shape[2:])} {stack.dtype}: every window must give the same logits shape")
+        stack[g0:g0 + len(group)].view((len(group) * B,) + tuple(stack.shape[2:])).copy_(out)
+    if meter is None:
+        return slide_predict(stack, grid, align_corners, return_logits)
+    mean = torch.empty((B, stack.shape[2], grid.H, grid.W), device=stack.device, dtype=torch.float32) if return_logits else None
+    meter.update_slide(stack, grid, target, mean_logits=mean)
+    return (meter.pred, mean) if return_logits else meter.pred
+
+
+def reference_slide(window_logits, grid: SlideGrid, align_corners: bool = False, labels=None, ignore_index: Optional[int] = None) -> dict:
+    """The numpy float64 oracle of ``lmv_dense_slide_fwd``, written as mmseg's loop: per window resize (``_up_matrix``), pad-add in window order, count, divide.
+    ``window_logits`` [G, B, K, h, w] (a tensor or an array, evaluated on the already rounded values).  Returns ``dict(z [B, K, H, W], pred, margin, count [H, W])``
+    and with ``labels`` also ``conf``, ``nll_sum``, ``n_valid`` (``reference_dense`` on ``z``)."""
+    x = window_logits.detach().cpu().to(torch.float64).numpy() if isinstance(window_logits, Tensor) else np.asarray(window_logits, dtype=np.float64)
+    if x.ndim != 5 or x.shape[0] != len(grid):
+        raise ValueError("reference_slide: [G, B, K, h, w] logits of the grid's windows expected")
+    G, B, K, h, w = x.shape
+    wh, ww = grid.window
+    if h > wh or w > ww:
+        raise ValueError("reference_slide: upsampling only")
+    my, mx = _up_matrix(wh, h, align_corners), _up_matrix(ww, w, align_corners)
+    preds, count = np.zeros((B, K, grid.H, grid.W)), np.zeros((grid.H, grid.W))
+    for g, (y1, y2, x1, x2) in enumerate(grid.boxes()):
+        preds[:, :, y1:y2, x1:x2] += np.matmul(np.matmul(my, x[g]), mx.T)          # preds += F.pad(resize(crop_seg_logit), ...)
+        count[y1:y2, x1:x2] += 1
+    assert (count == 0).sum() == 0
+    z = preds / count
+    ref = reference_dense(z, np.zeros((B, grid.H, grid.W), dtype=np.int64) if labels is None else labels, ignore_index=ignore_index)
+    out = dict(z=z, pred=ref["pred"], margin=ref["margin"], count=count.astype(np.int64))
+    if labels is not None:
+        out.update(conf=ref["conf"], nll_sum=ref["nll_sum"], n_valid=ref["n_valid"])
+    return out
 
 
 def _up_matrix(out: int, inn: int, align_corners: bool) -> np.ndarray:

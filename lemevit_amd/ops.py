@@ -1204,6 +1204,71 @@ def dense_up_loss_bwd(logits: Tensor, labels: Tensor, stats: Tensor, align_corne
     return out
 
 
+def dense_slide_workspace(B: int, K: int, H: int, W: int, device) -> Tensor:
+    """A workspace of lmv_dense_slide_workspace_bytes(B, K, H, W) for ``dense_slide_fwd`` with labels; (H, W) is the image's size."""
+    n = lib.lmv_dense_slide_workspace_bytes(int(B), int(K), int(H), int(W))
+    if n == 0:
+        raise ValueError(f"dense_slide_workspace: bad shape B = {B}, K = {K}, H = {H}, W = {W} (B >= 1, 2 <= K <= {_lib.DENSE_MAX_CLASSES}, B H W < 2^31)")
+    return torch.empty((n,), device=device, dtype=torch.uint8)
+
+
+def dense_slide_fwd(window_logits: Tensor, ys: Sequence[int], xs: Sequence[int], window: Tuple[int, int], size: Tuple[int, int], labels: Optional[Tensor] = None,
+                    align_corners: bool = False, ignore_index: Optional[int] = None, workspace: Optional[Tensor] = None, stats: Optional[Tensor] = None,
+                    pred: Optional[Tensor] = None, mean_logits: Optional[Tensor] = None, conf: Optional[Tensor] = None, meter: Optional[Tensor] = None) -> Optional[Tensor]:
+    """lmv_dense_slide_fwd: mmseg's sliding-window stitching (resize every window's logits to the window, add them into a full-size map in window order, divide by
+    the count map) followed by ``dense_up_loss_fwd``'s pixel, in one pass without those maps.  ``window_logits`` [G, B, K, h, w] float32 / bfloat16 with contiguous
+    h x w planes and ANY window / batch / class strides, G = len(ys) len(xs) windows in mmseg's order (``h_idx`` outer); window (iy, ix) covers the
+    ``window = (wh, ww)`` pixels at ``(ys[iy], xs[ix])`` of the ``size = (H, W)`` image; ``ys`` / ``xs`` are host integers (or ctypes int arrays, taken as they
+    are).  ``labels`` [B, H, W] / [B, 1, H, W] int64 or uint8: plain cross-entropy over the valid pixels; returns ``stats``.  Optional outputs of the same pass:
+    ``pred`` uint8 [B, H W], ``mean_logits`` float32 [B, K, H, W] (the stitched map), ``conf``, ``meter``.  ``labels=None`` is prediction only (returns None)."""
+    fn = "dense_slide_fwd"
+    if window_logits.dim() != 5:
+        raise ValueError(f"{fn}: [G, B, K, h, w] window logits expected, got {tuple(window_logits.shape)}")
+    G, B, K, h, w = window_logits.shape
+    gy, gx = len(ys), len(xs)
+    (wh, ww), (H, W) = (int(window[0]), int(window[1])), (int(size[0]), int(size[1]))
+    if not 2 <= K <= _lib.DENSE_MAX_CLASSES:
+        raise ValueError(f"{fn}: K = {K} classes outside 2 .. {_lib.DENSE_MAX_CLASSES}")
+    if not (1 <= gy <= _lib.DENSE_SLIDE_MAX_GRID and 1 <= gx <= _lib.DENSE_SLIDE_MAX_GRID) or G != gy * gx:
+        raise ValueError(f"{fn}: {G} windows for a grid of {gy} x {gx} (1 .. {_lib.DENSE_SLIDE_MAX_GRID} per axis)")
+    if B < 1 or h < 1 or w < 1 or wh < h or ww < w or B * H * W >= 1 << 31:
+        raise ValueError(f"{fn}: bad sizes {tuple(window_logits.shape)} -> windows of {(wh, ww)} in {(H, W)} (B >= 1, h >= 1, w >= 1, wh >= h, ww >= w: upsampling only, B H W < 2^31)")
+    if (w > 1 and window_logits.stride(4) != 1) or (h > 1 and window_logits.stride(3) != w):
+        raise ValueError(f"{fn}: the logits must have unit pixel stride (NCHW planes; channels-last logits are not supported)")
+    sc = window_logits.stride(2)
+    sb = window_logits.stride(1) if B > 1 else (K - 1) * sc + h * w
+    sg = window_logits.stride(0) if G > 1 else (B - 1) * sb + (K - 1) * sc + h * w
+    if sc < h * w or sb < (K - 1) * sc + h * w or sg < (B - 1) * sb + (K - 1) * sc + h * w:
+        raise ValueError(f"{fn}: overlapping class planes, images or windows (strides {window_logits.stride()})")
+    if labels is not None:
+        if labels.dtype not in (torch.int64, torch.uint8):
+            raise TypeError(f"{fn}: labels must be int64 or uint8, got {labels.dtype}")
+        if tuple(labels.shape) not in ((B, H, W), (B, 1, H, W)) or labels.device != window_logits.device:
+            raise ValueError(f"{fn}: labels must be [B, H, W] or [B, 1, H, W] of the image's size {(H, W)} on the logits' device, got {tuple(labels.shape)}")
+        if not labels.is_contiguous():
+            raise ValueError(f"{fn}: the label map must be contiguous")
+    elif pred is None and mean_logits is None:
+        raise ValueError(f"{fn}: neither labels nor pred nor mean_logits: nothing to compute")
+    if not window_logits.is_cuda:
+        raise RuntimeError("lemevit_amd: tensors must be on the GPU (no CPU fallback exists)")
+    dev = window_logits.device
+    code = dtype_code(window_logits)
+    if mean_logits is not None and (mean_logits.dtype != torch.float32 or tuple(mean_logits.shape) != (B, K, H, W) or mean_logits.device != dev or not mean_logits.is_contiguous()):
+        raise TypeError(f"{fn}: mean_logits must be a contiguous float32 tensor [{B}, {K}, {H}, {W}] on the logits' device")
+    need = 0 if labels is None else lib.lmv_dense_slide_workspace_bytes(B, K, H, W)
+    workspace, stats = _dense_fwd_buffers(fn, "dense_slide_workspace", dev, B, K, H * W, need, workspace, stats, pred, conf, meter)
+    if labels is None:
+        conf = meter = None
+    cy = ys if isinstance(ys, C.Array) else (C.c_int * gy)(*[int(v) for v in ys])
+    cx = xs if isinstance(xs, C.Array) else (C.c_int * gx)(*[int(v) for v in xs])
+    ldt = _lib.DENSE_LABEL_U8 if labels is None or labels.dtype == torch.uint8 else _lib.DENSE_LABEL_I64
+    check(lib.lmv_dense_slide_fwd(window_logits.data_ptr(), code, sg, sb, sc, B, K, h, w, C.addressof(cy), gy, C.addressof(cx), gx, wh, ww, H, W,
+                                  1 if align_corners else 0, _ptr(labels), ldt, -1 if ignore_index is None else int(ignore_index), _ptr(workspace),
+                                  workspace.numel() * workspace.element_size() if need else 0, _ptr(stats), _ptr(pred), _ptr(mean_logits), _ptr(conf), _ptr(meter),
+                                  _stream()), "lmv_dense_slide_fwd")
+    return stats
+
+
 # -------------------------------------------------------------------------------------------
 # A run of "S" blocks as one persistent launch (csrc/sstage.hip; inference, bf16)
 # -------------------------------------------------------------------------------------------
