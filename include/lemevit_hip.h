@@ -703,6 +703,80 @@ int lmv_dense_slide_fwd(const void* logits, int dtype, int64_t window_stride, in
                         double* meter, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Rotated RoIAlign over a feature pyramid (csrc/rroi.hip): the RoI layer of the reference's three Oriented R-CNN configs
+ * (object_detection/configs/obb/oriented_rcnn/: roi_layer=dict(type='RoIAlignRotated', out_size=7, sample_num=2) inside an OBB single-level extractor over
+ * featmap_strides=[4, 8, 16, 32] with extend_factor=(1.4, 1.2)), which the reference has as a CUDA extension only (mmdet/ops/roi_align_rotated/src; the CPU source
+ * there is the specification of the arithmetic).  An addition to ABI 14: callers detect it by symbol.  One plan launch, one forward launch and one backward launch
+ * serve ALL levels; no floating-point atomics, no pre-zeroed buffer, no host synchronisation: two calls agree bit for bit, and every entry point can be captured.
+ *
+ * Geometry.  rois: fp32 [R, 6], rows (batch_index, cx, cy, w, h, theta), theta in RADIANS (the reference's sources have the degree conversion commented out).
+ * levels[l], l < L <= LMV_RROI_MAX_LEVELS: a map [B, C, H_l, W_l] in fp32 or bf16 read through its own ELEMENT strides sb, sc, sh, sw (NCHW, channels-last, a view;
+ * all levels share B, C and the dtype), and spatial_scale_l = 1 / stride_l.  out_size (oh, ow), sample_num s in 1 .. LMV_RROI_MAX_SAMPLE_NUM (s = 0, the
+ * reference's adaptive grid, is refused), aligned in {0, 1}.  The output is [R, C, oh, ow], contiguous, in the maps' dtype, accumulated in fp32.
+ *
+ * Level rule (upstream mmdet's map_roi_levels; the OBB extractor's source is not part of the reference tree, so the order below restates upstream):
+ *     lvl = clamp(floor(log2(sqrt(w h) / finest_scale + 1e-6)), 0, L - 1)          from the UN-extended w, h
+ *     then  w *= extend_w,  h *= extend_h
+ * `level_index` (nullable int32 [R]) overrides the rule RoI by RoI (the extension still applies), so either order is expressible.
+ *
+ * Per RoI at its level, in fp32 with accurate sinf / cosf / log2f / sqrtf:
+ *     off = aligned ? 0.5 : 0;   cw = cx scale - off,  ch = cy scale - off;   rw = w scale,  rh = h scale  (aligned == 0: both clamped to >= 1)
+ *     bin_h = rh / oh,  bin_w = rw / ow;   sample (ph, pw, iy, ix):   yy = -rh / 2 + ph bin_h + (iy + .5) bin_h / s,   xx = -rw / 2 + pw bin_w + (ix + .5) bin_w / s
+ *     y = yy cos(theta) - xx sin(theta) + ch,   x = yy sin(theta) + xx cos(theta) + cw
+ *     y < -1, y > H, x < -1 or x > W: the sample contributes 0.  Otherwise y, x are clamped to >= 0; y_low = (int)y; y_low >= H - 1: y_low = y_high = H - 1, y = y_low;
+ *     else y_high = y_low + 1 (the same for x); ly = y - y_low, hy = 1 - ly:  w1 = hy hx, w2 = hy lx, w3 = ly hx, w4 = ly lx  on (y_low, x_low), (y_low, x_high),
+ *     (y_high, x_low), (y_high, x_high).
+ *     out[r, c, ph, pw] = (sum over the bin's s s samples, iy outer, of w1 v1 + w2 v2 + w3 v3 + w4 v4) / (s s)          (empty samples count in the divisor)
+ * A RoI whose batch_index truncates to a value outside [0, B), or whose level_index lies outside [0, L), is not a sample: its output row is zero and it reaches
+ * no gradient (the rule of lmv_eval_logits and of the dense label maps).  Negative w / h are not validated (that would synchronise): the formulas apply as they are.
+ *
+ * lmv_rroi_plan -- one launch, one workgroup per RoI.  plan (lmv_rroi_plan_bytes(R, oh, ow, s) bytes, 8-byte aligned): R headers of LMV_RROI_HEADER_BYTES
+ * {level, batch, valid, y0, y1, x0, x1, n: the rows / columns of the pixels its samples touch and the number of non-empty samples}, then R x (oh ow s s) sample
+ * records of LMV_RROI_SAMPLE_BYTES {y_low | y_high << 16, x_low | x_high << 16, w1 .. w4}; 4.7 KB per RoI at 7 x 7 x 2 x 2.  The `data` and stride fields of
+ * `levels` are not read.  The forward and the backward pass take ALL geometry from the plan, which makes the backward the adjoint of the forward to the bit; they
+ * must be given the R, L, B, H_l, W_l, oh, ow, s of the plan call (the forward skips a sample whose indices lie outside the map it is given, the backward only ever
+ * writes inside its own tile: a foreign plan gives wrong numbers, not a wild access).
+ *
+ * lmv_rroi_fwd -- one launch, one workgroup per (RoI, 64 channels).  Every output element is written exactly once, rows of invalid RoIs as zeros; no pre-zeroed
+ * buffer.  Lanes run along the memory-contiguous axis of each level's strides: along the bins over NCHW maps, along the channels over channels-last maps (whose
+ * chunk is transposed through LDS so that the store is contiguous too).
+ *
+ * lmv_rroi_bwd -- one launch, gather form.  dx[l]: [B, C, H_l, W_l] in `dtype` through its own strides (the layout of the forward's map, or any other);
+ * dy: [R, C, oh, ow], contiguous, in `dtype`.  dX is the exact adjoint:  dx[b, c, y, x] = sum of w_k dy[r, c, ph, pw] / (s s)  over the corners that land on (y, x),
+ * added in fp32 in a FIXED order (RoI index ascending, then sample order, then corner order w1 .. w4) and rounded once.  A workgroup owns an 8 x 16 pixel tile of
+ * one (level, image) and 64 channels, with the accumulator [pixel][channel] in LDS (33 KB, + 260 B per bin and 24 B per sample for the staged dY rows and sample
+ * records: 50 KB at 7 x 7 x 2 x 2, at most 122 KB); a wave owns two pixel rows and a lane a channel, so no accumulator is shared.  EVERY element of every level is written exactly once -- zeros where no sample lands, on a level that
+ * received no RoI, and at R = 0 -- without a memset and without an atomic.  The result over L levels equals the L single-level results bit for bit.
+ * There is no gradient for the RoIs, and no double backward.  The strides of dx[l] must give every element its own address (the library cannot tell an expanded
+ * view from its arguments' meaning and does not refuse it: several workgroups would store to one address); lemevit_amd/ops.py refuses such a buffer.
+ *
+ * Refused with LMV_ERR_SHAPE (a plan buffer that is too small: LMV_ERR_WORKSPACE) and a message that starts "rroi", before any launch: a null level table, a null
+ * map, null rois / plan / out / dy with R > 0; L outside 1 .. 5; s outside 1 .. 4; oh < 1, ow < 1, oh ow > LMV_RROI_MAX_BINS or oh ow s s > LMV_RROI_MAX_SAMPLES
+ * (what a plan record holds); R < 0, B < 1, C < 1; H_l or W_l outside 1 .. LMV_RROI_MAX_EXTENT (the 16-bit indices); a dtype code other than LMV_F32 / LMV_BF16;
+ * R oh ow s s, R C oh ow or B C H_l W_l >= 2^31; a negative stride, a misaligned buffer, an `aligned` other than 0 / 1, finest_scale <= 0.  R = 0 is legal: the
+ * plan and the forward launch nothing, the backward writes zeros everywhere.  lmv_rroi_plan_bytes returns 0 for arguments the plan call refuses (and for R = 0).
+ * ------------------------------------------------------------------------------------------ */
+#define LMV_RROI_MAX_LEVELS 5
+#define LMV_RROI_MAX_SAMPLE_NUM 4
+#define LMV_RROI_MAX_BINS 256
+#define LMV_RROI_MAX_SAMPLES 1024
+#define LMV_RROI_MAX_EXTENT 65535
+#define LMV_RROI_HEADER_BYTES 32
+#define LMV_RROI_SAMPLE_BYTES 24
+typedef struct lmv_rroi_level {
+  void* data;                 /* the level's map (forward) or gradient (backward); not read by the plan */
+  int64_t sb, sc, sh, sw;     /* ELEMENT strides of [B, C, H, W] */
+  int32_t H, W;
+  float spatial_scale;        /* read by the plan only */
+  int32_t _pad;
+} lmv_rroi_level;
+size_t lmv_rroi_plan_bytes(int R, int oh, int ow, int sample_num);
+int lmv_rroi_plan(const float* rois, const int32_t* level_index, int R, const lmv_rroi_level* levels, int L, int B, int oh, int ow, int sample_num, int aligned,
+                  float finest_scale, float extend_w, float extend_h, void* plan, size_t plan_bytes, void* stream);
+int lmv_rroi_fwd(const void* plan, int R, const lmv_rroi_level* levels, int L, int B, int C, int oh, int ow, int sample_num, int dtype, void* out, void* stream);
+int lmv_rroi_bwd(const void* plan, int R, const void* dy, const lmv_rroi_level* dx, int L, int B, int C, int oh, int ow, int sample_num, int dtype, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Whole-block schedules: ONE call enqueues every launch of a LeMeBlock (models/lemevit.py:500-660) on token-major tensors
  * x [B, H*W, C], c [B, M, C] -- `LeMeBlock.forward_with_x` ("S", :615-650), `forward_with_xc` ("D", :542-582), `forward_with_c`
  * ("C", :584-613; x is returned untouched by the caller, x_out / dx_out may be NULL).  Replaces the ~12 / ~30 per-op calls a Python

@@ -17,6 +17,8 @@ from .metrics import EvalMeter, accuracy, reference_metrics, validate  # noqa: F
 from . import dense  # noqa: F401
 from .dense import DenseCrossEntropy, DenseLoss, FocalLoss, SegMeter, dice_loss, hybrid_loss, jaccard_loss, reference_dense  # noqa: F401
 from .dense import SlideGrid, reference_slide, slide_grid, slide_inference, slide_predict  # noqa: F401
+from . import detection  # noqa: F401
+from .detection import RoIAlignRotated, RotatedRoIExtractor, reference_rroi_align, roi_align_rotated, rroi_align_torch  # noqa: F401
 from . import dist  # noqa: F401  (wrap_ddp, FlatGradSync, attach_flat_grad_sync)
 from .registry import create_model, is_model, list_models, load_checkpoint, register_model  # noqa: F401
 from .registry import lemevit_base, lemevit_small, lemevit_small_v2, lemevit_tiny, lemevit_tiny_v2, vit_tiny  # noqa: F401
@@ -26,4 +28,5 @@ __all__ = ["create_model", "register_model", "list_models", "is_model", "load_ch
            "lemevit_small_v2", "lemevit_tiny_v2", "vit_tiny", "ops", "FlatAdamW", "ModelEma", "layer_ids", "recipe", "Mixup", "MixedTarget", "RandomErasing",
            "SoftTargetCrossEntropy", "LabelSmoothingCrossEntropy", "metrics", "EvalMeter", "accuracy", "validate", "reference_metrics",
            "dense", "DenseLoss", "SegMeter", "hybrid_loss", "dice_loss", "jaccard_loss", "FocalLoss", "DenseCrossEntropy", "reference_dense",
-           "SlideGrid", "slide_grid", "slide_predict", "slide_inference", "reference_slide"]
+           "SlideGrid", "slide_grid", "slide_predict", "slide_inference", "reference_slide",
+           "detection", "roi_align_rotated", "RoIAlignRotated", "RotatedRoIExtractor", "reference_rroi_align", "rroi_align_torch"]

@@ -29,6 +29,8 @@ DENSE_MAX_CLASSES, DENSE_STATS_HEAD = 64, 6          # LMV_DENSE_MAX_CLASSES, LM
 DENSE_LABEL_I64, DENSE_LABEL_U8 = 0, 1
 DENSE_AVG_VALID, DENSE_AVG_ALL, DENSE_AVG_WEIGHT = 0, 1, 2
 DENSE_SLIDE_MAX_GRID = 64          # LMV_DENSE_SLIDE_MAX_GRID: windows per axis
+RROI_MAX_LEVELS, RROI_MAX_SAMPLE_NUM, RROI_MAX_BINS, RROI_MAX_SAMPLES, RROI_MAX_EXTENT = 5, 4, 256, 1024, 65535          # LMV_RROI_MAX_*
+RROI_HEADER_BYTES, RROI_SAMPLE_BYTES = 32, 24          # LMV_RROI_HEADER_BYTES, LMV_RROI_SAMPLE_BYTES
 
 
 class LinearProblem(C.Structure):
@@ -115,6 +117,11 @@ class MixRecord(C.Structure):
 
 class EraseRecord(C.Structure):
     _fields_ = [("box", (C.c_int32 * 4) * ERASE_MAX_BOXES)]          # box[i] = yl, yh, xl, xh
+
+
+class RroiLevel(C.Structure):
+    _fields_ = [("data", C.c_void_p), ("sb", C.c_int64), ("sc", C.c_int64), ("sh", C.c_int64), ("sw", C.c_int64), ("H", C.c_int32), ("W", C.c_int32),
+                ("spatial_scale", C.c_float), ("_pad", C.c_int32)]
 
 
 _P, _I, _L, _F, _Z = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_size_t
@@ -207,6 +214,10 @@ SIGNATURES = {
     "lmv_dense_up_loss_bwd": (_I, [_P, _I, _L, _L, _I, _I, _I, _I, _I, _I, _I, _P, _I, _L, _P, _F, _F, _F, _F, _F, _I, _P, _P, _P, _P]),
     "lmv_dense_slide_workspace_bytes": (_Z, [_I, _I, _I, _I]),
     "lmv_dense_slide_fwd": (_I, [_P, _I, _L, _L, _L, _I, _I, _I, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P, _I, _L, _P, _Z, _P, _P, _P, _P, _P, _P]),
+    "lmv_rroi_plan_bytes": (_Z, [_I, _I, _I, _I]),
+    "lmv_rroi_plan": (_I, [_P, _P, _I, C.POINTER(RroiLevel), _I, _I, _I, _I, _I, _I, _F, _F, _F, _P, _Z, _P]),
+    "lmv_rroi_fwd": (_I, [_P, _I, C.POINTER(RroiLevel), _I, _I, _I, _I, _I, _I, _I, _P, _P]),
+    "lmv_rroi_bwd": (_I, [_P, _I, _P, C.POINTER(RroiLevel), _I, _I, _I, _I, _I, _I, _I, _P]),
     "lmv_block_arena_bytes": (_Z, [C.POINTER(BlockDesc)]),
     "lmv_block_bwd_scratch_bytes": (_Z, [C.POINTER(BlockDesc)]),
     "lmv_block_fwd": (_I, [C.POINTER(BlockDesc), _P, _P, _P, _P, _P, _Z, _I, _P]),

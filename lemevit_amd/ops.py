@@ -1270,6 +1270,132 @@ def dense_slide_fwd(window_logits: Tensor, ys: Sequence[int], xs: Sequence[int],
 
 
 # -------------------------------------------------------------------------------------------
+# Rotated RoIAlign over a feature pyramid (csrc/rroi.hip; lemevit_amd/detection.py has the autograd nodes)
+# -------------------------------------------------------------------------------------------
+class RroiPlan:
+    """The plan of one ``rroi_plan`` call: ``buf`` (uint8, lmv_rroi_plan_bytes) and the geometry it was made for, which ``rroi_align_fwd`` / ``rroi_align_bwd``
+    hand back to the library unchanged."""
+    __slots__ = ("buf", "R", "B", "sizes", "oh", "ow", "sample_num")
+
+    def __init__(self, buf, R, B, sizes, oh, ow, sample_num):
+        self.buf, self.R, self.B, self.sizes, self.oh, self.ow, self.sample_num = buf, R, B, sizes, oh, ow, sample_num
+
+
+def rroi_plan_bytes(R: int, out_size: Tuple[int, int], sample_num: int) -> int:
+    """lmv_rroi_plan_bytes: the bytes of a plan for ``R`` RoIs (32 per RoI + 24 per sample)."""
+    oh, ow = int(out_size[0]), int(out_size[1])
+    n = lib.lmv_rroi_plan_bytes(int(R), oh, ow, int(sample_num))
+    if n == 0 and R != 0:
+        raise ValueError(f"rroi_plan_bytes: bad arguments R = {R}, out_size = {(oh, ow)}, sample_num = {sample_num} (sample_num in 1 .. {_lib.RROI_MAX_SAMPLE_NUM}: 0, the "
+                         f"adaptive grid, is not supported; at most {_lib.RROI_MAX_BINS} bins and {_lib.RROI_MAX_SAMPLES} samples per RoI)")
+    return n
+
+
+def strides_injective(shape, stride) -> bool:
+    """True when no two indices of a tensor of this shape and these strides share an address (dimensions sorted by stride, each one steps over the extent below it)"""
+    dims = sorted((st, n) for n, st in zip(shape, stride) if n > 1)
+    extent = 1
+    for st, n in dims:
+        if st < extent:
+            return False
+        extent += (n - 1) * st
+    return True
+
+
+def _rroi_levels(fn: str, maps: Optional[Sequence[Tensor]], sizes: Sequence[Tuple[int, int]], scales: Optional[Sequence[float]]):
+    L = len(sizes)
+    if not 1 <= L <= _lib.RROI_MAX_LEVELS:
+        raise ValueError(f"{fn}: {L} levels outside 1 .. {_lib.RROI_MAX_LEVELS}")
+    arr = (_lib.RroiLevel * L)()
+    for l in range(L):
+        arr[l].H, arr[l].W = int(sizes[l][0]), int(sizes[l][1])
+        arr[l].spatial_scale = float(scales[l]) if scales is not None else 0.0
+        if maps is not None:
+            t = maps[l]
+            arr[l].data = t.data_ptr()
+            arr[l].sb, arr[l].sc, arr[l].sh, arr[l].sw = t.stride()
+    return arr
+
+
+def _rroi_maps(fn: str, maps: Sequence[Tensor], plan: RroiPlan, what: str):
+    """The checks of the level tensors of a forward / backward call against the plan; returns (C, dtype code)"""
+    if len(maps) != len(plan.sizes):
+        raise ValueError(f"{fn}: {len(maps)} {what} for a plan over {len(plan.sizes)} levels")
+    t0 = maps[0]
+    if t0.dim() != 4:
+        raise ValueError(f"{fn}: [B, C, H, W] {what} expected, got {tuple(t0.shape)}")
+    C_ = int(t0.shape[1])
+    for l, t in enumerate(maps):
+        if tuple(t.shape) != (plan.B, C_, plan.sizes[l][0], plan.sizes[l][1]):
+            raise ValueError(f"{fn}: level {l}: {tuple(t.shape)} is not the plan's {(plan.B, C_) + tuple(plan.sizes[l])}")
+        if t.dtype != t0.dtype or t.device != plan.buf.device:
+            raise TypeError(f"{fn}: all {what} must share one dtype and the plan's device")
+        if not t.is_cuda:
+            raise RuntimeError("lemevit_amd: tensors must be on the GPU (no CPU fallback exists)")
+    return C_, dtype_code(t0)
+
+
+def rroi_plan(rois: Tensor, sizes: Sequence[Tuple[int, int]], spatial_scales: Sequence[float], B: int, out_size: Tuple[int, int], sample_num: int,
+              aligned: bool = True, levels: Optional[Tensor] = None, finest_scale: float = 56.0, extend_factor: Tuple[float, float] = (1.0, 1.0),
+              plan: Optional[Tensor] = None) -> RroiPlan:
+    """lmv_rroi_plan (one launch): ``rois`` float32 [R, 6] rows ``(batch_index, cx, cy, w, h, theta)``, theta in radians; ``sizes[l] = (H_l, W_l)`` and
+    ``spatial_scales[l]`` per level; ``levels``: int32 [R] overriding the level rule; ``plan``: a caller-supplied uint8 buffer of ``rroi_plan_bytes`` (a captured call
+    allocates nothing).  Returns the ``RroiPlan`` that ``rroi_align_fwd`` and ``rroi_align_bwd`` take (include/lemevit_hip.h has the level rule and the formulas)."""
+    fn = "rroi_plan"
+    if rois.dim() != 2 or rois.shape[1] != 6 or rois.dtype != torch.float32:
+        raise ValueError(f"{fn}: float32 [R, 6] rois expected, got {rois.dtype} {tuple(rois.shape)}")
+    if len(spatial_scales) != len(sizes):
+        raise ValueError(f"{fn}: {len(spatial_scales)} scales for {len(sizes)} levels")
+    R, (oh, ow) = int(rois.shape[0]), (int(out_size[0]), int(out_size[1]))
+    sizes = tuple((int(h), int(w)) for h, w in sizes)
+    arr = _rroi_levels(fn, None, sizes, spatial_scales)
+    if levels is not None and (levels.dtype != torch.int32 or tuple(levels.shape) != (R,) or levels.device != rois.device or not levels.is_contiguous()):
+        raise TypeError(f"{fn}: levels must be a contiguous int32 vector [{R}] on the rois' device")
+    need = rroi_plan_bytes(R, (oh, ow), sample_num)
+    if plan is None:
+        plan = torch.empty((max(need, 8),), device=rois.device, dtype=torch.uint8)
+    elif plan.dtype != torch.uint8 or plan.device != rois.device or not plan.is_contiguous() or plan.numel() < need:
+        raise ValueError(f"{fn}: the plan buffer must hold {need} bytes (uint8) on the rois' device (ops.rroi_plan_bytes)")
+    check(lib.lmv_rroi_plan(_ptr(rois), _ptr(levels), R, arr, len(sizes), int(B), oh, ow, int(sample_num), 1 if aligned else 0, float(finest_scale),
+                            float(extend_factor[0]), float(extend_factor[1]), _ptr(plan), plan.numel(), _stream()), "lmv_rroi_plan")
+    return RroiPlan(plan, R, int(B), sizes, oh, ow, int(sample_num))
+
+
+def rroi_align_fwd(feats: Sequence[Tensor], plan: RroiPlan, out: Optional[Tensor] = None) -> Tensor:
+    """lmv_rroi_fwd (one launch over all levels): ``feats[l]`` [B, C, H_l, W_l] float32 / bfloat16 in ANY strides (NCHW and channels-last are the fast ones).
+    Returns ``out`` [R, C, oh, ow], contiguous, in the features' dtype; every element is written once, rows of invalid RoIs as zeros."""
+    fn = "rroi_align_fwd"
+    C_, code = _rroi_maps(fn, feats, plan, "feature maps")
+    shape = (plan.R, C_, plan.oh, plan.ow)
+    if out is None:
+        out = torch.empty(shape, device=feats[0].device, dtype=feats[0].dtype)
+    elif out.dtype != feats[0].dtype or tuple(out.shape) != shape or out.device != feats[0].device or not out.is_contiguous():
+        raise TypeError(f"{fn}: out must be a contiguous {feats[0].dtype} tensor {shape} on the features' device")
+    arr = _rroi_levels(fn, feats, plan.sizes, None)
+    check(lib.lmv_rroi_fwd(plan.buf.data_ptr(), plan.R, arr, len(plan.sizes), plan.B, C_, plan.oh, plan.ow, plan.sample_num, code, out.data_ptr(), _stream()), "lmv_rroi_fwd")
+    return out
+
+
+def rroi_align_bwd(grad_out: Tensor, plan: RroiPlan, like: Sequence[Tensor], dx: Optional[Sequence[Tensor]] = None) -> List[Tensor]:
+    """lmv_rroi_bwd (one launch over all levels, no atomics): ``grad_out`` [R, C, oh, ow] contiguous; returns ``dx[l]`` in the dtype and layout of ``like[l]`` (the
+    forward's feature maps), EVERY element written once -- zeros included, on a level without RoIs and at R = 0.  ``dx``: caller-supplied buffers to write instead.
+    A map whose strides let two indices share an address (an expanded view) is refused: one element, one writer."""
+    fn = "rroi_align_bwd"
+    if dx is None:
+        dx = [torch.empty_like(t) for t in like]
+    C_, code = _rroi_maps(fn, dx, plan, "gradient maps")
+    for l, t in enumerate(dx):
+        if not strides_injective(t.shape, t.stride()):
+            raise ValueError(f"{fn}: level {l}: a gradient map with strides {tuple(t.stride())} aliases itself (an expanded view): every element must have its own address")
+    shape = (plan.R, C_, plan.oh, plan.ow)
+    if tuple(grad_out.shape) != shape or grad_out.dtype != dx[0].dtype or grad_out.device != dx[0].device or not grad_out.is_contiguous():
+        raise TypeError(f"{fn}: grad_out must be a contiguous {dx[0].dtype} tensor {shape} on the maps' device")
+    arr = _rroi_levels(fn, dx, plan.sizes, None)
+    check(lib.lmv_rroi_bwd(plan.buf.data_ptr(), plan.R, grad_out.data_ptr(), arr, len(plan.sizes), plan.B, C_, plan.oh, plan.ow, plan.sample_num, code, _stream()), "lmv_rroi_bwd")
+    return list(dx)
+
+
+# -------------------------------------------------------------------------------------------
 # A run of "S" blocks as one persistent launch (csrc/sstage.hip; inference, bf16)
 # -------------------------------------------------------------------------------------------
 def sstage_supported(C_: int, heads: int, hidden: int, H: int, W: int, M: int, dtype: torch.dtype) -> bool:
