@@ -196,7 +196,9 @@ __device__ __forceinline__ float gelu_grad_fast_f(float x) {
 
 // GELU of TWO values for the fused MLP kernel (fused.hip), where the activation is the binding VALU cost (4 C values per token, all
 // produced on-chip between two MFMA phases): Phi(x) = 0.5 + s q(s^2), s = clamp(x / 4, -1, 1), q = degree-7 minimax fit of
-// erf(x / sqrt 2) / 2 on [-4, 4] with q(1) = 1/2 exactly (so GELU(x <= -4) = 0 and GELU(x >= 4) = x).  No transcendental, and every
+// erf(x / sqrt 2) / 2 on [-4, 4] with q(1) = 1/2 in exact arithmetic.  The fp32 Horner chain below (fused steps) gives q(1) = 0.49999988, hence
+// Phi(+1) = 1 - 2^-23 and Phi(-1) = 2^-23 at the clamp: GELU(x >= 4) is x to within an fp32 ulp (x (1 - 2^-23); a bf16 store gives x back) and
+// GELU(x <= -4) is x 2^-23, NOT 0 (tests/test_stem_exact_gpu.py builds its exact regime on this).  No transcendental, and every
 // step is a packed-fp32 instruction (v_pk_mul_f32 / v_pk_fma_f32: two values per lane and issue).  |Phi error| <= 4.8e-5,
 // |GELU error| <= 1.9e-4 absolute (3.2e-5 for |x| <= 2) -- below half a bf16 ulp of the stored activation for |h| >= 0.05, and the
 // hidden activations only ever exist as bf16 MFMA operands.  (The stand-alone GEMM epilogues keep the erf formula above.)

@@ -1623,6 +1623,16 @@ def stem_fwd(x: Tensor, wpk: Tensor, b1: Tensor, b2: Tensor, Cm: int, Co: int) -
     B, C3, H, W = x.shape
     if C3 != 3 or not x.is_cuda:
         raise ValueError("lemevit_amd: stem_fwd takes [B, 3, H, W] images on the GPU")
+    if x.dtype != torch.float32 and x.dtype != torch.bfloat16:
+        raise ValueError(f"lemevit_amd: stem_fwd takes fp32 or bf16 images, not {x.dtype}")
+    # (the kernel reads lmv_stem_wpk_bytes(Cm, Co) bytes of wpk: a pack of the other variant, or anything that is not stem_pack's buffer, is refused here)
+    need = int(lib.lmv_stem_wpk_bytes(Cm, Co))
+    if not wpk.is_cuda or wpk.device != x.device:
+        raise ValueError(f"lemevit_amd: stem_fwd: wpk is on {wpk.device}, the images are on {x.device}")
+    if wpk.dtype != torch.uint8 or not wpk.is_contiguous():
+        raise ValueError(f"lemevit_amd: stem_fwd: wpk must be the contiguous uint8 buffer of stem_pack, not {wpk.dtype} with strides {tuple(wpk.stride())}")
+    if wpk.numel() != need:
+        raise ValueError(f"lemevit_amd: stem_fwd: wpk holds {wpk.numel()} bytes, the pack of a {Cm} -> {Co} stem has {need} (0: not a supported stem)")
     y = torch.empty((B, H // 4, W // 4, Co), device=x.device, dtype=torch.bfloat16)
     sb, sc, sh, sw = x.stride()
     check(lib.lmv_stem_fwd(x.data_ptr(), dtype_code(x), sb, sc, sh, sw, B, H, W, Cm, Co, wpk.data_ptr(), _f32(b1), _f32(b2), _ptr(y), _stream()), "lmv_stem_fwd")
