@@ -777,6 +777,54 @@ int lmv_rroi_fwd(const void* plan, int R, const lmv_rroi_level* levels, int L, i
 int lmv_rroi_bwd(const void* plan, int R, const void* dy, const lmv_rroi_level* dx, int L, int B, int C, int oh, int ow, int sample_num, int dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Rotated IoU and rotated NMS (csrc/obb.hip): the two remaining custom operators of the reference's Oriented R-CNN configs -- iou_calculator=dict(type='OBBOverlaps')
+ * (mmdet/ops/box_iou_rotated: obb_overlaps) in both assigners, and nms_pre / nms_thr=0.8 of the oriented RPN and nms=dict(type='obb_nms', iou_thr=0.1) of the test
+ * config (mmdet/ops/nms_rotated: obb_nms, arb_batched_nms).  An addition to ABI 14: callers detect it by symbol.  No host round trip, no atomics: two calls agree bit
+ * for bit and every entry point can be captured.
+ *
+ * Boxes.  fp32 rows (cx, cy, w, h, theta) with a ROW STRIDE in floats (>= 5: a [N, 6] dets tensor is read in place), theta in RADIANS; the width axis is
+ * (cos theta, -sin theta), the height axis (sin theta, cos theta) -- the reference's convention.
+ *
+ * The pair rule (single_box_iou_rotated and the wrapper's "too small" rule), in fp32 with cos / sin evaluated once per box (accurate cosf / sinf):
+ *     a box with a non-finite entry, or with w < 0.001 or h < 0.001 (which covers the reference's w h < 1e-14), gives 0 against everything;
+ *     I = area of the intersection;   iou = I / (w1 h1 + w2 h2 - I);   iof = I / (w1 h1);   a non-finite quotient gives 0.
+ * I is computed from the centre DIFFERENCE (a pair's value does not depend on where it sits in the image) with one box expressed in the other's frame, as the
+ * boundary integral of clamp(u, -W, W) dv over the four edges restricted to |v| <= H (csrc/obb.hip): no polygon is built, so exactly degenerate pairs (a duplicate,
+ * its theta + pi twin, its theta + pi / 2 twin with w and h swapped, shared edges, containment) are ordinary inputs.  Which box supplies the frame follows a total
+ * order on the boxes: iou(p, q) and iou(q, p) agree bit for bit.  Pairs whose bounding circles are apart give exactly 0.
+ * Deliberate differences from the reference: (1) its 24-point / Graham-scan routine breaks down on such pairs (0.25 instead of 1.0 for (100, 100, 40, 20, 0.3)
+ * against (100, 100, 40, 20, 0.3 + pi) in its float32 CPU build); this one does not.  (2) classes are separated by `groups`, not by adding class_id *
+ * (max_coordinate + 1) to the centres in fp32, which moves an IoU by about 1e-5 at 15 classes on a 1024^2 crop.
+ *
+ * lmv_obb_overlaps -- one launch.  out: fp32 [N, M] (aligned == 0) or [N] from the N pairs (b1[n], b2[n]) (aligned == 1, N == M); every element is written exactly
+ * once, stores run along M.  A workgroup owns a 16 x 64 tile and stages the tile's box records in LDS.  N == 0 or M == 0 launches nothing.
+ *
+ * lmv_obb_nms -- two launches.  order: int64 [N], the STABLE descending sort of the scores (the caller's; boxes, scores and groups are gathered through it, an
+ * entry outside [0, N) names no box).  groups: nullable int32 [N].  A box is a CANDIDATE iff score > score_thr (-inf: every score that is not NaN or -inf) and
+ * w >= 0.001 and h >= 0.001 (and all five entries are finite).  Non-candidates are never kept and never suppress.  A kept box suppresses every lower-ranked
+ * candidate of its group with IoU > iou_thr (strict, as the reference's CUDA kernel).
+ *     mask launch    64 x 64 tiles of the rank-ordered boxes, upper triangle; a wave64 owns rows of the tile, lane j evaluates (row, column j) and the ballot is
+ *                    the row's 64-bit word: workspace[rank * ceil(N / 64) + column_block], written for column_block >= row_block (the rest is never read).
+ *     reduce launch  one workgroup; thread c keeps word c of the `removed` bit vector.  Per block of 64 ranks the diagonal word is resolved serially and the rows
+ *                    of the kept ranks are ORed into `removed` in parallel.  keep: int64 [cap], cap = max_num > 0 ? max_num : N: the original indices of the kept
+ *                    boxes in rank order, then -1; count: one int64, the number written (at most max_num).  Every element of both is written exactly once.
+ * phases: 3 for both launches; 1 / 2 run one of them alone (probes: the reduce launch then reads a workspace that a mask launch has filled).
+ * N == 0 launches nothing: count = 0 and keep = -1 are set by memset nodes.  workspace: lmv_obb_nms_workspace_bytes(N) = N ceil(N / 64) 8 bytes, 8-byte aligned.
+ *
+ * Refused with LMV_ERR_SHAPE (a workspace that is too small: LMV_ERR_WORKSPACE) and a message that starts "obb", before any launch: null pointers, a row stride
+ * below 5, misaligned pointers, negative sizes, more than LMV_OBB_MAX_BOXES boxes on a side (overlaps) or N > LMV_OBB_NMS_MAX (nms), max_num < 0, a NaN threshold,
+ * an unknown mode, aligned / phases out of range.  lmv_obb_nms_workspace_bytes returns 0 for an N the call refuses (and for N = 0).
+ * ------------------------------------------------------------------------------------------ */
+#define LMV_OBB_IOU 0
+#define LMV_OBB_IOF 1
+#define LMV_OBB_MAX_BOXES 1048576
+#define LMV_OBB_NMS_MAX 16384
+int lmv_obb_overlaps(const float* boxes1, int stride1, int N, const float* boxes2, int stride2, int M, int mode, int aligned, float* out, void* stream);
+size_t lmv_obb_nms_workspace_bytes(int N);
+int lmv_obb_nms(const float* boxes, int stride, const float* scores, const int64_t* order, const int32_t* groups, int N, float iou_thr, float score_thr, int max_num,
+                int phases, void* workspace, size_t workspace_bytes, int64_t* keep, int64_t* count, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Whole-block schedules: ONE call enqueues every launch of a LeMeBlock (models/lemevit.py:500-660) on token-major tensors
  * x [B, H*W, C], c [B, M, C] -- `LeMeBlock.forward_with_x` ("S", :615-650), `forward_with_xc` ("D", :542-582), `forward_with_c`
  * ("C", :584-613; x is returned untouched by the caller, x_out / dx_out may be NULL).  Replaces the ~12 / ~30 per-op calls a Python

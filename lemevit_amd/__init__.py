@@ -19,6 +19,7 @@ from .dense import DenseCrossEntropy, DenseLoss, FocalLoss, SegMeter, dice_loss,
 from .dense import SlideGrid, reference_slide, slide_grid, slide_inference, slide_predict  # noqa: F401
 from . import detection  # noqa: F401
 from .detection import RoIAlignRotated, RotatedRoIExtractor, reference_rroi_align, roi_align_rotated, rroi_align_torch  # noqa: F401
+from .detection import arb_batched_nms, obb_nms, obb_nms_padded, obb_nms_torch, obb_overlaps, obb_overlaps_torch, reference_obb_nms, reference_obb_overlaps  # noqa: F401
 from . import dist  # noqa: F401  (wrap_ddp, FlatGradSync, attach_flat_grad_sync)
 from .registry import create_model, is_model, list_models, load_checkpoint, register_model  # noqa: F401
 from .registry import lemevit_base, lemevit_small, lemevit_small_v2, lemevit_tiny, lemevit_tiny_v2, vit_tiny  # noqa: F401
@@ -29,4 +30,5 @@ __all__ = ["create_model", "register_model", "list_models", "is_model", "load_ch
            "SoftTargetCrossEntropy", "LabelSmoothingCrossEntropy", "metrics", "EvalMeter", "accuracy", "validate", "reference_metrics",
            "dense", "DenseLoss", "SegMeter", "hybrid_loss", "dice_loss", "jaccard_loss", "FocalLoss", "DenseCrossEntropy", "reference_dense",
            "SlideGrid", "slide_grid", "slide_predict", "slide_inference", "reference_slide",
-           "detection", "roi_align_rotated", "RoIAlignRotated", "RotatedRoIExtractor", "reference_rroi_align", "rroi_align_torch"]
+           "detection", "roi_align_rotated", "RoIAlignRotated", "RotatedRoIExtractor", "reference_rroi_align", "rroi_align_torch",
+           "obb_overlaps", "obb_nms", "obb_nms_padded", "arb_batched_nms", "reference_obb_overlaps", "reference_obb_nms", "obb_overlaps_torch", "obb_nms_torch"]

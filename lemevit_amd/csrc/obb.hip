@@ -1,0 +1,342 @@
+// obb.hip -- rotated IoU and rotated NMS for the Oriented R-CNN configs (the reference's mmdet/ops/box_iou_rotated: obb_overlaps and mmdet/ops/nms_rotated: obb_nms /
+// arb_batched_nms): lmv_obb_overlaps, lmv_obb_nms (+ _workspace_bytes).  include/lemevit_hip.h has the semantics; this file has the pair function and the mappings.
+//
+//   pair      ONE device function, obb_pair, in fp32 from per-box records (cx, cy, w/2, h/2, cos, sin, half diagonal, flags, group) that are built once per box.
+//             The corners of box A are expressed in the frame of box B (from the centre difference and the sine / cosine of the angle difference), where B is the
+//             rectangle |u| <= W, |v| <= H, and the intersection area is the boundary integral
+//                 I = sum over the four edges of A (counter-clockwise) of  INT (clamp(u, -W, W) - k) dv   over the part of the edge with v in [-H, H]
+//             (for a fixed v the slice of A is an interval [uL, uR], its part inside the rectangle has length clamp(uR) - clamp(uL)).  On an edge the integrand is
+//             piecewise linear with breakpoints where u crosses -W and +W, so three trapezoids give it exactly.  There is no polygon, no vertex count and no
+//             decision about topology: min / max / select only, nothing indexed at run time (0 bytes of scratch), and the value is continuous in the boxes -- a
+//             duplicate, its theta + pi twin, and its theta + pi / 2 twin with w and h swapped give I = w h to rounding.  Which box plays A is decided by a total order
+//             on the records, so pair(p, q) == pair(q, p) bit for bit.
+//   overlaps  a workgroup owns a 16 x 64 tile of the [N, M] matrix and stages its 16 + 64 records in LDS; a lane owns a column, so the stores run along M.
+//   nms mask  64 x 64 tiles of the rank-ordered boxes, upper triangle; a wave owns 16 rows of the tile, lane j evaluates (row, column j) and the ballot is the row's
+//             word.  Different groups and pairs whose bounding circles are apart never reach the pair function.
+//   nms reduce  one workgroup, thread c owns word c of the `removed` bit vector in a register.  Per block of 64 ranks: every thread loads the 64 row words of its own
+//             column block (independent loads, issued before the serial part), wave 0 resolves the diagonal word serially on the scalar unit (row r's word is read
+//             out of lane r's registers: no memory access in the 64-step chain), and every thread ORs the rows that were kept into its word.  Then a scan over the popcounts places the kept ranks in keep[], the tail is -1, count is written.
+#include "common.h"
+#include <math.h>
+
+// No implicit fused multiply-adds in this file (the explicit fmaf calls stay): the pair function then rounds the same way in every kernel it is inlined into, so the
+// aligned pairs equal the diagonal of the matrix and the NMS decides on exactly the values the overlaps kernel reports.
+#pragma clang fp contract(off)
+
+namespace {
+
+constexpr int OB_TN = 16, OB_TM = 64;          // overlaps: rows x columns of a workgroup's tile
+constexpr int OB_VALID = 1, OB_CAND = 2;       // record flags: takes part in an IoU; NMS candidate
+constexpr float OB_MIN_SIDE = 0.001f;          // the wrapper's "too small" rule
+constexpr float OB_APART = 1.0001f;            // bounding circles: apart when d^2 > (r1 + r2)^2 * this (fp32 rounding is below 1e-6 relative: the reject is exact)
+
+struct ObbRec { float cx, cy, hw, hh, c, s, rad; int flags, group; };
+
+__device__ __forceinline__ ObbRec obb_none() {
+  ObbRec r; r.cx = r.cy = r.hw = r.hh = r.s = r.rad = 0.f; r.c = 1.f; r.flags = 0; r.group = 0;
+  return r;
+}
+
+// the record of one box row (cx, cy, w, h, theta); accurate sinf / cosf, once per box
+__device__ __forceinline__ ObbRec obb_load(const float* b) {
+  const float cx = b[0], cy = b[1], w = b[2], h = b[3], th = b[4];
+  ObbRec r;
+  r.cx = cx; r.cy = cy; r.hw = 0.5f * w; r.hh = 0.5f * h;
+  r.c = cosf(th); r.s = sinf(th);
+  r.rad = sqrtf(r.hw * r.hw + r.hh * r.hh);
+  const bool finite = isfinite(cx) && isfinite(cy) && isfinite(w) && isfinite(h) && isfinite(th) && isfinite(r.rad);
+  r.flags = (finite && w >= OB_MIN_SIDE && h >= OB_MIN_SIDE) ? OB_VALID : 0;
+  r.group = 0;
+  return r;
+}
+
+__device__ __forceinline__ float clampf(float x, float lo, float hi) { return fminf(fmaxf(x, lo), hi); }
+
+// INT (clamp(u, -W, W) - k) dv along the edge (u0, v0) -> (u1, v1), over its part with v in [-H, H].  Over a closed polygon the constant k integrates to zero (the
+// clipped v ranges of the rising and the falling edges cancel), so any k gives the same area; k = the clamped centre of A keeps every term of the size of A, not of
+// the size of the frame: no cancellation when a small box lies far from the centre of a large one.
+__device__ __forceinline__ float obb_edge(float u0, float v0, float u1, float v1, float W, float H, float k) {
+  const float du = u1 - u0, dv = v1 - v0;
+  const float rv = __builtin_amdgcn_rcpf(dv == 0.f ? 1.f : dv);          // (dv == 0: the edge contributes dv * ... = 0)
+  const float ta = (-H - v0) * rv, tb = (H - v0) * rv;
+  const float t0 = clampf(fminf(ta, tb), 0.f, 1.f), t3 = clampf(fmaxf(ta, tb), 0.f, 1.f);
+  const float ru = __builtin_amdgcn_rcpf(du == 0.f ? 1.f : du);
+  const float ba = (-W - u0) * ru, bb = (W - u0) * ru;
+  const float t1 = du == 0.f ? t0 : clampf(fminf(ba, bb), t0, t3);
+  const float t2 = du == 0.f ? t3 : clampf(fmaxf(ba, bb), t0, t3);
+  const float f0 = clampf(fmaf(t0, du, u0), -W, W) - k, f1 = clampf(fmaf(t1, du, u0), -W, W) - k;
+  const float f2 = clampf(fmaf(t2, du, u0), -W, W) - k, f3 = clampf(fmaf(t3, du, u0), -W, W) - k;
+  return 0.5f * dv * ((t1 - t0) * (f0 + f1) + (t2 - t1) * (f1 + f2) + (t3 - t2) * (f2 + f3));
+}
+
+// area of A n B: A's corners in B's frame (u axis = B's width axis (cos, -sin), v axis = B's height axis (sin, cos))
+__device__ __forceinline__ float obb_inter(const ObbRec& a, const ObbRec& b) {
+  const float dx = a.cx - b.cx, dy = a.cy - b.cy;
+  const float cu = dx * b.c - dy * b.s, cv = dx * b.s + dy * b.c;          // A's centre
+  const float cr = a.c * b.c + a.s * b.s, sr = a.s * b.c - a.c * b.s;          // cos / sin of (theta_A - theta_B): A's width axis is (cr, -sr), its height axis (sr, cr)
+  const float wu = a.hw * cr, wv = -a.hw * sr, hu = a.hh * sr, hv = a.hh * cr;
+  const float u0 = cu + wu + hu, v0 = cv + wv + hv;          // (+, +)
+  const float u1 = cu - wu + hu, v1 = cv - wv + hv;          // (-, +)
+  const float u2 = cu - wu - hu, v2 = cv - wv - hv;          // (-, -)
+  const float u3 = cu + wu - hu, v3 = cv + wv - hv;          // (+, -): counter-clockwise in (u, v)
+  const float W = b.hw, H = b.hh, k = clampf(cu, -W, W);
+  return (obb_edge(u0, v0, u1, v1, W, H, k) + obb_edge(u1, v1, u2, v2, W, H, k)) + (obb_edge(u2, v2, u3, v3, W, H, k) + obb_edge(u3, v3, u0, v0, W, H, k));
+}
+
+// a total order on the records (equal records: the same box, either order gives the same bits)
+__device__ __forceinline__ bool obb_before(const ObbRec& p, const ObbRec& q) {
+  const float pa = p.hw * p.hh, qa = q.hw * q.hh;
+  if (pa != qa) return pa < qa;          // the smaller box first
+  if (p.hw != q.hw) return p.hw < q.hw;
+  if (p.hh != q.hh) return p.hh < q.hh;
+  if (p.cx != q.cx) return p.cx < q.cx;
+  if (p.cy != q.cy) return p.cy < q.cy;
+  if (p.c != q.c) return p.c < q.c;
+  return p.s < q.s;
+}
+
+__device__ __forceinline__ ObbRec obb_select(bool first, const ObbRec& p, const ObbRec& q) {
+  ObbRec r;
+  r.cx = first ? p.cx : q.cx; r.cy = first ? p.cy : q.cy; r.hw = first ? p.hw : q.hw; r.hh = first ? p.hh : q.hh;
+  r.c = first ? p.c : q.c; r.s = first ? p.s : q.s; r.rad = first ? p.rad : q.rad; r.flags = first ? p.flags : q.flags; r.group = first ? p.group : q.group;
+  return r;
+}
+
+// THE pair function: IoU (mode LMV_OBB_IOU) or IoF = I / area(p) (LMV_OBB_IOF) of two records
+__device__ __forceinline__ float obb_pair(const ObbRec& p, const ObbRec& q, int mode) {
+  if (!(p.flags & q.flags & OB_VALID)) return 0.f;
+  const float dx = p.cx - q.cx, dy = p.cy - q.cy, rr = p.rad + q.rad;
+  if (dx * dx + dy * dy > rr * rr * OB_APART) return 0.f;          // bounding circles apart: exactly 0
+  const bool pf = obb_before(p, q);          // the smaller box is A, the larger one the frame
+  const ObbRec a = obb_select(pf, p, q), b = obb_select(pf, q, p);
+  const float a1 = 4.f * p.hw * p.hh, a2 = 4.f * q.hw * q.hh;
+  const float inter = fminf(fmaxf(obb_inter(a, b), 0.f), fminf(a1, a2));
+  const float v = mode == LMV_OBB_IOU ? inter / (a1 + a2 - inter) : inter / a1;
+  return isfinite(v) ? v : 0.f;
+}
+
+// ---- overlaps ----------------------------------------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void obb_overlaps_kernel(const float* __restrict__ b1, int s1, int N, const float* __restrict__ b2, int s2, int M, int mode,
+                                                           float* __restrict__ out) {
+  __shared__ ObbRec rows[OB_TN], cols[OB_TM];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int n0 = blockIdx.x * OB_TN, m0 = blockIdx.y * OB_TM;
+  if (tid < OB_TM) {
+    const int m = m0 + tid;
+    cols[tid] = m < M ? obb_load(b2 + (int64_t)m * s2) : obb_none();
+  } else if (tid < OB_TM + OB_TN) {
+    const int n = n0 + tid - OB_TM;
+    rows[tid - OB_TM] = n < N ? obb_load(b1 + (int64_t)n * s1) : obb_none();
+  }
+  __syncthreads();
+  const ObbRec q = cols[lane];
+  const int m = m0 + lane;
+#pragma unroll 1
+  for (int i = 0; i < OB_TN / 4; ++i) {
+    const int r = wv * (OB_TN / 4) + i, n = n0 + r;
+    if (n >= N) break;
+    const float v = obb_pair(rows[r], q, mode);
+    if (m < M) out[(int64_t)n * M + m] = v;
+  }
+}
+
+__global__ __launch_bounds__(256) void obb_overlaps_aligned_kernel(const float* __restrict__ b1, int s1, const float* __restrict__ b2, int s2, int N, int mode,
+                                                                   float* __restrict__ out) {
+  const int n = blockIdx.x * 256 + threadIdx.x;
+  if (n >= N) return;
+  const ObbRec p = obb_load(b1 + (int64_t)n * s1), q = obb_load(b2 + (int64_t)n * s2);
+  out[n] = obb_pair(p, q, mode);
+}
+
+// ---- NMS ---------------------------------------------------------------------------------------------------------------------------------------------------------
+struct NmsArgs {
+  const float* boxes; int stride; const float* scores; const int64_t* order; const int32_t* groups;
+  int N, nb; float iou_thr, score_thr; int cap; unsigned long long* mask; int64_t* keep; int64_t* count;
+};
+
+// the record of the box at a rank; an `order` entry outside [0, N) reads nothing and is no candidate
+__device__ __forceinline__ ObbRec nms_load(const NmsArgs& a, int rank) {
+  if (rank >= a.N) return obb_none();
+  const int64_t idx = a.order[rank];
+  if (idx < 0 || idx >= a.N) return obb_none();
+  ObbRec r = obb_load(a.boxes + idx * a.stride);
+  const float sc = a.scores[idx];
+  if ((r.flags & OB_VALID) ? sc > a.score_thr : false) r.flags |= OB_CAND;
+  r.group = a.groups ? a.groups[idx] : 0;
+  return r;
+}
+
+// candidate test alone (the reduce launch): score > score_thr and both sides >= 0.001, the rule of nms_load's flag for finite boxes; a non-finite box has no IoU
+// with anything and is no candidate either
+__device__ __forceinline__ bool nms_candidate(const NmsArgs& a, int rank) {
+  if (rank >= a.N) return false;
+  const int64_t idx = a.order[rank];
+  if (idx < 0 || idx >= a.N) return false;
+  const float* b = a.boxes + idx * a.stride;
+  const float cx = b[0], cy = b[1], w = b[2], h = b[3], th = b[4];
+  const float hw = 0.5f * w, hh = 0.5f * h;
+  const bool finite = isfinite(cx) && isfinite(cy) && isfinite(w) && isfinite(h) && isfinite(th) && isfinite(sqrtf(hw * hw + hh * hh));
+  return finite && w >= OB_MIN_SIDE && h >= OB_MIN_SIDE && a.scores[idx] > a.score_thr;
+}
+
+__global__ __launch_bounds__(256) void obb_nms_mask_kernel(NmsArgs a) {
+  const int rb = blockIdx.y, cb = blockIdx.x;
+  if (cb < rb) return;          // below the diagonal: never read
+  __shared__ ObbRec rows[64], cols[64];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  if (tid < 64) rows[tid] = nms_load(a, rb * 64 + tid);
+  else if (tid < 128) cols[tid - 64] = nms_load(a, cb * 64 + tid - 64);
+  __syncthreads();
+  const ObbRec q = cols[lane];
+  const int qrank = cb * 64 + lane;
+#pragma unroll 1
+  for (int i = 0; i < 16; ++i) {
+    const int r = wv * 16 + i, rrank = rb * 64 + r;
+    if (rrank >= a.N) break;          // (wave-uniform)
+    const ObbRec p = rows[r];
+    bool sup = false;
+    if ((p.flags & q.flags & OB_CAND) && qrank > rrank && p.group == q.group) sup = obb_pair(p, q, LMV_OBB_IOU) > a.iou_thr;
+    const unsigned long long word = __ballot(sup);
+    if (lane == 0) a.mask[(int64_t)rrank * a.nb + cb] = word;
+  }
+}
+
+__global__ __launch_bounds__(256) void obb_nms_reduce_kernel(NmsArgs a) {
+  __shared__ unsigned long long cur_sh, kept_sh;
+  __shared__ int scan[256];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int N = a.N, nb = a.nb;
+  // removed bits to start with: ranks past N and non-candidates.  Wave w builds words w, w + 4, ...; thread c then takes word c.
+  __shared__ unsigned long long init[256];
+  for (int w = wv; w < nb; w += 4) {
+    const unsigned long long word = __ballot(!nms_candidate(a, w * 64 + lane));
+    if (lane == 0) init[w] = word;
+  }
+  __syncthreads();
+  unsigned long long mine = tid < nb ? init[tid] : ~0ull;
+  for (int b = 0; b < nb; ++b) {
+    const int nrows = min(64, N - b * 64);
+    // this thread's column of the block's rows: independent loads, in flight during the serial part
+    unsigned long long wrow[64];
+    const bool active = tid > b && tid < nb;
+    const unsigned long long* src = a.mask + (int64_t)b * 64 * nb + tid;
+#pragma unroll
+    for (int r = 0; r < 64; ++r) wrow[r] = (active && r < nrows) ? src[(int64_t)r * nb] : 0ull;
+    if (tid == b) cur_sh = mine;
+    unsigned long long dword = 0ull;          // wave 0: lane r holds the diagonal word of row r
+    if (tid < nrows) dword = a.mask[((int64_t)b * 64 + tid) * nb + b];
+    __syncthreads();
+    if (wv == 0) {
+      // the serial part on the scalar unit: `cur` is wave-uniform, row r's word comes out of lane r's registers (a constant lane: v_readlane), no memory in the chain
+      const unsigned long long c0 = cur_sh;
+      // (the builtins return int: every half goes through `unsigned` before it is widened, or a set bit 31 would smear over the upper word)
+      unsigned long long cur = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(c0 >> 32)) << 32) |
+                               (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)c0);
+      const int dlo = (int)(unsigned)dword, dhi = (int)(unsigned)(dword >> 32);
+#pragma unroll
+      for (int r = 0; r < 64; ++r) {
+        const unsigned long long w = ((unsigned long long)(unsigned)__builtin_amdgcn_readlane(dhi, r) << 32) | (unsigned long long)(unsigned)__builtin_amdgcn_readlane(dlo, r);
+        if (!((cur >> r) & 1ull)) cur |= w;          // row r is kept: it removes what it overlaps (bits above r only)
+      }
+      if (lane == 0) kept_sh = ~cur;
+    }
+    __syncthreads();
+    const unsigned long long kept = kept_sh;
+    if (tid == b) mine = ~kept;
+    unsigned long long acc = 0ull;
+#pragma unroll
+    for (int r = 0; r < 64; ++r) acc |= ((kept >> r) & 1ull) ? wrow[r] : 0ull;
+    mine |= acc;
+  }
+  // kept ranks in rank order -> keep[0 .. count), -1 behind
+  const unsigned long long keptw = tid < nb ? ~mine : 0ull;
+  scan[tid] = __popcll(keptw);
+  __syncthreads();
+  for (int o = 1; o < 256; o <<= 1) {
+    const int v = tid >= o ? scan[tid - o] : 0;
+    __syncthreads();
+    scan[tid] += v;
+    __syncthreads();
+  }
+  const int total = scan[255];
+  int pos = scan[tid] - __popcll(keptw);
+  unsigned long long k = keptw;
+  while (k) {
+    const int r = __ffsll((long long)k) - 1;
+    k &= k - 1;
+    if (pos < a.cap) a.keep[pos] = a.order[tid * 64 + r];
+    ++pos;
+  }
+  const int written = min(total, a.cap);
+  for (int i = written + tid; i < a.cap; i += 256) a.keep[i] = -1;
+  if (tid == 0) *a.count = written;
+}
+
+int obb_check_boxes(const char* fn, const char* what, const float* b, int stride, int n) {
+  if (n < 0) LMV_FAIL(LMV_ERR_SHAPE, "%s: %d %s (a negative size)", fn, n, what);
+  if (stride < 5) LMV_FAIL(LMV_ERR_SHAPE, "%s: %s: a row stride of %d floats (at least 5: cx, cy, w, h, theta)", fn, what, stride);
+  if (n > 0 && !b) LMV_FAIL(LMV_ERR_SHAPE, "%s: null %s", fn, what);
+  if (((uintptr_t)b) & 3u) LMV_FAIL(LMV_ERR_SHAPE, "%s: misaligned %s", fn, what);
+  return LMV_OK;
+}
+
+}  // namespace
+
+extern "C" int lmv_obb_overlaps(const float* b1, int stride1, int N, const float* b2, int stride2, int M, int mode, int aligned, float* out, void* stream) {
+  const char* fn = "obb_overlaps";
+  if (int rc = obb_check_boxes(fn, "boxes1", b1, stride1, N)) return rc;
+  if (int rc = obb_check_boxes(fn, "boxes2", b2, stride2, M)) return rc;
+  if (mode != LMV_OBB_IOU && mode != LMV_OBB_IOF) LMV_FAIL(LMV_ERR_SHAPE, "%s: unknown mode %d (LMV_OBB_IOU / LMV_OBB_IOF)", fn, mode);
+  if (aligned != 0 && aligned != 1) LMV_FAIL(LMV_ERR_SHAPE, "%s: aligned = %d is neither 0 nor 1", fn, aligned);
+  if (aligned && N != M) LMV_FAIL(LMV_ERR_SHAPE, "%s: aligned pairs need N == M, got %d and %d", fn, N, M);
+  if (N > LMV_OBB_MAX_BOXES || M > LMV_OBB_MAX_BOXES) LMV_FAIL(LMV_ERR_SHAPE, "%s: %d x %d boxes: more than %d on a side", fn, N, M, LMV_OBB_MAX_BOXES);
+  if (((uintptr_t)out) & 3u) LMV_FAIL(LMV_ERR_SHAPE, "%s: misaligned out", fn);
+  if (N == 0 || M == 0) return LMV_OK;
+  if (!out) LMV_FAIL(LMV_ERR_SHAPE, "%s: null out", fn);
+  if (aligned) {
+    hipLaunchKernelGGL(obb_overlaps_aligned_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, (hipStream_t)stream, b1, stride1, b2, stride2, N, mode, out);
+  } else {
+    const dim3 grid((unsigned)((N + OB_TN - 1) / OB_TN), (unsigned)((M + OB_TM - 1) / OB_TM));
+    hipLaunchKernelGGL(obb_overlaps_kernel, grid, dim3(256), 0, (hipStream_t)stream, b1, stride1, N, b2, stride2, M, mode, out);
+  }
+  LMV_CHECK_LAUNCH(fn);
+  return LMV_OK;
+}
+
+extern "C" size_t lmv_obb_nms_workspace_bytes(int N) {
+  if (N < 0 || N > LMV_OBB_NMS_MAX) return 0;
+  return (size_t)N * (size_t)((N + 63) / 64) * 8;
+}
+
+extern "C" int lmv_obb_nms(const float* boxes, int stride, const float* scores, const int64_t* order, const int32_t* groups, int N, float iou_thr, float score_thr,
+                           int max_num, int phases, void* workspace, size_t workspace_bytes, int64_t* keep, int64_t* count, void* stream) {
+  const char* fn = "obb_nms";
+  if (int rc = obb_check_boxes(fn, "boxes", boxes, stride, N)) return rc;
+  if (N > LMV_OBB_NMS_MAX) LMV_FAIL(LMV_ERR_SHAPE, "%s: N = %d boxes, at most %d", fn, N, LMV_OBB_NMS_MAX);
+  if (max_num < 0) LMV_FAIL(LMV_ERR_SHAPE, "%s: max_num = %d < 0 (0: no limit)", fn, max_num);
+  if (iou_thr != iou_thr || score_thr != score_thr) LMV_FAIL(LMV_ERR_SHAPE, "%s: a NaN threshold (iou_thr = %g, score_thr = %g)", fn, iou_thr, score_thr);
+  if (phases < 1 || phases > 3) LMV_FAIL(LMV_ERR_SHAPE, "%s: phases = %d outside 1 .. 3 (1: mask launch, 2: reduce launch, 3: both)", fn, phases);
+  if (N > 0 && (!scores || !order)) LMV_FAIL(LMV_ERR_SHAPE, "%s: null scores / order", fn);
+  if (!count) LMV_FAIL(LMV_ERR_SHAPE, "%s: null count", fn);
+  const int cap = max_num > 0 ? max_num : N;
+  if (cap > 0 && !keep) LMV_FAIL(LMV_ERR_SHAPE, "%s: null keep", fn);
+  if ((((uintptr_t)scores) & 3u) || (((uintptr_t)groups) & 3u) || (((uintptr_t)order) & 7u) || (((uintptr_t)keep) & 7u) || (((uintptr_t)count) & 7u) ||
+      (((uintptr_t)workspace) & 7u))
+    LMV_FAIL(LMV_ERR_SHAPE, "%s: misaligned buffer", fn);
+  const size_t need = lmv_obb_nms_workspace_bytes(N);
+  if (workspace_bytes < need || (need > 0 && !workspace)) LMV_FAIL(LMV_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed (lmv_obb_nms_workspace_bytes)", fn, workspace_bytes, need);
+  hipStream_t st = (hipStream_t)stream;
+  if (N == 0) {          // no launch: count = 0, keep = -1 throughout
+    if (hipMemsetAsync(count, 0, sizeof(int64_t), st) != hipSuccess) LMV_FAIL(LMV_ERR_LAUNCH, "%s: cannot clear count", fn);
+    if (cap > 0 && hipMemsetAsync(keep, 0xff, (size_t)cap * sizeof(int64_t), st) != hipSuccess) LMV_FAIL(LMV_ERR_LAUNCH, "%s: cannot fill keep", fn);
+    return LMV_OK;
+  }
+  NmsArgs a;
+  a.boxes = boxes; a.stride = stride; a.scores = scores; a.order = order; a.groups = groups;
+  a.N = N; a.nb = (N + 63) / 64; a.iou_thr = iou_thr; a.score_thr = score_thr; a.cap = cap;
+  a.mask = reinterpret_cast<unsigned long long*>(workspace); a.keep = keep; a.count = count;
+  if (phases & 1) hipLaunchKernelGGL(obb_nms_mask_kernel, dim3((unsigned)a.nb, (unsigned)a.nb), dim3(256), 0, st, a);
+  if (phases & 2) hipLaunchKernelGGL(obb_nms_reduce_kernel, dim3(1), dim3(256), 0, st, a);
+  LMV_CHECK_LAUNCH(fn);
+  return LMV_OK;
+}

@@ -9,6 +9,16 @@ no ``nonzero``, no index copies, no host synchronisation, no floating-point atom
 Not supported: ``sample_num=0`` (the reference's adaptive grid: it raises), gradients for the RoIs, double backward, more than 5 levels.
 ``reference_rroi_align`` is the numpy float64 oracle (forward and adjoint); ``rroi_align_torch`` is the literal stock-PyTorch formulation, which the tests use
 as their fp32 comparator and the probe as its other side.  include/lemevit_hip.h has the formulas.
+
+Rotated IoU and rotated NMS (csrc/obb.hip), the other two custom operators of those configs, under the reference's names and signatures:
+
+    from lemevit_amd.detection import obb_overlaps, obb_nms, arb_batched_nms          # mmdet/ops/box_iou_rotated, mmdet/ops/nms_rotated
+    keep, count = obb_nms_padded(boxes, scores, 0.1, groups=labels, score_thr=0.05, max_num=2000)          # no synchronisation, capturable
+
+Two deliberate differences from the reference: classes are separated by ``groups`` (exact), not by adding ``class_id * (max_coordinate + 1)`` to the centres in
+fp32 (which moves an IoU by about 1e-5); and the values are right where the reference's 24-point / Graham-scan routine breaks down, e.g. 1.0, not 0.25, for a box
+against its theta + pi duplicate.  Not provided: ``poly_nms``, ``BT_nms``, the differentiable aligned IoU, horizontal NMS, fp16 / bf16 boxes, N > 16 384.
+``reference_obb_overlaps`` / ``reference_obb_nms`` are the numpy float64 oracles, ``obb_overlaps_torch`` / ``obb_nms_torch`` the stock-PyTorch formulations.
 """
 from __future__ import annotations
 
@@ -274,3 +284,245 @@ def rroi_align_torch(feats: Sequence[Tensor], rois: Tensor, out_size, spatial_sc
         else:
             out = out + sum(x.view(-1)[0] for x in feats[l:l + 1]) * 0.0          # (upstream keeps every level in the graph)
     return out
+
+
+# -------------------------------------------------------------------------------------------
+# Rotated IoU and rotated NMS (csrc/obb.hip): the reference's obb_overlaps / obb_nms / arb_batched_nms
+# -------------------------------------------------------------------------------------------
+OBB_MIN_SIDE = 0.001          # the reference wrapper's "too small" rule: a box with min(w, h) below it overlaps nothing and is no NMS candidate
+
+
+def _obb_clip_area(xp, cx1, cy1, w1, h1, t1, cx2, cy2, w2, h2, t2):
+    """Area of the intersection of two rotated boxes (arrays that broadcast), in the arrays' own precision, with the operations ``xp`` (numpy or torch) provides.
+    Box 1 is expressed in the frame of box 2, where box 2 is the rectangle |u| <= W, |v| <= H; every edge of box 1 is clipped to the strip |v| <= H and to the
+    lines u = -W and u = +W, and the area is the boundary integral of clamp(u, -W, W) dv over the clipped pieces (on each piece the integrand is linear: a
+    trapezoid is exact).  Duplicates, shared edges and containment are ordinary inputs: nothing is sorted and no vertex is counted."""
+    c1, s1, c2, s2 = xp.cos(t1), xp.sin(t1), xp.cos(t2), xp.sin(t2)
+    dx, dy = cx1 - cx2, cy1 - cy2
+    cu, cv = dx * c2 - dy * s2, dx * s2 + dy * c2
+    cr, sr = c1 * c2 + s1 * s2, s1 * c2 - c1 * s2
+    hw, hh, W, H = 0.5 * w1, 0.5 * h1, 0.5 * w2 + 0.0 * cu, 0.5 * h2 + 0.0 * cu          # (W, H take the broadcast shape)
+    wu, wv, hu, hv = hw * cr, -hw * sr, hh * sr, hh * cr
+    us = (cu + wu + hu, cu - wu + hu, cu - wu - hu, cu + wu - hu)          # counter-clockwise in (u, v)
+    vs = (cv + wv + hv, cv - wv + hv, cv - wv - hv, cv + wv - hv)
+
+    def clamp(x, lo, hi):
+        return xp.minimum(xp.maximum(x, lo), hi)
+
+    zero, one = 0.0 * cu, 0.0 * cu + 1.0
+    area = zero
+    for k in range(4):
+        u0, v0, u1, v1 = us[k], vs[k], us[(k + 1) % 4], vs[(k + 1) % 4]
+        du, dv = u1 - u0, v1 - v0
+        sdv, sdu = xp.where(dv == 0, one, dv), xp.where(du == 0, one, du)
+        ta, tb = (-H - v0) / sdv, (H - v0) / sdv
+        t0, t3 = clamp(xp.minimum(ta, tb), zero, one), clamp(xp.maximum(ta, tb), zero, one)
+        ba, bb = (-W - u0) / sdu, (W - u0) / sdu
+        tl = xp.where(du == 0, t0, clamp(xp.minimum(ba, bb), t0, t3))
+        th = xp.where(du == 0, t3, clamp(xp.maximum(ba, bb), t0, t3))
+        f0, f1, f2, f3 = [clamp(u0 + t * du, -W, W) for t in (t0, tl, th, t3)]
+        area = area + 0.5 * dv * ((tl - t0) * (f0 + f1) + (th - tl) * (f1 + f2) + (t3 - th) * (f2 + f3))
+    return area
+
+
+def _obb_ratio(xp, inter, a1, a2, mode):
+    inter = xp.minimum(xp.maximum(inter, 0.0 * inter), xp.minimum(a1, a2) + 0.0 * inter)
+    return inter / (a1 + a2 - inter) if mode == "iou" else inter / (a1 + 0.0 * inter)
+
+
+def _obb_np(b, what):
+    b = b.detach().double().cpu().numpy() if isinstance(b, torch.Tensor) else np.asarray(b, dtype=np.float64)
+    if b.ndim != 2 or b.shape[1] < 5:
+        raise ValueError(f"{what}: [N, >= 5] rows (cx, cy, w, h, theta) expected, got {b.shape}")
+    return b[:, :5]
+
+
+def reference_obb_overlaps(bboxes1, bboxes2, mode: str = "iou", is_aligned: bool = False) -> np.ndarray:
+    """The numpy float64 oracle of ``obb_overlaps``: [N, M] (or [N, 1] with ``is_aligned``).  Only pairs whose bounding circles meet are evaluated (all others are
+    exactly 0), by clipping (``_obb_clip_area``).  A box with a non-finite entry or with min(w, h) < 0.001 gives 0 against everything."""
+    if mode not in ("iou", "iof"):
+        raise ValueError(f"reference_obb_overlaps: mode must be 'iou' or 'iof', got {mode!r}")
+    b1, b2 = _obb_np(bboxes1, "bboxes1"), _obb_np(bboxes2, "bboxes2")
+    N, M = len(b1), len(b2)
+    if is_aligned and N != M:
+        raise ValueError("reference_obb_overlaps: aligned pairs need as many boxes on both sides")
+    with np.errstate(invalid="ignore"):
+        ok1 = np.isfinite(b1).all(1) & (b1[:, 2] >= OBB_MIN_SIDE) & (b1[:, 3] >= OBB_MIN_SIDE)
+        ok2 = np.isfinite(b2).all(1) & (b2[:, 2] >= OBB_MIN_SIDE) & (b2[:, 3] >= OBB_MIN_SIDE)
+    r1, r2 = 0.5 * np.hypot(b1[:, 2], b1[:, 3]), 0.5 * np.hypot(b2[:, 2], b2[:, 3])
+
+    def pairs(i, j):
+        p, q = b1[i], b2[j]
+        with np.errstate(all="ignore"):
+            inter = _obb_clip_area(np, p[:, 0], p[:, 1], p[:, 2], p[:, 3], p[:, 4], q[:, 0], q[:, 1], q[:, 2], q[:, 3], q[:, 4])
+            v = _obb_ratio(np, inter, p[:, 2] * p[:, 3], q[:, 2] * q[:, 3], mode)
+        return np.where(np.isfinite(v), v, 0.0)
+
+    if is_aligned:
+        out = np.zeros((N, 1))
+        i = np.nonzero(ok1 & ok2)[0]
+        out[i, 0] = pairs(i, i)
+        return out
+    out = np.zeros((N, M))
+    for lo in range(0, N, 512):
+        hi = min(N, lo + 512)
+        with np.errstate(all="ignore"):
+            d2 = (b1[lo:hi, None, 0] - b2[None, :, 0]) ** 2 + (b1[lo:hi, None, 1] - b2[None, :, 1]) ** 2
+            meet = (d2 <= (r1[lo:hi, None] + r2[None, :]) ** 2) & ok1[lo:hi, None] & ok2[None, :]
+        i, j = np.nonzero(meet)
+        out[lo + i, j] = pairs(lo + i, j)
+    return out
+
+
+def reference_obb_nms(boxes, scores, iou_thr: float, groups=None, score_thr=None, max_num=None, iou=None) -> np.ndarray:
+    """The oracle of ``obb_nms`` / ``obb_nms_padded``: greedy NMS on the float64 IoU matrix (``iou``: that matrix, when the caller has it).  Candidates: ``score >
+    score_thr`` (default -inf: NaN and -inf scores are none) and min(w, h) >= 0.001; ranks by descending score, ties by ascending index; a kept box suppresses the
+    lower-ranked candidates of its group with ``IoU > iou_thr``.  Returns the kept original indices in rank order (int64), at most ``max_num``."""
+    b = _obb_np(boxes, "boxes")
+    s = scores.detach().double().cpu().numpy() if isinstance(scores, torch.Tensor) else np.asarray(scores, dtype=np.float64)
+    N = len(b)
+    g = np.zeros(N, dtype=np.int64) if groups is None else (groups.cpu().numpy() if isinstance(groups, torch.Tensor) else np.asarray(groups)).astype(np.int64)
+    thr = -np.inf if score_thr is None else float(score_thr)
+    with np.errstate(invalid="ignore"):
+        cand = (s > thr) & np.isfinite(b).all(1) & (b[:, 2] >= OBB_MIN_SIDE) & (b[:, 3] >= OBB_MIN_SIDE)
+    if iou is None:
+        iou = reference_obb_overlaps(b, b)
+    order = np.argsort(-np.where(np.isnan(s), -np.inf, s), kind="stable")
+    alive = cand.copy()
+    keep = []
+    for i in order:
+        if not alive[i]:
+            continue
+        keep.append(i)
+        alive[i] = False
+        alive &= ~((iou[i] > iou_thr) & (g == g[i]))
+    keep = np.asarray(keep, dtype=np.int64)
+    return keep if not max_num else keep[:int(max_num)]
+
+
+def obb_overlaps_torch(bboxes1: Tensor, bboxes2: Tensor, mode: str = "iou", is_aligned: bool = False) -> Tensor:
+    """What a user would write in stock PyTorch: the whole [N, M] matrix (or the N aligned pairs) by broadcasting, in the boxes' dtype (float32), ``torch.cos`` /
+    ``torch.sin`` per box, no loop and no custom kernel -- about forty elementwise launches over N x M temporaries.  Works on any device."""
+    b1, b2 = bboxes1[:, :5], bboxes2[:, :5]
+    p = [b1[:, k] for k in range(5)] if is_aligned else [b1[:, None, k] for k in range(5)]
+    q = [b2[:, k] for k in range(5)] if is_aligned else [b2[None, :, k] for k in range(5)]
+    inter = _obb_clip_area(torch, *p, *q)
+    v = _obb_ratio(torch, inter, p[2] * p[3], q[2] * q[3], mode)
+    ok1 = torch.isfinite(b1).all(1) & (b1[:, 2] >= OBB_MIN_SIDE) & (b1[:, 3] >= OBB_MIN_SIDE)
+    ok2 = torch.isfinite(b2).all(1) & (b2[:, 2] >= OBB_MIN_SIDE) & (b2[:, 3] >= OBB_MIN_SIDE)
+    ok = (ok1 & ok2) if is_aligned else (ok1[:, None] & ok2[None, :])
+    v = torch.where(ok & torch.isfinite(v), v, torch.zeros_like(v))
+    return v[:, None] if is_aligned else v
+
+
+def obb_nms_torch(boxes: Tensor, scores: Tensor, iou_thr: float, groups: Optional[Tensor] = None, score_thr: Optional[float] = None,
+                  max_num: Optional[int] = None) -> Tensor:
+    """The stock formulation of rotated NMS: sort, the fp32 IoU matrix of the sorted boxes (``obb_overlaps_torch``), the suppression mask copied to the host and the
+    greedy scan there -- what the reference's CUDA path does with its N x N / 64 mask.  Returns the kept original indices (int64, on the boxes' device)."""
+    N = boxes.shape[0]
+    if N == 0:
+        return torch.zeros(0, dtype=torch.int64, device=boxes.device)
+    thr = -math.inf if score_thr is None else float(score_thr)
+    order = torch.sort(scores, descending=True, stable=True)[1]
+    b, s = boxes[order, :5], scores[order]
+    cand = (s > thr) & (b[:, 2] >= OBB_MIN_SIDE) & (b[:, 3] >= OBB_MIN_SIDE) & torch.isfinite(b).all(1)
+    mask = obb_overlaps_torch(b, b) > iou_thr
+    if groups is not None:
+        g = groups[order]
+        mask &= g[:, None] == g[None, :]
+    mask_h, cand_h = mask.cpu().numpy(), cand.cpu().numpy()          # the synchronisation and the copy the reference pays per call
+    removed = ~cand_h
+    keep = []
+    for i in range(N):
+        if removed[i]:
+            continue
+        keep.append(i)
+        removed[i + 1:] |= mask_h[i, i + 1:]
+    keep = order[torch.as_tensor(keep, dtype=torch.int64, device=boxes.device)]
+    return keep if not max_num else keep[:int(max_num)]
+
+
+def obb_overlaps(bboxes1, bboxes2, mode: str = "iou", is_aligned: bool = False, device_id=None):
+    """The reference's ``obb_overlaps(bboxes1, bboxes2, mode='iou', is_aligned=False, device_id=None)`` on the native kernel: tensors (on the GPU) or numpy arrays
+    (moved to ``cuda:device_id``, the current device by default, and returned as numpy) of rows ``(cx, cy, w, h, theta)``.  [N, M], or [N, 1] with ``is_aligned``;
+    an empty side gives the reference's empty shapes.  There is no gradient: a box tensor that requires grad raises (the reference's differentiable aligned path is
+    not provided)."""
+    if mode not in ("iou", "iof"):
+        raise ValueError(f"obb_overlaps: mode must be 'iou' or 'iof', got {mode!r}")
+    if type(bboxes1) is not type(bboxes2):
+        raise TypeError(f"obb_overlaps: both box sets must be of one type, got {type(bboxes1)} and {type(bboxes2)}")
+    is_numpy = isinstance(bboxes1, np.ndarray)
+    if not is_numpy and not isinstance(bboxes1, torch.Tensor):
+        raise TypeError(f"bboxes must be either a Tensor or numpy array, but got {type(bboxes1)}")
+    if is_aligned and bboxes1.shape[0] != bboxes2.shape[0]:
+        raise ValueError("obb_overlaps: is_aligned needs as many boxes on both sides")
+    if not is_numpy and (bboxes1.requires_grad or bboxes2.requires_grad):
+        raise RuntimeError("obb_overlaps: there is no gradient for the boxes (detach them; the differentiable aligned IoU is not provided)")
+    rows, cols = bboxes1.shape[0], bboxes2.shape[0]
+    if rows == 0 or cols == 0:          # (no launch; works without a GPU)
+        shape = (rows, 1) if is_aligned else (rows, cols)
+        return np.zeros(shape, dtype=np.float32) if is_numpy else bboxes1.new_zeros(shape, dtype=torch.float32)
+    if is_numpy:
+        dev = torch.device("cuda", torch.cuda.current_device() if device_id is None else int(device_id))
+        t1, t2 = torch.from_numpy(bboxes1).float().to(dev), torch.from_numpy(bboxes2).float().to(dev)
+    else:
+        t1, t2 = bboxes1.float(), bboxes2.float()
+    out = ops.obb_overlaps(t1[:, :5], t2[:, :5], mode, is_aligned)
+    return out.cpu().numpy() if is_numpy else out
+
+
+def obb_nms_padded(boxes: Tensor, scores: Tensor, iou_thr: float, groups: Optional[Tensor] = None, score_thr: Optional[float] = None,
+                   max_num: Optional[int] = None) -> Tuple[Tensor, Tensor]:
+    """Rotated NMS without a synchronisation: ``(keep, count)`` with ``keep`` int64 [max_num or N] -- the original indices of the kept boxes by descending score,
+    then -1 -- and ``count`` int64 [1].  ``boxes`` float32 [N, >= 5] are read in place.  Capturable after one eager call per shape.  With ``scores`` [R * K]
+    flattened, the boxes repeated per class and ``groups`` = the class id, this is the test-time multiclass NMS (``score_thr=0.05``, ``max_per_img=2000``) without
+    its ``nonzero``."""
+    if boxes.requires_grad or scores.requires_grad:
+        boxes, scores = boxes.detach(), scores.detach()
+    if groups is not None and groups.dtype != torch.int32:
+        groups = groups.to(torch.int32)
+    return ops.obb_nms(boxes.float(), scores.float(), iou_thr, groups, score_thr, max_num)
+
+
+def obb_nms(dets, iou_thr: float, device_id=None):
+    """The reference's ``obb_nms(dets, iou_thr, device_id=None) -> (dets[inds], inds)``: ``dets`` [N, 6] rows ``(cx, cy, w, h, theta, score)``, a tensor on the GPU or
+    a numpy array (moved to ``cuda:device_id``, the current device by default; numpy out).  One synchronisation, for the dynamic length."""
+    is_numpy = isinstance(dets, np.ndarray)
+    if not is_numpy and not isinstance(dets, torch.Tensor):
+        raise TypeError(f"dets must be eithr a Tensor or numpy array, but got {type(dets)}")
+    if dets.ndim != 2 or dets.shape[1] != 6:
+        raise ValueError(f"obb_nms: dets must be [N, 6] (cx, cy, w, h, theta, score), got {tuple(dets.shape)}")
+    if dets.shape[0] == 0:
+        inds = np.zeros(0, dtype=np.int64) if is_numpy else dets.new_zeros(0, dtype=torch.int64)
+        return dets[inds, :], inds
+    if is_numpy:
+        t = torch.from_numpy(dets).float().to(torch.device("cuda", torch.cuda.current_device() if device_id is None else int(device_id)))
+    else:
+        t = dets.detach().float()
+    keep, count = ops.obb_nms(t, t[:, 5], iou_thr)
+    inds = keep[:int(count.item())]
+    if is_numpy:
+        inds = inds.cpu().numpy()
+    return dets[inds, :], inds
+
+
+def arb_batched_nms(bboxes: Tensor, scores: Tensor, inds: Tensor, nms_cfg: dict, class_agnostic: bool = False):
+    """The reference's ``arb_batched_nms(bboxes, scores, inds, nms_cfg, class_agnostic=False) -> (dets [K, 6], keep)`` for 5-column boxes and ``type='obb_nms'``.
+    Classes are separated by ``groups = inds`` (exact; cross-class pairs cost no IoU), not by adding ``inds * (max_coordinate + 1)`` to the centres."""
+    cfg = dict(nms_cfg)
+    class_agnostic = cfg.pop("class_agnostic", class_agnostic)
+    nms_type = cfg.pop("type", "BT_nms")
+    if nms_type != "obb_nms":
+        raise NotImplementedError(f"arb_batched_nms: type={nms_type!r} is not supported (only 'obb_nms'; poly_nms, BT_nms and the horizontal nms are not provided)")
+    if bboxes.dim() != 2 or bboxes.size(-1) != 5:
+        raise NotImplementedError(f"arb_batched_nms: boxes of {bboxes.size(-1)} columns are not supported (only 5: cx, cy, w, h, theta; horizontal 4-column and "
+                                  "polygon 8-column boxes are not provided)")
+    iou_thr = cfg.pop("iou_thr")
+    if cfg:
+        raise TypeError(f"arb_batched_nms: unexpected nms_cfg entries {sorted(cfg)}")
+    if bboxes.shape[0] == 0:
+        keep = bboxes.new_zeros(0, dtype=torch.int64)
+    else:
+        k, count = ops.obb_nms(bboxes.detach().float(), scores.detach().float(), iou_thr, None if class_agnostic else inds.to(torch.int32).contiguous())
+        keep = k[:int(count.item())]
+    return torch.cat([bboxes[keep], scores[keep][:, None]], -1), keep

@@ -1396,6 +1396,98 @@ def rroi_align_bwd(grad_out: Tensor, plan: RroiPlan, like: Sequence[Tensor], dx:
 
 
 # -------------------------------------------------------------------------------------------
+# Rotated IoU and rotated NMS (csrc/obb.hip; lemevit_amd/detection.py has the reference's entry points)
+# -------------------------------------------------------------------------------------------
+def _obb_boxes(fn: str, what: str, t: Tensor) -> Tuple[int, int]:
+    """(data pointer, row stride in floats) of a float32 box tensor [N, >= 5] read in place: unit column stride, any row stride >= 5 (``dets[:, :5]`` of a [N, 6] tensor)"""
+    if t.dim() != 2 or t.shape[1] < 5 or t.dtype != torch.float32:
+        raise ValueError(f"{fn}: {what}: float32 [N, >= 5] rows (cx, cy, w, h, theta) expected, got {t.dtype} {tuple(t.shape)}")
+    if not t.is_cuda:
+        raise RuntimeError("lemevit_amd: tensors must be on the GPU (no CPU fallback exists)")
+    n = int(t.shape[0])
+    if n > 1 and (t.stride(1) != 1 or t.stride(0) < 5):
+        raise ValueError(f"{fn}: {what}: strides {tuple(t.stride())}: a unit column stride and a row stride >= 5 are needed (call .contiguous())")
+    if n == 1 and t.stride(1) != 1:
+        raise ValueError(f"{fn}: {what}: strides {tuple(t.stride())}: a unit column stride is needed (call .contiguous())")
+    return t.data_ptr(), (int(t.stride(0)) if n > 1 else max(int(t.stride(0)), 5))
+
+
+def obb_overlaps(boxes1: Tensor, boxes2: Tensor, mode: str = "iou", is_aligned: bool = False, out: Optional[Tensor] = None) -> Tensor:
+    """lmv_obb_overlaps (one launch): rotated IoU (``mode='iou'``) or IoF (``'iof'``: intersection over the area of ``boxes1``) of float32 boxes
+    ``(cx, cy, w, h, theta)``, theta in radians.  Returns float32 [N, M], or [N, 1] from the N pairs with ``is_aligned``; every element is written once.  ``out``: a
+    caller-supplied contiguous buffer of that shape (a captured call allocates nothing).  include/lemevit_hip.h has the rule."""
+    fn = "obb_overlaps"
+    if mode not in ("iou", "iof"):
+        raise ValueError(f"{fn}: mode must be 'iou' or 'iof', got {mode!r}")
+    p1, s1 = _obb_boxes(fn, "boxes1", boxes1)
+    p2, s2 = _obb_boxes(fn, "boxes2", boxes2)
+    N, M = int(boxes1.shape[0]), int(boxes2.shape[0])
+    if is_aligned and N != M:
+        raise ValueError(f"{fn}: aligned pairs need as many boxes on both sides, got {N} and {M}")
+    if boxes2.device != boxes1.device:
+        raise ValueError(f"{fn}: the two box tensors are on different devices")
+    shape = (N, 1) if is_aligned else (N, M)
+    if out is None:
+        out = torch.empty(shape, device=boxes1.device, dtype=torch.float32)
+    elif out.dtype != torch.float32 or tuple(out.shape) != shape or out.device != boxes1.device or not out.is_contiguous():
+        raise TypeError(f"{fn}: out must be a contiguous float32 tensor {shape} on the boxes' device")
+    check(lib.lmv_obb_overlaps(p1, s1, N, p2, s2, M, _lib.OBB_IOF if mode == "iof" else _lib.OBB_IOU, 1 if is_aligned else 0, out.data_ptr(), _stream()), "lmv_obb_overlaps")
+    return out
+
+
+def obb_nms_workspace_bytes(N: int) -> int:
+    """lmv_obb_nms_workspace_bytes: N ceil(N / 64) 8 bytes, the suppression words of ``obb_nms`` (N <= 16 384)"""
+    if not 0 <= int(N) <= _lib.OBB_NMS_MAX:
+        raise ValueError(f"obb_nms_workspace_bytes: N = {N} outside 0 .. {_lib.OBB_NMS_MAX}")
+    return int(lib.lmv_obb_nms_workspace_bytes(int(N)))
+
+
+def obb_nms(boxes: Tensor, scores: Tensor, iou_thr: float, groups: Optional[Tensor] = None, score_thr: Optional[float] = None, max_num: Optional[int] = None,
+            order: Optional[Tensor] = None, workspace: Optional[Tensor] = None, keep: Optional[Tensor] = None, count: Optional[Tensor] = None,
+            phases: int = 3) -> Tuple[Tensor, Tensor]:
+    """lmv_obb_nms (two launches, no host round trip): greedy rotated NMS of float32 ``boxes`` [N, >= 5] (read in place through their row stride) with float32
+    ``scores`` [N].  ``groups``: int32 [N]; boxes of different groups never suppress each other.  A box is a candidate iff ``score > score_thr`` (default -inf) and
+    both sides are >= 0.001; a kept box suppresses the lower-ranked candidates of its group with ``IoU > iou_thr``.  Returns ``(keep, count)``: ``keep`` int64 [cap],
+    ``cap = max_num or N``, the original indices of the kept boxes by descending score (ties: the lower index first), then -1; ``count`` int64 [1], the number
+    written.  The sort is ``torch.sort(stable=True)`` here (``order``: the caller's, int64 [N]); ``workspace`` (uint8, ``obb_nms_workspace_bytes(N)``), ``keep``
+    and ``count`` may be supplied so that a captured call allocates only what the sort does.  ``phases``: 1 / 2 run the mask / reduce launch alone (probes)."""
+    fn = "obb_nms"
+    p, s = _obb_boxes(fn, "boxes", boxes)
+    N, dev = int(boxes.shape[0]), boxes.device
+    if N > _lib.OBB_NMS_MAX:
+        raise ValueError(f"{fn}: N = {N} boxes, at most {_lib.OBB_NMS_MAX}")
+    if scores.dtype != torch.float32 or tuple(scores.shape) != (N,) or scores.device != dev:
+        raise ValueError(f"{fn}: float32 scores [{N}] on the boxes' device expected, got {scores.dtype} {tuple(scores.shape)}")
+    scores = scores.contiguous()
+    if groups is not None and (groups.dtype != torch.int32 or tuple(groups.shape) != (N,) or groups.device != dev or not groups.is_contiguous()):
+        raise TypeError(f"{fn}: groups must be a contiguous int32 vector [{N}] on the boxes' device")
+    max_num = 0 if max_num is None else int(max_num)
+    if max_num < 0:
+        raise ValueError(f"{fn}: max_num = {max_num} < 0")
+    if order is None:
+        order = torch.sort(scores, descending=True, stable=True)[1]
+    elif order.dtype != torch.int64 or tuple(order.shape) != (N,) or order.device != dev or not order.is_contiguous():
+        raise TypeError(f"{fn}: order must be a contiguous int64 vector [{N}] on the boxes' device")
+    cap = max_num if max_num > 0 else N
+    need = obb_nms_workspace_bytes(N)
+    if workspace is None:
+        workspace = torch.empty((max(need, 8),), device=dev, dtype=torch.uint8)
+    elif workspace.dtype != torch.uint8 or workspace.device != dev or not workspace.is_contiguous() or workspace.numel() < need:
+        raise ValueError(f"{fn}: the workspace must hold {need} bytes (uint8) on the boxes' device (ops.obb_nms_workspace_bytes)")
+    if keep is None:
+        keep = torch.empty((cap,), device=dev, dtype=torch.int64)
+    elif keep.dtype != torch.int64 or tuple(keep.shape) != (cap,) or keep.device != dev or not keep.is_contiguous():
+        raise TypeError(f"{fn}: keep must be a contiguous int64 vector [{cap}] on the boxes' device")
+    if count is None:
+        count = torch.empty((1,), device=dev, dtype=torch.int64)
+    elif count.dtype != torch.int64 or count.numel() != 1 or count.device != dev:
+        raise TypeError(f"{fn}: count must be one int64 on the boxes' device")
+    check(lib.lmv_obb_nms(p, s, scores.data_ptr(), order.data_ptr(), _ptr(groups), N, float(iou_thr), -math.inf if score_thr is None else float(score_thr), max_num,
+                          int(phases), workspace.data_ptr(), workspace.numel(), keep.data_ptr(), count.data_ptr(), _stream()), "lmv_obb_nms")
+    return keep, count
+
+
+# -------------------------------------------------------------------------------------------
 # A run of "S" blocks as one persistent launch (csrc/sstage.hip; inference, bf16)
 # -------------------------------------------------------------------------------------------
 def sstage_supported(C_: int, heads: int, hidden: int, H: int, W: int, M: int, dtype: torch.dtype) -> bool:
