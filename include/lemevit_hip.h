@@ -825,6 +825,91 @@ int lmv_obb_nms(const float* boxes, int stride, const float* scores, const int64
                 int phases, void* workspace, size_t workspace_bytes, int64_t* keep, int64_t* count, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Horizontal RoIAlign over a feature pyramid, adaptive sampling grid included (csrc/roi.hip): the RoI layers of the reference's Mask R-CNN config
+ * (object_detection/configs/mask_rcnn/: RoIAlign with out_size 7 in the box head and 14 in the mask head, sample_num=0, aligned=True, over featmap_strides
+ * [4, 8, 16, 32]), which the reference has as a CUDA extension (mmdet/ops/roi_align/src; cpu/roi_align_v2.cpp there is the specification of the arithmetic).  An
+ * addition to ABI 14: callers detect it by symbol.  One plan launch, one forward launch and one backward launch serve ALL levels; no floating-point atomics, no
+ * pre-zeroed buffer, no host synchronisation: two calls agree bit for bit, and every entry point can be captured.
+ *
+ * Geometry.  rois: fp32 [R, 5], rows (batch_index, x1, y1, x2, y2) in image coordinates.  levels[l], l < L <= LMV_ROI_MAX_LEVELS: a map [B, C, H_l, W_l] in fp32 or
+ * bf16 read through its own ELEMENT strides (lmv_roi_level is lmv_rroi_level), and spatial_scale_l = 1 / stride_l.  out_size (oh, ow) with oh ow <= LMV_ROI_MAX_BINS;
+ * sample_num s in 0 .. LMV_ROI_MAX_GRID, 0 being the reference's default, the adaptive grid.  Only aligned = true exists here (the reference's "v2" arithmetic).
+ * The output is [R, C, oh, ow], contiguous, in the maps' dtype, accumulated in fp32.
+ *
+ * Level rule (upstream mmdet's SingleRoIExtractor.map_roi_levels; its source is not part of the reference tree, so this restates upstream):
+ *     lvl = clamp(floor(log2(sqrt((x2 - x1) (y2 - y1)) / finest_scale + 1e-6)), 0, L - 1)          (NaN: level 0)
+ * `level_index` (nullable int32 [R]) overrides the rule RoI by RoI.
+ *
+ * Per RoI at its level, in fp32, operation by operation as roi_align_v2.cpp with aligned = true:
+ *     start_w = x1 scale - 0.5,  start_h = y1 scale - 0.5;   roi_w = (x2 scale - 0.5) - start_w,  roi_h likewise;   bin_h = roi_h / oh,  bin_w = roi_w / ow
+ *     g_h = s > 0 ? s : ceil(roi_h / oh),   g_w = s > 0 ? s : ceil(roi_w / ow)
+ *     sample (ph, pw, iy, ix), iy < g_h, ix < g_w:   y = start_h + ph bin_h + (iy + .5) bin_h / g_h,   x = start_w + pw bin_w + (ix + .5) bin_w / g_w
+ *     y < -1, y > H, x < -1 or x > W: the sample contributes 0.  Otherwise y, x <= 0 become 0; y_low = (int)y; y_low >= H - 1: y_low = y_high = H - 1, y = y_low;
+ *     else y_high = y_low + 1 (the same for x); ly = y - y_low, hy = 1 - ly: the weights hy hx, hy lx, ly hx, ly lx on the four corners (the rotated operator's rule).
+ *     out[r, c, ph, pw] = (sum over the bin's samples) / max(g_h g_w, 1)          (empty samples count in the divisor)
+ * y depends on (ph, iy) only and x on (pw, ix) only, and so does the empty rule: with A_y [oh x H], row ph = the sum over iy of (hy at y_low, ly at y_high), and
+ * A_x [ow x W] likewise,  out[r, c] = A_y f[c] A_x^T / count  and  dX[c] += A_y^T dY[r, c] A_x / count.  This is what the kernels evaluate; a row of A touches a
+ * run of consecutive pixels, and the runs of neighbouring bins share at most two pixels, so a RoI's record is bounded by the map (H_l + 2 oh and W_l + 2 ow
+ * weights), whatever the grid, and so is the cost of the forward and the backward pass.
+ *
+ * Data rules (none can be validated without a synchronisation; the oracle, lemevit_amd.detection.reference_roi_align, applies the same ones).  A RoI is INVALID --
+ * its output row is zero and it reaches no gradient -- when its batch_index truncates to a value outside [0, B); its level_index lies outside [0, L); a
+ * coordinate is not finite; roi_w < 0 or roi_h < 0 (the reference asserts); or its grid exceeds LMV_ROI_MAX_GRID = 128 on either axis (a RoI of more than 896
+ * pixels OF ITS LEVEL at oh = 7; one clipped to a 1333-pixel image on stride 4 needs 48).  A RoI of zero width or height is valid and gives zeros (grid 0, divisor 1).
+ *
+ * lmv_roi_plan -- one launch, one workgroup per RoI.  plan (lmv_roi_plan_bytes(R, levels, L, oh, ow) bytes, 16-byte aligned): per RoI a record of
+ * LMV_ROI_HEADER_BYTES {level, batch, valid, y0, y1, x0, x1: the pixels its samples touch, g_h, g_w, ny, nx: weights in use}, oh + ow bin entries of
+ * LMV_ROI_BIN_BYTES {first pixel, run length, offset of the run's weights}, then max_l H_l + 2 oh weights of A_y and max_l W_l + 2 ow of A_x, rounded up to 16 bytes
+ * (2.5 KB per RoI at 7 x 7 on the levels of an 800 x 1344 image).  The `data` and stride fields of `levels` are not read.  The forward and the backward pass take ALL
+ * geometry from the plan, which makes the backward the adjoint of the forward; they must be given the R, L, B, H_l, W_l, oh, ow of the plan call (a bin entry that
+ * does not fit the map or the record it is read with counts as an empty run: a foreign plan gives wrong numbers, not a wild access).
+ *
+ * lmv_roi_fwd -- one launch, one workgroup per (RoI, 64 channels), the RoI's bin table and weights staged in LDS.  Every output element is written exactly once,
+ * rows of invalid RoIs as zeros.  Lanes run along the bins over NCHW maps, along the channels over channels-last maps (transposed through LDS for the store).
+ *
+ * lmv_roi_bwd -- one launch, gather form.  dx[l]: [B, C, H_l, W_l] in `dtype` through its own strides; dy: [R, C, oh, ow], contiguous, in `dtype`.  A workgroup owns
+ * an 8 x 16 pixel tile of one (level, image) and 64 channels with the accumulator in LDS; per RoI that reaches the tile it stages dY / count and the tile's slices
+ * of A_y and A_x, and a pixel adds sum over (ph, pw) of A_y[ph, y] A_x[pw, x] dY[ph, pw] in a FIXED order (RoI index ascending, ph, pw).  EVERY element of every
+ * level is written exactly once -- zeros where no sample lands, on a level that received no RoI, and at R = 0.  The result over L levels equals the L
+ * single-level results bit for bit.  No gradient for the RoIs, no double backward.  The strides of dx[l] must give every element its own address
+ * (lemevit_amd/ops.py refuses a buffer that does not).
+ *
+ * Refused with LMV_ERR_SHAPE (a plan buffer that is too small: LMV_ERR_WORKSPACE) and a message that starts "roi", before any launch: a null level table, a null
+ * map, null rois / plan / out / dy with R > 0; L outside 1 .. 5; s outside 0 .. LMV_ROI_MAX_GRID; oh < 1, ow < 1, oh ow > LMV_ROI_MAX_BINS; R < 0, B < 1, C < 1; H_l or
+ * W_l outside 1 .. LMV_ROI_MAX_EXTENT; a dtype code other than LMV_F32 / LMV_BF16; R C oh ow or B C H_l W_l >= 2^31; a negative stride, a misaligned buffer,
+ * finest_scale <= 0; a forward whose staged record and tile exceed the 160 KB of LDS.  R = 0 is legal: the plan and the forward launch nothing, the backward writes
+ * zeros everywhere.  lmv_roi_plan_bytes returns 0 for arguments the plan call refuses (and for R = 0).
+ * ------------------------------------------------------------------------------------------ */
+#define LMV_ROI_MAX_LEVELS 5
+#define LMV_ROI_MAX_GRID 128
+#define LMV_ROI_MAX_BINS 256
+#define LMV_ROI_MAX_EXTENT 8192
+#define LMV_ROI_HEADER_BYTES 48
+#define LMV_ROI_BIN_BYTES 16
+typedef lmv_rroi_level lmv_roi_level;
+size_t lmv_roi_plan_bytes(int R, const lmv_roi_level* levels, int L, int oh, int ow);
+int lmv_roi_plan(const float* rois, const int32_t* level_index, int R, const lmv_roi_level* levels, int L, int B, int oh, int ow, int sample_num, float finest_scale,
+                 void* plan, size_t plan_bytes, void* stream);
+int lmv_roi_fwd(const void* plan, int R, const lmv_roi_level* levels, int L, int B, int C, int oh, int ow, int dtype, void* out, void* stream);
+int lmv_roi_bwd(const void* plan, int R, const void* dy, const lmv_roi_level* dx, int L, int B, int C, int oh, int ow, int dtype, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Horizontal NMS (csrc/nms.hip): mmdet/ops/nms (nms, batched_nms) of the reference's Mask R-CNN config -- the RPN proposals (nms_thr 0.7) and the test-time
+ * multiclass NMS (iou_thr 0.5, score_thr 0.05, max_per_img 100).  An addition to ABI 14: callers detect it by symbol.  The interface and the two launches are
+ * those of lmv_obb_nms above (order: the caller's STABLE descending sort; groups; candidates; keep padded with -1; count; phases; nothing synchronised; capturable),
+ * with boxes fp32 rows (x1, y1, x2, y2) read in place through a ROW STRIDE >= 4 floats and the pair rule of cpu/nms_cpu.cpp in fp32, operation by operation:
+ *     area = (x2 - x1)(y2 - y1);   inter = max(0, min(x2) - max(x1)) max(0, min(y2) - max(y1));   suppress iff inter / (area_i + area_j - inter) > iou_thr
+ * The comparison is strict, and a NaN quotient suppresses nothing: two zero-area duplicates are both kept, as in the reference.  A box is a CANDIDATE iff
+ * score > score_thr (-inf: every score that is not NaN or -inf) and its four coordinates are finite.  Deliberate difference from the reference: classes are
+ * separated by `groups` (exact), not by adding class_id (max_coordinate + 1) to the coordinates in fp32.
+ * Refused with LMV_ERR_SHAPE (LMV_ERR_WORKSPACE) and a message that starts "nms", before any launch: what lmv_obb_nms refuses, with N <= LMV_NMS_MAX.
+ * ------------------------------------------------------------------------------------------ */
+#define LMV_NMS_MAX 16384
+size_t lmv_nms_workspace_bytes(int N);
+int lmv_nms(const float* boxes, int stride, const float* scores, const int64_t* order, const int32_t* groups, int N, float iou_thr, float score_thr, int max_num,
+            int phases, void* workspace, size_t workspace_bytes, int64_t* keep, int64_t* count, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Whole-block schedules: ONE call enqueues every launch of a LeMeBlock (models/lemevit.py:500-660) on token-major tensors
  * x [B, H*W, C], c [B, M, C] -- `LeMeBlock.forward_with_x` ("S", :615-650), `forward_with_xc` ("D", :542-582), `forward_with_c`
  * ("C", :584-613; x is returned untouched by the caller, x_out / dx_out may be NULL).  Replaces the ~12 / ~30 per-op calls a Python

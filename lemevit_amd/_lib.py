@@ -32,6 +32,8 @@ DENSE_SLIDE_MAX_GRID = 64          # LMV_DENSE_SLIDE_MAX_GRID: windows per axis
 RROI_MAX_LEVELS, RROI_MAX_SAMPLE_NUM, RROI_MAX_BINS, RROI_MAX_SAMPLES, RROI_MAX_EXTENT = 5, 4, 256, 1024, 65535          # LMV_RROI_MAX_*
 RROI_HEADER_BYTES, RROI_SAMPLE_BYTES = 32, 24          # LMV_RROI_HEADER_BYTES, LMV_RROI_SAMPLE_BYTES
 OBB_IOU, OBB_IOF, OBB_MAX_BOXES, OBB_NMS_MAX = 0, 1, 1 << 20, 16384          # LMV_OBB_IOU, LMV_OBB_IOF, LMV_OBB_MAX_BOXES, LMV_OBB_NMS_MAX
+ROI_MAX_LEVELS, ROI_MAX_GRID, ROI_MAX_BINS, ROI_MAX_EXTENT, ROI_HEADER_BYTES, ROI_BIN_BYTES = 5, 128, 256, 8192, 48, 16          # LMV_ROI_*
+NMS_MAX = 16384          # LMV_NMS_MAX
 
 
 class LinearProblem(C.Structure):
@@ -222,6 +224,12 @@ SIGNATURES = {
     "lmv_obb_overlaps": (_I, [_P, _I, _I, _P, _I, _I, _I, _I, _P, _P]),
     "lmv_obb_nms_workspace_bytes": (_Z, [_I]),
     "lmv_obb_nms": (_I, [_P, _I, _P, _P, _P, _I, _F, _F, _I, _I, _P, _Z, _P, _P, _P]),
+    "lmv_roi_plan_bytes": (_Z, [_I, C.POINTER(RroiLevel), _I, _I, _I]),
+    "lmv_roi_plan": (_I, [_P, _P, _I, C.POINTER(RroiLevel), _I, _I, _I, _I, _I, _F, _P, _Z, _P]),
+    "lmv_roi_fwd": (_I, [_P, _I, C.POINTER(RroiLevel), _I, _I, _I, _I, _I, _I, _P, _P]),
+    "lmv_roi_bwd": (_I, [_P, _I, _P, C.POINTER(RroiLevel), _I, _I, _I, _I, _I, _I, _P]),
+    "lmv_nms_workspace_bytes": (_Z, [_I]),
+    "lmv_nms": (_I, [_P, _I, _P, _P, _P, _I, _F, _F, _I, _I, _P, _Z, _P, _P, _P]),
     "lmv_block_arena_bytes": (_Z, [C.POINTER(BlockDesc)]),
     "lmv_block_bwd_scratch_bytes": (_Z, [C.POINTER(BlockDesc)]),
     "lmv_block_fwd": (_I, [C.POINTER(BlockDesc), _P, _P, _P, _P, _P, _Z, _I, _P]),

@@ -1488,6 +1488,155 @@ def obb_nms(boxes: Tensor, scores: Tensor, iou_thr: float, groups: Optional[Tens
 
 
 # -------------------------------------------------------------------------------------------
+# Horizontal RoIAlign over a feature pyramid, adaptive grid included (csrc/roi.hip; lemevit_amd/detection.py has the autograd nodes)
+# -------------------------------------------------------------------------------------------
+class RoiPlan:
+    """The plan of one ``roi_plan`` call: ``buf`` (uint8, lmv_roi_plan_bytes) and the geometry it was made for, which ``roi_align_fwd`` / ``roi_align_bwd`` hand back
+    to the library unchanged."""
+    __slots__ = ("buf", "R", "B", "sizes", "oh", "ow", "sample_num")
+
+    def __init__(self, buf, R, B, sizes, oh, ow, sample_num):
+        self.buf, self.R, self.B, self.sizes, self.oh, self.ow, self.sample_num = buf, R, B, sizes, oh, ow, sample_num
+
+
+def _roi_levels(fn: str, maps: Optional[Sequence[Tensor]], sizes: Sequence[Tuple[int, int]], scales: Optional[Sequence[float]]):
+    if not 1 <= len(sizes) <= _lib.ROI_MAX_LEVELS:
+        raise ValueError(f"{fn}: {len(sizes)} levels outside 1 .. {_lib.ROI_MAX_LEVELS}")
+    return _rroi_levels(fn, maps, sizes, scales)          # (the same level record)
+
+
+def roi_plan_bytes(R: int, sizes: Sequence[Tuple[int, int]], out_size: Tuple[int, int]) -> int:
+    """lmv_roi_plan_bytes: the bytes of a plan for ``R`` RoIs over maps of ``sizes[l] = (H_l, W_l)``: per RoI 48 + 16 (oh + ow) + 4 (max H + 2 oh + max W + 2 ow),
+    rounded up to 16 -- bounded by the maps, whatever the sampling grid."""
+    oh, ow = int(out_size[0]), int(out_size[1])
+    n = lib.lmv_roi_plan_bytes(int(R), _roi_levels("roi_plan_bytes", None, sizes, None), len(sizes), oh, ow)
+    if n == 0 and R != 0:
+        raise ValueError(f"roi_plan_bytes: bad arguments R = {R}, sizes = {tuple(sizes)}, out_size = {(oh, ow)} (at most {_lib.ROI_MAX_BINS} bins, maps of 1 .. "
+                         f"{_lib.ROI_MAX_EXTENT} per axis)")
+    return n
+
+
+def roi_plan(rois: Tensor, sizes: Sequence[Tuple[int, int]], spatial_scales: Sequence[float], B: int, out_size: Tuple[int, int], sample_num: int = 0,
+             levels: Optional[Tensor] = None, finest_scale: float = 56.0, plan: Optional[Tensor] = None) -> RoiPlan:
+    """lmv_roi_plan (one launch): ``rois`` float32 [R, 5] rows ``(batch_index, x1, y1, x2, y2)``; ``sizes[l] = (H_l, W_l)`` and ``spatial_scales[l]`` per level;
+    ``sample_num`` 0 (the adaptive grid ``ceil(roi_size / out_size)`` per RoI and axis) .. 128; ``levels``: int32 [R] overriding the level rule; ``plan``: a
+    caller-supplied uint8 buffer of ``roi_plan_bytes`` (a captured call allocates nothing).  Returns the ``RoiPlan`` that ``roi_align_fwd`` and ``roi_align_bwd`` take
+    (include/lemevit_hip.h has the level rule, the formulas and the rules for invalid RoIs)."""
+    fn = "roi_plan"
+    if rois.dim() != 2 or rois.shape[1] != 5 or rois.dtype != torch.float32 or not rois.is_contiguous():
+        raise ValueError(f"{fn}: contiguous float32 [R, 5] rois expected, got {rois.dtype} {tuple(rois.shape)}")
+    if len(spatial_scales) != len(sizes):
+        raise ValueError(f"{fn}: {len(spatial_scales)} scales for {len(sizes)} levels")
+    if not 0 <= int(sample_num) <= _lib.ROI_MAX_GRID:
+        raise ValueError(f"{fn}: sample_num = {sample_num} outside 0 .. {_lib.ROI_MAX_GRID}")
+    R, (oh, ow) = int(rois.shape[0]), (int(out_size[0]), int(out_size[1]))
+    sizes = tuple((int(h), int(w)) for h, w in sizes)
+    arr = _roi_levels(fn, None, sizes, spatial_scales)
+    if levels is not None and (levels.dtype != torch.int32 or tuple(levels.shape) != (R,) or levels.device != rois.device or not levels.is_contiguous()):
+        raise TypeError(f"{fn}: levels must be a contiguous int32 vector [{R}] on the rois' device")
+    need = roi_plan_bytes(R, sizes, (oh, ow))
+    if plan is None:
+        plan = torch.empty((max(need, 16),), device=rois.device, dtype=torch.uint8)
+    elif plan.dtype != torch.uint8 or plan.device != rois.device or not plan.is_contiguous() or plan.numel() < need:
+        raise ValueError(f"{fn}: the plan buffer must hold {need} bytes (uint8) on the rois' device (ops.roi_plan_bytes)")
+    check(lib.lmv_roi_plan(_ptr(rois), _ptr(levels), R, arr, len(sizes), int(B), oh, ow, int(sample_num), float(finest_scale), _ptr(plan), plan.numel(), _stream()),
+          "lmv_roi_plan")
+    return RoiPlan(plan, R, int(B), sizes, oh, ow, int(sample_num))
+
+
+def roi_align_fwd(feats: Sequence[Tensor], plan: RoiPlan, out: Optional[Tensor] = None) -> Tensor:
+    """lmv_roi_fwd (one launch over all levels): ``feats[l]`` [B, C, H_l, W_l] float32 / bfloat16 in ANY strides (NCHW and channels-last are the fast ones).
+    Returns ``out`` [R, C, oh, ow], contiguous, in the features' dtype; every element is written once, rows of invalid RoIs as zeros."""
+    fn = "roi_align_fwd"
+    C_, code = _rroi_maps(fn, feats, plan, "feature maps")
+    shape = (plan.R, C_, plan.oh, plan.ow)
+    if out is None:
+        out = torch.empty(shape, device=feats[0].device, dtype=feats[0].dtype)
+    elif out.dtype != feats[0].dtype or tuple(out.shape) != shape or out.device != feats[0].device or not out.is_contiguous():
+        raise TypeError(f"{fn}: out must be a contiguous {feats[0].dtype} tensor {shape} on the features' device")
+    arr = _roi_levels(fn, feats, plan.sizes, None)
+    check(lib.lmv_roi_fwd(plan.buf.data_ptr(), plan.R, arr, len(plan.sizes), plan.B, C_, plan.oh, plan.ow, code, out.data_ptr(), _stream()), "lmv_roi_fwd")
+    return out
+
+
+def roi_align_bwd(grad_out: Tensor, plan: RoiPlan, like: Sequence[Tensor], dx: Optional[Sequence[Tensor]] = None) -> List[Tensor]:
+    """lmv_roi_bwd (one launch over all levels, no atomics): ``grad_out`` [R, C, oh, ow] contiguous; returns ``dx[l]`` in the dtype and layout of ``like[l]`` (the
+    forward's feature maps), EVERY element written once -- zeros included, on a level without RoIs and at R = 0.  ``dx``: caller-supplied buffers to write instead.
+    A map whose strides let two indices share an address (an expanded view) is refused: one element, one writer."""
+    fn = "roi_align_bwd"
+    if dx is None:
+        dx = [torch.empty_like(t) for t in like]
+    C_, code = _rroi_maps(fn, dx, plan, "gradient maps")
+    for l, t in enumerate(dx):
+        if not strides_injective(t.shape, t.stride()):
+            raise ValueError(f"{fn}: level {l}: a gradient map with strides {tuple(t.stride())} aliases itself (an expanded view): every element must have its own address")
+    shape = (plan.R, C_, plan.oh, plan.ow)
+    if tuple(grad_out.shape) != shape or grad_out.dtype != dx[0].dtype or grad_out.device != dx[0].device or not grad_out.is_contiguous():
+        raise TypeError(f"{fn}: grad_out must be a contiguous {dx[0].dtype} tensor {shape} on the maps' device")
+    arr = _roi_levels(fn, dx, plan.sizes, None)
+    check(lib.lmv_roi_bwd(plan.buf.data_ptr(), plan.R, grad_out.data_ptr(), arr, len(plan.sizes), plan.B, C_, plan.oh, plan.ow, code, _stream()), "lmv_roi_bwd")
+    return list(dx)
+
+
+# -------------------------------------------------------------------------------------------
+# Horizontal NMS (csrc/nms.hip; lemevit_amd/detection.py has the reference's entry points)
+# -------------------------------------------------------------------------------------------
+def nms_workspace_bytes(N: int) -> int:
+    """lmv_nms_workspace_bytes: N ceil(N / 64) 8 bytes, the suppression words of ``nms`` (N <= 16 384)"""
+    if not 0 <= int(N) <= _lib.NMS_MAX:
+        raise ValueError(f"nms_workspace_bytes: N = {N} outside 0 .. {_lib.NMS_MAX}")
+    return int(lib.lmv_nms_workspace_bytes(int(N)))
+
+
+def nms(boxes: Tensor, scores: Tensor, iou_thr: float, groups: Optional[Tensor] = None, score_thr: Optional[float] = None, max_num: Optional[int] = None,
+        order: Optional[Tensor] = None, workspace: Optional[Tensor] = None, keep: Optional[Tensor] = None, count: Optional[Tensor] = None,
+        phases: int = 3) -> Tuple[Tensor, Tensor]:
+    """lmv_nms (two launches, no host round trip): greedy NMS of float32 axis-aligned ``boxes`` [N, >= 4] rows ``(x1, y1, x2, y2)`` (read in place through their row
+    stride) with float32 ``scores`` [N]; the arguments, the candidates' score rule and the result ``(keep, count)`` are those of ``obb_nms``.  A kept box suppresses the
+    lower-ranked candidates of its group with ``inter / (area_i + area_j - inter) > iou_thr`` in float32 (a NaN quotient suppresses nothing)."""
+    fn = "nms"
+    if boxes.dim() != 2 or boxes.shape[1] < 4 or boxes.dtype != torch.float32:
+        raise ValueError(f"{fn}: boxes: float32 [N, >= 4] rows (x1, y1, x2, y2) expected, got {boxes.dtype} {tuple(boxes.shape)}")
+    if not boxes.is_cuda:
+        raise RuntimeError("lemevit_amd: tensors must be on the GPU (no CPU fallback exists)")
+    N, dev = int(boxes.shape[0]), boxes.device
+    if (N > 0 and boxes.stride(1) != 1) or (N > 1 and boxes.stride(0) < 4):
+        raise ValueError(f"{fn}: boxes: strides {tuple(boxes.stride())}: a unit column stride and a row stride >= 4 are needed (call .contiguous())")
+    s = int(boxes.stride(0)) if N > 1 else max(int(boxes.stride(0)), 4)
+    if N > _lib.NMS_MAX:
+        raise ValueError(f"{fn}: N = {N} boxes, at most {_lib.NMS_MAX}")
+    if scores.dtype != torch.float32 or tuple(scores.shape) != (N,) or scores.device != dev:
+        raise ValueError(f"{fn}: float32 scores [{N}] on the boxes' device expected, got {scores.dtype} {tuple(scores.shape)}")
+    scores = scores.contiguous()
+    if groups is not None and (groups.dtype != torch.int32 or tuple(groups.shape) != (N,) or groups.device != dev or not groups.is_contiguous()):
+        raise TypeError(f"{fn}: groups must be a contiguous int32 vector [{N}] on the boxes' device")
+    max_num = 0 if max_num is None else int(max_num)
+    if max_num < 0:
+        raise ValueError(f"{fn}: max_num = {max_num} < 0")
+    if order is None:
+        order = torch.sort(scores, descending=True, stable=True)[1]
+    elif order.dtype != torch.int64 or tuple(order.shape) != (N,) or order.device != dev or not order.is_contiguous():
+        raise TypeError(f"{fn}: order must be a contiguous int64 vector [{N}] on the boxes' device")
+    cap = max_num if max_num > 0 else N
+    need = nms_workspace_bytes(N)
+    if workspace is None:
+        workspace = torch.empty((max(need, 8),), device=dev, dtype=torch.uint8)
+    elif workspace.dtype != torch.uint8 or workspace.device != dev or not workspace.is_contiguous() or workspace.numel() < need:
+        raise ValueError(f"{fn}: the workspace must hold {need} bytes (uint8) on the boxes' device (ops.nms_workspace_bytes)")
+    if keep is None:
+        keep = torch.empty((cap,), device=dev, dtype=torch.int64)
+    elif keep.dtype != torch.int64 or tuple(keep.shape) != (cap,) or keep.device != dev or not keep.is_contiguous():
+        raise TypeError(f"{fn}: keep must be a contiguous int64 vector [{cap}] on the boxes' device")
+    if count is None:
+        count = torch.empty((1,), device=dev, dtype=torch.int64)
+    elif count.dtype != torch.int64 or count.numel() != 1 or count.device != dev:
+        raise TypeError(f"{fn}: count must be one int64 on the boxes' device")
+    check(lib.lmv_nms(boxes.data_ptr(), s, scores.data_ptr(), order.data_ptr(), _ptr(groups), N, float(iou_thr), -math.inf if score_thr is None else float(score_thr),
+                      max_num, int(phases), workspace.data_ptr(), workspace.numel(), keep.data_ptr(), count.data_ptr(), _stream()), "lmv_nms")
+    return keep, count
+
+
+# -------------------------------------------------------------------------------------------
 # A run of "S" blocks as one persistent launch (csrc/sstage.hip; inference, bf16)
 # -------------------------------------------------------------------------------------------
 def sstage_supported(C_: int, heads: int, hidden: int, H: int, W: int, M: int, dtype: torch.dtype) -> bool:
