@@ -910,6 +910,67 @@ int lmv_nms(const float* boxes, int stride, const float* scores, const int64_t* 
             int phases, void* workspace, size_t workspace_bytes, int64_t* keep, int64_t* count, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Max-IoU target assignment without the [boxes x ground truths] matrix, and horizontal overlaps (csrc/assign.hip): what the reference's Oriented R-CNN configs do
+ * twice per image with MaxIoUAssigner -- at the RPN on horizontal boxes (0.7 / 0.3 / 0.3, match_low_quality, gpu_assign_thr=200) and at the R-CNN head with
+ * iou_calculator=dict(type='OBBOverlaps') (0.5 / 0.5 / 0.5, no low-quality matches).  The sources of MaxIoUAssigner and bbox_overlaps are NOT part of the reference
+ * tree (only mmdet/ops and the backbone are): the rules below restate upstream mmdet 2.x.  An addition to ABI 14: callers detect it by symbol.  No host round trip,
+ * no floating-point atomics (integer maxima only, which do not depend on arrival order): two calls agree bit for bit, and every entry point can be captured.
+ *
+ * lmv_bbox_overlaps -- the horizontal counterpart of lmv_obb_overlaps, with its arguments and properties: boxes fp32 rows (x1, y1, x2, y2) read in place through a
+ * ROW STRIDE >= 4 floats; out fp32 [N, M] (aligned == 0) or [N] from the pairs (b1[n], b2[n]) (aligned == 1, N == M); modes LMV_OBB_IOU / LMV_OBB_IOF; one launch,
+ * every element written exactly once, stores run along M, N == 0 or M == 0 launches nothing.  The pair rule (upstream bbox_overlaps, which has no "+ 1"), in fp32:
+ *     w = max(min(x2, x2') - max(x1, x1'), 0),  h likewise;   I = w h;   a = (x2 - x1)(y2 - y1)
+ *     iou = I / max(a + a' - I, 1e-6);   iof = I / max(a, 1e-6)
+ * A box with a non-finite coordinate gives 0 against everything (the data rule of the rotated operator), and so does a non-finite quotient.  iou(p, q) and iou(q, p)
+ * agree bit for bit.
+ *
+ * lmv_max_iou_assign -- at most two launches and one memset node; the [N, G] values are never stored.  kind: LMV_ASSIGN_HORIZONTAL (k = 4 columns, the pair rule
+ * above) or LMV_ASSIGN_ROTATED (k = 5, the pair function of lmv_obb_overlaps: v[j, n] below equals lmv_obb_overlaps(boxes, gts)[n, j] bit for bit, pairs whose
+ * bounding circles are apart are exactly 0).
+ *     boxes        fp32 [N, k] shared by all images (box_batch_stride == 0) or [B, N, k] (box_batch_stride: floats from one image's boxes to the next's), rows read
+ *                  through box_stride >= k
+ *     gts          fp32 [B, Gmax, k], rows through gt_stride >= k (an image's rows are Gmax gt_stride floats apart)
+ *     gt_counts    nullable int32 [B] ON THE DEVICE: the valid rows per image, clamped to 0 .. Gmax by the kernel; null: Gmax everywhere.  Rows past the count are
+ *                  never read
+ *     gt_labels    nullable int64 [B, Gmax];   ignore: nullable uint8 [B, N] (non-zero: the box is ignored)
+ *     gt_inds      int64 [B, N];   max_overlaps fp32 [B, N];   labels (nullable) int64 [B, N], written only when gt_labels is given (with Gmax = 0 gt_labels may
+ *                  be null: every label is then -1).  Every element is written exactly once.
+ * Nothing is synchronised and every size the host needs is an argument: capturable after one eager call per shape.
+ * Rules, for one image with g valid ground truths and v[j, n] the pair value (IoU) of ground truth j and box n:
+ *     an ignored box gets gt_inds = -1, max_overlaps = -1, labels = -1 and takes no part in any ground truth's maximum (upstream's ignore_iof_thr outcome, and
+ *         allowed_border filtering without a boolean-index copy); deliberately also when g = 0
+ *     g = 0: every other box gets gt_inds = 0, max_overlaps = 0
+ *     otherwise max_overlaps[n] = max_j v[j, n], argmax[n] = the LOWEST j that attains it;   gt_max[j] = max over the boxes n that are not ignored of v[j, n]
+ *     base rule: gt_inds[n] = argmax[n] + 1 if max_overlaps[n] >= pos_iou_thr, else 0 if neg_lo <= max_overlaps[n] < neg_hi, else -1  (upstream's float
+ *         neg_iou_thr is neg_lo = 0, neg_hi = neg_iou_thr; its tuple form gives both)
+ *     match_low_quality overrides it as upstream's loop over j ascending does: with gt_max_assign_all = 1, gt_inds[n] = the LARGEST j + 1 with
+ *         gt_max[j] >= min_pos_iou and v[j, n] == gt_max[j] (fp32 equality of the kernel's own values); with gt_max_assign_all = 0, ground truth j is held by the
+ *         lowest n that attains gt_max[j], and a box takes the largest j + 1 it holds.  Upstream's literal consequence stays: with min_pos_iou <= 0 a ground truth
+ *         that overlaps nothing matches every box at value 0 (gt_max_assign_all = 1) or the image's first box that is not ignored (= 0)
+ *     labels[n] = gt_labels[gt_inds[n] - 1] where gt_inds[n] > 0, else -1
+ * Mapping: a workgroup owns 256 boxes of one image, a record per thread, and stages the ground-truth records through LDS in chunks of LMV_ASSIGN_GT_CHUNK.
+ * Launch 1 (only with match_low_quality): IoU >= 0, so its bit pattern orders as an unsigned integer; lanes with v > 0 issue an LDS integer max on the key
+ * (bits of v << 32) | ~n, the workgroup one global integer atomicMax per ground truth with a non-zero key, into a table [B, Gmax + 1] of 8-byte keys that a memset
+ * node zeroed (workspace: lmv_max_iou_assign_workspace_bytes(B, Gmax) = B (Gmax + 1) 8 bytes, 8-byte aligned, always required).  Launch 2 recomputes v with the same
+ * function and writes every output.
+ * Refused with LMV_ERR_SHAPE (a workspace that is too small or null: LMV_ERR_WORKSPACE) and a message that starts "assign", before any launch: null pointers with
+ * non-zero sizes, gt_labels without labels or labels without gt_labels (Gmax > 0), a row stride below k, B outside 1 .. LMV_ASSIGN_MAX_BATCH, negative sizes, N > LMV_OBB_MAX_BOXES, Gmax > LMV_ASSIGN_MAX_GT, a NaN threshold,
+ * neg_lo > neg_hi, an unknown kind, flags other than 0 / 1, misaligned buffers.  lmv_bbox_overlaps refuses what lmv_obb_overlaps refuses (row stride below 4), with
+ * a message that starts "bbox_overlaps".  lmv_max_iou_assign_workspace_bytes returns 0 for a B or Gmax the call refuses.
+ * ------------------------------------------------------------------------------------------ */
+#define LMV_ASSIGN_HORIZONTAL 0
+#define LMV_ASSIGN_ROTATED 1
+#define LMV_ASSIGN_GT_CHUNK 64
+#define LMV_ASSIGN_MAX_GT 16384
+#define LMV_ASSIGN_MAX_BATCH 4096
+int lmv_bbox_overlaps(const float* boxes1, int stride1, int N, const float* boxes2, int stride2, int M, int mode, int aligned, float* out, void* stream);
+size_t lmv_max_iou_assign_workspace_bytes(int B, int Gmax);
+int lmv_max_iou_assign(int kind, const float* boxes, int box_stride, int64_t box_batch_stride, int N, const float* gts, int gt_stride, int B, int Gmax,
+                       const int32_t* gt_counts, const int64_t* gt_labels, const uint8_t* ignore, float pos_iou_thr, float neg_lo, float neg_hi, float min_pos_iou,
+                       int match_low_quality, int gt_max_assign_all, void* workspace, size_t workspace_bytes, int64_t* gt_inds, float* max_overlaps, int64_t* labels,
+                       void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Whole-block schedules: ONE call enqueues every launch of a LeMeBlock (models/lemevit.py:500-660) on token-major tensors
  * x [B, H*W, C], c [B, M, C] -- `LeMeBlock.forward_with_x` ("S", :615-650), `forward_with_xc` ("D", :542-582), `forward_with_c`
  * ("C", :584-613; x is returned untouched by the caller, x_out / dx_out may be NULL).  Replaces the ~12 / ~30 per-op calls a Python

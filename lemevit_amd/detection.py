@@ -30,11 +30,26 @@ Horizontal RoIAlign with the ADAPTIVE grid (csrc/roi.hip) and horizontal NMS (cs
 one with a non-finite coordinate and one with a bad batch index or level give a zero row and reach no gradient (include/lemevit_hip.h).  Not provided:
 ``aligned=False``, ``use_torchvision=True``, ``soft_nms``, ``nms_match``, ``roi_pool``, RoI gradients.  Classes are separated by ``groups``, as in ``arb_batched_nms``.
 ``reference_roi_align`` / ``reference_nms`` are the numpy float64 oracles, ``roi_align_torch`` / ``nms_torch`` the stock-PyTorch formulations.
+
+Max-IoU target assignment WITHOUT the [boxes x ground truths] matrix (csrc/assign.hip), the step that calls the overlaps in every training iteration -- both
+assigners of the Oriented R-CNN configs, under upstream mmdet 2.x's names (their sources are not part of the reference tree: the rules restate upstream):
+
+    from lemevit_amd.detection import MaxIoUAssigner, AssignResult, bbox_overlaps
+    rpn = MaxIoUAssigner(pos_iou_thr=0.7, neg_iou_thr=0.3, min_pos_iou=0.3, match_low_quality=True, gpu_assign_thr=200)          # horizontal boxes
+    rcnn = MaxIoUAssigner(0.5, 0.5, 0.5, match_low_quality=False, iou_calculator=dict(type='OBBOverlaps'))          # rotated boxes
+    result = rpn.assign(anchors, gt_bboxes, gt_bboxes_ignore, gt_labels)          # one image, upstream's signature -> AssignResult
+    gt_inds, max_overlaps, labels = rpn.assign_batched(anchors, gts, gt_counts, gt_labels)          # B images, no synchronisation, capturable
+
+Per box a maximum and an argmax over the ground truths, per ground truth an integer maximum over the boxes: at most two launches, no floating-point atomics, two
+calls agree bit for bit; ``gpu_assign_thr`` is accepted and ignored (the assignment never leaves the device).  One deliberate difference: an ignored box is -1 also
+when the image has no ground truth.  Not provided: the samplers (``RandomSampler``, ``OBBRandomSampler``), target encoding (``MidpointOffsetCoder``,
+``OBB2OBBDeltaXYWHTCoder``), other assigners, fp16 / bf16 boxes, gradients.  ``reference_bbox_overlaps`` / ``reference_max_iou_assign`` are the numpy float64
+oracles, ``bbox_overlaps_torch`` / ``max_iou_assign_torch`` the stock-PyTorch formulations on the whole matrix.
 """
 from __future__ import annotations
 
 import math
-from typing import List, Optional, Sequence, Tuple
+from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -960,3 +975,232 @@ def soft_nms(dets, iou_thr, method="linear", sigma=0.5, min_score=1e-3):
 def nms_match(dets, thresh):
     """Not provided (the reference runs it on the CPU only; its Mask R-CNN config does not use it)."""
     raise NotImplementedError("nms_match is not provided")
+
+
+# -------------------------------------------------------------------------------------------
+# Max-IoU assignment without the [boxes x ground truths] matrix (csrc/assign.hip): upstream's bbox_overlaps and MaxIoUAssigner
+# -------------------------------------------------------------------------------------------
+BBOX_EPS = 1e-6          # upstream bbox_overlaps' eps: the floor of the union (iou) and of the first box's area (iof)
+
+
+def _bbox_formula(xp, p, q, mode: str):
+    """upstream ``bbox_overlaps`` (no "+ 1") on coordinate arrays that broadcast, in the arrays' own precision"""
+    w = xp.maximum(xp.minimum(p[2], q[2]) - xp.maximum(p[0], q[0]), 0.0 * (p[0] + q[0]))
+    h = xp.maximum(xp.minimum(p[3], q[3]) - xp.maximum(p[1], q[1]), 0.0 * (p[1] + q[1]))
+    inter = w * h
+    a1, a2 = (p[2] - p[0]) * (p[3] - p[1]), (q[2] - q[0]) * (q[3] - q[1])
+    den = a1 + a2 - inter if mode == "iou" else a1 + 0.0 * inter
+    return inter / xp.maximum(den, 0.0 * den + BBOX_EPS)
+
+
+def reference_bbox_overlaps(bboxes1, bboxes2, mode: str = "iou", is_aligned: bool = False) -> np.ndarray:
+    """The numpy float64 oracle of ``bbox_overlaps``: [N, M] (or [N, 1] with ``is_aligned``) by upstream's rule, which has no "+ 1":
+    ``I = max(min(x2, x2') - max(x1, x1'), 0) max(min(y2, y2') - max(y1, y1'), 0)``, ``iou = I / max(a + a' - I, 1e-6)``, ``iof = I / max(a, 1e-6)``.  A box with a
+    non-finite coordinate gives 0 against everything, and so does a non-finite quotient."""
+    if mode not in ("iou", "iof"):
+        raise ValueError(f"reference_bbox_overlaps: mode must be 'iou' or 'iof', got {mode!r}")
+    b1, b2 = _hb_np(bboxes1, "bboxes1"), _hb_np(bboxes2, "bboxes2")
+    if is_aligned and len(b1) != len(b2):
+        raise ValueError("reference_bbox_overlaps: aligned pairs need as many boxes on both sides")
+    ok1, ok2 = np.isfinite(b1).all(1), np.isfinite(b2).all(1)
+    c1, c2 = np.where(ok1[:, None], b1, 0.0), np.where(ok2[:, None], b2, 0.0)
+    p = [c1[:, k] for k in range(4)] if is_aligned else [c1[:, None, k] for k in range(4)]
+    q = [c2[:, k] for k in range(4)] if is_aligned else [c2[None, :, k] for k in range(4)]
+    with np.errstate(all="ignore"):
+        v = _bbox_formula(np, p, q, mode)
+    ok = (ok1 & ok2) if is_aligned else (ok1[:, None] & ok2[None, :])
+    v = np.where(ok & np.isfinite(v), v, 0.0)
+    return v[:, None] if is_aligned else v
+
+
+def bbox_overlaps_torch(bboxes1: Tensor, bboxes2: Tensor, mode: str = "iou", is_aligned: bool = False) -> Tensor:
+    """What a user would write in stock PyTorch (and what upstream's ``bbox_overlaps`` is): the whole [N, M] matrix by broadcasting, in the boxes' dtype.  Works on any
+    device."""
+    b1, b2 = bboxes1[:, :4], bboxes2[:, :4]
+    p = [b1[:, k] for k in range(4)] if is_aligned else [b1[:, None, k] for k in range(4)]
+    q = [b2[:, k] for k in range(4)] if is_aligned else [b2[None, :, k] for k in range(4)]
+    v = _bbox_formula(torch, p, q, mode)
+    ok1, ok2 = torch.isfinite(b1).all(1), torch.isfinite(b2).all(1)
+    ok = (ok1 & ok2) if is_aligned else (ok1[:, None] & ok2[None, :])
+    v = torch.where(ok & torch.isfinite(v), v, torch.zeros_like(v))
+    return v[:, None] if is_aligned else v
+
+
+def bbox_overlaps(bboxes1: Tensor, bboxes2: Tensor, mode: str = "iou", is_aligned: bool = False) -> Tensor:
+    """Upstream mmdet 2.x ``bbox_overlaps(bboxes1, bboxes2, mode='iou', is_aligned=False)`` on the native kernel (its source is not part of the reference tree: the
+    rule restates upstream, include/lemevit_hip.h): tensors on the GPU of rows ``(x1, y1, x2, y2)``; float32 [N, M], or [N, 1] with ``is_aligned``; an empty side
+    gives the empty shape without a launch.  There is no gradient: a box tensor that requires grad raises."""
+    if mode not in ("iou", "iof"):
+        raise ValueError(f"bbox_overlaps: mode must be 'iou' or 'iof', got {mode!r}")
+    if not isinstance(bboxes1, torch.Tensor) or not isinstance(bboxes2, torch.Tensor):
+        raise TypeError(f"bbox_overlaps: both box sets must be tensors, got {type(bboxes1)} and {type(bboxes2)}")
+    if is_aligned and bboxes1.shape[0] != bboxes2.shape[0]:
+        raise ValueError("bbox_overlaps: is_aligned needs as many boxes on both sides")
+    if bboxes1.requires_grad or bboxes2.requires_grad:
+        raise RuntimeError("bbox_overlaps: there is no gradient for the boxes (detach them)")
+    rows, cols = bboxes1.shape[0], bboxes2.shape[0]
+    if rows == 0 or cols == 0:
+        return bboxes1.new_zeros((rows, 1) if is_aligned else (rows, cols), dtype=torch.float32)
+    return ops.bbox_overlaps(bboxes1.float()[:, :4], bboxes2.float()[:, :4], mode, is_aligned)
+
+
+class AssignResult(NamedTuple):
+    """upstream's field names: ``gt_inds`` -1 ignore / 0 negative / j + 1 the ground truth; ``labels`` -1 where ``gt_inds <= 0`` (None without ``gt_labels``)"""
+    num_gts: int
+    gt_inds: Tensor
+    max_overlaps: Tensor
+    labels: Optional[Tensor]
+
+
+def _neg_range(neg_iou_thr) -> Tuple[float, float]:
+    if isinstance(neg_iou_thr, (tuple, list)):
+        if len(neg_iou_thr) != 2:
+            raise ValueError(f"neg_iou_thr: a tuple has two entries (lower, upper), got {neg_iou_thr!r}")
+        return float(neg_iou_thr[0]), float(neg_iou_thr[1])
+    return 0.0, float(neg_iou_thr)
+
+
+def reference_max_iou_assign(bboxes, gt_bboxes, pos_iou_thr: float, neg_iou_thr, min_pos_iou: float = 0.0, gt_max_assign_all: bool = True,
+                             match_low_quality: bool = True, gt_labels=None, ignore=None, overlaps=None):
+    """The numpy float64 oracle of the assignment for ONE image: upstream's ``MaxIoUAssigner.assign_wrt_overlaps``, literally, on the float64 matrix of
+    ``reference_bbox_overlaps`` (4 columns) or ``reference_obb_overlaps`` (5 columns) -- or on ``overlaps`` [N, G] (boxes x ground truths, the layout the overlaps
+    operators return) when the caller has it; the boxes may then be None.  ``ignore``: bool [N]; an ignored box's column is set to -1 before the maxima, which is what
+    upstream does for ``ignore_iof_thr``.  Returns ``(gt_inds int64 [N], max_overlaps float64 [N], labels int64 [N] or None)``.  The one deliberate difference from
+    upstream: an ignored box is -1 also when the image has no ground truth."""
+    if overlaps is None:
+        g = gt_bboxes.detach().cpu().numpy() if isinstance(gt_bboxes, torch.Tensor) else np.asarray(gt_bboxes)
+        overlaps = (reference_obb_overlaps if g.shape[-1] == 5 else reference_bbox_overlaps)(bboxes, gt_bboxes)
+    ov = np.array(overlaps, dtype=np.float64).T.copy()          # upstream's layout: [num_gts, num_bboxes]
+    G, N = ov.shape
+    ign = np.zeros(N, dtype=bool) if ignore is None else np.asarray(ignore.cpu() if isinstance(ignore, torch.Tensor) else ignore).astype(bool)
+    lo, hi = _neg_range(neg_iou_thr)
+    lab = None if gt_labels is None else np.asarray(gt_labels.cpu() if isinstance(gt_labels, torch.Tensor) else gt_labels).astype(np.int64)
+    gt_inds = np.full(N, -1, dtype=np.int64)
+    if G == 0 or N == 0:
+        max_ov = np.zeros(N)
+        if G == 0:
+            gt_inds[:] = 0
+        gt_inds[ign], max_ov[ign] = -1, -1.0
+        return gt_inds, max_ov, (None if lab is None else np.full(N, -1, dtype=np.int64))
+    ov[:, ign] = -1.0
+    max_ov, argmax = ov.max(0), ov.argmax(0)
+    gt_max, gt_argmax = ov.max(1), ov.argmax(1)
+    gt_inds[(max_ov >= lo) & (max_ov < hi)] = 0
+    pos = max_ov >= pos_iou_thr
+    gt_inds[pos] = argmax[pos] + 1
+    if match_low_quality:
+        for i in range(G):
+            if gt_max[i] >= min_pos_iou:
+                if gt_max_assign_all:
+                    gt_inds[ov[i] == gt_max[i]] = i + 1
+                else:
+                    gt_inds[gt_argmax[i]] = i + 1
+    labels = None
+    if lab is not None:
+        labels = np.full(N, -1, dtype=np.int64)
+        labels[gt_inds > 0] = lab[gt_inds[gt_inds > 0] - 1]
+    return gt_inds, max_ov, labels
+
+
+def max_iou_assign_torch(overlaps: Tensor, pos_iou_thr: float, neg_iou_thr, min_pos_iou: float = 0.0, gt_max_assign_all: bool = True, match_low_quality: bool = True,
+                         gt_labels: Optional[Tensor] = None, ignore: Optional[Tensor] = None):
+    """What a user writes today, for ONE image: upstream's procedure in stock tensor ops on the whole matrix ``overlaps`` [N, G] (``ops.bbox_overlaps(boxes, gts)`` /
+    ``ops.obb_overlaps(boxes, gts)``) -- ``max`` over both dimensions, comparisons, and the loop over the ground truths.  Works on any device and dtype.  Returns
+    ``(gt_inds int64 [N], max_overlaps [N], labels int64 [N] or None)``; ``ignore`` as in ``reference_max_iou_assign``."""
+    ov = overlaps.t().clone()          # upstream's layout: [num_gts, num_bboxes]
+    G, N = ov.shape
+    lo, hi = _neg_range(neg_iou_thr)
+    gt_inds = ov.new_full((N,), -1, dtype=torch.int64)
+    ign = None if ignore is None else ignore.to(torch.bool)
+    if G == 0 or N == 0:
+        max_ov = ov.new_zeros((N,))
+        if G == 0:
+            gt_inds[:] = 0
+        if ign is not None:
+            gt_inds[ign], max_ov[ign] = -1, -1.0
+        return gt_inds, max_ov, (None if gt_labels is None else ov.new_full((N,), -1, dtype=torch.int64))
+    if ign is not None:
+        ov[:, ign] = -1.0
+    max_ov, argmax = ov.max(dim=0)
+    gt_max, gt_argmax = ov.max(dim=1)
+    gt_inds[(max_ov >= lo) & (max_ov < hi)] = 0
+    pos = max_ov >= pos_iou_thr
+    gt_inds[pos] = argmax[pos] + 1
+    if match_low_quality:
+        for i in range(G):
+            if gt_max[i] >= min_pos_iou:
+                if gt_max_assign_all:
+                    gt_inds[ov[i, :] == gt_max[i]] = i + 1
+                else:
+                    gt_inds[gt_argmax[i]] = i + 1
+    labels = None
+    if gt_labels is not None:
+        labels = ov.new_full((N,), -1, dtype=torch.int64)
+        p = torch.nonzero(gt_inds > 0, as_tuple=False).squeeze(1)
+        labels[p] = gt_labels[gt_inds[p] - 1]
+    return gt_inds, max_ov, labels
+
+
+class MaxIoUAssigner:
+    """Upstream mmdet 2.x ``MaxIoUAssigner`` on the fused kernels (csrc/assign.hip): the assignment without the [boxes x ground truths] matrix, without a host
+    round trip, deterministic.  Its source is not part of the reference tree: the rules restate upstream (include/lemevit_hip.h).
+
+    ``iou_calculator``: ``dict(type='BboxOverlaps2D')`` -- boxes ``(x1, y1, x2, y2)``, the RPN assigner of the Oriented R-CNN configs -- or
+    ``dict(type='OBBOverlaps')`` -- boxes ``(cx, cy, w, h, theta)``, their R-CNN assigner; anything else raises NotImplementedError.  ``gpu_assign_thr`` is accepted
+    and IGNORED: upstream moves the assignment to the CPU above that many ground truths to save the matrix's memory; here there is no matrix and the assignment
+    never leaves the device.  ``ignore_iof_thr > 0`` with a non-empty ``gt_bboxes_ignore`` computes the per-box maximum IoF against the ignore regions with the matrix
+    operators (ignore regions are few) and passes ``max > ignore_iof_thr`` as ``ignore``.  One deliberate difference from upstream: an ignored box is -1 also when
+    the image has no ground truth.  No gradient flows through an assignment: the boxes are detached."""
+
+    def __init__(self, pos_iou_thr, neg_iou_thr, min_pos_iou=0.0, gt_max_assign_all=True, ignore_iof_thr=-1, ignore_wrt_candidates=True, match_low_quality=True,
+                 gpu_assign_thr=-1, iou_calculator=dict(type="BboxOverlaps2D")):
+        cfg = dict(iou_calculator) if isinstance(iou_calculator, dict) else dict(type=iou_calculator)
+        kind = cfg.pop("type", None)
+        if kind not in ("BboxOverlaps2D", "OBBOverlaps") or cfg:
+            raise NotImplementedError(f"MaxIoUAssigner: iou_calculator={iou_calculator!r} is not supported (only dict(type='BboxOverlaps2D') and dict(type='OBBOverlaps'))")
+        self.k = 5 if kind == "OBBOverlaps" else 4
+        self.iou_calculator = kind
+        self.pos_iou_thr, self.neg_lo, self.neg_hi, self.min_pos_iou = ops.assign_thresholds("MaxIoUAssigner", pos_iou_thr, neg_iou_thr, min_pos_iou)
+        self.neg_iou_thr = neg_iou_thr
+        self.gt_max_assign_all, self.match_low_quality = bool(gt_max_assign_all), bool(match_low_quality)
+        self.ignore_iof_thr, self.ignore_wrt_candidates = float(ignore_iof_thr), bool(ignore_wrt_candidates)
+        self.gpu_assign_thr = gpu_assign_thr          # ignored: see the class docstring
+
+    def _boxes(self, t: Tensor, what: str, dims) -> Tensor:
+        if not isinstance(t, torch.Tensor) or t.dim() not in dims or t.shape[-1] < self.k:
+            raise ValueError(f"MaxIoUAssigner ({self.iou_calculator}): {what}: a tensor of rows of at least {self.k} columns expected, got "
+                             f"{tuple(t.shape) if isinstance(t, torch.Tensor) else type(t)}")
+        return t.detach().float()[..., :self.k]
+
+    def assign_batched(self, boxes: Tensor, gts: Tensor, gt_counts: Optional[Tensor] = None, gt_labels: Optional[Tensor] = None, ignore: Optional[Tensor] = None,
+                       gt_inds: Optional[Tensor] = None, max_overlaps: Optional[Tensor] = None, labels: Optional[Tensor] = None, workspace: Optional[Tensor] = None):
+        """B images in one call, nothing synchronised: ``boxes`` [N, k] (shared, e.g. anchors) or [B, N, k]; ``gts`` [B, Gmax, k] with ``gt_counts`` int32 [B] valid
+        rows per image (rows past the count are never read); ``gt_labels`` int64 [B, Gmax]; ``ignore`` bool / uint8 [B, N].  Returns ``(gt_inds, max_overlaps,
+        labels)``, each [B, N] (``labels`` None without ``gt_labels``).  The output buffers and the workspace may be supplied: a captured call allocates nothing."""
+        boxes, gts = self._boxes(boxes, "boxes", (2, 3)), self._boxes(gts, "gts", (3,))
+        if gt_counts is not None and gt_counts.dtype != torch.int32:
+            gt_counts = gt_counts.to(torch.int32)
+        if gt_labels is not None and gt_labels.dtype != torch.int64:
+            gt_labels = gt_labels.to(torch.int64)
+        return ops.max_iou_assign(boxes, gts, self.pos_iou_thr, (self.neg_lo, self.neg_hi), self.min_pos_iou,
+                                  gt_counts, gt_labels, ignore, self.match_low_quality, self.gt_max_assign_all, gt_inds, max_overlaps, labels, workspace)
+
+    def assign(self, bboxes: Tensor, gt_bboxes: Tensor, gt_bboxes_ignore: Optional[Tensor] = None, gt_labels: Optional[Tensor] = None) -> AssignResult:
+        """upstream's ``assign(bboxes, gt_bboxes, gt_bboxes_ignore=None, gt_labels=None)`` for one image: ``bboxes`` [N, >= k], ``gt_bboxes`` [G, >= k]"""
+        boxes, gts = self._boxes(bboxes, "bboxes", (2,)), self._boxes(gt_bboxes, "gt_bboxes", (2,))
+        N, G = int(boxes.shape[0]), int(gts.shape[0])
+        ignore = None
+        if self.ignore_iof_thr > 0 and gt_bboxes_ignore is not None and gt_bboxes_ignore.numel() > 0 and N > 0:
+            regions = self._boxes(gt_bboxes_ignore, "gt_bboxes_ignore", (2,))
+            overlaps = ops.obb_overlaps if self.k == 5 else ops.bbox_overlaps
+            if self.ignore_wrt_candidates:
+                worst = overlaps(boxes, regions, "iof").max(dim=1)[0]
+            else:
+                worst = overlaps(regions, boxes, "iof").max(dim=0)[0]
+            ignore = (worst > self.ignore_iof_thr)[None]
+        if N == 0:          # (no launch; works without a GPU)
+            empty = boxes.new_zeros((0,), dtype=torch.int64)
+            return AssignResult(G, empty, boxes.new_zeros((0,)), None if gt_labels is None else empty.clone())
+        lab = None if gt_labels is None else gt_labels.reshape(1, G)
+        gt_inds, max_overlaps, labels = self.assign_batched(boxes, gts[None], None, lab, ignore)
+        return AssignResult(G, gt_inds[0], max_overlaps[0], None if labels is None else labels[0])

@@ -1637,6 +1637,141 @@ def nms(boxes: Tensor, scores: Tensor, iou_thr: float, groups: Optional[Tensor] 
 
 
 # -------------------------------------------------------------------------------------------
+# Horizontal overlaps and max-IoU assignment without the matrix (csrc/assign.hip; lemevit_amd/detection.py has MaxIoUAssigner)
+# -------------------------------------------------------------------------------------------
+def _rows(fn: str, what: str, t: Tensor, k: int, names: str) -> Tuple[int, int]:
+    """(data pointer, row stride in floats) of a float32 box tensor [N, >= k] read in place: unit column stride, any row stride >= k"""
+    if t.dim() != 2 or t.shape[1] < k or t.dtype != torch.float32:
+        raise ValueError(f"{fn}: {what}: float32 [N, >= {k}] rows ({names}) expected, got {t.dtype} {tuple(t.shape)}")
+    if not t.is_cuda:
+        raise RuntimeError("lemevit_amd: tensors must be on the GPU (no CPU fallback exists)")
+    n = int(t.shape[0])
+    if n > 1 and (t.stride(1) != 1 or t.stride(0) < k):
+        raise ValueError(f"{fn}: {what}: strides {tuple(t.stride())}: a unit column stride and a row stride >= {k} are needed (call .contiguous())")
+    if n == 1 and t.stride(1) != 1:
+        raise ValueError(f"{fn}: {what}: strides {tuple(t.stride())}: a unit column stride is needed (call .contiguous())")
+    return t.data_ptr(), (int(t.stride(0)) if n > 1 else max(int(t.stride(0)), k))
+
+
+def bbox_overlaps(boxes1: Tensor, boxes2: Tensor, mode: str = "iou", is_aligned: bool = False, out: Optional[Tensor] = None) -> Tensor:
+    """lmv_bbox_overlaps (one launch): IoU (``mode='iou'``) or IoF (``'iof'``: intersection over the area of ``boxes1``) of float32 axis-aligned boxes
+    ``(x1, y1, x2, y2)`` by upstream's rule (no "+ 1", eps 1e-6).  Returns float32 [N, M], or [N, 1] from the N pairs with ``is_aligned``; every element is written
+    once.  ``out``: a caller-supplied contiguous buffer of that shape (a captured call allocates nothing).  include/lemevit_hip.h has the rule."""
+    fn = "bbox_overlaps"
+    if mode not in ("iou", "iof"):
+        raise ValueError(f"{fn}: mode must be 'iou' or 'iof', got {mode!r}")
+    p1, s1 = _rows(fn, "boxes1", boxes1, 4, "x1, y1, x2, y2")
+    p2, s2 = _rows(fn, "boxes2", boxes2, 4, "x1, y1, x2, y2")
+    N, M = int(boxes1.shape[0]), int(boxes2.shape[0])
+    if is_aligned and N != M:
+        raise ValueError(f"{fn}: aligned pairs need as many boxes on both sides, got {N} and {M}")
+    if boxes2.device != boxes1.device:
+        raise ValueError(f"{fn}: the two box tensors are on different devices")
+    shape = (N, 1) if is_aligned else (N, M)
+    if out is None:
+        out = torch.empty(shape, device=boxes1.device, dtype=torch.float32)
+    elif out.dtype != torch.float32 or tuple(out.shape) != shape or out.device != boxes1.device or not out.is_contiguous():
+        raise TypeError(f"{fn}: out must be a contiguous float32 tensor {shape} on the boxes' device")
+    check(lib.lmv_bbox_overlaps(p1, s1, N, p2, s2, M, _lib.OBB_IOF if mode == "iof" else _lib.OBB_IOU, 1 if is_aligned else 0, out.data_ptr(), _stream()), "lmv_bbox_overlaps")
+    return out
+
+
+def max_iou_assign_workspace_bytes(B: int, Gmax: int) -> int:
+    """lmv_max_iou_assign_workspace_bytes: B (Gmax + 1) 8 bytes, the table of per-ground-truth maxima of ``max_iou_assign``"""
+    if not 1 <= int(B) <= _lib.ASSIGN_MAX_BATCH or not 0 <= int(Gmax) <= _lib.ASSIGN_MAX_GT:
+        raise ValueError(f"max_iou_assign_workspace_bytes: B = {B} outside 1 .. {_lib.ASSIGN_MAX_BATCH} or Gmax = {Gmax} outside 0 .. {_lib.ASSIGN_MAX_GT}")
+    return int(lib.lmv_max_iou_assign_workspace_bytes(int(B), int(Gmax)))
+
+
+def assign_thresholds(fn: str, pos_iou_thr, neg_iou_thr, min_pos_iou) -> Tuple[float, float, float, float]:
+    """(pos, neg_lo, neg_hi, min_pos) from upstream's arguments: a float ``neg_iou_thr`` is the range [0, neg_iou_thr), a tuple gives both bounds"""
+    if isinstance(neg_iou_thr, (tuple, list)):
+        if len(neg_iou_thr) != 2:
+            raise ValueError(f"{fn}: a tuple neg_iou_thr has two entries (lower, upper), got {neg_iou_thr!r}")
+        lo, hi = float(neg_iou_thr[0]), float(neg_iou_thr[1])
+    else:
+        lo, hi = 0.0, float(neg_iou_thr)
+    pos, mp = float(pos_iou_thr), float(min_pos_iou)
+    if any(math.isnan(x) for x in (pos, lo, hi, mp)):
+        raise ValueError(f"{fn}: a NaN threshold (pos_iou_thr = {pos}, neg_iou_thr = {neg_iou_thr!r}, min_pos_iou = {mp})")
+    if lo > hi:
+        raise ValueError(f"{fn}: neg_iou_thr = {neg_iou_thr!r}: the lower bound is above the upper one")
+    return pos, lo, hi, mp
+
+
+def max_iou_assign(boxes: Tensor, gts: Tensor, pos_iou_thr: float, neg_iou_thr, min_pos_iou: float = 0.0, gt_counts: Optional[Tensor] = None,
+                   gt_labels: Optional[Tensor] = None, ignore: Optional[Tensor] = None, match_low_quality: bool = True, gt_max_assign_all: bool = True,
+                   gt_inds: Optional[Tensor] = None, max_overlaps: Optional[Tensor] = None, labels: Optional[Tensor] = None,
+                   workspace: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Optional[Tensor]]:
+    """lmv_max_iou_assign (at most two launches and a memset, no host round trip, no [N, G] matrix): upstream's MaxIoUAssigner rules for B images at once.
+    ``boxes``: float32 [N, k] shared by all images or [B, N, k]; ``gts``: float32 [B, Gmax, k]; k = 4 (x1, y1, x2, y2) or 5 (cx, cy, w, h, theta), taken from
+    ``gts``; rows are read in place through their row stride.  ``gt_counts``: int32 [B] on the device, the valid rows per image (None: all); ``gt_labels``: int64
+    [B, Gmax]; ``ignore``: uint8 or bool [B, N].  Returns ``(gt_inds int64 [B, N], max_overlaps float32 [B, N], labels int64 [B, N] or None)``; ``gt_inds``,
+    ``max_overlaps``, ``labels`` and ``workspace`` (uint8, ``max_iou_assign_workspace_bytes(B, Gmax)``) may be supplied so that a captured call allocates nothing.
+    include/lemevit_hip.h has the rules."""
+    fn = "max_iou_assign"
+    pos, lo, hi, mp = assign_thresholds(fn, pos_iou_thr, neg_iou_thr, min_pos_iou)
+    if gts.dim() != 3 or gts.shape[2] not in (4, 5) or gts.dtype != torch.float32:
+        raise ValueError(f"{fn}: gts: float32 [B, Gmax, 4] (x1, y1, x2, y2) or [B, Gmax, 5] (cx, cy, w, h, theta) expected, got {gts.dtype} {tuple(gts.shape)}")
+    B, Gmax, k = (int(x) for x in gts.shape)
+    if boxes.dim() not in (2, 3) or boxes.shape[-1] != k or boxes.dtype != torch.float32 or (boxes.dim() == 3 and boxes.shape[0] != B):
+        raise ValueError(f"{fn}: boxes: float32 [N, {k}] or [{B}, N, {k}] expected, got {boxes.dtype} {tuple(boxes.shape)}")
+    if B < 1 or B > _lib.ASSIGN_MAX_BATCH:
+        raise ValueError(f"{fn}: B = {B} images outside 1 .. {_lib.ASSIGN_MAX_BATCH}")
+    if Gmax > _lib.ASSIGN_MAX_GT:
+        raise ValueError(f"{fn}: Gmax = {Gmax} ground truths, at most {_lib.ASSIGN_MAX_GT}")
+    N, dev = int(boxes.shape[-2]), boxes.device
+    if N > _lib.OBB_MAX_BOXES:
+        raise ValueError(f"{fn}: N = {N} boxes, at most {_lib.OBB_MAX_BOXES}")
+    if not boxes.is_cuda or not gts.is_cuda:
+        raise RuntimeError("lemevit_amd: tensors must be on the GPU (no CPU fallback exists)")
+    if gts.device != dev:
+        raise ValueError(f"{fn}: boxes and gts are on different devices")
+    if N > 0 and (boxes.stride(-1) != 1 or (N > 1 and boxes.stride(-2) < k)):
+        raise ValueError(f"{fn}: boxes: strides {tuple(boxes.stride())}: a unit column stride and a row stride >= {k} are needed (call .contiguous())")
+    bs = max(int(boxes.stride(-2)), k)
+    bb = 0
+    if boxes.dim() == 3 and B > 1:
+        bb = int(boxes.stride(0))
+        if bb < 0 or (bb != 0 and N > 0 and bb < (N - 1) * bs + k):
+            raise ValueError(f"{fn}: boxes: a batch stride of {bb} floats overlaps the rows of an image (call .contiguous())")
+    if Gmax > 0 and (gts.stride(2) != 1 or (Gmax > 1 and gts.stride(1) < k) or (B > 1 and gts.stride(0) != Gmax * max(int(gts.stride(1)), k))):
+        raise ValueError(f"{fn}: gts: strides {tuple(gts.stride())}: a unit column stride, a row stride >= {k} and images Gmax rows apart are needed (call .contiguous())")
+    gs = max(int(gts.stride(1)), k) if Gmax > 1 else (max(int(gts.stride(0)), k) if B > 1 and Gmax == 1 else k)
+    if gt_counts is not None and (gt_counts.dtype != torch.int32 or tuple(gt_counts.shape) != (B,) or gt_counts.device != dev or not gt_counts.is_contiguous()):
+        raise TypeError(f"{fn}: gt_counts must be a contiguous int32 vector [{B}] on the boxes' device")
+    if gt_labels is not None and (gt_labels.dtype != torch.int64 or tuple(gt_labels.shape) != (B, Gmax) or gt_labels.device != dev or not gt_labels.is_contiguous()):
+        raise TypeError(f"{fn}: gt_labels must be a contiguous int64 tensor [{B}, {Gmax}] on the boxes' device")
+    if ignore is not None:
+        if ignore.dtype == torch.bool:
+            ignore = ignore.view(torch.uint8)
+        if ignore.dtype != torch.uint8 or tuple(ignore.shape) != (B, N) or ignore.device != dev or not ignore.is_contiguous():
+            raise TypeError(f"{fn}: ignore must be a contiguous uint8 / bool tensor [{B}, {N}] on the boxes' device")
+
+    def buf(t, name, dtype):
+        if t is None:
+            return torch.empty((B, N), device=dev, dtype=dtype)
+        if t.dtype != dtype or tuple(t.shape) != (B, N) or t.device != dev or not t.is_contiguous():
+            raise TypeError(f"{fn}: {name} must be a contiguous {dtype} tensor [{B}, {N}] on the boxes' device")
+        return t
+    gt_inds, max_overlaps = buf(gt_inds, "gt_inds", torch.int64), buf(max_overlaps, "max_overlaps", torch.float32)
+    if gt_labels is not None:
+        labels = buf(labels, "labels", torch.int64)
+    elif labels is not None:
+        raise ValueError(f"{fn}: a labels buffer without gt_labels")
+    need = max_iou_assign_workspace_bytes(B, Gmax)
+    if workspace is None:
+        workspace = torch.empty((need,), device=dev, dtype=torch.uint8)
+    elif workspace.dtype != torch.uint8 or workspace.device != dev or not workspace.is_contiguous() or workspace.numel() < need:
+        raise ValueError(f"{fn}: the workspace must hold {need} bytes (uint8) on the boxes' device (ops.max_iou_assign_workspace_bytes)")
+    check(lib.lmv_max_iou_assign(_lib.ASSIGN_ROTATED if k == 5 else _lib.ASSIGN_HORIZONTAL, boxes.data_ptr(), bs, bb, N, gts.data_ptr(), gs, B, Gmax, _ptr(gt_counts),
+                                 _ptr(gt_labels), _ptr(ignore), pos, lo, hi, mp, 1 if match_low_quality else 0, 1 if gt_max_assign_all else 0, workspace.data_ptr(),
+                                 workspace.numel(), gt_inds.data_ptr(), max_overlaps.data_ptr(), None if labels is None else labels.data_ptr(), _stream()),
+          "lmv_max_iou_assign")
+    return gt_inds, max_overlaps, labels
+
+
+# -------------------------------------------------------------------------------------------
 # A run of "S" blocks as one persistent launch (csrc/sstage.hip; inference, bf16)
 # -------------------------------------------------------------------------------------------
 def sstage_supported(C_: int, heads: int, hidden: int, H: int, W: int, M: int, dtype: torch.dtype) -> bool:
