@@ -800,7 +800,9 @@ int lmv_rroi_bwd(const void* plan, int R, const void* dy, const lmv_rroi_level* 
  * once, stores run along M.  A workgroup owns a 16 x 64 tile and stages the tile's box records in LDS.  N == 0 or M == 0 launches nothing.
  *
  * lmv_obb_nms -- two launches.  order: int64 [N], the STABLE descending sort of the scores (the caller's; boxes, scores and groups are gathered through it, an
- * entry outside [0, N) names no box).  groups: nullable int32 [N].  A box is a CANDIDATE iff score > score_thr (-inf: every score that is not NaN or -inf) and
+ * entry outside [0, N) names no box: that rank is never kept and suppresses nothing).  The launches rank by `order` ALONE -- entry r is rank r; the scores are read
+ * only for the candidate rule -- so a permutation that is not the score sort is a legal ranking of the caller's own (tests/test_det_limits_gpu.py runs all three:
+ * the default sort passed in, entries that name no box, another permutation).  groups: nullable int32 [N].  A box is a CANDIDATE iff score > score_thr (-inf: every score that is not NaN or -inf) and
  * w >= 0.001 and h >= 0.001 (and all five entries are finite).  Non-candidates are never kept and never suppress.  A kept box suppresses every lower-ranked
  * candidate of its group with IoU > iou_thr (strict, as the reference's CUDA kernel).
  *     mask launch    64 x 64 tiles of the rank-ordered boxes, upper triangle; a wave64 owns rows of the tile, lane j evaluates (row, column j) and the ballot is

@@ -58,6 +58,10 @@ READ_FROM = min(BOX_THRESHOLDS + GT_THRESHOLDS) - MARGIN          # below it no 
 CHUNK = 64                                     # LMV_ASSIGN_GT_CHUNK (tests/test_assign_cpu.py holds it to _lib.ASSIGN_GT_CHUNK)
 # (N, G): every N of {1, 63, 64, 65, 255, 256, 257, 1000} and every G of {0, 1, CHUNK - 1, CHUNK, CHUNK + 1}
 SHAPES = [(1, 1), (1, CHUNK + 1), (63, 0), (64, CHUNK - 1), (65, CHUNK), (255, CHUNK + 1), (256, 1), (257, CHUNK + 1), (1000, CHUNK), (1000, CHUNK + 1)]
+# many ground truths (tests/test_det_limits_*.py): G = 2 CHUNK + 1 is the smallest G of three chunks, G = 257 the smallest at which the final launch's gather loop over
+# the table (256 threads) makes a second trip, G = 1000 is a crowded DOTA crop; the last line is the batched case B = 3, gt_counts = (300, 0, 257)
+SHAPES_MANY = [(257, 2 * CHUNK + 1), (1000, 256), (1000, 257), (300, 1000)]
+BATCH_MANY = (300, (300, 0, 257))
 KINDS = ("horizontal", "rotated")
 
 
@@ -198,9 +202,24 @@ def batch_case(kind: str, N: int, G: int):
                 ignore=torch.stack([c["ignore"] for c in cases]))
 
 
+def batch_many(kind: str):
+    """``batch_case`` with BATCH_MANY's counts: B = 3 images of N = 300 boxes with gt_counts = (300, 0, 257) and Gmax = 300 -- five chunks, a second trip of the
+    gather loop, an image without ground truths between them, and a count below Gmax (NaN padding rows)."""
+    N, counts = BATCH_MANY
+    cases = [assign_case(kind, N, g, seed) for seed, g in enumerate(counts)]
+    k, G = cases[0]["k"], max(counts)
+    gts = torch.full((3, G, k), float("nan"))
+    labels = torch.full((3, G), -77, dtype=torch.int64)
+    for b, c in enumerate(cases):
+        gts[b, :c["G"]] = c["gts"]
+        labels[b, :c["G"]] = c["labels"]
+    return dict(cases=cases, boxes=torch.stack([c["boxes"] for c in cases]), gts=gts, counts=torch.tensor(counts, dtype=torch.int32), labels=labels,
+                ignore=torch.stack([c["ignore"] for c in cases]))
+
+
 if __name__ == "__main__":
     for kind in KINDS:
-        for N, G in SHAPES:
-            c = assign_case(kind, N, G)
-            print(f"{kind:10s} N {N:5d} G {G:3d}: redrawn {c['redrawn']:4d}  margins " + "  ".join(f"{k} {v:.2e}" for k, v in c["margins"].items()) +
+        for N, G, seed in [(n, g, 0) for n, g in SHAPES + SHAPES_MANY] + [(BATCH_MANY[0], g, seed) for seed, g in enumerate(BATCH_MANY[1])]:
+            c = assign_case(kind, N, G, seed)
+            print(f"{kind:10s} N {N:5d} G {G:4d}: redrawn {c['redrawn']:4d}  margins " + "  ".join(f"{k} {v:.2e}" for k, v in c["margins"].items()) +
                   "   with ignore " + "  ".join(f"{k} {v:.2e}" for k, v in c["margins_ignore"].items()))
