@@ -973,6 +973,79 @@ int lmv_max_iou_assign(int kind, const float* boxes, int box_stride, int64_t box
                        void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Box coders of the Oriented R-CNN configs (csrc/coder.hip): MidpointOffsetCoder (the RPN head: anchors (x1, y1, x2, y2), ground truths / proposals
+ * (cx, cy, w, h, theta), D = 6 deltas, target_stds (1, 1, 1, 1, 0.5, 0.5)) and OBB2OBBDeltaXYWHTCoder (the R-CNN head: both sides (cx, cy, w, h, theta), D = 5 deltas,
+ * target_stds (0.1, 0.1, 0.2, 0.2, 0.1)).  Their sources are NOT part of the reference tree (only their names in the configs are): the rules below restate upstream
+ * (OBBDetection on mmdet 2.x) and are the specification.  An addition to ABI 14: callers detect it by symbol.  One launch per call, one thread per output row, 256
+ * threads per workgroup, operands read in place through their strides, no atomics, nothing synchronised, capturable; every output element is written exactly once.
+ * There is ONE device function per rule and every entry point inlines it (fp contraction off): the plain and the gathering form of an operation agree bit for bit,
+ * and so do two calls.
+ *
+ * kind: LMV_CODER_MIDPOINT (k = 4 box columns, D = 6) or LMV_CODER_OBB2OBB (k = 5, D = 5).  means / stds: HOST arrays of D floats, read during the call and passed
+ * to the kernel by value (nothing of them is read later: a captured call keeps the values it was captured with).
+ *
+ * Conventions (theta in radians, fp32 throughout, IEEE arithmetic):
+ *     regular_theta(t) = t + pi/2 - pi floor((t + pi/2) / pi) - pi/2          a floored modulo: the result is in [-pi/2, pi/2)
+ *     regular_obb(x, y, w, h, t): if w > h keep (w, h, t), else (h, w, t + pi/2); then t = regular_theta(t)
+ *     corners of (cx, cy, w, h, t) with c = cos t, s = sin t, v1 = (w/2 c, -w/2 s), v2 = (-h/2 s, -h/2 c):
+ *         p1 = ctr + v1 + v2,  p2 = ctr + v1 - v2,  p3 = ctr - v1 - v2,  p4 = ctr - v1 + v2
+ *     hull: ctr -+ (|w/2 c| + |h/2 s|, |w/2 s| + |h/2 c|)
+ *     normalisation: encode ends with (delta - mean) / std, decode begins with delta std + mean
+ *     size clamp: decode clamps dw, dh to +-|log(wh_ratio_clip)| (upstream's default wh_ratio_clip = 16 / 1000)
+ * Midpoint encode (anchor (x1, y1, x2, y2), ground truth obb): px, py the anchor's centre, pw, ph its sides; gx, gy, gw, gh the centre and sides of the ground
+ *     truth's hull; ga = max{ x_i : |y_i - min_j y_j| <= 0.1 } over the four corners (the x of the top vertex; the rightmost of two on a level top edge);
+ *     gb = max{ y_i : |x_i - max_j x_j| <= 0.1 };   deltas = ((gx - px)/pw, (gy - py)/ph, log(gw/pw), log(gh/ph), (ga - gx)/gw, (gb - gy)/gh)
+ * Midpoint decode: gw = pw exp(dw), gh = ph exp(dh), gx = px + pw dx, gy = py + ph dy;  x1, y1, x2, y2 = gx -+ gw/2, gy -+ gh/2;  da, db clamped to [-0.5, 0.5];
+ *     the four vertices (gx + da gw, y1), (x2, gy + db gh), (gx - da gw, y2), (x1, gy - db gh); each is moved along its ray from (gx, gy) to the largest of the four
+ *     distances to (gx, gy) (the parallelogram becomes a rectangle); theta = atan2(-(y_2 - y_1), x_2 - x_1) on the first two moved vertices; the centre is the mean
+ *     of the four; with c = cos theta, s = sin theta each centred vertex (ux, uy) goes to (ux c - uy s, ux s + uy c); w, h are the extents (max - min) of the first
+ *     and second rotated coordinate; the result is regular_obb(centre, w, h, theta).  Rotated proposals are not clipped to an image shape.
+ * OBB2OBB encode (proposal p, ground truth g): d1 = regular_theta(gt - pt), d2 = regular_theta(gt - pt + pi/2); if |d1| < |d2| then (gw', gh', dt) = (gw, gh, d1)
+ *     else (gh, gw, d2); with c = cos(-pt), s = sin(-pt): dx = (c (gx - px) + s (gy - py)) / pw, dy = (-s (gx - px) + c (gy - py)) / ph, dw = log(gw'/pw),
+ *     dh = log(gh'/ph);   deltas = (dx, dy, dw, dh, dt)
+ * OBB2OBB decode: gx = dx pw c - dy ph s + px, gy = dx pw s + dy ph c + py (the same c, s), gw = pw exp(dw), gh = ph exp(dh), gt = regular_theta(dt + pt); the
+ *     result is regular_obb(gx, gy, gw, gh, gt)
+ * Data rules: a degenerate anchor or a non-finite input gives whatever the formulas give (inf / NaN), as upstream; nothing traps, nothing is read out of bounds.
+ * Only the non-live rows of the encode are defined to be zero.
+ *
+ * lmv_box_encode -- targets and weights of B images in one launch.
+ *     boxes        fp32 [N, k] shared by all images (box_batch_stride == 0) or [B, N, k] (box_batch_stride: floats between the images' box sets), rows through
+ *                  box_stride >= k
+ *     gts          fp32 [B, Gmax, 5], rows through gt_stride >= 5 (an image's rows are Gmax gt_stride floats apart)
+ *     gt_counts    nullable int32 [B] ON THE DEVICE, clamped to 0 .. Gmax by the kernel; null: Gmax everywhere.  No row at or past the count is ever read
+ *     gt_inds      nullable int64 [B, N] (what lmv_max_iou_assign writes): row (b, n) is encoded against gts[b, gt_inds[b, n] - 1].  Null: the ALIGNED form, row n
+ *                  is paired with ground-truth row n (as if gt_inds[b, n] = n + 1; needs Gmax == N)
+ *     sampled      nullable uint8 [B, N]: a sampler's mask
+ *     targets      fp32 [B, N, D];   weights fp32 [B, N]
+ * Row (b, n) is LIVE if, and only if, 1 <= gt_inds[b, n] <= count[b] and (sampled given) sampled[b, n] != 0: its weight is 1 and its D targets the normalised
+ * deltas.  Every other row has weight 0 and D targets of exactly +0.0.
+ *
+ * lmv_box_decode -- boxes fp32 [N, k] through box_stride; deltas fp32 [N, D C] through delta_stride >= D C floats per row, C >= 1 delta sets per row (upstream's
+ * 0::D striding, class-specific regression: set c of row n is deltas[n, c D .. c D + D - 1] and is decoded against box n); out fp32 [N, 5 C] contiguous.  One
+ * thread per (row, set).
+ *
+ * lmv_box_decode_map -- the proposals of one level from a head's regression output read in place: map fp32 [A D, H, W] with arbitrary channel / row / column
+ * strides (in floats, map_stride_c / _h / _w), index int64 [K] on the device.  Row r = (h W + w) A + a of the level has delta d at channel a D + d, position (h, w)
+ * -- the order of permute(1, 2, 0).reshape(-1, D).  Output row i decodes row r = index[i]: out fp32 [K, 5] contiguous.  boxes: [K, k], row i (gathered == 1: already
+ * gathered), or [H W A, k], row index[i] (gathered == 0).  An index outside 0 .. H W A - 1 writes a row of zeros and reads nothing.
+ *
+ * Limits: N, K (and Gmax) <= LMV_OBB_MAX_BOXES, B in 1 .. LMV_ASSIGN_MAX_BATCH, 1 <= C <= LMV_CODER_MAX_SETS, H W A <= 2^31 - 1.
+ * Refused with LMV_ERR_SHAPE and a message that starts "box_encode" / "box_decode" / "box_decode_map", before any launch: an unknown kind, sizes outside the limits,
+ * negative sizes, row strides below k / 5 / D C, a negative batch stride, the aligned form with Gmax != N, null means / stds, a NaN mean or std, a wh_ratio_clip
+ * that is not a positive finite number, a gathered flag other than 0 / 1, null pointers with non-zero sizes, misaligned buffers.  N == 0 / K == 0 launches nothing.
+ * ------------------------------------------------------------------------------------------ */
+#define LMV_CODER_MIDPOINT 0
+#define LMV_CODER_OBB2OBB 1
+#define LMV_CODER_MAX_SETS 128
+int lmv_box_encode(int kind, const float* boxes, int box_stride, int64_t box_batch_stride, int N, const float* gts, int gt_stride, int B, int Gmax,
+                   const int32_t* gt_counts, const int64_t* gt_inds, const uint8_t* sampled, const float* means, const float* stds, float* targets, float* weights,
+                   void* stream);
+int lmv_box_decode(int kind, const float* boxes, int box_stride, const float* deltas, int64_t delta_stride, int N, int C, const float* means, const float* stds,
+                   float wh_ratio_clip, float* out, void* stream);
+int lmv_box_decode_map(int kind, const float* boxes, int box_stride, int gathered, const float* map, int A, int H, int W, int64_t map_stride_c, int64_t map_stride_h,
+                       int64_t map_stride_w, const int64_t* index, int K, const float* means, const float* stds, float wh_ratio_clip, float* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Whole-block schedules: ONE call enqueues every launch of a LeMeBlock (models/lemevit.py:500-660) on token-major tensors
  * x [B, H*W, C], c [B, M, C] -- `LeMeBlock.forward_with_x` ("S", :615-650), `forward_with_xc` ("D", :542-582), `forward_with_c`
  * ("C", :584-613; x is returned untouched by the caller, x_out / dx_out may be NULL).  Replaces the ~12 / ~30 per-op calls a Python

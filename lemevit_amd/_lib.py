@@ -35,6 +35,7 @@ OBB_IOU, OBB_IOF, OBB_MAX_BOXES, OBB_NMS_MAX = 0, 1, 1 << 20, 16384          # L
 ROI_MAX_LEVELS, ROI_MAX_GRID, ROI_MAX_BINS, ROI_MAX_EXTENT, ROI_HEADER_BYTES, ROI_BIN_BYTES = 5, 128, 256, 8192, 48, 16          # LMV_ROI_*
 NMS_MAX = 16384          # LMV_NMS_MAX
 ASSIGN_HORIZONTAL, ASSIGN_ROTATED, ASSIGN_GT_CHUNK, ASSIGN_MAX_GT, ASSIGN_MAX_BATCH = 0, 1, 64, 16384, 4096          # LMV_ASSIGN_*
+CODER_MIDPOINT, CODER_OBB2OBB, CODER_MAX_SETS = 0, 1, 128          # LMV_CODER_*
 
 
 class LinearProblem(C.Structure):
@@ -234,6 +235,9 @@ SIGNATURES = {
     "lmv_bbox_overlaps": (_I, [_P, _I, _I, _P, _I, _I, _I, _I, _P, _P]),
     "lmv_max_iou_assign_workspace_bytes": (_Z, [_I, _I]),
     "lmv_max_iou_assign": (_I, [_I, _P, _I, _L, _I, _P, _I, _I, _I, _P, _P, _P, _F, _F, _F, _F, _I, _I, _P, _Z, _P, _P, _P, _P]),
+    "lmv_box_encode": (_I, [_I, _P, _I, _L, _I, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "lmv_box_decode": (_I, [_I, _P, _I, _P, _L, _I, _I, _P, _P, _F, _P, _P]),
+    "lmv_box_decode_map": (_I, [_I, _P, _I, _I, _P, _I, _I, _I, _L, _L, _L, _P, _I, _P, _P, _F, _P, _P]),
     "lmv_block_arena_bytes": (_Z, [C.POINTER(BlockDesc)]),
     "lmv_block_bwd_scratch_bytes": (_Z, [C.POINTER(BlockDesc)]),
     "lmv_block_fwd": (_I, [C.POINTER(BlockDesc), _P, _P, _P, _P, _P, _Z, _I, _P]),

@@ -42,9 +42,25 @@ assigners of the Oriented R-CNN configs, under upstream mmdet 2.x's names (their
 
 Per box a maximum and an argmax over the ground truths, per ground truth an integer maximum over the boxes: at most two launches, no floating-point atomics, two
 calls agree bit for bit; ``gpu_assign_thr`` is accepted and ignored (the assignment never leaves the device).  One deliberate difference: an ignored box is -1 also
-when the image has no ground truth.  Not provided: the samplers (``RandomSampler``, ``OBBRandomSampler``), target encoding (``MidpointOffsetCoder``,
-``OBB2OBBDeltaXYWHTCoder``), other assigners, fp16 / bf16 boxes, gradients.  ``reference_bbox_overlaps`` / ``reference_max_iou_assign`` are the numpy float64
-oracles, ``bbox_overlaps_torch`` / ``max_iou_assign_torch`` the stock-PyTorch formulations on the whole matrix.
+when the image has no ground truth.  Not provided: the samplers (``RandomSampler``, ``OBBRandomSampler``), other assigners, fp16 / bf16 boxes, gradients.
+``reference_bbox_overlaps`` / ``reference_max_iou_assign`` are the numpy float64 oracles, ``bbox_overlaps_torch`` / ``max_iou_assign_torch`` the stock-PyTorch
+formulations on the whole matrix.
+
+The box coders of both heads of those configs (csrc/coder.hip), under upstream's names and signatures (their sources are not part of the reference tree either:
+include/lemevit_hip.h restates the rules) -- what connects ``assign_batched`` to a loss and an RPN head's output to ``obb_nms_padded`` / ``RotatedRoIExtractor``:
+
+    from lemevit_amd.detection import MidpointOffsetCoder, OBB2OBBDeltaXYWHTCoder
+    rpn_coder = MidpointOffsetCoder(target_stds=[1, 1, 1, 1, 0.5, 0.5])          # anchors (x1, y1, x2, y2) <-> obbs (cx, cy, w, h, theta), 6 deltas
+    rcnn_coder = OBB2OBBDeltaXYWHTCoder(target_stds=[0.1, 0.1, 0.2, 0.2, 0.1])          # obbs <-> obbs, 5 deltas
+    deltas = rpn_coder.encode(anchors, gt_obbs);  obbs = rcnn_coder.decode(rois, bbox_pred)          # upstream's signatures; decode takes [N, 5 C] class-wise deltas
+    targets, weights = rpn_coder.encode_assigned(anchors, gts, gt_inds, gt_counts)          # B images from assign_batched's gt_inds: no nonzero, no gather
+    proposals = rpn_coder.decode_map(anchors, rpn_bbox_pred[b], topk_inds)          # [A 6, H, W] read in place: no permute(1, 2, 0).reshape(-1, 6) copy
+
+One launch per call, nothing synchronised, capturable, two calls agree bit for bit, and the gathering forms equal the plain ones bit for bit.  Not provided: the
+samplers (``encode_assigned`` takes a sampler's mask as ``sampled``), ``DeltaXYWHBBoxCoder`` and the other coders of the Mask R-CNN config, gradients through
+decode, fp16 / bf16 boxes, clipping to ``max_shape`` (accepted and not applied, as upstream does for rotated boxes).  ``reference_midpoint_encode`` / ``_decode``,
+``reference_obb2obb_encode`` / ``_decode``, ``reference_encode_assigned`` and ``reference_obb_corners`` are the numpy float64 oracles, ``midpoint_encode_torch`` /
+``_decode_torch``, ``obb2obb_encode_torch`` / ``_decode_torch``, ``encode_assigned_torch`` and ``decode_map_torch`` the stock-PyTorch formulations.
 """
 from __future__ import annotations
 
@@ -1204,3 +1220,396 @@ class MaxIoUAssigner:
         lab = None if gt_labels is None else gt_labels.reshape(1, G)
         gt_inds, max_overlaps, labels = self.assign_batched(boxes, gts[None], None, lab, ignore)
         return AssignResult(G, gt_inds[0], max_overlaps[0], None if labels is None else labels[0])
+
+
+# -------------------------------------------------------------------------------------------
+# Box coders: MidpointOffsetCoder (RPN head) and OBB2OBBDeltaXYWHTCoder (R-CNN head) (csrc/coder.hip)
+# -------------------------------------------------------------------------------------------
+WH_RATIO_CLIP = 16 / 1000
+
+
+def _as_np(t, cols=None, what="boxes") -> np.ndarray:
+    a = (t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)).astype(np.float64)
+    if cols is not None and (a.ndim != 2 or a.shape[1] != cols):
+        raise ValueError(f"{what}: [N, {cols}] rows expected, got {a.shape}")
+    return a
+
+
+def reference_regular_theta(t):
+    """numpy float64: ``t + pi/2 - pi floor((t + pi/2) / pi) - pi/2``, a floored modulo into [-pi/2, pi/2)"""
+    t = np.asarray(t, dtype=np.float64)
+    return t + math.pi / 2 - math.pi * np.floor((t + math.pi / 2) / math.pi) - math.pi / 2
+
+
+def reference_regular_obb(obbs) -> np.ndarray:
+    """numpy float64 [..., 5]: the canonical form, w >= h (w > h keeps the row, else the sides swap and theta + pi/2) and theta in [-pi/2, pi/2)"""
+    o = np.array(obbs, dtype=np.float64)
+    keep = o[..., 2] > o[..., 3]
+    w, h = np.where(keep, o[..., 2], o[..., 3]), np.where(keep, o[..., 3], o[..., 2])
+    t = reference_regular_theta(np.where(keep, o[..., 4], o[..., 4] + math.pi / 2))
+    return np.stack([o[..., 0], o[..., 1], w, h, t], -1)
+
+
+def reference_obb_corners(obbs) -> np.ndarray:
+    """numpy float64 [N, 4, 2]: the corners p1 .. p4 of rows (cx, cy, w, h, theta) in the coders' order (include/lemevit_hip.h)"""
+    o = _as_np(obbs, 5, "obbs")
+    ctr = o[:, None, :2]
+    c, s = np.cos(o[:, 4]), np.sin(o[:, 4])
+    v1 = np.stack([o[:, 2] / 2 * c, -o[:, 2] / 2 * s], -1)[:, None]
+    v2 = np.stack([-o[:, 3] / 2 * s, -o[:, 3] / 2 * c], -1)[:, None]
+    return np.concatenate([ctr + v1 + v2, ctr + v1 - v2, ctr - v1 - v2, ctr - v1 + v2], 1)
+
+
+def _ref_norm(means, stds, D):
+    m, s = np.asarray(means, dtype=np.float64).reshape(-1), np.asarray(stds, dtype=np.float64).reshape(-1)
+    if m.shape != (D,) or s.shape != (D,):
+        raise ValueError(f"{D} means and {D} stds expected, got {m.shape[0]} and {s.shape[0]}")
+    return m, s
+
+
+def reference_midpoint_encode(bboxes, gt_bboxes, means=(0.0,) * 6, stds=(1.0, 1.0, 1.0, 1.0, 0.5, 0.5)) -> np.ndarray:
+    """The numpy float64 oracle of ``MidpointOffsetCoder.encode``, from the rules of include/lemevit_hip.h: anchors [N, 4] (x1, y1, x2, y2) against ground truths
+    [N, 5] (cx, cy, w, h, theta), row by row -> [N, 6]"""
+    p, g = _as_np(bboxes, 4, "bboxes"), _as_np(gt_bboxes, 5, "gt_bboxes")
+    m, s = _ref_norm(means, stds, 6)
+    out = np.zeros((len(p), 6))
+    corners = reference_obb_corners(g)
+    for n in range(len(p)):
+        px, py, pw, ph = (p[n, 0] + p[n, 2]) / 2, (p[n, 1] + p[n, 3]) / 2, p[n, 2] - p[n, 0], p[n, 3] - p[n, 1]
+        cx, cy, w, h, t = g[n]
+        ex = abs(w / 2 * math.cos(t)) + abs(h / 2 * math.sin(t))
+        ey = abs(w / 2 * math.sin(t)) + abs(h / 2 * math.cos(t))
+        gx, gy, gw, gh = cx, cy, 2 * ex, 2 * ey
+        xs, ys = corners[n, :, 0], corners[n, :, 1]
+        ga = max((x for x, y in zip(xs, ys) if abs(y - ys.min()) <= 0.1), default=-math.inf)
+        gb = max((y for x, y in zip(xs, ys) if abs(x - xs.max()) <= 0.1), default=-math.inf)
+        with np.errstate(all="ignore"):
+            out[n] = [(gx - px) / pw, (gy - py) / ph, np.log(gw / pw), np.log(gh / ph), (ga - gx) / gw, (gb - gy) / gh]
+    return (out - m) / s
+
+
+def reference_midpoint_decode(bboxes, deltas, means=(0.0,) * 6, stds=(1.0, 1.0, 1.0, 1.0, 0.5, 0.5), wh_ratio_clip: float = WH_RATIO_CLIP) -> np.ndarray:
+    """The numpy float64 oracle of ``MidpointOffsetCoder.decode``: anchors [N, 4], deltas [N, 6 C] -> [N, 5 C] canonical rows (cx, cy, w, h, theta)"""
+    p, d = _as_np(bboxes, 4, "bboxes"), _as_np(deltas)
+    m, s = _ref_norm(means, stds, 6)
+    N = len(p)
+    if d.ndim != 2 or d.shape[0] != N or d.shape[1] % 6:
+        raise ValueError(f"deltas: [{N}, 6 C] expected, got {d.shape}")
+    C_ = d.shape[1] // 6
+    clip = abs(math.log(wh_ratio_clip))
+    out = np.zeros((N, C_, 5))
+    with np.errstate(all="ignore"):
+        for n in range(N):
+            px, py, pw, ph = (p[n, 0] + p[n, 2]) / 2, (p[n, 1] + p[n, 3]) / 2, p[n, 2] - p[n, 0], p[n, 3] - p[n, 1]
+            for c in range(C_):
+                dx, dy, dw, dh, da, db = d[n, 6 * c:6 * c + 6] * s + m
+                dw, dh = np.clip(dw, -clip, clip), np.clip(dh, -clip, clip)
+                da, db = np.clip(da, -0.5, 0.5), np.clip(db, -0.5, 0.5)
+                gw, gh, gx, gy = pw * np.exp(dw), ph * np.exp(dh), px + pw * dx, py + ph * dy
+                ctr = np.array([gx, gy])
+                v = np.array([[gx + da * gw, gy - gh / 2], [gx + gw / 2, gy + db * gh], [gx - da * gw, gy + gh / 2], [gx - gw / 2, gy - db * gh]])
+                ray = v - ctr
+                dist = np.hypot(ray[:, 0], ray[:, 1])
+                v = ctr + ray * (dist.max() / dist)[:, None]
+                theta = math.atan2(-(v[1, 1] - v[0, 1]), v[1, 0] - v[0, 0]) if np.isfinite(v[:2]).all() else float("nan")
+                mid = v.mean(0)
+                u = v - mid
+                cs, sn = math.cos(theta), math.sin(theta)
+                r0, r1 = u[:, 0] * cs - u[:, 1] * sn, u[:, 0] * sn + u[:, 1] * cs
+                out[n, c] = [mid[0], mid[1], r0.max() - r0.min(), r1.max() - r1.min(), theta]
+    return reference_regular_obb(out).reshape(N, 5 * C_)
+
+
+def reference_obb2obb_encode(bboxes, gt_bboxes, means=(0.0,) * 5, stds=(1.0,) * 5) -> np.ndarray:
+    """The numpy float64 oracle of ``OBB2OBBDeltaXYWHTCoder.encode``: proposals [N, 5] against ground truths [N, 5], row by row -> [N, 5]"""
+    p, g = _as_np(bboxes, 5, "bboxes"), _as_np(gt_bboxes, 5, "gt_bboxes")
+    m, s = _ref_norm(means, stds, 5)
+    out = np.zeros((len(p), 5))
+    with np.errstate(all="ignore"):
+        for n in range(len(p)):
+            px, py, pw, ph, pt = p[n]
+            gx, gy, gw, gh, gt = g[n]
+            d1, d2 = float(reference_regular_theta(gt - pt)), float(reference_regular_theta(gt - pt + math.pi / 2))
+            if abs(d1) < abs(d2):
+                sw, sh, dt = gw, gh, d1
+            else:
+                sw, sh, dt = gh, gw, d2
+            c, sn = math.cos(-pt), math.sin(-pt)
+            out[n] = [(c * (gx - px) + sn * (gy - py)) / pw, (-sn * (gx - px) + c * (gy - py)) / ph, np.log(sw / pw), np.log(sh / ph), dt]
+    return (out - m) / s
+
+
+def reference_obb2obb_decode(bboxes, deltas, means=(0.0,) * 5, stds=(1.0,) * 5, wh_ratio_clip: float = WH_RATIO_CLIP) -> np.ndarray:
+    """The numpy float64 oracle of ``OBB2OBBDeltaXYWHTCoder.decode``: proposals [N, 5], deltas [N, 5 C] -> [N, 5 C] canonical rows"""
+    p, d = _as_np(bboxes, 5, "bboxes"), _as_np(deltas)
+    m, s = _ref_norm(means, stds, 5)
+    N = len(p)
+    if d.ndim != 2 or d.shape[0] != N or d.shape[1] % 5:
+        raise ValueError(f"deltas: [{N}, 5 C] expected, got {d.shape}")
+    C_ = d.shape[1] // 5
+    clip = abs(math.log(wh_ratio_clip))
+    with np.errstate(all="ignore"):
+        v = d.reshape(N, C_, 5) * s + m
+        px, py, pw, ph, pt = (p[:, None, i] for i in range(5))
+        c, sn = np.cos(-pt), np.sin(-pt)
+        gx = v[..., 0] * pw * c - v[..., 1] * ph * sn + px
+        gy = v[..., 0] * pw * sn + v[..., 1] * ph * c + py
+        gw, gh = pw * np.exp(np.clip(v[..., 2], -clip, clip)), ph * np.exp(np.clip(v[..., 3], -clip, clip))
+        gt = reference_regular_theta(v[..., 4] + pt)
+        return reference_regular_obb(np.stack([gx, gy, gw, gh, gt], -1)).reshape(N, 5 * C_)
+
+
+def reference_encode_assigned(kind: str, boxes, gts, gt_inds, means, stds, gt_counts=None, sampled=None):
+    """The numpy float64 oracle of ``encode_assigned``: ``kind`` 'midpoint' / 'obb2obb'; boxes [N, k] or [B, N, k], gts [B, Gmax, 5], gt_inds [B, N] -> (targets
+    [B, N, D], weights [B, N]).  A row is live iff 1 <= gt_inds <= count (and sampled): weight 1 and the oracle's deltas against ``gts[b, gt_inds - 1]``; every
+    other row is zero with weight 0, and no ground-truth row at or past the count is touched."""
+    enc, k, D = {"midpoint": (reference_midpoint_encode, 4, 6), "obb2obb": (reference_obb2obb_encode, 5, 5)}[kind]
+    g = _as_np(gts)
+    B, Gmax = g.shape[0], g.shape[1]
+    b_ = _as_np(boxes)
+    if b_.ndim == 2:
+        b_ = np.broadcast_to(b_[None], (B,) + b_.shape)
+    ind = np.asarray(gt_inds.cpu() if isinstance(gt_inds, torch.Tensor) else gt_inds).astype(np.int64)
+    N = b_.shape[1]
+    cnt = np.full(B, Gmax) if gt_counts is None else np.clip(np.asarray(gt_counts.cpu() if isinstance(gt_counts, torch.Tensor) else gt_counts).astype(np.int64), 0, Gmax)
+    smp = np.ones((B, N), dtype=bool) if sampled is None else np.asarray(sampled.cpu() if isinstance(sampled, torch.Tensor) else sampled).astype(bool)
+    targets, weights = np.zeros((B, N, D)), np.zeros((B, N))
+    for b in range(B):
+        live = np.nonzero((ind[b] >= 1) & (ind[b] <= cnt[b]) & smp[b])[0]
+        if live.size:
+            targets[b, live] = enc(b_[b, live], g[b, ind[b, live] - 1], means, stds)
+            weights[b, live] = 1.0
+    return targets, weights
+
+
+# ---- the literal stock-PyTorch formulations (upstream's tensor code): what a user writes today; any device, the inputs' dtype ----
+def _regular_theta_torch(theta: Tensor) -> Tensor:
+    return (theta + math.pi / 2) % math.pi - math.pi / 2
+
+
+def _regular_obb_torch(obboxes: Tensor) -> Tensor:
+    x, y, w, h, theta = obboxes.unbind(dim=-1)
+    w_regular, h_regular = torch.where(w > h, w, h), torch.where(w > h, h, w)
+    theta_regular = _regular_theta_torch(torch.where(w > h, theta, theta + math.pi / 2))
+    return torch.stack([x, y, w_regular, h_regular, theta_regular], dim=-1)
+
+
+def midpoint_encode_torch(bboxes: Tensor, gt_bboxes: Tensor, means=(0.0,) * 6, stds=(1.0, 1.0, 1.0, 1.0, 0.5, 0.5)) -> Tensor:
+    """upstream's ``bbox2delta_sp`` in stock tensor ops (about fifty elementwise launches): anchors [N, 4], ground truths [N, 5] -> [N, 6]"""
+    px, py = (bboxes[..., 0] + bboxes[..., 2]) * 0.5, (bboxes[..., 1] + bboxes[..., 3]) * 0.5
+    pw, ph = bboxes[..., 2] - bboxes[..., 0], bboxes[..., 3] - bboxes[..., 1]
+    center, w, h, theta = torch.split(gt_bboxes, [2, 1, 1, 1], dim=-1)
+    Cos, Sin = torch.cos(theta), torch.sin(theta)
+    x_bias, y_bias = torch.abs(w / 2 * Cos) + torch.abs(h / 2 * Sin), torch.abs(w / 2 * Sin) + torch.abs(h / 2 * Cos)
+    bias = torch.cat([x_bias, y_bias], dim=-1)
+    hbb = torch.cat([center - bias, center + bias], dim=-1)
+    vector1, vector2 = torch.cat([w / 2 * Cos, -w / 2 * Sin], dim=-1), torch.cat([-h / 2 * Sin, -h / 2 * Cos], dim=-1)
+    poly = torch.cat([center + vector1 + vector2, center + vector1 - vector2, center - vector1 - vector2, center - vector1 + vector2], dim=-1)
+    gx, gy = (hbb[..., 0] + hbb[..., 2]) * 0.5, (hbb[..., 1] + hbb[..., 3]) * 0.5
+    gw, gh = hbb[..., 2] - hbb[..., 0], hbb[..., 3] - hbb[..., 1]
+    x_coor, y_coor = poly[:, 0::2], poly[:, 1::2]
+    y_min, x_max = torch.min(y_coor, dim=1, keepdim=True)[0], torch.max(x_coor, dim=1, keepdim=True)[0]
+    _x_coor = x_coor.clone()
+    _x_coor[torch.abs(y_coor - y_min) > 0.1] = -float("inf")          # (upstream writes -1000 here: the same maximum for every coordinate above -1000)
+    ga = torch.max(_x_coor, dim=1)[0]
+    _y_coor = y_coor.clone()
+    _y_coor[torch.abs(x_coor - x_max) > 0.1] = -float("inf")
+    gb = torch.max(_y_coor, dim=1)[0]
+    deltas = torch.stack([(gx - px) / pw, (gy - py) / ph, torch.log(gw / pw), torch.log(gh / ph), (ga - gx) / gw, (gb - gy) / gh], dim=-1)
+    return deltas.sub_(deltas.new_tensor(means).unsqueeze(0)).div_(deltas.new_tensor(stds).unsqueeze(0))
+
+
+def midpoint_decode_torch(bboxes: Tensor, deltas: Tensor, means=(0.0,) * 6, stds=(1.0, 1.0, 1.0, 1.0, 0.5, 0.5), wh_ratio_clip: float = WH_RATIO_CLIP) -> Tensor:
+    """upstream's ``delta2bbox_sp`` and ``rectpoly2obb`` in stock tensor ops (about sixty launches): anchors [N, 4], deltas [N, 6 C] -> [N, 5 C]"""
+    means = deltas.new_tensor(means).repeat(1, deltas.size(1) // 6)
+    stds = deltas.new_tensor(stds).repeat(1, deltas.size(1) // 6)
+    denorm = deltas * stds + means
+    dx, dy, dw, dh, da, db = (denorm[:, i::6] for i in range(6))
+    max_ratio = float(np.abs(np.log(wh_ratio_clip)))
+    dw, dh = dw.clamp(min=-max_ratio, max=max_ratio), dh.clamp(min=-max_ratio, max=max_ratio)
+    px = ((bboxes[:, 0] + bboxes[:, 2]) * 0.5).unsqueeze(1).expand_as(dx)
+    py = ((bboxes[:, 1] + bboxes[:, 3]) * 0.5).unsqueeze(1).expand_as(dy)
+    pw = (bboxes[:, 2] - bboxes[:, 0]).unsqueeze(1).expand_as(dw)
+    ph = (bboxes[:, 3] - bboxes[:, 1]).unsqueeze(1).expand_as(dh)
+    gw, gh = pw * dw.exp(), ph * dh.exp()
+    gx, gy = px + pw * dx, py + ph * dy
+    x1, y1, x2, y2 = gx - gw * 0.5, gy - gh * 0.5, gx + gw * 0.5, gy + gh * 0.5
+    da, db = da.clamp(min=-0.5, max=0.5), db.clamp(min=-0.5, max=0.5)
+    ga, _ga, gb, _gb = gx + da * gw, gx - da * gw, gy + db * gh, gy - db * gh
+    polys = torch.stack([ga, y1, x2, gb, _ga, y2, x1, _gb], dim=-1)
+    center = torch.stack([gx, gy, gx, gy, gx, gy, gx, gy], dim=-1)
+    center_polys = polys - center
+    diag_len = torch.sqrt(center_polys[..., 0::2] ** 2 + center_polys[..., 1::2] ** 2)
+    max_diag_len = torch.max(diag_len, dim=-1, keepdim=True)[0]
+    diag_scale_factor = max_diag_len / diag_len
+    center_polys = center_polys * diag_scale_factor.repeat_interleave(2, dim=-1)
+    rectpolys = center_polys + center
+    # rectpoly2obb
+    theta = torch.atan2(-(rectpolys[..., 3] - rectpolys[..., 1]), rectpolys[..., 2] - rectpolys[..., 0])
+    Cos, Sin = torch.cos(theta), torch.sin(theta)
+    Matrix = torch.stack([Cos, -Sin, Sin, Cos], dim=-1).view(*theta.shape, 2, 2)
+    x, y = rectpolys[..., 0::2].mean(-1), rectpolys[..., 1::2].mean(-1)
+    ctr = torch.stack([x, y], dim=-1).unsqueeze(-2)
+    cpolys = rectpolys.view(*rectpolys.shape[:-1], 4, 2) - ctr
+    rotate_polys = torch.matmul(cpolys, Matrix.transpose(-1, -2))
+    xmin, xmax = torch.min(rotate_polys[..., :, 0], dim=-1)[0], torch.max(rotate_polys[..., :, 0], dim=-1)[0]
+    ymin, ymax = torch.min(rotate_polys[..., :, 1], dim=-1)[0], torch.max(rotate_polys[..., :, 1], dim=-1)[0]
+    obboxes = torch.stack([x, y, xmax - xmin, ymax - ymin, theta], dim=-1)
+    return _regular_obb_torch(obboxes).flatten(-2)
+
+
+def obb2obb_encode_torch(bboxes: Tensor, gt_bboxes: Tensor, means=(0.0,) * 5, stds=(1.0,) * 5) -> Tensor:
+    """upstream's ``obb2delta`` in stock tensor ops: proposals [N, 5], ground truths [N, 5] -> [N, 5]"""
+    px, py, pw, ph, ptheta = bboxes.unbind(dim=-1)
+    gx, gy, gw, gh, gtheta = gt_bboxes.unbind(dim=-1)
+    dtheta1 = _regular_theta_torch(gtheta - ptheta)
+    dtheta2 = _regular_theta_torch(gtheta - ptheta + math.pi / 2)
+    abs_dtheta1, abs_dtheta2 = torch.abs(dtheta1), torch.abs(dtheta2)
+    gw_regular = torch.where(abs_dtheta1 < abs_dtheta2, gw, gh)
+    gh_regular = torch.where(abs_dtheta1 < abs_dtheta2, gh, gw)
+    dtheta = torch.where(abs_dtheta1 < abs_dtheta2, dtheta1, dtheta2)
+    dx = (torch.cos(-ptheta) * (gx - px) + torch.sin(-ptheta) * (gy - py)) / pw
+    dy = (-torch.sin(-ptheta) * (gx - px) + torch.cos(-ptheta) * (gy - py)) / ph
+    deltas = torch.stack([dx, dy, torch.log(gw_regular / pw), torch.log(gh_regular / ph), dtheta], dim=-1)
+    return deltas.sub_(deltas.new_tensor(means).unsqueeze(0)).div_(deltas.new_tensor(stds).unsqueeze(0))
+
+
+def obb2obb_decode_torch(bboxes: Tensor, deltas: Tensor, means=(0.0,) * 5, stds=(1.0,) * 5, wh_ratio_clip: float = WH_RATIO_CLIP) -> Tensor:
+    """upstream's ``delta2obb`` in stock tensor ops: proposals [N, 5], deltas [N, 5 C] -> [N, 5 C]"""
+    means = deltas.new_tensor(means).repeat(1, deltas.size(1) // 5)
+    stds = deltas.new_tensor(stds).repeat(1, deltas.size(1) // 5)
+    denorm = deltas * stds + means
+    dx, dy, dw, dh, dtheta = (denorm[:, i::5] for i in range(5))
+    max_ratio = float(np.abs(np.log(wh_ratio_clip)))
+    dw, dh = dw.clamp(min=-max_ratio, max=max_ratio), dh.clamp(min=-max_ratio, max=max_ratio)
+    px, py, pw, ph, ptheta = (bboxes[:, i].unsqueeze(1).expand_as(dx) for i in range(5))
+    gx = dx * pw * torch.cos(-ptheta) - dy * ph * torch.sin(-ptheta) + px
+    gy = dx * pw * torch.sin(-ptheta) + dy * ph * torch.cos(-ptheta) + py
+    gw, gh = pw * dw.exp(), ph * dh.exp()
+    gtheta = _regular_theta_torch(dtheta + ptheta)
+    return _regular_obb_torch(torch.stack([gx, gy, gw, gh, gtheta], dim=-1)).flatten(-2)
+
+
+def encode_assigned_torch(encode, boxes: Tensor, gts: Tensor, gt_inds: Tensor, means, stds, gt_counts: Optional[Tensor] = None,
+                          sampled: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+    """What a user writes today for the targets of B images: per image a ``nonzero`` (a host synchronisation) for the positive rows, two gathers, ``encode``
+    (``midpoint_encode_torch`` / ``obb2obb_encode_torch``) and two scatters into zero-filled targets and weights"""
+    B, N = gt_inds.shape
+    D = len(means)
+    targets, weights = gts.new_zeros((B, N, D)), gts.new_zeros((B, N))
+    for b in range(B):
+        count = gts.shape[1] if gt_counts is None else gt_counts[b].clamp(0, gts.shape[1])
+        live = (gt_inds[b] >= 1) & (gt_inds[b] <= count)
+        if sampled is not None:
+            live = live & sampled[b].to(torch.bool)
+        pos = torch.nonzero(live, as_tuple=False).squeeze(1)
+        if pos.numel():
+            bx = boxes[b] if boxes.dim() == 3 else boxes
+            targets[b, pos] = encode(bx[pos], gts[b][gt_inds[b, pos] - 1], means, stds)
+            weights[b, pos] = 1.0
+    return targets, weights
+
+
+def decode_map_torch(decode, boxes: Tensor, bbox_pred: Tensor, index: Tensor, means, stds, gathered: bool = False, wh_ratio_clip: float = WH_RATIO_CLIP) -> Tensor:
+    """What a user writes today for the proposals of one level: the ``permute(1, 2, 0).reshape(-1, D)`` copy of the whole regression map, a gather of K rows,
+    a gather of the anchors, and ``decode`` (``midpoint_decode_torch`` / ``obb2obb_decode_torch``)"""
+    D = len(means)
+    rows = bbox_pred.permute(1, 2, 0).reshape(-1, D)[index]
+    return decode(boxes if gathered else boxes[index], rows, means, stds, wh_ratio_clip)
+
+
+class _BoxCoder:
+    """The shared body of the two coders on the fused kernels (csrc/coder.hip): one launch per call, operands read in place, nothing synchronised, capturable, two
+    calls agree bit for bit.  No gradient flows through a coder: the inputs are detached.  Empty inputs return empty outputs without a launch."""
+    kind, k, D = "", 0, 0
+    _encode_torch = _decode_torch = None
+
+    def __init__(self, target_means, target_stds):
+        self.means, self.stds = tuple(float(x) for x in target_means), tuple(float(x) for x in target_stds)
+        ops.coder_norm(type(self).__name__, self.kind, self.means, self.stds)
+
+    def _rows(self, t, what: str, cols: int, dims=(2,)) -> Tensor:
+        if not isinstance(t, torch.Tensor) or t.dim() not in dims or t.shape[-1] != cols:
+            raise ValueError(f"{type(self).__name__}: {what}: a tensor of rows of {cols} columns expected, got {tuple(t.shape) if isinstance(t, torch.Tensor) else type(t)}")
+        return t.detach().float()
+
+    def encode(self, bboxes: Tensor, gt_bboxes: Tensor) -> Tensor:
+        """upstream's ``encode(bboxes, gt_bboxes)``: ``bboxes`` [N, k] against ``gt_bboxes`` [N, 5], row by row -> deltas [N, D]"""
+        boxes, gts = self._rows(bboxes, "bboxes", self.k), self._rows(gt_bboxes, "gt_bboxes", 5)
+        if boxes.shape[0] != gts.shape[0]:
+            raise ValueError(f"{type(self).__name__}.encode: {boxes.shape[0]} boxes against {gts.shape[0]} ground truths: one of each per row is needed")
+        if boxes.shape[0] == 0:          # (no launch; works without a GPU)
+            return boxes.new_zeros((0, self.D))
+        return ops.box_encode(self.kind, boxes, gts[None], self.means, self.stds)[0][0]
+
+    def decode(self, bboxes: Tensor, pred_bboxes: Tensor, max_shape=None, wh_ratio_clip: float = WH_RATIO_CLIP) -> Tensor:
+        """upstream's ``decode(bboxes, pred_bboxes, max_shape=None, wh_ratio_clip=16 / 1000)``: ``bboxes`` [N, k], ``pred_bboxes`` [N, D C] -> [N, 5 C] canonical rows
+        (cx, cy, w, h, theta).  ``max_shape`` is accepted and not applied: rotated boxes are not clipped."""
+        boxes = self._rows(bboxes, "bboxes", self.k)
+        if not isinstance(pred_bboxes, torch.Tensor) or pred_bboxes.dim() != 2 or pred_bboxes.shape[0] != boxes.shape[0] or pred_bboxes.shape[1] == 0 or pred_bboxes.shape[1] % self.D:
+            raise ValueError(f"{type(self).__name__}.decode: pred_bboxes: [{boxes.shape[0]}, {self.D} C] expected, got "
+                             f"{tuple(pred_bboxes.shape) if isinstance(pred_bboxes, torch.Tensor) else type(pred_bboxes)}")
+        deltas = pred_bboxes.detach().float()
+        if boxes.shape[0] == 0:
+            return boxes.new_zeros((0, 5 * (deltas.shape[1] // self.D)))
+        return ops.box_decode(self.kind, boxes, deltas, self.means, self.stds, wh_ratio_clip)
+
+    def encode_assigned(self, boxes: Tensor, gts: Tensor, gt_inds: Tensor, gt_counts: Optional[Tensor] = None, sampled: Optional[Tensor] = None,
+                        targets: Optional[Tensor] = None, weights: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+        """The regression targets of B images from what ``MaxIoUAssigner.assign_batched`` returns, nothing synchronised: ``boxes`` [N, k] (shared) or [B, N, k];
+        ``gts`` [B, Gmax, 5]; ``gt_inds`` int64 [B, N]; ``gt_counts`` int32 [B]; ``sampled`` bool / uint8 [B, N], a sampler's mask.  Returns ``(targets [B, N, D],
+        weights [B, N])``: row (b, n) is live iff ``1 <= gt_inds <= count`` and it is sampled -- weight 1 and the deltas against ``gts[b, gt_inds - 1]``; every other
+        row is exactly zero with weight 0.  ``targets`` / ``weights`` may be supplied: a captured call allocates nothing."""
+        boxes, gts = self._rows(boxes, "boxes", self.k, (2, 3)), self._rows(gts, "gts", 5, (3,))
+        B, N = int(gts.shape[0]), int(boxes.shape[-2])
+        if not isinstance(gt_inds, torch.Tensor) or tuple(gt_inds.shape) != (B, N):
+            raise ValueError(f"{type(self).__name__}.encode_assigned: gt_inds: [{B}, {N}] expected, got {tuple(gt_inds.shape) if isinstance(gt_inds, torch.Tensor) else type(gt_inds)}")
+        if gt_inds.dtype != torch.int64:
+            gt_inds = gt_inds.to(torch.int64)
+        if gt_counts is not None and gt_counts.dtype != torch.int32:
+            gt_counts = gt_counts.to(torch.int32)
+        if N == 0 or B == 0:          # (no launch; works without a GPU)
+            return boxes.new_zeros((B, N, self.D)), boxes.new_zeros((B, N))
+        return ops.box_encode(self.kind, boxes, gts, self.means, self.stds, gt_inds, gt_counts, sampled, targets, weights)
+
+    def decode_map(self, boxes: Tensor, bbox_pred: Tensor, index: Tensor, gathered: bool = False, wh_ratio_clip: float = WH_RATIO_CLIP,
+                   out: Optional[Tensor] = None) -> Tensor:
+        """The proposals of one level from ``topk`` indices, ready for ``obb_nms_padded``: ``bbox_pred`` [A D, H, W], the head's regression output of one image
+        and level, read IN PLACE with any strides (no ``permute(1, 2, 0).reshape(-1, D)`` copy); ``index`` int64 [K] into the rows r = (h W + w) A + a of that
+        order; ``boxes`` [H W A, k], or with ``gathered`` [K, k].  Returns [K, 5]; an index out of range gives a row of zeros.  ``out`` may be supplied."""
+        if not isinstance(bbox_pred, torch.Tensor) or bbox_pred.dim() != 3 or bbox_pred.shape[0] % self.D:
+            raise ValueError(f"{type(self).__name__}.decode_map: bbox_pred: [A {self.D}, H, W] expected, got "
+                             f"{tuple(bbox_pred.shape) if isinstance(bbox_pred, torch.Tensor) else type(bbox_pred)}")
+        boxes = self._rows(boxes, "boxes", self.k)
+        if not isinstance(index, torch.Tensor) or index.dim() != 1:
+            raise ValueError(f"{type(self).__name__}.decode_map: index: an integer vector [K] expected")
+        if index.dtype != torch.int64:
+            index = index.to(torch.int64)
+        if index.shape[0] == 0:          # (no launch; works without a GPU)
+            return boxes.new_zeros((0, 5))
+        return ops.box_decode_map(self.kind, boxes, bbox_pred.detach().float(), index, self.means, self.stds, gathered, wh_ratio_clip, out)
+
+    def __repr__(self) -> str:
+        return f"{type(self).__name__}(target_means={self.means}, target_stds={self.stds})"
+
+
+class MidpointOffsetCoder(_BoxCoder):
+    """Upstream's ``MidpointOffsetCoder`` (the oriented RPN head's ``bbox_coder``, ``target_stds=[1, 1, 1, 1, 0.5, 0.5]``): anchors (x1, y1, x2, y2), ground truths
+    and proposals (cx, cy, w, h, theta), six deltas (dx, dy, dw, dh, da, db).  Its source is not part of the reference tree: the rules restate upstream
+    (include/lemevit_hip.h).  Out of scope: gradients through decode, fp16 / bf16 boxes, clipping to ``max_shape``."""
+    kind, k, D = "midpoint", 4, 6
+    _encode_torch, _decode_torch = staticmethod(midpoint_encode_torch), staticmethod(midpoint_decode_torch)
+
+    def __init__(self, target_means=(0.0,) * 6, target_stds=(1.0, 1.0, 1.0, 1.0, 0.5, 0.5)):
+        super().__init__(target_means, target_stds)
+
+
+class OBB2OBBDeltaXYWHTCoder(_BoxCoder):
+    """Upstream's ``OBB2OBBDeltaXYWHTCoder`` (the oriented R-CNN head's ``bbox_coder``, ``target_stds=[0.1, 0.1, 0.2, 0.2, 0.1]``): proposals, ground truths and
+    detections (cx, cy, w, h, theta), five deltas (dx, dy, dw, dh, dtheta); ``decode`` takes C delta sets per row (class-specific regression).  Its source is not
+    part of the reference tree: the rules restate upstream (include/lemevit_hip.h).  Out of scope: gradients through decode, fp16 / bf16 boxes, clipping."""
+    kind, k, D = "obb2obb", 5, 5
+    _encode_torch, _decode_torch = staticmethod(obb2obb_encode_torch), staticmethod(obb2obb_decode_torch)
+
+    def __init__(self, target_means=(0.0,) * 5, target_stds=(1.0,) * 5):
+        super().__init__(target_means, target_stds)

@@ -1772,6 +1772,154 @@ def max_iou_assign(boxes: Tensor, gts: Tensor, pos_iou_thr: float, neg_iou_thr, 
 
 
 # -------------------------------------------------------------------------------------------
+# Box coders: midpoint offset (RPN head) and OBB deltas (R-CNN head) (csrc/coder.hip; lemevit_amd/detection.py has MidpointOffsetCoder / OBB2OBBDeltaXYWHTCoder)
+# -------------------------------------------------------------------------------------------
+CODER_KINDS = {"midpoint": (_lib.CODER_MIDPOINT, 4, 6, "x1, y1, x2, y2"), "obb2obb": (_lib.CODER_OBB2OBB, 5, 5, "cx, cy, w, h, theta")}
+
+
+def coder_norm(fn: str, kind: str, means, stds):
+    """(kind code, k box columns, D deltas, the boxes' column names, means, stds as host float arrays of D entries) of a coder call"""
+    if kind not in CODER_KINDS:
+        raise ValueError(f"{fn}: kind must be 'midpoint' or 'obb2obb', got {kind!r}")
+    code, k, D, names = CODER_KINDS[kind]
+    means, stds = tuple(float(x) for x in means), tuple(float(x) for x in stds)
+    if len(means) != D or len(stds) != D:
+        raise ValueError(f"{fn}: {kind}: {D} means and {D} stds expected, got {len(means)} and {len(stds)}")
+    if any(math.isnan(x) for x in means + stds):
+        raise ValueError(f"{fn}: a NaN mean or std")
+    return code, k, D, names, (C.c_float * D)(*means), (C.c_float * D)(*stds)
+
+
+def _coder_clip(fn: str, wh_ratio_clip) -> float:
+    clip = float(wh_ratio_clip)
+    if not (clip > 0.0) or math.isinf(clip):
+        raise ValueError(f"{fn}: wh_ratio_clip = {wh_ratio_clip!r} is not a positive finite number")
+    return clip
+
+
+def _coder_out(fn: str, name: str, t: Optional[Tensor], shape, dev) -> Tensor:
+    if t is None:
+        return torch.empty(shape, device=dev, dtype=torch.float32)
+    if t.dtype != torch.float32 or tuple(t.shape) != tuple(shape) or t.device != dev or not t.is_contiguous():
+        raise TypeError(f"{fn}: {name} must be a contiguous float32 tensor {tuple(shape)} on the boxes' device")
+    return t
+
+
+def box_encode(kind: str, boxes: Tensor, gts: Tensor, means, stds, gt_inds: Optional[Tensor] = None, gt_counts: Optional[Tensor] = None,
+               sampled: Optional[Tensor] = None, targets: Optional[Tensor] = None, weights: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+    """lmv_box_encode (one launch, no host round trip): the regression targets of B images.  ``kind``: 'midpoint' (boxes (x1, y1, x2, y2), 6 deltas) or 'obb2obb'
+    (boxes (cx, cy, w, h, theta), 5 deltas).  ``boxes``: float32 [N, k] shared by all images or [B, N, k]; ``gts``: float32 [B, Gmax, 5]; rows are read in place
+    through their row stride.  ``gt_inds``: int64 [B, N] as ``max_iou_assign`` returns it -- row (b, n) is encoded against ``gts[b, gt_inds[b, n] - 1]``; None: the
+    aligned form, row n against ground truth n (Gmax == N).  ``gt_counts``: int32 [B] on the device (None: Gmax); ``sampled``: uint8 / bool [B, N].  Returns
+    ``(targets float32 [B, N, D], weights float32 [B, N])``: weight 1 on a live row (1 <= gt_inds <= count, sampled), else weight 0 and targets of exactly +0.0.
+    ``targets`` / ``weights`` may be supplied so that a captured call allocates nothing.  include/lemevit_hip.h has the rules."""
+    fn = "box_encode"
+    code, k, D, names, cm, cs = coder_norm(fn, kind, means, stds)
+    if gts.dim() != 3 or gts.shape[2] != 5 or gts.dtype != torch.float32:
+        raise ValueError(f"{fn}: gts: float32 [B, Gmax, 5] (cx, cy, w, h, theta) expected, got {gts.dtype} {tuple(gts.shape)}")
+    B, Gmax = int(gts.shape[0]), int(gts.shape[1])
+    if boxes.dim() not in (2, 3) or boxes.shape[-1] != k or boxes.dtype != torch.float32 or (boxes.dim() == 3 and boxes.shape[0] != B):
+        raise ValueError(f"{fn}: boxes: float32 [N, {k}] or [{B}, N, {k}] ({names}) expected, got {boxes.dtype} {tuple(boxes.shape)}")
+    if B < 1 or B > _lib.ASSIGN_MAX_BATCH:
+        raise ValueError(f"{fn}: B = {B} images outside 1 .. {_lib.ASSIGN_MAX_BATCH}")
+    N, dev = int(boxes.shape[-2]), boxes.device
+    if N > _lib.OBB_MAX_BOXES or Gmax > _lib.OBB_MAX_BOXES:
+        raise ValueError(f"{fn}: N = {N} boxes, Gmax = {Gmax} ground truths, at most {_lib.OBB_MAX_BOXES} each")
+    if gt_inds is None and Gmax != N:
+        raise ValueError(f"{fn}: the aligned form (gt_inds=None) pairs row n with ground truth n: Gmax = {Gmax} is not N = {N}")
+    if not boxes.is_cuda or not gts.is_cuda:
+        raise RuntimeError("lemevit_amd: tensors must be on the GPU (no CPU fallback exists)")
+    if gts.device != dev:
+        raise ValueError(f"{fn}: boxes and gts are on different devices")
+    if N > 0 and (boxes.stride(-1) != 1 or (N > 1 and boxes.stride(-2) < k)):
+        raise ValueError(f"{fn}: boxes: strides {tuple(boxes.stride())}: a unit column stride and a row stride >= {k} are needed (call .contiguous())")
+    bs = max(int(boxes.stride(-2)), k)
+    bb = 0
+    if boxes.dim() == 3 and B > 1:
+        bb = int(boxes.stride(0))
+        if bb < 0 or (bb != 0 and N > 0 and bb < (N - 1) * bs + k):
+            raise ValueError(f"{fn}: boxes: a batch stride of {bb} floats overlaps the rows of an image (call .contiguous())")
+    if Gmax > 0 and (gts.stride(2) != 1 or (Gmax > 1 and gts.stride(1) < 5) or (B > 1 and gts.stride(0) != Gmax * max(int(gts.stride(1)), 5))):
+        raise ValueError(f"{fn}: gts: strides {tuple(gts.stride())}: a unit column stride, a row stride >= 5 and images Gmax rows apart are needed (call .contiguous())")
+    gs = max(int(gts.stride(1)), 5) if Gmax > 1 else (max(int(gts.stride(0)), 5) if B > 1 and Gmax == 1 else 5)
+    if gt_counts is not None and (gt_counts.dtype != torch.int32 or tuple(gt_counts.shape) != (B,) or gt_counts.device != dev or not gt_counts.is_contiguous()):
+        raise TypeError(f"{fn}: gt_counts must be a contiguous int32 vector [{B}] on the boxes' device")
+    if gt_inds is not None and (gt_inds.dtype != torch.int64 or tuple(gt_inds.shape) != (B, N) or gt_inds.device != dev or not gt_inds.is_contiguous()):
+        raise TypeError(f"{fn}: gt_inds must be a contiguous int64 tensor [{B}, {N}] on the boxes' device")
+    if sampled is not None:
+        if sampled.dtype == torch.bool:
+            sampled = sampled.view(torch.uint8)
+        if sampled.dtype != torch.uint8 or tuple(sampled.shape) != (B, N) or sampled.device != dev or not sampled.is_contiguous():
+            raise TypeError(f"{fn}: sampled must be a contiguous uint8 / bool tensor [{B}, {N}] on the boxes' device")
+    targets = _coder_out(fn, "targets", targets, (B, N, D), dev)
+    weights = _coder_out(fn, "weights", weights, (B, N), dev)
+    check(lib.lmv_box_encode(code, boxes.data_ptr(), bs, bb, N, gts.data_ptr(), gs, B, Gmax, _ptr(gt_counts), _ptr(gt_inds), _ptr(sampled), cm, cs,
+                             targets.data_ptr(), weights.data_ptr(), _stream()), "lmv_box_encode")
+    return targets, weights
+
+
+def box_decode(kind: str, boxes: Tensor, deltas: Tensor, means, stds, wh_ratio_clip: float = 16 / 1000, out: Optional[Tensor] = None) -> Tensor:
+    """lmv_box_decode (one launch): ``boxes`` float32 [N, k] and ``deltas`` float32 [N, D C], both read in place through their row stride; C >= 1 delta sets per row
+    (class-specific regression, upstream's ``0::D`` striding), each decoded against the row's box.  Returns float32 [N, 5 C] rows (cx, cy, w, h, theta) in canonical
+    form (w >= h, -pi/2 <= theta < pi/2); ``out``: a caller-supplied contiguous buffer of that shape.  include/lemevit_hip.h has the rules."""
+    fn = "box_decode"
+    code, k, D, names, cm, cs = coder_norm(fn, kind, means, stds)
+    clip = _coder_clip(fn, wh_ratio_clip)
+    if boxes.dim() != 2 or boxes.shape[1] != k:
+        raise ValueError(f"{fn}: boxes: [N, {k}] rows ({names}) expected, got {tuple(boxes.shape)}")
+    N = int(boxes.shape[0])
+    if deltas.dim() != 2 or deltas.shape[0] != N or deltas.shape[1] == 0 or deltas.shape[1] % D or deltas.dtype != torch.float32:
+        raise ValueError(f"{fn}: deltas: float32 [{N}, {D} C] expected, got {deltas.dtype} {tuple(deltas.shape)}")
+    C_ = int(deltas.shape[1]) // D
+    if C_ > _lib.CODER_MAX_SETS:
+        raise ValueError(f"{fn}: C = {C_} delta sets per row, at most {_lib.CODER_MAX_SETS}")
+    if N > _lib.OBB_MAX_BOXES:
+        raise ValueError(f"{fn}: N = {N} rows, at most {_lib.OBB_MAX_BOXES}")
+    pb, sb = _rows(fn, "boxes", boxes, k, names)
+    pd, sd = _rows(fn, "deltas", deltas, D * C_, "the delta sets")
+    if deltas.device != boxes.device:
+        raise ValueError(f"{fn}: boxes and deltas are on different devices")
+    out = _coder_out(fn, "out", out, (N, 5 * C_), boxes.device)
+    check(lib.lmv_box_decode(code, pb, sb, pd, sd, N, C_, cm, cs, clip, out.data_ptr(), _stream()), "lmv_box_decode")
+    return out
+
+
+def box_decode_map(kind: str, boxes: Tensor, bbox_pred: Tensor, index: Tensor, means, stds, gathered: bool = False, wh_ratio_clip: float = 16 / 1000,
+                   out: Optional[Tensor] = None) -> Tensor:
+    """lmv_box_decode_map (one launch, no copy of the map): ``bbox_pred`` float32 [A D, H, W], one level of a head's regression output with ANY strides (a channel
+    slice, one image of a batch), read in place for the K rows named by ``index`` int64 [K]: row r = (h W + w) A + a, the order of
+    ``bbox_pred.permute(1, 2, 0).reshape(-1, D)``.  ``boxes``: float32 [H W A, k], gathered by the same index, or with ``gathered`` [K, k], row i for ``index[i]``.
+    Returns float32 [K, 5]; an index outside 0 .. H W A - 1 gives a row of zeros.  ``out``: a caller-supplied contiguous buffer [K, 5]."""
+    fn = "box_decode_map"
+    code, k, D, names, cm, cs = coder_norm(fn, kind, means, stds)
+    clip = _coder_clip(fn, wh_ratio_clip)
+    if bbox_pred.dim() != 3 or bbox_pred.shape[0] == 0 or bbox_pred.shape[0] % D or bbox_pred.shape[1] == 0 or bbox_pred.shape[2] == 0 or bbox_pred.dtype != torch.float32:
+        raise ValueError(f"{fn}: bbox_pred: a non-empty float32 map [A {D}, H, W] expected, got {bbox_pred.dtype} {tuple(bbox_pred.shape)}")
+    A, H, W = int(bbox_pred.shape[0]) // D, int(bbox_pred.shape[1]), int(bbox_pred.shape[2])
+    total = A * H * W
+    if total > (1 << 31) - 1:
+        raise ValueError(f"{fn}: H W A = {total} rows, at most 2^31 - 1")
+    if index.dim() != 1 or index.dtype != torch.int64 or not index.is_contiguous():
+        raise TypeError(f"{fn}: index must be a contiguous int64 vector, got {index.dtype} {tuple(index.shape)}")
+    K = int(index.shape[0])
+    if K > _lib.OBB_MAX_BOXES:
+        raise ValueError(f"{fn}: K = {K} rows, at most {_lib.OBB_MAX_BOXES}")
+    want = K if gathered else total
+    if boxes.dim() != 2 or boxes.shape[1] != k or boxes.shape[0] != want:
+        raise ValueError(f"{fn}: boxes: [{want}, {k}] ({'one row per index' if gathered else 'H W A rows, gathered by the index'}) expected, got {tuple(boxes.shape)}")
+    pb, sb = _rows(fn, "boxes", boxes, k, names)
+    if not bbox_pred.is_cuda or not index.is_cuda:
+        raise RuntimeError("lemevit_amd: tensors must be on the GPU (no CPU fallback exists)")
+    if bbox_pred.device != boxes.device or index.device != boxes.device:
+        raise ValueError(f"{fn}: boxes, bbox_pred and index are on different devices")
+    out = _coder_out(fn, "out", out, (K, 5), boxes.device)
+    sc, sh, sw = (int(x) for x in bbox_pred.stride())
+    check(lib.lmv_box_decode_map(code, pb, sb, 1 if gathered else 0, bbox_pred.data_ptr(), A, H, W, sc, sh, sw, index.data_ptr(), K, cm, cs, clip, out.data_ptr(),
+                                 _stream()), "lmv_box_decode_map")
+    return out
+
+
+# -------------------------------------------------------------------------------------------
 # A run of "S" blocks as one persistent launch (csrc/sstage.hip; inference, bf16)
 # -------------------------------------------------------------------------------------------
 def sstage_supported(C_: int, heads: int, hidden: int, H: int, W: int, M: int, dtype: torch.dtype) -> bool:
