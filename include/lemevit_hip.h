@@ -1046,6 +1046,70 @@ int lmv_box_decode_map(int kind, const float* boxes, int box_stride, int gathere
                        int64_t map_stride_w, const int64_t* index, int K, const float* means, const float* stds, float wh_ratio_clip, float* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The samplers of both heads of the Oriented R-CNN configs (csrc/sampler.hip): train_cfg.rpn.sampler = RandomSampler(num=256, pos_fraction=0.5, neg_pos_ub=-1,
+ * add_gt_as_proposals=False) over the anchors and train_cfg.rcnn.sampler = OBBRandomSampler(num=512, pos_fraction=0.25, neg_pos_ub=-1, add_gt_as_proposals=True)
+ * over the proposals plus the ground truths -- what sits between lmv_max_iou_assign and lmv_box_encode.  Their sources are NOT part of the reference tree (only
+ * their names in the configs are): the rules below restate upstream mmdet 2.x and are the specification.  An addition to ABI 14: callers detect it by symbol.  No
+ * host round trip, no floating-point atomics (integer counters only; no value depends on the order in which an atomic lands): two calls agree bit for bit, the
+ * number of launches is fixed by the arguments, and both entry points can be captured.
+ *
+ * lmv_random_sample -- B images; two launches and one memset node.
+ *   Element space of one image: M = (add_gt ? Gmax : 0) + N.  With add_gt, element e < Gmax is ground truth e: a candidate only if e < count[b], and then a
+ *     POSITIVE with assigned index e + 1; element Gmax + n is box n.  Without add_gt element n is box n (Gmax and gt_counts are not used).  This is upstream's
+ *     cat([gt_bboxes, bboxes]) + AssignResult.add_gt_ without the copies; the padding rows (count[b] <= e < Gmax) are never candidates.
+ *   Classes, from gt_inds int64 [B, N] (what lmv_max_iou_assign writes; nullable with N == 0): box n is positive if gt_inds > 0, negative if gt_inds == 0; anything
+ *     else (e.g. -1, ignored) is never sampled.  gt_counts: nullable int32 [B] ON THE DEVICE, clamped to 0 .. Gmax by the kernel; null: Gmax everywhere.
+ *   Quotas (upstream's arithmetic), with c_pos / c_neg the candidates of the image:  P = int(num * pos_fraction) is computed by the HOST and passed as an integer;
+ *     n_pos = min(c_pos, P);   E = num - n_pos;   if neg_pos_ub >= 0: E = min(E, (int)floor((double)neg_pos_ub * max(1, n_pos)));   n_neg = min(c_neg, E)
+ *     (neg_pos_ub is a float; negative: no bound; +inf: no bound either).
+ *   Choice: among the c candidates of a class the k = n_pos / n_neg chosen are those with the smallest 64-bit word (priority << 32) | e -- the smallest 32-bit
+ *     priority first, the lower element index on a tie; with c <= k all are taken.  The priority of element e of image b is
+ *       (a) priorities[b, e], a nullable uint32 [B, M] supplied by the caller (a test hook, and how a caller builds a score-ordered or IoU-balanced sampler), or
+ *       (b) with priorities null: word r0 of Philox4x32-10 (the generator of lmv_augment_images above) with the counter (e, b, 0, 0x53414d50) and the key words
+ *           (key[0], key[1]), key a uint32 [2] in DEVICE memory.  The running kernel reads the key: a captured call samples anew at every replay once the key has
+ *           been rewritten.  Every k-subset of a class is equally likely up to the generator's quality (ties of 32-bit priorities fall to the lower index).
+ *     With both given, priorities is used and the key is not read.
+ *   Outputs -- every element is written exactly once, on every call (nothing is assumed about what the buffers hold):
+ *     inds      int64 [B, num]: the chosen positives in ascending element order, then the chosen negatives in ascending element order, then -1
+ *     num_pos, num_neg   int32 [B]
+ *     mask      nullable uint8 [B, M]: 0 not sampled, 1 sampled positive, 2 sampled negative.  Without add_gt it is exactly what lmv_box_encode takes as `sampled`,
+ *               and mask != 0 is the RPN's label_weights.
+ *   Upstream draws a torch.randperm; the subset here is as uniform, but not the same draw, and inds is ordered.
+ *   Workspace: lmv_random_sample_workspace_bytes(B, M) = B (2048 + 5 ceil16(M)) bytes, 16-byte aligned, always required; 0 for a B or M the call refuses.  It
+ *     holds the [B, 2, 256] histograms of the priority's top byte per class and, per element, the priority and a class byte (rows padded to 16 elements).
+ *   Mapping: launch 1, grid-wide over 1024 elements x B, classifies, computes the priorities, stores both and counts the top bytes in LDS, flushed with integer
+ *     global atomics into the table the memset node zeroed; the bin totals are c_pos / c_neg.  Launch 2, one workgroup of 1024 threads per image, computes the
+ *     quotas, finds for an oversubscribed class only (c > k > 0) the threshold priority t and the number of elements equal to t to take (lowest index first) with
+ *     three more 8-bit radix-select sweeps over the workspace, and writes every output in one ordered sweep with block prefix scans.
+ *
+ * lmv_sample_gather -- the R-CNN head's inputs from inds in one launch, one thread per output row (upstream's bbox2roi, pos_assigned_gt_inds, pos_gt_labels).
+ *     inds         int64 [B, num] (what lmv_random_sample writes) into the element space above (add_gt, Gmax, N as in that call)
+ *     boxes        fp32 [N, k] shared by all images (box_batch_stride == 0) or [B, N, k], rows through box_stride >= k;  k = 4 or 5
+ *     gts          fp32 [B, Gmax, k], rows through gt_stride >= k; read only with add_gt, and never at or past count[b]
+ *     gt_inds      int64 [B, N];   gt_labels nullable int64 [B, Gmax];   gt_counts as above;   bg_label: the label of a negative
+ *     rois         fp32 [B, num, 1 + k]: row (b, s) = (b, the box's k columns)
+ *     s_gt_inds    int64 [B, num]: the assigned index j + 1 (a ground-truth element e: e + 1), 0 for a negative
+ *     s_labels     nullable int64 [B, num]: gt_labels[b, j] (-1 without gt_labels or with j >= Gmax), bg_label for a negative
+ *   A PADDING row -- inds = -1, or any index that names no candidate: outside 0 .. M - 1, a ground-truth element at or past count[b], a box with gt_inds < 0 --
+ *   reads nothing and is (-1, 0 ...) with s_gt_inds = -1 and s_labels = -1: lmv_rroi_fwd / lmv_roi_fwd give a zero row for batch index -1, and lmv_box_encode
+ *   with boxes = rois + 1 (box_stride = 1 + k), gt_inds = s_gt_inds gives weight 0.  Every output element is written exactly once.
+ *
+ * Limits: M <= LMV_OBB_MAX_BOXES, 1 <= num <= LMV_SAMPLE_MAX_NUM, 0 <= P <= num, B in 1 .. LMV_ASSIGN_MAX_BATCH.
+ * Refused with LMV_ERR_SHAPE (a workspace that is too small or null: LMV_ERR_WORKSPACE) and a message that starts "random_sample" / "sample_gather", before any
+ * launch: sizes outside the limits, negative sizes, add_gt other than 0 / 1, a NaN neg_pos_ub, both key and priorities null, k other than 4 / 5, a row stride below
+ * k, a negative batch stride, s_labels without gt_labels (Gmax > 0), null pointers with non-zero sizes, misaligned buffers.  lmv_random_sample with M == 0
+ * launches nothing and writes nothing.
+ * ------------------------------------------------------------------------------------------ */
+#define LMV_SAMPLE_MAX_NUM 16384
+size_t lmv_random_sample_workspace_bytes(int B, int M);
+int lmv_random_sample(const int64_t* gt_inds, int N, int B, const int32_t* gt_counts, int Gmax, int add_gt, int num, int P, float neg_pos_ub,
+                      const uint32_t* priorities, const uint32_t* key, void* workspace, size_t workspace_bytes, int64_t* inds, int32_t* num_pos, int32_t* num_neg,
+                      uint8_t* mask, void* stream);
+int lmv_sample_gather(const int64_t* inds, int num, const float* boxes, int box_stride, int64_t box_batch_stride, int N, int k, const float* gts, int gt_stride,
+                      int B, int Gmax, const int64_t* gt_inds, const int64_t* gt_labels, const int32_t* gt_counts, int add_gt, int64_t bg_label, float* rois,
+                      int64_t* s_gt_inds, int64_t* s_labels, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Whole-block schedules: ONE call enqueues every launch of a LeMeBlock (models/lemevit.py:500-660) on token-major tensors
  * x [B, H*W, C], c [B, M, C] -- `LeMeBlock.forward_with_x` ("S", :615-650), `forward_with_xc` ("D", :542-582), `forward_with_c`
  * ("C", :584-613; x is returned untouched by the caller, x_out / dx_out may be NULL).  Replaces the ~12 / ~30 per-op calls a Python

@@ -36,6 +36,7 @@ ROI_MAX_LEVELS, ROI_MAX_GRID, ROI_MAX_BINS, ROI_MAX_EXTENT, ROI_HEADER_BYTES, RO
 NMS_MAX = 16384          # LMV_NMS_MAX
 ASSIGN_HORIZONTAL, ASSIGN_ROTATED, ASSIGN_GT_CHUNK, ASSIGN_MAX_GT, ASSIGN_MAX_BATCH = 0, 1, 64, 16384, 4096          # LMV_ASSIGN_*
 CODER_MIDPOINT, CODER_OBB2OBB, CODER_MAX_SETS = 0, 1, 128          # LMV_CODER_*
+SAMPLE_MAX_NUM = 16384          # LMV_SAMPLE_MAX_NUM
 
 
 class LinearProblem(C.Structure):
@@ -238,6 +239,9 @@ SIGNATURES = {
     "lmv_box_encode": (_I, [_I, _P, _I, _L, _I, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "lmv_box_decode": (_I, [_I, _P, _I, _P, _L, _I, _I, _P, _P, _F, _P, _P]),
     "lmv_box_decode_map": (_I, [_I, _P, _I, _I, _P, _I, _I, _I, _L, _L, _L, _P, _I, _P, _P, _F, _P, _P]),
+    "lmv_random_sample_workspace_bytes": (_Z, [_I, _I]),
+    "lmv_random_sample": (_I, [_P, _I, _I, _P, _I, _I, _I, _I, _F, _P, _P, _P, _Z, _P, _P, _P, _P, _P]),
+    "lmv_sample_gather": (_I, [_P, _I, _P, _I, _L, _I, _I, _P, _I, _I, _I, _P, _P, _P, _I, _L, _P, _P, _P, _P]),
     "lmv_block_arena_bytes": (_Z, [C.POINTER(BlockDesc)]),
     "lmv_block_bwd_scratch_bytes": (_Z, [C.POINTER(BlockDesc)]),
     "lmv_block_fwd": (_I, [C.POINTER(BlockDesc), _P, _P, _P, _P, _P, _Z, _I, _P]),

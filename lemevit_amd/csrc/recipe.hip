@@ -9,6 +9,7 @@
 // All are bandwidth-trivial; none uses an atomic, and every output element has exactly one writer: two runs agree bit for bit.
 #include <math.h>
 #include "common.h"
+#include "philox.h"
 
 namespace {
 constexpr int MIX_TPB = 256;
@@ -63,17 +64,7 @@ template <typename TOUT, int V> __device__ __forceinline__ void mix_store(TOUT* 
 // ---- random erasing: the fill values (include/lemevit_hip.h states them; lemevit_amd/recipe.py restates them in float64) -------------------------------
 struct EraseArgs { const lmv_erase_record* table; const uint32_t* key; int mode; };
 
-// Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11; Random123's philox4x32_R(10, ...))
-__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t* r) {
-  constexpr uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
-#pragma unroll
-  for (int i = 0; i < 10; ++i) {
-    const uint32_t h0 = __umulhi(M0, c0), l0 = M0 * c0, h1 = __umulhi(M1, c2), l1 = M1 * c2;
-    c0 = h1 ^ c1 ^ k0; c1 = l1; c2 = h0 ^ c3 ^ k1; c3 = l0;
-    k0 += W0; k1 += W1;
-  }
-  r[0] = c0; r[1] = c1; r[2] = c2; r[3] = c3;
-}
+// (philox4x32_10: philox.h, shared with sampler.hip)
 
 // One Box-Muller pair from two words: u1 = ((ra >> 9) + 1) 2^-23 in (0, 1], u2 = (rb >> 8) 2^-24 in [0, 1) (both exact in fp32); rad = sqrt(-2 ln u1),
 // the pair is rad cos(2 pi u2), rad sin(2 pi u2).  sincospif takes 2 u2 (exact): the angle is never rounded.  Accurate logf: near u1 = 1 the square root

@@ -42,7 +42,7 @@ assigners of the Oriented R-CNN configs, under upstream mmdet 2.x's names (their
 
 Per box a maximum and an argmax over the ground truths, per ground truth an integer maximum over the boxes: at most two launches, no floating-point atomics, two
 calls agree bit for bit; ``gpu_assign_thr`` is accepted and ignored (the assignment never leaves the device).  One deliberate difference: an ignored box is -1 also
-when the image has no ground truth.  Not provided: the samplers (``RandomSampler``, ``OBBRandomSampler``), other assigners, fp16 / bf16 boxes, gradients.
+when the image has no ground truth.  Not provided: other assigners, fp16 / bf16 boxes, gradients.
 ``reference_bbox_overlaps`` / ``reference_max_iou_assign`` are the numpy float64 oracles, ``bbox_overlaps_torch`` / ``max_iou_assign_torch`` the stock-PyTorch
 formulations on the whole matrix.
 
@@ -56,11 +56,30 @@ include/lemevit_hip.h restates the rules) -- what connects ``assign_batched`` to
     targets, weights = rpn_coder.encode_assigned(anchors, gts, gt_inds, gt_counts)          # B images from assign_batched's gt_inds: no nonzero, no gather
     proposals = rpn_coder.decode_map(anchors, rpn_bbox_pred[b], topk_inds)          # [A 6, H, W] read in place: no permute(1, 2, 0).reshape(-1, 6) copy
 
-One launch per call, nothing synchronised, capturable, two calls agree bit for bit, and the gathering forms equal the plain ones bit for bit.  Not provided: the
-samplers (``encode_assigned`` takes a sampler's mask as ``sampled``), ``DeltaXYWHBBoxCoder`` and the other coders of the Mask R-CNN config, gradients through
+One launch per call, nothing synchronised, capturable, two calls agree bit for bit, and the gathering forms equal the plain ones bit for bit (``encode_assigned`` takes a sampler's mask as ``sampled``).  Not provided:
+``DeltaXYWHBBoxCoder`` and the other coders of the Mask R-CNN config, gradients through
 decode, fp16 / bf16 boxes, clipping to ``max_shape`` (accepted and not applied, as upstream does for rotated boxes).  ``reference_midpoint_encode`` / ``_decode``,
 ``reference_obb2obb_encode`` / ``_decode``, ``reference_encode_assigned`` and ``reference_obb_corners`` are the numpy float64 oracles, ``midpoint_encode_torch`` /
 ``_decode_torch``, ``obb2obb_encode_torch`` / ``_decode_torch``, ``encode_assigned_torch`` and ``decode_map_torch`` the stock-PyTorch formulations.
+
+The samplers of both heads (csrc/sampler.hip), under upstream's names (sources not in the reference tree: include/lemevit_hip.h restates the rules) -- what sits
+between ``assign_batched`` and ``encode_assigned``, so that the whole target side of both heads is native, batched and capturable:
+
+    from lemevit_amd.detection import RandomSampler, OBBRandomSampler
+    rpn_sampler = RandomSampler(num=256, pos_fraction=0.5, neg_pos_ub=-1, add_gt_as_proposals=False)
+    rcnn_sampler = OBBRandomSampler(num=512, pos_fraction=0.25, neg_pos_ub=-1, add_gt_as_proposals=True)
+    s = rpn_sampler.sample_batched(gt_inds)          # BatchSample(inds [B, num], num_pos [B], num_neg [B], mask [B, N]); mask is encode_assigned's ``sampled``
+    s = rcnn_sampler.sample_batched(gt_inds, gt_counts, Gmax)          # the element space of an image: its Gmax ground truths, then its N proposals
+    rois, s_gt_inds, s_labels = rcnn_sampler.gather(s, proposals, gts, gt_inds, gt_labels, gt_counts, bg_label=15)          # rois [B, num, 6] for RotatedRoIExtractor
+    targets, weights = rcnn_coder.encode_assigned(rois[..., 1:], gts, s_gt_inds, gt_counts)
+    result = rcnn_sampler.sample(assign_result, proposals, gt_bboxes, gt_labels)          # one image, upstream's signature -> SamplingResult (synchronises ONCE)
+    step = GraphedStep(fn, before_replay=rcnn_sampler.draw)          # a fresh key per replay: one small copy, nothing synchronised
+
+Two launches and a memset per ``sample_batched``, one launch per ``gather``: no ``nonzero``, no ``randperm``, no ``cat`` of the ground truths, no host round trip, two
+calls with one key agree bit for bit.  A deliberate difference: the subset is uniformly random as upstream's is, but NOT the draw ``torch.randperm`` would make, and
+``inds`` is ordered (positives ascending, then negatives ascending, then -1).  ``priorities`` replaces the random draw with the caller's order (the smallest first):
+a score-ordered sampler.  Not provided: ``IoUBalancedNegSampler``, ``OHEMSampler``, ``PseudoSampler``, ``InstanceBalancedPosSampler``, the head losses, fp16 / bf16
+boxes.  ``reference_random_sample`` / ``reference_sample_gather`` are the numpy oracles, ``random_sample_torch`` upstream's literal per-image tensor code.
 """
 from __future__ import annotations
 
@@ -1613,3 +1632,262 @@ class OBB2OBBDeltaXYWHTCoder(_BoxCoder):
 
     def __init__(self, target_means=(0.0,) * 5, target_stds=(1.0,) * 5):
         super().__init__(target_means, target_stds)
+
+
+# -------------------------------------------------------------------------------------------
+# Samplers: RandomSampler (RPN head) and OBBRandomSampler (R-CNN head) (csrc/sampler.hip)
+# -------------------------------------------------------------------------------------------
+SAMPLE_TAG = 0x53414d50          # counter word 3 of the priorities ("SAMP")
+
+
+class BatchSample(NamedTuple):
+    """``inds`` int64 [B, num]: the chosen positives in ascending element order, then the chosen negatives, then -1; ``num_pos`` / ``num_neg`` int32 [B]; ``mask``
+    uint8 [B, M]: 0 not sampled, 1 sampled positive, 2 sampled negative"""
+    inds: Tensor
+    num_pos: Tensor
+    num_neg: Tensor
+    mask: Optional[Tensor]
+
+
+def _int_np(t, dtype=np.int64) -> np.ndarray:
+    return np.asarray(t.detach().cpu() if isinstance(t, torch.Tensor) else t).astype(dtype)
+
+
+def sample_priorities(B: int, M: int, key) -> np.ndarray:
+    """Rule (b) of the sampler: uint64 [B, M] holding the 32-bit priorities, word r0 of Philox4x32-10 on the counter (e, b, 0, 0x53414d50) under ``key`` (two words)"""
+    from .recipe import philox4x32_10
+    e, b = np.arange(M, dtype=np.uint64)[None, :], np.arange(B, dtype=np.uint64)[:, None]
+    return np.broadcast_to(philox4x32_10((e, b, 0, SAMPLE_TAG), key)[0], (B, M)).copy()
+
+
+def sample_quotas(c_pos: int, c_neg: int, num: int, num_expected_pos: int, neg_pos_ub: float) -> Tuple[int, int]:
+    """upstream's quota arithmetic: (n_pos, n_neg) from the candidates of both classes; ``neg_pos_ub`` is taken as the float32 the library receives"""
+    n_pos = min(int(c_pos), int(num_expected_pos))
+    expected = int(num) - n_pos
+    ub = float(np.float32(neg_pos_ub))
+    if ub >= 0 and not math.isinf(ub):
+        expected = min(expected, int(math.floor(ub * max(1, n_pos))))
+    return n_pos, min(int(c_neg), expected)
+
+
+def reference_random_sample(gt_inds, num: int, pos_fraction: float, neg_pos_ub: float = -1, add_gt: bool = False, gt_counts=None, Gmax: int = 0, priorities=None,
+                            key=None):
+    """The numpy oracle of ``RandomSampler.sample_batched``, from the rules of include/lemevit_hip.h: ``gt_inds`` int64 [B, N]; with ``add_gt`` the element space is
+    the ``Gmax`` ground truths (candidates below ``gt_counts[b]``, positives) followed by the N boxes.  Per class the k chosen are the first k of the SORTED 64-bit
+    words ``(priority << 32) | element``; ``priorities`` [B, M] unsigned 32-bit values, or None: ``sample_priorities(B, M, key)``.  Returns ``(inds int64 [B, num],
+    num_pos int32 [B], num_neg int32 [B], mask uint8 [B, M])``."""
+    g = _int_np(gt_inds)
+    B, N = g.shape
+    off = int(Gmax) if add_gt else 0
+    M = off + N
+    cnt = np.full(B, off) if gt_counts is None else np.clip(_int_np(gt_counts), 0, off)
+    if priorities is None:
+        if key is None:
+            raise ValueError("reference_random_sample: give priorities or a key")
+        prio = sample_priorities(B, M, key)
+    else:
+        prio = _int_np(priorities).astype(np.uint64) & np.uint64(0xffffffff)
+    P = int(num * pos_fraction)
+    inds, mask = np.full((B, num), -1, dtype=np.int64), np.zeros((B, M), dtype=np.uint8)
+    num_pos, num_neg = np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.int32)
+    e = np.arange(M, dtype=np.uint64)
+    for b in range(B):
+        cls = np.zeros(M, dtype=np.uint8)
+        cls[:off][np.arange(off) < cnt[b]] = 1
+        cls[off:][g[b] > 0] = 1
+        cls[off:][g[b] == 0] = 2
+        words = (prio[b] << np.uint64(32)) | e
+        n_pos, n_neg = sample_quotas(int((cls == 1).sum()), int((cls == 2).sum()), num, P, neg_pos_ub)
+        at = 0
+        for c, k in ((1, n_pos), (2, n_neg)):
+            chosen = np.sort((np.sort(words[cls == c])[:k] & np.uint64(0xffffffff)).astype(np.int64))
+            inds[b, at:at + k] = chosen
+            mask[b, chosen] = c
+            at += k
+        num_pos[b], num_neg[b] = n_pos, n_neg
+    return inds, num_pos, num_neg, mask
+
+
+def reference_sample_gather(inds, boxes, gts, gt_inds, gt_labels=None, gt_counts=None, add_gt: bool = False, bg_label: int = 0):
+    """The numpy oracle of ``RandomSampler.gather``: ``(rois float32 [B, num, 1 + k], s_gt_inds int64 [B, num], s_labels int64 [B, num] or None)``.  A row whose
+    index names no candidate (-1, out of range, a ground-truth element at or past the count, a box with gt_inds < 0) is (-1, 0 ...), -1, -1."""
+    ind, g = _int_np(inds), _int_np(gt_inds)
+    gt = np.asarray(gts.detach().cpu() if isinstance(gts, torch.Tensor) else gts, dtype=np.float32)
+    bx = np.asarray(boxes.detach().cpu() if isinstance(boxes, torch.Tensor) else boxes, dtype=np.float32)
+    B, Gmax, k = gt.shape
+    if bx.ndim == 2:
+        bx = np.broadcast_to(bx[None], (B,) + bx.shape)
+    N, num = bx.shape[1], ind.shape[1]
+    off = Gmax if add_gt else 0
+    cnt = np.full(B, Gmax) if gt_counts is None else np.clip(_int_np(gt_counts), 0, Gmax)
+    lab = None if gt_labels is None else _int_np(gt_labels)
+    rois, s_gt, s_lab = np.zeros((B, num, 1 + k), dtype=np.float32), np.full((B, num), -1, dtype=np.int64), np.full((B, num), -1, dtype=np.int64)
+    rois[..., 0] = -1.0
+    for b in range(B):
+        for s in range(num):
+            e = int(ind[b, s])
+            if 0 <= e < off:
+                if e >= cnt[b]:
+                    continue
+                row, gi = gt[b, e], e + 1
+            elif off <= e < off + N and g[b, e - off] >= 0:
+                row, gi = bx[b, e - off], int(g[b, e - off])
+            else:
+                continue
+            rois[b, s, 0], rois[b, s, 1:], s_gt[b, s] = b, row, gi
+            s_lab[b, s] = bg_label if gi == 0 else (lab[b, gi - 1] if lab is not None and gi <= Gmax else -1)
+    return rois, s_gt, (None if lab is None else s_lab)
+
+
+def _random_choice_torch(gallery: Tensor, num: int) -> Tensor:
+    perm = torch.randperm(gallery.numel(), device=gallery.device)[:num]
+    return gallery[perm]
+
+
+def random_sample_torch(gt_inds: Tensor, num: int, pos_fraction: float, neg_pos_ub: float = -1, add_gt: bool = False, num_gts: int = 0) -> Tuple[Tensor, Tensor]:
+    """What a user writes today, for ONE image: upstream's ``RandomSampler`` in stock tensor ops -- ``AssignResult.add_gt_`` (a ``cat``), two ``nonzero`` (each a host
+    synchronisation), ``randperm`` over the candidates of an oversubscribed class, an index copy and ``unique``.  ``gt_inds`` int64 [N]; returns ``(pos_inds,
+    neg_inds)`` into the element space (``num_gts`` ground truths in front with ``add_gt``).  Its draws are ``torch.randperm``'s, not the native ones."""
+    if add_gt and num_gts > 0:
+        gt_inds = torch.cat([torch.arange(1, num_gts + 1, dtype=gt_inds.dtype, device=gt_inds.device), gt_inds])
+    num_expected_pos = int(num * pos_fraction)
+    pos_inds = torch.nonzero(gt_inds > 0, as_tuple=False)
+    if pos_inds.numel() != 0:
+        pos_inds = pos_inds.squeeze(1)
+    if pos_inds.numel() > num_expected_pos:
+        pos_inds = _random_choice_torch(pos_inds, num_expected_pos)
+    pos_inds = pos_inds.unique()
+    num_sampled_pos = pos_inds.numel()
+    num_expected_neg = num - num_sampled_pos
+    if neg_pos_ub >= 0:
+        neg_upper_bound = int(neg_pos_ub * max(1, num_sampled_pos))
+        if num_expected_neg > neg_upper_bound:
+            num_expected_neg = neg_upper_bound
+    neg_inds = torch.nonzero(gt_inds == 0, as_tuple=False)
+    if neg_inds.numel() != 0:
+        neg_inds = neg_inds.squeeze(1)
+    if len(neg_inds) > num_expected_neg:
+        neg_inds = _random_choice_torch(neg_inds, num_expected_neg)
+    neg_inds = neg_inds.unique()
+    return pos_inds, neg_inds
+
+
+class SamplingResult:
+    """upstream's fields: ``pos_inds`` / ``neg_inds`` index the element space (with ``add_gt_as_proposals`` the ground truths come first), ``pos_is_gt`` uint8,
+    ``pos_assigned_gt_inds`` is zero-based, ``bboxes`` = cat([pos_bboxes, neg_bboxes])"""
+
+    def __init__(self, pos_inds, neg_inds, pos_bboxes, neg_bboxes, pos_is_gt, num_gts, pos_assigned_gt_inds, pos_gt_bboxes, pos_gt_labels):
+        self.pos_inds, self.neg_inds, self.pos_bboxes, self.neg_bboxes, self.pos_is_gt = pos_inds, neg_inds, pos_bboxes, neg_bboxes, pos_is_gt
+        self.num_gts, self.pos_assigned_gt_inds, self.pos_gt_bboxes, self.pos_gt_labels = num_gts, pos_assigned_gt_inds, pos_gt_bboxes, pos_gt_labels
+
+    @property
+    def bboxes(self) -> Tensor:
+        return torch.cat([self.pos_bboxes, self.neg_bboxes])
+
+    def __repr__(self) -> str:
+        return f"SamplingResult(num_gts={self.num_gts}, pos={tuple(self.pos_inds.shape)}, neg={tuple(self.neg_inds.shape)})"
+
+
+class RandomSampler:
+    """Upstream mmdet 2.x ``RandomSampler`` on the fused kernels (csrc/sampler.hip): B images per call, two launches and a memset, no ``nonzero``, no ``randperm``,
+    no ``cat`` of the ground truths, nothing synchronised, capturable, two calls with one key agree bit for bit.  Its source is not part of the reference tree: the
+    rules restate upstream (include/lemevit_hip.h).  The subset is uniformly random as upstream's is, but NOT the draw ``torch.randperm`` would make, and the
+    indices come out ordered.  ``seed`` seeds the host generator the keys are drawn from; ``draw()`` writes a fresh key into the device key (one small copy, nothing
+    synchronised): ``GraphedStep(step, before_replay=sampler.draw)``.  Without a ``draw()`` every call samples with the same key."""
+
+    def __init__(self, num, pos_fraction, neg_pos_ub=-1, add_gt_as_proposals=True, seed=None, **kwargs):
+        self.num, self.pos_fraction, self.neg_pos_ub, self.add_gt_as_proposals = int(num), float(pos_fraction), float(neg_pos_ub), bool(add_gt_as_proposals)
+        self.num_expected_pos = int(self.num * self.pos_fraction)
+        if not 1 <= self.num <= ops._lib.SAMPLE_MAX_NUM:
+            raise ValueError(f"{type(self).__name__}: num = {num} outside 1 .. {ops._lib.SAMPLE_MAX_NUM}")
+        if not 0 <= self.num_expected_pos <= self.num or math.isnan(self.neg_pos_ub):
+            raise ValueError(f"{type(self).__name__}: pos_fraction = {pos_fraction} outside [0, 1] or neg_pos_ub = {neg_pos_ub} is NaN")
+        self.rng = np.random.default_rng(seed)
+        self.host_key: Tuple[int, int] = tuple(int(k) for k in self.rng.integers(0, 2 ** 32, 2))
+        self.key: Optional[Tensor] = None          # int32 [2] on the device: the kernel reads it
+
+    def _key_on(self, dev) -> Tensor:
+        if self.key is None or self.key.device != dev:
+            if dev.type == "cuda" and torch.cuda.is_current_stream_capturing():
+                raise RuntimeError(f"{type(self).__name__}: the key cannot be allocated under graph capture (make one eager call first)")
+            from .recipe import pack_erase_key
+            self.key = pack_erase_key(self.host_key).to(dev)
+        return self.key
+
+    def draw(self) -> Tuple[int, int]:
+        """A fresh 64-bit key: into the device key when there is one (a stream-ordered copy from a fresh host tensor, non-blocking: a replay in flight keeps what it
+        was given), else kept for the first call.  Returns the two key words."""
+        from .recipe import pack_erase_key
+        self.host_key = tuple(int(k) for k in self.rng.integers(0, 2 ** 32, 2))
+        if self.key is not None:
+            self.key.copy_(pack_erase_key(self.host_key), non_blocking=True)
+        return self.host_key
+
+    def sample_batched(self, gt_inds: Tensor, gt_counts: Optional[Tensor] = None, Gmax: int = 0, priorities: Optional[Tensor] = None, inds: Optional[Tensor] = None,
+                       num_pos: Optional[Tensor] = None, num_neg: Optional[Tensor] = None, mask: Optional[Tensor] = None,
+                       workspace: Optional[Tensor] = None) -> BatchSample:
+        """B images in one call, nothing synchronised: ``gt_inds`` int64 [B, N] from ``MaxIoUAssigner.assign_batched``.  With ``add_gt_as_proposals`` the element
+        space of an image is its ``Gmax`` ground truths (the first ``gt_counts[b]`` are positives with assigned index e + 1) followed by its N boxes -- upstream's
+        ``cat([gt_bboxes, bboxes])`` and ``add_gt_`` without the copies -- so M = Gmax + N; otherwise M = N and ``gt_counts`` / ``Gmax`` are not used.
+        ``priorities`` (uint32 bits, [B, M]) replaces the random draw: the smallest are taken, the lower index on a tie.  The outputs and the workspace
+        (``ops.random_sample_workspace_bytes(B, M)``) may be supplied: a captured call allocates nothing."""
+        if not isinstance(gt_inds, torch.Tensor) or gt_inds.dim() != 2:
+            raise ValueError(f"{type(self).__name__}.sample_batched: gt_inds: [B, N] expected, got {tuple(gt_inds.shape) if isinstance(gt_inds, torch.Tensor) else type(gt_inds)}")
+        if gt_inds.dtype != torch.int64:
+            gt_inds = gt_inds.to(torch.int64)
+        if gt_counts is not None and gt_counts.dtype != torch.int32:
+            gt_counts = gt_counts.to(torch.int32)
+        key = None if priorities is not None else self._key_on(gt_inds.device)
+        return BatchSample(*ops.random_sample(gt_inds, self.num, self.num_expected_pos, self.neg_pos_ub, self.add_gt_as_proposals, int(Gmax), gt_counts, priorities, key,
+                                              inds, num_pos, num_neg, mask, True, workspace))
+
+    def gather(self, sample, boxes: Tensor, gts: Tensor, gt_inds: Tensor, gt_labels: Optional[Tensor] = None, gt_counts: Optional[Tensor] = None, bg_label: int = 0,
+               rois: Optional[Tensor] = None, s_gt_inds: Optional[Tensor] = None, s_labels: Optional[Tensor] = None):
+        """The head's inputs from a ``BatchSample`` (or its ``inds``) in one launch: ``boxes`` [N, k] or [B, N, k], ``gts`` [B, Gmax, k], ``gt_inds`` [B, N] as given to
+        ``sample_batched``.  Returns ``(rois [B, num, 1 + k] = (b, box), s_gt_inds [B, num] = j + 1 / 0 negative, s_labels [B, num] = gt_labels[b, j] / bg_label, None
+        without gt_labels)`` -- upstream's ``bbox2roi``, ``pos_assigned_gt_inds + 1`` and ``pos_gt_labels`` with fixed shapes; a padding row is (-1, 0 ...), -1, -1,
+        for which the RoI extractors give a zero row and ``encode_assigned(rois[..., 1:], gts, s_gt_inds, gt_counts)`` weight 0.  ``bg_label``: the label of a
+        negative (mmdet 2.x: ``num_classes``).  The outputs may be supplied."""
+        inds = sample.inds if isinstance(sample, BatchSample) else sample
+        if gt_inds.dtype != torch.int64:
+            gt_inds = gt_inds.to(torch.int64)
+        if gt_counts is not None and gt_counts.dtype != torch.int32:
+            gt_counts = gt_counts.to(torch.int32)
+        if gt_labels is not None and gt_labels.dtype != torch.int64:
+            gt_labels = gt_labels.to(torch.int64)
+        return ops.sample_gather(inds, boxes.detach().float(), gts.detach().float(), gt_inds, gt_labels, gt_counts, self.add_gt_as_proposals, bg_label, rois, s_gt_inds,
+                                 s_labels)
+
+    def sample(self, assign_result, bboxes: Tensor, gt_bboxes: Tensor, gt_labels: Optional[Tensor] = None, **kwargs) -> SamplingResult:
+        """upstream's ``sample(assign_result, bboxes, gt_bboxes, gt_labels=None)`` for one image: ``bboxes`` [N, >= k], ``gt_bboxes`` [G, k], k = 4 or 5.  The shapes
+        of a ``SamplingResult`` depend on the data, so this form synchronises ONCE (the two counts); ``sample_batched`` + ``gather`` never do."""
+        who = type(self).__name__
+        if gt_bboxes.dim() != 2 or gt_bboxes.shape[1] not in (4, 5) or bboxes.dim() != 2 or bboxes.shape[1] < gt_bboxes.shape[1]:
+            raise ValueError(f"{who}.sample: gt_bboxes [G, 4] or [G, 5] and bboxes [N, >= that many columns] expected, got {tuple(gt_bboxes.shape)}, {tuple(bboxes.shape)}")
+        k, G, N = int(gt_bboxes.shape[1]), int(gt_bboxes.shape[0]), int(bboxes.shape[0])
+        boxes, gts = bboxes.detach().float()[:, :k], gt_bboxes.detach().float()
+        add_gt = self.add_gt_as_proposals and G > 0
+        off = G if add_gt else 0
+        empty = boxes.new_zeros((0,), dtype=torch.int64)
+        if off + N == 0:          # (no launch; works without a GPU)
+            return SamplingResult(empty, empty.clone(), boxes.new_zeros((0, k)), boxes.new_zeros((0, k)), boxes.new_zeros((0,), dtype=torch.uint8), G, empty.clone(),
+                                  boxes.new_zeros((0, k)), None if gt_labels is None else empty.clone())
+        gt_inds = assign_result.gt_inds.reshape(1, N).to(torch.int64)
+        s = self.sample_batched(gt_inds, None, G)
+        lab = None if gt_labels is None else gt_labels.reshape(1, G)
+        rois, s_gt, s_lab = self.gather(s, boxes, gts[None], gt_inds, lab)
+        n_pos, n_neg = (int(x) for x in torch.stack([s.num_pos[0], s.num_neg[0]]).tolist())          # the one synchronisation
+        pos_inds, neg_inds = s.inds[0, :n_pos], s.inds[0, n_pos:n_pos + n_neg]
+        assigned = s_gt[0, :n_pos] - 1
+        pos_labels = s_lab[0, :n_pos] if s_lab is not None else (assign_result.labels[pos_inds] if assign_result.labels is not None and off == 0 else None)
+        return SamplingResult(pos_inds, neg_inds, rois[0, :n_pos, 1:], rois[0, n_pos:n_pos + n_neg, 1:], (pos_inds < off).to(torch.uint8), G, assigned,
+                              gts[assigned] if G > 0 else boxes.new_zeros((0, k)), pos_labels)
+
+    def __repr__(self) -> str:
+        return (f"{type(self).__name__}(num={self.num}, pos_fraction={self.pos_fraction}, neg_pos_ub={self.neg_pos_ub}, "
+                f"add_gt_as_proposals={self.add_gt_as_proposals})")
+
+
+class OBBRandomSampler(RandomSampler):
+    """Upstream's ``OBBRandomSampler`` (the oriented R-CNN head's sampler: boxes and ground truths (cx, cy, w, h, theta)): the same code -- the sampler never looks
+    at a coordinate, and ``gather`` / ``sample`` take the column count from the ground truths."""

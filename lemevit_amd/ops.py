@@ -1920,6 +1920,150 @@ def box_decode_map(kind: str, boxes: Tensor, bbox_pred: Tensor, index: Tensor, m
 
 
 # -------------------------------------------------------------------------------------------
+# Samplers of both R-CNN heads (csrc/sampler.hip; lemevit_amd/detection.py has RandomSampler / OBBRandomSampler)
+# -------------------------------------------------------------------------------------------
+def random_sample_workspace_bytes(B: int, M: int) -> int:
+    """lmv_random_sample_workspace_bytes: B (2048 + 5 ceil16(M)) bytes -- the histograms and the per-element priority and class of ``random_sample``;
+    M = (Gmax with add_gt) + N elements per image"""
+    if not 1 <= int(B) <= _lib.ASSIGN_MAX_BATCH or not 0 <= int(M) <= _lib.OBB_MAX_BOXES:
+        raise ValueError(f"random_sample_workspace_bytes: B = {B} outside 1 .. {_lib.ASSIGN_MAX_BATCH} or M = {M} outside 0 .. {_lib.OBB_MAX_BOXES}")
+    return int(lib.lmv_random_sample_workspace_bytes(int(B), int(M)))
+
+
+def _sample_buf(fn: str, name: str, t: Optional[Tensor], shape, dtype, dev) -> Tensor:
+    if t is None:
+        return torch.empty(shape, device=dev, dtype=dtype)
+    if t.dtype != dtype or tuple(t.shape) != tuple(shape) or t.device != dev or not t.is_contiguous():
+        raise TypeError(f"{fn}: {name} must be a contiguous {dtype} tensor {tuple(shape)} on the device of gt_inds")
+    return t
+
+
+def _sample_counts(fn: str, gt_counts: Optional[Tensor], B: int, dev) -> Optional[Tensor]:
+    if gt_counts is not None and (gt_counts.dtype != torch.int32 or tuple(gt_counts.shape) != (B,) or gt_counts.device != dev or not gt_counts.is_contiguous()):
+        raise TypeError(f"{fn}: gt_counts must be a contiguous int32 vector [{B}] on the device of gt_inds")
+    return gt_counts
+
+
+def random_sample(gt_inds: Tensor, num: int, num_expected_pos: int, neg_pos_ub: float = -1.0, add_gt: bool = False, Gmax: int = 0,
+                  gt_counts: Optional[Tensor] = None, priorities: Optional[Tensor] = None, key: Optional[Tensor] = None, inds: Optional[Tensor] = None,
+                  num_pos: Optional[Tensor] = None, num_neg: Optional[Tensor] = None, mask: Optional[Tensor] = None, want_mask: bool = True,
+                  workspace: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor, Optional[Tensor]]:
+    """lmv_random_sample (two launches and a memset, no host round trip): upstream's RandomSampler rules for B images at once.  ``gt_inds``: int64 [B, N] as
+    ``max_iou_assign`` returns it (> 0 positive, 0 negative, anything else never sampled).  With ``add_gt`` the element space of an image is its ``Gmax`` ground
+    truths (those below ``gt_counts[b]`` are positives with assigned index e + 1) followed by its N boxes: M = Gmax + N; otherwise M = N.  ``num_expected_pos`` is
+    upstream's ``int(num * pos_fraction)``.  The k chosen of a class are those with the smallest (priority, element) pairs: ``priorities`` uint32 bits as an int32 /
+    uint32 tensor [B, M], or -- None -- Philox words under ``key``, an int32 [2] DEVICE tensor (``recipe.pack_erase_key``) that the running kernel reads.  Returns
+    ``(inds int64 [B, num], num_pos int32 [B], num_neg int32 [B], mask uint8 [B, M] or None)``: the chosen positives in ascending element order, then the chosen
+    negatives, then -1; mask 0 / 1 positive / 2 negative.  Every output and the workspace (uint8, ``random_sample_workspace_bytes(B, M)``) may be supplied so that a
+    captured call allocates nothing.  include/lemevit_hip.h has the rules."""
+    fn = "random_sample"
+    if gt_inds.dim() != 2 or gt_inds.dtype != torch.int64:
+        raise ValueError(f"{fn}: gt_inds: int64 [B, N] expected, got {gt_inds.dtype} {tuple(gt_inds.shape)}")
+    B, N = int(gt_inds.shape[0]), int(gt_inds.shape[1])
+    num, P, ub, Gmax = int(num), int(num_expected_pos), float(neg_pos_ub), int(Gmax)
+    if B < 1 or B > _lib.ASSIGN_MAX_BATCH:
+        raise ValueError(f"{fn}: B = {B} images outside 1 .. {_lib.ASSIGN_MAX_BATCH}")
+    if Gmax < 0:
+        raise ValueError(f"{fn}: Gmax = {Gmax} is negative")
+    M = (Gmax if add_gt else 0) + N
+    if M > _lib.OBB_MAX_BOXES:
+        raise ValueError(f"{fn}: M = {M} elements per image, at most {_lib.OBB_MAX_BOXES}")
+    if not 1 <= num <= _lib.SAMPLE_MAX_NUM:
+        raise ValueError(f"{fn}: num = {num} samples per image outside 1 .. {_lib.SAMPLE_MAX_NUM}")
+    if not 0 <= P <= num:
+        raise ValueError(f"{fn}: num_expected_pos = {P} outside 0 .. num = {num}")
+    if math.isnan(ub):
+        raise ValueError(f"{fn}: neg_pos_ub is NaN (negative: no bound)")
+    if priorities is None and key is None:
+        raise ValueError(f"{fn}: give priorities [B, M] or a key (int32 [2] on the device)")
+    if not gt_inds.is_cuda:
+        raise RuntimeError("lemevit_amd: tensors must be on the GPU (no CPU fallback exists)")
+    if not gt_inds.is_contiguous():
+        raise ValueError(f"{fn}: gt_inds must be contiguous")
+    dev = gt_inds.device
+    gt_counts = _sample_counts(fn, gt_counts, B, dev) if add_gt else None
+    if priorities is not None:
+        if priorities.dtype == torch.uint32:
+            priorities = priorities.view(torch.int32)
+        if priorities.dtype != torch.int32 or tuple(priorities.shape) != (B, M) or priorities.device != dev or not priorities.is_contiguous():
+            raise TypeError(f"{fn}: priorities must be a contiguous int32 / uint32 tensor [{B}, {M}] (the bits of unsigned 32-bit words) on the device of gt_inds")
+    if key is not None and (key.dtype != torch.int32 or tuple(key.shape) != (2,) or key.device != dev or not key.is_contiguous()):
+        raise TypeError(f"{fn}: key must be a contiguous int32 vector [2] on the device of gt_inds")
+    inds = _sample_buf(fn, "inds", inds, (B, num), torch.int64, dev)
+    num_pos = _sample_buf(fn, "num_pos", num_pos, (B,), torch.int32, dev)
+    num_neg = _sample_buf(fn, "num_neg", num_neg, (B,), torch.int32, dev)
+    if mask is not None or want_mask:
+        mask = _sample_buf(fn, "mask", mask, (B, M), torch.uint8, dev)
+    if M == 0:          # (no launch: nothing is a candidate)
+        inds.fill_(-1); num_pos.zero_(); num_neg.zero_()
+        return inds, num_pos, num_neg, mask
+    need = random_sample_workspace_bytes(B, M)
+    if workspace is None:
+        workspace = torch.empty((need,), device=dev, dtype=torch.uint8)
+    elif workspace.dtype != torch.uint8 or workspace.device != dev or not workspace.is_contiguous() or workspace.numel() < need or workspace.data_ptr() % 16:
+        raise ValueError(f"{fn}: the workspace must hold {need} bytes (uint8, 16-byte aligned) on the device of gt_inds (ops.random_sample_workspace_bytes)")
+    check(lib.lmv_random_sample(gt_inds.data_ptr() if N > 0 else None, N, B, _ptr(gt_counts), Gmax, 1 if add_gt else 0, num, P, ub, _ptr(priorities), _ptr(key),
+                                workspace.data_ptr(), workspace.numel(), inds.data_ptr(), num_pos.data_ptr(), num_neg.data_ptr(), _ptr(mask), _stream()),
+          "lmv_random_sample")
+    return inds, num_pos, num_neg, mask
+
+
+def sample_gather(inds: Tensor, boxes: Tensor, gts: Tensor, gt_inds: Tensor, gt_labels: Optional[Tensor] = None, gt_counts: Optional[Tensor] = None,
+                  add_gt: bool = False, bg_label: int = 0, rois: Optional[Tensor] = None, s_gt_inds: Optional[Tensor] = None,
+                  s_labels: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Optional[Tensor]]:
+    """lmv_sample_gather (one launch): the R-CNN head's inputs from ``random_sample``'s ``inds`` int64 [B, num].  ``boxes``: float32 [N, k] shared by all images or
+    [B, N, k], ``gts``: float32 [B, Gmax, k], k = 4 or 5, rows read in place through their row stride; ``gt_inds`` int64 [B, N]; ``gt_labels`` int64 [B, Gmax];
+    ``gt_counts`` int32 [B]; ``add_gt`` as in the sampling call.  Returns ``(rois float32 [B, num, 1 + k] = (b, box), s_gt_inds int64 [B, num] = j + 1 / 0 negative,
+    s_labels int64 [B, num] = gt_labels[b, j] / bg_label, None without gt_labels)``; a padding row is (-1, 0 ...), -1, -1.  The outputs may be supplied."""
+    fn = "sample_gather"
+    if gts.dim() != 3 or gts.shape[2] not in (4, 5) or gts.dtype != torch.float32:
+        raise ValueError(f"{fn}: gts: float32 [B, Gmax, 4] or [B, Gmax, 5] expected, got {gts.dtype} {tuple(gts.shape)}")
+    B, Gmax, k = (int(x) for x in gts.shape)
+    if boxes.dim() not in (2, 3) or boxes.shape[-1] != k or boxes.dtype != torch.float32 or (boxes.dim() == 3 and boxes.shape[0] != B):
+        raise ValueError(f"{fn}: boxes: float32 [N, {k}] or [{B}, N, {k}] expected, got {boxes.dtype} {tuple(boxes.shape)}")
+    N, dev = int(boxes.shape[-2]), boxes.device
+    if B < 1 or B > _lib.ASSIGN_MAX_BATCH:
+        raise ValueError(f"{fn}: B = {B} images outside 1 .. {_lib.ASSIGN_MAX_BATCH}")
+    if (Gmax if add_gt else 0) + N > _lib.OBB_MAX_BOXES or Gmax > _lib.OBB_MAX_BOXES:
+        raise ValueError(f"{fn}: N = {N} boxes and Gmax = {Gmax} ground truths: at most {_lib.OBB_MAX_BOXES} elements per image")
+    if inds.dim() != 2 or inds.shape[0] != B or inds.dtype != torch.int64 or not 1 <= inds.shape[1] <= _lib.SAMPLE_MAX_NUM:
+        raise ValueError(f"{fn}: inds: int64 [{B}, num], 1 <= num <= {_lib.SAMPLE_MAX_NUM}, expected, got {inds.dtype} {tuple(inds.shape)}")
+    num = int(inds.shape[1])
+    if not boxes.is_cuda or not gts.is_cuda or not inds.is_cuda:
+        raise RuntimeError("lemevit_amd: tensors must be on the GPU (no CPU fallback exists)")
+    if gts.device != dev or inds.device != dev or gt_inds.device != dev:
+        raise ValueError(f"{fn}: inds, boxes, gts and gt_inds are on different devices")
+    if not inds.is_contiguous():
+        raise ValueError(f"{fn}: inds must be contiguous")
+    if gt_inds.dtype != torch.int64 or tuple(gt_inds.shape) != (B, N) or not gt_inds.is_contiguous():
+        raise TypeError(f"{fn}: gt_inds must be a contiguous int64 tensor [{B}, {N}]")
+    if N > 0 and (boxes.stride(-1) != 1 or (N > 1 and boxes.stride(-2) < k)):
+        raise ValueError(f"{fn}: boxes: strides {tuple(boxes.stride())}: a unit column stride and a row stride >= {k} are needed (call .contiguous())")
+    bs = max(int(boxes.stride(-2)), k)
+    bb = 0
+    if boxes.dim() == 3 and B > 1:
+        bb = int(boxes.stride(0))
+        if bb < 0 or (bb != 0 and N > 0 and bb < (N - 1) * bs + k):
+            raise ValueError(f"{fn}: boxes: a batch stride of {bb} floats overlaps the rows of an image (call .contiguous())")
+    if Gmax > 0 and (gts.stride(2) != 1 or (Gmax > 1 and gts.stride(1) < k) or (B > 1 and gts.stride(0) != Gmax * max(int(gts.stride(1)), k))):
+        raise ValueError(f"{fn}: gts: strides {tuple(gts.stride())}: a unit column stride, a row stride >= {k} and images Gmax rows apart are needed (call .contiguous())")
+    gs = max(int(gts.stride(1)), k) if Gmax > 1 else (max(int(gts.stride(0)), k) if B > 1 and Gmax == 1 else k)
+    gt_counts = _sample_counts(fn, gt_counts, B, dev)
+    if gt_labels is not None and (gt_labels.dtype != torch.int64 or tuple(gt_labels.shape) != (B, Gmax) or gt_labels.device != dev or not gt_labels.is_contiguous()):
+        raise TypeError(f"{fn}: gt_labels must be a contiguous int64 tensor [{B}, {Gmax}] on the boxes' device")
+    rois = _sample_buf(fn, "rois", rois, (B, num, 1 + k), torch.float32, dev)
+    s_gt_inds = _sample_buf(fn, "s_gt_inds", s_gt_inds, (B, num), torch.int64, dev)
+    if gt_labels is not None:
+        s_labels = _sample_buf(fn, "s_labels", s_labels, (B, num), torch.int64, dev)
+    elif s_labels is not None:
+        raise ValueError(f"{fn}: an s_labels buffer without gt_labels")
+    check(lib.lmv_sample_gather(inds.data_ptr(), num, boxes.data_ptr() if N > 0 else None, bs, bb, N, k, gts.data_ptr() if Gmax > 0 else None, gs, B, Gmax,
+                                gt_inds.data_ptr() if N > 0 else None, _ptr(gt_labels), _ptr(gt_counts), 1 if add_gt else 0, int(bg_label), rois.data_ptr(),
+                                s_gt_inds.data_ptr(), None if s_labels is None else s_labels.data_ptr(), _stream()), "lmv_sample_gather")
+    return rois, s_gt_inds, s_labels
+
+
+# -------------------------------------------------------------------------------------------
 # A run of "S" blocks as one persistent launch (csrc/sstage.hip; inference, bf16)
 # -------------------------------------------------------------------------------------------
 def sstage_supported(C_: int, heads: int, hidden: int, H: int, W: int, M: int, dtype: torch.dtype) -> bool:
