@@ -727,8 +727,9 @@ int lmv_dense_slide_fwd(const void* logits, int dtype, int64_t window_stride, in
  *     else y_high = y_low + 1 (the same for x); ly = y - y_low, hy = 1 - ly:  w1 = hy hx, w2 = hy lx, w3 = ly hx, w4 = ly lx  on (y_low, x_low), (y_low, x_high),
  *     (y_high, x_low), (y_high, x_high).
  *     out[r, c, ph, pw] = (sum over the bin's s s samples, iy outer, of w1 v1 + w2 v2 + w3 v3 + w4 v4) / (s s)          (empty samples count in the divisor)
- * A RoI whose batch_index truncates to a value outside [0, B), or whose level_index lies outside [0, L), is not a sample: its output row is zero and it reaches
- * no gradient (the rule of lmv_eval_logits and of the dense label maps).  Negative w / h are not validated (that would synchronise): the formulas apply as they are.
+ * A RoI whose batch_index truncates to a value outside [0, B) (a NaN batch_index included), whose level_index lies outside [0, L), or whose cx, cy, w, h or theta
+ * is not finite (the rule of lmv_roi_plan; the reference lets the NaN through), is not a sample: its output row is zero and it reaches no gradient (the rule of
+ * lmv_eval_logits and of the dense label maps).  Finite negative w / h are not validated (that would synchronise): the formulas apply as they are.
  *
  * lmv_rroi_plan -- one launch, one workgroup per RoI.  plan (lmv_rroi_plan_bytes(R, oh, ow, s) bytes, 8-byte aligned): R headers of LMV_RROI_HEADER_BYTES
  * {level, batch, valid, y0, y1, x0, x1, n: the rows / columns of the pixels its samples touch and the number of non-empty samples}, then R x (oh ow s s) sample

@@ -72,7 +72,8 @@ __global__ __launch_bounds__(256) void rroi_plan_kernel(RrPlanArgs a) {
     const float v = floorf(log2f(sqrtf(w * h) / a.finest + 1e-6f));
     lvl = v >= (float)(a.g.L - 1) ? a.g.L - 1 : v > 0.f ? (int)v : 0;          // (NaN: level 0)
   }
-  const bool valid = bf > -1.f && bf < (float)a.g.B && lvl >= 0 && lvl < a.g.L;          // (int)bf truncates towards zero, as the reference's `int roi_batch_ind = roi[0]`
+  // (int)bf truncates towards zero, as the reference's `int roi_batch_ind = roi[0]`; a non-finite field makes the RoI invalid, as in roi.hip
+  const bool valid = bf > -1.f && bf < (float)a.g.B && lvl >= 0 && lvl < a.g.L && isfinite(roi[1]) && isfinite(roi[2]) && isfinite(w) && isfinite(h) && isfinite(theta);
   const int lv = valid ? lvl : 0;
   w *= a.ext_w; h *= a.ext_h;
   const int H = a.g.H[lv], W = a.g.W[lv];
@@ -97,7 +98,7 @@ __global__ __launch_bounds__(256) void rroi_plan_kernel(RrPlanArgs a) {
       rec.yy = RR_EMPTY; rec.xx = 0; rec.w[0] = rec.w[1] = rec.w[2] = rec.w[3] = 0.f;
     } else {
       y = y < 0.f ? 0.f : y; x = x < 0.f ? 0.f : x;
-      int yl = (int)y, xl = (int)x, yh, xh;          // (a NaN coordinate converts to 0: the indices stay inside the map, the weights carry the NaN)
+      int yl = (int)y, xl = (int)x, yh, xh;          // (whatever the conversion gives, the clamps below keep the indices inside the map)
       if (yl >= H - 1) { yl = yh = H - 1; y = (float)yl; } else { yh = yl + 1; }
       if (xl >= W - 1) { xl = xh = W - 1; x = (float)xl; } else { xh = xl + 1; }
       yl = max(yl, 0); xl = max(xl, 0);

@@ -263,7 +263,9 @@ def reference_rroi_align(feats, rois, out_size, spatial_scales, sample_num: int,
     dxs = None if g is None else [np.zeros_like(f) for f in feats]
     for r in range(R):
         b, l = rois[r, 0], int(lv[r])
-        if not (-1.0 < b < B) or not 0 <= l < L:          # (the batch index truncates towards zero, as a C++ int conversion does)
+        if not (-1.0 < b < B) or not 0 <= l < L:          # (the batch index truncates towards zero, as a C++ int conversion does; NaN fails)
+            continue
+        if not np.isfinite(rois[r, 1:]).all():          # a non-finite cx, cy, w, h or theta: a zero row, no gradient (the rule of the horizontal operator)
             continue
         b = int(b)
         H, W = feats[l].shape[2:]
@@ -288,8 +290,8 @@ def _rroi_torch_level(feat: Tensor, rois: Tensor, out_size, scale: float, s: int
     B, C_, H, W = feat.shape
     oh, ow = out_size
     dt, dev, vt = rois.dtype, feat.device, feat.dtype          # the geometry in the RoIs' dtype (float32), the values in the features'
-    bi = rois[:, 0].long()
-    ok = (bi >= 0) & (bi < B)
+    ok = (rois[:, 0] > -1) & (rois[:, 0] < B) & torch.isfinite(rois[:, 1:]).all(1)          # (a non-finite cx, cy, w, h or theta: a zero row, no gradient)
+    bi = torch.nan_to_num(rois[:, 0]).clamp(-1, B).long()
     off = 0.5 if aligned else 0.0
     cw, ch = rois[:, 1] * scale - off, rois[:, 2] * scale - off
     rw, rh = rois[:, 3] * scale, rois[:, 4] * scale
@@ -304,7 +306,7 @@ def _rroi_torch_level(feat: Tensor, rois: Tensor, out_size, scale: float, s: int
     y = yy * ct - xx * st + ch[:, None, None, None, None]
     x = yy * st + xx * ct + cw[:, None, None, None, None]
     keep = ~((y < -1) | (y > H) | (x < -1) | (x > W)) & ok[:, None, None, None, None]
-    y, x = y.clamp(min=0), x.clamp(min=0)
+    y, x = torch.nan_to_num(y).clamp(min=0, max=H), torch.nan_to_num(x).clamp(min=0, max=W)          # (beyond H / W nothing is kept; the conversion stays defined)
     yl, xl = y.long(), x.long()
     ty, tx = yl >= H - 1, xl >= W - 1
     yl, xl = torch.where(ty, H - 1, yl), torch.where(tx, W - 1, xl)
@@ -336,7 +338,7 @@ def rroi_align_torch(feats: Sequence[Tensor], rois: Tensor, out_size, spatial_sc
     if L == 1 and levels is None:
         return _rroi_torch_level(feats[0], ext, (oh, ow), spatial_scales[0], s, aligned)
     if levels is None:
-        levels = torch.floor(torch.log2(torch.sqrt(rois[:, 3] * rois[:, 4]) / finest_scale + 1e-6)).clamp(min=0, max=L - 1).long()
+        levels = torch.nan_to_num(torch.floor(torch.log2(torch.sqrt(rois[:, 3] * rois[:, 4]) / finest_scale + 1e-6)), nan=0.0).clamp(min=0, max=L - 1).long()
     out = feats[0].new_zeros((rois.shape[0], feats[0].shape[1], oh, ow))
     for l in range(L):
         inds = (levels == l).nonzero(as_tuple=False).squeeze(1)
@@ -820,7 +822,7 @@ def _roi_torch_level(feat: Tensor, rois: Tensor, out_size, scale: float, s: int)
     x = start_w[:, None, None] + torch.arange(ow, device=dev, dtype=dt)[None, :, None] * bin_w[:, None, None] + (ix[None, None, :] + 0.5) * bin_w[:, None, None] / gwc          # [R, ow, Gw]
     my = (iy[None, None, :] < gh[:, None, None]) & ok[:, None, None] & ~((y < -1) | (y > H))
     mx = (ix[None, None, :] < gw[:, None, None]) & ~((x < -1) | (x > W))
-    y, x = torch.nan_to_num(y).clamp(min=0), torch.nan_to_num(x).clamp(min=0)
+    y, x = torch.nan_to_num(y).clamp(min=0, max=H), torch.nan_to_num(x).clamp(min=0, max=W)          # (beyond H / W nothing is kept; the conversion stays defined at 1e30)
     yl, xl = y.long().clamp(max=H - 1), x.long().clamp(max=W - 1)
     ty, tx = yl >= H - 1, xl >= W - 1
     yh, xh = torch.where(ty, yl, yl + 1), torch.where(tx, xl, xl + 1)

@@ -1342,8 +1342,8 @@ def rroi_plan(rois: Tensor, sizes: Sequence[Tuple[int, int]], spatial_scales: Se
     ``spatial_scales[l]`` per level; ``levels``: int32 [R] overriding the level rule; ``plan``: a caller-supplied uint8 buffer of ``rroi_plan_bytes`` (a captured call
     allocates nothing).  Returns the ``RroiPlan`` that ``rroi_align_fwd`` and ``rroi_align_bwd`` take (include/lemevit_hip.h has the level rule and the formulas)."""
     fn = "rroi_plan"
-    if rois.dim() != 2 or rois.shape[1] != 6 or rois.dtype != torch.float32:
-        raise ValueError(f"{fn}: float32 [R, 6] rois expected, got {rois.dtype} {tuple(rois.shape)}")
+    if rois.dim() != 2 or rois.shape[1] != 6 or rois.dtype != torch.float32 or not rois.is_contiguous():          # (the library reads rows of 6 floats)
+        raise ValueError(f"{fn}: contiguous float32 [R, 6] rois expected, got {rois.dtype} {tuple(rois.shape)}")
     if len(spatial_scales) != len(sizes):
         raise ValueError(f"{fn}: {len(spatial_scales)} scales for {len(sizes)} levels")
     R, (oh, ow) = int(rois.shape[0]), (int(out_size[0]), int(out_size[1]))
