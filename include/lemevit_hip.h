@@ -1111,6 +1111,95 @@ int lmv_sample_gather(const int64_t* inds, int num, const float* boxes, int box_
                       int64_t* s_gt_inds, int64_t* s_labels, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The head losses of the Oriented R-CNN configs (csrc/headloss.hip), forward and backward -- what follows lmv_random_sample / lmv_sample_gather in a training step.
+ * RPN head: CrossEntropyLoss(use_sigmoid=True) + SmoothL1Loss(beta=1/9); R-CNN head: CrossEntropyLoss(use_sigmoid=False) + SmoothL1Loss(beta=1.0) with
+ * reg_class_agnostic=True, num_classes=15.  Their sources are NOT part of the reference tree (only their names in the configs are): the rules below restate upstream
+ * (OBBDetection on mmdet 2.x) and are the specification.  An addition to ABI 14: callers detect it by symbol.
+ *
+ * Common to the four entry points: fp32 arithmetic, exponentials taken with the maximum subtracted, fp contraction off; NO floating-point atomics; every summation
+ * order is fixed by the arguments (two calls agree bit for bit); nothing is synchronised with the host and every call can be captured; every output element is
+ * written exactly once (a zero is +0.0) and no buffer needs pre-zeroing.  Maps and predictions are fp32 or bf16 (`dtype`: LMV_F32 / LMV_BF16, one for all of a
+ * call), read in place through ELEMENT strides; gradients are written in that dtype through their own strides.  The regression targets are never stored: a live row
+ * computes its target with the coder's device rule (the function lmv_box_encode inlines), so it has the bits that call would have written.
+ * means / stds: HOST arrays of D floats, passed by value as in lmv_box_encode.  beta, w_cls, w_bbox: the smooth-L1 threshold and the two loss weights.
+ *     smoothL1(d) = 0.5 d^2 / beta if |d| < beta, else |d| - 0.5 beta;   its derivative: d / beta if |d| < beta, else sign(d)
+ *
+ * lmv_rpn_loss_fwd / lmv_rpn_loss_bwd -- B images, L <= LMV_RPN_LOSS_MAX_LEVELS levels of (H_l, W_l) positions, A anchors per position.
+ *   Element space of one image: anchor r = (h W_l + w) A + a of level l is element off_l + r, off_l = sum_{l' < l} H_l' W_l' A -- the row order of
+ *     lmv_box_decode_map and of upstream's permute(0, 2, 3, 1).reshape; N = sum_l H_l W_l A.
+ *   levels       HOST table of L lmv_rpn_loss_level, read during the call: cls the class map [B, A, H, W] (channel a: the logit of anchor a), reg the regression
+ *                map [B, A D, H, W] (channel a D + d: delta d of anchor a), each with its four strides (batch, channel, row, column); dcls / dreg and their strides:
+ *                the two gradient maps, used by the backward call only
+ *   mask         uint8 [B, N], what lmv_random_sample writes (add_gt = 0): 0 not sampled, 1 sampled positive, anything else sampled negative
+ *   anchors      fp32 [N, 4] shared by all images (anchor_batch_stride == 0) or [B, N, 4], rows through anchor_stride >= 4
+ *   gts          fp32 [B, Gmax, 5] through gt_stride >= 5;  gt_counts nullable int32 [B] ON THE DEVICE, clamped to 0 .. Gmax by the kernel (null: Gmax)
+ *   gt_inds      int64 [B, N], what lmv_max_iou_assign writes
+ *   kind         LMV_CODER_MIDPOINT (D = 6); nothing else is wired up
+ *   Rules: a sampled anchor (mask != 0) with logit z and t = [mask == 1] has the class term max(z, 0) - z t + log1p(exp(-|z|)) (weight 1).  A row is LIVE for
+ *     the regression if mask == 1 and 1 <= gt_inds <= count[b] (the rule of lmv_box_encode); its term is sum_d smoothL1(reg_d - target_d), target = the midpoint
+ *     encode of the anchor against gts[b, gt_inds - 1].  With n_pos_b / n_neg_b the number of mask bytes == 1 / other non-zero bytes of image b:
+ *         avg = sum_b (max(n_pos_b, 1) + max(n_neg_b, 1))          (upstream's num_total_samples)
+ *         loss_cls[l] = w_cls sum_{level l} class terms / avg;   loss_bbox[l] = w_bbox sum_{level l} regression terms / avg
+ *   stats        fp32 [LMV_RPN_LOSS_STATS(L) = 2 L + 3]: loss_cls[L], loss_bbox[L], n_pos, n_neg (all images), 1 / avg
+ *   Forward: two launches.  The sweep gives one wave to every 1024 consecutive mask bytes of an image, 16 bytes per lane -- one 16-byte load when N % 16 == 0 and
+ *     the mask is 16-byte aligned, byte loads otherwise, the same arithmetic in the same order either way -- and only a non-zero byte does work; a lane adds its
+ *     terms in element order, the wave adds its lanes with a fixed butterfly and stores one partial row.  One reduce workgroup adds the rows in double in a fixed
+ *     order.  workspace: lmv_rpn_loss_workspace_bytes(B, N) = 48 B ceil(N / 1024) bytes, 16-byte aligned; 0 for a B or N the call refuses.
+ *   Backward: one launch, one thread per (image, anchor).  It re-reads the mask, the maps and the assignment, reads 1 / avg from `stats` (what the forward call
+ *     wrote) and gout, a nullable DEVICE float [2 L] -- the upstream gradient of loss_cls[0 .. L-1], loss_bbox[0 .. L-1]; null: ones -- and writes EVERY element of
+ *     the 2 L gradient maps once: dcls = gout[l] w_cls (sigmoid(z) - t) / avg at a sampled anchor, dreg = gout[L + l] w_bbox smoothL1'(reg - target) / avg on a
+ *     live row, +0.0 everywhere else (also on a level without a sampled anchor).  A gradient map must not alias itself (injective strides).
+ *
+ * lmv_rcnn_loss_fwd / lmv_rcnn_loss_bwd -- R sampled RoIs of B images, K classes plus the background class K.
+ *   cls_score    [R, K + 1] through cls_stride >= K + 1 elements;   bbox_pred [R, D C] through bbox_stride >= D C, C = 1 (class-agnostic) or C = K
+ *   rois         fp32 [R, 1 + 5] through roi_stride >= 6, what lmv_sample_gather writes: column 0 is the image index b; b outside 0 .. B - 1 (or NaN): padding
+ *   s_gt_inds, s_labels   int64 [R];   gts, gt_counts as above;   kind LMV_CODER_OBB2OBB (D = 5); nothing else is wired up
+ *   Rules: a row is VALID if 0 <= label <= K and its b is in range, LIVE if valid, label < K and 1 <= s_gt_inds <= count[b]; n_valid = the number of valid rows.
+ *         loss_cls  = w_cls sum_valid (log sum_c exp(z_c - max z) - (z_label - max z)) / max(n_valid, 1)
+ *         loss_bbox = w_bbox sum_live sum_d smoothL1(bbox_pred[set D + d] - target_d) / n_valid, 0 if n_valid == 0; set = 0 if C == 1, else the label; target =
+ *                     the OBB2OBB encode of rois[r, 1 .. 5] against gts[b, s_gt_inds - 1].  (The divisor is upstream's bbox_targets.size(0): all sampled RoIs.)
+ *         acc       = 100 #(valid rows with argmax == label) / n_valid, 0 if n_valid == 0; argmax: the first index of the maximum, NaN greatest (lmv_dense_loss_fwd)
+ *   stats        fp32 [LMV_RCNN_LOSS_STATS = 7]: loss_cls, loss_bbox, acc, n_valid, n_live, 1 / max(n_valid, 1), 1 / n_valid (0 if n_valid == 0)
+ *   Forward: two launches (one lane per row, one partial row per wave; one reduce workgroup, in double, in a fixed order); workspace
+ *     lmv_rcnn_loss_workspace_bytes(R) = 32 ceil(R / 64) bytes, 16-byte aligned.  R == 0 writes zero stats (all seven) and nothing else.
+ *   Backward: one launch, one thread per row; gout: nullable DEVICE float [2] (loss_cls, loss_bbox).  It writes all of dcls [R, K + 1] (dcls_stride) and dbbox
+ *     [R, D C] (dbbox_stride): dcls = gout[0] w_cls (softmax(z) - onehot(label)) / max(n_valid, 1) on a valid row, a zero row elsewhere; dbbox = gout[1] w_bbox
+ *     smoothL1'(.) / n_valid in the chosen set of a live row, +0.0 everywhere else.  R == 0 launches nothing.
+ *
+ * Limits: N <= LMV_OBB_MAX_BOXES, H_l W_l <= LMV_OBB_MAX_BOXES, 1 <= A <= LMV_CODER_MAX_SETS, R and Gmax <= LMV_OBB_MAX_BOXES, B in 1 .. LMV_ASSIGN_MAX_BATCH,
+ * 1 <= K <= LMV_CODER_MAX_SETS - 1.  The reduce launch of a forward call is ONE workgroup over all partial rows (RPN: B ceil(N / 1024); R-CNN: ceil(R / 64)): 2 048 /
+ * 64 rows at the configs' shapes; at the limits (B = 4096 with N = 2^20: 4 M rows) its time grows with the row count and it, not the sweep, sets the call's time.
+ * Refused with LMV_ERR_SHAPE and a message that starts "rpn_loss" / "rcnn_loss", before any launch: an unknown kind or dtype, sizes outside the limits, null
+ * pointers, buffers not aligned to their element (the workspace: 16 bytes), a map stride below 1 or a batch stride below the extent of one image, row strides below
+ * the row, a beta that is not a positive finite number, a negative or NaN loss weight, null means / stds or a NaN among them, a workspace that is too small.
+ * ------------------------------------------------------------------------------------------ */
+#define LMV_RPN_LOSS_MAX_LEVELS 5
+#define LMV_RPN_LOSS_STATS(L) (2 * (L) + 3)
+#define LMV_RCNN_LOSS_STATS 7
+typedef struct lmv_rpn_loss_level {
+  const void* cls; const void* reg;          /* [B, A, H, W] and [B, A D, H, W] */
+  void* dcls; void* dreg;                    /* their gradients (backward only) */
+  int64_t cls_stride[4], reg_stride[4], dcls_stride[4], dreg_stride[4];          /* batch, channel, row, column; in elements */
+  int32_t H, W;
+} lmv_rpn_loss_level;
+size_t lmv_rpn_loss_workspace_bytes(int B, int64_t N);
+int lmv_rpn_loss_fwd(const lmv_rpn_loss_level* levels, int L, int A, int dtype, int B, const uint8_t* mask, const float* anchors, int anchor_stride,
+                     int64_t anchor_batch_stride, const float* gts, int gt_stride, int Gmax, const int32_t* gt_counts, const int64_t* gt_inds, int kind,
+                     const float* means, const float* stds, float beta, float w_cls, float w_bbox, void* workspace, size_t workspace_bytes, float* stats, void* stream);
+int lmv_rpn_loss_bwd(const lmv_rpn_loss_level* levels, int L, int A, int dtype, int B, const uint8_t* mask, const float* anchors, int anchor_stride,
+                     int64_t anchor_batch_stride, const float* gts, int gt_stride, int Gmax, const int32_t* gt_counts, const int64_t* gt_inds, int kind,
+                     const float* means, const float* stds, float beta, float w_cls, float w_bbox, const float* stats, const float* gout, void* stream);
+size_t lmv_rcnn_loss_workspace_bytes(int R);
+int lmv_rcnn_loss_fwd(const void* cls_score, int64_t cls_stride, const void* bbox_pred, int64_t bbox_stride, int dtype, int R, int K, int C, const float* rois,
+                      int roi_stride, const int64_t* s_gt_inds, const int64_t* s_labels, const float* gts, int gt_stride, int B, int Gmax, const int32_t* gt_counts,
+                      int kind, const float* means, const float* stds, float beta, float w_cls, float w_bbox, void* workspace, size_t workspace_bytes, float* stats,
+                      void* stream);
+int lmv_rcnn_loss_bwd(const void* cls_score, int64_t cls_stride, const void* bbox_pred, int64_t bbox_stride, int dtype, int R, int K, int C, const float* rois,
+                      int roi_stride, const int64_t* s_gt_inds, const int64_t* s_labels, const float* gts, int gt_stride, int B, int Gmax, const int32_t* gt_counts,
+                      int kind, const float* means, const float* stds, float beta, float w_cls, float w_bbox, const float* stats, const float* gout, void* dcls,
+                      int64_t dcls_stride, void* dbbox, int64_t dbbox_stride, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Whole-block schedules: ONE call enqueues every launch of a LeMeBlock (models/lemevit.py:500-660) on token-major tensors
  * x [B, H*W, C], c [B, M, C] -- `LeMeBlock.forward_with_x` ("S", :615-650), `forward_with_xc` ("D", :542-582), `forward_with_c`
  * ("C", :584-613; x is returned untouched by the caller, x_out / dx_out may be NULL).  Replaces the ~12 / ~30 per-op calls a Python

@@ -23,6 +23,7 @@ from .detection import arb_batched_nms, obb_nms, obb_nms_padded, obb_nms_torch, 
 from .detection import RoIAlign, RoIExtractor, batched_nms, nms, nms_padded, nms_torch, reference_nms, reference_roi_align, roi_align, roi_align_torch  # noqa: F401
 from .detection import AssignResult, MaxIoUAssigner, bbox_overlaps, bbox_overlaps_torch, max_iou_assign_torch, reference_bbox_overlaps, reference_max_iou_assign  # noqa: F401
 from .detection import BatchSample, OBBRandomSampler, RandomSampler, SamplingResult, random_sample_torch, reference_random_sample, reference_sample_gather  # noqa: F401
+from .detection import bbox_head_loss, bbox_head_loss_torch, reference_bbox_head_loss, reference_rpn_head_loss, rpn_head_loss, rpn_head_loss_torch  # noqa: F401
 from . import dist  # noqa: F401  (wrap_ddp, FlatGradSync, attach_flat_grad_sync)
 from .registry import create_model, is_model, list_models, load_checkpoint, register_model  # noqa: F401
 from .registry import lemevit_base, lemevit_small, lemevit_small_v2, lemevit_tiny, lemevit_tiny_v2, vit_tiny  # noqa: F401
@@ -38,4 +39,5 @@ __all__ = ["create_model", "register_model", "list_models", "is_model", "load_ch
            "roi_align", "RoIAlign", "RoIExtractor", "reference_roi_align", "roi_align_torch", "nms", "batched_nms", "nms_padded", "reference_nms", "nms_torch",
            "bbox_overlaps", "MaxIoUAssigner", "AssignResult", "reference_bbox_overlaps", "reference_max_iou_assign", "bbox_overlaps_torch", "max_iou_assign_torch",
            "RandomSampler", "OBBRandomSampler", "BatchSample", "SamplingResult", "reference_random_sample",
-           "reference_sample_gather", "random_sample_torch"]
+           "reference_sample_gather", "random_sample_torch", "rpn_head_loss", "bbox_head_loss", "rpn_head_loss_torch", "bbox_head_loss_torch",
+           "reference_rpn_head_loss", "reference_bbox_head_loss"]

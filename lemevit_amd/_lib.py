@@ -37,6 +37,7 @@ NMS_MAX = 16384          # LMV_NMS_MAX
 ASSIGN_HORIZONTAL, ASSIGN_ROTATED, ASSIGN_GT_CHUNK, ASSIGN_MAX_GT, ASSIGN_MAX_BATCH = 0, 1, 64, 16384, 4096          # LMV_ASSIGN_*
 CODER_MIDPOINT, CODER_OBB2OBB, CODER_MAX_SETS = 0, 1, 128          # LMV_CODER_*
 SAMPLE_MAX_NUM = 16384          # LMV_SAMPLE_MAX_NUM
+RPN_LOSS_MAX_LEVELS, RCNN_LOSS_STATS = 5, 7          # LMV_RPN_LOSS_MAX_LEVELS, LMV_RCNN_LOSS_STATS (LMV_RPN_LOSS_STATS(L) = 2 L + 3)
 
 
 class LinearProblem(C.Structure):
@@ -128,6 +129,11 @@ class EraseRecord(C.Structure):
 class RroiLevel(C.Structure):
     _fields_ = [("data", C.c_void_p), ("sb", C.c_int64), ("sc", C.c_int64), ("sh", C.c_int64), ("sw", C.c_int64), ("H", C.c_int32), ("W", C.c_int32),
                 ("spatial_scale", C.c_float), ("_pad", C.c_int32)]
+
+
+class RpnLossLevel(C.Structure):
+    _fields_ = [("cls", C.c_void_p), ("reg", C.c_void_p), ("dcls", C.c_void_p), ("dreg", C.c_void_p), ("cls_stride", C.c_int64 * 4), ("reg_stride", C.c_int64 * 4),
+                ("dcls_stride", C.c_int64 * 4), ("dreg_stride", C.c_int64 * 4), ("H", C.c_int32), ("W", C.c_int32)]
 
 
 _P, _I, _L, _F, _Z = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_size_t
@@ -242,6 +248,12 @@ SIGNATURES = {
     "lmv_random_sample_workspace_bytes": (_Z, [_I, _I]),
     "lmv_random_sample": (_I, [_P, _I, _I, _P, _I, _I, _I, _I, _F, _P, _P, _P, _Z, _P, _P, _P, _P, _P]),
     "lmv_sample_gather": (_I, [_P, _I, _P, _I, _L, _I, _I, _P, _I, _I, _I, _P, _P, _P, _I, _L, _P, _P, _P, _P]),
+    "lmv_rpn_loss_workspace_bytes": (_Z, [_I, _L]),
+    "lmv_rpn_loss_fwd": (_I, [C.POINTER(RpnLossLevel), _I, _I, _I, _I, _P, _P, _I, _L, _P, _I, _I, _P, _P, _I, _P, _P, _F, _F, _F, _P, _Z, _P, _P]),
+    "lmv_rpn_loss_bwd": (_I, [C.POINTER(RpnLossLevel), _I, _I, _I, _I, _P, _P, _I, _L, _P, _I, _I, _P, _P, _I, _P, _P, _F, _F, _F, _P, _P, _P]),
+    "lmv_rcnn_loss_workspace_bytes": (_Z, [_I]),
+    "lmv_rcnn_loss_fwd": (_I, [_P, _L, _P, _L, _I, _I, _I, _I, _P, _I, _P, _P, _P, _I, _I, _I, _P, _I, _P, _P, _F, _F, _F, _P, _Z, _P, _P]),
+    "lmv_rcnn_loss_bwd": (_I, [_P, _L, _P, _L, _I, _I, _I, _I, _P, _I, _P, _P, _P, _I, _I, _I, _P, _I, _P, _P, _F, _F, _F, _P, _P, _P, _L, _P, _L, _P]),
     "lmv_block_arena_bytes": (_Z, [C.POINTER(BlockDesc)]),
     "lmv_block_bwd_scratch_bytes": (_Z, [C.POINTER(BlockDesc)]),
     "lmv_block_fwd": (_I, [C.POINTER(BlockDesc), _P, _P, _P, _P, _P, _Z, _I, _P]),

@@ -78,8 +78,23 @@ between ``assign_batched`` and ``encode_assigned``, so that the whole target sid
 Two launches and a memset per ``sample_batched``, one launch per ``gather``: no ``nonzero``, no ``randperm``, no ``cat`` of the ground truths, no host round trip, two
 calls with one key agree bit for bit.  A deliberate difference: the subset is uniformly random as upstream's is, but NOT the draw ``torch.randperm`` would make, and
 ``inds`` is ordered (positives ascending, then negatives ascending, then -1).  ``priorities`` replaces the random draw with the caller's order (the smallest first):
-a score-ordered sampler.  Not provided: ``IoUBalancedNegSampler``, ``OHEMSampler``, ``PseudoSampler``, ``InstanceBalancedPosSampler``, the head losses, fp16 / bf16
+a score-ordered sampler.  Not provided: ``IoUBalancedNegSampler``, ``OHEMSampler``, ``PseudoSampler``, ``InstanceBalancedPosSampler``, fp16 / bf16
 boxes.  ``reference_random_sample`` / ``reference_sample_gather`` are the numpy oracles, ``random_sample_torch`` upstream's literal per-image tensor code.
+
+The head losses of both heads (csrc/headloss.hip), forward and backward, each ONE autograd node -- the last step of target generation, after which assigner ->
+sampler -> coder -> loss -> backward run without a host synchronisation (sources not in the reference tree: include/lemevit_hip.h restates upstream's rules):
+
+    from lemevit_amd.detection import rpn_head_loss, bbox_head_loss
+    losses = rpn_head_loss(cls_scores, bbox_preds, anchors, gts, gt_inds, s.mask, gt_counts)          # dict(loss_rpn_cls [L], loss_rpn_bbox [L]); maps read in place
+    losses = bbox_head_loss(cls_score, bbox_pred, rois, gts, s_gt_inds, s_labels, gt_counts, num_classes=15)          # dict(loss_cls, acc, loss_bbox)
+
+Sigmoid cross-entropy + smooth L1 (beta 1/9) over the sampled anchors with upstream's ``num_total_samples`` as the averaging factor; softmax cross-entropy, accuracy
+and smooth L1 (beta 1) over the sampled RoIs with the number of valid rows.  No dense [B, N, 6] targets, no permute copies, no ``.item()``: a live row encodes its
+target inline with the coders' device rule.  Two launches forward, one backward, no floating-point atomics, two calls agree bit for bit; with ``stats`` /
+``workspace`` supplied the forward allocates nothing (``ops.rpn_loss_bwd`` / ``ops.rcnn_loss_bwd`` take the backward's buffers).  Not provided: stand-alone ``CrossEntropyLoss`` / ``SmoothL1Loss`` modules on arbitrary tensors,
+``build_loss``, focal / IoU / L1 losses, ``pos_weight > 0``, ``reduction_override``, class weights, the Mask R-CNN config's ``DeltaXYWHBBoxCoder`` targets and mask
+loss, fp16.  ``reference_rpn_head_loss`` / ``reference_bbox_head_loss`` are the numpy float64 oracles (losses, counts, analytic gradients), ``rpn_head_loss_torch``
+/ ``bbox_head_loss_torch`` the stock-PyTorch formulations.
 """
 from __future__ import annotations
 
@@ -1893,3 +1908,278 @@ class RandomSampler:
 class OBBRandomSampler(RandomSampler):
     """Upstream's ``OBBRandomSampler`` (the oriented R-CNN head's sampler: boxes and ground truths (cx, cy, w, h, theta)): the same code -- the sampler never looks
     at a coordinate, and ``gather`` / ``sample`` take the column count from the ground truths."""
+
+
+# -------------------------------------------------------------------------------------------
+# Head losses: the RPN head's and the R-CNN head's classification + regression losses, forward and backward (csrc/headloss.hip)
+# -------------------------------------------------------------------------------------------
+RPN_TARGET_STDS = (1.0, 1.0, 1.0, 1.0, 0.5, 0.5)          # the configs' MidpointOffsetCoder
+RCNN_TARGET_STDS = (0.1, 0.1, 0.2, 0.2, 0.1)              # the configs' OBB2OBBDeltaXYWHTCoder
+
+
+def _grad_like(t: Tensor) -> Tensor:
+    """an uninitialised gradient in the input's own layout; a layout in which two indices share an address (an expanded view) gets a contiguous one instead"""
+    if ops.strides_injective(t.shape, t.stride()):
+        return torch.empty_strided(t.shape, t.stride(), dtype=t.dtype, device=t.device)
+    return torch.empty(t.shape, dtype=t.dtype, device=t.device)
+
+
+def _gout(parts: Sequence[Optional[Tensor]], sizes: Sequence[int], dev) -> Tensor:
+    """the upstream gradients of the returned losses as one float32 vector (an unused loss: zeros)"""
+    return torch.cat([torch.zeros(n, device=dev) if g is None else g.reshape(n).float() for g, n in zip(parts, sizes)])
+
+
+def _loss_stats(stats: Optional[Tensor]) -> None:
+    """a caller-supplied ``stats`` buffer is about to be overwritten by a kernel: tell autograd, so that an earlier node that saved it raises in its backward
+    instead of reading this call's 1 / avg"""
+    if stats is not None:
+        torch.autograd.graph.increment_version(stats)
+
+
+class _RpnLossFn(torch.autograd.Function):
+    """ONE node over the 2 L maps of the RPN head: forward = sweep + reduce, backward = one launch that writes every gradient map once."""
+
+    @staticmethod
+    def forward(ctx, cfg, stats, workspace, anchors, gts, gt_inds, mask, gt_counts, *maps):
+        L = len(maps) // 2
+        _loss_stats(stats)
+        stats = ops.rpn_loss_fwd(maps[:L], maps[L:], anchors, gts, gt_inds, mask, gt_counts, *cfg, stats, workspace)
+        ctx.save_for_backward(stats, anchors, gts, gt_inds, mask, gt_counts, *maps)
+        ctx.cfg = cfg
+        return stats[:L], stats[L:2 * L]
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_cls, g_bbox):
+        stats, anchors, gts, gt_inds, mask, gt_counts, *maps = ctx.saved_tensors
+        L = len(maps) // 2
+        grads = [_grad_like(m) for m in maps]
+        ops.rpn_loss_bwd(maps[:L], maps[L:], anchors, gts, gt_inds, mask, gt_counts, *ctx.cfg, stats, _gout((g_cls, g_bbox), (L, L), stats.device), grads[:L], grads[L:])
+        return (None,) * 8 + tuple(grads)
+
+
+def _loss_aux(gt_inds: Tensor, gt_counts: Optional[Tensor]):
+    if gt_inds.dtype != torch.int64:
+        gt_inds = gt_inds.to(torch.int64)
+    if gt_counts is not None and gt_counts.dtype != torch.int32:
+        gt_counts = gt_counts.to(torch.int32)
+    return gt_inds, gt_counts
+
+
+def rpn_head_loss(cls_scores: Sequence[Tensor], bbox_preds: Sequence[Tensor], anchors: Tensor, gts: Tensor, gt_inds: Tensor, mask: Tensor,
+                  gt_counts: Optional[Tensor] = None, coder: Optional[MidpointOffsetCoder] = None, beta: float = 1.0 / 9.0, loss_weight_cls: float = 1.0,
+                  loss_weight_bbox: float = 1.0, stats: Optional[Tensor] = None, workspace: Optional[Tensor] = None) -> dict:
+    """The oriented RPN head's losses of B images -- upstream's ``CrossEntropyLoss(use_sigmoid=True)`` and ``SmoothL1Loss(beta=1/9)`` over the sampled anchors, with
+    ``avg_factor = num_total_samples`` -- as ONE autograd node over all maps: ``cls_scores[l]`` [B, A, H_l, W_l] and ``bbox_preds[l]`` [B, 6 A, H_l, W_l] (float32 or
+    bfloat16, any strides, read in place: no ``permute(0, 2, 3, 1).reshape`` copies); ``anchors`` [N, 4] or [B, N, 4] in the level-major row order of those
+    reshapes; ``gts`` [B, Gmax, 5]; ``gt_inds`` [B, N] from ``assign_batched``; ``mask`` [B, N] from ``RandomSampler.sample_batched``.  No dense target tensor is
+    built: a sampled positive encodes its target inline.  Returns ``dict(loss_rpn_cls=Tensor[L], loss_rpn_bbox=Tensor[L])`` (unbound: upstream's per-level lists).
+    Only the maps are differentiable.  ``stats`` (float32 [2 L + 3]) and ``workspace`` (uint8, ``ops.rpn_loss_workspace_bytes(B, N)``) may be supplied: the forward
+    then allocates nothing.  The returned losses are views of ``stats`` and the backward reads 1 / avg from it: a supplied buffer must not be handed to another
+    call before this one's backward has run (autograd raises if it is).  The backward allocates the gradient maps and a [2 L] vector; a captured step that needs
+    an allocation-free backward calls ``ops.rpn_loss_bwd`` with its own buffers, which is the launch this node makes."""
+    coder = MidpointOffsetCoder(target_stds=RPN_TARGET_STDS) if coder is None else coder
+    if coder.kind != "midpoint":
+        raise ValueError(f"rpn_head_loss: a MidpointOffsetCoder is needed, got {type(coder).__name__}")
+    gt_inds, gt_counts = _loss_aux(gt_inds, gt_counts)
+    cfg = (coder.means, coder.stds, float(beta), float(loss_weight_cls), float(loss_weight_bbox))
+    loss_cls, loss_bbox = _RpnLossFn.apply(cfg, stats, workspace, anchors.detach().float(), gts.detach().float(), gt_inds, mask, gt_counts, *cls_scores, *bbox_preds)
+    return dict(loss_rpn_cls=loss_cls, loss_rpn_bbox=loss_bbox)
+
+
+class _RcnnLossFn(torch.autograd.Function):
+    """ONE node over cls_score and bbox_pred: forward = sweep + reduce, backward = one launch that writes both gradients once."""
+
+    @staticmethod
+    def forward(ctx, cfg, stats, workspace, rois, gts, s_gt_inds, s_labels, gt_counts, cls_score, bbox_pred):
+        _loss_stats(stats)
+        stats = ops.rcnn_loss_fwd(cls_score, bbox_pred, rois, gts, s_gt_inds, s_labels, gt_counts, *cfg, stats, workspace)
+        ctx.save_for_backward(stats, rois, gts, s_gt_inds, s_labels, gt_counts, cls_score, bbox_pred)
+        ctx.cfg = cfg
+        acc = stats[2]
+        ctx.mark_non_differentiable(acc)
+        return stats[0], stats[1], acc
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_cls, g_bbox, _g_acc):
+        stats, rois, gts, s_gt_inds, s_labels, gt_counts, cls_score, bbox_pred = ctx.saved_tensors
+        dcls = torch.empty_like(cls_score, memory_format=torch.contiguous_format)
+        dbbox = torch.empty_like(bbox_pred, memory_format=torch.contiguous_format)
+        ops.rcnn_loss_bwd(cls_score, bbox_pred, rois, gts, s_gt_inds, s_labels, gt_counts, *ctx.cfg, stats, _gout((g_cls, g_bbox), (1, 1), stats.device), dcls, dbbox)
+        return (None,) * 8 + (dcls, dbbox)
+
+
+def bbox_head_loss(cls_score: Tensor, bbox_pred: Tensor, rois: Tensor, gts: Tensor, s_gt_inds: Tensor, s_labels: Tensor, gt_counts: Optional[Tensor] = None,
+                   coder: Optional[OBB2OBBDeltaXYWHTCoder] = None, num_classes: int = 15, reg_class_agnostic: bool = True, beta: float = 1.0,
+                   loss_weight_cls: float = 1.0, loss_weight_bbox: float = 1.0, stats: Optional[Tensor] = None, workspace: Optional[Tensor] = None) -> dict:
+    """The oriented R-CNN head's losses over the R sampled RoIs of B images -- upstream's ``CrossEntropyLoss(use_sigmoid=False)``, ``accuracy`` and
+    ``SmoothL1Loss(beta=1.0)`` -- as ONE autograd node over ``cls_score`` [R, num_classes + 1] and ``bbox_pred`` [R, 5] (``reg_class_agnostic``) or
+    [R, 5 num_classes] (float32 or bfloat16, read in place through their row stride).  ``rois`` [B, num, 6] or [R, 6], ``s_gt_inds`` / ``s_labels`` [B, num] or [R]:
+    what ``OBBRandomSampler.gather(..., bg_label=num_classes)`` returns, padding rows (b = -1, label = -1) included; ``gts`` [B, Gmax, 5].  The averaging factors
+    (the number of valid rows) stay on the device: no ``.item()``, no ``pos_inds.any()``, no boolean-index copy.  Returns ``dict(loss_cls, acc, loss_bbox)``, 0-dim
+    tensors; ``acc`` carries no gradient.  ``stats`` (float32 [7]) and ``workspace`` (uint8, ``ops.rcnn_loss_workspace_bytes(R)``) may be supplied: the forward then
+    allocates nothing (the rule for a supplied ``stats`` is that of ``rpn_head_loss``).  The backward allocates both gradients and a [2] vector; a captured step
+    that needs an allocation-free backward calls ``ops.rcnn_loss_bwd`` with its own buffers, which is the launch this node makes."""
+    coder = OBB2OBBDeltaXYWHTCoder(target_stds=RCNN_TARGET_STDS) if coder is None else coder
+    if coder.kind != "obb2obb":
+        raise ValueError(f"bbox_head_loss: an OBB2OBBDeltaXYWHTCoder is needed, got {type(coder).__name__}")
+    K = int(num_classes)
+    if cls_score.dim() != 2 or cls_score.shape[1] != K + 1:
+        raise ValueError(f"bbox_head_loss: cls_score: [R, num_classes + 1 = {K + 1}] expected, got {tuple(cls_score.shape)}")
+    if bbox_pred.dim() != 2 or bbox_pred.shape[1] != (5 if reg_class_agnostic else 5 * K):
+        raise ValueError(f"bbox_head_loss: bbox_pred: [R, {5 if reg_class_agnostic else 5 * K}] expected (reg_class_agnostic={reg_class_agnostic}), got {tuple(bbox_pred.shape)}")
+    s_gt_inds, gt_counts = _loss_aux(s_gt_inds, gt_counts)
+    if s_labels.dtype != torch.int64:
+        s_labels = s_labels.to(torch.int64)
+    cfg = (coder.means, coder.stds, float(beta), float(loss_weight_cls), float(loss_weight_bbox))
+    loss_cls, loss_bbox, acc = _RcnnLossFn.apply(cfg, stats, workspace, rois.detach().float().reshape(-1, 6), gts.detach().float(), s_gt_inds.reshape(-1),
+                                                 s_labels.reshape(-1), gt_counts, cls_score, bbox_pred)
+    return dict(loss_cls=loss_cls, acc=acc, loss_bbox=loss_bbox)
+
+
+# ---- the literal stock-PyTorch formulations: what a user writes today; any device, the inputs' dtype; gradients from autograd ----
+def _smooth_l1_torch(pred: Tensor, target: Tensor, beta: float) -> Tensor:
+    diff = torch.abs(pred - target)
+    return torch.where(diff < beta, 0.5 * diff * diff / beta, diff - 0.5 * beta)
+
+
+def rpn_head_loss_torch(cls_scores: Sequence[Tensor], bbox_preds: Sequence[Tensor], anchors: Tensor, gts: Tensor, gt_inds: Tensor, mask: Tensor,
+                        gt_counts: Optional[Tensor] = None, means=(0.0,) * 6, stds=RPN_TARGET_STDS, beta: float = 1.0 / 9.0, loss_weight_cls: float = 1.0,
+                        loss_weight_bbox: float = 1.0) -> dict:
+    """What a user writes today (upstream's ``RPNHead.loss``): dense [B, N, 6] targets from ``encode_assigned_torch``, per level the ``permute(0, 2, 3, 1).reshape``
+    copies of both maps, a weighted ``binary_cross_entropy_with_logits`` over all anchors and the element-wise smooth-L1 chain over all [B N, 6] elements"""
+    import torch.nn.functional as F
+    dt = cls_scores[0].dtype
+    targets, weights = encode_assigned_torch(midpoint_encode_torch, anchors.to(dt), gts.to(dt), gt_inds, means, stds, gt_counts, mask == 1)
+    labels, label_weights = (mask == 1).to(dt), (mask != 0).to(dt)
+    n_pos, n_neg = (mask == 1).sum(1), ((mask != 0) & (mask != 1)).sum(1)
+    avg = (n_pos.clamp(min=1) + n_neg.clamp(min=1)).sum().to(dt)          # num_total_samples
+    off, loss_cls, loss_bbox = 0, [], []
+    for c, r in zip(cls_scores, bbox_preds):
+        B, A, H, W = c.shape
+        n = H * W * A
+        z = c.permute(0, 2, 3, 1).reshape(-1)
+        d = r.permute(0, 2, 3, 1).reshape(-1, 6)
+        lc = F.binary_cross_entropy_with_logits(z, labels[:, off:off + n].reshape(-1), reduction="none") * label_weights[:, off:off + n].reshape(-1)
+        lb = _smooth_l1_torch(d, targets[:, off:off + n].reshape(-1, 6), beta) * weights[:, off:off + n].reshape(-1, 1)
+        loss_cls.append(loss_weight_cls * lc.sum() / avg)
+        loss_bbox.append(loss_weight_bbox * lb.sum() / avg)
+        off += n
+    return dict(loss_rpn_cls=torch.stack(loss_cls), loss_rpn_bbox=torch.stack(loss_bbox))
+
+
+def bbox_head_loss_torch(cls_score: Tensor, bbox_pred: Tensor, rois: Tensor, gts: Tensor, s_gt_inds: Tensor, s_labels: Tensor, gt_counts: Optional[Tensor] = None,
+                         means=(0.0,) * 5, stds=RCNN_TARGET_STDS, num_classes: int = 15, reg_class_agnostic: bool = True, beta: float = 1.0,
+                         loss_weight_cls: float = 1.0, loss_weight_bbox: float = 1.0) -> dict:
+    """What a user writes today (upstream's ``OBBoxHead.loss``): ``avg_factor = max(sum(label_weights > 0).item(), 1)`` and ``if pos_inds.any():`` (two host
+    synchronisations), ``cross_entropy``, ``accuracy``, a boolean-index copy of the positive rows, ``encode`` and the smooth-L1 chain"""
+    import torch.nn.functional as F
+    dt, K = cls_score.dtype, int(num_classes)
+    rois, ind, lab = rois.reshape(-1, 6).to(dt), s_gt_inds.reshape(-1), s_labels.reshape(-1)
+    B, Gmax = gts.shape[0], gts.shape[1]
+    b = rois[:, 0]
+    valid = (lab >= 0) & (lab <= K) & (b >= 0) & (b < B)
+    n_valid = int(valid.sum().item())
+    zero = cls_score.sum() * 0
+    if n_valid == 0:
+        return dict(loss_cls=zero, acc=zero.detach(), loss_bbox=bbox_pred.sum() * 0)
+    rows = torch.nonzero(valid).squeeze(1)
+    loss_cls = loss_weight_cls * F.cross_entropy(cls_score[rows], lab[rows], reduction="sum") / max(n_valid, 1)
+    acc = 100.0 * (cls_score[rows].argmax(1) == lab[rows]).sum().to(dt) / n_valid
+    bi = b.clamp(0, B - 1).long()
+    count = torch.full((B,), Gmax, device=gts.device, dtype=torch.int64) if gt_counts is None else gt_counts.clamp(0, Gmax).long()
+    live = valid & (lab < K) & (ind >= 1) & (ind <= count[bi])
+    if live.any():
+        pos = torch.nonzero(live).squeeze(1)
+        target = obb2obb_encode_torch(rois[pos, 1:], gts.to(dt)[bi[pos], ind[pos] - 1], means, stds)
+        pred = bbox_pred[pos] if reg_class_agnostic else bbox_pred.view(bbox_pred.shape[0], -1, 5)[pos, lab[pos]]
+        loss_bbox = loss_weight_bbox * _smooth_l1_torch(pred, target, beta).sum() / n_valid
+    else:
+        loss_bbox = bbox_pred.sum() * 0
+    return dict(loss_cls=loss_cls, acc=acc.detach(), loss_bbox=loss_bbox)
+
+
+# ---- the numpy float64 oracles, from the rules of include/lemevit_hip.h: losses, counts and analytic gradients ----
+def _f64(t) -> np.ndarray:
+    return t.detach().to(torch.float64).cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t, dtype=np.float64)
+
+
+def _smooth_l1_np(d: np.ndarray, beta: float):
+    a = np.abs(d)
+    return np.where(a < beta, 0.5 * d * d / beta, a - 0.5 * beta), np.where(a < beta, d / beta, np.sign(d))
+
+
+def reference_rpn_head_loss(cls_scores, bbox_preds, anchors, gts, gt_inds, mask, gt_counts=None, means=(0.0,) * 6, stds=RPN_TARGET_STDS, beta: float = 1.0 / 9.0,
+                            loss_weight_cls: float = 1.0, loss_weight_bbox: float = 1.0, gout=None) -> dict:
+    """The numpy float64 oracle of ``rpn_head_loss`` on top of ``reference_encode_assigned``: ``dict(loss_cls [L], loss_bbox [L], n_pos, n_neg, avg, dcls, dreg)``
+    with ``dcls[l]`` / ``dreg[l]`` the analytic gradients in the maps' [B, C, H, W] shapes under the upstream gradients ``gout`` [2 L] (None: ones)"""
+    m = _int_np(mask)
+    B, N = m.shape
+    L = len(cls_scores)
+    targets, weights = reference_encode_assigned("midpoint", anchors, gts, gt_inds, means, stds, gt_counts, m == 1)
+    n_pos_b, n_neg_b = (m == 1).sum(1), ((m != 0) & (m != 1)).sum(1)
+    avg = float((np.maximum(n_pos_b, 1) + np.maximum(n_neg_b, 1)).sum())
+    g = np.ones(2 * L) if gout is None else _f64(gout).reshape(2 * L)
+    out = dict(loss_cls=np.zeros(L), loss_bbox=np.zeros(L), n_pos=int(n_pos_b.sum()), n_neg=int(n_neg_b.sum()), avg=avg, dcls=[], dreg=[])
+    off = 0
+    for l in range(L):
+        c, r = _f64(cls_scores[l]), _f64(bbox_preds[l])
+        _, A, H, W = c.shape
+        n = H * W * A
+        z = c.transpose(0, 2, 3, 1).reshape(B, n)
+        d = r.transpose(0, 2, 3, 1).reshape(B, n, 6) - targets[:, off:off + n]
+        ml = m[:, off:off + n]
+        smp, t = ml != 0, (ml == 1).astype(np.float64)
+        terms = np.maximum(z, 0) - z * t + np.log1p(np.exp(-np.abs(z)))
+        sig = np.where(z >= 0, 1 / (1 + np.exp(-np.abs(z))), np.exp(-np.abs(z)) / (1 + np.exp(-np.abs(z))))
+        val, der = _smooth_l1_np(d, beta)
+        live = weights[:, off:off + n] > 0
+        out["loss_cls"][l] = loss_weight_cls * terms[smp].sum() / avg
+        out["loss_bbox"][l] = loss_weight_bbox * val[live].sum() / avg
+        dc = np.where(smp, g[l] * loss_weight_cls * (sig - t) / avg, 0.0)
+        dr = np.where(live[..., None], g[L + l] * loss_weight_bbox * der / avg, 0.0)
+        out["dcls"].append(dc.reshape(B, H, W, A).transpose(0, 3, 1, 2))
+        out["dreg"].append(dr.reshape(B, H, W, A * 6).transpose(0, 3, 1, 2))
+        off += n
+    if off != N:
+        raise ValueError(f"reference_rpn_head_loss: the maps hold {off} anchors per image, the mask {N}")
+    return out
+
+
+def reference_bbox_head_loss(cls_score, bbox_pred, rois, gts, s_gt_inds, s_labels, gt_counts=None, means=(0.0,) * 5, stds=RCNN_TARGET_STDS, num_classes: int = 15,
+                             beta: float = 1.0, loss_weight_cls: float = 1.0, loss_weight_bbox: float = 1.0, gout=None) -> dict:
+    """The numpy float64 oracle of ``bbox_head_loss``: ``dict(loss_cls, loss_bbox, acc, n_valid, n_live, dcls [R, K + 1], dbbox [R, 5 C])``; C from ``bbox_pred``"""
+    z, p, ro, g_ = _f64(cls_score), _f64(bbox_pred), _f64(rois).reshape(-1, 6), _f64(gts)
+    ind, lab = _int_np(s_gt_inds).reshape(-1), _int_np(s_labels).reshape(-1)
+    R, K, B, Gmax = z.shape[0], int(num_classes), g_.shape[0], g_.shape[1]
+    C_ = p.shape[1] // 5
+    cnt = np.full(B, Gmax) if gt_counts is None else np.clip(_int_np(gt_counts), 0, Gmax)
+    go = np.ones(2) if gout is None else _f64(gout).reshape(2)
+    with np.errstate(invalid="ignore"):
+        inb = (ro[:, 0] >= 0) & (ro[:, 0] < B)
+    b = np.where(inb, ro[:, 0], 0).astype(np.int64)
+    valid = inb & (lab >= 0) & (lab <= K)
+    live = valid & (lab < K) & (ind >= 1) & (ind <= cnt[b])
+    n_valid, n_live = int(valid.sum()), int(live.sum())
+    dcls, dbbox = np.zeros_like(z), np.zeros_like(p)
+    out = dict(loss_cls=0.0, loss_bbox=0.0, acc=0.0, n_valid=n_valid, n_live=n_live, dcls=dcls, dbbox=dbbox)
+    if n_valid == 0:
+        return out
+    rows = np.nonzero(valid)[0]
+    zs = z[rows] - z[rows].max(1, keepdims=True)
+    lse = np.log(np.exp(zs).sum(1))
+    out["loss_cls"] = loss_weight_cls * (lse - zs[np.arange(len(rows)), lab[rows]]).sum() / max(n_valid, 1)
+    soft = np.exp(zs - lse[:, None])
+    soft[np.arange(len(rows)), lab[rows]] -= 1.0
+    dcls[rows] = go[0] * loss_weight_cls * soft / max(n_valid, 1)
+    out["acc"] = 100.0 * float((z[rows].argmax(1) == lab[rows]).sum()) / n_valid
+    pos = np.nonzero(live)[0]
+    if pos.size:
+        target = reference_obb2obb_encode(ro[pos, 1:], g_[b[pos], ind[pos] - 1], means, stds)
+        sets = np.zeros(len(pos), dtype=np.int64) if C_ == 1 else lab[pos]
+        cols = sets[:, None] * 5 + np.arange(5)[None]
+        val, der = _smooth_l1_np(p[pos[:, None], cols] - target, beta)
+        out["loss_bbox"] = loss_weight_bbox * val.sum() / n_valid
+        dbbox[pos[:, None], cols] = go[1] * loss_weight_bbox * der / n_valid
+    return out

@@ -2064,6 +2064,213 @@ def sample_gather(inds: Tensor, boxes: Tensor, gts: Tensor, gt_inds: Tensor, gt_
 
 
 # -------------------------------------------------------------------------------------------
+# Head losses of the Oriented R-CNN configs (csrc/headloss.hip; lemevit_amd/detection.py has rpn_head_loss / bbox_head_loss)
+# -------------------------------------------------------------------------------------------
+def _loss_scalars(fn: str, beta, w_cls, w_bbox) -> Tuple[float, float, float]:
+    beta, w_cls, w_bbox = float(beta), float(w_cls), float(w_bbox)
+    if not (beta > 0.0) or math.isinf(beta):
+        raise ValueError(f"{fn}: beta = {beta!r} is not a positive finite number")
+    if not (w_cls >= 0.0) or not (w_bbox >= 0.0):
+        raise ValueError(f"{fn}: loss weights {w_cls!r} / {w_bbox!r}: a negative or NaN loss weight")
+    return beta, w_cls, w_bbox
+
+
+def _loss_gts(fn: str, gts: Tensor, gt_counts: Optional[Tensor], dev) -> Tuple[int, int, int]:
+    """(B, Gmax, row stride) of contiguous-per-image ground truths float32 [B, Gmax, 5]"""
+    if gts.dim() != 3 or gts.shape[2] != 5 or gts.dtype != torch.float32 or gts.device != dev:
+        raise ValueError(f"{fn}: gts: float32 [B, Gmax, 5] (cx, cy, w, h, theta) on the predictions' device expected, got {gts.dtype} {tuple(gts.shape)}")
+    B, Gmax = int(gts.shape[0]), int(gts.shape[1])
+    if not 1 <= B <= _lib.ASSIGN_MAX_BATCH or Gmax > _lib.OBB_MAX_BOXES:
+        raise ValueError(f"{fn}: B = {B} images outside 1 .. {_lib.ASSIGN_MAX_BATCH} or Gmax = {Gmax} above {_lib.OBB_MAX_BOXES}")
+    if Gmax > 0 and not gts.is_contiguous():
+        raise ValueError(f"{fn}: gts must be contiguous")
+    if gt_counts is not None and (gt_counts.dtype != torch.int32 or tuple(gt_counts.shape) != (B,) or gt_counts.device != dev or not gt_counts.is_contiguous()):
+        raise TypeError(f"{fn}: gt_counts must be a contiguous int32 vector [{B}] on the predictions' device")
+    return B, Gmax, 5
+
+
+def _loss_buf(fn: str, name: str, t: Optional[Tensor], n: int, dev) -> Tensor:
+    if t is None:
+        return torch.empty((n,), device=dev, dtype=torch.float32)
+    if t.dtype != torch.float32 or tuple(t.shape) != (n,) or t.device != dev or not t.is_contiguous():
+        raise TypeError(f"{fn}: {name} must be a contiguous float32 vector [{n}] on the predictions' device")
+    return t
+
+
+def _loss_workspace(fn: str, workspace: Optional[Tensor], need: int, dev, sizer: str) -> Tensor:
+    if workspace is None:
+        return torch.empty((max(need, 16),), device=dev, dtype=torch.uint8)
+    if workspace.dtype != torch.uint8 or workspace.device != dev or not workspace.is_contiguous() or workspace.numel() < need or workspace.data_ptr() % 16:
+        raise ValueError(f"{fn}: the workspace must hold {need} bytes (uint8, 16-byte aligned) on the predictions' device (ops.{sizer})")
+    return workspace
+
+
+def _loss_rows(fn: str, what: str, t: Tensor, k: int) -> Tuple[int, int]:
+    """(data pointer, row stride in elements) of predictions [R, k] read or written in place: unit column stride, any row stride >= k"""
+    n = int(t.shape[0])
+    if (n > 0 and t.stride(1) != 1) or (n > 1 and t.stride(0) < k):
+        raise ValueError(f"{fn}: {what}: strides {tuple(t.stride())}: a unit column stride and a row stride >= {k} are needed (call .contiguous())")
+    return (t.data_ptr() if n else None), (int(t.stride(0)) if n > 1 else k)
+
+
+def rpn_loss_workspace_bytes(B: int, N: int) -> int:
+    """lmv_rpn_loss_workspace_bytes: 48 B ceil(N / 1024) bytes, the per-wave partial rows of ``rpn_loss_fwd``"""
+    if not 1 <= int(B) <= _lib.ASSIGN_MAX_BATCH or not 1 <= int(N) <= _lib.OBB_MAX_BOXES:
+        raise ValueError(f"rpn_loss_workspace_bytes: B = {B} outside 1 .. {_lib.ASSIGN_MAX_BATCH} or N = {N} outside 1 .. {_lib.OBB_MAX_BOXES}")
+    return int(lib.lmv_rpn_loss_workspace_bytes(int(B), int(N)))
+
+
+def rcnn_loss_workspace_bytes(R: int) -> int:
+    """lmv_rcnn_loss_workspace_bytes: 32 ceil(R / 64) bytes, the per-wave partial rows of ``rcnn_loss_fwd``"""
+    if not 0 <= int(R) <= _lib.OBB_MAX_BOXES:
+        raise ValueError(f"rcnn_loss_workspace_bytes: R = {R} outside 0 .. {_lib.OBB_MAX_BOXES}")
+    return int(lib.lmv_rcnn_loss_workspace_bytes(int(R)))
+
+
+def _rpn_loss_call(fn: str, cls_scores: Sequence[Tensor], bbox_preds: Sequence[Tensor], anchors: Tensor, gts: Tensor, gt_inds: Tensor, mask: Tensor,
+                   gt_counts: Optional[Tensor], means, stds, beta, w_cls, w_bbox, dcls: Optional[Sequence[Tensor]] = None, dreg: Optional[Sequence[Tensor]] = None):
+    """the checked arguments shared by lmv_rpn_loss_fwd and lmv_rpn_loss_bwd, up to and including w_bbox; and (L, B, N, device)"""
+    code, k, D, names, cm, cs = coder_norm(fn, "midpoint", means, stds)
+    beta, w_cls, w_bbox = _loss_scalars(fn, beta, w_cls, w_bbox)
+    L = len(cls_scores)
+    if not 1 <= L <= _lib.RPN_LOSS_MAX_LEVELS or len(bbox_preds) != L:
+        raise ValueError(f"{fn}: {L} class maps and {len(bbox_preds)} regression maps: 1 .. {_lib.RPN_LOSS_MAX_LEVELS} levels, one of each per level")
+    c0 = cls_scores[0]
+    if c0.dim() != 4:
+        raise ValueError(f"{fn}: cls_scores[0]: [B, A, H, W] expected, got {tuple(c0.shape)}")
+    B, A, dev, dt = int(c0.shape[0]), int(c0.shape[1]), c0.device, c0.dtype
+    code_dt = dtype_code(c0)
+    if not 1 <= A <= _lib.CODER_MAX_SETS:
+        raise ValueError(f"{fn}: A = {A} anchors per position outside 1 .. {_lib.CODER_MAX_SETS}")
+    levels = (_lib.RpnLossLevel * L)()
+    N = 0
+    for l in range(L):
+        c, r = cls_scores[l], bbox_preds[l]
+        if c.dim() != 4 or r.dim() != 4 or c.shape[0] != B or c.shape[1] != A or tuple(r.shape) != (B, A * D, c.shape[2], c.shape[3]) or c.shape[2] < 1 or c.shape[3] < 1:
+            raise ValueError(f"{fn}: level {l}: a class map [{B}, {A}, H, W] and a regression map [{B}, {A * D}, H, W] expected, got {tuple(c.shape)} and {tuple(r.shape)}")
+        maps = [("cls", c), ("reg", r)] + ([("dcls", dcls[l]), ("dreg", dreg[l])] if dcls is not None else [])
+        for name, t in maps:
+            if t.dtype != dt or t.device != dev or not t.is_cuda:
+                raise TypeError(f"{fn}: level {l}: every map must have the dtype and the (GPU) device of cls_scores[0]; there is no CPU fallback")
+            if name[0] == "d" and (tuple(t.shape) != tuple((c if name == "dcls" else r).shape) or not strides_injective(t.shape, t.stride())):
+                raise ValueError(f"{fn}: level {l}: the gradient map {name} must have its input's shape and strides under which no two elements share an address")
+            setattr(levels[l], name, t.data_ptr())
+            setattr(levels[l], name + "_stride", (C.c_int64 * 4)(*[max(int(s), 1) if t.shape[i] == 1 else int(s) for i, s in enumerate(t.stride())]))
+        levels[l].H, levels[l].W = int(c.shape[2]), int(c.shape[3])
+        N += levels[l].H * levels[l].W * A
+    if N > _lib.OBB_MAX_BOXES:
+        raise ValueError(f"{fn}: N = {N} anchors per image, at most {_lib.OBB_MAX_BOXES}")
+    Bg, Gmax, gs = _loss_gts(fn, gts, gt_counts, dev)
+    if Bg != B:
+        raise ValueError(f"{fn}: gts hold {Bg} images, the maps {B}")
+    if anchors.dim() not in (2, 3) or anchors.shape[-1] != 4 or anchors.shape[-2] != N or anchors.dtype != torch.float32 or anchors.device != dev or \
+            not anchors.is_contiguous() or (anchors.dim() == 3 and anchors.shape[0] != B):
+        raise ValueError(f"{fn}: anchors: contiguous float32 [{N}, 4] or [{B}, {N}, 4] on the maps' device expected, got {anchors.dtype} {tuple(anchors.shape)}")
+    if mask.dtype == torch.bool:
+        mask = mask.view(torch.uint8)
+    if mask.dtype != torch.uint8 or tuple(mask.shape) != (B, N) or mask.device != dev or not mask.is_contiguous():
+        raise TypeError(f"{fn}: mask must be a contiguous uint8 tensor [{B}, {N}] on the maps' device (a sampler's mask)")
+    if gt_inds.dtype != torch.int64 or tuple(gt_inds.shape) != (B, N) or gt_inds.device != dev or not gt_inds.is_contiguous():
+        raise TypeError(f"{fn}: gt_inds must be a contiguous int64 tensor [{B}, {N}] on the maps' device")
+    args = (levels, L, A, code_dt, B, mask.data_ptr(), anchors.data_ptr(), 4, N * 4 if anchors.dim() == 3 else 0, gts.data_ptr() if Gmax > 0 else None, gs, Gmax,
+            _ptr(gt_counts), gt_inds.data_ptr(), code, cm, cs, beta, w_cls, w_bbox)
+    return args, L, B, N, dev
+
+
+def rpn_loss_fwd(cls_scores: Sequence[Tensor], bbox_preds: Sequence[Tensor], anchors: Tensor, gts: Tensor, gt_inds: Tensor, mask: Tensor,
+                 gt_counts: Optional[Tensor], means, stds, beta: float = 1.0 / 9.0, w_cls: float = 1.0, w_bbox: float = 1.0, stats: Optional[Tensor] = None,
+                 workspace: Optional[Tensor] = None) -> Tensor:
+    """lmv_rpn_loss_fwd (two launches, no host round trip): the RPN head's sigmoid cross-entropy and smooth-L1 losses of B images over the sampled anchors of L
+    levels.  ``cls_scores[l]`` [B, A, H_l, W_l] and ``bbox_preds[l]`` [B, 6 A, H_l, W_l], float32 or bfloat16, are read in place with any strides; ``mask`` uint8
+    [B, N] is the sampler's mask, ``gt_inds`` int64 [B, N] the assigner's indices, ``anchors`` float32 [N, 4] or [B, N, 4], ``gts`` float32 [B, Gmax, 5],
+    ``gt_counts`` int32 [B] or None.  Returns ``stats`` float32 [2 L + 3]: loss_cls[L], loss_bbox[L], n_pos, n_neg, 1 / avg.  ``stats`` and the workspace
+    (``rpn_loss_workspace_bytes(B, N)``) may be supplied so that a captured call allocates nothing.  include/lemevit_hip.h has the rules."""
+    fn = "rpn_loss_fwd"
+    args, L, B, N, dev = _rpn_loss_call(fn, cls_scores, bbox_preds, anchors, gts, gt_inds, mask, gt_counts, means, stds, beta, w_cls, w_bbox)
+    stats = _loss_buf(fn, "stats", stats, 2 * L + 3, dev)
+    need = rpn_loss_workspace_bytes(B, N)
+    workspace = _loss_workspace(fn, workspace, need, dev, "rpn_loss_workspace_bytes")
+    check(lib.lmv_rpn_loss_fwd(*args, workspace.data_ptr(), workspace.numel(), stats.data_ptr(), _stream()), "lmv_rpn_loss_fwd")
+    return stats
+
+
+def rpn_loss_bwd(cls_scores: Sequence[Tensor], bbox_preds: Sequence[Tensor], anchors: Tensor, gts: Tensor, gt_inds: Tensor, mask: Tensor,
+                 gt_counts: Optional[Tensor], means, stds, beta: float, w_cls: float, w_bbox: float, stats: Tensor, gout: Optional[Tensor],
+                 dcls: Sequence[Tensor], dreg: Sequence[Tensor]) -> None:
+    """lmv_rpn_loss_bwd (one launch): writes every element of the gradient maps ``dcls[l]`` / ``dreg[l]`` (the inputs' shapes and dtype, any injective strides)
+    once -- the gradient at sampled anchors / live rows, +0.0 elsewhere.  ``stats``: what ``rpn_loss_fwd`` returned; ``gout``: float32 [2 L] on the device, the
+    upstream gradient of every returned loss, or None (ones)."""
+    fn = "rpn_loss_bwd"
+    if len(dcls) != len(cls_scores) or len(dreg) != len(cls_scores):
+        raise ValueError(f"{fn}: one class and one regression gradient map per level are needed")
+    args, L, B, N, dev = _rpn_loss_call(fn, cls_scores, bbox_preds, anchors, gts, gt_inds, mask, gt_counts, means, stds, beta, w_cls, w_bbox, dcls, dreg)
+    stats = _loss_buf(fn, "stats", stats, 2 * L + 3, dev)
+    if gout is not None:
+        gout = _loss_buf(fn, "gout", gout, 2 * L, dev)
+    check(lib.lmv_rpn_loss_bwd(*args, stats.data_ptr(), _ptr(gout), _stream()), "lmv_rpn_loss_bwd")
+
+
+def _rcnn_loss_call(fn: str, cls_score: Tensor, bbox_pred: Tensor, rois: Tensor, gts: Tensor, s_gt_inds: Tensor, s_labels: Tensor, gt_counts: Optional[Tensor],
+                    means, stds, beta, w_cls, w_bbox):
+    code, k, D, names, cm, cs = coder_norm(fn, "obb2obb", means, stds)
+    beta, w_cls, w_bbox = _loss_scalars(fn, beta, w_cls, w_bbox)
+    if cls_score.dim() != 2 or cls_score.shape[1] < 2 or cls_score.shape[1] > _lib.CODER_MAX_SETS:
+        raise ValueError(f"{fn}: cls_score: [R, K + 1] with 1 <= K <= {_lib.CODER_MAX_SETS - 1} expected, got {tuple(cls_score.shape)}")
+    R, K, dev = int(cls_score.shape[0]), int(cls_score.shape[1]) - 1, cls_score.device
+    if bbox_pred.dim() != 2 or bbox_pred.shape[0] != R or bbox_pred.shape[1] not in (D, D * K) or bbox_pred.dtype != cls_score.dtype or bbox_pred.device != dev:
+        raise ValueError(f"{fn}: bbox_pred: [{R}, {D}] (class-agnostic) or [{R}, {D * K}] in the dtype and on the device of cls_score expected, got "
+                         f"{bbox_pred.dtype} {tuple(bbox_pred.shape)}")
+    C_ = int(bbox_pred.shape[1]) // D
+    code_dt = dtype_code(cls_score)
+    if R > _lib.OBB_MAX_BOXES:
+        raise ValueError(f"{fn}: R = {R} rows, at most {_lib.OBB_MAX_BOXES}")
+    if not cls_score.is_cuda:
+        raise RuntimeError("lemevit_amd: tensors must be on the GPU (no CPU fallback exists)")
+    pc, sc = _loss_rows(fn, "cls_score", cls_score, K + 1)
+    pb, sb = _loss_rows(fn, "bbox_pred", bbox_pred, D * C_)
+    B, Gmax, gs = _loss_gts(fn, gts, gt_counts, dev)
+    if rois.dim() != 2 or tuple(rois.shape) != (R, 6) or rois.dtype != torch.float32 or rois.device != dev or not rois.is_contiguous():
+        raise ValueError(f"{fn}: rois: contiguous float32 [{R}, 6] (b, cx, cy, w, h, theta) on the predictions' device expected, got {rois.dtype} {tuple(rois.shape)}")
+    for name, t in (("s_gt_inds", s_gt_inds), ("s_labels", s_labels)):
+        if t.dtype != torch.int64 or tuple(t.shape) != (R,) or t.device != dev or not t.is_contiguous():
+            raise TypeError(f"{fn}: {name} must be a contiguous int64 vector [{R}] on the predictions' device")
+    args = (pc, sc, pb, sb, code_dt, R, K, C_, rois.data_ptr() if R else None, 6, s_gt_inds.data_ptr() if R else None, s_labels.data_ptr() if R else None,
+            gts.data_ptr() if Gmax > 0 else None, gs, B, Gmax, _ptr(gt_counts), code, cm, cs, beta, w_cls, w_bbox)
+    return args, R, K, C_, dev
+
+
+def rcnn_loss_fwd(cls_score: Tensor, bbox_pred: Tensor, rois: Tensor, gts: Tensor, s_gt_inds: Tensor, s_labels: Tensor, gt_counts: Optional[Tensor], means, stds,
+                  beta: float = 1.0, w_cls: float = 1.0, w_bbox: float = 1.0, stats: Optional[Tensor] = None, workspace: Optional[Tensor] = None) -> Tensor:
+    """lmv_rcnn_loss_fwd (two launches, no host round trip): the R-CNN head's softmax cross-entropy, accuracy and smooth-L1 loss over R sampled RoIs.
+    ``cls_score`` [R, K + 1] and ``bbox_pred`` [R, 5] or [R, 5 K], float32 or bfloat16, read in place through their row stride; ``rois`` float32 [R, 6],
+    ``s_gt_inds`` / ``s_labels`` int64 [R] as ``sample_gather`` writes them (flattened); ``gts`` float32 [B, Gmax, 5].  Returns ``stats`` float32 [7]: loss_cls,
+    loss_bbox, acc, n_valid, n_live, 1 / max(n_valid, 1), 1 / n_valid.  ``stats`` and the workspace (``rcnn_loss_workspace_bytes(R)``) may be supplied."""
+    fn = "rcnn_loss_fwd"
+    args, R, K, C_, dev = _rcnn_loss_call(fn, cls_score, bbox_pred, rois, gts, s_gt_inds, s_labels, gt_counts, means, stds, beta, w_cls, w_bbox)
+    stats = _loss_buf(fn, "stats", stats, _lib.RCNN_LOSS_STATS, dev)
+    workspace = _loss_workspace(fn, workspace, rcnn_loss_workspace_bytes(R), dev, "rcnn_loss_workspace_bytes")
+    check(lib.lmv_rcnn_loss_fwd(*args, workspace.data_ptr(), workspace.numel(), stats.data_ptr(), _stream()), "lmv_rcnn_loss_fwd")
+    return stats
+
+
+def rcnn_loss_bwd(cls_score: Tensor, bbox_pred: Tensor, rois: Tensor, gts: Tensor, s_gt_inds: Tensor, s_labels: Tensor, gt_counts: Optional[Tensor], means, stds,
+                  beta: float, w_cls: float, w_bbox: float, stats: Tensor, gout: Optional[Tensor], dcls: Tensor, dbbox: Tensor) -> None:
+    """lmv_rcnn_loss_bwd (one launch): writes all of ``dcls`` [R, K + 1] and ``dbbox`` [R, 5 C] (the inputs' dtype, unit column stride) once.  ``stats``: what
+    ``rcnn_loss_fwd`` returned; ``gout``: float32 [2] on the device (loss_cls, loss_bbox) or None (ones)."""
+    fn = "rcnn_loss_bwd"
+    args, R, K, C_, dev = _rcnn_loss_call(fn, cls_score, bbox_pred, rois, gts, s_gt_inds, s_labels, gt_counts, means, stds, beta, w_cls, w_bbox)
+    stats = _loss_buf(fn, "stats", stats, _lib.RCNN_LOSS_STATS, dev)
+    if gout is not None:
+        gout = _loss_buf(fn, "gout", gout, 2, dev)
+    for name, t, like in (("dcls", dcls, cls_score), ("dbbox", dbbox, bbox_pred)):
+        if t.dtype != like.dtype or tuple(t.shape) != tuple(like.shape) or t.device != dev:
+            raise TypeError(f"{fn}: {name} must have the shape, dtype and device of its input")
+    pdc, sdc = _loss_rows(fn, "dcls", dcls, K + 1)
+    pdb, sdb = _loss_rows(fn, "dbbox", dbbox, 5 * C_)
+    check(lib.lmv_rcnn_loss_bwd(*args, stats.data_ptr(), _ptr(gout), pdc, sdc, pdb, sdb, _stream()), "lmv_rcnn_loss_bwd")
+
+
+# -------------------------------------------------------------------------------------------
 # A run of "S" blocks as one persistent launch (csrc/sstage.hip; inference, bf16)
 # -------------------------------------------------------------------------------------------
 def sstage_supported(C_: int, heads: int, hidden: int, H: int, W: int, M: int, dtype: torch.dtype) -> bool:
