@@ -703,7 +703,7 @@ int lmv_dense_slide_fwd(const void* logits, int dtype, int64_t window_stride, in
                         double* meter, void* stream);
 
 /* ------------------------------------------------------------------------------------------
- * Rotated RoIAlign over a feature pyramid (csrc/rroi.hip): the RoI layer of the reference's three Oriented R-CNN configs
+ * Rotated RoIAlign over a feature pyramid (csrc/rroi.hip; csrc/roi_frame.h has what it shares with csrc/roi.hip): the RoI layer of the reference's three Oriented R-CNN configs
  * (object_detection/configs/obb/oriented_rcnn/: roi_layer=dict(type='RoIAlignRotated', out_size=7, sample_num=2) inside an OBB single-level extractor over
  * featmap_strides=[4, 8, 16, 32] with extend_factor=(1.4, 1.2)), which the reference has as a CUDA extension only (mmdet/ops/roi_align_rotated/src; the CPU source
  * there is the specification of the arithmetic).  An addition to ABI 14: callers detect it by symbol.  One plan launch, one forward launch and one backward launch
@@ -778,7 +778,7 @@ int lmv_rroi_fwd(const void* plan, int R, const lmv_rroi_level* levels, int L, i
 int lmv_rroi_bwd(const void* plan, int R, const void* dy, const lmv_rroi_level* dx, int L, int B, int C, int oh, int ow, int sample_num, int dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------------
- * Rotated IoU and rotated NMS (csrc/obb.hip): the two remaining custom operators of the reference's Oriented R-CNN configs -- iou_calculator=dict(type='OBBOverlaps')
+ * Rotated IoU and rotated NMS (csrc/obb.hip; the NMS frame is csrc/nms_frame.h): the two remaining custom operators of the reference's Oriented R-CNN configs -- iou_calculator=dict(type='OBBOverlaps')
  * (mmdet/ops/box_iou_rotated: obb_overlaps) in both assigners, and nms_pre / nms_thr=0.8 of the oriented RPN and nms=dict(type='obb_nms', iou_thr=0.1) of the test
  * config (mmdet/ops/nms_rotated: obb_nms, arb_batched_nms).  An addition to ABI 14: callers detect it by symbol.  No host round trip, no atomics: two calls agree bit
  * for bit and every entry point can be captured.
@@ -828,7 +828,7 @@ int lmv_obb_nms(const float* boxes, int stride, const float* scores, const int64
                 int phases, void* workspace, size_t workspace_bytes, int64_t* keep, int64_t* count, void* stream);
 
 /* ------------------------------------------------------------------------------------------
- * Horizontal RoIAlign over a feature pyramid, adaptive sampling grid included (csrc/roi.hip): the RoI layers of the reference's Mask R-CNN config
+ * Horizontal RoIAlign over a feature pyramid, adaptive sampling grid included (csrc/roi.hip; csrc/roi_frame.h has what it shares with csrc/rroi.hip): the RoI layers of the reference's Mask R-CNN config
  * (object_detection/configs/mask_rcnn/: RoIAlign with out_size 7 in the box head and 14 in the mask head, sample_num=0, aligned=True, over featmap_strides
  * [4, 8, 16, 32]), which the reference has as a CUDA extension (mmdet/ops/roi_align/src; cpu/roi_align_v2.cpp there is the specification of the arithmetic).  An
  * addition to ABI 14: callers detect it by symbol.  One plan launch, one forward launch and one backward launch serve ALL levels; no floating-point atomics, no
@@ -897,7 +897,7 @@ int lmv_roi_fwd(const void* plan, int R, const lmv_roi_level* levels, int L, int
 int lmv_roi_bwd(const void* plan, int R, const void* dy, const lmv_roi_level* dx, int L, int B, int C, int oh, int ow, int dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------------
- * Horizontal NMS (csrc/nms.hip): mmdet/ops/nms (nms, batched_nms) of the reference's Mask R-CNN config -- the RPN proposals (nms_thr 0.7) and the test-time
+ * Horizontal NMS (csrc/nms.hip; csrc/nms_frame.h has what it shares with csrc/obb.hip): mmdet/ops/nms (nms, batched_nms) of the reference's Mask R-CNN config -- the RPN proposals (nms_thr 0.7) and the test-time
  * multiclass NMS (iou_thr 0.5, score_thr 0.05, max_per_img 100).  An addition to ABI 14: callers detect it by symbol.  The interface and the two launches are
  * those of lmv_obb_nms above (order: the caller's STABLE descending sort; groups; candidates; keep padded with -1; count; phases; nothing synchronised; capturable),
  * with boxes fp32 rows (x1, y1, x2, y2) read in place through a ROW STRIDE >= 4 floats and the pair rule of cpu/nms_cpu.cpp in fp32, operation by operation:

@@ -11,11 +11,10 @@
 //             duplicate, its theta + pi twin, and its theta + pi / 2 twin with w and h swapped give I = w h to rounding.  Which box plays A is decided by a total order
 //             on the records, so pair(p, q) == pair(q, p) bit for bit.
 //   overlaps  a workgroup owns a 16 x 64 tile of the [N, M] matrix and stages its 16 + 64 records in LDS; a lane owns a column, so the stores run along M.
-//   nms mask  64 x 64 tiles of the rank-ordered boxes, upper triangle; a wave owns 16 rows of the tile, lane j evaluates (row, column j) and the ballot is the row's
-//             word.  Different groups and pairs whose bounding circles are apart never reach the pair function.
-//   nms reduce  nms_reduce.h (shared with the horizontal NMS of nms.hip): one workgroup, the `removed` bit vector in registers, keep[] and count written once.
+//   nms       nms_frame.h (shared with the horizontal NMS of nms.hip) has the mask launch, the reduce launch and the host side; this file has the record at a rank and
+//             the candidate rule.  Different groups and pairs whose bounding circles are apart never reach the pair function.
 #include "common.h"
-#include "nms_reduce.h"
+#include "nms_frame.h"
 #include <math.h>
 
 // No implicit fused multiply-adds in this file (the explicit fmaf calls stay): the pair function then rounds the same way in every kernel it is inlined into, so the
@@ -62,11 +61,6 @@ __global__ __launch_bounds__(256) void obb_overlaps_aligned_kernel(const float* 
 }
 
 // ---- NMS ---------------------------------------------------------------------------------------------------------------------------------------------------------
-struct NmsArgs {
-  const float* boxes; int stride; const float* scores; const int64_t* order; const int32_t* groups;
-  int N, nb; float iou_thr, score_thr; int cap; unsigned long long* mask; int64_t* keep; int64_t* count;
-};
-
 // the record of the box at a rank; an `order` entry outside [0, N) reads nothing and is no candidate
 __device__ __forceinline__ ObbRec nms_load(const NmsArgs& a, int rank) {
   if (rank >= a.N) return obb_none();
@@ -93,32 +87,17 @@ __device__ __forceinline__ bool nms_candidate(const NmsArgs& a, int rank) {
 }
 
 __global__ __launch_bounds__(256) void obb_nms_mask_kernel(NmsArgs a) {
-  const int rb = blockIdx.y, cb = blockIdx.x;
-  if (cb < rb) return;          // below the diagonal: never read
-  __shared__ ObbRec rows[64], cols[64];
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  if (tid < 64) rows[tid] = nms_load(a, rb * 64 + tid);
-  else if (tid < 128) cols[tid - 64] = nms_load(a, cb * 64 + tid - 64);
-  __syncthreads();
-  const ObbRec q = cols[lane];
-  const int qrank = cb * 64 + lane;
-#pragma unroll 1
-  for (int i = 0; i < 16; ++i) {
-    const int r = wv * 16 + i, rrank = rb * 64 + r;
-    if (rrank >= a.N) break;          // (wave-uniform)
-    const ObbRec p = rows[r];
-    bool sup = false;
-    if ((p.flags & q.flags & OB_CAND) && qrank > rrank && p.group == q.group) sup = obb_pair(p, q, LMV_OBB_IOU) > a.iou_thr;
-    const unsigned long long word = __ballot(sup);
-    if (lane == 0) a.mask[(int64_t)rrank * a.nb + cb] = word;
-  }
+  lmv_nms_mask<ObbRec, OB_CAND>(a, [](const NmsArgs& a, int rank) { return nms_load(a, rank); },
+                                [&](const ObbRec& p, const ObbRec& q) { return obb_pair(p, q, LMV_OBB_IOU) > a.iou_thr; });
 }
 
 struct ObbCandidate {
   __device__ __forceinline__ bool operator()(const NmsArgs& a, int rank) const { return nms_candidate(a, rank); }
 };
 
-__global__ __launch_bounds__(256) void obb_nms_reduce_kernel(NmsArgs a) { lmv_nms_reduce(a, ObbCandidate()); }          // nms_reduce.h: shared with nms.hip
+__global__ __launch_bounds__(256) void obb_nms_reduce_kernel(NmsArgs a) { lmv_nms_reduce(a, ObbCandidate()); }
+
+constexpr NmsOp OB_OP = {"obb_nms", 5, "cx, cy, w, h, theta", LMV_OBB_NMS_MAX, "lmv_obb_nms_workspace_bytes", obb_nms_mask_kernel, obb_nms_reduce_kernel};
 
 int obb_check_boxes(const char* fn, const char* what, const float* b, int stride, int n) {
   if (n < 0) LMV_FAIL(LMV_ERR_SHAPE, "%s: %d %s (a negative size)", fn, n, what);
@@ -151,40 +130,9 @@ extern "C" int lmv_obb_overlaps(const float* b1, int stride1, int N, const float
   return LMV_OK;
 }
 
-extern "C" size_t lmv_obb_nms_workspace_bytes(int N) {
-  if (N < 0 || N > LMV_OBB_NMS_MAX) return 0;
-  return (size_t)N * (size_t)((N + 63) / 64) * 8;
-}
+extern "C" size_t lmv_obb_nms_workspace_bytes(int N) { return lmv_nms_bytes(N, LMV_OBB_NMS_MAX); }
 
 extern "C" int lmv_obb_nms(const float* boxes, int stride, const float* scores, const int64_t* order, const int32_t* groups, int N, float iou_thr, float score_thr,
                            int max_num, int phases, void* workspace, size_t workspace_bytes, int64_t* keep, int64_t* count, void* stream) {
-  const char* fn = "obb_nms";
-  if (int rc = obb_check_boxes(fn, "boxes", boxes, stride, N)) return rc;
-  if (N > LMV_OBB_NMS_MAX) LMV_FAIL(LMV_ERR_SHAPE, "%s: N = %d boxes, at most %d", fn, N, LMV_OBB_NMS_MAX);
-  if (max_num < 0) LMV_FAIL(LMV_ERR_SHAPE, "%s: max_num = %d < 0 (0: no limit)", fn, max_num);
-  if (iou_thr != iou_thr || score_thr != score_thr) LMV_FAIL(LMV_ERR_SHAPE, "%s: a NaN threshold (iou_thr = %g, score_thr = %g)", fn, iou_thr, score_thr);
-  if (phases < 1 || phases > 3) LMV_FAIL(LMV_ERR_SHAPE, "%s: phases = %d outside 1 .. 3 (1: mask launch, 2: reduce launch, 3: both)", fn, phases);
-  if (N > 0 && (!scores || !order)) LMV_FAIL(LMV_ERR_SHAPE, "%s: null scores / order", fn);
-  if (!count) LMV_FAIL(LMV_ERR_SHAPE, "%s: null count", fn);
-  const int cap = max_num > 0 ? max_num : N;
-  if (cap > 0 && !keep) LMV_FAIL(LMV_ERR_SHAPE, "%s: null keep", fn);
-  if ((((uintptr_t)scores) & 3u) || (((uintptr_t)groups) & 3u) || (((uintptr_t)order) & 7u) || (((uintptr_t)keep) & 7u) || (((uintptr_t)count) & 7u) ||
-      (((uintptr_t)workspace) & 7u))
-    LMV_FAIL(LMV_ERR_SHAPE, "%s: misaligned buffer", fn);
-  const size_t need = lmv_obb_nms_workspace_bytes(N);
-  if (workspace_bytes < need || (need > 0 && !workspace)) LMV_FAIL(LMV_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed (lmv_obb_nms_workspace_bytes)", fn, workspace_bytes, need);
-  hipStream_t st = (hipStream_t)stream;
-  if (N == 0) {          // no launch: count = 0, keep = -1 throughout
-    if (hipMemsetAsync(count, 0, sizeof(int64_t), st) != hipSuccess) LMV_FAIL(LMV_ERR_LAUNCH, "%s: cannot clear count", fn);
-    if (cap > 0 && hipMemsetAsync(keep, 0xff, (size_t)cap * sizeof(int64_t), st) != hipSuccess) LMV_FAIL(LMV_ERR_LAUNCH, "%s: cannot fill keep", fn);
-    return LMV_OK;
-  }
-  NmsArgs a;
-  a.boxes = boxes; a.stride = stride; a.scores = scores; a.order = order; a.groups = groups;
-  a.N = N; a.nb = (N + 63) / 64; a.iou_thr = iou_thr; a.score_thr = score_thr; a.cap = cap;
-  a.mask = reinterpret_cast<unsigned long long*>(workspace); a.keep = keep; a.count = count;
-  if (phases & 1) hipLaunchKernelGGL(obb_nms_mask_kernel, dim3((unsigned)a.nb, (unsigned)a.nb), dim3(256), 0, st, a);
-  if (phases & 2) hipLaunchKernelGGL(obb_nms_reduce_kernel, dim3(1), dim3(256), 0, st, a);
-  LMV_CHECK_LAUNCH(fn);
-  return LMV_OK;
+  return lmv_nms_run(OB_OP, boxes, stride, scores, order, groups, N, iou_thr, score_thr, max_num, phases, workspace, workspace_bytes, keep, count, stream);
 }

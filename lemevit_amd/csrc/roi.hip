@@ -18,6 +18,7 @@
 //          row / column); a pixel then takes sum over those bins of A_y A_x dY.  Every dX element is stored exactly once; no memset, no floating-point atomic, a
 //          fixed order of additions.
 #include "common.h"
+#include "roi_frame.h"          // the frame shared with rroi.hip: records, level rule, forward / backward scaffolding, host checks (included BEFORE the pragma)
 #include <math.h>
 
 // No implicit fused multiply-adds (the explicit fmaf calls stay): the plan restates the reference's fp32 expressions operation by operation.
@@ -25,24 +26,13 @@
 
 namespace {
 
-constexpr int RO_TH = 8, RO_TW = 16;         // backward: tile of pixels (rows x columns); a wave owns RO_TH / 4 rows
-constexpr int RO_PIX = RO_TH * RO_TW, RO_ROWS = RO_TH / 4;
-constexpr int RO_CH = 64;                    // channels per workgroup (forward and backward)
-constexpr int RO_CHP = RO_CH + 1;            // LDS row pitch in floats
-
-struct RoHeader { int level, batch, valid, y0, y1, x0, x1, gh, gw, ny, nx, pad; };          // LMV_ROI_HEADER_BYTES; y0 > y1: no sample lands anywhere; ny / nx: weights in use
+struct RoHeader : RoiHead { int gh, gw, ny, nx, pad; };                                       // LMV_ROI_HEADER_BYTES; ny / nx: weights in use
 struct RoBin { int first, len, off, pad; };                                                   // LMV_ROI_BIN_BYTES: pixels first .. first + len - 1, weights at off .. off + len - 1 of the axis
 static_assert(sizeof(RoHeader) == LMV_ROI_HEADER_BYTES && sizeof(RoBin) == LMV_ROI_BIN_BYTES, "plan record layout");
 
-struct RoGeom {
-  int L, B, R, oh, ow;
-  int H[LMV_ROI_MAX_LEVELS], W[LMV_ROI_MAX_LEVELS];
+struct RoGeom : RoiGeom {
   int capY, capX;          // weights per axis a record holds: max H_l + 2 oh, max W_l + 2 ow
   int64_t stride;          // bytes per RoI record
-};
-struct RoMaps {
-  void* data[LMV_ROI_MAX_LEVELS];
-  int64_t sb[LMV_ROI_MAX_LEVELS], sc[LMV_ROI_MAX_LEVELS], sh[LMV_ROI_MAX_LEVELS], sw[LMV_ROI_MAX_LEVELS];
 };
 struct RoPlanArgs {
   RoGeom g;
@@ -51,8 +41,8 @@ struct RoPlanArgs {
   int sn; float finest;
   char* plan;
 };
-struct RoFwdArgs { RoGeom g; RoMaps m; const char* plan; void* out; int C; };
-struct RoBwdArgs { RoGeom g; RoMaps m; const char* plan; const void* dy; int C; int first[LMV_ROI_MAX_LEVELS + 1]; };
+struct RoFwdArgs { RoGeom g; RoiMaps m; const char* plan; void* out; int C; };
+struct RoBwdArgs { RoGeom g; RoiMaps m; const char* plan; const void* dy; int C; int first[LMV_ROI_MAX_LEVELS + 1]; };
 
 // one sample coordinate of an axis -> (low, high, weight of high); false: the sample is empty
 __device__ __forceinline__ bool ro_sample(float start, float bin, int p, int i, int g, int ext, int* lo, int* hi, float* l) {
@@ -79,15 +69,8 @@ __global__ __launch_bounds__(256) void roi_plan_kernel(RoPlanArgs a) {
   const int r = blockIdx.x, tid = threadIdx.x, oh = a.g.oh, ow = a.g.ow, nb = oh + ow;
   const float* roi = a.rois + (int64_t)r * 5;
   const float bf = roi[0], x1 = roi[1], y1 = roi[2], x2 = roi[3], y2 = roi[4];
-  int lvl;
-  if (a.levels) {
-    lvl = a.levels[r];
-  } else {
-    // upstream mmdet's map_roi_levels; accurate sqrtf / log2f (a level is a discontinuity)
-    const float v = floorf(log2f(sqrtf((x2 - x1) * (y2 - y1)) / a.finest + 1e-6f));
-    lvl = v >= (float)(a.g.L - 1) ? a.g.L - 1 : v > 0.f ? (int)v : 0;          // (NaN: level 0)
-  }
-  bool valid = bf > -1.f && bf < (float)a.g.B && lvl >= 0 && lvl < a.g.L && isfinite(x1) && isfinite(y1) && isfinite(x2) && isfinite(y2);
+  const int lvl = a.levels ? a.levels[r] : roi_level((x2 - x1) * (y2 - y1), a.finest, a.g.L);
+  bool valid = roi_valid(bf, lvl, a.g) && isfinite(x1) && isfinite(y1) && isfinite(x2) && isfinite(y2);
   const int lv = valid ? lvl : 0;
   const int H = a.g.H[lv], W = a.g.W[lv];
   const float scale = a.scale[lv];
@@ -162,7 +145,7 @@ __global__ __launch_bounds__(256) void roi_plan_kernel(RoPlanArgs a) {
 }
 
 __device__ __forceinline__ bool ro_header_ok(const RoHeader& hd, const RoGeom& g) {
-  return hd.valid == 1 && hd.level >= 0 && hd.level < g.L && hd.batch >= 0 && hd.batch < g.B && hd.ny >= 0 && hd.ny <= g.capY && hd.nx >= 0 && hd.nx <= g.capX;
+  return roi_head_ok(hd, g) && hd.ny >= 0 && hd.ny <= g.capY && hd.nx >= 0 && hd.nx <= g.capX;
 }
 __device__ __forceinline__ float ro_count(const RoHeader& hd) {
   const int n = hd.gh * hd.gw;
@@ -177,14 +160,11 @@ __global__ __launch_bounds__(256) void roi_fwd_kernel(RoFwdArgs a) {
   RoBin* tb = reinterpret_cast<RoBin*>(lds);          // [oh + ow]; the x entries with off already moved behind the y weights
   float* wts = lds + 4 * nb;                          // [capY + capX]
   float* tile = wts + a.g.capY + a.g.capX;            // channels-last only: [channel][bins | 1]
-  const int r = blockIdx.x, c0 = blockIdx.y * RO_CH, nch = min(RO_CH, a.C - c0), tid = threadIdx.x, n = nch * bins;
-  T* out = reinterpret_cast<T*>(a.out) + ((int64_t)r * a.C + c0) * bins;          // this workgroup's n contiguous output elements
-  const char* rec = a.plan + (int64_t)r * a.g.stride;
+  const RoiChunk<T> k = roi_fwd_chunk<T>(a.out, a.C, bins);
+  const int tid = threadIdx.x;
+  const char* rec = a.plan + (int64_t)k.r * a.g.stride;
   const RoHeader hd = *reinterpret_cast<const RoHeader*>(rec);
-  if (!ro_header_ok(hd, a.g) || hd.ny == 0 || hd.nx == 0) {          // (workgroup-uniform)
-    for (int i = tid; i < n; i += 256) DT<T>::st(out + i, 0.f);
-    return;
-  }
+  if (!ro_header_ok(hd, a.g) || hd.ny == 0 || hd.nx == 0) return roi_fwd_zero(k);          // (workgroup-uniform)
   const int l = hd.level, H = a.g.H[l], W = a.g.W[l];
   const RoBin* gtb = reinterpret_cast<const RoBin*>(rec + LMV_ROI_HEADER_BYTES);
   const float* gw = reinterpret_cast<const float*>(rec + LMV_ROI_HEADER_BYTES + (int64_t)nb * LMV_ROI_BIN_BYTES);
@@ -196,63 +176,53 @@ __global__ __launch_bounds__(256) void roi_fwd_kernel(RoFwdArgs a) {
   for (int i = tid; i < hd.ny; i += 256) wts[i] = gw[i];
   for (int i = tid; i < hd.nx; i += 256) wts[a.g.capY + i] = gw[a.g.capY + i];
   __syncthreads();
-  const int64_t sc = a.m.sc[l], sh = a.m.sh[l], sw = a.m.sw[l];
-  const T* x = reinterpret_cast<const T*>(a.m.data[l]) + (int64_t)hd.batch * a.m.sb[l] + (int64_t)c0 * sc;
-  const bool cl = sc == 1 && sw != 1;          // lanes along the channels
-  const int pitch = bins | 1;
-  const float count = ro_count(hd);
-  for (int i = tid; i < n; i += 256) {
-    const int c = cl ? i % nch : i / bins, bin = cl ? i / nch : i - c * bins;
+  const RoiMap<T> x = roi_map<T>(a.m, l, hd.batch, k.c0);
+  roi_fwd_store(k, x.cl, ro_count(hd), tile, [&](int c, int bin) {          // run_y x run_x pixels, rows outer
     const RoBin by = tb[bin / ow], bx = tb[oh + bin % ow];
-    const T* xc = x + (int64_t)c * sc + (int64_t)by.first * sh + (int64_t)bx.first * sw;
+    const T* xc = x.p + (int64_t)c * x.sc + (int64_t)by.first * x.sh + (int64_t)bx.first * x.sw;
     const float* wy = wts + by.off;
     const float* wx = wts + bx.off;
     float acc = 0.f;
     for (int ky = 0; ky < by.len; ++ky) {
-      const T* row = xc + (int64_t)ky * sh;
+      const T* row = xc + (int64_t)ky * x.sh;
       float s = 0.f;
-      for (int kx = 0; kx < bx.len; ++kx) s = fmaf(wx[kx], DT<T>::ld(row + (int64_t)kx * sw), s);
+      for (int kx = 0; kx < bx.len; ++kx) s = fmaf(wx[kx], DT<T>::ld(row + (int64_t)kx * x.sw), s);
       acc = fmaf(wy[ky], s, acc);
     }
-    acc /= count;
-    if (cl) tile[c * pitch + bin] = acc;
-    else DT<T>::st(out + i, acc);
-  }
-  if (cl) {
-    __syncthreads();
-    for (int i = tid; i < n; i += 256) { const int c = i / bins, bin = i - c * bins; DT<T>::st(out + i, tile[c * pitch + bin]); }
-  }
+    return acc;
+  });
 }
 
 // ---- backward --------------------------------------------------------------------------------------------------------------------------------------------------
+// The tile decode, header scan, dY staging and dX store are those of roi_frame.h's backward pieces, spelled out here: see the note there (registers, prologue order).
 template <typename T>
 __global__ __launch_bounds__(256) void roi_bwd_kernel(RoBwdArgs a) {
   extern __shared__ float lds[];
   const int oh = a.g.oh, ow = a.g.ow, nb = oh + ow, bins = oh * ow;
-  float* acc = lds;                                   // [RO_PIX][RO_CHP]
-  float* dys = acc + RO_PIX * RO_CHP;                 // [bins][RO_CHP]
-  float* wy = dys + bins * RO_CHP;                    // [RO_TH][oh]: A_y of the staged RoI on the tile's rows
-  float* wx = wy + RO_TH * oh;                        // [RO_TW][ow]
-  int* rng = reinterpret_cast<int*>(wx + RO_TW * ow); // [RO_TH + RO_TW][2]: the first and the last bin that reach a row / column
+  float* acc = lds;                                   // [ROI_PIX][ROI_CHP]
+  float* dys = acc + ROI_PIX * ROI_CHP;                 // [bins][ROI_CHP]
+  float* wy = dys + bins * ROI_CHP;                    // [ROI_TH][oh]: A_y of the staged RoI on the tile's rows
+  float* wx = wy + ROI_TH * oh;                        // [ROI_TW][ow]
+  int* rng = reinterpret_cast<int*>(wx + ROI_TW * ow); // [ROI_TH + ROI_TW][2]: the first and the last bin that reach a row / column
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   int blk = blockIdx.x, l = 0;
   while (l + 1 < a.g.L && blk >= a.first[l + 1]) ++l;
   blk -= a.first[l];
-  const int H = a.g.H[l], W = a.g.W[l], tnx = (W + RO_TW - 1) / RO_TW, tny = (H + RO_TH - 1) / RO_TH, nchunk = (a.C + RO_CH - 1) / RO_CH;
+  const int H = a.g.H[l], W = a.g.W[l], tnx = (W + ROI_TW - 1) / ROI_TW, tny = (H + ROI_TH - 1) / ROI_TH, nchunk = (a.C + ROI_CH - 1) / ROI_CH;
   const int chunk = blk % nchunk; blk /= nchunk;
-  const int tx0 = (blk % tnx) * RO_TW; blk /= tnx;
-  const int ty0 = (blk % tny) * RO_TH, b = blk / tny;
-  const int c0 = chunk * RO_CH, nch = min(RO_CH, a.C - c0), R = a.g.R;
+  const int tx0 = (blk % tnx) * ROI_TW; blk /= tnx;
+  const int ty0 = (blk % tny) * ROI_TH, b = blk / tny;
+  const int c0 = chunk * ROI_CH, nch = min(ROI_CH, a.C - c0), R = a.g.R;
   const T* dy = reinterpret_cast<const T*>(a.dy);
 
-  for (int i = tid; i < RO_PIX * RO_CHP; i += 256) acc[i] = 0.f;
+  for (int i = tid; i < ROI_PIX * ROI_CHP; i += 256) acc[i] = 0.f;
 
   for (int r0 = 0; r0 < R; r0 += 64) {
     const int rl = r0 + lane;
     bool hit = false;
     if (rl < R) {
       const RoHeader hd = *reinterpret_cast<const RoHeader*>(a.plan + (int64_t)rl * a.g.stride);
-      hit = ro_header_ok(hd, a.g) && hd.level == l && hd.batch == b && hd.y1 >= ty0 && hd.y0 < ty0 + RO_TH && hd.x1 >= tx0 && hd.x0 < tx0 + RO_TW;
+      hit = ro_header_ok(hd, a.g) && hd.level == l && hd.batch == b && hd.y1 >= ty0 && hd.y0 < ty0 + ROI_TH && hd.x1 >= tx0 && hd.x0 < tx0 + ROI_TW;
     }
     unsigned long long mask = __ballot(hit);          // the same word in all four waves: the loop below is workgroup-uniform
     while (mask) {
@@ -266,34 +236,34 @@ __global__ __launch_bounds__(256) void roi_bwd_kernel(RoBwdArgs a) {
       const float count = ro_count(hd);
       __syncthreads();          // the walk of the previous hit (and the zero fill) is over
       const T* dr = dy + ((int64_t)r * a.C + c0) * bins;
-      for (int i = tid; i < nch * bins; i += 256) { const int c = i / bins, bin = i - c * bins; dys[bin * RO_CHP + c] = DT<T>::ld(dr + i) / count; }
-      if (tid < 2 * (RO_TH + RO_TW)) rng[tid] = (tid & 1) ? -1 : 0x7fffffff;
+      for (int i = tid; i < nch * bins; i += 256) { const int c = i / bins, bin = i - c * bins; dys[bin * ROI_CHP + c] = DT<T>::ld(dr + i) / count; }
+      if (tid < 2 * (ROI_TH + ROI_TW)) rng[tid] = (tid & 1) ? -1 : 0x7fffffff;
       __syncthreads();
-      for (int i = tid; i < RO_TH * oh + RO_TW * ow; i += 256) {
-        const bool isy = i < RO_TH * oh;
-        const int jj = isy ? i : i - RO_TH * oh, nbin = isy ? oh : ow, t = jj / nbin, p = jj - t * nbin, pix = (isy ? ty0 : tx0) + t;
+      for (int i = tid; i < ROI_TH * oh + ROI_TW * ow; i += 256) {
+        const bool isy = i < ROI_TH * oh;
+        const int jj = isy ? i : i - ROI_TH * oh, nbin = isy ? oh : ow, t = jj / nbin, p = jj - t * nbin, pix = (isy ? ty0 : tx0) + t;
         const RoBin bn = isy ? ro_bin(gtb, p, H, hd.ny) : ro_bin(gtb, oh + p, W, hd.nx);
         const int k = pix - bn.first;
         const bool in = k >= 0 && k < bn.len;
         (isy ? wy : wx)[jj] = in ? gw[(isy ? 0 : a.g.capY) + bn.off + k] : 0.f;
         if (in) {          // integer min / max: the result does not depend on the order
-          int* rg = rng + 2 * (isy ? t : RO_TH + t);
+          int* rg = rng + 2 * (isy ? t : ROI_TH + t);
           atomicMin(rg, p); atomicMax(rg + 1, p);
         }
       }
       __syncthreads();
 #pragma unroll
-      for (int rr = 0; rr < RO_ROWS; ++rr) {
-        const int ty = RO_ROWS * wv + rr, pa = rng[2 * ty], pb = rng[2 * ty + 1];
+      for (int rr = 0; rr < ROI_ROWS; ++rr) {
+        const int ty = ROI_ROWS * wv + rr, pa = rng[2 * ty], pb = rng[2 * ty + 1];
         if (pa > pb) continue;          // (wave-uniform)
-        for (int tx = 0; tx < RO_TW; ++tx) {
-          const int qa = rng[2 * (RO_TH + tx)], qb = rng[2 * (RO_TH + tx) + 1];
+        for (int tx = 0; tx < ROI_TW; ++tx) {
+          const int qa = rng[2 * (ROI_TH + tx)], qb = rng[2 * (ROI_TH + tx) + 1];
           if (qa > qb || lane >= nch) continue;
-          float* ap = acc + (ty * RO_TW + tx) * RO_CHP + lane;
+          float* ap = acc + (ty * ROI_TW + tx) * ROI_CHP + lane;
           float s = *ap;
           for (int ph = pa; ph <= pb; ++ph) {
             const float wyv = wy[ty * oh + ph];
-            for (int pw = qa; pw <= qb; ++pw) s = fmaf(wyv * wx[tx * ow + pw], dys[(ph * ow + pw) * RO_CHP + lane], s);
+            for (int pw = qa; pw <= qb; ++pw) s = fmaf(wyv * wx[tx * ow + pw], dys[(ph * ow + pw) * ROI_CHP + lane], s);
           }
           *ap = s;
         }
@@ -304,53 +274,25 @@ __global__ __launch_bounds__(256) void roi_bwd_kernel(RoBwdArgs a) {
   const int64_t sc = a.m.sc[l], sh = a.m.sh[l], sw = a.m.sw[l];
   T* dx = reinterpret_cast<T*>(a.m.data[l]) + (int64_t)b * a.m.sb[l] + (int64_t)c0 * sc;
   const bool cl = sc == 1 && sw != 1;
-  for (int i = tid; i < RO_PIX * RO_CH; i += 256) {
-    const int c = cl ? i % RO_CH : i / RO_PIX, p = cl ? i / RO_CH : i % RO_PIX;
-    const int y = ty0 + p / RO_TW, x = tx0 + p % RO_TW;
-    if (c < nch && y < H && x < W) DT<T>::st(dx + (int64_t)c * sc + (int64_t)y * sh + (int64_t)x * sw, acc[p * RO_CHP + c]);
+  for (int i = tid; i < ROI_PIX * ROI_CH; i += 256) {
+    const int c = cl ? i % ROI_CH : i / ROI_PIX, p = cl ? i / ROI_CH : i % ROI_PIX;
+    const int y = ty0 + p / ROI_TW, x = tx0 + p % ROI_TW;
+    if (c < nch && y < H && x < W) DT<T>::st(dx + (int64_t)c * sc + (int64_t)y * sh + (int64_t)x * sw, acc[p * ROI_CHP + c]);
   }
 }
 
 // ---- host --------------------------------------------------------------------------------------------------------------------------------------------------------
-int ro_check(const char* fn, int R, const lmv_roi_level* lv, int L, int B, int oh, int ow, bool need_data, RoGeom* g, RoMaps* m) {
-  if (!lv) LMV_FAIL(LMV_ERR_SHAPE, "%s: null level table", fn);
-  if (L < 1 || L > LMV_ROI_MAX_LEVELS) LMV_FAIL(LMV_ERR_SHAPE, "%s: L = %d levels outside 1 .. %d", fn, L, LMV_ROI_MAX_LEVELS);
-  if (oh < 1 || ow < 1 || (int64_t)oh * ow > LMV_ROI_MAX_BINS) LMV_FAIL(LMV_ERR_SHAPE, "%s: out_size %d x %d outside 1 .. %d bins", fn, oh, ow, LMV_ROI_MAX_BINS);
-  if (R < 0 || B < 1) LMV_FAIL(LMV_ERR_SHAPE, "%s: bad shape R = %d, B = %d (R >= 0, B >= 1)", fn, R, B);
-  g->L = L; g->B = B; g->R = R; g->oh = oh; g->ow = ow;
+constexpr RoiRule RO_RULE = {LMV_ROI_MAX_EXTENT, 0, LMV_ROI_MAX_GRID, "0: the adaptive grid", 0, 15u};
+
+// roi_frame.h's geometry check, then what a record of this operator holds (sn: the plan call's sample_num; the other calls pass 0)
+int ro_check(const char* fn, int R, const lmv_roi_level* lv, int L, int B, int oh, int ow, int sn, bool need_data, RoGeom* g, RoiMaps* m) {
+  if (int rc = roi_check(fn, RO_RULE, R, lv, L, B, oh, ow, sn, need_data, g, m)) return rc;
   int mh = 0, mw = 0;
-  for (int l = 0; l < L; ++l) {
-    if (lv[l].H < 1 || lv[l].W < 1 || lv[l].H > LMV_ROI_MAX_EXTENT || lv[l].W > LMV_ROI_MAX_EXTENT)
-      LMV_FAIL(LMV_ERR_SHAPE, "%s: level %d: map of %d x %d outside 1 .. %d per axis", fn, l, lv[l].H, lv[l].W, LMV_ROI_MAX_EXTENT);
-    if (need_data && !lv[l].data) LMV_FAIL(LMV_ERR_SHAPE, "%s: level %d: null map", fn, l);
-    g->H[l] = lv[l].H; g->W[l] = lv[l].W;
-    mh = lv[l].H > mh ? lv[l].H : mh; mw = lv[l].W > mw ? lv[l].W : mw;
-    if (m) { m->data[l] = lv[l].data; m->sb[l] = lv[l].sb; m->sc[l] = lv[l].sc; m->sh[l] = lv[l].sh; m->sw[l] = lv[l].sw; }
-  }
-  for (int l = L; l < LMV_ROI_MAX_LEVELS; ++l) { g->H[l] = g->W[l] = 1; }
+  for (int l = 0; l < L; ++l) { mh = lv[l].H > mh ? lv[l].H : mh; mw = lv[l].W > mw ? lv[l].W : mw; }
   g->capY = mh + 2 * oh; g->capX = mw + 2 * ow;
   const int64_t raw = LMV_ROI_HEADER_BYTES + (int64_t)(oh + ow) * LMV_ROI_BIN_BYTES + (int64_t)(g->capY + g->capX) * 4;
   g->stride = (raw + 15) / 16 * 16;
   if ((int64_t)R * g->stride >= (1ll << 40)) LMV_FAIL(LMV_ERR_SHAPE, "%s: R = %d RoIs of %lld plan bytes: 2^40 bytes or more", fn, R, (long long)g->stride);
-  return LMV_OK;
-}
-
-int ro_check_maps(const char* fn, const lmv_roi_level* lv, int L, int B, int C, int R, int oh, int ow, int dtype) {
-  if (C < 1) LMV_FAIL(LMV_ERR_SHAPE, "%s: C = %d channels", fn, C);
-  if (dtype != LMV_F32 && dtype != LMV_BF16) LMV_FAIL(LMV_ERR_SHAPE, "%s: unsupported dtype code %d (fp32 / bf16)", fn, dtype);
-  if ((int64_t)R * C * oh * ow >= (1ll << 31)) LMV_FAIL(LMV_ERR_SHAPE, "%s: output of %d x %d x %d x %d: 2^31 elements or more", fn, R, C, oh, ow);
-  for (int l = 0; l < L; ++l) {
-    if ((int64_t)B * C * lv[l].H * lv[l].W >= (1ll << 31)) LMV_FAIL(LMV_ERR_SHAPE, "%s: level %d: map of %d x %d x %d x %d: 2^31 elements or more", fn, l, B, C, lv[l].H, lv[l].W);
-    if (lv[l].sb < 0 || lv[l].sc < 0 || lv[l].sh < 0 || lv[l].sw < 0) LMV_FAIL(LMV_ERR_SHAPE, "%s: level %d: negative stride", fn, l);
-    if (((uintptr_t)lv[l].data) & (dtype == LMV_F32 ? 3u : 1u)) LMV_FAIL(LMV_ERR_SHAPE, "%s: level %d: misaligned map", fn, l);
-  }
-  return LMV_OK;
-}
-
-template <typename K>
-int ro_reserve(const char* fn, K kernel, size_t lds) {
-  if (lds > 160 * 1024) LMV_FAIL(LMV_ERR_SHAPE, "%s: %zu bytes of LDS needed, 163840 available (smaller maps or fewer bins)", fn, lds);
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) LMV_FAIL(LMV_ERR_LAUNCH, "%s: cannot reserve LDS", fn);
   return LMV_OK;
 }
 
@@ -361,7 +303,7 @@ extern "C" size_t lmv_roi_plan_bytes(int R, const lmv_roi_level* lv, int L, int 
   if (!lv || L < 1 || L > LMV_ROI_MAX_LEVELS || oh < 1 || ow < 1 || (int64_t)oh * ow > LMV_ROI_MAX_BINS || R < 0) return 0;
   for (int l = 0; l < L; ++l)
     if (lv[l].H < 1 || lv[l].W < 1 || lv[l].H > LMV_ROI_MAX_EXTENT || lv[l].W > LMV_ROI_MAX_EXTENT) return 0;
-  if (ro_check("roi_plan_bytes", R, lv, L, 1, oh, ow, false, &g, nullptr)) return 0;
+  if (ro_check("roi_plan_bytes", R, lv, L, 1, oh, ow, 0, false, &g, nullptr)) return 0;
   return (size_t)R * (size_t)g.stride;
 }
 
@@ -369,10 +311,9 @@ extern "C" int lmv_roi_plan(const float* rois, const int32_t* levels, int R, con
                             void* plan, size_t plan_bytes, void* stream) {
   const char* fn = "roi_plan";
   RoPlanArgs a;
-  if (int rc = ro_check(fn, R, lv, L, B, oh, ow, false, &a.g, nullptr)) return rc;
-  if (sample_num < 0 || sample_num > LMV_ROI_MAX_GRID) LMV_FAIL(LMV_ERR_SHAPE, "%s: sample_num = %d outside 0 .. %d (0: the adaptive grid)", fn, sample_num, LMV_ROI_MAX_GRID);
+  if (int rc = ro_check(fn, R, lv, L, B, oh, ow, sample_num, false, &a.g, nullptr)) return rc;
   if (R > 0 && (!rois || !plan)) LMV_FAIL(LMV_ERR_SHAPE, "%s: null rois / plan", fn);
-  if ((((uintptr_t)rois) & 3u) || (((uintptr_t)levels) & 3u) || (((uintptr_t)plan) & 15u)) LMV_FAIL(LMV_ERR_SHAPE, "%s: misaligned buffer", fn);
+  if ((((uintptr_t)rois) & 3u) || (((uintptr_t)levels) & 3u) || (((uintptr_t)plan) & RO_RULE.plan_mask)) LMV_FAIL(LMV_ERR_SHAPE, "%s: misaligned buffer", fn);
   if (!(finest_scale > 0.f)) LMV_FAIL(LMV_ERR_SHAPE, "%s: finest_scale = %g <= 0", fn, finest_scale);
   const size_t need = (size_t)R * (size_t)a.g.stride;
   if (plan_bytes < need) LMV_FAIL(LMV_ERR_WORKSPACE, "%s: plan of %zu bytes, %zu needed (lmv_roi_plan_bytes)", fn, plan_bytes, need);
@@ -387,51 +328,23 @@ extern "C" int lmv_roi_plan(const float* rois, const int32_t* levels, int R, con
 extern "C" int lmv_roi_fwd(const void* plan, int R, const lmv_roi_level* lv, int L, int B, int C, int oh, int ow, int dtype, void* out, void* stream) {
   const char* fn = "roi_fwd";
   RoFwdArgs a;
-  if (int rc = ro_check(fn, R, lv, L, B, oh, ow, true, &a.g, &a.m)) return rc;
-  if (int rc = ro_check_maps(fn, lv, L, B, C, R, oh, ow, dtype)) return rc;
-  if (R > 0 && (!plan || !out)) LMV_FAIL(LMV_ERR_SHAPE, "%s: null plan / out", fn);
-  if ((((uintptr_t)plan) & 15u) || (((uintptr_t)out) & (dtype == LMV_F32 ? 3u : 1u))) LMV_FAIL(LMV_ERR_SHAPE, "%s: misaligned buffer", fn);
+  if (int rc = ro_check(fn, R, lv, L, B, oh, ow, 0, true, &a.g, &a.m)) return rc;
+  if (int rc = roi_check_io(fn, RO_RULE, lv, L, B, C, R, oh, ow, dtype, plan, out, "out")) return rc;
   if (R == 0) return LMV_OK;
-  const int nchunk = (C + RO_CH - 1) / RO_CH;
-  if (nchunk > 65535) LMV_FAIL(LMV_ERR_SHAPE, "%s: C = %d: more than 65535 chunks of %d channels", fn, C, RO_CH);
+  dim3 grid;
+  if (int rc = roi_fwd_grid(fn, R, C, &grid)) return rc;
   a.plan = reinterpret_cast<const char*>(plan); a.out = out; a.C = C;
-  const size_t lds = ((size_t)(oh + ow) * 4 + (size_t)a.g.capY + a.g.capX + (size_t)RO_CH * ((oh * ow) | 1)) * sizeof(float);          // 2.3 KB + 64 x 49 floats at 7 x 7 on a 200 x 336 map
-  const dim3 grid((unsigned)R, (unsigned)nchunk);
-  if (dtype == LMV_F32) {
-    if (int rc = ro_reserve(fn, roi_fwd_kernel<float>, lds)) return rc;
-    hipLaunchKernelGGL(roi_fwd_kernel<float>, grid, dim3(256), lds, (hipStream_t)stream, a);
-  } else {
-    if (int rc = ro_reserve(fn, roi_fwd_kernel<bf16_t>, lds)) return rc;
-    hipLaunchKernelGGL(roi_fwd_kernel<bf16_t>, grid, dim3(256), lds, (hipStream_t)stream, a);
-  }
-  LMV_CHECK_LAUNCH(fn);
-  return LMV_OK;
+  const size_t lds = ((size_t)(oh + ow) * 4 + (size_t)a.g.capY + a.g.capX + (size_t)ROI_CH * ((oh * ow) | 1)) * sizeof(float);          // 2.3 KB + 64 x 49 floats at 7 x 7 on a 200 x 336 map
+  return roi_launch(fn, roi_fwd_kernel<float>, roi_fwd_kernel<bf16_t>, dtype, grid, lds, stream, a);
 }
 
 extern "C" int lmv_roi_bwd(const void* plan, int R, const void* dy, const lmv_roi_level* dx, int L, int B, int C, int oh, int ow, int dtype, void* stream) {
   const char* fn = "roi_bwd";
   RoBwdArgs a;
-  if (int rc = ro_check(fn, R, dx, L, B, oh, ow, true, &a.g, &a.m)) return rc;
-  if (int rc = ro_check_maps(fn, dx, L, B, C, R, oh, ow, dtype)) return rc;
-  if (R > 0 && (!plan || !dy)) LMV_FAIL(LMV_ERR_SHAPE, "%s: null plan / dy", fn);
-  if ((((uintptr_t)plan) & 15u) || (((uintptr_t)dy) & (dtype == LMV_F32 ? 3u : 1u))) LMV_FAIL(LMV_ERR_SHAPE, "%s: misaligned buffer", fn);
-  const int nchunk = (C + RO_CH - 1) / RO_CH;
-  int64_t total = 0;
-  for (int l = 0; l < L; ++l) {
-    a.first[l] = (int)total;
-    total += (int64_t)B * ((dx[l].H + RO_TH - 1) / RO_TH) * ((dx[l].W + RO_TW - 1) / RO_TW) * nchunk;
-    if (total >= (1ll << 31)) LMV_FAIL(LMV_ERR_SHAPE, "%s: 2^31 tiles or more", fn);
-  }
-  for (int l = L; l <= LMV_ROI_MAX_LEVELS; ++l) a.first[l] = (int)total;
+  if (int rc = ro_check(fn, R, dx, L, B, oh, ow, 0, true, &a.g, &a.m)) return rc;
+  if (int rc = roi_check_io(fn, RO_RULE, dx, L, B, C, R, oh, ow, dtype, plan, dy, "dy")) return rc;
+  if (int rc = roi_bwd_tiles(fn, dx, L, B, C, a.first)) return rc;
   a.plan = reinterpret_cast<const char*>(plan); a.dy = dy; a.C = C;
-  const size_t lds = (((size_t)RO_PIX + (size_t)oh * ow) * RO_CHP + (size_t)RO_TH * oh + (size_t)RO_TW * ow + 2 * (RO_TH + RO_TW)) * sizeof(float);          // 33 KB + 260 B per bin + the tile's weights: at most 117 KB
-  if (dtype == LMV_F32) {
-    if (int rc = ro_reserve(fn, roi_bwd_kernel<float>, lds)) return rc;
-    hipLaunchKernelGGL(roi_bwd_kernel<float>, dim3((unsigned)total), dim3(256), lds, (hipStream_t)stream, a);
-  } else {
-    if (int rc = ro_reserve(fn, roi_bwd_kernel<bf16_t>, lds)) return rc;
-    hipLaunchKernelGGL(roi_bwd_kernel<bf16_t>, dim3((unsigned)total), dim3(256), lds, (hipStream_t)stream, a);
-  }
-  LMV_CHECK_LAUNCH(fn);
-  return LMV_OK;
+  const size_t lds = (((size_t)ROI_PIX + (size_t)oh * ow) * ROI_CHP + (size_t)ROI_TH * oh + (size_t)ROI_TW * ow + 2 * (ROI_TH + ROI_TW)) * sizeof(float);          // 33 KB + 260 B per bin + the tile's weights: at most 117 KB
+  return roi_launch(fn, roi_bwd_kernel<float>, roi_bwd_kernel<bf16_t>, dtype, dim3((unsigned)a.first[LMV_ROI_MAX_LEVELS]), lds, stream, a);
 }

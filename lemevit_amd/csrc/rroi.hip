@@ -14,27 +14,17 @@
 //          ballot and walks only those that touch its rows, in sample order.
 //          Every dX element is stored exactly once; no memset, no atomic, a fixed order of additions.
 #include "common.h"
+#include "roi_frame.h"          // the frame shared with roi.hip: records, level rule, forward / backward scaffolding, host checks
 
 namespace {
 
-constexpr int RR_TH = 8, RR_TW = 16;         // backward: tile of pixels (rows x columns); a wave owns RR_TH / 4 rows
-constexpr int RR_PIX = RR_TH * RR_TW, RR_ROWS = RR_TH / 4;
-constexpr int RR_CH = 64;                    // channels per workgroup (forward and backward)
-constexpr int RR_CHP = RR_CH + 1;            // LDS row pitch in floats: [pixel][channel] read along either axis without a bank conflict
 constexpr unsigned RR_EMPTY = 0xffffffffu;   // y word of a sample that contributes nothing
 
-struct RrHeader { int level, batch, valid, y0, y1, x0, x1, nsamp; };          // LMV_RROI_HEADER_BYTES; y0 > y1: no sample lands anywhere
+struct RrHeader : RoiHead { int nsamp; };                                    // LMV_RROI_HEADER_BYTES
 struct RrSample { unsigned yy, xx; float w[4]; };                            // LMV_RROI_SAMPLE_BYTES; yy = y_low | y_high << 16, xx likewise
 static_assert(sizeof(RrHeader) == LMV_RROI_HEADER_BYTES && sizeof(RrSample) == LMV_RROI_SAMPLE_BYTES, "plan record layout");
 
-struct RrGeom {
-  int L, B, R, oh, ow, sn;
-  int H[LMV_RROI_MAX_LEVELS], W[LMV_RROI_MAX_LEVELS];
-};
-struct RrMaps {
-  void* data[LMV_RROI_MAX_LEVELS];
-  int64_t sb[LMV_RROI_MAX_LEVELS], sc[LMV_RROI_MAX_LEVELS], sh[LMV_RROI_MAX_LEVELS], sw[LMV_RROI_MAX_LEVELS];
-};
+struct RrGeom : RoiGeom { int sn; };
 struct RrPlanArgs {
   RrGeom g;
   float scale[LMV_RROI_MAX_LEVELS];
@@ -42,8 +32,8 @@ struct RrPlanArgs {
   int aligned; float finest, ext_w, ext_h;
   RrHeader* hdr; RrSample* smp;
 };
-struct RrFwdArgs { RrGeom g; RrMaps m; const RrHeader* hdr; const RrSample* smp; void* out; int C; };
-struct RrBwdArgs { RrGeom g; RrMaps m; const RrHeader* hdr; const RrSample* smp; const void* dy; int C; int first[LMV_RROI_MAX_LEVELS + 1]; };
+struct RrFwdArgs { RrGeom g; RoiMaps m; const RrHeader* hdr; const RrSample* smp; void* out; int C; };
+struct RrBwdArgs { RrGeom g; RoiMaps m; const RrHeader* hdr; const RrSample* smp; const void* dy; int C; int first[LMV_RROI_MAX_LEVELS + 1]; };
 
 __device__ __forceinline__ int wave_min_i(int v) {
 #pragma unroll
@@ -64,16 +54,8 @@ __global__ __launch_bounds__(256) void rroi_plan_kernel(RrPlanArgs a) {
   const float bf = roi[0];
   float w = roi[3], h = roi[4];
   const float theta = roi[5];
-  int lvl;
-  if (a.levels) {
-    lvl = a.levels[r];
-  } else {
-    // upstream mmdet's map_roi_levels on the UN-extended box; accurate sqrtf / log2f (a level is a discontinuity)
-    const float v = floorf(log2f(sqrtf(w * h) / a.finest + 1e-6f));
-    lvl = v >= (float)(a.g.L - 1) ? a.g.L - 1 : v > 0.f ? (int)v : 0;          // (NaN: level 0)
-  }
-  // (int)bf truncates towards zero, as the reference's `int roi_batch_ind = roi[0]`; a non-finite field makes the RoI invalid, as in roi.hip
-  const bool valid = bf > -1.f && bf < (float)a.g.B && lvl >= 0 && lvl < a.g.L && isfinite(roi[1]) && isfinite(roi[2]) && isfinite(w) && isfinite(h) && isfinite(theta);
+  const int lvl = a.levels ? a.levels[r] : roi_level(w * h, a.finest, a.g.L);          // the level rule on the UN-extended box
+  const bool valid = roi_valid(bf, lvl, a.g) && isfinite(roi[1]) && isfinite(roi[2]) && isfinite(w) && isfinite(h) && isfinite(theta);          // a non-finite field: invalid
   const int lv = valid ? lvl : 0;
   w *= a.ext_w; h *= a.ext_h;
   const int H = a.g.H[lv], W = a.g.W[lv];
@@ -132,82 +114,46 @@ __global__ __launch_bounds__(256) void rroi_plan_kernel(RrPlanArgs a) {
 template <typename T>
 __global__ __launch_bounds__(256) void rroi_fwd_kernel(RrFwdArgs a) {
   extern __shared__ float tile[];          // channels-last only: [channel][bins | 1]
-  const int r = blockIdx.x, c0 = blockIdx.y * RR_CH, nch = min(RR_CH, a.C - c0), tid = threadIdx.x;
-  const int bins = a.g.oh * a.g.ow, ss = a.g.sn * a.g.sn, n = nch * bins;
-  T* out = reinterpret_cast<T*>(a.out) + ((int64_t)r * a.C + c0) * bins;          // this workgroup's n contiguous output elements
-  const RrHeader hd = a.hdr[r];
-  const bool ok = hd.valid && hd.level >= 0 && hd.level < a.g.L && hd.batch >= 0 && hd.batch < a.g.B;
-  if (!ok || hd.nsamp == 0) {
-    for (int i = tid; i < n; i += 256) DT<T>::st(out + i, 0.f);
-    return;
-  }
+  const int bins = a.g.oh * a.g.ow, ss = a.g.sn * a.g.sn;
+  const RoiChunk<T> k = roi_fwd_chunk<T>(a.out, a.C, bins);
+  const RrHeader hd = a.hdr[k.r];
+  if (!roi_head_ok(hd, a.g) || hd.nsamp == 0) return roi_fwd_zero(k);          // (workgroup-uniform)
   const int l = hd.level, H = a.g.H[l], W = a.g.W[l];
-  const int64_t sc = a.m.sc[l], sh = a.m.sh[l], sw = a.m.sw[l];
-  const T* x = reinterpret_cast<const T*>(a.m.data[l]) + (int64_t)hd.batch * a.m.sb[l] + (int64_t)c0 * sc;
-  const RrSample* smp = a.smp + (int64_t)r * bins * ss;
-  const bool cl = sc == 1 && sw != 1;          // lanes along the channels
-  const int pitch = bins | 1;
-  const float count = (float)ss;
-  for (int i = tid; i < n; i += 256) {
-    const int c = cl ? i % nch : i / bins, bin = cl ? i / nch : i - c * bins;
-    const T* xc = x + (int64_t)c * sc;
+  const RoiMap<T> x = roi_map<T>(a.m, l, hd.batch, k.c0);
+  const int64_t sh = x.sh, sw = x.sw;
+  const RrSample* smp = a.smp + (int64_t)k.r * bins * ss;
+  roi_fwd_store(k, x.cl, (float)ss, tile, [&](int c, int bin) {          // the bin's samples in sample order
+    const T* xc = x.p + (int64_t)c * x.sc;
     const RrSample* sp = smp + bin * ss;
     float acc = 0.f;
-    for (int k = 0; k < ss; ++k) {
-      const RrSample s = sp[k];
+    for (int j = 0; j < ss; ++j) {
+      const RrSample s = sp[j];
       const unsigned yl = s.yy & 0xffffu, yh = s.yy >> 16, xl = s.xx & 0xffffu, xh = s.xx >> 16;
       if (s.yy == RR_EMPTY || yl >= (unsigned)H || yh >= (unsigned)H || xl >= (unsigned)W || xh >= (unsigned)W) continue;          // (the index tests: a plan of another geometry cannot reach outside the map)
       const int64_t oyl = (int64_t)yl * sh, oyh = (int64_t)yh * sh, oxl = (int64_t)xl * sw, oxh = (int64_t)xh * sw;
       acc += s.w[0] * DT<T>::ld(xc + oyl + oxl) + s.w[1] * DT<T>::ld(xc + oyl + oxh) + s.w[2] * DT<T>::ld(xc + oyh + oxl) + s.w[3] * DT<T>::ld(xc + oyh + oxh);
     }
-    acc /= count;
-    if (cl) tile[c * pitch + bin] = acc;
-    else DT<T>::st(out + i, acc);
-  }
-  if (cl) {
-    __syncthreads();
-    for (int i = tid; i < n; i += 256) { const int c = i / bins, bin = i - c * bins; DT<T>::st(out + i, tile[c * pitch + bin]); }
-  }
+    return acc;
+  });
 }
 
 // ---- backward --------------------------------------------------------------------------------------------------------------------------------------------------
 template <typename T>
 __global__ __launch_bounds__(256) void rroi_bwd_kernel(RrBwdArgs a) {
   extern __shared__ float lds[];
-  float* acc = lds;                                   // [RR_PIX][RR_CHP]
-  float* dys = lds + RR_PIX * RR_CHP;                 // [bins][RR_CHP]
+  float* acc = lds;                                   // [ROI_PIX][ROI_CHP]
+  float* dys = lds + ROI_PIX * ROI_CHP;               // [bins][ROI_CHP]
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  int blk = blockIdx.x, l = 0;
-  while (l + 1 < a.g.L && blk >= a.first[l + 1]) ++l;
-  blk -= a.first[l];
-  const int H = a.g.H[l], W = a.g.W[l], tnx = (W + RR_TW - 1) / RR_TW, tny = (H + RR_TH - 1) / RR_TH, nchunk = (a.C + RR_CH - 1) / RR_CH;
-  const int chunk = blk % nchunk; blk /= nchunk;
-  const int tx0 = (blk % tnx) * RR_TW; blk /= tnx;
-  const int ty0 = (blk % tny) * RR_TH, b = blk / tny;
-  const int c0 = chunk * RR_CH, nch = min(RR_CH, a.C - c0);
-  const int bins = a.g.oh * a.g.ow, ss = a.g.sn * a.g.sn, R = a.g.R;
-  const float count = (float)ss;
-  const int wy0 = ty0 + RR_ROWS * wv;          // this wave's pixel rows: wy0 .. wy0 + RR_ROWS - 1
-  const T* dy = reinterpret_cast<const T*>(a.dy);
-  unsigned* sms = reinterpret_cast<unsigned*>(dys + bins * RR_CHP);          // [bins ss] sample records of 6 words
-
-  for (int i = tid; i < RR_PIX * RR_CHP; i += 256) acc[i] = 0.f;
-
+  const int bins = a.g.oh * a.g.ow, ss = a.g.sn * a.g.sn;
+  unsigned* sms = reinterpret_cast<unsigned*>(dys + bins * ROI_CHP);          // [bins ss] sample records of 6 words
+  const RoiTile tile = roi_bwd_tile(a, acc);
+  const int tx0 = tile.tx0, nch = tile.nch, R = a.g.R;
+  const int wy0 = tile.ty0 + ROI_ROWS * wv;          // this wave's pixel rows: wy0 .. wy0 + ROI_ROWS - 1
   for (int r0 = 0; r0 < R; r0 += 64) {
-    const int rl = r0 + lane;
-    bool hit = false;
-    if (rl < R) {
-      const RrHeader hd = a.hdr[rl];
-      hit = hd.valid && hd.level == l && hd.batch == b && hd.y1 >= ty0 && hd.y0 < ty0 + RR_TH && hd.x1 >= tx0 && hd.x0 < tx0 + RR_TW;
-    }
-    unsigned long long mask = __ballot(hit);          // the same word in all four waves: the loop below is workgroup-uniform
-    while (mask) {
-      const int j = __ffsll((long long)mask) - 1;
-      mask &= mask - 1;
-      const int r = __builtin_amdgcn_readfirstlane(r0 + j);
-      __syncthreads();          // the walk of the previous hit (and the zero fill) is over
-      const T* dr = dy + ((int64_t)r * a.C + c0) * bins;
-      for (int i = tid; i < nch * bins; i += 256) { const int c = i / bins, bin = i - c * bins; dys[bin * RR_CHP + c] = DT<T>::ld(dr + i) / count; }
+    unsigned long long mask = roi_bwd_scan<RrHeader>(reinterpret_cast<const char*>(a.hdr), sizeof(RrHeader), R, tile, r0, [&](const RrHeader& hd) { return roi_head_ok(hd, a.g); });
+    while (mask) {          // per hit: the rotated sample walk
+      const int r = roi_bwd_next(r0, &mask);
+      roi_bwd_stage_dy<T>(tile, a.dy, r, a.C, bins, (float)ss, dys);
       const unsigned* sg = reinterpret_cast<const unsigned*>(a.smp + (int64_t)r * bins * ss);
       for (int i = tid; i < bins * ss * 6; i += 256) sms[i] = sg[i];
       __syncthreads();
@@ -215,12 +161,12 @@ __global__ __launch_bounds__(256) void rroi_bwd_kernel(RrBwdArgs a) {
       // A wave with nothing of this RoI in its rows skips the walk (the barriers above are outside this branch).  Otherwise 64 samples are tested at a time, a lane
       // each (all 64 lanes, also those without a channel), and only the samples that touch the wave's rows are walked, in ascending order, by the lanes that own a channel
       const int ns = bins * ss;
-      for (int s0 = 0; hd.y1 >= wy0 && hd.y0 < wy0 + RR_ROWS && s0 < ns; s0 += 64) {
+      for (int s0 = 0; hd.y1 >= wy0 && hd.y0 < wy0 + ROI_ROWS && s0 < ns; s0 += 64) {
         bool touch = false;
         if (s0 + lane < ns) {
           const unsigned ty = sms[(s0 + lane) * 6], tx = sms[(s0 + lane) * 6 + 1];
-          const bool trl = (unsigned)((int)(ty & 0xffffu) - wy0) < (unsigned)RR_ROWS, trh = (unsigned)((int)(ty >> 16) - wy0) < (unsigned)RR_ROWS;
-          const bool til = (unsigned)((int)(tx & 0xffffu) - tx0) < (unsigned)RR_TW, tih = (unsigned)((int)(tx >> 16) - tx0) < (unsigned)RR_TW;
+          const bool trl = (unsigned)((int)(ty & 0xffffu) - wy0) < (unsigned)ROI_ROWS, trh = (unsigned)((int)(ty >> 16) - wy0) < (unsigned)ROI_ROWS;
+          const bool til = (unsigned)((int)(tx & 0xffffu) - tx0) < (unsigned)ROI_TW, tih = (unsigned)((int)(tx >> 16) - tx0) < (unsigned)ROI_TW;
           touch = ty != RR_EMPTY && (trl || trh) && (til || tih);
         }
         unsigned long long todo = __ballot(touch);
@@ -228,84 +174,54 @@ __global__ __launch_bounds__(256) void rroi_bwd_kernel(RrBwdArgs a) {
           const int si = __builtin_amdgcn_readfirstlane(s0 + __ffsll((long long)todo) - 1);
           todo &= todo - 1;
           if (lane >= nch) continue;
-          const float g = dys[(si / ss) * RR_CHP + lane];
+          const float g = dys[(si / ss) * ROI_CHP + lane];
           const unsigned* sp = sms + si * 6;          // the same address in every lane: a broadcast read
           const unsigned yy = __builtin_amdgcn_readfirstlane(sp[0]), xx = __builtin_amdgcn_readfirstlane(sp[1]);          // (uniform: the tests below are scalar branches)
           const int yl = (int)(yy & 0xffffu), yh = (int)(yy >> 16), xl = (int)(xx & 0xffffu), xh = (int)(xx >> 16);
           const int ryl = yl - wy0, ryh = yh - wy0, cxl = xl - tx0, cxh = xh - tx0;
-          const bool rl = (unsigned)ryl < (unsigned)RR_ROWS, rh = (unsigned)ryh < (unsigned)RR_ROWS, inl = (unsigned)cxl < (unsigned)RR_TW, inh = (unsigned)cxh < (unsigned)RR_TW;
-          float* rowl = acc + ((RR_ROWS * wv + ryl) * RR_TW) * RR_CHP + lane;
-          float* rowh = acc + ((RR_ROWS * wv + ryh) * RR_TW) * RR_CHP + lane;
+          const bool rl = (unsigned)ryl < (unsigned)ROI_ROWS, rh = (unsigned)ryh < (unsigned)ROI_ROWS, inl = (unsigned)cxl < (unsigned)ROI_TW, inh = (unsigned)cxh < (unsigned)ROI_TW;
+          float* rowl = acc + ((ROI_ROWS * wv + ryl) * ROI_TW) * ROI_CHP + lane;
+          float* rowh = acc + ((ROI_ROWS * wv + ryh) * ROI_TW) * ROI_CHP + lane;
           const float w0 = __uint_as_float(sp[2]) * g, w1 = __uint_as_float(sp[3]) * g, w2 = __uint_as_float(sp[4]) * g, w3 = __uint_as_float(sp[5]) * g;
           if (yl != yh && xl != xh) {
             // four different pixels: the four read-modify-writes are independent, so all reads are issued before the first add (one LDS latency per sample, not four)
             const bool h0 = rl && inl, h1 = rl && inh, h2 = rh && inl, h3 = rh && inh;
             float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-            if (h0) a0 = rowl[cxl * RR_CHP];
-            if (h1) a1 = rowl[cxh * RR_CHP];
-            if (h2) a2 = rowh[cxl * RR_CHP];
-            if (h3) a3 = rowh[cxh * RR_CHP];
+            if (h0) a0 = rowl[cxl * ROI_CHP];
+            if (h1) a1 = rowl[cxh * ROI_CHP];
+            if (h2) a2 = rowh[cxl * ROI_CHP];
+            if (h3) a3 = rowh[cxh * ROI_CHP];
             a0 += w0; a1 += w1; a2 += w2; a3 += w3;
-            if (h0) rowl[cxl * RR_CHP] = a0;
-            if (h1) rowl[cxh * RR_CHP] = a1;
-            if (h2) rowh[cxl * RR_CHP] = a2;
-            if (h3) rowh[cxh * RR_CHP] = a3;
+            if (h0) rowl[cxl * ROI_CHP] = a0;
+            if (h1) rowl[cxh * ROI_CHP] = a1;
+            if (h2) rowh[cxl * ROI_CHP] = a2;
+            if (h3) rowh[cxh * ROI_CHP] = a3;
           } else {          // a clamped edge: corners share a pixel, the adds stay in corner order
             if (rl) {
-              if (inl) rowl[cxl * RR_CHP] += w0;
-              if (inh) rowl[cxh * RR_CHP] += w1;
+              if (inl) rowl[cxl * ROI_CHP] += w0;
+              if (inh) rowl[cxh * ROI_CHP] += w1;
             }
             if (rh) {
-              if (inl) rowh[cxl * RR_CHP] += w2;
-              if (inh) rowh[cxh * RR_CHP] += w3;
+              if (inl) rowh[cxl * ROI_CHP] += w2;
+              if (inh) rowh[cxh * ROI_CHP] += w3;
             }
           }
         }
       }
     }
   }
-  __syncthreads();
-  const int64_t sc = a.m.sc[l], sh = a.m.sh[l], sw = a.m.sw[l];
-  T* dx = reinterpret_cast<T*>(a.m.data[l]) + (int64_t)b * a.m.sb[l] + (int64_t)c0 * sc;
-  const bool cl = sc == 1 && sw != 1;
-  for (int i = tid; i < RR_PIX * RR_CH; i += 256) {
-    const int c = cl ? i % RR_CH : i / RR_PIX, p = cl ? i / RR_CH : i % RR_PIX;
-    const int y = ty0 + p / RR_TW, x = tx0 + p % RR_TW;
-    if (c < nch && y < H && x < W) DT<T>::st(dx + (int64_t)c * sc + (int64_t)y * sh + (int64_t)x * sw, acc[p * RR_CHP + c]);
-  }
+  roi_bwd_store<T>(a.m, tile, acc);
 }
 
 // ---- host --------------------------------------------------------------------------------------------------------------------------------------------------------
-int rr_check(const char* fn, int R, const lmv_rroi_level* lv, int L, int B, int oh, int ow, int sn, bool need_data, RrGeom* g, RrMaps* m) {
-  if (!lv) LMV_FAIL(LMV_ERR_SHAPE, "%s: null level table", fn);
-  if (L < 1 || L > LMV_RROI_MAX_LEVELS) LMV_FAIL(LMV_ERR_SHAPE, "%s: L = %d levels outside 1 .. %d", fn, L, LMV_RROI_MAX_LEVELS);
-  if (sn < 1 || sn > LMV_RROI_MAX_SAMPLE_NUM) LMV_FAIL(LMV_ERR_SHAPE, "%s: sample_num = %d outside 1 .. %d (0, the adaptive grid, is not supported)", fn, sn, LMV_RROI_MAX_SAMPLE_NUM);
-  if (oh < 1 || ow < 1 || (int64_t)oh * ow > LMV_RROI_MAX_BINS) LMV_FAIL(LMV_ERR_SHAPE, "%s: out_size %d x %d outside 1 .. %d bins", fn, oh, ow, LMV_RROI_MAX_BINS);
-  if ((int64_t)oh * ow * sn * sn > LMV_RROI_MAX_SAMPLES) LMV_FAIL(LMV_ERR_SHAPE, "%s: %d x %d bins of %d x %d samples: more than the %d samples a plan record holds", fn, oh, ow, sn, sn, LMV_RROI_MAX_SAMPLES);
-  if (R < 0 || B < 1) LMV_FAIL(LMV_ERR_SHAPE, "%s: bad shape R = %d, B = %d (R >= 0, B >= 1)", fn, R, B);
-  if ((int64_t)R * oh * ow * sn * sn >= (1ll << 31)) LMV_FAIL(LMV_ERR_SHAPE, "%s: R = %d RoIs of %d samples: 2^31 samples or more", fn, R, oh * ow * sn * sn);
-  g->L = L; g->B = B; g->R = R; g->oh = oh; g->ow = ow; g->sn = sn;
-  for (int l = 0; l < L; ++l) {
-    if (lv[l].H < 1 || lv[l].W < 1 || lv[l].H > LMV_RROI_MAX_EXTENT || lv[l].W > LMV_RROI_MAX_EXTENT)
-      LMV_FAIL(LMV_ERR_SHAPE, "%s: level %d: map of %d x %d outside 1 .. %d per axis", fn, l, lv[l].H, lv[l].W, LMV_RROI_MAX_EXTENT);
-    if (need_data && !lv[l].data) LMV_FAIL(LMV_ERR_SHAPE, "%s: level %d: null map", fn, l);
-    g->H[l] = lv[l].H; g->W[l] = lv[l].W;
-    if (m) { m->data[l] = lv[l].data; m->sb[l] = lv[l].sb; m->sc[l] = lv[l].sc; m->sh[l] = lv[l].sh; m->sw[l] = lv[l].sw; }
-  }
-  return LMV_OK;
-}
+constexpr RoiRule RR_RULE = {LMV_RROI_MAX_EXTENT, 1, LMV_RROI_MAX_SAMPLE_NUM, "0, the adaptive grid, is not supported", LMV_RROI_MAX_SAMPLES, 7u};
 
-int rr_check_maps(const char* fn, const lmv_rroi_level* lv, int L, int B, int C, int R, int oh, int ow, int dtype) {
-  if (C < 1) LMV_FAIL(LMV_ERR_SHAPE, "%s: C = %d channels", fn, C);
-  if (dtype != LMV_F32 && dtype != LMV_BF16) LMV_FAIL(LMV_ERR_SHAPE, "%s: unsupported dtype code %d (fp32 / bf16)", fn, dtype);
-  if ((int64_t)R * C * oh * ow >= (1ll << 31)) LMV_FAIL(LMV_ERR_SHAPE, "%s: output of %d x %d x %d x %d: 2^31 elements or more", fn, R, C, oh, ow);
-  for (int l = 0; l < L; ++l) {
-    if ((int64_t)B * C * lv[l].H * lv[l].W >= (1ll << 31)) LMV_FAIL(LMV_ERR_SHAPE, "%s: level %d: map of %d x %d x %d x %d: 2^31 elements or more", fn, l, B, C, lv[l].H, lv[l].W);
-    if (lv[l].sb < 0 || lv[l].sc < 0 || lv[l].sh < 0 || lv[l].sw < 0) LMV_FAIL(LMV_ERR_SHAPE, "%s: level %d: negative stride", fn, l);
-    if (((uintptr_t)lv[l].data) & (dtype == LMV_F32 ? 3u : 1u)) LMV_FAIL(LMV_ERR_SHAPE, "%s: level %d: misaligned map", fn, l);
-  }
-  return LMV_OK;
+int rr_check(const char* fn, int R, const lmv_rroi_level* lv, int L, int B, int oh, int ow, int sn, bool need_data, RrGeom* g, RoiMaps* m) {
+  g->sn = sn;
+  return roi_check(fn, RR_RULE, R, lv, L, B, oh, ow, sn, need_data, g, m);
 }
+// a plan is R headers, then R records of oh ow s s samples
+RrSample* rr_samples(const void* plan, int R) { return reinterpret_cast<RrSample*>(reinterpret_cast<char*>(const_cast<void*>(plan)) + (size_t)R * LMV_RROI_HEADER_BYTES); }
 
 }  // namespace
 
@@ -322,16 +238,15 @@ extern "C" int lmv_rroi_plan(const float* rois, const int32_t* levels, int R, co
   RrPlanArgs a;
   if (int rc = rr_check(fn, R, lv, L, B, oh, ow, sample_num, false, &a.g, nullptr)) return rc;
   if (R > 0 && (!rois || !plan)) LMV_FAIL(LMV_ERR_SHAPE, "%s: null rois / plan", fn);
-  if ((((uintptr_t)rois) & 3u) || (((uintptr_t)levels) & 3u) || (((uintptr_t)plan) & 7u)) LMV_FAIL(LMV_ERR_SHAPE, "%s: misaligned buffer", fn);
+  if ((((uintptr_t)rois) & 3u) || (((uintptr_t)levels) & 3u) || (((uintptr_t)plan) & RR_RULE.plan_mask)) LMV_FAIL(LMV_ERR_SHAPE, "%s: misaligned buffer", fn);
   if (aligned != 0 && aligned != 1) LMV_FAIL(LMV_ERR_SHAPE, "%s: aligned = %d is neither 0 nor 1", fn, aligned);
   if (!(finest_scale > 0.f)) LMV_FAIL(LMV_ERR_SHAPE, "%s: finest_scale = %g <= 0", fn, finest_scale);
   const size_t need = lmv_rroi_plan_bytes(R, oh, ow, sample_num);
   if (plan_bytes < need) LMV_FAIL(LMV_ERR_WORKSPACE, "%s: plan of %zu bytes, %zu needed (lmv_rroi_plan_bytes)", fn, plan_bytes, need);
   if (R == 0) return LMV_OK;
-  for (int l = 0; l < L; ++l) a.scale[l] = lv[l].spatial_scale;
+  for (int l = 0; l < LMV_RROI_MAX_LEVELS; ++l) a.scale[l] = l < L ? lv[l].spatial_scale : 0.f;
   a.rois = rois; a.levels = levels; a.aligned = aligned; a.finest = finest_scale; a.ext_w = extend_w; a.ext_h = extend_h;
-  a.hdr = reinterpret_cast<RrHeader*>(plan);
-  a.smp = reinterpret_cast<RrSample*>(reinterpret_cast<char*>(plan) + (size_t)R * LMV_RROI_HEADER_BYTES);
+  a.hdr = reinterpret_cast<RrHeader*>(plan); a.smp = rr_samples(plan, R);
   hipLaunchKernelGGL(rroi_plan_kernel, dim3(R), dim3(256), 0, (hipStream_t)stream, a);
   LMV_CHECK_LAUNCH(fn);
   return LMV_OK;
@@ -341,54 +256,24 @@ extern "C" int lmv_rroi_fwd(const void* plan, int R, const lmv_rroi_level* lv, i
   const char* fn = "rroi_fwd";
   RrFwdArgs a;
   if (int rc = rr_check(fn, R, lv, L, B, oh, ow, sample_num, true, &a.g, &a.m)) return rc;
-  if (int rc = rr_check_maps(fn, lv, L, B, C, R, oh, ow, dtype)) return rc;
-  if (R > 0 && (!plan || !out)) LMV_FAIL(LMV_ERR_SHAPE, "%s: null plan / out", fn);
-  if ((((uintptr_t)plan) & 7u) || (((uintptr_t)out) & (dtype == LMV_F32 ? 3u : 1u))) LMV_FAIL(LMV_ERR_SHAPE, "%s: misaligned buffer", fn);
+  if (int rc = roi_check_io(fn, RR_RULE, lv, L, B, C, R, oh, ow, dtype, plan, out, "out")) return rc;
   if (R == 0) return LMV_OK;
-  const int nchunk = (C + RR_CH - 1) / RR_CH;
-  if (nchunk > 65535) LMV_FAIL(LMV_ERR_SHAPE, "%s: C = %d: more than 65535 chunks of %d channels", fn, C, RR_CH);
-  a.hdr = reinterpret_cast<const RrHeader*>(plan);
-  a.smp = reinterpret_cast<const RrSample*>(reinterpret_cast<const char*>(plan) + (size_t)R * LMV_RROI_HEADER_BYTES);
+  dim3 grid;
+  if (int rc = roi_fwd_grid(fn, R, C, &grid)) return rc;
+  a.hdr = reinterpret_cast<const RrHeader*>(plan); a.smp = rr_samples(plan, R);
   a.out = out; a.C = C;
-  const size_t lds = (size_t)RR_CH * ((oh * ow) | 1) * sizeof(float);          // <= 64 x 257 floats
-  const dim3 grid((unsigned)R, (unsigned)nchunk);
-  if (dtype == LMV_F32) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(rroi_fwd_kernel<float>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) LMV_FAIL(LMV_ERR_LAUNCH, "%s: cannot reserve LDS", fn);
-    hipLaunchKernelGGL(rroi_fwd_kernel<float>, grid, dim3(256), lds, (hipStream_t)stream, a);
-  } else {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(rroi_fwd_kernel<bf16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) LMV_FAIL(LMV_ERR_LAUNCH, "%s: cannot reserve LDS", fn);
-    hipLaunchKernelGGL(rroi_fwd_kernel<bf16_t>, grid, dim3(256), lds, (hipStream_t)stream, a);
-  }
-  LMV_CHECK_LAUNCH(fn);
-  return LMV_OK;
+  const size_t lds = (size_t)ROI_CH * ((oh * ow) | 1) * sizeof(float);          // <= 64 x 257 floats
+  return roi_launch(fn, rroi_fwd_kernel<float>, rroi_fwd_kernel<bf16_t>, dtype, grid, lds, stream, a);
 }
 
 extern "C" int lmv_rroi_bwd(const void* plan, int R, const void* dy, const lmv_rroi_level* dx, int L, int B, int C, int oh, int ow, int sample_num, int dtype, void* stream) {
   const char* fn = "rroi_bwd";
   RrBwdArgs a;
   if (int rc = rr_check(fn, R, dx, L, B, oh, ow, sample_num, true, &a.g, &a.m)) return rc;
-  if (int rc = rr_check_maps(fn, dx, L, B, C, R, oh, ow, dtype)) return rc;
-  if (R > 0 && (!plan || !dy)) LMV_FAIL(LMV_ERR_SHAPE, "%s: null plan / dy", fn);
-  if ((((uintptr_t)plan) & 7u) || (((uintptr_t)dy) & (dtype == LMV_F32 ? 3u : 1u))) LMV_FAIL(LMV_ERR_SHAPE, "%s: misaligned buffer", fn);
-  const int nchunk = (C + RR_CH - 1) / RR_CH;
-  int64_t total = 0;
-  for (int l = 0; l < L; ++l) {
-    a.first[l] = (int)total;
-    total += (int64_t)B * ((dx[l].H + RR_TH - 1) / RR_TH) * ((dx[l].W + RR_TW - 1) / RR_TW) * nchunk;
-    if (total >= (1ll << 31)) LMV_FAIL(LMV_ERR_SHAPE, "%s: 2^31 tiles or more", fn);
-  }
-  for (int l = L; l <= LMV_RROI_MAX_LEVELS; ++l) a.first[l] = (int)total;
-  a.hdr = reinterpret_cast<const RrHeader*>(plan);
-  a.smp = reinterpret_cast<const RrSample*>(reinterpret_cast<const char*>(plan) + (size_t)R * LMV_RROI_HEADER_BYTES);
+  if (int rc = roi_check_io(fn, RR_RULE, dx, L, B, C, R, oh, ow, dtype, plan, dy, "dy")) return rc;
+  if (int rc = roi_bwd_tiles(fn, dx, L, B, C, a.first)) return rc;
+  a.hdr = reinterpret_cast<const RrHeader*>(plan); a.smp = rr_samples(plan, R);
   a.dy = dy; a.C = C;
-  const size_t lds = ((size_t)RR_PIX + (size_t)oh * ow) * RR_CHP * sizeof(float) + (size_t)oh * ow * sample_num * sample_num * LMV_RROI_SAMPLE_BYTES;          // 33 KB + 260 B per bin + 24 B per sample: <= 122 KB of the 160 KB
-  if (dtype == LMV_F32) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(rroi_bwd_kernel<float>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) LMV_FAIL(LMV_ERR_LAUNCH, "%s: cannot reserve LDS", fn);
-    hipLaunchKernelGGL(rroi_bwd_kernel<float>, dim3((unsigned)total), dim3(256), lds, (hipStream_t)stream, a);
-  } else {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(rroi_bwd_kernel<bf16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) LMV_FAIL(LMV_ERR_LAUNCH, "%s: cannot reserve LDS", fn);
-    hipLaunchKernelGGL(rroi_bwd_kernel<bf16_t>, dim3((unsigned)total), dim3(256), lds, (hipStream_t)stream, a);
-  }
-  LMV_CHECK_LAUNCH(fn);
-  return LMV_OK;
+  const size_t lds = ((size_t)ROI_PIX + (size_t)oh * ow) * ROI_CHP * sizeof(float) + (size_t)oh * ow * sample_num * sample_num * LMV_RROI_SAMPLE_BYTES;          // 33 KB + 260 B per bin + 24 B per sample: <= 122 KB of the 160 KB
+  return roi_launch(fn, rroi_bwd_kernel<float>, rroi_bwd_kernel<bf16_t>, dtype, dim3((unsigned)a.first[LMV_RROI_MAX_LEVELS]), lds, stream, a);
 }

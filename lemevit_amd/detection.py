@@ -122,16 +122,30 @@ def _check_sample_num(sample_num: int) -> int:
     return s
 
 
-class _RroiFn(torch.autograd.Function):
-    """ONE node over all levels: forward = plan + forward launch, backward = one launch that writes every level's gradient once."""
+ROI_MAX_GRID = 128          # LMV_ROI_MAX_GRID: a RoI whose grid ceil(roi_size / out_size) exceeds it on either axis is invalid (a zero row, no gradient)
+
+
+def _check_roi_sample_num(sample_num: int) -> int:
+    s = int(sample_num)
+    if not 0 <= s <= ROI_MAX_GRID:
+        raise ValueError(f"roi_align: sample_num = {s} outside 0 .. {ROI_MAX_GRID} (0: the adaptive grid)")
+    return s
+
+
+class _RoiAlignFn(torch.autograd.Function):
+    """ONE node over all levels, for both RoIAlign kinds: forward = plan + forward launch, backward = one launch that writes every level's gradient once."""
 
     @staticmethod
     def forward(ctx, rois, levels, cfg, *feats):
-        out_size, scales, sample_num, aligned, finest_scale, extend_factor = cfg
+        rotated, out_size, scales, sample_num, finest_scale, aligned, extend_factor = cfg
         feats = list(feats)
-        plan = ops.rroi_plan(rois, [f.shape[-2:] for f in feats], scales, feats[0].shape[0], out_size, sample_num, aligned, levels, finest_scale, extend_factor)
-        out = ops.rroi_align_fwd(feats, plan)
-        ctx.plan = plan
+        sizes, B = [f.shape[-2:] for f in feats], feats[0].shape[0]
+        if rotated:
+            plan = ops.rroi_plan(rois, sizes, scales, B, out_size, sample_num, aligned, levels, finest_scale, extend_factor)
+        else:
+            plan = ops.roi_plan(rois, sizes, scales, B, out_size, sample_num, levels, finest_scale)
+        out = (ops.rroi_align_fwd if rotated else ops.roi_align_fwd)(feats, plan)
+        ctx.plan, ctx.rotated = plan, rotated
         ctx.meta = [(tuple(f.shape), tuple(f.stride()), f.dtype, f.device) for f in feats]
         return out
 
@@ -143,25 +157,59 @@ class _RroiFn(torch.autograd.Function):
         # dX in the feature's own layout; a layout in which two indices share an address (an expanded view) gets a contiguous gradient instead
         dx = [torch.empty_strided(shape, stride, dtype=dtype, device=device) if ops.strides_injective(shape, stride) else torch.empty(shape, dtype=dtype, device=device)
               for shape, stride, dtype, device in ctx.meta]
-        ops.rroi_align_bwd(grad_out.contiguous(), ctx.plan, dx, dx=dx)
+        (ops.rroi_align_bwd if ctx.rotated else ops.roi_align_bwd)(grad_out.contiguous(), ctx.plan, dx, dx=dx)
         return (None, None, None) + tuple(dx)
 
 
-def _rroi_apply(feats: Sequence[Tensor], rois: Tensor, levels: Optional[Tensor], out_size, scales, sample_num, aligned, finest_scale, extend_factor) -> Tensor:
-    if rois.dim() != 2 or rois.size(1) != 6:
-        raise ValueError(f"roi_align_rotated: rois must be [R, 6] (batch_index, cx, cy, w, h, theta), got {tuple(rois.shape)}")
+def _roi_apply(rotated: bool, feats: Sequence[Tensor], rois: Tensor, levels: Optional[Tensor], out_size, scales, sample_num, finest_scale, aligned=True,
+               extend_factor=(1.0, 1.0)) -> Tensor:
+    name, cols, fields = ("roi_align_rotated", 6, "cx, cy, w, h, theta") if rotated else ("roi_align", 5, "x1, y1, x2, y2")
+    if rois.dim() != 2 or rois.size(1) != cols:
+        raise ValueError(f"{name}: rois must be [R, {cols}] (batch_index, {fields}), got {tuple(rois.shape)}")
     if rois.requires_grad:
-        raise RuntimeError("roi_align_rotated: there is no gradient for the RoIs (detach them)")
+        raise RuntimeError(f"{name}: there is no gradient for the RoIs (detach them)")
     oh, ow = _pair(out_size)
-    cfg = ((int(oh), int(ow)), tuple(float(s) for s in scales), _check_sample_num(sample_num), bool(aligned), float(finest_scale), (float(extend_factor[0]), float(extend_factor[1])))
-    return _RroiFn.apply(rois.detach().float().contiguous(), levels, cfg, *feats)
+    cfg = (rotated, (int(oh), int(ow)), tuple(float(s) for s in scales), (_check_sample_num if rotated else _check_roi_sample_num)(sample_num), float(finest_scale),
+           bool(aligned), (float(extend_factor[0]), float(extend_factor[1])))
+    return _RoiAlignFn.apply(rois.detach().float().contiguous(), levels, cfg, *feats)
+
+
+class _RoIExtractorBase(nn.Module):
+    """What both single-level extractors share: the level-count check, ``num_inputs`` and the feature / channel checks of ``forward``."""
+
+    def __init__(self, check_sample_num, out_size, sample_num, featmap_strides, out_channels, finest_scale):
+        super().__init__()
+        if not 1 <= len(featmap_strides) <= MAX_LEVELS:
+            raise ValueError(f"{type(self).__name__}: {len(featmap_strides)} levels outside 1 .. {MAX_LEVELS}")
+        self.out_size = _pair(out_size)
+        self.sample_num = check_sample_num(sample_num)
+        self.featmap_strides = tuple(featmap_strides)
+        self.out_channels = int(out_channels)
+        self.finest_scale = float(finest_scale)
+
+    @property
+    def num_inputs(self):
+        return len(self.featmap_strides)
+
+    def _levels(self, feats: Sequence[Tensor]):
+        """(the first ``num_inputs`` feature maps, their spatial scales)"""
+        feats = list(feats)[:len(self.featmap_strides)]
+        if len(feats) != len(self.featmap_strides):
+            raise ValueError(f"{type(self).__name__}: {len(feats)} feature maps for {len(self.featmap_strides)} strides")
+        if feats[0].shape[1] != self.out_channels:
+            raise ValueError(f"{type(self).__name__}: {feats[0].shape[1]} channels, out_channels = {self.out_channels}")
+        return feats, [1.0 / s for s in self.featmap_strides]
+
+    def extra_repr(self):
+        return (f"out_size={self.out_size}, sample_num={self.sample_num}, featmap_strides={self.featmap_strides}, out_channels={self.out_channels}, "
+                f"finest_scale={self.finest_scale}")
 
 
 def roi_align_rotated(features: Tensor, rois: Tensor, out_size, spatial_scale: float, sample_num: int = 0, aligned: bool = True) -> Tensor:
     """The reference's ``roi_align_rotated(features, rois, out_size, spatial_scale, sample_num=0, aligned=True)`` (single level, under autograd).  ``rois`` [R, 6] rows
     ``(batch_index, cx, cy, w, h, theta)`` with theta in RADIANS.  ``sample_num`` keeps the reference's default of 0, which raises here (the adaptive grid is not
     supported): pass 1 .. 4."""
-    return _rroi_apply([features], rois, None, out_size, (spatial_scale,), sample_num, aligned, 56.0, (1.0, 1.0))
+    return _roi_apply(True, [features], rois, None, out_size, (spatial_scale,), sample_num, 56.0, aligned)
 
 
 class RoIAlignRotated(nn.Module):
@@ -174,14 +222,14 @@ class RoIAlignRotated(nn.Module):
         self.sample_num, self.aligned = int(sample_num), aligned
 
     def forward(self, features: Tensor, rois: Tensor) -> Tensor:
-        return roi_align_rotated(features, rois, self.out_size, self.spatial_scale, self.sample_num, self.aligned)          # (_rroi_apply checks the [R, 6] shape)
+        return roi_align_rotated(features, rois, self.out_size, self.spatial_scale, self.sample_num, self.aligned)          # (_roi_apply checks the [R, 6] shape)
 
     def __repr__(self) -> str:
         fields = [f"out_size={self.out_size}", f"spatial_scale={self.spatial_scale}", f"sample_num={self.sample_num}", f"aligned={self.aligned}"]
         return type(self).__name__ + "(" + "".join(f"\n    {f}," for f in fields)
 
 
-class RotatedRoIExtractor(nn.Module):
+class RotatedRoIExtractor(_RoIExtractorBase):
     """The OBB single-level RoI extractor of the Oriented R-CNN configs (``roi_layer=dict(type='RoIAlignRotated', out_size=7, sample_num=2)``,
     ``featmap_strides=[4, 8, 16, 32]``, ``extend_factor=(1.4, 1.2)``) as ONE autograd node over all levels.  The level of a RoI is upstream mmdet's ``map_roi_levels``
     on the UN-extended box, ``clamp(floor(log2(sqrt(w h) / finest_scale + 1e-6)), 0, L - 1)``; after that ``w *= extend_factor[0]``, ``h *= extend_factor[1]``.  (The
@@ -190,32 +238,16 @@ class RotatedRoIExtractor(nn.Module):
     eager call per shape."""
 
     def __init__(self, out_size=7, sample_num=2, featmap_strides=(4, 8, 16, 32), out_channels=256, finest_scale=56, extend_factor=(1.4, 1.2), aligned=True):
-        super().__init__()
-        if not 1 <= len(featmap_strides) <= MAX_LEVELS:
-            raise ValueError(f"RotatedRoIExtractor: {len(featmap_strides)} levels outside 1 .. {MAX_LEVELS}")
-        self.out_size = _pair(out_size)
-        self.sample_num = _check_sample_num(sample_num)
-        self.featmap_strides = tuple(featmap_strides)
-        self.out_channels = int(out_channels)
-        self.finest_scale = float(finest_scale)
+        super().__init__(_check_sample_num, out_size, sample_num, featmap_strides, out_channels, finest_scale)
         self.extend_factor = (float(extend_factor[0]), float(extend_factor[1]))
         self.aligned = bool(aligned)
 
-    @property
-    def num_inputs(self):
-        return len(self.featmap_strides)
-
     def forward(self, feats: Sequence[Tensor], rois: Tensor, levels: Optional[Tensor] = None) -> Tensor:
-        feats = list(feats)[:len(self.featmap_strides)]
-        if len(feats) != len(self.featmap_strides):
-            raise ValueError(f"RotatedRoIExtractor: {len(feats)} feature maps for {len(self.featmap_strides)} strides")
-        if feats[0].shape[1] != self.out_channels:
-            raise ValueError(f"RotatedRoIExtractor: {feats[0].shape[1]} channels, out_channels = {self.out_channels}")
-        return _rroi_apply(feats, rois, levels, self.out_size, [1.0 / s for s in self.featmap_strides], self.sample_num, self.aligned, self.finest_scale, self.extend_factor)
+        feats, scales = self._levels(feats)
+        return _roi_apply(True, feats, rois, levels, self.out_size, scales, self.sample_num, self.finest_scale, self.aligned, self.extend_factor)
 
     def extra_repr(self):
-        return (f"out_size={self.out_size}, sample_num={self.sample_num}, featmap_strides={self.featmap_strides}, out_channels={self.out_channels}, "
-                f"finest_scale={self.finest_scale}, extend_factor={self.extend_factor}, aligned={self.aligned}")
+        return super().extra_repr() + f", extend_factor={self.extend_factor}, aligned={self.aligned}"
 
 
 # -------------------------------------------------------------------------------------------
@@ -224,8 +256,13 @@ class RotatedRoIExtractor(nn.Module):
 def map_roi_levels(rois, num_levels: int, finest_scale: float = 56.0):
     """Upstream mmdet's rule on [R, 6] rois (numpy, float64): ``clamp(floor(log2(sqrt(w h) / finest_scale + 1e-6)), 0, L - 1)``."""
     rois = np.asarray(rois, dtype=np.float64)
+    return _level_rule(lambda: rois[:, 3] * rois[:, 4], num_levels, finest_scale)
+
+
+def _level_rule(area, num_levels: int, finest_scale: float):
+    """The level of the boxes of ``area()`` (numpy, float64); NaN gives level 0"""
     with np.errstate(divide="ignore", invalid="ignore"):
-        lv = np.floor(np.log2(np.sqrt(rois[:, 3] * rois[:, 4]) / finest_scale + 1e-6))
+        lv = np.floor(np.log2(np.sqrt(area()) / finest_scale + 1e-6))
     return np.clip(np.nan_to_num(lv, nan=0.0, neginf=0.0, posinf=float(num_levels - 1)), 0, num_levels - 1).astype(np.int64)
 
 
@@ -457,23 +494,27 @@ def reference_obb_nms(boxes, scores, iou_thr: float, groups=None, score_thr=None
     score_thr`` (default -inf: NaN and -inf scores are none) and min(w, h) >= 0.001; ranks by descending score, ties by ascending index; a kept box suppresses the
     lower-ranked candidates of its group with ``IoU > iou_thr``.  Returns the kept original indices in rank order (int64), at most ``max_num``."""
     b = _obb_np(boxes, "boxes")
+    with np.errstate(invalid="ignore"):
+        shape_ok = np.isfinite(b).all(1) & (b[:, 2] >= OBB_MIN_SIDE) & (b[:, 3] >= OBB_MIN_SIDE)
+    return _reference_greedy(shape_ok, scores, iou_thr, groups, score_thr, max_num, reference_obb_overlaps(b, b) if iou is None else iou)
+
+
+def _reference_greedy(shape_ok, scores, iou_thr: float, groups, score_thr, max_num, iou) -> np.ndarray:
+    """The greedy float64 loop of both NMS oracles.  ``shape_ok``: the boxes that may be candidates at all (the box type's rule); ``iou``: the [N, N] matrix."""
     s = scores.detach().double().cpu().numpy() if isinstance(scores, torch.Tensor) else np.asarray(scores, dtype=np.float64)
-    N = len(b)
+    N = len(shape_ok)
     g = np.zeros(N, dtype=np.int64) if groups is None else (groups.cpu().numpy() if isinstance(groups, torch.Tensor) else np.asarray(groups)).astype(np.int64)
     thr = -np.inf if score_thr is None else float(score_thr)
     with np.errstate(invalid="ignore"):
-        cand = (s > thr) & np.isfinite(b).all(1) & (b[:, 2] >= OBB_MIN_SIDE) & (b[:, 3] >= OBB_MIN_SIDE)
-    if iou is None:
-        iou = reference_obb_overlaps(b, b)
-    order = np.argsort(-np.where(np.isnan(s), -np.inf, s), kind="stable")
-    alive = cand.copy()
-    keep = []
-    for i in order:
-        if not alive[i]:
-            continue
-        keep.append(i)
-        alive[i] = False
-        alive &= ~((iou[i] > iou_thr) & (g == g[i]))
+        alive = (s > thr) & shape_ok
+        order = np.argsort(-np.where(np.isnan(s), -np.inf, s), kind="stable")
+        keep = []
+        for i in order:
+            if not alive[i]:
+                continue
+            keep.append(i)
+            alive[i] = False
+            alive &= ~((iou[i] > iou_thr) & (g == g[i]))          # (a NaN quotient: no)
     keep = np.asarray(keep, dtype=np.int64)
     return keep if not max_num else keep[:int(max_num)]
 
@@ -497,14 +538,20 @@ def obb_nms_torch(boxes: Tensor, scores: Tensor, iou_thr: float, groups: Optiona
                   max_num: Optional[int] = None) -> Tensor:
     """The stock formulation of rotated NMS: sort, the fp32 IoU matrix of the sorted boxes (``obb_overlaps_torch``), the suppression mask copied to the host and the
     greedy scan there -- what the reference's CUDA path does with its N x N / 64 mask.  Returns the kept original indices (int64, on the boxes' device)."""
+    return _nms_torch(boxes, scores, groups, score_thr, max_num, 5, lambda b: (b[:, 2] >= OBB_MIN_SIDE) & (b[:, 3] >= OBB_MIN_SIDE), lambda b: obb_overlaps_torch(b, b) > iou_thr)
+
+
+def _nms_torch(boxes: Tensor, scores: Tensor, groups: Optional[Tensor], score_thr, max_num, cols: int, shape_ok, suppresses) -> Tensor:
+    """Both stock formulations: sort, the candidates (``shape_ok(b)``: the box type's rule, finiteness apart), the fp32 mask ``suppresses(b)`` of the sorted boxes, and
+    the greedy scan on the host."""
     N = boxes.shape[0]
     if N == 0:
         return torch.zeros(0, dtype=torch.int64, device=boxes.device)
     thr = -math.inf if score_thr is None else float(score_thr)
     order = torch.sort(scores, descending=True, stable=True)[1]
-    b, s = boxes[order, :5], scores[order]
-    cand = (s > thr) & (b[:, 2] >= OBB_MIN_SIDE) & (b[:, 3] >= OBB_MIN_SIDE) & torch.isfinite(b).all(1)
-    mask = obb_overlaps_torch(b, b) > iou_thr
+    b, s = boxes[order, :cols], scores[order]
+    cand = (s > thr) & shape_ok(b) & torch.isfinite(b).all(1)
+    mask = suppresses(b)
     if groups is not None:
         g = groups[order]
         mask &= g[:, None] == g[None, :]
@@ -565,11 +612,17 @@ def obb_nms_padded(boxes: Tensor, scores: Tensor, iou_thr: float, groups: Option
 def obb_nms(dets, iou_thr: float, device_id=None):
     """The reference's ``obb_nms(dets, iou_thr, device_id=None) -> (dets[inds], inds)``: ``dets`` [N, 6] rows ``(cx, cy, w, h, theta, score)``, a tensor on the GPU or
     a numpy array (moved to ``cuda:device_id``, the current device by default; numpy out).  One synchronisation, for the dynamic length."""
+    return _nms_dets("obb_nms", ops.obb_nms, "cx, cy, w, h, theta, score", dets, iou_thr, device_id)
+
+
+def _nms_dets(name: str, op, fields: str, dets, iou_thr: float, device_id):
+    """The reference's dets form of both NMS kinds: the score is the last of the ``fields``"""
+    cols = fields.count(",") + 1
     is_numpy = isinstance(dets, np.ndarray)
     if not is_numpy and not isinstance(dets, torch.Tensor):
-        raise TypeError(f"dets must be eithr a Tensor or numpy array, but got {type(dets)}")
-    if dets.ndim != 2 or dets.shape[1] != 6:
-        raise ValueError(f"obb_nms: dets must be [N, 6] (cx, cy, w, h, theta, score), got {tuple(dets.shape)}")
+        raise TypeError(f"dets must be either a Tensor or numpy array, but got {type(dets)}")
+    if dets.ndim != 2 or dets.shape[1] != cols:
+        raise ValueError(f"{name}: dets must be [N, {cols}] ({fields}), got {tuple(dets.shape)}")
     if dets.shape[0] == 0:
         inds = np.zeros(0, dtype=np.int64) if is_numpy else dets.new_zeros(0, dtype=torch.int64)
         return dets[inds, :], inds
@@ -577,11 +630,24 @@ def obb_nms(dets, iou_thr: float, device_id=None):
         t = torch.from_numpy(dets).float().to(torch.device("cuda", torch.cuda.current_device() if device_id is None else int(device_id)))
     else:
         t = dets.detach().float()
-    keep, count = ops.obb_nms(t, t[:, 5], iou_thr)
+    keep, count = op(t, t[:, cols - 1], iou_thr)
     inds = keep[:int(count.item())]
     if is_numpy:
         inds = inds.cpu().numpy()
     return dets[inds, :], inds
+
+
+def _batched_nms(name: str, op, bboxes: Tensor, scores: Tensor, inds: Tensor, cfg: dict, class_agnostic: bool):
+    """What follows the type and column checks of ``arb_batched_nms`` / ``batched_nms``: ``cfg`` holds ``iou_thr`` and nothing else"""
+    iou_thr = cfg.pop("iou_thr")
+    if cfg:
+        raise TypeError(f"{name}: unexpected nms_cfg entries {sorted(cfg)}")
+    if bboxes.shape[0] == 0:
+        keep = bboxes.new_zeros(0, dtype=torch.int64)
+    else:
+        k, count = op(bboxes.detach().float(), scores.detach().float(), iou_thr, None if class_agnostic else inds.to(torch.int32).contiguous())
+        keep = k[:int(count.item())]
+    return torch.cat([bboxes[keep], scores[keep][:, None]], -1), keep
 
 
 def arb_batched_nms(bboxes: Tensor, scores: Tensor, inds: Tensor, nms_cfg: dict, class_agnostic: bool = False):
@@ -595,71 +661,19 @@ def arb_batched_nms(bboxes: Tensor, scores: Tensor, inds: Tensor, nms_cfg: dict,
     if bboxes.dim() != 2 or bboxes.size(-1) != 5:
         raise NotImplementedError(f"arb_batched_nms: boxes of {bboxes.size(-1)} columns are not supported (only 5: cx, cy, w, h, theta; horizontal 4-column and "
                                   "polygon 8-column boxes are not provided)")
-    iou_thr = cfg.pop("iou_thr")
-    if cfg:
-        raise TypeError(f"arb_batched_nms: unexpected nms_cfg entries {sorted(cfg)}")
-    if bboxes.shape[0] == 0:
-        keep = bboxes.new_zeros(0, dtype=torch.int64)
-    else:
-        k, count = ops.obb_nms(bboxes.detach().float(), scores.detach().float(), iou_thr, None if class_agnostic else inds.to(torch.int32).contiguous())
-        keep = k[:int(count.item())]
-    return torch.cat([bboxes[keep], scores[keep][:, None]], -1), keep
+    return _batched_nms("arb_batched_nms", ops.obb_nms, bboxes, scores, inds, cfg, class_agnostic)
 
 
 # -------------------------------------------------------------------------------------------
 # Horizontal RoIAlign with the adaptive grid (csrc/roi.hip): the reference's roi_align / RoIAlign and the single-level extractor of the Mask R-CNN config
 # -------------------------------------------------------------------------------------------
-ROI_MAX_GRID = 128          # LMV_ROI_MAX_GRID: a RoI whose grid ceil(roi_size / out_size) exceeds it on either axis is invalid (a zero row, no gradient)
-
-
-def _check_roi_sample_num(sample_num: int) -> int:
-    s = int(sample_num)
-    if not 0 <= s <= ROI_MAX_GRID:
-        raise ValueError(f"roi_align: sample_num = {s} outside 0 .. {ROI_MAX_GRID} (0: the adaptive grid)")
-    return s
-
-
-class _RoiFn(torch.autograd.Function):
-    """ONE node over all levels: forward = plan + forward launch, backward = one launch that writes every level's gradient once."""
-
-    @staticmethod
-    def forward(ctx, rois, levels, cfg, *feats):
-        out_size, scales, sample_num, finest_scale = cfg
-        feats = list(feats)
-        plan = ops.roi_plan(rois, [f.shape[-2:] for f in feats], scales, feats[0].shape[0], out_size, sample_num, levels, finest_scale)
-        out = ops.roi_align_fwd(feats, plan)
-        ctx.plan = plan
-        ctx.meta = [(tuple(f.shape), tuple(f.stride()), f.dtype, f.device) for f in feats]
-        return out
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, grad_out):
-        if not any(ctx.needs_input_grad[3:]):
-            return (None, None, None) + (None,) * len(ctx.meta)
-        dx = [torch.empty_strided(shape, stride, dtype=dtype, device=device) if ops.strides_injective(shape, stride) else torch.empty(shape, dtype=dtype, device=device)
-              for shape, stride, dtype, device in ctx.meta]
-        ops.roi_align_bwd(grad_out.contiguous(), ctx.plan, dx, dx=dx)
-        return (None, None, None) + tuple(dx)
-
-
-def _roi_apply(feats: Sequence[Tensor], rois: Tensor, levels: Optional[Tensor], out_size, scales, sample_num, finest_scale) -> Tensor:
-    if rois.dim() != 2 or rois.size(1) != 5:
-        raise ValueError(f"roi_align: rois must be [R, 5] (batch_index, x1, y1, x2, y2), got {tuple(rois.shape)}")
-    if rois.requires_grad:
-        raise RuntimeError("roi_align: there is no gradient for the RoIs (detach them)")
-    oh, ow = _pair(out_size)
-    cfg = ((int(oh), int(ow)), tuple(float(s) for s in scales), _check_roi_sample_num(sample_num), float(finest_scale))
-    return _RoiFn.apply(rois.detach().float().contiguous(), levels, cfg, *feats)
-
-
 def roi_align(features: Tensor, rois: Tensor, out_size, spatial_scale: float, sample_num: int = 0, aligned: bool = True) -> Tensor:
     """The reference's ``roi_align(features, rois, out_size, spatial_scale, sample_num=0, aligned=True)`` (single level, under autograd).  ``rois`` [R, 5] rows
     ``(batch_index, x1, y1, x2, y2)``.  ``sample_num=0`` is the adaptive grid ``ceil(roi_size / out_size)`` per RoI and per axis.  ``aligned=False`` (the reference's
     legacy GPU-only "v1" arithmetic, which its Mask R-CNN config does not use) raises ``NotImplementedError``."""
     if not aligned:
         raise NotImplementedError("roi_align: aligned=False (the reference's legacy 'v1' kernel) is not provided")
-    return _roi_apply([features], rois, None, out_size, (spatial_scale,), sample_num, 56.0)
+    return _roi_apply(False, [features], rois, None, out_size, (spatial_scale,), sample_num, 56.0)
 
 
 class RoIAlign(nn.Module):
@@ -683,7 +697,7 @@ class RoIAlign(nn.Module):
         return type(self).__name__ + "(" + "".join(f"\n    {f}," for f in fields) + f"\n    aligned={self.aligned})"
 
 
-class RoIExtractor(nn.Module):
+class RoIExtractor(_RoIExtractorBase):
     """The single-level RoI extractor of the Mask R-CNN config (``roi_layer=dict(type='RoIAlign', out_size=7 | 14, sample_num=0)``, ``featmap_strides=[4, 8, 16, 32]``) as
     ONE autograd node over all levels.  The level of a RoI is upstream mmdet's ``SingleRoIExtractor.map_roi_levels``,
     ``clamp(floor(log2(sqrt((x2 - x1)(y2 - y1)) / finest_scale + 1e-6)), 0, L - 1)`` (the extractor's source is not part of the reference tree: this restates upstream);
@@ -691,39 +705,18 @@ class RoIExtractor(nn.Module):
     nothing, and is capturable after one eager call per shape."""
 
     def __init__(self, out_size=7, sample_num=0, featmap_strides=(4, 8, 16, 32), out_channels=256, finest_scale=56):
-        super().__init__()
-        if not 1 <= len(featmap_strides) <= MAX_LEVELS:
-            raise ValueError(f"RoIExtractor: {len(featmap_strides)} levels outside 1 .. {MAX_LEVELS}")
-        self.out_size = _pair(out_size)
-        self.sample_num = _check_roi_sample_num(sample_num)
-        self.featmap_strides = tuple(featmap_strides)
-        self.out_channels = int(out_channels)
-        self.finest_scale = float(finest_scale)
-
-    @property
-    def num_inputs(self):
-        return len(self.featmap_strides)
+        super().__init__(_check_roi_sample_num, out_size, sample_num, featmap_strides, out_channels, finest_scale)
 
     def forward(self, feats: Sequence[Tensor], rois: Tensor, levels: Optional[Tensor] = None) -> Tensor:
-        feats = list(feats)[:len(self.featmap_strides)]
-        if len(feats) != len(self.featmap_strides):
-            raise ValueError(f"RoIExtractor: {len(feats)} feature maps for {len(self.featmap_strides)} strides")
-        if feats[0].shape[1] != self.out_channels:
-            raise ValueError(f"RoIExtractor: {feats[0].shape[1]} channels, out_channels = {self.out_channels}")
-        return _roi_apply(feats, rois, levels, self.out_size, [1.0 / s for s in self.featmap_strides], self.sample_num, self.finest_scale)
-
-    def extra_repr(self):
-        return (f"out_size={self.out_size}, sample_num={self.sample_num}, featmap_strides={self.featmap_strides}, out_channels={self.out_channels}, "
-                f"finest_scale={self.finest_scale}")
+        feats, scales = self._levels(feats)
+        return _roi_apply(False, feats, rois, levels, self.out_size, scales, self.sample_num, self.finest_scale)
 
 
 def map_roi_levels_xyxy(rois, num_levels: int, finest_scale: float = 56.0):
     """Upstream mmdet's rule on [R, 5] rois ``(batch_index, x1, y1, x2, y2)`` (numpy, float64): ``clamp(floor(log2(sqrt((x2 - x1)(y2 - y1)) / finest_scale + 1e-6)), 0,
     L - 1)``; NaN gives level 0."""
     rois = np.asarray(rois, dtype=np.float64).reshape(-1, 5)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        lv = np.floor(np.log2(np.sqrt((rois[:, 3] - rois[:, 1]) * (rois[:, 4] - rois[:, 2])) / finest_scale + 1e-6))
-    return np.clip(np.nan_to_num(lv, nan=0.0, neginf=0.0, posinf=float(num_levels - 1)), 0, num_levels - 1).astype(np.int64)
+    return _level_rule(lambda: (rois[:, 3] - rois[:, 1]) * (rois[:, 4] - rois[:, 2]), num_levels, finest_scale)
 
 
 def reference_roi_geometry(roi, spatial_scale: float, out_size, sample_num: int):
@@ -909,57 +902,22 @@ def reference_nms(boxes, scores, iou_thr: float, groups=None, score_thr=None, ma
     (default -inf: NaN and -inf scores are none) and four finite coordinates; ranks by descending score, ties by ascending index; a kept box suppresses the
     lower-ranked candidates of its group with a quotient ``> iou_thr`` (NaN: no).  Returns the kept original indices in rank order (int64), at most ``max_num``."""
     b = _hb_np(boxes, "boxes")
-    s = scores.detach().double().cpu().numpy() if isinstance(scores, torch.Tensor) else np.asarray(scores, dtype=np.float64)
-    N = len(b)
-    g = np.zeros(N, dtype=np.int64) if groups is None else (groups.cpu().numpy() if isinstance(groups, torch.Tensor) else np.asarray(groups)).astype(np.int64)
-    thr = -np.inf if score_thr is None else float(score_thr)
-    with np.errstate(invalid="ignore"):
-        cand = (s > thr) & np.isfinite(b).all(1)
-    if iou is None:
-        iou = reference_nms_overlaps(np.where(np.isfinite(b), b, 0.0))
-    order = np.argsort(-np.where(np.isnan(s), -np.inf, s), kind="stable")
-    alive = cand.copy()
-    keep = []
-    with np.errstate(invalid="ignore"):
-        for i in order:
-            if not alive[i]:
-                continue
-            keep.append(i)
-            alive[i] = False
-            alive &= ~((iou[i] > iou_thr) & (g == g[i]))
-    keep = np.asarray(keep, dtype=np.int64)
-    return keep if not max_num else keep[:int(max_num)]
+    return _reference_greedy(np.isfinite(b).all(1), scores, iou_thr, groups, score_thr, max_num,
+                             reference_nms_overlaps(np.where(np.isfinite(b), b, 0.0)) if iou is None else iou)
 
 
 def nms_torch(boxes: Tensor, scores: Tensor, iou_thr: float, groups: Optional[Tensor] = None, score_thr: Optional[float] = None,
               max_num: Optional[int] = None) -> Tensor:
     """The stock formulation: sort, the fp32 quotient matrix of the sorted boxes by broadcasting, the suppression mask copied to the host and the greedy scan there --
     what the reference's CUDA path does with its N x N / 64 mask.  Returns the kept original indices (int64, on the boxes' device)."""
-    N = boxes.shape[0]
-    if N == 0:
-        return torch.zeros(0, dtype=torch.int64, device=boxes.device)
-    thr = -math.inf if score_thr is None else float(score_thr)
-    order = torch.sort(scores, descending=True, stable=True)[1]
-    b, s = boxes[order, :4], scores[order]
-    cand = (s > thr) & torch.isfinite(b).all(1)
-    area = (b[:, 2] - b[:, 0]) * (b[:, 3] - b[:, 1])
-    w = (torch.minimum(b[:, None, 2], b[None, :, 2]) - torch.maximum(b[:, None, 0], b[None, :, 0])).clamp(min=0)
-    h = (torch.minimum(b[:, None, 3], b[None, :, 3]) - torch.maximum(b[:, None, 1], b[None, :, 1])).clamp(min=0)
-    inter = w * h
-    mask = inter / (area[:, None] + area[None, :] - inter) > iou_thr
-    if groups is not None:
-        g = groups[order]
-        mask &= g[:, None] == g[None, :]
-    mask_h, cand_h = mask.cpu().numpy(), cand.cpu().numpy()          # the synchronisation and the copy the reference pays per call
-    removed = ~cand_h
-    keep = []
-    for i in range(N):
-        if removed[i]:
-            continue
-        keep.append(i)
-        removed[i + 1:] |= mask_h[i, i + 1:]
-    keep = order[torch.as_tensor(keep, dtype=torch.int64, device=boxes.device)]
-    return keep if not max_num else keep[:int(max_num)]
+    def suppresses(b):
+        area = (b[:, 2] - b[:, 0]) * (b[:, 3] - b[:, 1])
+        w = (torch.minimum(b[:, None, 2], b[None, :, 2]) - torch.maximum(b[:, None, 0], b[None, :, 0])).clamp(min=0)
+        h = (torch.minimum(b[:, None, 3], b[None, :, 3]) - torch.maximum(b[:, None, 1], b[None, :, 1])).clamp(min=0)
+        inter = w * h
+        return inter / (area[:, None] + area[None, :] - inter) > iou_thr
+
+    return _nms_torch(boxes, scores, groups, score_thr, max_num, 4, lambda b: True, suppresses)
 
 
 def nms_padded(boxes: Tensor, scores: Tensor, iou_thr: float, groups: Optional[Tensor] = None, score_thr: Optional[float] = None,
@@ -978,23 +936,7 @@ def nms_padded(boxes: Tensor, scores: Tensor, iou_thr: float, groups: Optional[T
 def nms(dets, iou_thr: float, device_id=None):
     """The reference's ``nms(dets, iou_thr, device_id=None) -> (dets[inds], inds)``: ``dets`` [N, 5] rows ``(x1, y1, x2, y2, score)``, a tensor on the GPU or a numpy
     array (moved to ``cuda:device_id``, the current device by default -- there is no CPU path; numpy out).  One synchronisation, for the dynamic length."""
-    is_numpy = isinstance(dets, np.ndarray)
-    if not is_numpy and not isinstance(dets, torch.Tensor):
-        raise TypeError(f"dets must be either a Tensor or numpy array, but got {type(dets)}")
-    if dets.ndim != 2 or dets.shape[1] != 5:
-        raise ValueError(f"nms: dets must be [N, 5] (x1, y1, x2, y2, score), got {tuple(dets.shape)}")
-    if dets.shape[0] == 0:
-        inds = np.zeros(0, dtype=np.int64) if is_numpy else dets.new_zeros(0, dtype=torch.int64)
-        return dets[inds, :], inds
-    if is_numpy:
-        t = torch.from_numpy(dets).float().to(torch.device("cuda", torch.cuda.current_device() if device_id is None else int(device_id)))
-    else:
-        t = dets.detach().float()
-    keep, count = ops.nms(t, t[:, 4], iou_thr)
-    inds = keep[:int(count.item())]
-    if is_numpy:
-        inds = inds.cpu().numpy()
-    return dets[inds, :], inds
+    return _nms_dets("nms", ops.nms, "x1, y1, x2, y2, score", dets, iou_thr, device_id)
 
 
 def batched_nms(bboxes: Tensor, scores: Tensor, inds: Tensor, nms_cfg: dict, class_agnostic: bool = False):
@@ -1008,15 +950,7 @@ def batched_nms(bboxes: Tensor, scores: Tensor, inds: Tensor, nms_cfg: dict, cla
         raise NotImplementedError(f"batched_nms: type={nms_type!r} is not supported (only 'nms'; soft_nms and nms_match are not provided)")
     if bboxes.dim() != 2 or bboxes.size(-1) != 4:
         raise ValueError(f"batched_nms: boxes must be [N, 4] (x1, y1, x2, y2), got {tuple(bboxes.shape)}")
-    iou_thr = cfg.pop("iou_thr")
-    if cfg:
-        raise TypeError(f"batched_nms: unexpected nms_cfg entries {sorted(cfg)}")
-    if bboxes.shape[0] == 0:
-        keep = bboxes.new_zeros(0, dtype=torch.int64)
-    else:
-        k, count = ops.nms(bboxes.detach().float(), scores.detach().float(), iou_thr, None if class_agnostic else inds.to(torch.int32).contiguous())
-        keep = k[:int(count.item())]
-    return torch.cat([bboxes[keep], scores[keep][:, None]], -1), keep
+    return _batched_nms("batched_nms", ops.nms, bboxes, scores, inds, cfg, class_agnostic)
 
 
 def soft_nms(dets, iou_thr, method="linear", sigma=0.5, min_score=1e-3):

@@ -1272,13 +1272,16 @@ def dense_slide_fwd(window_logits: Tensor, ys: Sequence[int], xs: Sequence[int],
 # -------------------------------------------------------------------------------------------
 # Rotated RoIAlign over a feature pyramid (csrc/rroi.hip; lemevit_amd/detection.py has the autograd nodes)
 # -------------------------------------------------------------------------------------------
-class RroiPlan:
-    """The plan of one ``rroi_plan`` call: ``buf`` (uint8, lmv_rroi_plan_bytes) and the geometry it was made for, which ``rroi_align_fwd`` / ``rroi_align_bwd``
-    hand back to the library unchanged."""
+class RoiPlan:
+    """The plan of one ``rroi_plan`` / ``roi_plan`` call: ``buf`` (uint8, lmv_rroi_plan_bytes / lmv_roi_plan_bytes) and the geometry it was made for, which the
+    operator's ``*_align_fwd`` / ``*_align_bwd`` hand back to the library unchanged."""
     __slots__ = ("buf", "R", "B", "sizes", "oh", "ow", "sample_num")
 
     def __init__(self, buf, R, B, sizes, oh, ow, sample_num):
         self.buf, self.R, self.B, self.sizes, self.oh, self.ow, self.sample_num = buf, R, B, sizes, oh, ow, sample_num
+
+
+RroiPlan = RoiPlan
 
 
 def rroi_plan_bytes(R: int, out_size: Tuple[int, int], sample_num: int) -> int:
@@ -1302,10 +1305,11 @@ def strides_injective(shape, stride) -> bool:
     return True
 
 
-def _rroi_levels(fn: str, maps: Optional[Sequence[Tensor]], sizes: Sequence[Tuple[int, int]], scales: Optional[Sequence[float]]):
+def _roi_levels(fn: str, maps: Optional[Sequence[Tensor]], sizes: Sequence[Tuple[int, int]], scales: Optional[Sequence[float]]):
+    """The level table of both RoIAlign operators (lmv_roi_level is lmv_rroi_level)"""
     L = len(sizes)
-    if not 1 <= L <= _lib.RROI_MAX_LEVELS:
-        raise ValueError(f"{fn}: {L} levels outside 1 .. {_lib.RROI_MAX_LEVELS}")
+    if not 1 <= L <= _lib.ROI_MAX_LEVELS:
+        raise ValueError(f"{fn}: {L} levels outside 1 .. {_lib.ROI_MAX_LEVELS}")
     arr = (_lib.RroiLevel * L)()
     for l in range(L):
         arr[l].H, arr[l].W = int(sizes[l][0]), int(sizes[l][1])
@@ -1317,7 +1321,7 @@ def _rroi_levels(fn: str, maps: Optional[Sequence[Tensor]], sizes: Sequence[Tupl
     return arr
 
 
-def _rroi_maps(fn: str, maps: Sequence[Tensor], plan: RroiPlan, what: str):
+def _roi_maps(fn: str, maps: Sequence[Tensor], plan: RoiPlan, what: str):
     """The checks of the level tensors of a forward / backward call against the plan; returns (C, dtype code)"""
     if len(maps) != len(plan.sizes):
         raise ValueError(f"{fn}: {len(maps)} {what} for a plan over {len(plan.sizes)} levels")
@@ -1335,6 +1339,35 @@ def _rroi_maps(fn: str, maps: Sequence[Tensor], plan: RroiPlan, what: str):
     return C_, dtype_code(t0)
 
 
+def _align_fwd(fn: str, entry: str, feats: Sequence[Tensor], plan: RoiPlan, out: Optional[Tensor], extra: tuple) -> Tensor:
+    """The forward of both RoIAlign operators: ``entry(plan, R, levels, L, B, C, oh, ow, *extra, dtype, out, stream)``"""
+    C_, code = _roi_maps(fn, feats, plan, "feature maps")
+    shape = (plan.R, C_, plan.oh, plan.ow)
+    if out is None:
+        out = torch.empty(shape, device=feats[0].device, dtype=feats[0].dtype)
+    elif out.dtype != feats[0].dtype or tuple(out.shape) != shape or out.device != feats[0].device or not out.is_contiguous():
+        raise TypeError(f"{fn}: out must be a contiguous {feats[0].dtype} tensor {shape} on the features' device")
+    arr = _roi_levels(fn, feats, plan.sizes, None)
+    check(getattr(lib, entry)(plan.buf.data_ptr(), plan.R, arr, len(plan.sizes), plan.B, C_, plan.oh, plan.ow, *extra, code, out.data_ptr(), _stream()), entry)
+    return out
+
+
+def _align_bwd(fn: str, entry: str, grad_out: Tensor, plan: RoiPlan, like: Sequence[Tensor], dx: Optional[Sequence[Tensor]], extra: tuple) -> List[Tensor]:
+    """The backward of both RoIAlign operators: ``entry(plan, R, dy, levels, L, B, C, oh, ow, *extra, dtype, stream)``"""
+    if dx is None:
+        dx = [torch.empty_like(t) for t in like]
+    C_, code = _roi_maps(fn, dx, plan, "gradient maps")
+    for l, t in enumerate(dx):
+        if not strides_injective(t.shape, t.stride()):
+            raise ValueError(f"{fn}: level {l}: a gradient map with strides {tuple(t.stride())} aliases itself (an expanded view): every element must have its own address")
+    shape = (plan.R, C_, plan.oh, plan.ow)
+    if tuple(grad_out.shape) != shape or grad_out.dtype != dx[0].dtype or grad_out.device != dx[0].device or not grad_out.is_contiguous():
+        raise TypeError(f"{fn}: grad_out must be a contiguous {dx[0].dtype} tensor {shape} on the maps' device")
+    arr = _roi_levels(fn, dx, plan.sizes, None)
+    check(getattr(lib, entry)(plan.buf.data_ptr(), plan.R, grad_out.data_ptr(), arr, len(plan.sizes), plan.B, C_, plan.oh, plan.ow, *extra, code, _stream()), entry)
+    return list(dx)
+
+
 def rroi_plan(rois: Tensor, sizes: Sequence[Tuple[int, int]], spatial_scales: Sequence[float], B: int, out_size: Tuple[int, int], sample_num: int,
               aligned: bool = True, levels: Optional[Tensor] = None, finest_scale: float = 56.0, extend_factor: Tuple[float, float] = (1.0, 1.0),
               plan: Optional[Tensor] = None) -> RroiPlan:
@@ -1348,7 +1381,7 @@ def rroi_plan(rois: Tensor, sizes: Sequence[Tuple[int, int]], spatial_scales: Se
         raise ValueError(f"{fn}: {len(spatial_scales)} scales for {len(sizes)} levels")
     R, (oh, ow) = int(rois.shape[0]), (int(out_size[0]), int(out_size[1]))
     sizes = tuple((int(h), int(w)) for h, w in sizes)
-    arr = _rroi_levels(fn, None, sizes, spatial_scales)
+    arr = _roi_levels(fn, None, sizes, spatial_scales)
     if levels is not None and (levels.dtype != torch.int32 or tuple(levels.shape) != (R,) or levels.device != rois.device or not levels.is_contiguous()):
         raise TypeError(f"{fn}: levels must be a contiguous int32 vector [{R}] on the rois' device")
     need = rroi_plan_bytes(R, (oh, ow), sample_num)
@@ -1364,54 +1397,19 @@ def rroi_plan(rois: Tensor, sizes: Sequence[Tuple[int, int]], spatial_scales: Se
 def rroi_align_fwd(feats: Sequence[Tensor], plan: RroiPlan, out: Optional[Tensor] = None) -> Tensor:
     """lmv_rroi_fwd (one launch over all levels): ``feats[l]`` [B, C, H_l, W_l] float32 / bfloat16 in ANY strides (NCHW and channels-last are the fast ones).
     Returns ``out`` [R, C, oh, ow], contiguous, in the features' dtype; every element is written once, rows of invalid RoIs as zeros."""
-    fn = "rroi_align_fwd"
-    C_, code = _rroi_maps(fn, feats, plan, "feature maps")
-    shape = (plan.R, C_, plan.oh, plan.ow)
-    if out is None:
-        out = torch.empty(shape, device=feats[0].device, dtype=feats[0].dtype)
-    elif out.dtype != feats[0].dtype or tuple(out.shape) != shape or out.device != feats[0].device or not out.is_contiguous():
-        raise TypeError(f"{fn}: out must be a contiguous {feats[0].dtype} tensor {shape} on the features' device")
-    arr = _rroi_levels(fn, feats, plan.sizes, None)
-    check(lib.lmv_rroi_fwd(plan.buf.data_ptr(), plan.R, arr, len(plan.sizes), plan.B, C_, plan.oh, plan.ow, plan.sample_num, code, out.data_ptr(), _stream()), "lmv_rroi_fwd")
-    return out
+    return _align_fwd("rroi_align_fwd", "lmv_rroi_fwd", feats, plan, out, (plan.sample_num,))
 
 
 def rroi_align_bwd(grad_out: Tensor, plan: RroiPlan, like: Sequence[Tensor], dx: Optional[Sequence[Tensor]] = None) -> List[Tensor]:
     """lmv_rroi_bwd (one launch over all levels, no atomics): ``grad_out`` [R, C, oh, ow] contiguous; returns ``dx[l]`` in the dtype and layout of ``like[l]`` (the
     forward's feature maps), EVERY element written once -- zeros included, on a level without RoIs and at R = 0.  ``dx``: caller-supplied buffers to write instead.
     A map whose strides let two indices share an address (an expanded view) is refused: one element, one writer."""
-    fn = "rroi_align_bwd"
-    if dx is None:
-        dx = [torch.empty_like(t) for t in like]
-    C_, code = _rroi_maps(fn, dx, plan, "gradient maps")
-    for l, t in enumerate(dx):
-        if not strides_injective(t.shape, t.stride()):
-            raise ValueError(f"{fn}: level {l}: a gradient map with strides {tuple(t.stride())} aliases itself (an expanded view): every element must have its own address")
-    shape = (plan.R, C_, plan.oh, plan.ow)
-    if tuple(grad_out.shape) != shape or grad_out.dtype != dx[0].dtype or grad_out.device != dx[0].device or not grad_out.is_contiguous():
-        raise TypeError(f"{fn}: grad_out must be a contiguous {dx[0].dtype} tensor {shape} on the maps' device")
-    arr = _rroi_levels(fn, dx, plan.sizes, None)
-    check(lib.lmv_rroi_bwd(plan.buf.data_ptr(), plan.R, grad_out.data_ptr(), arr, len(plan.sizes), plan.B, C_, plan.oh, plan.ow, plan.sample_num, code, _stream()), "lmv_rroi_bwd")
-    return list(dx)
+    return _align_bwd("rroi_align_bwd", "lmv_rroi_bwd", grad_out, plan, like, dx, (plan.sample_num,))
 
 
 # -------------------------------------------------------------------------------------------
 # Rotated IoU and rotated NMS (csrc/obb.hip; lemevit_amd/detection.py has the reference's entry points)
 # -------------------------------------------------------------------------------------------
-def _obb_boxes(fn: str, what: str, t: Tensor) -> Tuple[int, int]:
-    """(data pointer, row stride in floats) of a float32 box tensor [N, >= 5] read in place: unit column stride, any row stride >= 5 (``dets[:, :5]`` of a [N, 6] tensor)"""
-    if t.dim() != 2 or t.shape[1] < 5 or t.dtype != torch.float32:
-        raise ValueError(f"{fn}: {what}: float32 [N, >= 5] rows (cx, cy, w, h, theta) expected, got {t.dtype} {tuple(t.shape)}")
-    if not t.is_cuda:
-        raise RuntimeError("lemevit_amd: tensors must be on the GPU (no CPU fallback exists)")
-    n = int(t.shape[0])
-    if n > 1 and (t.stride(1) != 1 or t.stride(0) < 5):
-        raise ValueError(f"{fn}: {what}: strides {tuple(t.stride())}: a unit column stride and a row stride >= 5 are needed (call .contiguous())")
-    if n == 1 and t.stride(1) != 1:
-        raise ValueError(f"{fn}: {what}: strides {tuple(t.stride())}: a unit column stride is needed (call .contiguous())")
-    return t.data_ptr(), (int(t.stride(0)) if n > 1 else max(int(t.stride(0)), 5))
-
-
 def obb_overlaps(boxes1: Tensor, boxes2: Tensor, mode: str = "iou", is_aligned: bool = False, out: Optional[Tensor] = None) -> Tensor:
     """lmv_obb_overlaps (one launch): rotated IoU (``mode='iou'``) or IoF (``'iof'``: intersection over the area of ``boxes1``) of float32 boxes
     ``(cx, cy, w, h, theta)``, theta in radians.  Returns float32 [N, M], or [N, 1] from the N pairs with ``is_aligned``; every element is written once.  ``out``: a
@@ -1419,8 +1417,8 @@ def obb_overlaps(boxes1: Tensor, boxes2: Tensor, mode: str = "iou", is_aligned: 
     fn = "obb_overlaps"
     if mode not in ("iou", "iof"):
         raise ValueError(f"{fn}: mode must be 'iou' or 'iof', got {mode!r}")
-    p1, s1 = _obb_boxes(fn, "boxes1", boxes1)
-    p2, s2 = _obb_boxes(fn, "boxes2", boxes2)
+    p1, s1 = _rows(fn, "boxes1", boxes1, 5, "cx, cy, w, h, theta")
+    p2, s2 = _rows(fn, "boxes2", boxes2, 5, "cx, cy, w, h, theta")
     N, M = int(boxes1.shape[0]), int(boxes2.shape[0])
     if is_aligned and N != M:
         raise ValueError(f"{fn}: aligned pairs need as many boxes on both sides, got {N} and {M}")
@@ -1451,11 +1449,16 @@ def obb_nms(boxes: Tensor, scores: Tensor, iou_thr: float, groups: Optional[Tens
     ``cap = max_num or N``, the original indices of the kept boxes by descending score (ties: the lower index first), then -1; ``count`` int64 [1], the number
     written.  The sort is ``torch.sort(stable=True)`` here (``order``: the caller's, int64 [N]); ``workspace`` (uint8, ``obb_nms_workspace_bytes(N)``), ``keep``
     and ``count`` may be supplied so that a captured call allocates only what the sort does.  ``phases``: 1 / 2 run the mask / reduce launch alone (probes)."""
-    fn = "obb_nms"
-    p, s = _obb_boxes(fn, "boxes", boxes)
+    return _greedy_nms("obb_nms", 5, "cx, cy, w, h, theta", _lib.OBB_NMS_MAX, boxes, scores, iou_thr, groups, score_thr, max_num, order, workspace, keep, count, phases)
+
+
+def _greedy_nms(fn: str, k: int, names: str, max_n: int, boxes: Tensor, scores: Tensor, iou_thr: float, groups, score_thr, max_num, order, workspace, keep, count,
+                phases: int) -> Tuple[Tensor, Tensor]:
+    """``obb_nms`` (fn = 'obb_nms', rows of k = 5) and ``nms`` (fn = 'nms', k = 4): the checks, the sort, the buffers and the call of ``lmv_<fn>``"""
+    p, s = _rows(fn, "boxes", boxes, k, names)
     N, dev = int(boxes.shape[0]), boxes.device
-    if N > _lib.OBB_NMS_MAX:
-        raise ValueError(f"{fn}: N = {N} boxes, at most {_lib.OBB_NMS_MAX}")
+    if N > max_n:
+        raise ValueError(f"{fn}: N = {N} boxes, at most {max_n}")
     if scores.dtype != torch.float32 or tuple(scores.shape) != (N,) or scores.device != dev:
         raise ValueError(f"{fn}: float32 scores [{N}] on the boxes' device expected, got {scores.dtype} {tuple(scores.shape)}")
     scores = scores.contiguous()
@@ -1469,11 +1472,11 @@ def obb_nms(boxes: Tensor, scores: Tensor, iou_thr: float, groups: Optional[Tens
     elif order.dtype != torch.int64 or tuple(order.shape) != (N,) or order.device != dev or not order.is_contiguous():
         raise TypeError(f"{fn}: order must be a contiguous int64 vector [{N}] on the boxes' device")
     cap = max_num if max_num > 0 else N
-    need = obb_nms_workspace_bytes(N)
+    need = int(getattr(lib, f"lmv_{fn}_workspace_bytes")(N))
     if workspace is None:
         workspace = torch.empty((max(need, 8),), device=dev, dtype=torch.uint8)
     elif workspace.dtype != torch.uint8 or workspace.device != dev or not workspace.is_contiguous() or workspace.numel() < need:
-        raise ValueError(f"{fn}: the workspace must hold {need} bytes (uint8) on the boxes' device (ops.obb_nms_workspace_bytes)")
+        raise ValueError(f"{fn}: the workspace must hold {need} bytes (uint8) on the boxes' device (ops.{fn}_workspace_bytes)")
     if keep is None:
         keep = torch.empty((cap,), device=dev, dtype=torch.int64)
     elif keep.dtype != torch.int64 or tuple(keep.shape) != (cap,) or keep.device != dev or not keep.is_contiguous():
@@ -1482,29 +1485,14 @@ def obb_nms(boxes: Tensor, scores: Tensor, iou_thr: float, groups: Optional[Tens
         count = torch.empty((1,), device=dev, dtype=torch.int64)
     elif count.dtype != torch.int64 or count.numel() != 1 or count.device != dev:
         raise TypeError(f"{fn}: count must be one int64 on the boxes' device")
-    check(lib.lmv_obb_nms(p, s, scores.data_ptr(), order.data_ptr(), _ptr(groups), N, float(iou_thr), -math.inf if score_thr is None else float(score_thr), max_num,
-                          int(phases), workspace.data_ptr(), workspace.numel(), keep.data_ptr(), count.data_ptr(), _stream()), "lmv_obb_nms")
+    check(getattr(lib, f"lmv_{fn}")(p, s, scores.data_ptr(), order.data_ptr(), _ptr(groups), N, float(iou_thr), -math.inf if score_thr is None else float(score_thr), max_num,
+                                    int(phases), workspace.data_ptr(), workspace.numel(), keep.data_ptr(), count.data_ptr(), _stream()), f"lmv_{fn}")
     return keep, count
 
 
 # -------------------------------------------------------------------------------------------
 # Horizontal RoIAlign over a feature pyramid, adaptive grid included (csrc/roi.hip; lemevit_amd/detection.py has the autograd nodes)
 # -------------------------------------------------------------------------------------------
-class RoiPlan:
-    """The plan of one ``roi_plan`` call: ``buf`` (uint8, lmv_roi_plan_bytes) and the geometry it was made for, which ``roi_align_fwd`` / ``roi_align_bwd`` hand back
-    to the library unchanged."""
-    __slots__ = ("buf", "R", "B", "sizes", "oh", "ow", "sample_num")
-
-    def __init__(self, buf, R, B, sizes, oh, ow, sample_num):
-        self.buf, self.R, self.B, self.sizes, self.oh, self.ow, self.sample_num = buf, R, B, sizes, oh, ow, sample_num
-
-
-def _roi_levels(fn: str, maps: Optional[Sequence[Tensor]], sizes: Sequence[Tuple[int, int]], scales: Optional[Sequence[float]]):
-    if not 1 <= len(sizes) <= _lib.ROI_MAX_LEVELS:
-        raise ValueError(f"{fn}: {len(sizes)} levels outside 1 .. {_lib.ROI_MAX_LEVELS}")
-    return _rroi_levels(fn, maps, sizes, scales)          # (the same level record)
-
-
 def roi_plan_bytes(R: int, sizes: Sequence[Tuple[int, int]], out_size: Tuple[int, int]) -> int:
     """lmv_roi_plan_bytes: the bytes of a plan for ``R`` RoIs over maps of ``sizes[l] = (H_l, W_l)``: per RoI 48 + 16 (oh + ow) + 4 (max H + 2 oh + max W + 2 ow),
     rounded up to 16 -- bounded by the maps, whatever the sampling grid."""
@@ -1547,35 +1535,14 @@ def roi_plan(rois: Tensor, sizes: Sequence[Tuple[int, int]], spatial_scales: Seq
 def roi_align_fwd(feats: Sequence[Tensor], plan: RoiPlan, out: Optional[Tensor] = None) -> Tensor:
     """lmv_roi_fwd (one launch over all levels): ``feats[l]`` [B, C, H_l, W_l] float32 / bfloat16 in ANY strides (NCHW and channels-last are the fast ones).
     Returns ``out`` [R, C, oh, ow], contiguous, in the features' dtype; every element is written once, rows of invalid RoIs as zeros."""
-    fn = "roi_align_fwd"
-    C_, code = _rroi_maps(fn, feats, plan, "feature maps")
-    shape = (plan.R, C_, plan.oh, plan.ow)
-    if out is None:
-        out = torch.empty(shape, device=feats[0].device, dtype=feats[0].dtype)
-    elif out.dtype != feats[0].dtype or tuple(out.shape) != shape or out.device != feats[0].device or not out.is_contiguous():
-        raise TypeError(f"{fn}: out must be a contiguous {feats[0].dtype} tensor {shape} on the features' device")
-    arr = _roi_levels(fn, feats, plan.sizes, None)
-    check(lib.lmv_roi_fwd(plan.buf.data_ptr(), plan.R, arr, len(plan.sizes), plan.B, C_, plan.oh, plan.ow, code, out.data_ptr(), _stream()), "lmv_roi_fwd")
-    return out
+    return _align_fwd("roi_align_fwd", "lmv_roi_fwd", feats, plan, out, ())
 
 
 def roi_align_bwd(grad_out: Tensor, plan: RoiPlan, like: Sequence[Tensor], dx: Optional[Sequence[Tensor]] = None) -> List[Tensor]:
     """lmv_roi_bwd (one launch over all levels, no atomics): ``grad_out`` [R, C, oh, ow] contiguous; returns ``dx[l]`` in the dtype and layout of ``like[l]`` (the
     forward's feature maps), EVERY element written once -- zeros included, on a level without RoIs and at R = 0.  ``dx``: caller-supplied buffers to write instead.
     A map whose strides let two indices share an address (an expanded view) is refused: one element, one writer."""
-    fn = "roi_align_bwd"
-    if dx is None:
-        dx = [torch.empty_like(t) for t in like]
-    C_, code = _rroi_maps(fn, dx, plan, "gradient maps")
-    for l, t in enumerate(dx):
-        if not strides_injective(t.shape, t.stride()):
-            raise ValueError(f"{fn}: level {l}: a gradient map with strides {tuple(t.stride())} aliases itself (an expanded view): every element must have its own address")
-    shape = (plan.R, C_, plan.oh, plan.ow)
-    if tuple(grad_out.shape) != shape or grad_out.dtype != dx[0].dtype or grad_out.device != dx[0].device or not grad_out.is_contiguous():
-        raise TypeError(f"{fn}: grad_out must be a contiguous {dx[0].dtype} tensor {shape} on the maps' device")
-    arr = _roi_levels(fn, dx, plan.sizes, None)
-    check(lib.lmv_roi_bwd(plan.buf.data_ptr(), plan.R, grad_out.data_ptr(), arr, len(plan.sizes), plan.B, C_, plan.oh, plan.ow, code, _stream()), "lmv_roi_bwd")
-    return list(dx)
+    return _align_bwd("roi_align_bwd", "lmv_roi_bwd", grad_out, plan, like, dx, ())
 
 
 # -------------------------------------------------------------------------------------------
@@ -1594,46 +1561,7 @@ def nms(boxes: Tensor, scores: Tensor, iou_thr: float, groups: Optional[Tensor] 
     """lmv_nms (two launches, no host round trip): greedy NMS of float32 axis-aligned ``boxes`` [N, >= 4] rows ``(x1, y1, x2, y2)`` (read in place through their row
     stride) with float32 ``scores`` [N]; the arguments, the candidates' score rule and the result ``(keep, count)`` are those of ``obb_nms``.  A kept box suppresses the
     lower-ranked candidates of its group with ``inter / (area_i + area_j - inter) > iou_thr`` in float32 (a NaN quotient suppresses nothing)."""
-    fn = "nms"
-    if boxes.dim() != 2 or boxes.shape[1] < 4 or boxes.dtype != torch.float32:
-        raise ValueError(f"{fn}: boxes: float32 [N, >= 4] rows (x1, y1, x2, y2) expected, got {boxes.dtype} {tuple(boxes.shape)}")
-    if not boxes.is_cuda:
-        raise RuntimeError("lemevit_amd: tensors must be on the GPU (no CPU fallback exists)")
-    N, dev = int(boxes.shape[0]), boxes.device
-    if (N > 0 and boxes.stride(1) != 1) or (N > 1 and boxes.stride(0) < 4):
-        raise ValueError(f"{fn}: boxes: strides {tuple(boxes.stride())}: a unit column stride and a row stride >= 4 are needed (call .contiguous())")
-    s = int(boxes.stride(0)) if N > 1 else max(int(boxes.stride(0)), 4)
-    if N > _lib.NMS_MAX:
-        raise ValueError(f"{fn}: N = {N} boxes, at most {_lib.NMS_MAX}")
-    if scores.dtype != torch.float32 or tuple(scores.shape) != (N,) or scores.device != dev:
-        raise ValueError(f"{fn}: float32 scores [{N}] on the boxes' device expected, got {scores.dtype} {tuple(scores.shape)}")
-    scores = scores.contiguous()
-    if groups is not None and (groups.dtype != torch.int32 or tuple(groups.shape) != (N,) or groups.device != dev or not groups.is_contiguous()):
-        raise TypeError(f"{fn}: groups must be a contiguous int32 vector [{N}] on the boxes' device")
-    max_num = 0 if max_num is None else int(max_num)
-    if max_num < 0:
-        raise ValueError(f"{fn}: max_num = {max_num} < 0")
-    if order is None:
-        order = torch.sort(scores, descending=True, stable=True)[1]
-    elif order.dtype != torch.int64 or tuple(order.shape) != (N,) or order.device != dev or not order.is_contiguous():
-        raise TypeError(f"{fn}: order must be a contiguous int64 vector [{N}] on the boxes' device")
-    cap = max_num if max_num > 0 else N
-    need = nms_workspace_bytes(N)
-    if workspace is None:
-        workspace = torch.empty((max(need, 8),), device=dev, dtype=torch.uint8)
-    elif workspace.dtype != torch.uint8 or workspace.device != dev or not workspace.is_contiguous() or workspace.numel() < need:
-        raise ValueError(f"{fn}: the workspace must hold {need} bytes (uint8) on the boxes' device (ops.nms_workspace_bytes)")
-    if keep is None:
-        keep = torch.empty((cap,), device=dev, dtype=torch.int64)
-    elif keep.dtype != torch.int64 or tuple(keep.shape) != (cap,) or keep.device != dev or not keep.is_contiguous():
-        raise TypeError(f"{fn}: keep must be a contiguous int64 vector [{cap}] on the boxes' device")
-    if count is None:
-        count = torch.empty((1,), device=dev, dtype=torch.int64)
-    elif count.dtype != torch.int64 or count.numel() != 1 or count.device != dev:
-        raise TypeError(f"{fn}: count must be one int64 on the boxes' device")
-    check(lib.lmv_nms(boxes.data_ptr(), s, scores.data_ptr(), order.data_ptr(), _ptr(groups), N, float(iou_thr), -math.inf if score_thr is None else float(score_thr),
-                      max_num, int(phases), workspace.data_ptr(), workspace.numel(), keep.data_ptr(), count.data_ptr(), _stream()), "lmv_nms")
-    return keep, count
+    return _greedy_nms("nms", 4, "x1, y1, x2, y2", _lib.NMS_MAX, boxes, scores, iou_thr, groups, score_thr, max_num, order, workspace, keep, count, phases)
 
 
 # -------------------------------------------------------------------------------------------

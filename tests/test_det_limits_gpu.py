@@ -1,4 +1,4 @@
-"""The detection operators on the GPU where their own tests do not reach (csrc/nms_reduce.h, csrc/obb.hip, csrc/nms.hip, csrc/assign.hip, csrc/obb_pair.h).
+"""The detection operators on the GPU where their own tests do not reach (csrc/nms_frame.h, csrc/obb.hip, csrc/nms.hip, csrc/assign.hip, csrc/obb_pair.h).
 
 NMS: N = 16 384, 16 383 and 16 321 -- all 256 threads of the reduce workgroup own a word, the last word full, one bit short, and holding one box -- against keep lists
 that factorise over separated clusters; the caller's ``order`` (the default sort itself, entries that name no box, a permutation that is not the score sort); the two
@@ -20,7 +20,7 @@ formulation on the GPU; both against the independent oracle):
     crossed     1.0e-05    1.0e-06               nested      1.7e-05    1.6e-05
 
 Cell by cell (family, mode, layout) the kernel's error is at most 1.8 x E_torch where both are below 1e-6 (bigtheta, iou, matrix: 4.5e-07 against 2.6e-07) and at most
-1.04 x E_torch above that (long, iof, matrix); every cell is inside its bound.  With nms_reduce.h's last thread switched off (``tid < min(nb, 255)``) or
+1.04 x E_torch above that (long, iof, matrix); every cell is inside its bound.  With the last thread of nms_frame.h's reduce launch switched off (``tid < min(nb, 255)``) or
 assign.hip's gather loop cut to one trip, every test of test_obb_gpu.py, test_nms_gpu.py and test_assign_gpu.py still passes and 26 tests of this file fail
 (tried once, by hand; no such build is kept).
 """
