@@ -1200,6 +1200,70 @@ int lmv_rcnn_loss_bwd(const void* cls_score, int64_t cls_stride, const void* bbo
                       int64_t dcls_stride, void* dbbox, int64_t dbbox_stride, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The proposal stage of the oriented RPN head of the Oriented R-CNN configs (csrc/proposal.hip): upstream's OrientedRPNHead.get_bboxes / _get_bboxes_single with
+ * train_cfg.rpn_proposal = test_cfg.rpn = (nms_across_levels=False, nms_pre=2000, nms_post=2000, max_num=2000, nms_thr=0.8, min_bbox_size=0) -- what turns the
+ * head's maps into the proposals that lmv_max_iou_assign, lmv_random_sample and lmv_rroi_plan take.  The head's source is NOT part of the reference tree (only its
+ * name in the configs is): the rules below restate upstream (OBBDetection on mmdet 2.x) and are the specification.  An addition to ABI 14: callers detect it by
+ * symbol.  No host round trip, no floating-point atomics (integer counters only; no value depends on the order in which an atomic lands): two calls agree bit for
+ * bit, the number of launches is fixed by the arguments, and both entry points can be captured.
+ *
+ * lmv_rpn_select -- B images, L <= LMV_RPN_LOSS_MAX_LEVELS levels; three launches and one memset node.
+ *   levels       HOST table of L lmv_rpn_loss_level, read during the call: cls [B, A, H, W] and reg [B, 6 A, H, W] with their four ELEMENT strides (batch, channel,
+ *                row, column), fp32 or bf16 (`dtype`, one for all of a call), read in place: contiguous, channels-last or a channel slice.  dcls / dreg are not read.
+ *   anchors      fp32 [N, 4] shared by all images, rows through anchor_stride >= 4; N = sum_l n_l, n_l = H_l W_l A.  Row r = (h W_l + w) A + a of level l is anchor
+ *                off_l + r, off_l = sum_{l' < l} n_l' -- the element space of lmv_rpn_loss_fwd and the row order of lmv_box_decode_map.
+ *   The selection rule:
+ *     The rank of a row is decided by its LOGIT, not by the rounded sigmoid (the sigmoid is monotone, and fp32 saturation would invent ties).  key = the
+ *     order-preserving 32-bit image of the fp32 logit (bits | 0x80000000 for a non-negative value, ~bits for a negative one; a bf16 logit widens exactly; -0.0
+ *     ranks equal to +0.0; +inf / -inf are ordinary values).  The greater logit first; on a tie the smaller row index first: level l's slots are its rows in
+ *     ascending order of the 64-bit word (~key << 32) | r.  A row with a NaN logit is NOT a candidate -- a deliberate difference from upstream, whose sort puts NaN
+ *     first; it is lmv_obb_nms's own "a NaN score is no candidate".  Upstream's sort is unstable, so its choice among tied scores differs from run to run; this one
+ *     is fixed.  Level l contributes K_l = min(nms_pre, n_l) slots (upstream skips the sort when n_l <= nms_pre; here such a level is ranked all the same); the
+ *     slots past the number of candidates are EMPTY: index -1, a box of zeros, score -inf.  Ktot = sum_l K_l; slot s of level l is element koff_l + s of an image.
+ *   Outputs -- every element is written exactly once, on every call:
+ *     index      int64 [B, Ktot]: the row r within the slot's level, -1 for an empty slot
+ *     groups     int32 [B, Ktot]: the slot's level l (lmv_obb_nms's `groups`: nms_across_levels=False)
+ *     scores     fp32 [B, Ktot]: 1 / (1 + exp(-z)) in fp32; -inf for an empty slot and, with min_bbox_size > 0, for a box that fails (w >= min_bbox_size and
+ *                h >= min_bbox_size) -- lmv_obb_nms then does not take it as a candidate
+ *     boxes      fp32 [B, Ktot, 5]: the midpoint decode (the rule above, kind LMV_CODER_MIDPOINT; means / stds HOST arrays of 6 floats by value; wh_ratio_clip)
+ *                of anchor off_l + r with the six deltas at channels 6 a .. 6 a + 5 of position (h, w): the device function lmv_box_decode_map inlines, so a row has
+ *                the bits that call writes for the same index
+ *     order      int64 [B, Ktot]: the image's slots, as elements 0 .. Ktot - 1, by ascending (~key, level, slot number), empty slots last in element order -- the
+ *                stable descending order of the concatenated levels by logit, and what lmv_obb_nms takes as `order` (with boxes + b Ktot 5, scores + b Ktot,
+ *                groups + b Ktot and N = Ktot, per image).  A slot whose score min_bbox_size turned into -inf keeps its rank; it is no candidate there.
+ *   Workspace: lmv_rpn_select_workspace_bytes(sizes, L, A, B, nms_pre), sizes a HOST array (H_0, W_0, H_1, W_1, ...) = B (5120 + 4 sum_l ceil16(n_l) + 4 Ktot) bytes,
+ *     16-byte aligned, always required; 0 for sizes the call refuses.  It holds the [B, 5, 256] histograms of the top byte of ~key per level, ~key of every row
+ *     (a level's row padded to 16 entries) and ~key of every slot.  It may hold anything on entry.
+ *   Mapping: launch 1, grid-wide over 2 048 rows x B, computes ~key of every row, stores it and counts the top bytes in LDS, flushed with integer global atomics
+ *     into the table the memset node zeroed; the bin total is the number of candidates.  Launch 2, one workgroup of 1 024 threads per (image, level), finds for an
+ *     oversubscribed level only the threshold and the number of rows equal to it to take (lowest index first) with three more 8-bit radix-select sweeps over the
+ *     workspace, collects the chosen words in one ordered sweep with a block prefix scan, sorts the at most 2 048 words in LDS (16 KB) and writes the slots.
+ *     Launch 3, one thread per slot: rank = slot number + by binary search the number of slots of every other level in front (on equal keys the lower level).
+ *
+ * lmv_rpn_gather -- the fixed-shape results of B images in one launch, from what lmv_obb_nms wrote per image: keep int64 [B, max_num] (ranks order, then -1) and
+ * count int64 [B].  boxes fp32 [B, Ktot, 5] and scores fp32 [B, Ktot] as above.  With c_b = clamp(count[b], 0, max_num):
+ *     proposals  fp32 [B, max_num, 5]: the kept boxes in rank order, then rows of zeros
+ *     out_scores fp32 [B, max_num]: their scores, -inf on padding
+ *     num        int32 [B]: c_b
+ *     ignore     uint8 [B, max_num]: 1 on padding, 0 on a proposal -- lmv_max_iou_assign's `ignore`: a padding row gets gt_inds = -1 and no sampler draws it
+ * A keep entry outside 0 .. Ktot - 1 in front of the count reads nothing and is padding.  Every output element is written exactly once.
+ *
+ * Limits: 1 <= nms_pre <= LMV_RPN_MAX_PRE, L <= LMV_RPN_LOSS_MAX_LEVELS (so Ktot <= 10 240 <= LMV_OBB_NMS_MAX; the configs' shape, 1024 x 1024 with strides 4 .. 64
+ * and A = 3: 2000 x 4 + 768 = 8 768), N <= LMV_OBB_MAX_BOXES, 1 <= A <= LMV_CODER_MAX_SETS, B in 1 .. LMV_ASSIGN_MAX_BATCH, 1 <= max_num <= LMV_OBB_NMS_MAX.
+ * Refused with LMV_ERR_SHAPE (a workspace that is too small or null: LMV_ERR_WORKSPACE) and a message that starts "rpn_select" / "rpn_gather", before any launch:
+ * sizes outside the limits, an unknown dtype, null pointers, buffers not aligned to their element (the workspace: 16 bytes), a map stride below 1 or a batch
+ * stride below the extent of one image, an anchor row stride below 4, a negative or NaN min_bbox_size, a wh_ratio_clip that is not a positive finite number, null
+ * means / stds or a NaN among them, Ktot (rpn_gather) outside 1 .. LMV_OBB_NMS_MAX.
+ * ------------------------------------------------------------------------------------------ */
+#define LMV_RPN_MAX_PRE 2048
+size_t lmv_rpn_select_workspace_bytes(const int32_t* sizes, int L, int A, int B, int nms_pre);
+int lmv_rpn_select(const lmv_rpn_loss_level* levels, int L, int A, int dtype, int B, const float* anchors, int anchor_stride, int nms_pre, float min_bbox_size,
+                   const float* means, const float* stds, float wh_ratio_clip, void* workspace, size_t workspace_bytes, int64_t* index, int32_t* groups, float* scores,
+                   float* boxes, int64_t* order, void* stream);
+int lmv_rpn_gather(const float* boxes, const float* scores, int Ktot, const int64_t* keep, const int64_t* count, int B, int max_num, float* proposals,
+                   float* out_scores, int32_t* num, uint8_t* ignore, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Whole-block schedules: ONE call enqueues every launch of a LeMeBlock (models/lemevit.py:500-660) on token-major tensors
  * x [B, H*W, C], c [B, M, C] -- `LeMeBlock.forward_with_x` ("S", :615-650), `forward_with_xc` ("D", :542-582), `forward_with_c`
  * ("C", :584-613; x is returned untouched by the caller, x_out / dx_out may be NULL).  Replaces the ~12 / ~30 per-op calls a Python

@@ -24,6 +24,7 @@ from .detection import RoIAlign, RoIExtractor, batched_nms, nms, nms_padded, nms
 from .detection import AssignResult, MaxIoUAssigner, bbox_overlaps, bbox_overlaps_torch, max_iou_assign_torch, reference_bbox_overlaps, reference_max_iou_assign  # noqa: F401
 from .detection import BatchSample, OBBRandomSampler, RandomSampler, SamplingResult, random_sample_torch, reference_random_sample, reference_sample_gather  # noqa: F401
 from .detection import bbox_head_loss, bbox_head_loss_torch, reference_bbox_head_loss, reference_rpn_head_loss, rpn_head_loss, rpn_head_loss_torch  # noqa: F401
+from .detection import AnchorGenerator, RPNProposalBuffers, RPNProposals, get_bboxes, reference_rpn_proposals, reference_rpn_select, rpn_proposals, rpn_proposals_torch  # noqa: F401
 from . import dist  # noqa: F401  (wrap_ddp, FlatGradSync, attach_flat_grad_sync)
 from .registry import create_model, is_model, list_models, load_checkpoint, register_model  # noqa: F401
 from .registry import lemevit_base, lemevit_small, lemevit_small_v2, lemevit_tiny, lemevit_tiny_v2, vit_tiny  # noqa: F401
@@ -40,4 +41,5 @@ __all__ = ["create_model", "register_model", "list_models", "is_model", "load_ch
            "bbox_overlaps", "MaxIoUAssigner", "AssignResult", "reference_bbox_overlaps", "reference_max_iou_assign", "bbox_overlaps_torch", "max_iou_assign_torch",
            "RandomSampler", "OBBRandomSampler", "BatchSample", "SamplingResult", "reference_random_sample",
            "reference_sample_gather", "random_sample_torch", "rpn_head_loss", "bbox_head_loss", "rpn_head_loss_torch", "bbox_head_loss_torch",
-           "reference_rpn_head_loss", "reference_bbox_head_loss"]
+           "reference_rpn_head_loss", "reference_bbox_head_loss", "AnchorGenerator", "RPNProposals", "RPNProposalBuffers", "rpn_proposals", "get_bboxes",
+           "rpn_proposals_torch", "reference_rpn_select", "reference_rpn_proposals"]

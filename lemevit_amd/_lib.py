@@ -38,6 +38,7 @@ ASSIGN_HORIZONTAL, ASSIGN_ROTATED, ASSIGN_GT_CHUNK, ASSIGN_MAX_GT, ASSIGN_MAX_BA
 CODER_MIDPOINT, CODER_OBB2OBB, CODER_MAX_SETS = 0, 1, 128          # LMV_CODER_*
 SAMPLE_MAX_NUM = 16384          # LMV_SAMPLE_MAX_NUM
 RPN_LOSS_MAX_LEVELS, RCNN_LOSS_STATS = 5, 7          # LMV_RPN_LOSS_MAX_LEVELS, LMV_RCNN_LOSS_STATS (LMV_RPN_LOSS_STATS(L) = 2 L + 3)
+RPN_MAX_PRE = 2048          # LMV_RPN_MAX_PRE
 
 
 class LinearProblem(C.Structure):
@@ -254,6 +255,9 @@ SIGNATURES = {
     "lmv_rcnn_loss_workspace_bytes": (_Z, [_I]),
     "lmv_rcnn_loss_fwd": (_I, [_P, _L, _P, _L, _I, _I, _I, _I, _P, _I, _P, _P, _P, _I, _I, _I, _P, _I, _P, _P, _F, _F, _F, _P, _Z, _P, _P]),
     "lmv_rcnn_loss_bwd": (_I, [_P, _L, _P, _L, _I, _I, _I, _I, _P, _I, _P, _P, _P, _I, _I, _I, _P, _I, _P, _P, _F, _F, _F, _P, _P, _P, _L, _P, _L, _P]),
+    "lmv_rpn_select_workspace_bytes": (_Z, [C.POINTER(C.c_int32), _I, _I, _I, _I]),
+    "lmv_rpn_select": (_I, [C.POINTER(RpnLossLevel), _I, _I, _I, _I, _P, _I, _I, _F, _P, _P, _F, _P, _Z, _P, _P, _P, _P, _P, _P]),
+    "lmv_rpn_gather": (_I, [_P, _P, _I, _P, _P, _I, _I, _P, _P, _P, _P, _P]),
     "lmv_block_arena_bytes": (_Z, [C.POINTER(BlockDesc)]),
     "lmv_block_bwd_scratch_bytes": (_Z, [C.POINTER(BlockDesc)]),
     "lmv_block_fwd": (_I, [C.POINTER(BlockDesc), _P, _P, _P, _P, _P, _Z, _I, _P]),

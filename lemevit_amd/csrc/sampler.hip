@@ -12,6 +12,7 @@
 //             packed per-class counts) writes inds, mask and the counts.  Every output element is written exactly once.
 #include "common.h"
 #include "philox.h"
+#include "select_frame.h"
 #include <math.h>
 
 namespace {
@@ -93,48 +94,6 @@ __device__ __forceinline__ void sm_load(const uint8_t* __restrict__ cls, const u
   }
 }
 
-// One wave: the bin d of a 256-bin histogram with  sum(h[0 .. d - 1]) < r <= sum(h[0 .. d])  (1 <= r <= the histogram's total), and r - sum(h[0 .. d - 1]).
-// Lane l owns bins 4 l .. 4 l + 3; exactly one lane finds the bin and writes both results.
-__device__ __forceinline__ void sm_pick(const uint32_t* h, uint32_t r, int lane, uint32_t* bin, uint32_t* rest) {
-  const uint32_t v[4] = {h[4 * lane], h[4 * lane + 1], h[4 * lane + 2], h[4 * lane + 3]};
-  const uint32_t s = (v[0] + v[1]) + (v[2] + v[3]);
-  uint32_t inc = s;
-#pragma unroll
-  for (int o = 1; o < LMV_WAVE; o <<= 1) {
-    const uint32_t t = __shfl_up(inc, o, LMV_WAVE);
-    if (lane >= o) inc += t;
-  }
-  uint32_t below = inc - s;
-  if (below < r && r <= inc) {
-    int j = 0;
-    while (j < 3 && r > below + v[j]) { below += v[j]; ++j; }
-    *bin = (uint32_t)(4 * lane + j);
-    *rest = r - below;
-  }
-}
-
-// the exclusive prefix of v over the workgroup's threads, in thread order, and the workgroup's total; wt: SM_WAVES words of LDS that nobody else uses until the
-// next barrier but one
-__device__ __forceinline__ uint32_t sm_scan(uint32_t v, uint32_t* wt, int lane, int wave, uint32_t* total) {
-  uint32_t inc = v;
-#pragma unroll
-  for (int o = 1; o < LMV_WAVE; o <<= 1) {
-    const uint32_t t = __shfl_up(inc, o, LMV_WAVE);
-    if (lane >= o) inc += t;
-  }
-  if (lane == LMV_WAVE - 1) wt[wave] = inc;
-  __syncthreads();
-  uint32_t before = 0u, all = 0u;
-#pragma unroll
-  for (int w = 0; w < SM_WAVES; ++w) {
-    const uint32_t x = wt[w];
-    all += x;
-    before += w < wave ? x : 0u;
-  }
-  *total = all;
-  return before + (inc - v);
-}
-
 __global__ __launch_bounds__(SM_T2) void sample_select_kernel(SmArgs a) {
   __shared__ uint32_t h[2][256];
   __shared__ uint32_t wt[2][2][SM_WAVES];          // [parity of the iteration][scan][wave]
@@ -173,7 +132,7 @@ __global__ __launch_bounds__(SM_T2) void sample_select_kernel(SmArgs a) {
     if (wave < 2 && (int)s_mode[wave] == SM_TAKE_SOME) {
       uint32_t bin = 0u, rest = 0u;
       const uint32_t r = s_rest[wave];
-      sm_pick(h[wave], r, lane, &bin, &rest);
+      lmv_select_pick(h[wave], r, lane, &bin, &rest);
       if (rest) { s_pref[wave] = bin << 24; s_rest[wave] = rest; }          // (the finding lane alone: rest >= 1 there, 0 elsewhere)
     }
     for (int shift = 16; shift >= 0; shift -= 8) {
@@ -196,7 +155,7 @@ __global__ __launch_bounds__(SM_T2) void sample_select_kernel(SmArgs a) {
       if (wave < 2 && (int)s_mode[wave] == SM_TAKE_SOME) {
         uint32_t bin = 0u, rest = 0u;
         const uint32_t r = s_rest[wave];
-        sm_pick(h[wave], r, lane, &bin, &rest);
+        lmv_select_pick(h[wave], r, lane, &bin, &rest);
         if (rest) { s_pref[wave] |= bin << shift; s_rest[wave] = rest; }
       }
     }
@@ -227,7 +186,7 @@ __global__ __launch_bounds__(SM_T2) void sample_select_kernel(SmArgs a) {
         if (c[j] == SM_POS && mode0 == SM_TAKE_SOME && p[j] == t0) mine += 1u;
         if (c[j] == SM_NEG && mode1 == SM_TAKE_SOME && p[j] == t1) mine += 1u << 16;
       }
-      const uint32_t ex = sm_scan(mine, wt[parity][0], lane, wave, &total);
+      const uint32_t ex = lmv_select_scan<SM_WAVES>(mine, wt[parity][0], lane, wave, &total);
       my0 += (int)(ex & 0xffffu); my1 += (int)(ex >> 16);
       eq0 += (int)(total & 0xffffu); eq1 += (int)(total >> 16);
     }
@@ -252,7 +211,7 @@ __global__ __launch_bounds__(SM_T2) void sample_select_kernel(SmArgs a) {
       }
       chosen |= take ? (1u << j) : 0u;
     }
-    const uint32_t ex = sm_scan(mine, wt[parity][1], lane, wave, &total);
+    const uint32_t ex = lmv_select_scan<SM_WAVES>(mine, wt[parity][1], lane, wave, &total);
     int at0 = out0 + (int)(ex & 0xffffu), at1 = n_pos + out1 + (int)(ex >> 16);
     out0 += (int)(total & 0xffffu); out1 += (int)(total >> 16);
     if (e0 < a.M) {

@@ -95,6 +95,21 @@ target inline with the coders' device rule.  Two launches forward, one backward,
 ``build_loss``, focal / IoU / L1 losses, ``pos_weight > 0``, ``reduction_override``, class weights, the Mask R-CNN config's ``DeltaXYWHBBoxCoder`` targets and mask
 loss, fp16.  ``reference_rpn_head_loss`` / ``reference_bbox_head_loss`` are the numpy float64 oracles (losses, counts, analytic gradients), ``rpn_head_loss_torch``
 / ``bbox_head_loss_torch`` the stock-PyTorch formulations.
+
+The RPN head's proposal stage (csrc/proposal.hip) -- upstream's ``OrientedRPNHead.get_bboxes``: what turns the head's maps into the proposals of the R-CNN head, so that
+RPN head -> proposals -> assigner -> sampler -> RoI extractor run without a host synchronisation (sources not in the reference tree: include/lemevit_hip.h restates the rules):
+
+    from lemevit_amd.detection import AnchorGenerator, rpn_proposals, get_bboxes, RPNProposalBuffers
+    levels, anchors = AnchorGenerator(strides=[4, 8, 16, 32, 64], ratios=[0.5, 1.0, 2.0], scales=[8]).grid_anchors(featmap_sizes, device)
+    out = rpn_proposals(cls_scores, bbox_preds, anchors, rpn_coder, nms_pre=2000, max_num=2000, nms_thr=0.8)          # RPNProposals(proposals [B, 2000, 5], scores, num, ignore)
+    gt_inds, _, _ = rcnn.assign_batched(out.proposals, gts, gt_counts, ignore=out.ignore)          # a padding row is -1 and is never sampled
+    dets = get_bboxes(cls_scores, bbox_preds, anchors, rpn_coder, cfg)          # upstream's per-image [n_b, 6] rows (cx, cy, w, h, theta, score); synchronises once
+
+Per level the ``nms_pre`` rows of greatest LOGIT (an exact radix select on the score maps read in place, ties by row index, no sort of a level), their fp32 sigmoid and
+midpoint decode (the bits of ``decode_map``), rotated NMS within levels, one gather: a memset and 4 + 2 B launches, nothing synchronised, two calls agree bit for bit, and
+with ``buffers`` nothing is allocated and the call can be captured.  Two deliberate differences: a NaN logit is no candidate (upstream's sort puts it first), and ties
+are decided by logit and index (upstream's sort is unstable).  Not provided: ``nms_across_levels=True``, the Mask R-CNN config's horizontal RPN proposals
+(``DeltaXYWHBBoxCoder``), fp16, gradients.  ``reference_rpn_select`` / ``reference_rpn_proposals`` are the numpy oracles, ``rpn_proposals_torch`` the stock formulation.
 """
 from __future__ import annotations
 
@@ -2116,4 +2131,257 @@ def reference_bbox_head_loss(cls_score, bbox_pred, rois, gts, s_gt_inds, s_label
         val, der = _smooth_l1_np(p[pos[:, None], cols] - target, beta)
         out["loss_bbox"] = loss_weight_bbox * val.sum() / n_valid
         dbbox[pos[:, None], cols] = go[1] * loss_weight_bbox * der / n_valid
+    return out
+
+
+# -------------------------------------------------------------------------------------------
+# The RPN head's proposal stage: AnchorGenerator, rpn_proposals, get_bboxes (csrc/proposal.hip)
+# -------------------------------------------------------------------------------------------
+RPN_MAX_PRE = 2048
+
+
+class RPNProposals(NamedTuple):
+    """What ``rpn_proposals`` returns for B images, all of fixed shape: ``proposals`` float32 [B, max_num, 5] (the kept boxes in rank order, then zero rows), ``scores``
+    float32 [B, max_num] (-inf on padding), ``num`` int32 [B], ``ignore`` uint8 [B, max_num] (1 on padding: ``assign_batched``'s ``ignore``)"""
+    proposals: Tensor
+    scores: Tensor
+    num: Tensor
+    ignore: Tensor
+
+
+class AnchorGenerator:
+    """Upstream mmdet 2.x's ``AnchorGenerator`` as the configs use it (``scales=[8], ratios=[0.5, 1.0, 2.0], strides=[4, 8, 16, 32, 64]``; its source is not part of
+    the reference tree, the rules restate upstream): per level ``h_ratios = sqrt(ratios)``, ``w_ratios = 1 / h_ratios``, the base anchors ``(cx - w/2, cy - h/2,
+    cx + w/2, cy + h/2)`` with ``w = base_size w_ratio scale``, ``h = base_size h_ratio scale`` (ratio-major, then scale) centred at ``center_offset * base_size``, and
+    the shifts ``arange * stride``.  Row ``(h W + w) A + a`` of a level is position (h, w), base anchor a -- the order of ``decode_map``, ``rpn_head_loss`` and
+    ``rpn_proposals``.  Host-side torch in float32, cached per (sizes, device): not a hot path.  Not provided: ``scale_major=False``, ``octave_base_scale``,
+    ``valid_flags``, per-axis strides."""
+
+    def __init__(self, strides, ratios, scales, base_sizes=None, center_offset: float = 0.0):
+        self.strides = [int(s) for s in strides]
+        self.base_sizes = list(self.strides) if base_sizes is None else [float(s) for s in base_sizes]
+        if not self.strides or len(self.base_sizes) != len(self.strides) or min(self.strides) < 1:
+            raise ValueError(f"AnchorGenerator: strides {list(strides)} and base_sizes {base_sizes}: one positive stride and one base size per level are needed")
+        self.ratios, self.scales, self.center_offset = [float(r) for r in ratios], [float(s) for s in scales], float(center_offset)
+        if not self.ratios or not self.scales or min(self.ratios) <= 0 or min(self.scales) <= 0:
+            raise ValueError(f"AnchorGenerator: ratios {list(ratios)} and scales {list(scales)} must be positive and not empty")
+        self._cache = {}
+
+    @property
+    def num_levels(self) -> int:
+        return len(self.strides)
+
+    @property
+    def num_base_anchors(self) -> int:
+        return len(self.ratios) * len(self.scales)
+
+    def base_anchors(self, level: int) -> Tensor:
+        """float32 [A, 4] of one level, on the CPU"""
+        size = torch.tensor(float(self.base_sizes[level]), dtype=torch.float32)
+        ratios, scales = torch.tensor(self.ratios, dtype=torch.float32), torch.tensor(self.scales, dtype=torch.float32)
+        h_ratios = torch.sqrt(ratios)
+        w_ratios = 1 / h_ratios
+        ws = (size * w_ratios[:, None] * scales[None, :]).reshape(-1)
+        hs = (size * h_ratios[:, None] * scales[None, :]).reshape(-1)
+        cx, cy = self.center_offset * size, self.center_offset * size
+        return torch.stack([cx - 0.5 * ws, cy - 0.5 * hs, cx + 0.5 * ws, cy + 0.5 * hs], -1)
+
+    def grid_anchors(self, featmap_sizes, device="cpu") -> Tuple[List[Tensor], Tensor]:
+        """``(per-level list of float32 [H_l W_l A, 4], their concatenation [N, 4])`` on ``device`` for ``featmap_sizes[l] = (H_l, W_l)``"""
+        sizes = tuple((int(h), int(w)) for h, w in featmap_sizes)
+        if len(sizes) != self.num_levels:
+            raise ValueError(f"AnchorGenerator.grid_anchors: {len(sizes)} feature-map sizes for {self.num_levels} levels")
+        key = (sizes, str(torch.device(device)))
+        if key not in self._cache:
+            levels = []
+            for l, (H, W) in enumerate(sizes):
+                xs = torch.arange(W, dtype=torch.float32) * self.strides[l]
+                ys = torch.arange(H, dtype=torch.float32) * self.strides[l]
+                xx, yy = xs.repeat(H), ys[:, None].repeat(1, W).reshape(-1)
+                shifts = torch.stack([xx, yy, xx, yy], -1)
+                levels.append((self.base_anchors(l)[None] + shifts[:, None]).reshape(-1, 4).to(device))
+            self._cache[key] = (levels, torch.cat(levels).contiguous())
+        levels, flat = self._cache[key]
+        return list(levels), flat
+
+    def __repr__(self) -> str:
+        return f"AnchorGenerator(strides={self.strides}, ratios={self.ratios}, scales={self.scales}, base_sizes={self.base_sizes}, center_offset={self.center_offset})"
+
+
+def _rpn_levels(fn: str, cls_scores, bbox_preds):
+    """(B, A, sizes) of the head's maps"""
+    if len(cls_scores) == 0 or len(cls_scores) != len(bbox_preds):
+        raise ValueError(f"{fn}: {len(cls_scores)} class maps and {len(bbox_preds)} regression maps: one of each per level")
+    if any(not isinstance(c, torch.Tensor) or c.dim() != 4 for c in cls_scores):
+        raise ValueError(f"{fn}: cls_scores: maps [B, A, H, W] expected")
+    return int(cls_scores[0].shape[0]), int(cls_scores[0].shape[1]), [(int(c.shape[2]), int(c.shape[3])) for c in cls_scores]
+
+
+class RPNProposalBuffers:
+    """Every buffer of one ``rpn_proposals`` call -- the candidates (index, groups, scores, boxes, order), the two workspaces, what the NMS keeps and the four
+    results -- allocated once, so that a call with ``buffers=`` (a captured one, or every iteration of a loop) allocates nothing.  ``sizes[l] = (H_l, W_l)``."""
+
+    def __init__(self, sizes, A: int, B: int, nms_pre: int, max_num: int, device):
+        self.sizes, self.A, self.B, self.nms_pre, self.max_num = [(int(h), int(w)) for h, w in sizes], int(A), int(B), int(nms_pre), int(max_num)
+        if not 1 <= self.max_num <= ops._lib.OBB_NMS_MAX:
+            raise ValueError(f"RPNProposalBuffers: max_num = {max_num} outside 1 .. {ops._lib.OBB_NMS_MAX}")
+        need = ops.rpn_select_workspace_bytes(self.sizes, self.A, self.B, self.nms_pre)          # (checks the sizes)
+        n = [h * w * self.A for h, w in self.sizes]
+        self.N, self.Ktot = sum(n), sum(min(self.nms_pre, x) for x in n)
+        dev = self.device = torch.device(device)
+
+        def new(shape, dtype):
+            return torch.empty(shape, device=dev, dtype=dtype)
+        B, K, M = self.B, self.Ktot, self.max_num
+        self.index, self.groups, self.cand_scores = new((B, K), torch.int64), new((B, K), torch.int32), new((B, K), torch.float32)
+        self.boxes, self.order = new((B, K, 5), torch.float32), new((B, K), torch.int64)
+        self.workspace, self.nms_workspace = new((need,), torch.uint8), new((max(ops.obb_nms_workspace_bytes(K), 8),), torch.uint8)
+        self.keep, self.count = new((B, M), torch.int64), new((B,), torch.int64)
+        self.proposals, self.scores, self.num, self.ignore = new((B, M, 5), torch.float32), new((B, M), torch.float32), new((B,), torch.int32), new((B, M), torch.uint8)
+
+    def matches(self, sizes, A: int, B: int, nms_pre: int, max_num: int, device) -> bool:
+        return (self.sizes, self.A, self.B, self.nms_pre, self.max_num, self.index.device) == (list(sizes), A, B, nms_pre, max_num, device)          # (the device with its index)
+
+
+def rpn_proposals(cls_scores: Sequence[Tensor], bbox_preds: Sequence[Tensor], anchors: Tensor, coder, nms_pre: int = 2000, max_num: int = 2000, nms_thr: float = 0.8,
+                  min_bbox_size: float = 0, buffers: Optional[RPNProposalBuffers] = None) -> RPNProposals:
+    """The proposal stage of the oriented RPN head for B images, nothing synchronised (upstream ``OrientedRPNHead.get_bboxes`` with ``nms_across_levels=False`` and
+    ``nms_post == max_num``): per level the ``nms_pre`` rows of greatest logit (ties: the smaller row index; a NaN logit is no candidate), their midpoint decode
+    against ``anchors`` float32 [N, 4] (``AnchorGenerator.grid_anchors``'s concatenation) and their fp32 sigmoid; per image rotated NMS at ``nms_thr`` within each
+    level, ranked by logit; the first ``max_num`` kept.  ``cls_scores[l]`` [B, A, H_l, W_l] / ``bbox_preds[l]`` [B, 6 A, H_l, W_l], float32 or bfloat16, are read in
+    place with any strides: no permute copy, no sort of a level.  With ``min_bbox_size > 0`` a box with a side below it is no candidate.  Returns
+    ``RPNProposals(proposals, scores, num, ignore)`` of fixed shape; ``ignore`` is ``MaxIoUAssigner.assign_batched``'s.  With ``buffers``
+    (``RPNProposalBuffers(sizes, A, B, nms_pre, max_num, device)``) the call allocates nothing and can be captured: a memset and 4 + 2 B launches on one stream."""
+    fn = "rpn_proposals"
+    if not isinstance(coder, MidpointOffsetCoder):
+        raise NotImplementedError(f"{fn}: the coder must be a MidpointOffsetCoder (the oriented RPN head's); {type(coder).__name__} is not wired up -- the Mask R-CNN "
+                                  "config's DeltaXYWHBBoxCoder and its horizontal RPN proposals are not provided")
+    B, A, sizes = _rpn_levels(fn, cls_scores, bbox_preds)
+    if not isinstance(anchors, torch.Tensor):
+        raise TypeError(f"{fn}: anchors: the concatenated float32 [N, 4] tensor expected (AnchorGenerator.grid_anchors(...)[1])")
+    dev = cls_scores[0].device
+    if buffers is None:
+        buffers = RPNProposalBuffers(sizes, A, B, nms_pre, max_num, dev)
+    elif not buffers.matches(sizes, A, B, int(nms_pre), int(max_num), dev):
+        raise ValueError(f"{fn}: the buffers were made for other sizes (levels, A, B, nms_pre, max_num or device differ)")
+    f = buffers
+    ops.rpn_select([c.detach() for c in cls_scores], [r.detach() for r in bbox_preds], anchors, coder.means, coder.stds, nms_pre, float(min_bbox_size), WH_RATIO_CLIP,
+                   f.index, f.groups, f.cand_scores, f.boxes, f.order, f.workspace)
+    for b in range(B):
+        ops.obb_nms(f.boxes[b], f.cand_scores[b], float(nms_thr), f.groups[b], None, f.max_num, f.order[b], f.nms_workspace, f.keep[b], f.count[b:b + 1])
+    return RPNProposals(*ops.rpn_gather(f.boxes, f.cand_scores, f.keep, f.count, f.proposals, f.scores, f.num, f.ignore))
+
+
+def get_bboxes(cls_scores: Sequence[Tensor], bbox_preds: Sequence[Tensor], anchors: Tensor, coder, cfg: Optional[dict] = None, **kwargs) -> List[Tensor]:
+    """Upstream's return value of ``OrientedRPNHead.get_bboxes``: per image float32 [n_b, 6] rows ``(cx, cy, w, h, theta, score)``.  ``cfg``: the configs'
+    ``train_cfg.rpn_proposal`` / ``test_cfg.rpn`` (``nms_pre``, ``nms_post``, ``max_num``, ``nms_thr``, ``min_bbox_size``; ``nms_across_levels=True`` is not
+    provided), overridden by keyword arguments.  One synchronisation, for the lengths."""
+    c = dict(nms_across_levels=False, nms_pre=2000, nms_post=2000, max_num=2000, nms_thr=0.8, min_bbox_size=0)
+    c.update(dict(cfg or {}), **kwargs)
+    if c["nms_across_levels"]:
+        raise NotImplementedError("get_bboxes: nms_across_levels=True is not provided (the configs set False)")
+    out = rpn_proposals(cls_scores, bbox_preds, anchors, coder, c["nms_pre"], min(int(c["max_num"]), int(c["nms_post"])), c["nms_thr"], c["min_bbox_size"])
+    return [torch.cat([out.proposals[b, :n], out.scores[b, :n, None]], 1) for b, n in enumerate(out.num.tolist())]
+
+
+def rpn_proposals_torch(cls_scores: Sequence[Tensor], bbox_preds: Sequence[Tensor], anchors, coder, nms_pre: int = 2000, max_num: int = 2000, nms_thr: float = 0.8,
+                        min_bbox_size: float = 0) -> List[Tensor]:
+    """The stock formulation, as upstream writes ``_get_bboxes_single``: per image and level the ``permute(1, 2, 0).reshape`` copies, the sigmoid, a full
+    ``sort(descending=True)`` when the level has more than ``nms_pre`` rows, index copies of deltas and anchors; then ``cat``, ``midpoint_decode_torch``, the
+    ``min_bbox_size`` filter, ``obb_nms_torch`` with the level ids and a slice.  Returns per image float32 [n_b, 6].  ``anchors``: the per-level list or [N, 4]."""
+    B, A, sizes = _rpn_levels("rpn_proposals_torch", cls_scores, bbox_preds)
+    if isinstance(anchors, torch.Tensor):
+        anchors = list(torch.split(anchors, [h * w * A for h, w in sizes]))
+    results = []
+    for b in range(B):
+        m_scores, m_deltas, m_anchors, m_ids = [], [], [], []
+        for l, (c, r) in enumerate(zip(cls_scores, bbox_preds)):
+            scores = c[b].permute(1, 2, 0).reshape(-1).float().sigmoid()
+            deltas = r[b].permute(1, 2, 0).reshape(-1, 6).float()
+            anc = anchors[l]
+            if nms_pre > 0 and scores.shape[0] > nms_pre:
+                ranked, rank_inds = scores.sort(descending=True)
+                topk = rank_inds[:nms_pre]
+                scores, deltas, anc = ranked[:nms_pre], deltas[topk], anc[topk]
+            m_scores.append(scores); m_deltas.append(deltas); m_anchors.append(anc)
+            m_ids.append(torch.full((scores.shape[0],), l, dtype=torch.int64, device=scores.device))
+        scores, ids = torch.cat(m_scores), torch.cat(m_ids)
+        proposals = midpoint_decode_torch(torch.cat(m_anchors), torch.cat(m_deltas), coder.means, coder.stds, WH_RATIO_CLIP)
+        if min_bbox_size > 0:
+            valid = torch.nonzero((proposals[:, 2] >= min_bbox_size) & (proposals[:, 3] >= min_bbox_size)).reshape(-1)
+            proposals, scores, ids = proposals[valid], scores[valid], ids[valid]
+        keep = obb_nms_torch(proposals, scores, nms_thr, ids)
+        results.append(torch.cat([proposals[keep], scores[keep, None]], 1)[:max_num])
+    return results
+
+
+# ---- the numpy oracles, from the rules of include/lemevit_hip.h ----
+def rpn_logit_words(logits, nms_pre: int) -> np.ndarray:
+    """uint64 [K]: the first ``min(nms_pre, n)`` of the ascending 64-bit words ``(~key << 32) | r`` over the rows r of one level of one image (``logits``: float32
+    [n]) that are not NaN; key = the order-preserving image of the fp32 logit, -0.0 as +0.0.  A literal sort."""
+    z = np.ascontiguousarray(np.asarray(logits, dtype=np.float32).reshape(-1))
+    bits = np.where(z == 0, np.float32(0), z).view(np.uint32).astype(np.uint64)
+    key = np.where(bits & 0x80000000, ~bits & 0xFFFFFFFF, bits | 0x80000000)
+    words = (((~key) & 0xFFFFFFFF) << np.uint64(32)) | np.arange(z.size, dtype=np.uint64)
+    return np.sort(words[~np.isnan(z)])[:min(int(nms_pre), z.size)]
+
+
+def _rpn_rows(t) -> np.ndarray:
+    """[B, C, H, W] -> float32 [B, H W, C]"""
+    a = t.detach().float().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t, dtype=np.float32)
+    return np.ascontiguousarray(a.transpose(0, 2, 3, 1).reshape(a.shape[0], a.shape[2] * a.shape[3], a.shape[1]))
+
+
+def reference_rpn_select(cls_scores, nms_pre: int = 2000):
+    """The oracle of ``ops.rpn_select``'s integers: ``(index int64 [B, Ktot], groups int32 [B, Ktot], order int64 [B, Ktot], logits float32 [B, Ktot])``; an empty
+    slot has index -1 and logit NaN.  ``order``: the slots by ascending (~key, level, slot), empty slots last in element order."""
+    rows = [_rpn_rows(c) for c in cls_scores]
+    B = rows[0].shape[0]
+    K = [min(int(nms_pre), r.shape[1] * r.shape[2]) for r in rows]
+    Ktot = sum(K)
+    index, groups = np.full((B, Ktot), -1, dtype=np.int64), np.zeros((B, Ktot), dtype=np.int32)
+    ukey, logits = np.full((B, Ktot), 0xFFFFFFFF, dtype=np.uint64), np.full((B, Ktot), np.nan, dtype=np.float32)
+    order = np.zeros((B, Ktot), dtype=np.int64)
+    for b in range(B):
+        k0 = 0
+        for l, r in enumerate(rows):
+            z = r[b].reshape(-1)
+            w = rpn_logit_words(z, nms_pre)
+            index[b, k0:k0 + len(w)] = (w & np.uint64(0xFFFFFFFF)).astype(np.int64)
+            ukey[b, k0:k0 + len(w)] = w >> np.uint64(32)
+            logits[b, k0:k0 + len(w)] = z[index[b, k0:k0 + len(w)]]
+            groups[b, k0:k0 + K[l]] = l
+            k0 += K[l]
+        order[b] = np.lexsort((np.arange(Ktot), groups[b], ukey[b]))
+    return index, groups, order, logits
+
+
+def reference_rpn_proposals(cls_scores, bbox_preds, anchors, means=(0.0,) * 6, stds=(1.0, 1.0, 1.0, 1.0, 0.5, 0.5), nms_pre: int = 2000, max_num: int = 2000,
+                            nms_thr: float = 0.8, min_bbox_size: float = 0):
+    """The numpy float64 oracle of ``rpn_proposals``: ``reference_rpn_select``, ``reference_midpoint_decode`` of the chosen rows, the float64 sigmoid, the
+    ``min_bbox_size`` rule, ``reference_obb_nms`` with the level ids on the ranks of ``order``, truncation.  Returns per image a dict: ``keep`` (the kept slots, as
+    elements 0 .. Ktot - 1, in rank order), ``boxes`` / ``scores`` (float64, all Ktot slots; an empty slot is zeros / -inf), ``index``, ``groups``, ``order``."""
+    index, groups, order, logits = reference_rpn_select(cls_scores, nms_pre)
+    regs = [_rpn_rows(r) for r in bbox_preds]
+    anc = _as_np(anchors, 4, "anchors")
+    B, Ktot = index.shape
+    A = _rpn_rows(cls_scores[0]).shape[2]
+    n = [r.shape[1] * A for r in regs]
+    off = np.concatenate([[0], np.cumsum(n)])
+    out = []
+    for b in range(B):
+        boxes, scores = np.zeros((Ktot, 5)), np.full(Ktot, -np.inf)
+        live = np.nonzero(index[b] >= 0)[0]
+        r, l = index[b, live], groups[b, live]
+        deltas = np.stack([regs[li][b].reshape(-1, 6)[ri] for li, ri in zip(l, r)]) if len(live) else np.zeros((0, 6))
+        boxes[live] = reference_midpoint_decode(anc[off[l] + r], deltas, means, stds) if len(live) else boxes[live]
+        with np.errstate(over="ignore"):
+            scores[live] = 1.0 / (1.0 + np.exp(-logits[b, live].astype(np.float64)))
+        if min_bbox_size > 0:
+            with np.errstate(invalid="ignore"):
+                scores[~((boxes[:, 2] >= min_bbox_size) & (boxes[:, 3] >= min_bbox_size))] = -np.inf
+        rank = np.empty(Ktot)
+        rank[order[b]] = -np.arange(Ktot, dtype=np.float64)          # the NMS ranks by `order`: a surrogate score that descends along it
+        keep = reference_obb_nms(boxes, np.where(scores > -np.inf, rank, -np.inf), nms_thr, groups[b], None, max_num)
+        out.append(dict(keep=keep, boxes=boxes, scores=scores, index=index[b], groups=groups[b], order=order[b]))
     return out

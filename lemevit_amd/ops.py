@@ -2199,6 +2199,133 @@ def rcnn_loss_bwd(cls_score: Tensor, bbox_pred: Tensor, rois: Tensor, gts: Tenso
 
 
 # -------------------------------------------------------------------------------------------
+# The RPN head's proposal stage (csrc/proposal.hip; lemevit_amd/detection.py has rpn_proposals / get_bboxes / AnchorGenerator)
+# -------------------------------------------------------------------------------------------
+def _rpn_buf(fn: str, name: str, t: Optional[Tensor], shape, dtype, dev) -> Tensor:
+    if t is None:
+        return torch.empty(shape, device=dev, dtype=dtype)
+    if t.dtype != dtype or tuple(t.shape) != tuple(shape) or t.device != dev or not t.is_contiguous():
+        raise TypeError(f"{fn}: {name} must be a contiguous {dtype} tensor {tuple(shape)} on the maps' device")
+    return t
+
+
+def _rpn_sizes(fn: str, sizes: Sequence[Tuple[int, int]], A: int, B: int, nms_pre: int) -> Tuple[int, int]:
+    """(N, Ktot) of levels of ``sizes[l] = (H_l, W_l)`` positions with A anchors each, after the limits of lmv_rpn_select"""
+    L, A, B, nms_pre = len(sizes), int(A), int(B), int(nms_pre)
+    if not 1 <= L <= _lib.RPN_LOSS_MAX_LEVELS:
+        raise ValueError(f"{fn}: {L} levels: 1 .. {_lib.RPN_LOSS_MAX_LEVELS} are supported")
+    if not 1 <= A <= _lib.CODER_MAX_SETS:
+        raise ValueError(f"{fn}: A = {A} anchors per position outside 1 .. {_lib.CODER_MAX_SETS}")
+    if not 1 <= B <= _lib.ASSIGN_MAX_BATCH:
+        raise ValueError(f"{fn}: B = {B} images outside 1 .. {_lib.ASSIGN_MAX_BATCH}")
+    if not 1 <= nms_pre <= _lib.RPN_MAX_PRE:
+        raise ValueError(f"{fn}: nms_pre = {nms_pre} outside 1 .. {_lib.RPN_MAX_PRE}")
+    if any(int(h) < 1 or int(w) < 1 for h, w in sizes):
+        raise ValueError(f"{fn}: sizes {list(sizes)}: every level needs at least one position")
+    n = [int(h) * int(w) * A for h, w in sizes]
+    N, Ktot = sum(n), sum(min(nms_pre, x) for x in n)
+    if N > _lib.OBB_MAX_BOXES:
+        raise ValueError(f"{fn}: N = {N} anchors per image, at most {_lib.OBB_MAX_BOXES}")
+    if Ktot > _lib.OBB_NMS_MAX:
+        raise ValueError(f"{fn}: Ktot = {Ktot} slots per image, at most {_lib.OBB_NMS_MAX}")
+    return N, Ktot
+
+
+def rpn_select_workspace_bytes(sizes: Sequence[Tuple[int, int]], A: int, B: int, nms_pre: int) -> int:
+    """lmv_rpn_select_workspace_bytes: B (5120 + 4 sum_l ceil16(H_l W_l A) + 4 Ktot) bytes -- the histograms, the key of every row and the key of every slot of
+    ``rpn_select``; ``sizes[l] = (H_l, W_l)``"""
+    _rpn_sizes("rpn_select_workspace_bytes", sizes, A, B, nms_pre)
+    flat = (C.c_int32 * (2 * len(sizes)))(*[int(x) for hw in sizes for x in hw])
+    return int(lib.lmv_rpn_select_workspace_bytes(flat, len(sizes), int(A), int(B), int(nms_pre)))
+
+
+def rpn_select(cls_scores: Sequence[Tensor], bbox_preds: Sequence[Tensor], anchors: Tensor, means, stds, nms_pre: int = 2000, min_bbox_size: float = 0.0,
+               wh_ratio_clip: float = 16 / 1000, index: Optional[Tensor] = None, groups: Optional[Tensor] = None, scores: Optional[Tensor] = None,
+               boxes: Optional[Tensor] = None, order: Optional[Tensor] = None, workspace: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """lmv_rpn_select (three launches and a memset, no host round trip): the top ``nms_pre`` candidates per level of an oriented RPN head's output for B images at
+    once.  ``cls_scores[l]`` [B, A, H_l, W_l] and ``bbox_preds[l]`` [B, 6 A, H_l, W_l], float32 or bfloat16, are read in place with any strides; ``anchors`` float32
+    [N, 4], N = sum_l H_l W_l A, row (h W_l + w) A + a of level l at off_l + that.  Level l fills K_l = min(nms_pre, n_l) slots with its rows by descending LOGIT,
+    ties by ascending row index; a NaN logit is no candidate; slots past the candidates are empty.  Returns ``(index int64 [B, Ktot], groups int32 [B, Ktot],
+    scores float32 [B, Ktot], boxes float32 [B, Ktot, 5], order int64 [B, Ktot])``: the row within the level (-1: empty), the level id, the fp32 sigmoid (-inf: empty,
+    or a side below ``min_bbox_size`` > 0), the midpoint decode (the bits of ``box_decode_map``) and the image's slots by descending logit (``obb_nms``'s ``order``).
+    Every output and the workspace (uint8, ``rpn_select_workspace_bytes(sizes, A, B, nms_pre)``) may be supplied so that a captured call allocates nothing.
+    include/lemevit_hip.h has the rules."""
+    fn = "rpn_select"
+    code, k, D, names, cm, cs = coder_norm(fn, "midpoint", means, stds)
+    clip = _coder_clip(fn, wh_ratio_clip)
+    L = len(cls_scores)
+    if not 1 <= L <= _lib.RPN_LOSS_MAX_LEVELS or len(bbox_preds) != L:
+        raise ValueError(f"{fn}: {L} class maps and {len(bbox_preds)} regression maps: 1 .. {_lib.RPN_LOSS_MAX_LEVELS} levels, one of each per level")
+    c0 = cls_scores[0]
+    if c0.dim() != 4:
+        raise ValueError(f"{fn}: cls_scores[0]: [B, A, H, W] expected, got {tuple(c0.shape)}")
+    B, A, dev, dt = int(c0.shape[0]), int(c0.shape[1]), c0.device, c0.dtype
+    for l in range(L):
+        c, r = cls_scores[l], bbox_preds[l]
+        if c.dim() != 4 or r.dim() != 4 or c.shape[0] != B or c.shape[1] != A or tuple(r.shape) != (B, A * D, c.shape[2], c.shape[3]):
+            raise ValueError(f"{fn}: level {l}: a class map [{B}, {A}, H, W] and a regression map [{B}, {A * D}, H, W] expected, got {tuple(c.shape)} and {tuple(r.shape)}")
+    sizes = [(int(c.shape[2]), int(c.shape[3])) for c in cls_scores]
+    N, Ktot = _rpn_sizes(fn, sizes, A, B, nms_pre)
+    min_bbox_size = float(min_bbox_size)
+    if not min_bbox_size >= 0.0:
+        raise ValueError(f"{fn}: min_bbox_size = {min_bbox_size!r} is negative or NaN (0: no rule)")
+    code_dt = dtype_code(c0)
+    levels = (_lib.RpnLossLevel * L)()
+    for l in range(L):
+        for name, t in (("cls", cls_scores[l]), ("reg", bbox_preds[l])):
+            if t.dtype != dt or t.device != dev or not t.is_cuda:
+                raise TypeError(f"{fn}: level {l}: every map must have the dtype and the (GPU) device of cls_scores[0]; there is no CPU fallback")
+            setattr(levels[l], name, t.data_ptr())
+            setattr(levels[l], name + "_stride", (C.c_int64 * 4)(*[max(int(s), 1) if t.shape[i] == 1 else int(s) for i, s in enumerate(t.stride())]))
+        levels[l].H, levels[l].W = sizes[l]
+    if anchors.dim() != 2 or tuple(anchors.shape) != (N, 4) or anchors.dtype != torch.float32 or anchors.device != dev or not anchors.is_contiguous():
+        raise ValueError(f"{fn}: anchors: contiguous float32 [{N}, 4] on the maps' device expected, got {anchors.dtype} {tuple(anchors.shape)}")
+    index = _rpn_buf(fn, "index", index, (B, Ktot), torch.int64, dev)
+    groups = _rpn_buf(fn, "groups", groups, (B, Ktot), torch.int32, dev)
+    scores = _rpn_buf(fn, "scores", scores, (B, Ktot), torch.float32, dev)
+    boxes = _rpn_buf(fn, "boxes", boxes, (B, Ktot, 5), torch.float32, dev)
+    order = _rpn_buf(fn, "order", order, (B, Ktot), torch.int64, dev)
+    need = rpn_select_workspace_bytes(sizes, A, B, nms_pre)
+    workspace = _loss_workspace(fn, workspace, need, dev, "rpn_select_workspace_bytes")
+    check(lib.lmv_rpn_select(levels, L, A, code_dt, B, anchors.data_ptr(), 4, int(nms_pre), min_bbox_size, cm, cs, clip, workspace.data_ptr(), workspace.numel(),
+                             index.data_ptr(), groups.data_ptr(), scores.data_ptr(), boxes.data_ptr(), order.data_ptr(), _stream()), "lmv_rpn_select")
+    return index, groups, scores, boxes, order
+
+
+def rpn_gather(boxes: Tensor, scores: Tensor, keep: Tensor, count: Tensor, proposals: Optional[Tensor] = None, out_scores: Optional[Tensor] = None,
+               num: Optional[Tensor] = None, ignore: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """lmv_rpn_gather (one launch): the fixed-shape proposals of B images from what ``obb_nms`` kept per image.  ``boxes`` float32 [B, Ktot, 5] and ``scores`` float32
+    [B, Ktot] as ``rpn_select`` returns them; ``keep`` int64 [B, max_num] (an image's kept slots in rank order, then -1) and ``count`` int64 [B].  Returns
+    ``(proposals float32 [B, max_num, 5], scores float32 [B, max_num], num int32 [B], ignore uint8 [B, max_num])``: the kept boxes in rank order, then zero rows with
+    score -inf and ``ignore`` 1 -- exactly ``max_iou_assign``'s ``ignore``.  Every output may be supplied so that a captured call allocates nothing."""
+    fn = "rpn_gather"
+    if boxes.dim() != 3 or boxes.shape[2] != 5 or boxes.dtype != torch.float32:
+        raise ValueError(f"{fn}: boxes: float32 [B, Ktot, 5] expected, got {boxes.dtype} {tuple(boxes.shape)}")
+    B, Ktot, dev = int(boxes.shape[0]), int(boxes.shape[1]), boxes.device
+    if not 1 <= B <= _lib.ASSIGN_MAX_BATCH:
+        raise ValueError(f"{fn}: B = {B} images outside 1 .. {_lib.ASSIGN_MAX_BATCH}")
+    if not 1 <= Ktot <= _lib.OBB_NMS_MAX:
+        raise ValueError(f"{fn}: Ktot = {Ktot} slots per image outside 1 .. {_lib.OBB_NMS_MAX}")
+    if keep.dim() != 2 or keep.shape[0] != B or keep.dtype != torch.int64:
+        raise ValueError(f"{fn}: keep: int64 [{B}, max_num] expected, got {keep.dtype} {tuple(keep.shape)}")
+    max_num = int(keep.shape[1])
+    if not 1 <= max_num <= _lib.OBB_NMS_MAX:
+        raise ValueError(f"{fn}: max_num = {max_num} outside 1 .. {_lib.OBB_NMS_MAX}")
+    if not boxes.is_cuda:
+        raise RuntimeError("lemevit_amd: tensors must be on the GPU (no CPU fallback exists)")
+    for name, t, shape, dtype in (("boxes", boxes, (B, Ktot, 5), torch.float32), ("scores", scores, (B, Ktot), torch.float32), ("keep", keep, (B, max_num), torch.int64),
+                                  ("count", count, (B,), torch.int64)):
+        _rpn_buf(fn, name, t, shape, dtype, dev)
+    proposals = _rpn_buf(fn, "proposals", proposals, (B, max_num, 5), torch.float32, dev)
+    out_scores = _rpn_buf(fn, "out_scores", out_scores, (B, max_num), torch.float32, dev)
+    num = _rpn_buf(fn, "num", num, (B,), torch.int32, dev)
+    ignore = _rpn_buf(fn, "ignore", ignore, (B, max_num), torch.uint8, dev)
+    check(lib.lmv_rpn_gather(boxes.data_ptr(), scores.data_ptr(), Ktot, keep.data_ptr(), count.data_ptr(), B, max_num, proposals.data_ptr(), out_scores.data_ptr(),
+                             num.data_ptr(), ignore.data_ptr(), _stream()), "lmv_rpn_gather")
+    return proposals, out_scores, num, ignore
+
+
+# -------------------------------------------------------------------------------------------
 # A run of "S" blocks as one persistent launch (csrc/sstage.hip; inference, bf16)
 # -------------------------------------------------------------------------------------------
 def sstage_supported(C_: int, heads: int, hidden: int, H: int, W: int, M: int, dtype: torch.dtype) -> bool:
